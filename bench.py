@@ -73,6 +73,8 @@ def parse():
                          "ncclAllGather of the records -- what INTEGRATION.md section 3 recommends to a C++ host; --gpus N = N device entries")
     ap.add_argument("--steady-seconds", type=float, default=1.5, help="length of the steady-state loop behind the timed region")
     ap.add_argument("--secondary-scans", type=int, default=50, help="scans in each secondary (e2e / GICP / pipeline) loop")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy (rank 0; float32/float64)")
     a = ap.parse_args()
     batch = WORKLOADS[a.workload][2] == "batch"
     # (batch50k: the workers' buffers settle over the first few calls -- a call with reallocations takes 18-32 ms instead of 12.5 --
@@ -82,7 +84,24 @@ def parse():
         a.steps = 10 if batch else 50
     if a.warmup is None:
         a.warmup = 4 if batch else 10
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     return a
+
+
+DUMP_FIELDS = ("T", "converged", "iterations", "state", "n_corr", "mse", "gicp_solver")
+
+
+def dump_outputs(out_dir: str, results, with_fitness: bool) -> None:
+    """--dump-outputs: this rank's result dicts of the last timed step (one per scan pair, in order) as DIR/<field>.npy,
+    every field stacked over the pairs -- T float32 (n, 4, 4), the integer and boolean fields as float64 (exact).  Only what
+    the path computed: fitness only where the path requests it (the batch workloads; elsewhere the library leaves it NaN),
+    and not the timers (t_total_ms, t_device_ms), which are measurements.  A few hundred bytes per pair: far below 64 MB."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for f in DUMP_FIELDS + (("fitness",) if with_fitness else ()):
+        v = np.stack([np.asarray(r[f]) for r in results])
+        np.save(os.path.join(out_dir, f + ".npy"), v.astype(np.float32 if f == "T" else np.float64))
 
 
 def _free_port() -> int:
@@ -313,6 +332,8 @@ def run_multi_entry(a):
         res, recs = step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, res, with_fitness=True)
     iters_all = a.steps * sum(r["iterations"] for r in res)
     assert np.array_equal(recs[:, 0], np.arange(n_total))
     out = {"metric": "icp_iterations_per_sec", "value": iters_all / elapsed, "unit": "iterations/s", "n_gpus": n_dev, "steps": a.steps,
@@ -431,6 +452,8 @@ def main():
         gather(last)
     barrier()
     elapsed = time.perf_counter() - t0
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, last if batch else [last], with_fitness=batch)   # the pair step: align() without fitness
     # (the collector stays off through the secondary measurements below: they are timed loops too)
     prof = ctx.profile()
     # Right behind the timed region, on rank 0: a DENSE pass for the roofline -- the same alignments with EVERY sweep's kernel

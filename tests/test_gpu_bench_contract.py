@@ -123,3 +123,34 @@ def test_brute_force_roofline_is_a_fraction():
     assert 0.0 < b["frac"] < 1.0 and b["peak"] == 2500.0 and abs(b["frac"] - b["achieved"] / b["peak"]) < 1e-12
     assert b["useful_flops_equiv"]["tflops"] > 0 and "lane_slots_per_candidate" in d["roofline"].get("issue", {"lane_slots_per_candidate": 0})
     assert d["secondary_loop_scans"] == 4 and "STATIC" in d["roofline"]["traffic_source"]
+
+
+def _bench_dump(out_dir):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--workload", "5kx5k", "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(out_dir)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    return d
+
+
+def test_bench_dump_outputs_writes_the_last_step_and_repeats(tmp_path):
+    """--dump-outputs DIR: the result of the last timed step as DIR/<field>.npy (float32 / float64, well under 64 MB),
+    every value finite (only what the path computed: the pair step requests no fitness), and the same on a second run with
+    the same arguments (seeded inputs)."""
+    import numpy as np
+    _bench_dump(tmp_path / "a")
+    _bench_dump(tmp_path / "b")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"T.npy", "iterations.npy", "n_corr.npy", "mse.npy"} <= set(names) and "fitness.npy" not in names
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.isfinite(x).all(), n
+        assert x.shape == y.shape and np.array_equal(x, y), n
+    T, it, nc = (np.load(tmp_path / "a" / n) for n in ("T.npy", "iterations.npy", "n_corr.npy"))
+    assert T.shape == (1, 4, 4) and T.dtype == np.float32 and it.tolist() == [10.0]   # --iters 10, forced
+    assert 0 < nc[0] <= 5000
+    assert not np.array_equal(T[0], np.eye(4, dtype=np.float32))
