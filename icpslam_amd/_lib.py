@@ -15,10 +15,10 @@ if os.environ.get("ICPGPU_LIB_PATH"):   # A/B builds of an experiment (scripts/)
     LIB_PATH = os.environ["ICPGPU_LIB_PATH"]
 
 OK, ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_NO_INPUT, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
-P2P_SVD, GICP = 0, 1
+P2P_SVD, GICP, P2PLANE = 0, 1, 2
 GICP_INNER_EXACT, GICP_INNER_QUADRATIC = 0, 1
 GICP_SOLVER_NONE, GICP_SOLVER_HOST, GICP_SOLVER_DEVICE, GICP_SOLVER_QUADRATIC = 0, 1, 2, 3
-HEADER_VERSION = 1001          # the icpgpu.h these mirrors were written against (ICPGPU_HEADER_VERSION)
+HEADER_VERSION = 1002          # the icpgpu.h these mirrors were written against (ICPGPU_HEADER_VERSION)
 NN_AUTO, NN_BRUTE, NN_GRID = 0, 1, 2
 STATE_NAMES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE",
                5: "NO_CORRESPONDENCES"}
@@ -78,6 +78,7 @@ EXPORTS = [
     "icpgpu_posegraph_get_keyframe", "icpgpu_posegraph_get_edge", "icpgpu_posegraph_write_g2o",
     "icpgpu_map_set_search", "icpgpu_map_reset", "icpgpu_map_add_points", "icpgpu_map_add_source", "icpgpu_map_size", "icpgpu_map_get_points",
     "icpgpu_map_nn_target", "icpgpu_count_candidates", "icpgpu_count_candidates_read",
+    "icpgpu_set_target_normals", "icpgpu_normals", "icpgpu_reduce_point_to_plane", "icpgpu_solve_point_to_plane",
 ]
 
 _lib = None
@@ -141,6 +142,10 @@ def load():
     L.icpgpu_gicp_covariances.argtypes = [vp, C.c_int, dp]
     L.icpgpu_gicp_quadratic_eval.argtypes = [dp, fp, dp, dp, dp]
     L.icpgpu_gicp_quadratic_sums.argtypes = [vp, fp, dp]
+    L.icpgpu_set_target_normals.argtypes = [vp, fp, C.c_size_t]
+    L.icpgpu_normals.argtypes = [vp, C.c_int, fp]
+    L.icpgpu_reduce_point_to_plane.argtypes = [vp, fp, C.c_double, dp]
+    L.icpgpu_solve_point_to_plane.argtypes = [dp, dp]
     L.icpgpu_voxel_grid.argtypes = [vp, fp, C.c_size_t, C.c_float, fp, C.POINTER(C.c_size_t)]
     L.icpgpu_voxel_grid_fetch.argtypes = [vp, fp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.icpgpu_voxel_grid_view.argtypes = [vp, fp, C.c_size_t, C.c_float, C.POINTER(fp), C.POINTER(C.c_size_t)]

@@ -236,6 +236,13 @@ struct icpgpu_ctx {
   int spec_cooldown = 0;
   DeviceBuf cov_src, cov_tgt, maha;
   uint64_t cov_src_version = 0, cov_tgt_version = 0;
+  // point-to-plane mode (icpgpu_p2plane.cpp): the clouds' estimated normals (float4, cached per cloud version; 0 = none), the raw
+  // covariances they come from (scratch), the grid of their 20-NN search, the caller's target normals (icpgpu_set_target_normals:
+  // in force until the target changes hands) and the reduction's per-workgroup partials
+  DeviceBuf nrm_src, nrm_tgt, nrm_raw, nrm_user, p2plane_partials;
+  uint64_t nrm_src_version = 0, nrm_tgt_version = 0;
+  GridIndex nrm_grid;
+  bool nrm_supplied = false;
   // Per-iteration result mailbox in pinned, mapped host memory: 17 sums + 17 sequence flags.  The final reduction
   // stores straight into it and the host polls the flags -- no copy engine and no stream synchronisation (whose wake-up
   // costs 20-70 us depending on how the process set up the runtime) on the iteration path.
@@ -538,12 +545,18 @@ int align_p2p(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitne
 // icpgpu_voxel.cpp
 int voxel_filter_device(icpgpu_ctx* c, const float4* d_in, int n, float leaf, DeviceBuf& out, int* n_out, bool* passthrough,
                         int* bbox_enc_out = nullptr, bool publish = false, bool* published = nullptr, unsigned long long* fp_sum = nullptr);
-// icpgpu_gicp.cpp
-int ensure_covariances(icpgpu_ctx* c, const Cloud& cloud, uint64_t version, GridIndex& G, DeviceBuf& cov, uint64_t& cov_version, bool allow_unchecked = false);
+// icpgpu_gicp.cpp (normals: the point-to-plane mode's normals of the cloud instead of its covariances -- cov is then scratch)
+int ensure_covariances(icpgpu_ctx* c, const Cloud& cloud, uint64_t version, GridIndex& G, DeviceBuf& cov, uint64_t& cov_version, bool allow_unchecked = false,
+                       float4* normals = nullptr);
 int covariance_grid_check(icpgpu_ctx* c);
 int align_gicp(icpgpu_ctx* c, const float* guess_in, float* out_xyzw, int want_fitness, icpgpu_result* res);
 int gicp_run_begin(icpgpu_ctx* c, GicpRun& r, int want_fitness, icpgpu_result* res, bool combine = false);
 int gicp_run_step(icpgpu_ctx* c, GicpRun& r);  // < 0 error, 0 nothing yet, 1 moved on (r.phase == GicpRun::Done: finished)
 void gicp_run_solver_launched(icpgpu_ctx* c, GicpRun& r, hipStream_t solve_stream);  // WantSolve -> Solve (the scheduler launched r.item)
+// icpgpu_p2plane.cpp
+int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitness, icpgpu_result* res);
+// x = (A^T A)^-1 A^T r from the 29 sums (partial-pivot LU, float64) -> Tk = constructTransformationMatrix(x); false (Tk = identity)
+// when a pivot is zero or x is not finite
+bool solve_point_to_plane(const double sums[kP2planeTerms], Mat4d& Tk);
 
 }  // namespace icpgpu_impl

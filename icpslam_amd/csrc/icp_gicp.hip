@@ -793,6 +793,37 @@ __global__ __launch_bounds__(256) void gicp_cov_finish_kernel(int n, double* __r
   for (int k = 0; k < 6; ++k) c[k] = C[k];
 }
 
+// The point-to-plane mode's surface normals (icp_p2plane.hip): the same raw covariance and the same
+// svd3_left_vectors as gicp_cov_finish_kernel, but instead of the regularised covariance the third column of U -- the direction
+// computeCovariances scales by epsilon -- rounded to float and turned towards the viewpoint (0, 0, 0) as PCL's
+// flipNormalTowardsViewpoint does: cos = ((vx nx + vy ny) + vz nz) in float with v = 0 - p, flipped when cos < 0.  Marker points
+// (non-finite, or a cloud of fewer than 20 finite points) get (NaN, NaN, NaN, 0).  cov6 is left holding the raw covariances.
+__global__ __launch_bounds__(256) void gicp_normal_finish_kernel(const float4* __restrict__ cloud, int n, const double* __restrict__ cov6,
+                                                                 float4* __restrict__ normals, int* __restrict__ zero2) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (zero2 && i == 0) zero2[0] = zero2[1] = 0;
+  if (i >= n) return;
+  const double* c = cov6 + (size_t)i * 6;
+  const double a0 = c[0], a1 = c[1], a2 = c[2], a3 = c[3], a4 = c[4], a5 = c[5];
+  float4 out = make_float4(__int_as_float(0x7FC00000), __int_as_float(0x7FC00000), __int_as_float(0x7FC00000), 0.0f);
+  if (a0 == a0) {  // not the marker
+    const double A[9] = {a0, a1, a2, a1, a3, a4, a2, a4, a5};
+    double U[9];
+    svd3_left_vectors(A, U);
+    float nx = (float)U[2], ny = (float)U[5], nz = (float)U[8];
+    const float4 p = cloud[i];
+    const float vx = __fsub_rn(0.0f, p.x), vy = __fsub_rn(0.0f, p.y), vz = __fsub_rn(0.0f, p.z);
+    const float cos_theta = __fadd_rn(__fadd_rn(__fmul_rn(vx, nx), __fmul_rn(vy, ny)), __fmul_rn(vz, nz));
+    if (cos_theta < 0.0f) {
+      nx = -nx;
+      ny = -ny;
+      nz = -nz;
+    }
+    out = make_float4(nx, ny, nz, 0.0f);
+  }
+  normals[i] = out;
+}
+
 // ---- Mahalanobis matrices --------------------------------------------------------------------------------------
 // M = (C_t + R C_s R^T)^-1 of one correspondence, upper triangle (a, b: the two covariances' upper triangles)
 __device__ __forceinline__ void gicp_maha_of(const double* __restrict__ a, const double* __restrict__ b, const Rot3d& R, double* __restrict__ M) {
@@ -1750,7 +1781,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // over (clouds up to kGicpCovFarMost points; in larger ones gicp_cov_kernel finishes the list); without it gicp_cov_kernel does
 // every point, as until round 5.
 hipError_t launch_gicp_covariances(const float4* cloud, int n, const float4* sorted, const int* cell_start,
-                                   const GridDesc& g, double* cov6, hipStream_t stream, int* list, bool list_counters_zero) {
+                                   const GridDesc& g, double* cov6, hipStream_t stream, int* list, bool list_counters_zero,
+                                   float4* normals) {
   if (n <= 0) return hipSuccess;
   // development flavour, ICPGPU_COV_SELECT=0: the streaming kernel for every point
   static const bool select = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_COV_SELECT"); return !e || atoi(e) != 0; }();
@@ -1796,13 +1828,18 @@ hipError_t launch_gicp_covariances(const float4* cloud, int n, const float4* sor
   } else {
     hipLaunchKernelGGL(gicp_cov_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, cloud, n, sorted, cell_start, g, cov6, nullptr, nullptr);
   }
-  hipLaunchKernelGGL(gicp_cov_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, cov6, (list && select) ? list : nullptr);
+  if (normals)  // (the point-to-plane mode: normals instead of regularised covariances; cov6 keeps the raw ones)
+    hipLaunchKernelGGL(gicp_normal_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, cloud, n, cov6, normals,
+                       (list && select) ? list : nullptr);
+  else
+    hipLaunchKernelGGL(gicp_cov_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, cov6, (list && select) ? list : nullptr);
   return hipGetLastError();
 }
 
 // The covariances of a cloud WITHOUT a grid (the k-NN grid refuses a cloud whose densest cell of the largest table holds thousands of
 // points): every finite point through the far-field kernel's whole-cloud passes.  n <= kGicpCovFarMost; list as above.
-hipError_t launch_gicp_covariances_brute(const float4* cloud, int n, double* cov6, hipStream_t stream, int* list, bool list_counters_zero) {
+hipError_t launch_gicp_covariances_brute(const float4* cloud, int n, double* cov6, hipStream_t stream, int* list, bool list_counters_zero,
+                                         float4* normals) {
   if (n <= 0) return hipSuccess;
   if (n > kGicpCovFarMost || !list) return hipErrorInvalidValue;
   if (!list_counters_zero) {
@@ -1812,7 +1849,10 @@ hipError_t launch_gicp_covariances_brute(const float4* cloud, int n, double* cov
   int* far_list = list + 2 + n;
   hipLaunchKernelGGL(gicp_cov_all_far_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, cloud, n, cov6, far_list, list + 1);
   hipLaunchKernelGGL(gicp_cov_far_kernel, dim3(std::min(n, 1024)), dim3(1024), 0, stream, cloud, n, cov6, 0.05f, far_list, list + 1);
-  hipLaunchKernelGGL(gicp_cov_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, cov6, list);
+  if (normals)
+    hipLaunchKernelGGL(gicp_normal_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, cloud, n, cov6, normals, list);
+  else
+    hipLaunchKernelGGL(gicp_cov_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, cov6, list);
   return hipGetLastError();
 }
 

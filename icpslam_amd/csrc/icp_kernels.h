@@ -239,10 +239,14 @@ struct Rot3d {
 };
 static constexpr int kGicpCovFarMost = 1 << 16;  // clouds up to this size: the far-field kernel (a workgroup over the whole cloud per point)
 // the covariances of a cloud that has no grid (n <= kGicpCovFarMost): every point through the far-field kernel; list as below
-hipError_t launch_gicp_covariances_brute(const float4* cloud, int n, double* cov6, hipStream_t stream, int* list, bool list_counters_zero);
+hipError_t launch_gicp_covariances_brute(const float4* cloud, int n, double* cov6, hipStream_t stream, int* list, bool list_counters_zero,
+                                         float4* normals = nullptr);
 // cov6[i] = upper triangle (xx, xy, xz, yy, yz, zz) of the regularised covariance of point i's 20 nearest neighbours
+// normals (optional, n float4): the point-to-plane mode's surface normals instead (gicp_normal_finish_kernel): cov6 is then left
+// holding the RAW covariances, scratch for the caller
 hipError_t launch_gicp_covariances(const float4* cloud, int n, const float4* sorted, const int* cell_start,
-                                   const GridDesc& g, double* cov6, hipStream_t stream, int* list = nullptr, bool list_counters_zero = false);
+                                   const GridDesc& g, double* cov6, hipStream_t stream, int* list = nullptr, bool list_counters_zero = false,
+                                   float4* normals = nullptr);
 // (list: 2 n + 2 ints of scratch -- the points the selecting kernel hands to the far-field and the streaming kernel; icp_gicp.hip.
 //  list_counters_zero: list[0] and list[1] are zero -- true from the second cloud on the same buffer: the last kernel leaves them so)
 // maha6[i] = upper triangle of (C_t[j] + R C_s[i] R^T)^-1 for every source point whose key passes d2 < thr
@@ -325,6 +329,17 @@ static constexpr unsigned int kGicpServerExit = 0xFFFFFFFFu;
 hipError_t launch_gicp_server(int blocks, const float4* src, int n_s, const float4* tgt, const unsigned long long* keys, float thr,
                               const Xform& base, const double* maha6, double* host_partials, unsigned long long* host_flags,
                               unsigned int* cmd, unsigned int first_seq, unsigned int seq_hi, hipStream_t stream);
+
+// ---- point-to-plane mode (icp_p2plane.hip): pcl::IterativeClosestPointWithNormals + TransformationEstimationPointToPlaneLLS --
+// sums[29] over the pairs of a key sweep whose d2 <= thr (the point-to-point accept rule): [0] n, [1] sum d2, [2..22] the upper
+// triangle of A^T A over (a, b, c, nx, ny, nz) row by row, [23..28] A^T r -- pairs whose target normal is not finite count in [0]
+// and [1] only.  partials: p2plane_blocks(n_s) x kP2planeTerms doubles of device memory.  Like launch_reduce: with flags the 29
+// sums go to the host mailbox as result pairs numbered seq (words 2k, 2k + 1), otherwise to sums_out (device memory).
+static constexpr int kP2planeTerms = 29;
+int p2plane_blocks(int n_s);
+hipError_t launch_p2plane_reduce(const float4* src, int n_s, const float4* tgt, const float4* normals, const unsigned long long* keys,
+                                 const Xform& T, float thr, double* partials, double* sums_out, unsigned long long* flags,
+                                 unsigned long long seq, hipStream_t stream);
 
 // ---- the mapper's one-point-per-voxel map (icp_map.hip), SURVEY.md 8(f4) --------------------------------------------
 struct MapDesc {

@@ -521,12 +521,13 @@ int create_context(icpgpu_ctx** out_ctx, int device_id, bool with_stream) {
   for (auto& ev : c->ev)
     if ((e = hipEventCreate(&ev)) != hipSuccess) return bail("hipEventCreate", e);
   // mailbox: 24 doubles the host keeps the current sums (and a few spare slots) in, then the 17 {sum, number} pairs the
-  // device writes (reduce_final_kernel)
-  if ((e = hipHostMalloc(reinterpret_cast<void**>(&c->h_sums), (24 + 2 * kReduceTerms) * sizeof(double),
+  // device writes (reduce_final_kernel) -- 29 of them in the point-to-plane mode (icp_p2plane.hip)
+  constexpr int kMailboxPairs = kP2planeTerms > kReduceTerms ? kP2planeTerms : kReduceTerms;
+  if ((e = hipHostMalloc(reinterpret_cast<void**>(&c->h_sums), (24 + 2 * kMailboxPairs) * sizeof(double),
                          hipHostMallocMapped | hipHostMallocCoherent)) !=  // fine-grained: the polled flags must become visible without a sync
       hipSuccess)
     return bail("hipHostMalloc", e);
-  std::memset(c->h_sums, 0, (24 + 2 * kReduceTerms) * sizeof(double));
+  std::memset(c->h_sums, 0, (24 + 2 * kMailboxPairs) * sizeof(double));
   if ((e = hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_sums_dev), c->h_sums, 0)) != hipSuccess)
     return bail("hipHostGetDevicePointer", e);
   c->h_flags = reinterpret_cast<volatile unsigned long long*>(c->h_sums + 24);
@@ -631,7 +632,7 @@ int icpgpu_destroy(icpgpu_ctx* c) {
   release(c->partials);
   release(c->sums);
   release(c->out);
-  for (GridIndex* G : {&c->cov_grid_src, &c->cov_grid_tgt}) {
+  for (GridIndex* G : {&c->cov_grid_src, &c->cov_grid_tgt, &c->nrm_grid}) {
     release(G->sorted);
     release(G->cell_start);
     release(G->cell_of_point);
@@ -643,6 +644,7 @@ int icpgpu_destroy(icpgpu_ctx* c) {
   }
   release(c->cov_src);
   release(c->cov_tgt);
+  for (DeviceBuf* b : {&c->nrm_src, &c->nrm_tgt, &c->nrm_raw, &c->nrm_user, &c->p2plane_partials}) release(*b);
   release(c->maha);
   release(c->cov_list);
   release(c->vox_in);
@@ -715,7 +717,7 @@ int icpgpu_set_params(icpgpu_ctx* c, const icpgpu_params* user) {
   default_params_full(&full);
   std::memcpy(&full, user, std::min(c->abi_params, sizeof(full)));
   const icpgpu_params* p = &full;
-  if (p->method != ICPGPU_P2P_SVD && p->method != ICPGPU_GICP) return fail(c, ICPGPU_ERR_INVALID_ARG, "bad method");
+  if (p->method != ICPGPU_P2P_SVD && p->method != ICPGPU_GICP && p->method != ICPGPU_P2PLANE) return fail(c, ICPGPU_ERR_INVALID_ARG, "bad method");
   if (p->nn_mode < ICPGPU_NN_AUTO || p->nn_mode > ICPGPU_NN_GRID) return fail(c, ICPGPU_ERR_INVALID_ARG, "bad nn_mode");
   if (p->brute_variant < 0 || p->brute_variant > 2) return fail(c, ICPGPU_ERR_INVALID_ARG, "bad brute_variant");
   if (p->gicp_inner != ICPGPU_GICP_INNER_EXACT && p->gicp_inner != ICPGPU_GICP_INNER_QUADRATIC)
@@ -778,6 +780,7 @@ int icpgpu_set_source(icpgpu_ctx* c, const float* xyzw, size_t n) {
 // part.  Callers that replace the source in the same step must set the target FIRST (the C++ shim does).
 int icpgpu_set_target(icpgpu_ctx* c, const float* xyzw, size_t n) {
   ENTER(c);
+  c->nrm_supplied = false;  // (icpgpu_set_target_normals: the caller's normals belong to the cloud they were given with)
   if (recognise_enabled() && n > 0 && xyzw) {
     bool tgt_cand = c->tgt.set && c->tgt.n == n && !c->tgt.buf.external;
     bool src_cand = c->src.set && c->src.n == n && !c->src.buf.external;
@@ -839,6 +842,7 @@ int icpgpu_set_source_device(icpgpu_ctx* c, const void* d, size_t n) {
 }
 int icpgpu_set_target_device(icpgpu_ctx* c, const void* d, size_t n) {
   ENTER(c);
+  c->nrm_supplied = false;
   c->tgt_version++;
   return set_cloud_device(c, c->tgt, d, n);
 }
@@ -923,6 +927,7 @@ int icpgpu_cloud_sizes(const icpgpu_ctx* c, size_t* n_source, size_t* n_target) 
 namespace icpgpu_impl {
 int promote_internal(icpgpu_ctx* c) {
   if (!c->src.set) return fail(c, ICPGPU_ERR_NO_INPUT, "promote_source_to_target: no source set");
+  c->nrm_supplied = false;  // (estimated normals are per cloud version: the new target's are estimated when first needed)
   std::swap(c->src, c->tgt);
   c->tgt_fp = c->src_fp;  // (versions are re-stamped below)
   const bool fp_follows = c->src_fp_version == c->src_version;

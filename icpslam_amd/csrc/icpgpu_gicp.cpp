@@ -51,7 +51,8 @@ static int cov_grid_begin(icpgpu_ctx* c, const Cloud& cloud, uint64_t version, G
   return gb_begin(c, b, cloud, version, cut_used, /*adapt=*/false, G, nullptr, knn_pop, h_start);
 }
 
-static int cov_launch(icpgpu_ctx* c, const Cloud& cloud, uint64_t version, GridIndex& G, DeviceBuf& cov, uint64_t& cov_version, bool timed) {
+static int cov_launch(icpgpu_ctx* c, const Cloud& cloud, uint64_t version, GridIndex& G, DeviceBuf& cov, uint64_t& cov_version, bool timed,
+                      float4* normals = nullptr) {
   if (G.usable) {
     const double cut = std::max(1e-3, c->params.max_correspondence_distance);
     c->cov_h_hint = (double)G.g.h;
@@ -73,10 +74,10 @@ static int cov_launch(icpgpu_ctx* c, const Cloud& cloud, uint64_t version, GridI
   if (G.usable)
     HIP_TRY(c, launch_gicp_covariances(cloud.data(), (int)cloud.n, static_cast<const float4*>(G.sorted.ptr),
                                        static_cast<const int*>(G.cell_start.ptr), G.g, static_cast<double*>(cov.ptr), c->stream,
-                                       static_cast<int*>(c->cov_list.ptr), counters_zero));
+                                       static_cast<int*>(c->cov_list.ptr), counters_zero, normals));
   else
     HIP_TRY(c, launch_gicp_covariances_brute(cloud.data(), (int)cloud.n, static_cast<double*>(cov.ptr), c->stream,
-                                             static_cast<int*>(c->cov_list.ptr), counters_zero));
+                                             static_cast<int*>(c->cov_list.ptr), counters_zero, normals));
   c->cov_list_zeroed = c->cov_list.ptr;
   c->cov_list_zeroed_cap = c->cov_list.cap;
   if (timed) {
@@ -96,14 +97,15 @@ static int cov_launch(icpgpu_ctx* c, const Cloud& cloud, uint64_t version, GridI
 // covariance pass are queued in one go, the statistics are posted behind the count pass and checked by covariance_grid_check() when
 // the alignment first waits for the device anyway.  (Per scan of the reference's pipeline this was the one remaining host round trip
 // of the index build: ~110 us of host wall in front of a 96 us kernel)
-int ensure_covariances(icpgpu_ctx* c, const Cloud& cloud, uint64_t version, GridIndex& G, DeviceBuf& cov, uint64_t& cov_version, bool allow_unchecked) {
+int ensure_covariances(icpgpu_ctx* c, const Cloud& cloud, uint64_t version, GridIndex& G, DeviceBuf& cov, uint64_t& cov_version, bool allow_unchecked,
+                       float4* normals) {
   GridBuild b;
   b.post = true;  // (the read-backs go through fetch_ints, as in build_grid)
   bool needed = false;
   int rc = cov_grid_begin(c, cloud, version, G, cov, cov_version, b, needed);
   if (rc || !needed) return rc;
   static const bool unchecked_enabled = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_COV_GRID_UNCHECKED"); return !e || std::atoi(e) != 0; }();
-  if (allow_unchecked && unchecked_enabled && b.state == GridBuild::WaitCount && b.h_start > 0.0 && !c->spec_grid.pending) {
+  if (allow_unchecked && !normals && unchecked_enabled && b.state == GridBuild::WaitCount && b.h_start > 0.0 && !c->spec_grid.pending) {
     if (c->spec_cooldown > 0) {
       c->spec_cooldown -= 1;
     } else {
@@ -129,7 +131,7 @@ int ensure_covariances(icpgpu_ctx* c, const Cloud& cloud, uint64_t version, Grid
     if (!rc) rc = gb_advance(c, b);
   }
   if (rc) return rc;
-  return cov_launch(c, cloud, version, G, cov, cov_version, /*timed=*/true);
+  return cov_launch(c, cloud, version, G, cov, cov_version, /*timed=*/true, normals);
 }
 
 // The statistics of a covariance grid that was built ahead of them (above): 0 = none pending or all is well (the grid's

@@ -326,6 +326,7 @@ int icpgpu_map_nn_target(icpgpu_ctx* c, const float* pose, const float* pose_inv
   const int n_s = (int)c->src.n;
   if (c->tgt.buf.external) c->tgt.buf = DeviceBuf{};
   c->tgt_version++;
+  c->nrm_supplied = false;
   c->tgt.set = true;
   c->tgt.n = 0;
   c->tgt.bbox_version = 0;

@@ -573,7 +573,9 @@ int icpgpu_align(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fi
   // a caller whose icpgpu_result is not this library's (include/icpgpu.h, ABI rule) gets the leading bytes it knows
   icpgpu_result own;
   icpgpu_result* res = c->abi_result == sizeof(icpgpu_result) ? user_res : &own;
-  const int rc = c->params.method == ICPGPU_GICP ? align_gicp(c, guess, out_xyzw, want_fitness, res) : align_p2p(c, guess, out_xyzw, want_fitness, res);
+  const int rc = c->params.method == ICPGPU_GICP      ? align_gicp(c, guess, out_xyzw, want_fitness, res)
+                 : c->params.method == ICPGPU_P2PLANE ? align_p2plane(c, guess, out_xyzw, want_fitness, res)
+                                                      : align_p2p(c, guess, out_xyzw, want_fitness, res);
   if (res != user_res) {
     std::memset(user_res, 0, c->abi_result);
     std::memcpy(user_res, res, std::min(c->abi_result, sizeof(own)));
@@ -697,7 +699,9 @@ int icpgpu_align_view(icpgpu_ctx* c, const float* guess, int want_fitness, icpgp
     ~ViewGuard() { c->want_view = false; }
   } guard{c};
   c->want_view = true;
-  const int rc = c->params.method == ICPGPU_GICP ? align_gicp(c, guess, nullptr, want_fitness, res) : align_p2p(c, guess, nullptr, want_fitness, res);
+  const int rc = c->params.method == ICPGPU_GICP      ? align_gicp(c, guess, nullptr, want_fitness, res)
+                 : c->params.method == ICPGPU_P2PLANE ? align_p2plane(c, guess, nullptr, want_fitness, res)
+                                                      : align_p2p(c, guess, nullptr, want_fitness, res);
   if (res != user_res) {
     std::memset(user_res, 0, c->abi_result);
     std::memcpy(user_res, res, std::min(c->abi_result, sizeof(own)));

@@ -245,6 +245,33 @@ class Context:
         full[:, 2, 0], full[:, 2, 1], full[:, 2, 2] = out[:, 2], out[:, 4], out[:, 5]
         return full
 
+    # point-to-plane mode (method P2PLANE) ----------------------------------------------------------------------
+    def set_target_normals(self, normals):
+        """icpgpu_set_target_normals: (n_target, 4) float32 {nx, ny, nz, pad} -- the target's normals as a PointNormal cloud carries
+        them (PCL's semantics exactly); dropped whenever the target changes."""
+        normals = _as_cloud(normals)
+        self._check(self._L.icpgpu_set_target_normals(self._h, _fp(normals), normals.shape[0]))
+
+    def normals(self, of_target: bool = True) -> np.ndarray:
+        """(n, 4) float32: the normals the point-to-plane mode uses for the target (the caller's, else estimated) or the source's
+        estimate; NaN rows for points without a neighbourhood (include/icpgpu.h, ICPGPU_P2PLANE)."""
+        n = self.n_target if of_target else self.n_source
+        out = np.zeros((n, 4), np.float32)
+        self._check(self._L.icpgpu_normals(self._h, int(of_target), _fp(out) if n else None))
+        return out
+
+    def reduce_point_to_plane(self, T, max_dist: float) -> np.ndarray:
+        """icpgpu_reduce_point_to_plane over the last nn() sweep: (29,) float64 = n, sum d2, the 21 upper-triangle entries of A^T A
+        over (a, b, c, nx, ny, nz), the 6 of A^T r."""
+        sums = np.zeros(29, np.float64)
+        Tb = _colmajor16(T)
+        self._check(self._L.icpgpu_reduce_point_to_plane(self._h, _fp(Tb), float(max_dist), sums.ctypes.data_as(C.POINTER(C.c_double))))
+        return sums
+
+    def solve_point_to_plane(self, sums):
+        """icpgpu_solve_point_to_plane: the 4x4 incremental transform from the 29 sums, or None for a singular system."""
+        return solve_point_to_plane(sums)
+
     def gicp_quadratic_sums(self, T=None) -> np.ndarray:
         """(75, 2) the sums of GICP's quadratic inner objective at transform T as (hi, lo) pairs (icp_gicp_quadratic.h) -- the
         device half of params.gicp_inner = GICP_INNER_QUADRATIC, for tests."""
@@ -309,6 +336,19 @@ class Context:
         v = C.c_uint64()
         self._check(self._L.icpgpu_count_candidates_read(self._h, C.byref(v)))
         return int(v.value)
+
+
+def solve_point_to_plane(sums):
+    """icpgpu_solve_point_to_plane (host only): (AᵀA)⁻¹Aᵀr -> constructTransformationMatrix, 4x4 float64; None when singular."""
+    L = _lib.load()
+    sums = np.ascontiguousarray(sums, np.float64)
+    if sums.shape != (29,):
+        raise ValueError("sums must be the 29 float64 terms of icpgpu_reduce_point_to_plane")
+    Tk = np.zeros(16, np.float64)
+    dp = C.POINTER(C.c_double)
+    if L.icpgpu_solve_point_to_plane(sums.ctypes.data_as(dp), Tk.ctypes.data_as(dp)) != 0:
+        return None
+    return Tk.reshape(4, 4).T.copy()
 
 
 def result_dict(res: Result, cloud):
@@ -412,3 +452,44 @@ class GeneralizedIterativeClosestPoint(IterativeClosestPoint):
         """NOT a PCL method (the C++ shim has the same one): the inner minimisation on the quadratic form of each outer iteration,
         icpgpu_params.gicp_inner -- faster, within tolerance of the default's result instead of on its bits (include/icpgpu.h)."""
         self._params.gicp_inner = _lib.GICP_INNER_QUADRATIC if on else _lib.GICP_INNER_EXACT
+
+
+class IterativeClosestPointWithNormals(IterativeClosestPoint):
+    """pcl::IterativeClosestPointWithNormals<PointNormal, PointNormal>-shaped front end (TransformationEstimationPointToPlaneLLS): the
+    point-to-point loop with the linearised point-to-plane solve.  setInputTarget(cloud, normals) hands the target's normals over as
+    a PointNormal cloud carries them; without them the target's normals are estimated on the device (GICP's plane: include/icpgpu.h,
+    ICPGPU_P2PLANE -- not pcl::NormalEstimation's)."""
+
+    METHOD = _lib.P2PLANE
+
+    def __init__(self, device_id: int = 0, method: int | None = None):
+        super().__init__(device_id, method)
+        self._target_normals = None
+
+    def setInputTarget(self, cloud, normals=None):
+        self._target = _as_cloud(cloud)
+        self._target_normals = None if normals is None else _as_cloud(normals)
+
+    def _upload(self):
+        self._ctx.set_params(self._params)
+        self._ctx.set_source(self._source)
+        self._ctx.set_target(self._target)
+        if self._target_normals is not None:
+            self._ctx.set_target_normals(self._target_normals)   # (after set_target: a new target drops the normals it had)
+
+    def align(self, guess=None) -> np.ndarray:
+        if self._source is None or self._target is None:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "align: setInputSource/setInputTarget first")
+        self._upload()
+        self._result = self._ctx.align(guess=guess, want_cloud=True)
+        self._ctx._last_user = self
+        return self._result["cloud"]
+
+    def getFitnessScore(self, max_range: float = float(np.finfo(np.float64).max)) -> float:
+        if self._result is not None and getattr(self._ctx, "_last_user", None) is not self:
+            self._upload()                       # the base class puts the clouds back; the normals go with the target
+            self._ctx._last_user = None
+            self._ctx.nn(self._result["T"])
+            s = self._ctx.reduce(self._result["T"], 1e18 if max_range >= 1e36 else float(np.sqrt(max_range)))
+            return float(s[16] / s[0]) if s[0] > 0 else float(np.finfo(np.float64).max)
+        return super().getFitnessScore(max_range)

@@ -37,7 +37,7 @@ extern "C" {
 #endif
 
 #define ICPGPU_VERSION_MAJOR 1
-#define ICPGPU_VERSION_MINOR 1
+#define ICPGPU_VERSION_MINOR 2
 #define ICPGPU_HEADER_VERSION (ICPGPU_VERSION_MAJOR * 1000 + ICPGPU_VERSION_MINOR)
 /* ABI rule (1.0).  icpgpu_params, icpgpu_result and icpgpu_profile only ever GROW AT THE END, and the library never assumes the
  * caller's structs are as long as its own: the caller's sizeof of the three travels with icpgpu_create (the macro below hands them
@@ -47,7 +47,8 @@ extern "C" {
  * icpgpu_create_abi refuses a header of another MAJOR version (ICPGPU_ERR_UNSUPPORTED).  Until 0.4 the structs grew in place with
  * nothing but a comment to protect an older caller; the unsized symbols of those versions (icpgpu_create, icpgpu_default_params,
  * icpgpu_align_batch_multi) are NOT exported any more, so a binary built against a 0.x header fails at load time instead of
- * overrunning its structs.  History: 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
+ * overrunning its structs.  History: 1.2 ICPGPU_P2PLANE, icpgpu_set_target_normals, icpgpu_normals, icpgpu_reduce_point_to_plane,
+ * icpgpu_solve_point_to_plane (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
  * icpgpu_profile.gicp_quadratic_solves; 0.3 icpgpu_profile (sources_adopted, gicp_host_solves, gicp_solver_choice). */
 
@@ -85,8 +86,20 @@ typedef enum {
 
 /* Solver. The reference instantiates pcl::GeneralizedIterativeClosestPoint (icp_odometer.cpp:188,
  * octree_mapper.cpp:104); BASELINE.json's north_star specifies point-to-point ICP
- * (pcl::IterativeClosestPoint semantics), which is the primary mode. */
-typedef enum { ICPGPU_P2P_SVD = 0, ICPGPU_GICP = 1 } icpgpu_method;
+ * (pcl::IterativeClosestPoint semantics), which is the primary mode.
+ * ICPGPU_P2PLANE (1.2) is pcl::IterativeClosestPointWithNormals with TransformationEstimationPointToPlaneLLS -- the "ICP that uses
+ * the surface" the reference wonders about at icp_odometer.cpp:187: the point-to-point loop (correspondences, rejection, convergence
+ * criteria, result fields) with the linearised point-to-plane solve in place of Umeyama.  The target's normals are the caller's
+ * (icpgpu_set_target_normals: PCL's semantics exactly, for PointNormal clouds) or ESTIMATED on the device: NOT
+ * pcl::NormalEstimation's eigen33 solve but GICP's plane -- the 20 nearest neighbours and the raw covariance computeCovariances
+ * forms, the same Eigen JacobiSVD restatement, the third left singular vector (the one computeCovariances scales by epsilon), rounded
+ * to float and turned towards the viewpoint (0, 0, 0) as flipNormalTowardsViewpoint does; points that get GICP's identity marker
+ * (non-finite, or every point of a cloud with fewer than 20 finite points) get a NaN normal, and a pair whose target normal is not
+ * finite is a correspondence that adds nothing to the solve (PCL's skip).  A singular system (a zero pivot or a non-finite
+ * solution: one plane and nothing else) -- undefined in PCL -- ends the alignment with converged = 0, ICPGPU_NOT_CONVERGED and
+ * the last finite transform.  Single alignments only: icpgpu_align_batch* return ICPGPU_ERR_UNSUPPORTED.  Parity against PCL
+ * binaries is unpinned, like every other mode's. */
+typedef enum { ICPGPU_P2P_SVD = 0, ICPGPU_GICP = 1, ICPGPU_P2PLANE = 2 } icpgpu_method;
 
 /* GICP's inner minimisation (PCL: estimateRigidTransformationBFGS, ~35 cost evaluations per outer iteration).
  *   EXACT      every evaluation is a pass over the correspondences with PCL's arithmetic (points transformed in float32); the
@@ -178,7 +191,7 @@ typedef struct {
   uint64_t voxel_launches;    /* voxel-grid filter runs */
   double voxel_ms;            /* key + sort + flag/scan + centroid kernels */
   uint64_t voxel_bytes;       /* algorithmic bytes: 16*N in + 16*N_out */
-  uint64_t gicp_cov_launches; /* GICP: per-cloud 20-NN covariance passes */
+  uint64_t gicp_cov_launches; /* GICP: per-cloud 20-NN covariance passes (and P2PLANE's normal estimates: the same kernels) */
   double gicp_cov_ms;
   uint64_t gicp_cost_launches; /* GICP: BFGS function/gradient evaluations (one device reduction each; with gicp_inner = QUADRATIC they
                                * run on the host, and gicp_eval_ms then holds the passes' and the minimisations' wall time) */
@@ -327,6 +340,27 @@ int icpgpu_transform(icpgpu_ctx* ctx, const float* T, float* out_xyzw);
 /* a11 (GICP mode): per-point regularised covariances U diag(1,1,1e-3) U^T of the 20 nearest neighbours
  * (pcl::GeneralizedIterativeClosestPoint::computeCovariances); out6 = n x {xx, xy, xz, yy, yz, zz}. */
 int icpgpu_gicp_covariances(icpgpu_ctx* ctx, int of_target, double* out6);
+/* ---- point-to-plane mode (ICPGPU_P2PLANE, 1.2) ------------------------------------------------------ */
+/* replaces setInputTarget's normals: pcl::IterativeClosestPointWithNormals<PointNormal, PointNormal> reads them from the target
+ * cloud's normal_x/y/z.  n float4 {nx, ny, nz, pad} (pad ignored), n == the target's size; copied, in force until the target changes
+ * (icpgpu_set_target -- recognised or not --, icpgpu_set_target_device, icpgpu_promote_source_to_target, icpgpu_map_nn_target drop
+ * them).  Without them P2PLANE estimates the target's normals at its first alignment after the target changed and keeps them while
+ * the target is the same cloud (a target icpgpu_set_target recognises included). */
+int icpgpu_set_target_normals(icpgpu_ctx* ctx, const float* nxyzw, size_t n);
+/* the normals P2PLANE uses for the target (of_target != 0: the caller's if set, else the estimate) or the source's estimate;
+ * out_nxyzw = n float4 {nx, ny, nz, 0}, NaN for marker points (pcl::NormalEstimation's output slot; see ICPGPU_P2PLANE).
+ * Estimating needs >= 20 points: ICPGPU_ERR_INVALID_ARG otherwise, as icpgpu_gicp_covariances. */
+int icpgpu_normals(icpgpu_ctx* ctx, int of_target, float* out_nxyzw);
+/* the counterpart of icpgpu_reduce: over pairs of the last icpgpu_nn sweep with (double)d2 <= max_dist^2, s = T * source[i] (float),
+ * d = target[idx], n = its normal -- TransformationEstimationPointToPlaneLLS::estimateRigidTransformation's sums in float64:
+ * sums = {n, sum d2, the 21 upper-triangle entries of A^T A over (a, b, c, nx, ny, nz) row by row, the 6 of A^T r} (DESIGN.md
+ * section 3 fixes the float expressions of a, b, c, r).  Same kernels and bits as an alignment's iterations. */
+int icpgpu_reduce_point_to_plane(icpgpu_ctx* ctx, const float* T, double max_dist, double sums[29]);
+/* (host) the symmetrised A^T A inverted as Eigen's 6x6 inverse() does (partial-pivot LU, float64), x = (A^T A)^-1 A^T r,
+ * Tk = constructTransformationMatrix(x0..x5) = [Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)] column-major with correctly rounded sin / cos.
+ * A zero pivot or a non-finite x: ICPGPU_ERR_INVALID_ARG and Tk = identity (the singular-system rule above). */
+int icpgpu_solve_point_to_plane(const double sums[29], double Tk[16]);
+
 /* ICPGPU_GICP_DEVICE=auto only: time GICP's two inner solvers on THIS box with the context's current source, target and parameters
  * (method GICP; a few alignments whose results are discarded) and keep the faster for the context's single alignments from now on.
  * *choice (nullable) = icpgpu_gicp_solver.  Never called implicitly: without it the fixed rule above holds, so two identical runs

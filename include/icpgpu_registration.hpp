@@ -284,6 +284,8 @@ class IterativeClosestPoint {
       }
       if (icpgpu_set_params(ctx_, &params_) != ICPGPU_OK) return false;
       if (icpgpu_set_target(ctx_, nt ? reinterpret_cast<const float*>(&target_->points[0]) : nullptr, nt) != ICPGPU_OK) return false;
+      // (after set_target, which drops the normals a target had: IterativeClosestPointWithNormals::setTargetNormals)
+      if (target_normals_ && icpgpu_set_target_normals(ctx_, target_normals_, n_target_normals_) != ICPGPU_OK) return false;
     } else if (icpgpu_set_params(ctx_, &params_) != ICPGPU_OK) {
       return false;
     }
@@ -337,6 +339,8 @@ class IterativeClosestPoint {
 
  protected:
   icpgpu_params params_;  // (GeneralizedIterativeClosestPoint sets its solver options here)
+  const float* target_normals_ = nullptr;  // (IterativeClosestPointWithNormals: the caller's target normals, n float4)
+  std::size_t n_target_normals_ = 0;
 
  private:
   icpgpu_result result_;
@@ -360,6 +364,22 @@ class GeneralizedIterativeClosestPoint : public IterativeClosestPoint<CloudT> {
   // scans/s of the reference's pipeline, results within the stated tolerance of the default's instead of on its bits.  An
   // unchanged call site opts in with ICPGPU_GICP_INNER=quadratic in the environment.
   void setQuadraticInnerSolver(bool on) { this->params_.gicp_inner = on ? ICPGPU_GICP_INNER_QUADRATIC : ICPGPU_GICP_INNER_EXACT; }
+};
+
+// pcl::IterativeClosestPointWithNormals<PointNormal, PointNormal>'s counterpart (TransformationEstimationPointToPlaneLLS): same
+// protocol, method = ICPGPU_P2PLANE -- the point-to-point loop with the linearised point-to-plane solve (the alternative the reference
+// names at icp_odometer.cpp:187).  The clouds stay 16-byte points; a PointNormal cloud's normals come separately through
+// setTargetNormals (n float4 {nx, ny, nz, pad}, n == the target's size, valid until align() returns).  Without them the target's normals are
+// estimated on the device: GICP's plane, not pcl::NormalEstimation's solve (include/icpgpu.h, ICPGPU_P2PLANE).
+template <class CloudT>
+class IterativeClosestPointWithNormals : public IterativeClosestPoint<CloudT> {
+ public:
+  explicit IterativeClosestPointWithNormals(int device = 0) : IterativeClosestPoint<CloudT>(device, ICPGPU_P2PLANE) {}
+  // NOT a PCL method (PCL reads normal_x/y/z of the target cloud): nxyzw = nullptr goes back to the estimated normals
+  void setTargetNormals(const float* nxyzw, std::size_t n) {
+    this->target_normals_ = nxyzw;
+    this->n_target_normals_ = nxyzw ? n : 0;
+  }
 };
 
 // pcl::VoxelGrid<PointT>-shaped front end for the odometer's pre-step
