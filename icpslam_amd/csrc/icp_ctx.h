@@ -127,26 +127,24 @@ struct BruteSeed {
 // The mapper's one-point-per-voxel map (icp_map.hip; octree_mapper.cpp:55-90).
 struct VoxelMap {
   bool defined = false;   // resolution set by icpgpu_map_reset
-  bool anchored = false;  // lattice origin fixed by the first point ever added
   MapDesc desc{};
   int n = 0;              // points in the map
   uint64_t version = 1;   // bumped whenever points are appended
   unsigned int cap = 0;   // hash-set capacity (power of two, load <= 1/2)
   Cloud pts;              // the map cloud (owned)
   DeviceBuf keys, vals, first, staged, moved, slot_of, flags, rank, temp, counter, nn_keys;
+  DeviceBuf pkeys;        // every map point's voxel key (first box's frame), as PCL gave it when the point was added
   DeviceBuf first_user, uflags, urank, uniq_index;
   Cloud uniq;             // the distinct points of the last nn cloud (what the ICP target's grid is built from)
   GridIndex grid;         // for the nn-cloud search
-  // PCL-faithful approxNearestSearch mode (icpgpu_map_set_search): the octree's bounding box as PCL grows it, replayed over
-  // the map points in insertion order, and the hash set of occupied octree nodes (icp_map.hip)
+  // the octree's bounding box as PCL grows it (adoptBoundingBoxToPoint), replayed over every insertion batch in input order:
+  // the map's keys come from it, and so does the PCL-faithful approxNearestSearch mode (icpgpu_map_set_search), whose hash set
+  // of occupied octree nodes follows the map (icp_map.hip)
   int search_mode = ICPGPU_MAP_SEARCH_EXACT;
   bool box_defined = false;
   ApproxBox box{};
-  ApproxHistory box_hist{};   // every version of the box with the map index it is in force from (PCL keys are never recomputed)
-  long long box_shift[3] = {0, 0, 0};  // voxels the minimum has moved since the first box
-  int box_upto = 0;           // map points already folded into the box
   uint64_t box_version = 0;   // bumped whenever the box grows
-  DeviceBuf node_keys, node_vals;
+  DeviceBuf node_keys, node_vals, leaf_next;
   unsigned int node_cap = 0;
   int nodes_upto = 0;         // map points whose paths are in the node set
   uint64_t nodes_box_version = ~0ull;

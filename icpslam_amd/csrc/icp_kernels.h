@@ -343,34 +343,45 @@ hipError_t launch_p2plane_reduce(const float4* src, int n_s, const float4* tgt, 
 
 // ---- the mapper's one-point-per-voxel map (icp_map.hip), SURVEY.md 8(f4) --------------------------------------------
 struct MapDesc {
-  double ox, oy, oz;  // lattice origin = first inserted point - resolution (PCL OctreePointCloud: first box p +- res/2, widened to 2 voxels by getKeyBitSize)
-  double res;         // voxel size (octree_resolution_, 0.5 m)
+  double res;  // voxel size (octree_resolution_, 0.5 m); the voxel keys come from the octree's box (ApproxBox / ApproxHistory)
 };
-// PCL's octree geometry for the faithful approxNearestSearch mode (icp_map.hip): the bounding box as
-// OctreePointCloud::adoptBoundingBoxToPoint has grown it, in double; depth = levels below the root (side = 2^depth voxels)
+// PCL's octree geometry (OctreePointCloud, octree_pointcloud.hpp): the bounding box as adoptBoundingBoxToPoint has grown it, in
+// double; depth = levels below the root (side = 2^depth voxels); shift = whole voxels the minimum has moved since the first
+// box; origin = the first box's minimum
 struct ApproxBox {
   double min[3], max[3];
+  double origin[3];
+  long long shift[3];
   double res;
   int depth;
 };
-// PCL assigns a point's leaf key ONCE, from the bounding box of the moment it is added (genOctreeKeyforPoint), and re-roots the
-// tree when the box doubles -- a stored key then moves by whole voxels with the minimum; it is never recomputed from the new
-// minimum (which could round the other way for a point on a voxel border: the FIRST point sits on one by construction, the
-// first box being centred on it).  The history of the box: version v is in force from map index first[v] on; a point added
-// under it has key trunc((p - min[v]) / res) + (shift_now - shift[v]), shifts in voxels.
+// PCL keys a point ONCE, from the bounding box in force when the point is tested (genOctreeKeyforPoint), and re-roots the tree
+// when the box doubles -- a stored key then moves by whole voxels with the minimum; it is never recomputed from the new minimum
+// (which could round the other way for a point on a voxel face; a resolution that is not a power of two makes the minimum
+// round as it moves).  Map keys are therefore kept in the first box's frame: trunc((p - min[v]) / res) - shift[v] under the box
+// version v in force for the point.  The versions of one insertion batch: version k is in force from batch index first[k] on
+// (first = -1: carried over from earlier batches); the point AT first[k] grew the box (or was the first point of the map) and
+// is appended whatever its key holds, isVoxelOccupiedAtPoint() being false outside the box.
 constexpr int kApproxMaxVersions = 24;
 struct ApproxHistory {
   int n;
   int first[kApproxMaxVersions];
-  double min[kApproxMaxVersions][3];
+  double min[kApproxMaxVersions][3], max[kApproxMaxVersions][3];
   long long shift[kApproxMaxVersions][3];
 };
-hipError_t launch_approx_first_outside(const float4* pts, int n, const ApproxBox& b, int* d_first, hipStream_t stream);
+constexpr long long kMapKeyReach = (1ll << 20) - 1;  // voxels a map key may lie from the first box's minimum (21 bits per axis)
+// a point farther than this (in voxels) from the first box's minimum can never get a key in reach: a key and the point's
+// offset / res differ by less than one voxel plus the rounding of the minimum's moves
+constexpr double kMapFar = 1048576.0 + 2.0;
+// first point of pts[0..n) (index order) that is finite, not far, and outside the box (any finite one: box undefined)
+hipError_t launch_approx_first_outside(const float4* pts, int n, const ApproxBox& b, bool defined, int* d_first, hipStream_t stream);
 hipError_t launch_approx_fill(unsigned long long* keys, int* vals, unsigned int cap, hipStream_t stream);
-hipError_t launch_approx_insert(const float4* pts, int lo, int hi, const ApproxBox& b, const ApproxHistory& h, unsigned long long* keys,
-                                int* vals, unsigned int cap, hipStream_t stream);
+// the node paths of map points [lo, hi) from their stored keys; leaves chain their points through leaf_next
+hipError_t launch_approx_insert(const unsigned long long* pkeys, int lo, int hi, const ApproxBox& b, unsigned long long* keys,
+                                int* vals, int* leaf_next, unsigned int cap, hipStream_t stream);
 hipError_t launch_approx_descend(const float4* queries, int n, const Xform& T, const ApproxBox& b, const unsigned long long* keys,
-                                 const int* vals, unsigned int cap, unsigned long long* out, hipStream_t stream);
+                                 const int* vals, const int* leaf_next, const float4* map_pts, unsigned int cap,
+                                 unsigned long long* out, hipStream_t stream);
 int approx_max_depth();
 // generic primitives (icp_scan.hip): exclusive prefix sum of int32 (scratch: exclusive_scan_scratch_ints(n) ints) and a stable
 // LSD radix sort of (key, value) int32 pairs from the first halves of keys / vals (2 n ints each) into the second halves
@@ -381,13 +392,16 @@ hipError_t launch_radix_sort_pairs(int* keys, int* vals, int n, unsigned int end
 size_t map_scan_temp_bytes(int n);
 // hash set: keys (packed voxel coordinates, all-ones = empty), vals (map index, -1 = claimed this call), first (bids)
 hipError_t launch_map_fill(unsigned long long* keys, int* vals, int* first, unsigned int cap, hipStream_t stream);
-hipError_t launch_map_rehash(const float4* map_pts, int n_map, const MapDesc& m, unsigned long long* keys, int* vals,
-                             unsigned int cap, hipStream_t stream);
-// addPointsToMap(): p = T * in[i]; the first point (lowest i) of every unoccupied voxel is appended to map_pts at
-// base + (its rank among the appended), input order preserved; *d_n_added = number appended.  cap is a power of two.
-hipError_t launch_map_insert(const float4* in, int n, const Xform& T, const MapDesc& m, unsigned long long* keys, int* vals,
-                             int* first, unsigned int cap, float4* moved, int* slot_of, int* flags, int* rank, void* temp,
-                             size_t temp_bytes, int base, float4* map_pts, int* d_n_added, hipStream_t stream);
+hipError_t launch_map_rehash(const unsigned long long* pkeys, int n_map, unsigned long long* keys, int* vals, unsigned int cap,
+                             hipStream_t stream);
+// moved[i] = T * in[i] (w = 1)
+hipError_t launch_map_xform(const float4* in, int n, const Xform& T, float4* moved, hipStream_t stream);
+// addPointsToMap() for moved[0..n): every point keyed under the box version h gives it; the first point (lowest i) of every
+// unoccupied voxel, and every point that grew the box, is appended to map_pts at base + (its rank among the appended), input
+// order preserved, its key to pkeys; *d_n_added = number appended.  cap is a power of two.
+hipError_t launch_map_insert(const float4* moved, int n, const ApproxHistory& h, double res, unsigned long long* keys, int* vals,
+                             int* first, unsigned int cap, int* slot_of, int* flags, int* rank, void* temp, size_t temp_bytes,
+                             int base, float4* map_pts, unsigned long long* pkeys, int* d_n_added, hipStream_t stream);
 // nn cloud: out = T_out * map[index(keys[i])] for every non-empty key, order preserved; *d_n_out = points written
 hipError_t launch_map_nn_gather(const unsigned long long* keys, int n, const float4* map_pts, const Xform& T_out, int* flags,
                                 int* rank, void* temp, size_t temp_bytes, float4* out, int* d_n_out, hipStream_t stream);

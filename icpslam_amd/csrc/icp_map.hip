@@ -5,10 +5,14 @@
 //   :62-69  addPointsToMap()    for every point IN ORDER: if its octree voxel is not occupied, append it to map_cloud_
 //   :72-90  approxNearestNeighbors()  for every scan point the nearest map point -> "nn cloud", the ICP target
 // The octree itself is PCL's; what the reference relies on is (i) one point per leaf voxel, the FIRST one to arrive,
-// (ii) leaf voxels of a fixed lattice: PCL anchors the lattice at (first point - resolution: the first box p +- res/2 widened by getKeyBitSize) and only ever grows the
-// bounding box by whole octree side lengths, so voxel membership is floor((p - origin) / resolution) evaluated in double
-// (OctreePointCloud::genOctreeKeyforPoint), (iii) a nearest-neighbour query per scan point.  (iii) is approximate in PCL
-// (approxNearestSearch descends by voxel centre); here it is EXACT, which is what SURVEY.md 8(f4) asks for.
+// (ii) PCL's leaf keys: trunc((p - min) / resolution) in double under the bounding box in force when the point is tested
+// (OctreePointCloud::genOctreeKeyforPoint), the box starting at the first point +- resolution (p +- res/2 widened by
+// getKeyBitSize) and doubling towards every point outside it -- such a point is always added, isVoxelOccupiedAtPoint() being
+// false outside the box; keys are kept in the first box's frame (ApproxHistory in icp_kernels.h).  The minimum moves by
+// whole side lengths, but each move rounds in double, so for a resolution that is not a power of two a point on a voxel face
+// can key one voxel off floor((p - first minimum) / res) (until this was found the map keyed that lattice; powers of two
+// round exactly and were never affected).  (iii) a nearest-neighbour query per scan point.  (iii) is approximate in PCL
+// (approxNearestSearch descends by voxel centre); here it is EXACT by default, which is what SURVEY.md 8(f4) asks for.
 //
 // MI355X design: the octree becomes an open-addressing hash set keyed by the packed voxel coordinates (64-bit keys,
 // linear probing, load factor <= 1/2).  "First point in input order wins" is made deterministic under parallel
@@ -37,13 +41,15 @@ __device__ __forceinline__ unsigned long long hash_key(unsigned long long k) {  
   return k;
 }
 
-// voxel of a point: floor((p - origin) / resolution) per axis in double, like PCL's genOctreeKeyforPoint
-__device__ __forceinline__ bool voxel_key(const MapDesc& m, float x, float y, float z, unsigned long long& key) {
-  const double fx = floor(((double)x - m.ox) / m.res), fy = floor(((double)y - m.oy) / m.res), fz = floor(((double)z - m.oz) / m.res);
-  const double lim = (double)(kVoxelBias - 1);
-  if (!(fabs(fx) <= lim && fabs(fy) <= lim && fabs(fz) <= lim)) return false;  // also rejects NaN
-  const unsigned long long ux = (unsigned long long)((long long)fx + kVoxelBias), uy = (unsigned long long)((long long)fy + kVoxelBias),
-                           uz = (unsigned long long)((long long)fz + kVoxelBias);
+// PCL's key of a point inside box version v (genOctreeKeyforPoint: truncation), in the first box's frame; false beyond the reach
+__device__ __forceinline__ bool pcl_key(const ApproxHistory& h, int v, double res, float x, float y, float z, unsigned long long& key) {
+  const long long kx = (long long)(((double)x - h.min[v][0]) / res) - h.shift[v][0];
+  const long long ky = (long long)(((double)y - h.min[v][1]) / res) - h.shift[v][1];
+  const long long kz = (long long)(((double)z - h.min[v][2]) / res) - h.shift[v][2];
+  if (kx < -kMapKeyReach || kx > kMapKeyReach || ky < -kMapKeyReach || ky > kMapKeyReach || kz < -kMapKeyReach || kz > kMapKeyReach)
+    return false;
+  const unsigned long long ux = (unsigned long long)(kx + kVoxelBias), uy = (unsigned long long)(ky + kVoxelBias),
+                           uz = (unsigned long long)(kz + kVoxelBias);
   key = (uz << 42) | (uy << 21) | ux;
   return true;
 }
@@ -73,25 +79,17 @@ __global__ __launch_bounds__(256) void map_fill_kernel(unsigned long long* __res
   }
 }
 
-// re-insert the existing map points after the table has grown (one point per voxel: no races on the value)
-__global__ __launch_bounds__(256) void map_rehash_kernel(const float4* __restrict__ map_pts, int n_map, MapDesc m,
+// re-insert the existing map points after the table has grown, from their stored keys
+__global__ __launch_bounds__(256) void map_rehash_kernel(const unsigned long long* __restrict__ pkeys, int n_map,
                                                          unsigned long long* __restrict__ keys, int* __restrict__ vals,
                                                          unsigned int mask) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n_map) return;
-  const float4 p = map_pts[i];
-  unsigned long long key;
-  if (!voxel_key(m, p.x, p.y, p.z, key)) return;
-  const int s = find_or_claim(keys, mask, key);
+  const int s = find_or_claim(keys, mask, pkeys[i]);
   if (s >= 0) vals[s] = i;
 }
 
-// pass 1: transform, locate / claim the voxel, and bid for it with the input index (lowest index wins)
-__global__ __launch_bounds__(256) void map_claim_kernel(const float4* __restrict__ in, int n, Xform T, MapDesc m,
-                                                        unsigned long long* __restrict__ keys,
-                                                        const int* __restrict__ vals, int* __restrict__ first,
-                                                        unsigned int mask, float4* __restrict__ moved,
-                                                        int* __restrict__ slot_of) {
+__global__ __launch_bounds__(256) void map_xform_kernel(const float4* __restrict__ in, int n, Xform T, float4* __restrict__ moved) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const float4 s = in[i];
@@ -99,13 +97,39 @@ __global__ __launch_bounds__(256) void map_claim_kernel(const float4* __restrict
   xform_point(T, s.x, s.y, s.z, p.x, p.y, p.z);
   p.w = 1.0f;
   moved[i] = p;
+}
+
+constexpr int kGrewBox = 1 << 30;  // slot_of flag: the point grew the box (slots < 2^30: cap <= 2^30)
+
+// pass 1: key the point under its box version, locate / claim the voxel, and bid for it with the input index (lowest wins);
+// a point that grew the box is appended whatever the voxel holds (it still bids, so that later points find the voxel taken)
+__global__ __launch_bounds__(256) void map_claim_kernel(const float4* __restrict__ moved, int n, ApproxHistory h, double res,
+                                                        unsigned long long* __restrict__ keys,
+                                                        const int* __restrict__ vals, int* __restrict__ first,
+                                                        unsigned int mask, int* __restrict__ slot_of) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = moved[i];
+  int v = -1;
+  for (int k = 0; k < h.n; ++k)
+    if (h.first[k] <= i) v = k;
   int slot = -1;
   unsigned long long key;
-  if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && voxel_key(m, p.x, p.y, p.z, key)) {
-    slot = find_or_claim(keys, mask, key);
-    if (slot >= 0) {
-      if (vals[slot] >= 0) slot = -1;  // voxel occupied by an earlier call: isVoxelOccupiedAtPoint() == true
-      else atomicMin(&first[slot], i);
+  if (v >= 0 && isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
+    const bool grew = h.first[v] == i;
+    const double x = p.x, y = p.y, z = p.z;
+    // a point outside its box that did not grow it was beyond the reach (icpgpu_map.cpp, map_replay_box): dropped
+    const bool inside = !(x < h.min[v][0] || y < h.min[v][1] || z < h.min[v][2] || x >= h.max[v][0] || y >= h.max[v][1] ||
+                          z >= h.max[v][2]);
+    if ((grew || inside) && pcl_key(h, v, res, p.x, p.y, p.z, key)) {
+      slot = find_or_claim(keys, mask, key);
+      if (slot >= 0) {
+        if (!grew && vals[slot] >= 0) slot = -1;  // voxel occupied by an earlier call: isVoxelOccupiedAtPoint() == true
+        else {
+          atomicMin(&first[slot], i);
+          if (grew) slot |= kGrewBox;
+        }
+      }
     }
   }
   slot_of[i] = slot;
@@ -116,21 +140,24 @@ __global__ __launch_bounds__(256) void map_flag_kernel(const int* __restrict__ s
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const int s = slot_of[i];
-  flags[i] = (s >= 0 && first[s] == i) ? 1 : 0;
+  flags[i] = (s >= 0 && ((s & kGrewBox) || first[s] == i)) ? 1 : 0;
 }
 
 // pass 2: the winners append themselves at base + rank (input order preserved) and seal their voxel
 __global__ __launch_bounds__(256) void map_commit_kernel(const float4* __restrict__ moved, const int* __restrict__ slot_of,
                                                          const int* __restrict__ flags, const int* __restrict__ rank,
                                                          int n, int base, float4* __restrict__ map_pts,
+                                                         unsigned long long* __restrict__ pkeys,
+                                                         const unsigned long long* __restrict__ keys,
                                                          int* __restrict__ vals, int* __restrict__ first,
                                                          int* __restrict__ n_added) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   if (flags[i]) {
-    const int s = slot_of[i], idx = base + rank[i];
+    const int s = slot_of[i] & ~kGrewBox, idx = base + rank[i];
     map_pts[idx] = moved[i];
-    vals[s] = idx;
+    pkeys[idx] = keys[s];
+    vals[s] = idx;  // (two points share a slot only if one of them grew the box: either index marks it occupied)
     first[s] = kNoPoint;
   }
   if (i == n - 1) *n_added = rank[i] + flags[i];
@@ -195,23 +222,30 @@ __global__ __launch_bounds__(256) void map_unique_gather_kernel(const int* __res
 // OctreePointCloudSearch::approxNearestSearch descends from the root to the EXISTING child whose voxel centre is nearest to
 // the query (float squared distance, the first child in index order x*4 + y*2 + z on ties) and returns the point of the leaf
 // it ends in.  The octree is PCL's (not under /root/reference: restated from PCL 1.8's octree_pointcloud.hpp /
-// octree_search.hpp, as oracle/map_approx_np.py restates it -- PARITY UNPINNED); its geometry is the bounding box PCL grows
-// point by point (ApproxBox: the host replays adoptBoundingBoxToPoint on the map points in insertion order, the device
-// only finds the next point outside the box).  The tree itself becomes a hash set of occupied nodes keyed by (level, node
-// key = leaf key >> (depth - level)); the leaf entries carry the map point's index.
+// octree_search.hpp, as oracle/map_oracle.c's orc_octree_* restate it -- PARITY UNPINNED); its geometry is the bounding box
+// PCL grows point by point (ApproxBox: the host replays adoptBoundingBoxToPoint over every insertion batch in input order, the
+// device only finds the next point outside the box), and its leaf keys are the map's own (stored per map point).  The tree
+// itself becomes a hash set of occupied nodes keyed by (level, node key = leaf key >> (depth - level)); a leaf entry heads the
+// chain of its map points (more than one only where a point that grew the box landed in an occupied leaf).
 constexpr int kApproxMaxDepth = 19;  // 19 bits per axis + 5 bits of level in a 64-bit key
 __device__ __forceinline__ unsigned long long node_key(int level, long long kx, long long ky, long long kz) {
   return ((unsigned long long)level << 57) | ((unsigned long long)kx << 38) | ((unsigned long long)ky << 19) | (unsigned long long)kz;
 }
-// first map point of pts[0..n) (index order) that lies outside the box: *first = min index (INT_MAX: none)
-__global__ __launch_bounds__(256) void approx_first_outside_kernel(const float4* __restrict__ pts, int n, ApproxBox b,
+// first point of pts[0..n) (index order) that is finite, not far from the first box and outside the box -- with no box yet,
+// the first finite point: *first = min index (INT_MAX: none)
+__global__ __launch_bounds__(256) void approx_first_outside_kernel(const float4* __restrict__ pts, int n, ApproxBox b, bool defined,
                                                                    int* __restrict__ first) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   bool out = false;
   if (i < n) {
     const float4 p = pts[i];
     const double x = p.x, y = p.y, z = p.z;
-    out = x < b.min[0] || y < b.min[1] || z < b.min[2] || x >= b.max[0] || y >= b.max[1] || z >= b.max[2];
+    out = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
+    if (out && defined) {
+      const bool far = !(fabs((x - b.origin[0]) / b.res) <= kMapFar && fabs((y - b.origin[1]) / b.res) <= kMapFar &&
+                         fabs((z - b.origin[2]) / b.res) <= kMapFar);
+      out = !far && (x < b.min[0] || y < b.min[1] || z < b.min[2] || x >= b.max[0] || y >= b.max[1] || z >= b.max[2]);
+    }
   }
   const unsigned long long m = __ballot(out);
   if (m && (threadIdx.x & 63) == 0) atomicMin(first, i + (__ffsll((long long)m) - 1));
@@ -221,30 +255,26 @@ __global__ __launch_bounds__(256) void approx_fill_kernel(unsigned long long* __
   const unsigned int i = blockIdx.x * 256 + threadIdx.x;
   if (i < cap) {
     keys[i] = kEmptySlot;
-    vals[i] = kNoPoint;
+    vals[i] = -1;
   }
 }
 
-// the nodes on the path root -> leaf of map points [lo, hi)
-__global__ __launch_bounds__(256) void approx_insert_kernel(const float4* __restrict__ pts, int lo, int hi, ApproxBox b,
-                                                            ApproxHistory h, unsigned long long* __restrict__ keys,
-                                                            int* __restrict__ vals, unsigned int mask) {
+// the nodes on the path root -> leaf of map points [lo, hi): the stored key (first box's frame) moved by the whole voxels the
+// minimum has moved since; each leaf heads a chain of its points (leaf_next; order irrelevant: the descent takes the nearest,
+// the lowest index on ties, which is PCL's first in insertion order)
+__global__ __launch_bounds__(256) void approx_insert_kernel(const unsigned long long* __restrict__ pkeys, int lo, int hi, ApproxBox b,
+                                                            unsigned long long* __restrict__ keys, int* __restrict__ vals,
+                                                            int* __restrict__ leaf_next, unsigned int mask) {
   const int i = lo + blockIdx.x * 256 + threadIdx.x;
   if (i >= hi) return;
-  // the key PCL gave the point when it was added (box version v = the last one whose first index is <= i), moved by the
-  // whole voxels the minimum has moved since
-  int v = 0;
-  for (int k = 1; k < h.n; ++k)
-    if (h.first[k] <= i) v = k;
-  const float4 p = pts[i];
-  const int cur = h.n - 1;
-  const long long kx = (long long)(((double)p.x - h.min[v][0]) / b.res) + (h.shift[cur][0] - h.shift[v][0]);
-  const long long ky = (long long)(((double)p.y - h.min[v][1]) / b.res) + (h.shift[cur][1] - h.shift[v][1]);
-  const long long kz = (long long)(((double)p.z - h.min[v][2]) / b.res) + (h.shift[cur][2] - h.shift[v][2]);
+  const unsigned long long pk = pkeys[i];
+  const long long kx = (long long)(pk & 0x1FFFFFull) - kVoxelBias + b.shift[0];
+  const long long ky = (long long)((pk >> 21) & 0x1FFFFFull) - kVoxelBias + b.shift[1];
+  const long long kz = (long long)((pk >> 42) & 0x1FFFFFull) - kVoxelBias + b.shift[2];
   for (int d = 1; d <= b.depth; ++d) {
     const int sh = b.depth - d;
     const int s = find_or_claim(keys, mask, node_key(d, kx >> sh, ky >> sh, kz >> sh));
-    if (s >= 0 && d == b.depth) atomicMin(&vals[s], i);  // one point per leaf (two only if PCL's lattice and ours differ by an ulp)
+    if (s >= 0 && d == b.depth) leaf_next[i] = atomicExch(&vals[s], i);
   }
 }
 
@@ -262,7 +292,8 @@ __device__ __forceinline__ int approx_lookup(const unsigned long long* __restric
 // approxNearestSearchRecursive for q = T * query[i]; out[i] = (0 << 32 | map index) or the empty key for a non-finite query
 __global__ __launch_bounds__(256) void approx_descend_kernel(const float4* __restrict__ queries, int n, Xform T, ApproxBox b,
                                                              const unsigned long long* __restrict__ keys,
-                                                             const int* __restrict__ vals, unsigned int mask,
+                                                             const int* __restrict__ vals, const int* __restrict__ leaf_next,
+                                                             const float4* __restrict__ map_pts, unsigned int mask,
                                                              unsigned long long* __restrict__ out) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -307,8 +338,22 @@ __global__ __launch_bounds__(256) void approx_descend_kernel(const float4* __res
     kz = bz;
     leaf_slot = best_slot;
   }
-  const int idx = b.depth == 0 ? 0 : vals[leaf_slot];  // depth 0: the box is one voxel, the map one point
-  out[i] = (unsigned long long)(unsigned int)idx;
+  // the leaf: the nearest of its points (pointSquaredDist, candidate - query), the first in insertion order on ties
+  int idx = 0;  // depth 0: the box is one voxel, the map one point
+  if (b.depth > 0) {
+    float best = 0.f;
+    idx = -1;
+    for (int j = vals[leaf_slot]; j >= 0; j = leaf_next[j]) {
+      const float4 c = map_pts[j];
+      const float dx = c.x - qx, dy = c.y - qy, dz = c.z - qz;
+      const float dist = (dx * dx + dy * dy) + dz * dz;
+      if (idx < 0 || dist < best || (dist == best && j < idx)) {
+        best = dist;
+        idx = j;
+      }
+    }
+  }
+  out[i] = idx < 0 ? kEmptySlot : (unsigned long long)(unsigned int)idx;  // (an empty leaf cannot happen: every leaf has a point)
 }
 
 }  // namespace
@@ -320,24 +365,30 @@ hipError_t launch_map_fill(unsigned long long* keys, int* vals, int* first, unsi
   return hipGetLastError();
 }
 
-hipError_t launch_map_rehash(const float4* map_pts, int n_map, const MapDesc& m, unsigned long long* keys, int* vals,
-                             unsigned int cap, hipStream_t stream) {
+hipError_t launch_map_rehash(const unsigned long long* pkeys, int n_map, unsigned long long* keys, int* vals, unsigned int cap,
+                             hipStream_t stream) {
   if (n_map <= 0) return hipSuccess;
-  hipLaunchKernelGGL(map_rehash_kernel, dim3((n_map + 255) / 256), dim3(256), 0, stream, map_pts, n_map, m, keys, vals, cap - 1);
+  hipLaunchKernelGGL(map_rehash_kernel, dim3((n_map + 255) / 256), dim3(256), 0, stream, pkeys, n_map, keys, vals, cap - 1);
   return hipGetLastError();
 }
 
-hipError_t launch_map_insert(const float4* in, int n, const Xform& T, const MapDesc& m, unsigned long long* keys, int* vals,
-                             int* first, unsigned int cap, float4* moved, int* slot_of, int* flags, int* rank, void* temp,
-                             size_t temp_bytes, int base, float4* map_pts, int* d_n_added, hipStream_t stream) {
+hipError_t launch_map_xform(const float4* in, int n, const Xform& T, float4* moved, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_xform_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, in, n, T, moved);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_insert(const float4* moved, int n, const ApproxHistory& h, double res, unsigned long long* keys, int* vals,
+                             int* first, unsigned int cap, int* slot_of, int* flags, int* rank, void* temp, size_t temp_bytes,
+                             int base, float4* map_pts, unsigned long long* pkeys, int* d_n_added, hipStream_t stream) {
   if (n <= 0) return hipSuccess;
   const dim3 grid((n + 255) / 256), block(256);
-  hipLaunchKernelGGL(map_claim_kernel, grid, block, 0, stream, in, n, T, m, keys, vals, first, cap - 1, moved, slot_of);
+  hipLaunchKernelGGL(map_claim_kernel, grid, block, 0, stream, moved, n, h, res, keys, vals, first, cap - 1, slot_of);
   hipLaunchKernelGGL(map_flag_kernel, grid, block, 0, stream, slot_of, first, n, flags);
   hipError_t e = launch_exclusive_scan(flags, rank, n, static_cast<int*>(temp), stream);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(map_commit_kernel, grid, block, 0, stream, moved, slot_of, flags, rank, n, base, map_pts, vals, first,
-                     d_n_added);
+  hipLaunchKernelGGL(map_commit_kernel, grid, block, 0, stream, moved, slot_of, flags, rank, n, base, map_pts, pkeys, keys, vals,
+                     first, d_n_added);
   return hipGetLastError();
 }
 
@@ -371,26 +422,29 @@ hipError_t launch_map_nn_unique(const unsigned long long* keys, const int* flags
 }  // namespace icpgpu
 
 namespace icpgpu {
-hipError_t launch_approx_first_outside(const float4* pts, int n, const ApproxBox& b, int* d_first, hipStream_t stream) {
+hipError_t launch_approx_first_outside(const float4* pts, int n, const ApproxBox& b, bool defined, int* d_first, hipStream_t stream) {
   hipError_t e = hipMemsetAsync(d_first, 0x7F, sizeof(int), stream);  // 0x7F7F7F7F: larger than any index
   if (e != hipSuccess || n <= 0) return e;
-  hipLaunchKernelGGL(approx_first_outside_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, pts, n, b, d_first);
+  hipLaunchKernelGGL(approx_first_outside_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, pts, n, b, defined, d_first);
   return hipGetLastError();
 }
 hipError_t launch_approx_fill(unsigned long long* keys, int* vals, unsigned int cap, hipStream_t stream) {
   hipLaunchKernelGGL(approx_fill_kernel, dim3((cap + 255) / 256), dim3(256), 0, stream, keys, vals, cap);
   return hipGetLastError();
 }
-hipError_t launch_approx_insert(const float4* pts, int lo, int hi, const ApproxBox& b, const ApproxHistory& h, unsigned long long* keys,
-                                int* vals, unsigned int cap, hipStream_t stream) {
-  if (hi <= lo || b.depth == 0 || h.n < 1) return hipSuccess;
-  hipLaunchKernelGGL(approx_insert_kernel, dim3((hi - lo + 255) / 256), dim3(256), 0, stream, pts, lo, hi, b, h, keys, vals, cap - 1);
+hipError_t launch_approx_insert(const unsigned long long* pkeys, int lo, int hi, const ApproxBox& b, unsigned long long* keys,
+                                int* vals, int* leaf_next, unsigned int cap, hipStream_t stream) {
+  if (hi <= lo || b.depth == 0) return hipSuccess;
+  hipLaunchKernelGGL(approx_insert_kernel, dim3((hi - lo + 255) / 256), dim3(256), 0, stream, pkeys, lo, hi, b, keys, vals, leaf_next,
+                     cap - 1);
   return hipGetLastError();
 }
 hipError_t launch_approx_descend(const float4* queries, int n, const Xform& T, const ApproxBox& b, const unsigned long long* keys,
-                                 const int* vals, unsigned int cap, unsigned long long* out, hipStream_t stream) {
+                                 const int* vals, const int* leaf_next, const float4* map_pts, unsigned int cap,
+                                 unsigned long long* out, hipStream_t stream) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(approx_descend_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, queries, n, T, b, keys, vals, cap - 1, out);
+  hipLaunchKernelGGL(approx_descend_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, queries, n, T, b, keys, vals, leaf_next,
+                     map_pts, cap - 1, out);
   return hipGetLastError();
 }
 int approx_max_depth() { return kApproxMaxDepth; }

@@ -34,8 +34,8 @@ void xform_point_host(const Xform& T, const float* s, float p[3]) {
 // The octree's FIRST bounding box, as PCL builds it for the first point ever added (OctreePointCloud::adoptBoundingBoxToPoint on
 // an empty octree: box = p +- resolution / 2, then getKeyBitSize()): getKeyBitSize takes max_voxels = max(ceil(extent / res), 2),
 // so the tree starts ONE level deep with a side of 2 voxels, and -- the octree holding no leaf yet -- splits the oversize
-// evenly: min -= (side - extent) / 2, max += the same.  The box is therefore p +- resolution and the leaf lattice's origin
-// p - resolution (until round 4 this code stopped at p +- resolution / 2, depth 0: a lattice shifted by half a voxel).
+// evenly: min -= (side - extent) / 2, max += the same.  The box is therefore p +- resolution, its minimum p - resolution (until
+// round 4 this code stopped at p +- resolution / 2, depth 0: keys shifted by half a voxel).
 // Every operation below is PCL's, in double, in PCL's order, so that a resolution that is not a power of two rounds alike.
 void pcl_first_box(const float p[3], double res, double bmin[3], double bmax[3], int* depth) {
   const double eps = (double)FLT_EPSILON;  // PCL: const float minValue = std::numeric_limits<float>::epsilon()
@@ -58,35 +58,9 @@ void pcl_first_box(const float p[3], double res, double bmin[3], double bmax[3],
   *depth = (int)d;
 }
 
-// The lattice is anchored by the first point that is ever added: origin = the minimum corner of that first box (the box only
-// ever grows by whole octree side lengths afterwards, so the lattice never moves).  d_in: the batch in HBM.
-int map_anchor(icpgpu_ctx* c, const float4* d_in, int n, const Xform& T) {
-  VoxelMap& M = c->map;
-  std::vector<float> chunk;
-  for (int off = 0; off < n && !M.anchored; off += 4096) {
-    const int m = std::min(4096, n - off);
-    chunk.resize((size_t)m * 4);
-    HIP_TRY(c, hipMemcpyAsync(chunk.data(), d_in + off, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < m; ++i) {
-      float p[3];
-      xform_point_host(T, &chunk[(size_t)i * 4], p);
-      if (std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2])) {
-        double bmin[3], bmax[3];
-        int depth;
-        pcl_first_box(p, M.desc.res, bmin, bmax, &depth);
-        M.desc.ox = bmin[0];
-        M.desc.oy = bmin[1];
-        M.desc.oz = bmin[2];
-        M.anchored = true;
-        break;
-      }
-    }
-  }
-  return ICPGPU_OK;
-}
+int map_replay_box(icpgpu_ctx* c, const float4* moved, int n, ApproxHistory& H);
 
-// addPointsToMap() for a batch already in HBM
+// addPointsToMap() for a batch already in HBM: the box versions first (map_replay_box), then the claim over the batch
 int map_insert_device(icpgpu_ctx* c, const float4* d_in, int n, const float* pose, size_t* n_added) {
   VoxelMap& M = c->map;
   if (n_added) *n_added = 0;
@@ -95,8 +69,13 @@ int map_insert_device(icpgpu_ctx* c, const float4* d_in, int n, const float* pos
   if ((size_t)M.n + (size_t)n > (size_t)INT32_MAX / 4) return fail(c, ICPGPU_ERR_INVALID_ARG, "map too large");
   const Xform T = to_xform(pose);
   int rc;
-  if (!M.anchored && (rc = map_anchor(c, d_in, n, T))) return rc;
-  if (!M.anchored) return ICPGPU_OK;  // nothing finite in the batch: the map stays empty
+  if ((rc = ensure(c, M.moved, (size_t)n * sizeof(float4)))) return rc;
+  if ((rc = ensure(c, M.counter, 4 * sizeof(int)))) return rc;
+  HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
+  HIP_TRY(c, launch_map_xform(d_in, n, T, static_cast<float4*>(M.moved.ptr), c->stream));
+  ApproxHistory H;
+  if ((rc = map_replay_box(c, static_cast<const float4*>(M.moved.ptr), n, H))) return rc;
+  if (H.n == 0) return ICPGPU_OK;  // nothing finite in the batch and no box yet: the map stays empty
 
   // hash set with load <= 1/2 even if every point of the batch opens a new voxel
   const size_t need = 2 * ((size_t)M.n + (size_t)n);
@@ -109,23 +88,23 @@ int map_insert_device(icpgpu_ctx* c, const float4* d_in, int n, const float* pos
     M.cap = cap;
     HIP_TRY(c, launch_map_fill(static_cast<unsigned long long*>(M.keys.ptr), static_cast<int*>(M.vals.ptr),
                                static_cast<int*>(M.first.ptr), cap, c->stream));
-    HIP_TRY(c, launch_map_rehash(M.pts.data(), M.n, M.desc, static_cast<unsigned long long*>(M.keys.ptr),
+    HIP_TRY(c, launch_map_rehash(static_cast<const unsigned long long*>(M.pkeys.ptr), M.n, static_cast<unsigned long long*>(M.keys.ptr),
                                  static_cast<int*>(M.vals.ptr), cap, c->stream));
   }
   if ((rc = grow_preserving(c, M.pts.buf, (size_t)M.n * sizeof(float4), ((size_t)M.n + (size_t)n) * sizeof(float4)))) return rc;
-  if ((rc = ensure(c, M.moved, (size_t)n * sizeof(float4)))) return rc;
+  if ((rc = grow_preserving(c, M.pkeys, (size_t)M.n * sizeof(unsigned long long), ((size_t)M.n + (size_t)n) * sizeof(unsigned long long))))
+    return rc;
   if ((rc = ensure(c, M.slot_of, (size_t)n * sizeof(int)))) return rc;
   if ((rc = ensure(c, M.flags, (size_t)n * sizeof(int)))) return rc;
   if ((rc = ensure(c, M.rank, (size_t)n * sizeof(int)))) return rc;
   const size_t temp_bytes = map_scan_temp_bytes(n);
   if ((rc = ensure(c, M.temp, temp_bytes))) return rc;
-  if ((rc = ensure(c, M.counter, 4 * sizeof(int)))) return rc;
   int* d_added = static_cast<int*>(M.counter.ptr);
-  HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
-  HIP_TRY(c, launch_map_insert(d_in, n, T, M.desc, static_cast<unsigned long long*>(M.keys.ptr), static_cast<int*>(M.vals.ptr),
-                               static_cast<int*>(M.first.ptr), M.cap, static_cast<float4*>(M.moved.ptr),
-                               static_cast<int*>(M.slot_of.ptr), static_cast<int*>(M.flags.ptr), static_cast<int*>(M.rank.ptr),
-                               M.temp.ptr, temp_bytes, M.n, static_cast<float4*>(M.pts.buf.ptr), d_added, c->stream));
+  HIP_TRY(c, launch_map_insert(static_cast<const float4*>(M.moved.ptr), n, H, M.desc.res, static_cast<unsigned long long*>(M.keys.ptr),
+                               static_cast<int*>(M.vals.ptr), static_cast<int*>(M.first.ptr), M.cap, static_cast<int*>(M.slot_of.ptr),
+                               static_cast<int*>(M.flags.ptr), static_cast<int*>(M.rank.ptr), M.temp.ptr, temp_bytes, M.n,
+                               static_cast<float4*>(M.pts.buf.ptr), static_cast<unsigned long long*>(M.pkeys.ptr), d_added,
+                               c->stream));
   HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
   HIP_TRY(c, hipMemcpyAsync(c->h_ints, d_added, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -144,16 +123,19 @@ int map_insert_device(icpgpu_ctx* c, const float4* d_in, int n, const float* pos
 }
 
 
-// OctreePointCloud::adoptBoundingBoxToPoint for one point outside the box (oracle/map_approx_np.py::_adopt restates the same):
-// the box doubles -- all three axes at once, the old root becoming the UPPER child on every axis the point does not violate
-// from above -- until the point is inside
-void approx_adopt(VoxelMap& M, const float p[3]) {
-  ApproxBox& b = M.box;
+// OctreePointCloud::adoptBoundingBoxToPoint (oracle/map_oracle.c restates the same): the first point defines the box
+// (pcl_first_box); a point outside it doubles it -- all three axes at once, the old root becoming the UPPER child on every axis
+// the point does not violate from above -- until the point is inside
+void approx_adopt(ApproxBox& b, bool& defined, const float p[3]) {
   const double eps = (double)FLT_EPSILON;
   for (;;) {
-    if (!M.box_defined) {
+    if (!defined) {
       pcl_first_box(p, b.res, b.min, b.max, &b.depth);  // p +- res, depth 1 (getKeyBitSize)
-      M.box_defined = true;
+      for (int a = 0; a < 3; ++a) {
+        b.origin[a] = b.min[a];
+        b.shift[a] = 0;
+      }
+      defined = true;
       continue;
     }
     bool lower[3], upper[3], any = false;
@@ -167,55 +149,80 @@ void approx_adopt(VoxelMap& M, const float p[3]) {
     for (int a = 0; a < 3; ++a)
       if (!upper[a]) {
         b.min[a] -= side;
-        M.box_shift[a] += 1ll << b.depth;  // stored keys move by whole voxels with the minimum
+        b.shift[a] += 1ll << b.depth;  // stored keys move by whole voxels with the minimum
       }
     b.depth += 1;
     for (int a = 0; a < 3; ++a) b.max[a] = b.min[a] + ((double)(1ll << b.depth) * b.res - eps);
   }
 }
 
-// bring the box and the node set up to date with the map, then keys[i] = approxNearestSearch(pose * source[i])
+// The box versions one batch is keyed under (ApproxHistory, icp_kernels.h): replay adoptBoundingBoxToPoint over moved[0..n) in
+// input order.  Only a point outside the box changes it, and such a point is always added, so the device only has to find the
+// next one (one round trip per batch when the box does not grow, two more per growth).  A point whose key under the grown box
+// would lie beyond +-kMapKeyReach voxels is dropped and leaves the box as it was (oracle/map_oracle.c: map_candidate).
+int map_replay_box(icpgpu_ctx* c, const float4* moved, int n, ApproxHistory& H) {
+  VoxelMap& M = c->map;
+  // advanced on a copy, committed only when the whole batch has been replayed: an error leaves the map's box as it was
+  ApproxBox box = M.box;
+  bool defined = M.box_defined;
+  int grown = 0;
+  box.res = M.desc.res;
+  H.n = 0;
+  auto push = [&](int first) {
+    H.first[H.n] = first;
+    for (int a = 0; a < 3; ++a) {
+      H.min[H.n][a] = box.min[a];
+      H.max[H.n][a] = box.max[a];
+      H.shift[H.n][a] = box.shift[a];
+    }
+    H.n += 1;
+  };
+  if (defined) push(-1);
+  int* d_first = static_cast<int*>(M.counter.ptr) + 2;
+  for (int from = 0; from < n;) {
+    HIP_TRY(c, launch_approx_first_outside(moved + from, n - from, box, defined, d_first, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->h_ints, d_first, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->h_ints[0] >= n - from) break;  // the rest is inside
+    const int g = from + c->h_ints[0];
+    float p[4];
+    HIP_TRY(c, hipMemcpyAsync(p, moved + g, sizeof(p), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    ApproxBox b = box;
+    bool d = defined;
+    approx_adopt(b, d, p);
+    bool reach = true;
+    for (int a = 0; a < 3; ++a) {
+      const long long k = (long long)(((double)p[a] - b.min[a]) / b.res) - b.shift[a];
+      reach = reach && k >= -kMapKeyReach && k <= kMapKeyReach;
+    }
+    // (out of reach: only a point in the shell kMapKeyReach .. kMapFar voxels out gets here -- a few voxels thick)
+    if (reach) {
+      // (cannot happen: a growth at least doubles the side, and the reach bounds it to 2^22 voxels -- 22 versions at most)
+      if (H.n == kApproxMaxVersions)
+        return fail(c, ICPGPU_ERR_UNSUPPORTED, "map: the octree's bounding box grew more than %d times in one batch", kApproxMaxVersions - 1);
+      box = b;
+      defined = true;
+      grown++;
+      push(g);
+    }
+    from = g + 1;
+  }
+  M.box = box;
+  M.box_defined = defined;
+  M.box_version += (uint64_t)grown;
+  return ICPGPU_OK;
+}
+
+// bring the node set up to date with the map (the box already is), then keys[i] = approxNearestSearch(pose * source[i])
 int approx_nn_keys(icpgpu_ctx* c, const Xform& T, int n_s, unsigned long long* keys) {
   VoxelMap& M = c->map;
   int rc;
-  if ((rc = ensure(c, M.counter, 4 * sizeof(int)))) return rc;
-  int* d_first = static_cast<int*>(M.counter.ptr) + 2;
-  M.box.res = M.desc.res;
-  // (1) the bounding box: replay the growth over the points added since the last call (a handful of round trips per map LIFE)
-  while (M.box_upto < M.n) {
-    if (M.box_defined) {
-      HIP_TRY(c, launch_approx_first_outside(M.pts.data() + M.box_upto, M.n - M.box_upto, M.box, d_first, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(c->h_ints, d_first, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      if (c->h_ints[0] >= M.n - M.box_upto) {  // all inside
-        M.box_upto = M.n;
-        break;
-      }
-      M.box_upto += c->h_ints[0];
-    }
-    float p[4];
-    HIP_TRY(c, hipMemcpyAsync(p, M.pts.data() + M.box_upto, sizeof(p), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    approx_adopt(M, p);
-    M.box_version++;
-    if (M.box_hist.n >= kApproxMaxVersions) return fail(c, ICPGPU_ERR_UNSUPPORTED, "map: the octree's bounding box changed more than %d times", kApproxMaxVersions);
-    {  // the version in force from this point on (the point that made the box grow is keyed under the grown box)
-      ApproxHistory& H = M.box_hist;
-      H.first[H.n] = M.box_upto;
-      for (int a = 0; a < 3; ++a) {
-        H.min[H.n][a] = M.box.min[a];
-        H.shift[H.n][a] = M.box_shift[a];
-      }
-      H.n += 1;
-    }
-    M.box_upto += 1;
-    if (M.box.depth > approx_max_depth()) break;  // (reported below -- on this call and on every later one)
-  }
-  // the depth limit holds for EVERY call, not only for the one that grew the box: node keys pack 19 bits per axis
+  // the depth limit holds for EVERY call while the map is this deep: node keys pack 19 bits per axis
   if (M.box.depth > approx_max_depth())
     return fail(c, ICPGPU_ERR_UNSUPPORTED, "map: the octree is %d levels deep (approximate search supports %d)", M.box.depth,
                 approx_max_depth());
-  // (2) the set of occupied nodes: level d holds at most min(n, 8^d) of them
+  // the set of occupied nodes: level d holds at most min(n, 8^d) of them
   size_t nodes = 0;
   for (int d = 1; d <= M.box.depth; ++d) {
     const double full = std::pow(8.0, (double)d);
@@ -224,6 +231,7 @@ int approx_nn_keys(icpgpu_ctx* c, const Xform& T, int n_s, unsigned long long* k
   unsigned int cap = 1u << 12;
   while ((size_t)cap < 2 * nodes + 16) cap <<= 1;
   bool rebuild = M.nodes_box_version != M.box_version;
+  if ((rc = grow_preserving(c, M.leaf_next, (size_t)M.nodes_upto * sizeof(int), (size_t)M.n * sizeof(int)))) return rc;
   if (cap > M.node_cap) {
     if ((rc = ensure(c, M.node_keys, (size_t)cap * sizeof(unsigned long long)))) return rc;
     if ((rc = ensure(c, M.node_vals, (size_t)cap * sizeof(int)))) return rc;
@@ -237,10 +245,12 @@ int approx_nn_keys(icpgpu_ctx* c, const Xform& T, int n_s, unsigned long long* k
     M.nodes_upto = 0;
     M.nodes_box_version = M.box_version;
   }
-  HIP_TRY(c, launch_approx_insert(M.pts.data(), M.nodes_upto, M.n, M.box, M.box_hist, nk, nv, M.node_cap, c->stream));
+  HIP_TRY(c, launch_approx_insert(static_cast<const unsigned long long*>(M.pkeys.ptr), M.nodes_upto, M.n, M.box, nk, nv,
+                                  static_cast<int*>(M.leaf_next.ptr), M.node_cap, c->stream));
   M.nodes_upto = M.n;
-  // (3) the descent
-  HIP_TRY(c, launch_approx_descend(c->src.data(), n_s, T, M.box, nk, nv, M.node_cap, keys, c->stream));
+  // the descent
+  HIP_TRY(c, launch_approx_descend(c->src.data(), n_s, T, M.box, nk, nv, static_cast<const int*>(M.leaf_next.ptr), M.pts.data(),
+                                   M.node_cap, keys, c->stream));
   return ICPGPU_OK;
 }
 
@@ -260,17 +270,13 @@ int icpgpu_map_reset(icpgpu_ctx* c, double resolution) {
   if (!(resolution > 0.0) || !std::isfinite(resolution)) return fail(c, ICPGPU_ERR_INVALID_ARG, "map: resolution must be positive");
   VoxelMap& M = c->map;
   M.defined = true;
-  M.anchored = false;
-  M.desc = MapDesc{0.0, 0.0, 0.0, resolution};
+  M.desc = MapDesc{resolution};
   M.n = 0;
   M.pts.n = 0;
   M.pts.set = true;
   M.version++;
   M.cap = 0;  // the hash set is rebuilt by the next insertion
   M.box_defined = false;
-  M.box_hist.n = 0;
-  M.box_shift[0] = M.box_shift[1] = M.box_shift[2] = 0;
-  M.box_upto = 0;
   M.box_version++;
   M.nodes_upto = 0;
   M.nodes_box_version = ~0ull;

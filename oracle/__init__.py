@@ -96,6 +96,24 @@ def lib():
         L.orc_map_add_points_sequential.restype = C.c_long
         L.orc_map_nn_cloud.argtypes = [C.c_void_p, fp, C.c_size_t, fp, fp, fp]
         L.orc_map_nn_cloud.restype = C.c_long
+        L.orc_octree_create.argtypes = [C.c_double]
+        L.orc_octree_create.restype = C.c_void_p
+        L.orc_octree_destroy.argtypes = [C.c_void_p]
+        L.orc_octree_destroy.restype = None
+        L.orc_octree_size.argtypes = [C.c_void_p]
+        L.orc_octree_size.restype = C.c_size_t
+        L.orc_octree_points.argtypes = [C.c_void_p]
+        L.orc_octree_points.restype = fp
+        L.orc_octree_depth.argtypes = [C.c_void_p]
+        L.orc_octree_depth.restype = C.c_int
+        L.orc_octree_box.argtypes = [C.c_void_p, dp]
+        L.orc_octree_box.restype = None
+        L.orc_octree_add_points.argtypes = [C.c_void_p, fp, C.c_size_t, fp]
+        L.orc_octree_add_points.restype = C.c_long
+        L.orc_octree_approx_nn.argtypes = [C.c_void_p, fp, C.c_size_t, fp, ip]
+        L.orc_octree_approx_nn.restype = None
+        L.orc_octree_nn_cloud.argtypes = [C.c_void_p, fp, C.c_size_t, fp, fp, fp]
+        L.orc_octree_nn_cloud.restype = C.c_long
         _lib = L
     return _lib
 
@@ -276,4 +294,79 @@ class VoxelMap:
         n = self._L.orc_map_nn_cloud(self._h, pc, cloud.shape[0], pa, pb, out.ctypes.data_as(C.POINTER(C.c_float)))
         if n < 0:
             raise MemoryError("orc_map_nn_cloud")
+        return out[:n].copy()
+
+
+class PclOctreeMap:
+    """PCL 1.8's OctreePointCloudSearch as the mapper uses it (oracle/map_oracle.c, orc_octree_*): addPointsToMap through the
+    octree's own bounding-box growth and leaf test, and approxNearestSearch.  PARITY UNPINNED (PCL is not part of the
+    reference); restated from PCL's algorithm, independently of oracle/map_approx_np.py and of the kernels."""
+
+    def __init__(self, resolution: float = 0.5):
+        self._L = lib()
+        self.res = float(resolution)
+        self._h = self._L.orc_octree_create(self.res)
+        if not self._h:
+            raise MemoryError("orc_octree_create")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.orc_octree_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return int(self._L.orc_octree_size(self._h))
+
+    @property
+    def depth(self) -> int:
+        return int(self._L.orc_octree_depth(self._h))
+
+    @property
+    def box(self):
+        """(min, max) of the octree's bounding box, float64 (min_x_ .. max_z_)"""
+        b = np.zeros(6, np.float64)
+        self._L.orc_octree_box(self._h, b.ctypes.data_as(C.POINTER(C.c_double)))
+        return b[:3].copy(), b[3:].copy()
+
+    def add_points(self, cloud, pose=None) -> int:
+        cloud, pc = _f32(cloud)
+        g = None
+        if pose is not None:
+            gc, g = _f32(_colmajor(pose))
+        n = self._L.orc_octree_add_points(self._h, pc, cloud.shape[0], g)
+        if n < 0:
+            raise MemoryError("orc_octree_add_points")
+        return int(n)
+
+    def points(self) -> np.ndarray:
+        n = len(self)
+        if n == 0:
+            return np.zeros((0, 4), np.float32)
+        return np.ctypeslib.as_array(self._L.orc_octree_points(self._h), shape=(n, 4)).copy()
+
+    def approx_indices(self, cloud, pose=None) -> np.ndarray:
+        """approxNearestSearch(pose * cloud[i]) per point: map indices, -1 for a non-finite query"""
+        cloud, pc = _f32(cloud)
+        g = None
+        if pose is not None:
+            gc, g = _f32(_colmajor(pose))
+        idx = np.empty(cloud.shape[0], np.int32)
+        self._L.orc_octree_approx_nn(self._h, pc, cloud.shape[0], g, idx.ctypes.data_as(C.POINTER(C.c_int32)))
+        return idx
+
+    def nn_cloud(self, cloud, pose, pose_inv) -> np.ndarray:
+        """approxNearestNeighbors(pose * cloud) moved back by pose_inv, non-finite queries dropped (VoxelMap.nn_cloud's contract)"""
+        cloud, pc = _f32(cloud)
+        a, pa = _f32(_colmajor(pose))
+        b, pb = _f32(_colmajor(pose_inv))
+        out = np.empty_like(cloud)
+        n = self._L.orc_octree_nn_cloud(self._h, pc, cloud.shape[0], pa, pb, out.ctypes.data_as(C.POINTER(C.c_float)))
+        if n < 0:
+            raise MemoryError("orc_octree_nn_cloud")
         return out[:n].copy()

@@ -8,12 +8,13 @@
 What PCL does:
   * the bounding box starts as the first point +- resolution / 2, which getKeyBitSize() at once turns into a tree ONE level
     deep (max_voxels = max(ceil(extent / resolution), 2)) whose 2-voxel side is centred on that box: first point +- resolution;
-    it then doubles (all three axes at once) whenever a point falls outside, towards the side the point is on; the lattice of
-    leaf voxels never moves (the minimum moves by whole side lengths);
-  * one point per leaf here (octree_mapper.cpp:62-69 only adds a point whose leaf is empty);
+    it then doubles (all three axes at once) whenever a point falls outside, towards the side the point is on; the minimum
+    moves by whole side lengths (each move rounded in double), and a point is keyed under the box of the moment it is added;
+  * one point per leaf here (octree_mapper.cpp:62-69 only adds a point whose leaf is empty) -- except that a point OUTSIDE
+    the box is always added (isVoxelOccupiedAtPoint is false there) and may, once the box has grown round it, share a leaf;
   * approxNearestSearch descends from the root: at every level it goes to the EXISTING child whose voxel centre is nearest to
     the query (float squared distance, first child on ties in child-index order x*4 + y*2 + z), and returns the point of the
-    leaf it ends in -- never looking at any other leaf.
+    leaf it ends in (the nearest of its points, the first on ties) -- never looking at any other leaf.
 """
 from __future__ import annotations
 
@@ -32,7 +33,7 @@ class ApproxOctreeMap:
         self.max = np.zeros(3)
         self.depth = 0                  # octree_depth_: number of levels below the root; side = 2**depth voxels
         self.points: list[np.ndarray] = []
-        self.leaf: dict[tuple[int, int, int], int] = {}   # leaf key -> point index
+        self.leaf: dict[tuple[int, int, int], list[int]] = {}   # leaf key -> point indices, in insertion order
 
     # OctreePointCloud::adoptBoundingBoxToPoint
     def _adopt(self, p):
@@ -82,7 +83,7 @@ class ApproxOctreeMap:
             if inside and self._key(p) in self.leaf:      # isVoxelOccupiedAtPoint
                 continue
             self._adopt(p)
-            self.leaf[self._key(p)] = len(self.points)
+            self.leaf.setdefault(self._key(p), []).append(len(self.points))
             self.points.append(p.copy())
             added += 1
         self._levels = None
@@ -113,7 +114,13 @@ class ApproxOctreeMap:
                 if best is None or dist < best:
                     best, best_key = dist, nk
             key = best_key
-        return self.leaf[key]
+        best, best_i = None, None
+        for i in self.leaf[key]:
+            diff = self.points[i] - q
+            dist = f32(diff[0] * diff[0] + diff[1] * diff[1] + diff[2] * diff[2])
+            if best is None or dist < best:
+                best, best_i = dist, i
+        return best_i
 
     def nn_indices_approx(self, queries) -> np.ndarray:
         return np.array([self.approx_nearest(q) for q in np.asarray(queries, f32)], np.int64)

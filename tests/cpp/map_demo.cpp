@@ -1,9 +1,11 @@
 // map_demo.cpp -- the mapper's sequence (octree_mapper.cpp:133-172) written against the C++ shim.
-// usage: map_demo <scan0.bin> <n0> <scan1.bin> <n1> <pose1: 16 floats column-major> <pose1_inv: 16 floats>
+// usage: map_demo <scan0.bin> <n0> <scan1.bin> <n1> <pose1: 16 floats column-major> <pose1_inv: 16 floats> [approx <nn.bin>]
+//   approx: setPclApproximateSearch(true) and then resetMap() (the mode must survive the reset); the nn cloud goes to nn.bin
 // prints: map_size_after_seed n_nn converged iterations T[16] map_size_after_growth checksum(nn cloud)
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "icpgpu_registration.hpp"
@@ -31,6 +33,7 @@ static mock_pcl::PointCloud::Ptr load(const char* path, std::size_t n) {
 
 int main(int argc, char** argv) {
   if (argc < 5 + 32) return 2;
+  const bool approx = argc >= 5 + 32 + 2 && std::string(argv[37]) == "approx";
   auto scan0 = load(argv[1], std::strtoull(argv[2], nullptr, 10));
   auto cloud = load(argv[3], std::strtoull(argv[4], nullptr, 10));
   float pose[16], pose_inv[16];
@@ -40,6 +43,10 @@ int main(int argc, char** argv) {
   }
   try {
     icpgpu::OctreeMap<mock_pcl::PointCloud> map(/*octree_resolution_=*/0.5);
+    if (approx) {
+      map.setPclApproximateSearch(true);
+      map.resetMap();
+    }
     map.addPointsToMap(*scan0, icpgpu::Matrix4::Identity());                       // first scan: the map is empty (:137-141)
     const std::size_t seeded = map.size();
     mock_pcl::PointCloud::Ptr nn_cloud(new mock_pcl::PointCloud());
@@ -56,6 +63,14 @@ int main(int argc, char** argv) {
     const auto T = icp.getFinalTransformation();
     double checksum = 0.0;
     for (const auto& p : nn_cloud->points) checksum += (double)p.x + 2.0 * p.y + 3.0 * p.z + p.pad;
+    if (approx) {
+      FILE* f = std::fopen(argv[38], "wb");
+      if (!f || std::fwrite(nn_cloud->points.data(), sizeof(mock_pcl::PointXYZ), nn_cloud->size(), f) != nn_cloud->size()) {
+        std::perror(argv[38]);
+        return 2;
+      }
+      std::fclose(f);
+    }
     std::printf("%zu %zu %d %d", seeded, nn_cloud->size(), icp.hasConverged() ? 1 : 0, icp.getResult().iterations);
     for (int i = 0; i < 16; ++i) std::printf(" %.9g", T.data()[i]);
     map.addPointsToMap(*cloud, icpgpu::make_matrix4(pose));                        // grown with the (here: raw) pose, :152

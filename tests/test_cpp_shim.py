@@ -86,13 +86,13 @@ def test_gicp_shim_matches_oracle_and_objects_do_not_disturb_each_other(built, t
     assert abs(float(l2[1]) - other["fitness"]) <= 1e-9 * max(1.0, other["fitness"])
 
 
-def _run_map(exe, tmp_path, scan0, scan1, pose, pose_inv):
+def _run_map(exe, tmp_path, scan0, scan1, pose, pose_inv, *extra):
     a, b = tmp_path / "s0.bin", tmp_path / "s1.bin"
     scan0.tofile(a)
     scan1.tofile(b)
     cm = lambda M: [repr(float(v)) for v in np.asarray(M, np.float32).T.reshape(-1)]  # column-major
-    return subprocess.run([str(exe), str(a), str(scan0.shape[0]), str(b), str(scan1.shape[0])] + cm(pose) + cm(pose_inv),
-                          capture_output=True, text=True)
+    return subprocess.run([str(exe), str(a), str(scan0.shape[0]), str(b), str(scan1.shape[0])] + cm(pose) + cm(pose_inv) +
+                          [str(x) for x in extra], capture_output=True, text=True)
 
 
 def test_map_shim_compiles_and_fails_loudly_without_gpu(built, tmp_path):
@@ -130,6 +130,43 @@ def test_map_shim_matches_oracle(built, tmp_path):
     assert int(v[20]) == len(ref)
     c = nn.astype(np.float64)
     assert abs(float(v[21]) - (c[:, 0] + 2 * c[:, 1] + 3 * c[:, 2] + c[:, 3]).sum()) <= 1e-2
+
+
+@pytest.mark.gpu
+def test_map_shim_pcl_approx_search_survives_reset_and_matches_the_c_octree(built, tmp_path):
+    """OctreeMap::setPclApproximateSearch(true), then resetMap(): the mode is the object's and is re-applied by the reset.
+    The nn cloud equals PCL's approxNearestSearch as oracle.PclOctreeMap restates it, bit for bit (and differs from the exact
+    one); the map grows like the octree; the refinement on that nn cloud matches the oracle's."""
+    exe = _build_demo(tmp_path, "map_demo")
+    scan1, scan0, Tgt = synth.make_pair(20000, 20000, seed=8)
+    pose = Tgt.astype(np.float64).copy()
+    pose[:3, 3] += (0.1, -0.05, 0.0)
+    pose = pose.astype(np.float32)
+    pose_inv = np.linalg.inv(pose.astype(np.float64)).astype(np.float32)
+    out = tmp_path / "nn.bin"
+    r = _run_map(exe, tmp_path, scan0, scan1, pose, pose_inv, "approx", out)
+    assert r.returncode == 0, r.stderr
+    v = r.stdout.split()
+    octree = oracle.PclOctreeMap(0.5)
+    octree.add_points(scan0, np.eye(4))
+    assert int(v[0]) == len(octree)
+    nn = octree.nn_cloud(scan1, pose, pose_inv)
+    got = np.fromfile(out, np.float32).reshape(-1, 4)
+    assert int(v[1]) == nn.shape[0] == got.shape[0]
+    assert np.array_equal(got.view(np.uint32), nn.view(np.uint32))
+    assert not np.array_equal(got, _exact_nn(scan0, scan1, pose, pose_inv))         # the approximate search, not the exact one
+    o = oracle.icp_align(scan1, nn, oracle.default_params(max_iterations=30))
+    assert int(v[2]) == int(o["converged"]) and int(v[3]) == o["iterations"]
+    T = np.array([float(x) for x in v[4:20]]).reshape(4, 4).T
+    assert np.abs(T[:3, :3] - o["T"][:3, :3]).max() <= 1e-4 and np.linalg.norm(T[:3, 3] - o["T"][:3, 3]) <= 1e-3
+    octree.add_points(scan1, pose)
+    assert int(v[20]) == len(octree)
+
+
+def _exact_nn(scan0, scan1, pose, pose_inv):
+    ref = oracle.VoxelMap(0.5)
+    ref.add_points(scan0, np.eye(4))
+    return ref.nn_cloud(scan1, pose, pose_inv)
 
 
 def _build_c_demo(tmp_path):

@@ -203,3 +203,137 @@ def test_pcl_approx_search_mode_returns_the_restatements_nn_cloud(built, seed, n
         ie, _ = oracle.nn(scans[n_scans], am.map_points(), raw)
         got = c.map_nn_target(raw, raw_inv)
         assert np.array_equal(got, oracle.transform_cloud(am.map_points()[ie[fin]], raw_inv))
+
+
+def _face_queries(cloud, rng, n=6000):
+    q = np.ones((n, 4), np.float32)
+    q[:, :3] = cloud[rng.integers(0, cloud.shape[0], n), :3] + rng.normal(0.0, 0.3, (n, 3)).astype(np.float32)
+    q[:50, :3] *= np.float32(40.0)                              # far from the map
+    q[7, :3] = np.nan                                           # dropped
+    return q
+
+
+@pytest.mark.parametrize("approx", [False, True])
+@pytest.mark.parametrize("res", [0.2, 0.3, 0.05, 0.02, 0.25, 0.5])
+def test_face_campaign_map_and_nn_cloud_equal_the_c_octree(built, res, approx):
+    """~10k points on voxel faces +- 1 ulp (tests/test_map_oracle.py: face_cloud), keyed by PCL under nine boxes, inserted in
+    three batches (in the map frame, so that they stay on the faces) so that the points that grow the box sit in the middle
+    of a batch and the points on either side of one are keyed under different box versions: the map equals PCL's octree (oracle.PclOctreeMap) bit for bit, in
+    both search modes; the approximate nn cloud equals the octree's, the exact one oracle.nn's on that map."""
+    from icpslam_amd import Context
+    from test_map_oracle import face_cloud
+    cloud = face_cloud(res, 0)
+    T = None
+    octree = oracle.PclOctreeMap(res)
+    with Context(0) as c:
+        c.map_reset(res)
+        c.map_set_search(approx)
+        for part in np.array_split(cloud, 3):
+            assert c.map_add_points(part, T) == octree.add_points(part, T)
+        assert np.array_equal(_bits(c.map_points()), _bits(octree.points()))
+        rng = np.random.default_rng(int(res * 1000))
+        q = _face_queries(cloud, rng)
+        P = synth.pose_matrix(0.05, 0.02, -0.01, 0.0, 0.0, 0.01)
+        Pinv = np.linalg.inv(P.astype(np.float64)).astype(np.float32)
+        c.set_source(q)
+        got = c.map_nn_target(P, Pinv)
+        if approx:
+            want = octree.nn_cloud(q, P, Pinv)
+        else:
+            idx, _ = oracle.nn(q, octree.points(), P)
+            want = oracle.transform_cloud(octree.points()[idx[idx >= 0]], Pinv)
+        assert got.shape == want.shape == (q.shape[0] - 1, 4)
+        assert np.array_equal(_bits(got), _bits(want))
+
+
+def test_pcl_approx_interleaved_adds_and_searches_equal_a_map_built_at_once(built):
+    """The node set grows incrementally between searches (and is rebuilt when the box grows or its capacity doubles): after
+    every scan the nn cloud equals the C octree's, and the last one equals that of a fresh context that added everything
+    first."""
+    from icpslam_amd import Context
+    rng = np.random.default_rng(21)
+    scene = synth.make_scene(121)
+    poses = [np.eye(4)]
+    for _ in range(5):
+        poses.append(poses[-1] @ synth.pose_matrix(rng.uniform(0.5, 1.5), rng.uniform(-0.3, 0.3), 0.0, 0.0, 0.0,
+                                                   np.deg2rad(rng.uniform(-5, 5))))
+    scans = [synth.scan(scene, P.astype(np.float32), 20000, seed=1210 + k) for k, P in enumerate(poses)]
+    octree = oracle.PclOctreeMap(0.3)
+    q = scans[-1]
+    P = poses[-1].astype(np.float32)
+    Pinv = np.linalg.inv(P.astype(np.float64)).astype(np.float32)
+    with Context(0) as a:
+        a.map_reset(0.3)
+        a.map_set_search(True)
+        a.set_source(q)
+        for s, S in zip(scans[:-1], poses[:-1]):
+            S = S.astype(np.float32)
+            assert a.map_add_points(s, S) == octree.add_points(s, S)
+            got = a.map_nn_target(P, Pinv)
+            assert np.array_equal(_bits(got), _bits(octree.nn_cloud(q, P, Pinv))), (len(octree), octree.depth)
+    with Context(0) as b:
+        b.map_reset(0.3)
+        b.map_set_search(True)
+        for s, S in zip(scans[:-1], poses[:-1]):
+            b.map_add_points(s, S.astype(np.float32))
+        b.set_source(q)
+        assert np.array_equal(_bits(b.map_nn_target(P, Pinv)), _bits(got))
+
+
+def test_pcl_approx_depth_limits(built):
+    """Depth 19 (two points ~300 m apart at res 0.001) is searched like the C octree; depth 20 (~600 m) is refused with
+    ICPGPU_ERR_UNSUPPORTED on that search and on every later one, while the exact search stays correct; map_reset recovers."""
+    from icpslam_amd import Context
+    from icpslam_amd._lib import ERR_UNSUPPORTED, IcpGpuError
+    rng = np.random.default_rng(19)
+    q = np.ones((2000, 4), np.float32)
+    I = np.eye(4, dtype=np.float32)
+    with Context(0) as c:
+        for sep, depth in ((300.0, 19), (600.0, 20)):
+            pts = np.ones((2000, 4), np.float32)
+            pts[0, :3] = (1.0, 2.0, 3.0)
+            pts[1, :3] = (1.0 + sep, 2.0 - sep / 3, 3.0 + sep / 2)
+            t = rng.uniform(0.05, 0.95, (1998, 1))              # on the segment between them: inside the box
+            pts[2:, :3] = pts[0, :3] + t * (pts[1, :3] - pts[0, :3]) + rng.normal(0, 0.01, (1998, 3))
+            q[:, :3] = pts[rng.integers(0, 2000, 2000), :3] + rng.normal(0, 0.1, (2000, 3)).astype(np.float32)
+            octree, vm = oracle.PclOctreeMap(0.001), oracle.VoxelMap(0.001)
+            c.map_reset(0.001)
+            c.map_set_search(True)
+            assert c.map_add_points(pts) == octree.add_points(pts) == vm.add_points(pts)
+            assert octree.depth == depth
+            c.set_source(q)
+            if depth == 19:
+                assert np.array_equal(_bits(c.map_nn_target(I, I)), _bits(octree.nn_cloud(q, I, I)))
+                continue
+            for _ in range(2):
+                with pytest.raises(IcpGpuError) as e:
+                    c.map_nn_target(I, I)
+                assert e.value.code == ERR_UNSUPPORTED
+            c.map_add_points(pts[:10])                          # (nothing new: the map stays 20 levels deep)
+            with pytest.raises(IcpGpuError):
+                c.map_nn_target(I, I)
+            c.map_set_search(False)
+            assert np.array_equal(_bits(c.map_nn_target(I, I)), _bits(vm.nn_cloud(q, I, I)))
+            c.map_set_search(True)
+            c.map_reset(0.001)
+            small = oracle.PclOctreeMap(0.001)
+            assert c.map_add_points(pts[:1]) == small.add_points(pts[:1]) == 1
+            assert np.array_equal(_bits(c.map_nn_target(I, I)), _bits(small.nn_cloud(q, I, I)))
+
+
+def test_points_beyond_the_keys_reach_are_dropped_like_the_c_octree(ctx):
+    """Keys are 21 bits per axis: a point more than 2^20 - 1 voxels from the first box's minimum is dropped and does not grow
+    the box; the map equals the C octree's (which applies the same rule)."""
+    rng = np.random.default_rng(3)
+    pts = np.ones((4000, 4), np.float32)
+    pts[:, :3] = rng.uniform(-5, 5, (4000, 3))
+    pts[100, :3] = (1.0e6, 0.5, 0.5)
+    pts[200, :3] = (1.5e6, 0.5, 0.5)
+    pts[300, :3] = (0.5, -1.2e6, 0.5)
+    pts[400, :3] = (1048574.5, 1048576.9, -3.0)              # the thin shell just beyond the reach
+    pts[500, :3] = (-1.0e6, 0.5, 3.5)
+    octree = oracle.PclOctreeMap(1.0)
+    ctx.map_reset(1.0)
+    assert ctx.map_add_points(pts) == octree.add_points(pts)
+    assert np.array_equal(_bits(ctx.map_points()), _bits(octree.points()))
+    assert not (np.abs(octree.points()[:, :3]) > 1.1e6).any()

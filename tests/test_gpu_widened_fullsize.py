@@ -150,6 +150,71 @@ def test_mapper_flow_200k_scans_into_a_million_point_map(ctx):
     assert refined_ok == 7, refined_ok
 
 
+def test_mapper_flow_200k_scans_into_a_million_point_map_pcl_approx_search(built):
+    """The same flow with OctreeMapper(..., pcl_approx_search=True): the nn cloud of PCL's approxNearestSearch as the reference
+    calls it (octree_mapper.cpp:84) at config 3's scale.  After every scan the map equals PCL's octree (oracle.PclOctreeMap:
+    equal growth, bit for bit at scans 3 and 7) and the nn cloud equals the octree's bit for bit; then one more scan against
+    the million-point map.
+
+    FINDING (GICP on these nn clouds): the greedy descent sends the scan's points beyond the map's edge to a few edge leaves,
+    so one map point repeats thousands of times in the nn cloud (scan 6: about 4 100 times).  With its neighbours that fills
+    one cell of the GICP covariance index past 4096 points (kMaxCellPopulation; identical points cannot be split by smaller
+    cells), and a 200k-point cloud is too large for the grid-less kernel, so estimateTransformICP returns
+    ICPGPU_ERR_UNSUPPORTED -- a loud error, never a wrong result.  Asserted per scan: either the 30-iteration GICP equals
+    oracle.icp_align bit for bit (transform, iterations, correspondences) -- scans 1-5 and 7 -- or the device refuses with
+    ICPGPU_ERR_UNSUPPORTED and the nn cloud holds one point more than 2048 times.  Both maps then grow with the oracle's
+    refined pose."""
+    from icpslam_amd import Context
+    from icpslam_amd._lib import ERR_UNSUPPORTED, IcpGpuError
+    from icpslam_amd.sequence import pose_compose
+    scene = synth.make_scene(seed=41)
+    poses = [synth.pose_matrix(1.5 * k, 0.1 * k, 0.0, 0.0, 0.0, 0.03 * k) for k in range(8)]
+    with ThreadPoolExecutor(8) as ex:
+        scans = list(ex.map(lambda kp: synth.scan(scene, kp[1], 200000, seed=410 + kp[0]), enumerate(poses)))
+    err = synth.pose_matrix(0.12, -0.08, 0.02, 0.0, 0.0, 0.008)
+    res = 0.02
+    octree = oracle.PclOctreeMap(res)
+    p_gicp = oracle.default_params(method=oracle.GICP, max_iterations=30)
+    outcomes = []
+    with Context(0) as c:
+        mapper = OctreeMapper(c, octree_resolution=res, pcl_approx_search=True)
+        for k, (scan, P) in enumerate(zip(scans, poses)):
+            raw = pose_from_matrix((P.astype(np.float64) @ err.astype(np.float64)).astype(np.float32) if k else P)
+            raw_M, raw_Minv = pose_to_matrix(raw), pose_to_matrix(pose_inverse(raw))
+            if k == 0:
+                ok, transform, refined, info = mapper.refineTransformAndGrowMap(scan, raw)
+                assert not ok and info["seeded"] and info["added"] == octree.add_points(scan, raw_M)
+                continue
+            if k == 7:
+                assert mapper.map_size >= 1_000_000
+            nn_gpu = mapper.approxNearestNeighbors(scan, raw, want_cloud=True)
+            nn_ref = octree.nn_cloud(scan, raw_M, raw_Minv)
+            assert nn_gpu.shape == nn_ref.shape == (200000, 4)
+            assert np.array_equal(_bits(nn_gpu), _bits(nn_ref)), k
+            o = oracle.icp_align(scan, nn_ref, p_gicp)
+            assert o["converged"], k
+            try:
+                ok, transform, res_gpu = mapper.estimateTransformICP()
+            except IcpGpuError as e:
+                assert e.code == ERR_UNSUPPORTED, (k, str(e))
+                most = int(np.unique(_bits(nn_ref), axis=0, return_counts=True)[1].max())
+                assert most > 2048, (k, most)                      # (4 046 and 4 108 in two runs)
+                outcomes.append(("refused", most))
+            else:
+                assert ok
+                assert (res_gpu["iterations"], res_gpu["n_corr"]) == (o["iterations"], o["n_corr"]), k
+                assert np.array_equal(_bits(res_gpu["T"]), _bits(np.asarray(o["T"], np.float32))), k
+                outcomes.append(("equal", o["iterations"]))
+            refined = pose_compose(raw, pose_from_matrix(np.asarray(o["T"], np.float32)))
+            added = c.map_add_source(pose_to_matrix(refined))
+            assert added == octree.add_points(scan, pose_to_matrix(refined)), k
+            assert mapper.map_size == len(octree)
+            if k in (3, 7):
+                assert np.array_equal(_bits(mapper.map_cloud()), _bits(octree.points())), k
+        assert mapper.map_size == len(octree) >= 1_000_000 and 12 <= octree.depth <= 19, (len(octree), octree.depth)
+    print("GICP on the approximate nn clouds:", outcomes)
+
+
 # ---- (c) the QUADRATIC inner solver on a voxel-filtered drive ---------------------------------------------------------------------
 def test_quadratic_mode_on_a_voxel_filtered_drive_keeps_the_gate_decisions(built):
     """The reference's per-scan pipeline (VoxelGrid 0.2 m + GICP + the accept gate `converged and fitness < 20`,

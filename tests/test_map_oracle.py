@@ -1,25 +1,72 @@
 """CPU tests of the map oracle (oracle/map_oracle.c): the semantics the GPU map is held to."""
 import numpy as np
+import pytest
 
 import oracle
 from icpslam_amd import synth
 
 
 def _brute_map(points, res):
-    """Independent restatement in NumPy: first point per voxel of the lattice anchored at the octree's first box minimum (first point - res: PCL's getKeyBitSize)."""
-    pts = np.asarray(points, np.float32)
-    fin = np.isfinite(pts[:, :3]).all(1)
-    if not fin.any():
-        return np.zeros((0, 4), np.float32)
-    p0 = pts[fin][0, :3].astype(np.float64)
-    origin = (p0 - res / 2.0) - (2.0 * res - ((p0 + res / 2.0) - (p0 - res / 2.0))) / 2.0   # box p0 +- res/2 -> 2-voxel tree
+    """Independent restatement in NumPy of addPointsToMap with PCL's keys: the octree's box starts as the first finite point
+    +- res / 2, widened by getKeyBitSize to a 2-voxel tree (min = that point - res), and doubles towards every point that falls
+    outside it; a point inside the box is keyed trunc((p - min) / res) under the box of the moment and appended iff no earlier
+    point has that key; a point outside the box is always appended (isVoxelOccupiedAtPoint is false there).  Keys are kept in
+    the first box's frame (minus the whole voxels the minimum has moved)."""
+    eps = float(np.finfo(np.float32).eps)
+    mn = mx = None
+    depth, shift = 0, np.zeros(3, np.int64)
     out, seen = [], set()
-    for p in pts[fin]:
-        k = tuple(np.floor((p[:3].astype(np.float64) - origin) / res).astype(np.int64))
-        if k not in seen:
-            seen.add(k)
-            out.append(p)
-    return np.array(out, np.float32)
+    for p in np.asarray(points, np.float32):
+        if not np.isfinite(p[:3]).all():
+            continue
+        q = p[:3].astype(np.float64)
+        inside = mn is not None and bool((q >= mn).all() and (q < mx).all())
+        if mn is None:
+            mn, mx = q - res / 2.0, q + res / 2.0
+            depth = int(np.ceil(np.log(float(max(int(np.ceil((mx - mn - eps) / res).max()), 2))) / np.log(2.0) - eps))
+            over = (float(1 << depth) * res - (mx - mn)) / 2.0
+            mn, mx = np.where(over > eps, mn - over, mn), np.where(over > eps, mx + over, mx)
+        while not ((q >= mn).all() and (q < mx).all()):
+            up = q >= mx
+            mn = np.where(up, mn, mn - float(1 << depth) * res)
+            shift = shift + np.where(up, 0, 1 << depth)
+            depth += 1
+            mx = mn + (float(1 << depth) * res - eps)
+        k = tuple((((q - mn) / res).astype(np.int64) - shift).tolist())
+        if inside and k in seen:
+            continue
+        seen.add(k)
+        out.append(p)
+    return np.array(out, np.float32).reshape(-1, 4)
+
+
+def face_cloud(res, seed, n=10000):
+    """A first point, then ~n points on the voxel faces of its lattice (one ulp below, on, one ulp above, or inside, per axis),
+    in nine runs separated by eight points that grow the octree's box towards each octant in turn: the runs are keyed under
+    nine different boxes.  Where the resolution is not a power of two the box's minimum rounds as it moves, and PCL's key of a
+    point on a face differs from floor((p - first minimum) / res)."""
+    rng = np.random.default_rng(seed)
+    p0 = rng.uniform(-3, 3, 3).astype(np.float32)
+    o = p0.astype(np.float64) - res
+    octants = rng.permutation(8)
+    out = [np.append(p0, 1)[None]]
+    for j, idx in enumerate(np.array_split(np.arange(n), 9)):
+        m = len(idx)
+        k = rng.integers(-10, 10, (m, 3))
+        f = (o + k * res).astype(np.float32)
+        side = rng.integers(0, 4, (m, 3))
+        f = np.where(side == 0, np.nextafter(f, np.float32(-np.inf)), f)
+        f = np.where(side == 2, np.nextafter(f, np.float32(np.inf)), f)
+        f = np.where(side == 3, (o + (k + rng.uniform(0.1, 0.9, (m, 3))) * res).astype(np.float32), f)
+        out.append(np.hstack([f, np.ones((m, 1), np.float32)]))
+        if j < 8:
+            s = np.array([1.0 if (octants[j] >> b) & 1 else -1.0 for b in (2, 1, 0)])
+            g = p0 + s * res * (2.0 ** (3 + j)) * rng.uniform(1.1, 1.4, 3)
+            out.append(np.append(g.astype(np.float32), 1)[None])
+    return np.vstack(out).astype(np.float32)
+
+
+FACE_RES = [0.2, 0.3, 0.05, 0.02, 0.25, 0.5]      # 0.25 and 0.5: powers of two, the controls
 
 
 def test_first_point_per_voxel_in_input_order():
@@ -139,3 +186,188 @@ def test_batch_form_equals_the_sequential_loop():
         q, _, _ = synth.make_pair(500, 10, seed=seed)
         I = np.eye(4, dtype=np.float32)
         assert np.array_equal(a.nn_cloud(q, I, I), b.nn_cloud(q, I, I))     # (the sorted key arrays agree as well)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _four_points():
+    c = np.ones((4, 4), np.float32)
+    c[:, :3] = [[0, 0, 0], [-100, -100, -100], [26.95, 0.5, 0.5], [27.0, 0.5, 0.5]]
+    return c
+
+
+def test_a_point_on_a_voxel_face_after_the_box_has_grown():
+    """27.0 lies on a face of the first box's lattice; with the box grown to min -102.2 PCL computes 129.2 / 0.2 = 645.99..
+    and puts it in 26.95's voxel, which is occupied: three points, not four, in every restatement."""
+    from oracle.map_approx_np import ApproxOctreeMap
+    c = _four_points()
+    assert oracle.VoxelMap(0.2).add_points(c) == 3
+    assert oracle.VoxelMap(0.2).add_points(c, sequential=True) == 3
+    assert ApproxOctreeMap(0.2).add_points(c) == 3
+    assert oracle.PclOctreeMap(0.2).add_points(c) == 3
+    assert _brute_map(c, 0.2).shape[0] == 3
+
+
+@pytest.mark.parametrize("res", FACE_RES)
+def test_face_campaign_every_restatement_keys_like_pcl(res):
+    """~10k points on lattice faces +- 1 ulp, keyed under nine boxes: the C octree (PCL's tree), the NumPy octree, the lattice
+    map (batch and sequential) and the NumPy lattice restatement hold the same points in the same order, bit for bit."""
+    from oracle.map_approx_np import ApproxOctreeMap
+    for seed in (0, 2):
+        c = face_cloud(res, seed)
+        octree = oracle.PclOctreeMap(res)
+        n = octree.add_points(c)
+        want = octree.points()
+        assert octree.depth >= 10 and n == want.shape[0]
+        am = ApproxOctreeMap(res)
+        assert am.add_points(c) == n and np.array_equal(_bits(am.map_points()), _bits(want))
+        for sequential in (False, True):
+            vm = oracle.VoxelMap(res)
+            assert vm.add_points(c, sequential=sequential) == n
+            assert np.array_equal(_bits(vm.points()), _bits(want))
+        assert np.array_equal(_bits(_brute_map(c, res)), _bits(want))
+        # in batches, with a pose: the box carries over from call to call
+        T = synth.pose_matrix(0.3, -0.2, 0.1, 0.01, 0.02, 0.2)
+        octree, vm = oracle.PclOctreeMap(res), oracle.VoxelMap(res)
+        for part in np.array_split(c, 5):
+            assert octree.add_points(part, T) == vm.add_points(part, T)
+        assert np.array_equal(_bits(vm.points()), _bits(octree.points()))
+
+
+def _approx_both(points, queries, res):
+    """the C octree's and the NumPy octree's approximate indices for the same map (built from the same points)"""
+    from oracle.map_approx_np import ApproxOctreeMap
+    octree, am = oracle.PclOctreeMap(res), ApproxOctreeMap(res)
+    assert octree.add_points(points) == am.add_points(points)
+    assert np.array_equal(_bits(octree.points()), _bits(am.map_points()))
+    return octree, am, octree.approx_indices(queries)
+
+
+@pytest.mark.parametrize("res", [0.5, 0.3, 0.2, 1.0])
+def test_c_octree_approx_indices_equal_the_numpy_restatement_on_scans(res):
+    rng = np.random.default_rng(int(res * 10))
+    scene = synth.make_scene(80)
+    poses = [np.eye(4)]
+    for _ in range(2):
+        poses.append(poses[-1] @ synth.pose_matrix(rng.uniform(-0.6, 0.6), rng.uniform(-0.3, 0.3), 0.0, 0.0, 0.0,
+                                                   np.deg2rad(rng.uniform(-4, 4))))
+    scans = [synth.scan(scene, P, 5000, seed=810 + k) for k, P in enumerate(poses)]
+    pts = np.vstack([oracle.transform_cloud(s, P.astype(np.float32)) for s, P in zip(scans[:2], poses[:2])])
+    q = oracle.transform_cloud(scans[2], poses[2].astype(np.float32))
+    octree, am, idx = _approx_both(pts, q, res)
+    assert np.array_equal(idx, am.nn_indices_approx(q))
+    # the nn cloud: the same indices, moved back by the inverse pose
+    P = poses[2].astype(np.float32)
+    Pinv = np.linalg.inv(P.astype(np.float64)).astype(np.float32)
+    assert np.array_equal(octree.nn_cloud(scans[2], P, Pinv), oracle.transform_cloud(octree.points()[idx], Pinv))
+
+
+def test_c_octree_approx_ties_go_to_the_first_child():
+    """Queries at a parent node's centre (eight children at one distance) and midway between two child centres on each axis
+    (two at one distance): the first child in index order x*4 + y*2 + z wins, in both restatements."""
+    g = [(1.0, 1.0, 1.0)] + [(x + 0.2, y + 0.2, z + 0.2) for x in (0, 1) for y in (0, 1) for z in (0, 1) if x + y + z < 3]
+    pts = np.ones((8, 4), np.float32)
+    pts[:, :3] = g                  # box 0 .. 2 round the first point (1, 1, 1) at res 1: one point in each leaf of the root
+    q = np.ones((4, 4), np.float32)
+    q[:, :3] = [[1.0, 1.0, 1.0], [1.0, 0.5, 0.5], [0.5, 1.0, 0.5], [0.5, 0.5, 1.0]]
+    octree, am, idx = _approx_both(pts, q, 1.0)
+    assert octree.depth == 1
+    assert idx.tolist() == [1, 1, 1, 1] == am.nn_indices_approx(q).tolist()     # child 0: the point 0.2, 0.2, 0.2
+    # deeper: every node centre of a random 9-level tree and the midpoints between its children's centres
+    rng = np.random.default_rng(5)
+    res = 0.25
+    pts = np.ones((3000, 4), np.float32)
+    pts[:, :3] = (rng.integers(-60, 60, (3000, 3)) * res + res / 2).astype(np.float32)
+    octree, am, _ = _approx_both(pts, pts[:1], res)
+    mn, _ = octree.box
+    depth = octree.depth
+    qs = []
+    for _ in range(400):
+        d = int(rng.integers(0, depth))
+        key = ((pts[int(rng.integers(0, 3000)), :3] - mn) / res).astype(np.int64) >> (depth - d)
+        size = res * float(1 << (depth - d))
+        ctr = ((key + 0.5) * size + mn).astype(np.float32)
+        qs.append(ctr)
+        axis = int(rng.integers(0, 3))
+        mid = ctr.copy()
+        mid[axis] = np.float32(ctr[axis] - np.float32(size / 4))   # between the two children's centres along `axis`
+        qs.append(mid)
+    q = np.ones((len(qs), 4), np.float32)
+    q[:, :3] = qs
+    assert np.array_equal(octree.approx_indices(q), am.nn_indices_approx(q))
+
+
+def test_c_octree_approx_far_and_nonfinite_queries_and_a_one_point_map():
+    a, _, _ = synth.make_pair(4000, 10, seed=91)
+    q = np.ones((600, 4), np.float32)
+    rng = np.random.default_rng(91)
+    q[:, :3] = rng.uniform(-1, 1, (600, 3)) * np.float32(1e4)       # far outside the box
+    q[:300, :3] *= np.float32(1e-3)
+    octree, am, idx = _approx_both(a, q, 0.5)
+    assert np.array_equal(idx, am.nn_indices_approx(q))
+    q[[3, 77], :3] = np.nan
+    q[5, 1] = np.inf
+    idx = octree.approx_indices(q)
+    assert (idx[[3, 5, 77]] == -1).all() and (idx[np.isfinite(q[:, :3]).all(1)] >= 0).all()
+    I = np.eye(4, dtype=np.float32)
+    assert octree.nn_cloud(q, I, I).shape[0] == q.shape[0] - 3
+    one = oracle.PclOctreeMap(0.5)
+    one.add_points(a[:1])
+    assert len(one) == 1 and (one.approx_indices(q)[np.isfinite(q[:, :3]).all(1)] == 0).all()
+
+
+def test_c_octree_approx_on_a_deep_tree():
+    """res 0.01 over +-200 m: an octree 16 levels deep"""
+    rng = np.random.default_rng(17)
+    pts = np.ones((4000, 4), np.float32)
+    pts[:, :3] = rng.uniform(-200, 200, (4000, 3))
+    pts[2000:, :3] = pts[:2000, :3] + rng.normal(0, 0.02, (2000, 3))
+    q = np.ones((3000, 4), np.float32)
+    q[:, :3] = pts[rng.integers(0, 4000, 3000), :3] + rng.normal(0, 0.5, (3000, 3))
+    octree, am, idx = _approx_both(pts, q, 0.01)
+    assert octree.depth >= 15
+    assert np.array_equal(idx, am.nn_indices_approx(q))
+
+
+def test_c_octree_box_edges_point_at_min_and_just_below_max():
+    """A point exactly at the box's minimum is inside (key 0); a point within FLT_EPSILON below the nominal edge lies at or
+    above max_ (= min + side - FLT_EPSILON), so it is outside: it is appended although the leaf it lands in after the growth
+    is occupied -- a leaf with two points, where approxNearestSearch takes the nearer one."""
+    from oracle.map_approx_np import ApproxOctreeMap
+    pts = np.ones((6, 4), np.float32)
+    pts[0, :3] = 0.25                                   # first box -0.25 .. 0.75 at res 0.5
+    pts[1, :3] = -0.5                                   # grows it: min -1.25, max 0.75 - FLT_EPSILON
+    pts[2, :3] = -1.25                                  # exactly at min
+    pts[3, :3] = (np.nextafter(np.float32(0.75), np.float32(0)), 0.3, 0.3)   # >= max_: outside, grows, shares 0.25's leaf
+    pts[4, :3] = (0.3, 0.3, 0.3)                        # inside, occupied
+    pts[5, :3] = (-1.2, -1.2, -1.2)                     # inside, occupied by the point at min
+    octree, am = oracle.PclOctreeMap(0.5), ApproxOctreeMap(0.5)
+    assert octree.add_points(pts) == am.add_points(pts) == 4
+    assert np.array_equal(_bits(octree.points()), _bits(pts[:4]))
+    assert np.array_equal(_bits(_brute_map(pts, 0.5)), _bits(pts[:4]))
+    vm = oracle.VoxelMap(0.5)
+    assert vm.add_points(pts) == 4 and np.array_equal(_bits(vm.points()), _bits(pts[:4]))
+    q = np.ones((4, 4), np.float32)
+    q[:, :3] = [[0.26, 0.26, 0.26], [0.74, 0.3, 0.3], [-1.25, -1.25, -1.25], [0.5, 0.28, 0.28]]
+    idx = octree.approx_indices(q)
+    assert idx.tolist() == [0, 3, 2, 3] and np.array_equal(idx, am.nn_indices_approx(q))
+
+
+def test_points_beyond_the_keys_reach_are_dropped_by_every_restatement():
+    """A key is 21 bits per axis: a point keyed more than 2^20 - 1 voxels from the first box's minimum is dropped and leaves the
+    box as it was -- in the lattice form and in the C octree alike (PCL has no such limit; the products do)."""
+    pts = np.ones((5, 4), np.float32)
+    pts[0, :3] = (0.5, 0.5, 0.5)
+    pts[1, :3] = (1.0e6, 0.5, 0.5)             # ~1.0e6 voxels out at res 1: in reach, grows the box
+    pts[2, :3] = (1.5e6, 0.5, 0.5)             # beyond 2^20 voxels: dropped
+    pts[3, :3] = (0.5, -1.2e6, 0.5)            # dropped
+    pts[4, :3] = (-1.0e6, 0.5, 3.5)            # in reach
+    octree = oracle.PclOctreeMap(1.0)
+    assert octree.add_points(pts) == 3
+    assert np.array_equal(_bits(octree.points()), _bits(pts[[0, 1, 4]]))
+    for sequential in (False, True):
+        vm = oracle.VoxelMap(1.0)
+        assert vm.add_points(pts, sequential=sequential) == 3
+        assert np.array_equal(_bits(vm.points()), _bits(pts[[0, 1, 4]]))
