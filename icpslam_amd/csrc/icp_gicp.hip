@@ -42,12 +42,6 @@ __device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v,
   return ((unsigned long long)hi << 32) | lo;
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // Left singular vectors of a symmetric 3x3 (row-major), columns by decreasing singular value: Eigen::JacobiSVD<Matrix3d>(A,
 // ComputeFullU).matrixU() as the CPU checker restates it for computeCovariances (Eigen 3.3's two-sided Jacobi iteration on the
 // scaled matrix, pairs (1,0) (2,0) (2,1), a pair rotated while an off-diagonal exceeds 2 eps x the largest diagonal met so far,
@@ -170,6 +164,10 @@ __device__ void svd3_left_vectors(const double A[9], double U[9]) {
 }
 
 // ---- computeCovariances -----------------------------------------------------------------------------------------
+__device__ __forceinline__ void wave_lds_handover();
+__device__ __forceinline__ void cov_emit(const unsigned long long* top, double* scratch, const float4* __restrict__ cloud, int i,
+                                         double* __restrict__ cov6, int lane);
+
 // (list, optional: the points gicp_cov_select_kernel left over -- list[0 .. *list_n); without it every point of the cloud)
 __global__ __launch_bounds__(256) void gicp_cov_kernel(const float4* __restrict__ cloud, int n,
                                                        const float4* __restrict__ sorted,
@@ -178,6 +176,7 @@ __global__ __launch_bounds__(256) void gicp_cov_kernel(const float4* __restrict_
                                                        const int* __restrict__ list_n) {
   __shared__ unsigned long long s_key[4][GK];  // per-wave staging of the top-20 while it is re-ranked
   __shared__ int s_pos[4][GK];
+  __shared__ double s_scratch[4][9 * GK + 9];  // cov_emit's terms and sums
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   // one wave per point; with a list: a few hundred waves walk it (it is short or empty: an empty launch sized for the cloud cost 4.6 us)
   for (int slot = blockIdx.x * 4 + wv;; slot += gridDim.x * 4) {
@@ -188,7 +187,6 @@ __global__ __launch_bounds__(256) void gicp_cov_kernel(const float4* __restrict_
   }
   if (i >= n) return;
   const float4 s = cloud[i];
-  double C[6] = {1.0, 0.0, 0.0, 1.0, 0.0, 1.0};
   bool have_patch = false;
   if (finite3g(s.x, s.y, s.z)) {
     int cx, cy, cz;
@@ -283,38 +281,17 @@ __global__ __launch_bounds__(256) void gicp_cov_kernel(const float4* __restrict_
       const bool full = kth != kEmptyKey;  // all 20 slots filled
       if ((full && __uint_as_float((unsigned int)(kth >> 32)) <= safe * safe) || rho >= span) break;
     }
-    // lanes 0..19 hold the neighbours: mean and second moments (float products, double sums), wave-reduced
-    double sx = 0, sy = 0, sz = 0, xx = 0, yx = 0, yy2 = 0, zx = 0, zy = 0, zz2 = 0;
-    int have = 0;
-    if (lane < GK && mypos >= 0) {
-      const float4 q = sorted[mypos];
-      sx = q.x; sy = q.y; sz = q.z;
-      xx = (double)(q.x * q.x);
-      yx = (double)(q.y * q.x);
-      yy2 = (double)(q.y * q.y);
-      zx = (double)(q.z * q.x);
-      zy = (double)(q.z * q.y);
-      zz2 = (double)(q.z * q.z);
-      have = 1;
-    }
-    const int cnt = __popcll(__ballot(have));
-    sx = wave_sum_d(sx); sy = wave_sum_d(sy); sz = wave_sum_d(sz);
-    xx = wave_sum_d(xx); yx = wave_sum_d(yx); yy2 = wave_sum_d(yy2);
-    zx = wave_sum_d(zx); zy = wave_sum_d(zy); zz2 = wave_sum_d(zz2);
-    if (cnt == GK) {  // hand the sample covariance (6 distinct entries) to gicp_cov_finish_kernel
-      const double k = (double)GK;
-      const double mx = sx / k, my = sy / k, mz = sz / k;
-      C[0] = xx / k - mx * mx;
-      C[1] = yx / k - my * mx;
-      C[2] = zx / k - mz * mx;
-      C[3] = yy2 / k - my * my;
-      C[4] = zy / k - mz * my;
-      C[5] = zz2 / k - mz * mz;
+    // Lanes 0..19 hold the neighbours in key order (every merge hands lane r the key of rank r): staged in LDS in that order,
+    // their moments are the selecting kernels' (cov_emit: sequential sums, the oracle's order), handed to gicp_cov_finish_kernel.
+    if (__popcll(__ballot(lane < GK && mypos >= 0)) == GK) {
+      if (lane < GK) s_key[wv][lane] = mykey;
+      wave_lds_handover();
+      cov_emit(s_key[wv], s_scratch[wv], cloud, i, cov6, lane);
       have_patch = true;
     }
   }
-  if (!have_patch) C[0] = __longlong_as_double(0x7FF8000000000000ll);  // marker: identity covariance
-  if (lane < 6) cov6[(size_t)i * 6 + lane] = C[lane];
+  if (!have_patch && lane < 6)  // marker: identity covariance
+    cov6[(size_t)i * 6 + lane] = lane == 0 ? __longlong_as_double(0x7FF8000000000000ll) : (lane == 3 || lane == 5 ? 1.0 : 0.0);
   if (!list) return;
   }
 }
@@ -406,12 +383,12 @@ __device__ __forceinline__ void cov_pick20(unsigned long long* buf, unsigned lon
   ranked = c_hi;
 }
 
-// Lanes 0..19 of `top` hold the neighbours in key order: mean and second moments exactly as gicp_cov_kernel forms them -- there nine
-// butterfly sums over the wave (xor 32, 16, 8, 4, 2, 1 with zeros in the lanes above 19) and nine divisions in every lane; here
-// the SAME tree of additions (fp addition commutes, so the butterfly's value in lane 0 is a fixed tree over the 20 terms: the xor-32
-// step adds a zero, the xor-16 step pairs terms l and l + 16 for l < 4 and adds zeros elsewhere, then 8 + 4 + 2 + 1 pairings) is
-// walked by ONE lane per sum over the terms in LDS, and one lane per covariance entry does its three divisions.  One wave;
-// `scratch`: 189 doubles of LDS (the key list's buffer: the list is dead).
+// Lanes 0..19 of `top` hold the neighbours in key order: mean and second moments (float products widened to double) as the oracle
+// and PCL's computeCovariances form them -- each of the nine sums added from zero ONE TERM AFTER ANOTHER in key order, by one lane
+// over the terms in LDS -- and one lane per covariance entry does its three divisions.  The order matters: where a patch straddles
+// a coordinate plane the terms span many binades and the double sums round (a wave butterfly's sums differed from
+// the oracle's on ~1 point in 10^5: scripts/cov_campaign.py).  One wave; `scratch`: 189 doubles of LDS (the selecting
+// kernels pass the key list's buffer: the list is dead).  gicp_cov_kernel emits through here too.
 __device__ __forceinline__ void cov_emit(const unsigned long long* top, double* scratch, const float4* __restrict__ cloud, int i,
                                          double* __restrict__ cov6, int lane) {
   double* term = scratch;  // [9][20]
@@ -431,13 +408,10 @@ __device__ __forceinline__ void cov_emit(const unsigned long long* top, double* 
   wave_lds_handover();
   if (lane < 9) {
     const volatile double* v = term + lane * GK;  // (volatile: read in the order of use -- all twenty at once cost 40 registers)
-    // a(l) = lane l's value after the xor-32 and xor-16 steps; then c(l) = a(l) + a(l + 8), d(l) = c(l) + c(l + 4),
-    // e(0) = d(0) + d(2), e(1) = d(1) + d(3), sum = e(0) + e(1)
-    auto a = [&](int l) -> double { return (v[l] + 0.0) + (l < 4 ? v[l + 16] + 0.0 : 0.0); };
-    auto d = [&](int l) -> double { return (a(l) + a(l + 8)) + (a(l + 4) + a(l + 12)); };
-    const double e0 = d(0) + d(2);
-    const double e1 = d(1) + d(3);
-    sums[lane] = e0 + e1;
+    double sum = 0.0;
+#pragma unroll
+    for (int l = 0; l < GK; ++l) sum += v[l];
+    sums[lane] = sum;
   }
   wave_lds_handover();
   if (lane < 6) {

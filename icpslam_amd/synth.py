@@ -249,3 +249,25 @@ def make_scan_vs_submap(n_scan: int, n_map: int, seed: int):
     # ground truth that maps `moved` onto the map: P * guess_pose^-1
     T_gt = P @ np.linalg.inv(guess_pose)
     return moved, submap, T_gt
+
+
+def plane_through_origin(n: int, seed: int, half: float = 5.0, noise: float = 0.02) -> np.ndarray:
+    """n points on the tilted plane z = 0.3 x - 0.2 y (+ noise) through the sensor, |x|, |y| <= half: patches near the origin
+    straddle all three coordinate planes, so their moment terms span many binades."""
+    rng = np.random.default_rng(seed)
+    xy = rng.uniform(-half, half, (n, 2))
+    out = np.ones((n, 4), np.float32)
+    out[:, 0], out[:, 1] = xy[:, 0], xy[:, 1]
+    out[:, 2] = 0.3 * xy[:, 0] - 0.2 * xy[:, 1] + rng.normal(0.0, noise, n)
+    return out
+
+
+def wall_through_sensor(n: int, seed: int, length: float = 20.0, noise: float = 0.02) -> np.ndarray:
+    """n points on a wall y ~ 0 (x in [-length, length], z in [-2, 3]) that passes through the sensor: y straddles 0 in every
+    patch, and the normal (~ +-y) is nearly perpendicular to the view ray, so its orientation rests on the last bits."""
+    rng = np.random.default_rng(seed)
+    out = np.ones((n, 4), np.float32)
+    out[:, 0] = rng.uniform(-length, length, n)
+    out[:, 1] = rng.normal(0.0, noise, n)
+    out[:, 2] = rng.uniform(-2.0, 3.0, n)
+    return out

@@ -82,6 +82,9 @@ def lib():
         L.orc_svd3.restype = None
         L.orc_svd3_eigen_u.argtypes = [dp, dp, dp]
         L.orc_svd3_eigen_u.restype = None
+        L.orc_gicp_neighbours.argtypes = [fp, C.c_size_t, C.c_int, ip]
+        L.orc_gicp_normals.argtypes = [fp, C.c_size_t, C.c_int, fp]
+        L.orc_gicp_normals.restype = None
         L.orc_map_create.argtypes = [C.c_double]
         L.orc_map_create.restype = C.c_void_p
         L.orc_map_destroy.argtypes = [C.c_void_p]
@@ -226,6 +229,24 @@ def gicp_covariances(cloud, arith=ARITH_FMA, pcl_order=False) -> np.ndarray:
     if rc != 0:
         raise RuntimeError("orc_gicp_covariances: cloud smaller than k = 20")
     return out.reshape(-1, 3, 3)
+
+
+def gicp_neighbours(cloud, arith=ARITH_FMA) -> np.ndarray:
+    """(n, 20) int32: the neighbours computeCovariances uses, ascending (d2, index); -1 rows at non-finite points."""
+    cloud, pc = _f32(cloud)
+    out = np.full((cloud.shape[0], 20), -1, np.int32)
+    if lib().orc_gicp_neighbours(pc, cloud.shape[0], arith, out.ctypes.data_as(C.POINTER(C.c_int32))) != 0:
+        raise RuntimeError("orc_gicp_neighbours: fewer than k = 20 finite points")
+    return out
+
+
+def gicp_normals(cloud, arith=ARITH_FMA) -> np.ndarray:
+    """(n, 4) float32: P2PLANE's estimated normals -- the raw covariance's smallest singular direction (U's third column) in
+    float, turned towards (0, 0, 0); (NaN, NaN, NaN, 0) at non-finite points and everywhere in a cloud of < 20 finite points."""
+    cloud, pc = _f32(cloud)
+    out = np.empty((cloud.shape[0], 4), np.float32)
+    lib().orc_gicp_normals(pc, cloud.shape[0], arith, out.ctypes.data_as(C.POINTER(C.c_float)))
+    return out
 
 
 def svd3_eigen_u(A):

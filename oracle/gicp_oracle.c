@@ -195,34 +195,44 @@ void orc_svd3_eigen_u(const double A[9], double U[9], double sv[3]) {
 /* ------------------------------------------------------------------------------------------ */
 /* computeCovariances                                                                          */
 /* ------------------------------------------------------------------------------------------ */
+/* The 20 nearest neighbours of cloud[i] (ascending (d2, index): nearestKSearch's output) and their raw sample covariance, row-major,
+ * both triangles: the moments are added ONE AFTER ANOTHER in that order -- PCL's loop -- each a float * float product rounded to
+ * float and widened to double.  Their order matters where the products span many binades (a patch straddling a coordinate
+ * plane): a parallel implementation adds them in the same order. */
+static void raw_covariance(const void* tree, const float* cloud, size_t i, int32_t idx[GICP_K], double cov[9]) {
+  float d2[GICP_K];
+  orc_kd_knn(tree, cloud + 4 * i, GICP_K, idx, d2);
+  double mean[3] = {0, 0, 0};
+  for (int e = 0; e < 9; ++e) cov[e] = 0.0;
+  for (int j = 0; j < GICP_K; ++j) {
+    const float* pt = cloud + 4 * (size_t)idx[j];
+    mean[0] += pt[0];
+    mean[1] += pt[1];
+    mean[2] += pt[2];
+    /* float * float products (rounded to float), accumulated in double -- as the C++ expression evaluates */
+    cov[0] += (double)(pt[0] * pt[0]);
+    cov[3] += (double)(pt[1] * pt[0]);
+    cov[4] += (double)(pt[1] * pt[1]);
+    cov[6] += (double)(pt[2] * pt[0]);
+    cov[7] += (double)(pt[2] * pt[1]);
+    cov[8] += (double)(pt[2] * pt[2]);
+  }
+  for (int a = 0; a < 3; ++a) mean[a] /= (double)GICP_K;
+  for (int k = 0; k < 3; ++k)
+    for (int l = 0; l <= k; ++l) {
+      cov[3 * k + l] /= (double)GICP_K;
+      cov[3 * k + l] -= mean[k] * mean[l];
+      cov[3 * l + k] = cov[3 * k + l];
+    }
+}
+
 int orc_gicp_covariances_ex(const float* cloud, size_t n, int arith, int pcl_order, double* cov_out /* n x 9 row-major */) {
   if (n < GICP_K) return -1; /* PCL: "Number or points in cloud is less than k_correspondences_" */
   void* tree = orc_kd_build(cloud, n, arith);
   int32_t idx[GICP_K];
-  float d2[GICP_K];
   for (size_t i = 0; i < n; ++i) {
-    orc_kd_knn(tree, cloud + 4 * i, GICP_K, idx, d2);
-    double mean[3] = {0, 0, 0}, cov[9] = {0};
-    for (int j = 0; j < GICP_K; ++j) {
-      const float* pt = cloud + 4 * (size_t)idx[j];
-      mean[0] += pt[0];
-      mean[1] += pt[1];
-      mean[2] += pt[2];
-      /* float * float products (rounded to float), accumulated in double -- as the C++ expression evaluates */
-      cov[0] += (double)(pt[0] * pt[0]);
-      cov[3] += (double)(pt[1] * pt[0]);
-      cov[4] += (double)(pt[1] * pt[1]);
-      cov[6] += (double)(pt[2] * pt[0]);
-      cov[7] += (double)(pt[2] * pt[1]);
-      cov[8] += (double)(pt[2] * pt[2]);
-    }
-    for (int a = 0; a < 3; ++a) mean[a] /= (double)GICP_K;
-    for (int k = 0; k < 3; ++k)
-      for (int l = 0; l <= k; ++l) {
-        cov[3 * k + l] /= (double)GICP_K;
-        cov[3 * k + l] -= mean[k] * mean[l];
-        cov[3 * l + k] = cov[3 * k + l];
-      }
+    double cov[9];
+    raw_covariance(tree, cloud, i, idx, cov);
     double U[9], s[3];
     orc_svd3_eigen_u(cov, U, s);
     /* cov = sum_k v_k u_k u_k^T, v = (1, 1, epsilon).  The lower triangle is computed -- entry (r, c) = sum_k (v_k u_rk) u_ck,
@@ -258,6 +268,61 @@ int orc_gicp_covariances_ex(const float* cloud, size_t n, int arith, int pcl_ord
 
 int orc_gicp_covariances(const float* cloud, size_t n, int arith, double* cov_out) {
   return orc_gicp_covariances_ex(cloud, n, arith, 0, cov_out);
+}
+
+static size_t count_finite(const float* cloud, size_t n) {
+  size_t m = 0;
+  for (size_t i = 0; i < n; ++i) m += isfinite(cloud[4 * i]) && isfinite(cloud[4 * i + 1]) && isfinite(cloud[4 * i + 2]);
+  return m;
+}
+
+int orc_gicp_neighbours(const float* cloud, size_t n, int arith, int32_t* idx_out) {
+  if (count_finite(cloud, n) < GICP_K) return -1;
+  void* tree = orc_kd_build(cloud, n, arith);
+  double cov[9];
+  for (size_t i = 0; i < n; ++i) {
+    if (!(isfinite(cloud[4 * i]) && isfinite(cloud[4 * i + 1]) && isfinite(cloud[4 * i + 2]))) {
+      for (int j = 0; j < GICP_K; ++j) idx_out[GICP_K * i + j] = -1;
+      continue;
+    }
+    raw_covariance(tree, cloud, i, idx_out + GICP_K * i, cov);
+  }
+  orc_kd_free(tree);
+  return 0;
+}
+
+/* The point-to-plane mode's estimated normals: U's third column of the RAW covariance (the direction computeCovariances scales
+ * by epsilon), rounded to float and turned towards the viewpoint (0, 0, 0) as pcl::flipNormalTowardsViewpoint does in float:
+ * v = 0 - p, cos = (vx nx + vy ny) + vz nz, every operation rounded (nothing contracted), flipped when cos < 0. */
+void orc_gicp_normals(const float* cloud, size_t n, int arith, float* out /* n x 4 */) {
+  const float qnan = nanf("");
+  for (size_t i = 0; i < n; ++i) {
+    out[4 * i] = out[4 * i + 1] = out[4 * i + 2] = qnan;
+    out[4 * i + 3] = 0.0f;
+  }
+  if (count_finite(cloud, n) < GICP_K) return;
+  void* tree = orc_kd_build(cloud, n, arith);
+  int32_t idx[GICP_K];
+  for (size_t i = 0; i < n; ++i) {
+    const float* p = cloud + 4 * i;
+    if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]))) continue;
+    double cov[9], U[9], s[3];
+    raw_covariance(tree, cloud, i, idx, cov);
+    orc_svd3_eigen_u(cov, U, s);
+    float nx = (float)U[2], ny = (float)U[5], nz = (float)U[8];
+    const float vx = 0.0f - p[0], vy = 0.0f - p[1], vz = 0.0f - p[2];
+    const float xy = vx * nx + vy * ny;
+    const float cos_theta = xy + vz * nz;
+    if (cos_theta < 0.0f) {
+      nx = -nx;
+      ny = -ny;
+      nz = -nz;
+    }
+    out[4 * i] = nx;
+    out[4 * i + 1] = ny;
+    out[4 * i + 2] = nz;
+  }
+  orc_kd_free(tree);
 }
 
 /* ------------------------------------------------------------------------------------------ */

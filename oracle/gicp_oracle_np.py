@@ -92,6 +92,32 @@ def covariances(cloud):
     return np.einsum("k,nrk,nck->nrc", v, U, U)
 
 
+def normals(cloud):
+    """(n, 4) float32: the point-to-plane mode's estimated normals -- the smallest singular direction of each finite point's raw
+    20-NN covariance (neighbours among the finite points), rounded to float32 and turned towards the viewpoint (0, 0, 0) as
+    pcl::flipNormalTowardsViewpoint does: cos = (vx nx + vy ny) + vz nz in float32 with v = 0 - p, flipped when cos < 0.
+    (NaN, NaN, NaN, 0) at non-finite points and at every point of a cloud with fewer than 20 finite points."""
+    p32 = np.ascontiguousarray(cloud[:, :3], f32)
+    out = np.zeros((p32.shape[0], 4), f32)
+    out[:, :3] = np.nan
+    fin = np.flatnonzero(np.isfinite(p32).all(axis=1))
+    if fin.size < K_CORR:
+        return out
+    pts = p32[fin]
+    _, nbr = cKDTree(pts.astype(np.float64)).query(pts.astype(np.float64), k=K_CORR)
+    q = pts[nbr]                                                       # (m, 20, 3) float32
+    mean = q.astype(np.float64).sum(axis=1) / K_CORR
+    cov = (q[:, :, :, None] * q[:, :, None, :]).astype(np.float64).sum(axis=1) / K_CORR - mean[:, :, None] * mean[:, None, :]
+    U, _, _ = np.linalg.svd(cov)
+    n = U[:, :, 2].astype(f32)
+    v = (f32(0) - pts).astype(f32)
+    cos = ((v[:, 0] * n[:, 0]).astype(f32) + (v[:, 1] * n[:, 1]).astype(f32)).astype(f32)
+    cos = (cos + (v[:, 2] * n[:, 2]).astype(f32)).astype(f32)
+    n[cos < 0] = -n[cos < 0]
+    out[fin, :3] = n
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the state vector x = (tx, ty, tz, roll, pitch, yaw)
 # ---------------------------------------------------------------------------------------------------------------------

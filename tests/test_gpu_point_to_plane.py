@@ -1,6 +1,6 @@
 """Point-to-plane ICP (method P2PLANE: pcl::IterativeClosestPointWithNormals + TransformationEstimationPointToPlaneLLS) on the device.
 
-The restatements are written here, from the oracle's pieces: its covariances (the normals), its nearest neighbours and its float32
+The restatements are written here, from the oracle's pieces: its normals (oracle.gicp_normals), its nearest neighbours and its float32
 transform (the reduction), and the point-to-point restatement's DefaultConvergenceCriteria (the loop).  Parity against PCL binaries is
 unpinned, as for every other mode."""
 import os
@@ -29,9 +29,11 @@ def _ctx(**kw):
 
 # ---- normals ---------------------------------------------------------------------------------------------------------------------
 def _check_normals(cloud, nrm, gicp_cov):
-    """nrm against the oracle's covariances (finite points: I - C = (1 - eps) n n^T) and the orientation rule; NaN exactly where the
-    covariance kernels write their identity marker (gicp_cov: the device's GICP covariances, C == I bit for bit), which is where
-    the point is not finite (the oracle computes a covariance there: it is compared on finite points only)."""
+    """nrm against the oracle's normals bit for bit (direction and orientation: oracle.gicp_normals, itself pinned to a NumPy
+    restatement in tests/test_oracle.py), the oracle's covariances (finite points: I - C = (1 - eps) n n^T) and the orientation
+    rule; NaN exactly where the covariance kernels write their identity marker (gicp_cov: the device's GICP covariances, C == I bit
+    for bit), which is where the point is not finite (the oracle computes a covariance there: it is compared on finite points only)."""
+    assert np.array_equal(nrm.view(np.uint32), oracle.gicp_normals(cloud).view(np.uint32))
     finite = np.isfinite(cloud[:, :3]).all(axis=1)
     marker = np.all(gicp_cov.reshape(-1, 9) == np.eye(3).reshape(9), axis=1)
     nan = np.isnan(nrm[:, :3]).any(axis=1)
@@ -65,6 +67,21 @@ def test_normals_match_the_oracle_covariances():
         assert 15000 < vox.shape[0] < 40000 and not np.isfinite(raw).all()
 
 
+def test_normals_on_the_wall_through_the_sensor_and_at_the_origin():
+    """A wall y ~ 0 through the sensor: the normal (~ +-y) is nearly perpendicular to the view ray, so the flip depends on the last
+    bits of U, and the moment sums round (their order shows); a point exactly at the viewpoint has cos = 0 and is never flipped;
+    a plane through the origin.  Bit for bit the oracle's normals."""
+    wall = synth.wall_through_sensor(40000, seed=2)
+    wall[123, :3] = 0.0
+    plane = synth.plane_through_origin(40000, seed=3)
+    plane[7, :3] = 0.0
+    with Context(0) as ctx:
+        for cloud in (wall, plane):
+            ctx.set_target(cloud)
+            got = ctx.normals(of_target=True)
+            assert _check_normals(cloud, got, ctx.gicp_covariances(of_target=True)) == cloud.shape[0]
+
+
 def test_normals_of_a_cloud_with_fewer_than_20_finite_points_are_nan():
     cloud = synth.make_pair(40, 40, seed=2)[0]
     cloud[::2, 0] = np.nan                                             # 20 of 40 non-finite: 20 finite points left, still enough
@@ -74,6 +91,7 @@ def test_normals_of_a_cloud_with_fewer_than_20_finite_points_are_nan():
         nrm = ctx.normals()
         cov = ctx.gicp_covariances(of_target=True)
     assert np.isnan(nrm[:, :3]).all()
+    assert np.array_equal(nrm.view(np.uint32), oracle.gicp_normals(cloud).view(np.uint32))
     assert np.all(cov == np.eye(3))                                    # every point carries GICP's identity marker
 
 
@@ -190,7 +208,7 @@ def test_alignment_matches_the_restatement(n):
             ctx.set_target(tgt)
             ctx.set_source(src)
             got = ctx.align()
-            ref = restated_align(src, tgt, ctx.normals())
+            ref = restated_align(src, tgt, oracle.gicp_normals(tgt))
             _same(got, ref)
             sup = _supplied_normals(tgt)
             ctx.set_target_normals(sup)
@@ -203,7 +221,7 @@ def test_alignment_at_200k():
         ctx.set_target(tgt)
         ctx.set_source(src)
         got = ctx.align(want_fitness=True)
-        _same(got, restated_align(src, tgt, ctx.normals()))
+        _same(got, restated_align(src, tgt, oracle.gicp_normals(tgt)))
         assert np.isfinite(got["fitness"])
 
 

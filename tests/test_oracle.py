@@ -373,3 +373,35 @@ def test_gicp_summation_order_sensitivity():
     worst_exact = max(r[0][1] for r in res)
     worst_yard = max(r[1][1] for r in res)
     assert worst_exact <= max(3.0 * worst_yard, 1e-3), (worst_exact, worst_yard)
+
+
+# ---- P2PLANE's estimated normals: two restatements ----------------------------------------------------------------------------
+def test_gicp_normals_two_restatements_agree():
+    """oracle.gicp_normals (gicp_oracle.c: own kd-tree, sequential moments, Eigen's Jacobi SVD) against gicp_oracle_np.normals
+    (SciPy kd-tree, LAPACK SVD): the same direction to 1e-6 and the same orientation wherever the flip's cosine clearly exceeds
+    its rounding; NaN at non-finite points, neighbours among the finite ones; all NaN below 20 finite points."""
+    from oracle import gicp_oracle_np as gnp
+    tgt = synth.make_pair(10, 4000, seed=6)[1]
+    tgt[::401, 1] = np.nan
+    wall = synth.wall_through_sensor(3000, seed=2)
+    wall[0, :3] = 0.0                                          # a point exactly at the viewpoint: cos = 0, never flipped
+    for cloud in (tgt, wall, synth.plane_through_origin(3000, seed=3)):
+        a, b = oracle.gicp_normals(cloud), gnp.normals(cloud)
+        fin = np.isfinite(cloud[:, :3]).all(axis=1)
+        assert a.shape == b.shape == cloud.shape and (a[:, 3] == 0).all() and (b[:, 3] == 0).all()
+        assert np.isnan(a[~fin, :3]).all() and np.isnan(b[~fin, :3]).all() and np.isfinite(a[fin, :3]).all()
+        na, nb = a[fin, :3].astype(np.float64), b[fin, :3].astype(np.float64)
+        assert np.abs(np.linalg.norm(na, axis=1) - 1).max() <= 1e-6
+        assert np.minimum(np.abs(na - nb).max(axis=1), np.abs(na + nb).max(axis=1)).max() <= 1e-6
+        p = cloud[fin, :3].astype(np.float64)
+        clear = np.abs((-p * na).sum(axis=1)) > 1e-5 * np.maximum(np.linalg.norm(p, axis=1), 1.0)
+        assert clear.mean() > 0.5
+        assert ((na * nb).sum(axis=1)[clear] > 0).all()
+        assert ((-p * na).sum(axis=1)[clear] > 0).all()       # turned towards (0, 0, 0)
+    few = tgt[:40].copy()
+    few[::2, 0] = np.nan
+    few[1, 2] = np.inf                                         # 19 finite points: no neighbourhood anywhere
+    for out in (oracle.gicp_normals(few), gnp.normals(few)):
+        assert np.isnan(out[:, :3]).all() and (out[:, 3] == 0).all()
+    few[1, 2] = 1.0                                            # 20: every finite point has one
+    assert np.isfinite(oracle.gicp_normals(few)[~np.isnan(few[:, 0]), :3]).all()
