@@ -9,7 +9,8 @@
 // math library differs from both.  The arithmetic contract therefore says: these four are the CORRECTLY
 // ROUNDED functions.  The oracle computes them in binary128 (libquadmath) and rounds once; this file computes them in
 // double-double arithmetic:
-//   x = k * (pi / 256) + t, |t| <= pi / 512   (Cody-Waite reduction: pi / 256 in three parts, k * part exact for |k| < 2^20)
+//   x = k * (pi / 256) + t, |t| <= pi / 512   (Cody-Waite reduction: pi / 256 in three parts, k * part exact for |k| < 2^20;
+//                                             beyond, |x| > ~12868, in four parts exact for |k| < 2^26)
 //   sin t = t + t^3 P(t^2), cos t = 1 - (t^2 / 2 - t^4 Q(t^2))   (the small corrections in float64: they are < 2^-15 of the result)
 //   sin x, cos x from sin / cos (i pi / 256) (table, double-double) by the addition theorems, in double-double
 // with a relative error below 2^-68 before the one final rounding: the result is the correctly rounded one unless the exact
@@ -74,10 +75,19 @@ ICPGPU_HDI inline void sincos_cr_with(const double (*kTable)[4], double x, doubl
   const double kd = __builtin_rint(x * kInvStep);
   const int k = (int)kd;
   // t = x - k * pi / 256 as a double-double: the first product is exact, so is the first difference
-  const double t1 = x - kd * kStep1;
-  DDv t = two_sum(t1, -(kd * kStep2));
-  t.lo -= kd * kStep3;
-  t = two_sum(t.hi, t.lo);
+  DDv t;
+  if (kd > -1048576.0 && kd < 1048576.0) {
+    const double t1 = x - kd * kStep1;
+    t = two_sum(t1, -(kd * kStep2));
+    t.lo -= kd * kStep3;
+    t = two_sum(t.hi, t.lo);
+  } else {  // |k| >= 2^20: k * kStep1 is no longer exact; pi / 256 in four parts, the first three products exact
+    const double t1 = x - kd * kWide1;
+    t = two_sum(t1, -(kd * kWide2));
+    DDv u = two_sum(t.hi, -(kd * kWide3));
+    u.lo += t.lo - kd * kWide4;
+    t = two_sum(u.hi, u.lo);
+  }
   // sin t, cos t
   const DDv u = two_prod(t.hi, t.hi);
   const double u1 = u.hi;

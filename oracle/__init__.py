@@ -19,6 +19,7 @@ NN_KDTREE, NN_BRUTE = 0, 1
 PREC_F64, PREC_PCL_F32 = 0, 1
 ARITH_FMA, ARITH_FLANN = 0, 1
 GICP_SUMS_EXACT, GICP_SUMS_SEQUENTIAL, GICP_SUMS_SEQUENTIAL_REVERSED, GICP_SUMS_SMOOTH = 0, 1, 2, 3
+P2PLANE_SUMS_EXACT, P2PLANE_SUMS_SEQUENTIAL, P2PLANE_SUMS_ABS = 0, 1, 2
 STATE_NAMES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE",
                5: "NO_CORRESPONDENCES"}
 
@@ -44,9 +45,15 @@ class IterTrace(C.Structure):
                 ("n_corr", C.c_uint), ("mse", C.c_double)]
 
 
+class P2planeTrace(C.Structure):
+    _fields_ = [("final", C.c_double * 16), ("Tk", C.c_double * 16), ("sums", C.c_double * 29), ("n_corr", C.c_uint),
+                ("mse", C.c_double)]
+
+
 def build(force: bool = False) -> str:
     """Compile oracle/liboracle.so with the committed Makefile (gcc only)."""
-    srcs = [os.path.join(_HERE, f) for f in ("icp_oracle.c", "gicp_oracle.c", "map_oracle.c", "icp_oracle.h", "Makefile")]
+    srcs = [os.path.join(_HERE, f) for f in ("icp_oracle.c", "gicp_oracle.c", "map_oracle.c", "p2plane_oracle.c", "icp_oracle.h",
+                                            "Makefile")]
     stale = (not os.path.exists(_LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(_LIB_PATH) for s in srcs)
     if force or stale:
@@ -85,6 +92,10 @@ def lib():
         L.orc_gicp_neighbours.argtypes = [fp, C.c_size_t, C.c_int, ip]
         L.orc_gicp_normals.argtypes = [fp, C.c_size_t, C.c_int, fp]
         L.orc_gicp_normals.restype = None
+        L.orc_p2plane_sums.argtypes = [fp, C.c_size_t, fp, fp, fp, ip, fp, C.c_double, C.c_int, dp]
+        L.orc_p2plane_solve.argtypes = [dp, dp]
+        L.orc_p2plane_align.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.POINTER(Params), fp, fp, C.c_int,
+                                        C.POINTER(Result), C.POINTER(P2planeTrace)]
         L.orc_map_create.argtypes = [C.c_double]
         L.orc_map_create.restype = C.c_void_p
         L.orc_map_destroy.argtypes = [C.c_void_p]
@@ -211,6 +222,66 @@ def icp_align(src, tgt, params: Params | None = None, guess=None, want_cloud=Fal
     return dict(T=res.matrix(), converged=bool(res.converged), iterations=int(res.iterations),
                 state=int(res.convergence_state), n_corr=int(res.n_correspondences), mse=float(res.mse_last),
                 fitness=float(res.fitness), cloud=out, trace=tr)
+
+
+def p2plane_sums(src, tgt, normals, T, idx, d2, max_dist, mode=P2PLANE_SUMS_EXACT) -> np.ndarray:
+    """(29,) float64: n, sum d2, the upper triangle of A^T A over (a, b, c, nx, ny, nz) row by row, A^T r over the pairs
+    (idx >= 0, (double)d2 <= max_dist^2) of T * src and tgt[idx].  mode EXACT: each sum rounded
+    once from the exact sum of its terms; SEQUENTIAL: PCL's float64 loop in source order; ABS: exact sums of |term|."""
+    src, ps = _f32(src)
+    tgt, pt = _f32(tgt)
+    nrm, pn = _f32(normals)
+    assert nrm.shape[0] == tgt.shape[0]
+    Tc, pT = _f32(_colmajor(T))
+    idx = np.ascontiguousarray(idx, np.int32)
+    d2 = np.ascontiguousarray(d2, np.float32)
+    sums = np.zeros(29, np.float64)
+    if lib().orc_p2plane_sums(ps, src.shape[0], pt, pn, pT, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                              d2.ctypes.data_as(C.POINTER(C.c_float)), float(max_dist), int(mode),
+                              sums.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+        raise MemoryError("orc_p2plane_sums")
+    return sums
+
+
+def p2plane_solve(sums):
+    """The incremental transform (4x4 float64) from the 29 sums, or None for a singular system."""
+    sums = np.ascontiguousarray(sums, np.float64)
+    assert sums.shape == (29,)
+    Tk = np.zeros(16, np.float64)
+    if lib().orc_p2plane_solve(sums.ctypes.data_as(C.POINTER(C.c_double)), Tk.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+        return None
+    return Tk.reshape(4, 4).T.copy()
+
+
+def p2plane_align(src, tgt, params: Params | None = None, guess=None, normals=None, want_cloud=False, want_fitness=False,
+                  trace=True):
+    """pcl::IterativeClosestPointWithNormals::align (oracle/p2plane_oracle.c); normals None: oracle.gicp_normals(tgt).
+    Returns icp_align's dict; trace: per completed iteration dict(final = the transform BEFORE the step, Tk, sums, n_corr, mse)."""
+    params = params or default_params()
+    src, ps = _f32(src)
+    tgt, pt = _f32(tgt)
+    pn = None
+    if normals is not None:
+        nrm, pn = _f32(normals)
+        assert nrm.shape[0] == tgt.shape[0]
+    res = Result()
+    out = np.empty_like(src) if want_cloud else None
+    tr = (P2planeTrace * max(1, params.max_iterations))() if trace else None
+    g = None
+    if guess is not None:
+        gc, g = _f32(_colmajor(guess))
+    rc = lib().orc_p2plane_align(ps, src.shape[0], pt, tgt.shape[0], pn, C.byref(params), g,
+                                 out.ctypes.data_as(C.POINTER(C.c_float)) if out is not None else None,
+                                 int(want_fitness), C.byref(res), tr)
+    if rc != 0:
+        raise RuntimeError(f"orc_p2plane_align rc={rc}")
+    steps = None
+    if trace:
+        steps = [dict(final=np.array(t.final).reshape(4, 4).T.copy(), Tk=np.array(t.Tk).reshape(4, 4).T.copy(),
+                      sums=np.array(t.sums), n_corr=int(t.n_corr), mse=float(t.mse)) for t in tr[: res.iterations]]
+    return dict(T=res.matrix(), converged=bool(res.converged), iterations=int(res.iterations),
+                state=int(res.convergence_state), n_corr=int(res.n_correspondences), mse=float(res.mse_last),
+                fitness=float(res.fitness), cloud=out, trace=steps)
 
 
 def voxel_grid(cloud, leaf: float):

@@ -403,7 +403,9 @@ static void kd_nearest(const kd_tree* t, const float* q, int32_t* idx, float* d2
     mind += offs[a] * offs[a];
   }
   kd_search_rec(&Q, 0, mind, offs);
-  *idx = Q.best_idx == INT32_MAX ? -1 : Q.best_idx; /* non-finite query: no neighbour (like the brute-force scan) */
+  /* non-finite query (every d2 infinite, or NaN): no neighbour, like the brute-force scan -- the tie rule above would otherwise
+   * take an index at d2 = inf, e.g. for a point with an infinite coordinate moved by a transform that is not the identity */
+  *idx = (Q.best_idx == INT32_MAX || !(Q.best < INFINITY)) ? -1 : Q.best_idx;
   *d2 = Q.best;
 }
 

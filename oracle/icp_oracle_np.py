@@ -88,3 +88,180 @@ def icp_align(src, tgt, max_iterations=10, transformation_epsilon=1e-6, max_corr
         d, _ = tree.query(X.astype(np.float64), k=1)
         out["fitness"] = float((d * d).mean())
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# point-to-plane (pcl::IterativeClosestPointWithNormals + TransformationEstimationPointToPlaneLLS), the second restatement
+# of oracle/p2plane_oracle.c: float32 terms from NumPy casts, math.fsum for the exact sums, the LU in plain Python floats,
+# sin / cos from mpmath at 120 bits rounded once.  Correspondences from the library kd-tree, re-ranked by the float32 key.
+# ---------------------------------------------------------------------------------------------------------------------
+def _d2_f32(q, p):
+    """fma(dz, dz, fma(dy, dy, dx dx)) in float32 (a float product is exact in float64; the cast is the fma's rounding, which
+    only an exact float32 midpoint could double-round)"""
+    f = np.float32
+    dx, dy, dz = ((q[:, k] - p[:, k]).astype(f).astype(np.float64) for k in range(3))
+    a = (dx * dx).astype(f).astype(np.float64)
+    a = (dy * dy + a).astype(f).astype(np.float64)
+    return (dz * dz + a).astype(f)
+
+
+def nn_f32(X, tgt, tree=None, fin=None, k=8):
+    """(idx, d2): the lowest (float32 d2, index) among the k nearest in float64; -1 for non-finite queries or no target"""
+    n = X.shape[0]
+    idx = np.full(n, -1, np.int64)
+    d2 = np.full(n, np.inf, np.float32)
+    if fin is None:
+        fin = np.flatnonzero(np.isfinite(tgt).all(axis=1))
+    if n == 0 or fin.size == 0:
+        return idx, d2
+    if tree is None:
+        tree = cKDTree(tgt[fin].astype(np.float64), leafsize=15)
+    ok = np.isfinite(X).all(axis=1)
+    kk = min(k, fin.size)
+    _, jj = tree.query(X[ok].astype(np.float64), k=kk)
+    jj = fin[np.asarray(jj).reshape(-1, kk)]
+    cand = np.stack([_d2_f32(tgt[jj[:, c]], X[ok]) for c in range(kk)], axis=1)
+    best = cand.min(axis=1)
+    jbest = np.where(cand == best[:, None], jj, np.iinfo(np.int64).max).min(axis=1)
+    idx[ok], d2[ok] = jbest, best
+    return idx, d2
+
+
+def p2plane_terms(s, d, n):
+    """The float32 terms of estimateRigidTransformation for pairs (s = T source, d = target, n = normal): (m, 29) float64
+    columns 2.. (columns 0, 1 left to the caller)"""
+    f = np.float32
+    sx, sy, sz = (s[:, k].astype(f) for k in range(3))
+    nx, ny, nz = (n[:, k].astype(f) for k in range(3))
+    dx, dy, dz = (d[:, k].astype(f) for k in range(3))
+    a = (nz * sy) - (ny * sz)
+    b = (nx * sz) - (nz * sx)
+    c = (ny * sx) - (nx * sy)
+    r = ((nx * dx) + (ny * dy)) + (nz * dz)
+    r = ((r - (nx * sx)) - (ny * sy)) - (nz * sz)
+    W = np.stack([a, b, c, nx, ny, nz], axis=1).astype(np.float64)
+    iu = np.triu_indices(6)
+    return np.concatenate([(W[:, :, None] * W[:, None, :])[:, iu[0], iu[1]], W * r.astype(np.float64)[:, None]], axis=1)
+
+
+def p2plane_sums(X, tgt, nrm, idx, d2, max_dist):
+    import math
+    keep = (idx >= 0) & (d2.astype(np.float64) <= max_dist * max_dist)
+    j = idx[keep]
+    n = nrm[j, :3]
+    fin = np.isfinite(n).all(axis=1)
+    terms = p2plane_terms(X[keep][fin], tgt[j][fin], n[fin])
+    sums = [float(keep.sum()), math.fsum(d2[keep].astype(np.float64))]
+    sums += [math.fsum(terms[:, k]) for k in range(27)]
+    return np.array(sums)
+
+
+def p2plane_solve(sums):
+    """symmetrise, Eigen's PartialPivLU (first of equal pivots), inverse column by column, x = inv b, PCL's
+    constructTransformationMatrix with correctly rounded sin / cos; None when singular"""
+    import mpmath
+    A = [[0.0] * 6 for _ in range(6)]
+    it = iter(sums[2:23])
+    for i in range(6):
+        for j in range(i, 6):
+            A[i][j] = A[j][i] = float(next(it))
+    b = [float(v) for v in sums[23:29]]
+    perm = list(range(6))
+    for k in range(6):
+        p, m = k, abs(A[k][k])
+        for i in range(k + 1, 6):
+            if abs(A[i][k]) > m:
+                p, m = i, abs(A[i][k])
+        if not m > 0.0:
+            return None
+        A[k], A[p] = A[p], A[k]
+        perm[k], perm[p] = perm[p], perm[k]
+        for i in range(k + 1, 6):
+            A[i][k] = A[i][k] / A[k][k]
+            for j in range(k + 1, 6):
+                A[i][j] = A[i][j] - A[i][k] * A[k][j]
+    inv = [[0.0] * 6 for _ in range(6)]
+    for col in range(6):
+        y = [1.0 if perm[i] == col else 0.0 for i in range(6)]
+        for i in range(6):
+            for j in range(i):
+                y[i] = y[i] - A[i][j] * y[j]
+        for i in reversed(range(6)):
+            for j in range(i + 1, 6):
+                y[i] = y[i] - A[i][j] * y[j]
+            y[i] = y[i] / A[i][i]
+        for i in range(6):
+            inv[i][col] = y[i]
+    x = []
+    for i in range(6):
+        acc = 0.0
+        for j in range(6):
+            acc = acc + inv[i][j] * b[j]
+        if not np.isfinite(acc):
+            return None
+        x.append(acc)
+    with mpmath.workprec(120):
+        sc = [(float(mpmath.sin(mpmath.mpf(v))), float(mpmath.cos(mpmath.mpf(v)))) if abs(v) <= 524288.0
+              else (float(np.sin(v)), float(np.cos(v))) for v in x[:3]]
+    (sa, ca), (sb, cb), (sg, cg) = sc
+    return np.array([[cg * cb, -sg * ca + cg * sb * sa, sg * sa + cg * sb * ca, x[3]],
+                     [sg * cb, cg * ca + sg * sb * sa, -cg * sa + sg * sb * ca, x[4]],
+                     [-sb, cb * sa, cb * ca, x[5]],
+                     [0.0, 0.0, 0.0, 1.0]])
+
+
+def p2plane_align(src, tgt, nrm, max_iterations=10, transformation_epsilon=1e-6, max_correspondence_distance=1.0,
+                  euclidean_fitness_epsilon=-np.finfo(np.float64).max, min_correspondences=3, guess=None,
+                  force_iterations=False, want_fitness=False):
+    """The second restatement of orc_p2plane_align; nrm (n_t, >= 3) the target's normals.  trace entries: final (before the
+    step), Tk, sums, n_corr, mse"""
+    from oracle.gicp_oracle_np import transform_f32
+    src = np.asarray(src, np.float32)
+    tgt = np.asarray(tgt, np.float32)[:, :3]
+    nrm = np.asarray(nrm, np.float32)[:, :3]
+    out = dict(T=np.eye(4, dtype=np.float32), converged=False, iterations=0, state=NOT_CONVERGED, n_corr=0, mse=0.0,
+               fitness=float("nan"), trace=[])
+    if tgt.shape[0] == 0:
+        return out
+    fin = np.flatnonzero(np.isfinite(tgt).all(axis=1))
+    tree = cKDTree(tgt[fin].astype(np.float64), leafsize=15) if fin.size else None
+    final = np.eye(4) if guess is None else np.asarray(guess, np.float32).astype(np.float64)
+    mse_prev = np.finfo(np.float64).max
+    nr, converged, state, n_c, mse = 0, False, NOT_CONVERGED, 0, 0.0
+    while True:
+        X = transform_f32(src, final.astype(np.float32))
+        idx, d2 = nn_f32(X, tgt, tree, fin)
+        sums = p2plane_sums(X, tgt, nrm, idx, d2, max_correspondence_distance)
+        n_c = int(sums[0])
+        if n_c < min_correspondences:
+            state, converged = NO_CORRESPONDENCES, False
+            break
+        Tk = p2plane_solve(sums)
+        if Tk is None:
+            state, converged = NOT_CONVERGED, False
+            break
+        mse = sums[1] / sums[0]
+        out["trace"].append(dict(final=final.copy(), Tk=Tk, sums=sums, n_corr=n_c, mse=mse))
+        final = Tk @ final
+        nr += 1
+        if nr >= max_iterations:
+            converged, state = True, ITERATIONS
+        elif not force_iterations:
+            cos_angle = 0.5 * (np.trace(Tk[:3, :3]) - 1.0)
+            tsq = float(Tk[:3, 3] @ Tk[:3, 3])
+            if cos_angle >= 1.0 - transformation_epsilon and tsq <= transformation_epsilon:
+                converged, state = True, TRANSFORM
+            elif abs(mse - mse_prev) < 1e-12:
+                converged, state = True, ABS_MSE
+            elif abs(mse - mse_prev) / mse_prev < euclidean_fitness_epsilon:
+                converged, state = True, REL_MSE
+            mse_prev = mse
+        if converged:
+            break
+    out.update(T=final.astype(np.float32), converged=converged, iterations=nr, state=state, n_corr=n_c, mse=mse)
+    if want_fitness:
+        X = transform_f32(src, final.astype(np.float32))
+        _, d2 = nn_f32(X, tgt, tree, fin)
+        ok = np.isfinite(d2)
+        out["fitness"] = float(d2[ok].astype(np.float64).mean()) if ok.any() else float(np.finfo(np.float64).max)
+    return out

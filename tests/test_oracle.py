@@ -405,3 +405,117 @@ def test_gicp_normals_two_restatements_agree():
         assert np.isnan(out[:, :3]).all() and (out[:, 3] == 0).all()
     few[1, 2] = 1.0                                            # 20: every finite point has one
     assert np.isfinite(oracle.gicp_normals(few)[~np.isnan(few[:, 0]), :3]).all()
+
+
+# ---- point-to-plane: oracle/p2plane_oracle.c against oracle/icp_oracle_np.py (p2plane_align) --------------------------------
+P2_CASES = [(s, n) for s, n in zip(range(12), (300, 1000, 3000, 8000) * 3)]
+
+
+@pytest.mark.parametrize("seed,n", P2_CASES)
+def test_p2plane_two_restatements_agree(seed, n):
+    """Iterations, state and n_corr identical, each iteration's EXACT sums equal bit for bit (both round once), T to 1e-9;
+    seeds 0-3 with a guess, 4-7 with euclidean_fitness_epsilon > 0, the even ones with supplied normals."""
+    src, tgt, _ = synth.make_pair(n, n, seed=400 + seed)
+    guess = synth.pose_matrix(0.1, -0.05, 0.02, 0.01, -0.01, 0.02).astype(np.float32) if seed < 4 else None
+    feps = 1e-3 if 4 <= seed < 8 else -np.finfo(np.float64).max
+    nrm = oracle.gicp_normals(tgt)
+    if seed % 2 == 0:
+        nrm[::5, :3] *= np.float32(-2.5)
+        nrm[::13, 2] = np.nan
+    a = oracle.p2plane_align(src, tgt, oracle.default_params(euclidean_fitness_epsilon=feps), guess=guess, normals=nrm,
+                             want_fitness=True)
+    b = onp.p2plane_align(src, tgt, nrm, euclidean_fitness_epsilon=feps, guess=guess, want_fitness=True)
+    assert (a["iterations"], a["state"], a["n_corr"], a["converged"]) == (b["iterations"], b["state"], b["n_corr"], b["converged"])
+    assert a["iterations"] >= 1
+    for x, y in zip(a["trace"], b["trace"]):
+        assert x["n_corr"] == y["n_corr"]
+        assert np.array_equal(x["sums"].view(np.uint64), y["sums"].view(np.uint64))
+        assert np.abs(x["final"] - y["final"]).max() <= 1e-9
+    assert np.abs(a["T"].astype(np.float64) - b["T"]).max() <= 1e-9
+    assert abs(a["mse"] - b["mse"]) <= 1e-12 * a["mse"] and abs(a["fitness"] - b["fitness"]) <= 1e-12 * a["fitness"]
+    if 4 <= seed < 8:
+        assert a["state"] in (oracle_state("REL_MSE"), oracle_state("TRANSFORM"), oracle_state("ABS_MSE"))
+
+
+def oracle_state(name):
+    return {v: k for k, v in oracle.STATE_NAMES.items()}[name]
+
+
+def test_p2plane_rel_mse_is_reached():
+    src, tgt, _ = synth.make_pair(3000, 3000, seed=404)
+    p = oracle.default_params(euclidean_fitness_epsilon=0.05, max_iterations=30)
+    a = oracle.p2plane_align(src, tgt, p)
+    b = onp.p2plane_align(src, tgt, oracle.gicp_normals(tgt), euclidean_fitness_epsilon=0.05, max_iterations=30)
+    assert a["state"] == b["state"] == oracle_state("REL_MSE") and a["iterations"] == b["iterations"]
+
+
+def test_p2plane_sums_modes():
+    """EXACT is order-independent (a permuted source gives the same bits), SEQUENTIAL within its rounding of it, ABS bounds it."""
+    src, tgt, _ = synth.make_pair(20000, 20000, seed=5)
+    nrm = oracle.gicp_normals(tgt)
+    idx, d2 = oracle.nn(src, tgt)
+    ex = oracle.p2plane_sums(src, tgt, nrm, np.eye(4), idx, d2, 1.0)
+    perm = np.random.default_rng(0).permutation(src.shape[0])
+    assert np.array_equal(ex.view(np.uint64), oracle.p2plane_sums(src[perm], tgt, nrm, np.eye(4), idx[perm], d2[perm], 1.0).view(np.uint64))
+    seq = oracle.p2plane_sums(src, tgt, nrm, np.eye(4), idx, d2, 1.0, mode=oracle.P2PLANE_SUMS_SEQUENTIAL)
+    mag = oracle.p2plane_sums(src, tgt, nrm, np.eye(4), idx, d2, 1.0, mode=oracle.P2PLANE_SUMS_ABS)
+    assert ex[0] == seq[0] == mag[0] > 19000
+    assert np.all(np.abs(seq - ex) <= 20000 * 2.0 ** -53 * mag) and np.all(np.abs(ex) <= mag)
+    assert not np.array_equal(seq, ex)                              # (the two orders do round differently here)
+
+
+def test_p2plane_known_answer_identity_and_permutation():
+    for seed in range(3):
+        src, tgt, T_gt = synth.make_known_answer_pair(8000, seed=seed)
+        r = oracle.p2plane_align(src, tgt, oracle.default_params(max_iterations=50))
+        assert dR(r["T"], T_gt) <= 1e-4 and dt(r["T"], T_gt) <= 1e-3, seed
+    src, tgt, _ = synth.make_pair(4000, 4000, seed=9)
+    r = oracle.p2plane_align(tgt, tgt)
+    assert r["converged"] and dR(r["T"], np.eye(4)) <= 1e-6 and dt(r["T"], np.eye(4)) <= 1e-6
+    a = oracle.p2plane_align(src, tgt)
+    perm = np.random.default_rng(1).permutation(src.shape[0])
+    b = oracle.p2plane_align(src[perm], tgt)
+    assert (a["iterations"], a["state"], a["n_corr"]) == (b["iterations"], b["state"], b["n_corr"])
+    assert np.array_equal(a["T"].view(np.uint32), b["T"].view(np.uint32))          # EXACT sums: the same bits in any order
+
+
+def test_p2plane_singular_and_degenerate():
+    src, tgt, _ = synth.make_pair(2000, 2000, seed=2)
+    guess = synth.pose_matrix(0.2, 0.1, 0.0, 0.0, 0.0, 0.05).astype(np.float32)
+    nan = np.full((tgt.shape[0], 4), np.nan, np.float32)
+    for g in (None, guess):
+        r = oracle.p2plane_align(src, tgt, normals=nan, guess=g)
+        assert (r["converged"], r["state"], r["iterations"]) == (False, oracle_state("NOT_CONVERGED"), 0)
+        assert np.array_equal(r["T"], np.eye(4, dtype=np.float32) if g is None else g) and r["n_corr"] > 1000
+    r = oracle.p2plane_align(src[:2], tgt)
+    assert r["state"] == oracle_state("NO_CORRESPONDENCES") and r["iterations"] == 0
+    r = oracle.p2plane_align(src, tgt[:0])
+    assert r["state"] == oracle_state("NOT_CONVERGED") and np.array_equal(r["T"], np.eye(4, dtype=np.float32))
+
+
+def test_p2plane_oracle_matches_golden():
+    g = _golden("p2plane_1k5.npz")
+    for name in ("est", "sup"):
+        nrm = g[f"{name}_nrm"]
+        if name == "est":
+            assert np.array_equal(oracle.gicp_normals(g["tgt"]).view(np.uint32), nrm.view(np.uint32))
+        r = oracle.p2plane_align(g["src"], g["tgt"], guess=g["guess"], normals=nrm, want_fitness=True)
+        assert (r["iterations"], r["state"], r["n_corr"]) == (int(g[f"{name}_iterations"]), int(g[f"{name}_state"]),
+                                                              int(g[f"{name}_n_corr"]))
+        got = np.array([t["sums"] for t in r["trace"]])
+        assert np.array_equal(got.view(np.uint64), g[f"{name}_sums"].view(np.uint64))
+        assert np.abs(r["T"].astype(np.float64) - g[f"{name}_T"]).max() <= 1e-9
+        assert abs(r["fitness"] - float(g[f"{name}_fitness"])) <= 1e-12 * float(g[f"{name}_fitness"])
+
+
+def test_kdtree_gives_no_neighbour_to_an_infinite_point_under_any_transform():
+    """a coordinate of +-inf moved by a transform that is not the identity: every d2 is inf; like the brute-force scan, no
+    neighbour (the kd-tree's tie rule once took one at d2 = inf)"""
+    src, tgt, _ = synth.make_pair(3000, 3000, seed=76)
+    src[5::101, 0] = np.inf
+    src[::97, 1] = np.nan
+    T = synth.pose_matrix(0.3, -0.2, 0.1, 0.01, 0.02, 0.03)
+    a, da = oracle.nn(src, tgt, T)
+    b, db = oracle.nn(src, tgt, T, nn_mode=oracle.NN_BRUTE)
+    assert np.array_equal(a, b) and np.array_equal(da.view(np.uint32), db.view(np.uint32))
+    assert (a[~np.isfinite(src[:, :3]).all(axis=1)] == -1).all()

@@ -1,5 +1,6 @@
 """CPU tests of the point-to-plane mode's boundary (ICPGPU_P2PLANE, C-ABI 1.2): the header, the exports, the shim, and the host
-solve -- (AᵀA)⁻¹Aᵀr by partial-pivot LU, then PCL's constructTransformationMatrix -- against a NumPy restatement."""
+solve -- (AᵀA)⁻¹Aᵀr by partial-pivot LU, then PCL's constructTransformationMatrix -- against a NumPy restatement and, bit for bit,
+against the oracle's (oracle/p2plane_oracle.c)."""
 import ctypes as C
 import os
 import subprocess
@@ -9,6 +10,7 @@ import pytest
 
 from icpslam_amd import _lib, synth
 from icpslam_amd.registration import solve_point_to_plane
+import oracle  # (test infrastructure: the C restatement)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("icpgpu_set_target_normals", "icpgpu_normals", "icpgpu_reduce_point_to_plane", "icpgpu_solve_point_to_plane")
@@ -119,3 +121,93 @@ def test_p2plane_shim_compiles_and_fails_loudly_without_gpu(built, tmp_path):
     tgt.tofile(b)
     r = subprocess.run([str(exe), str(a), "100", str(b), "100", "10"], capture_output=True, text=True)
     assert r.returncode == 3 and "no CPU fallback" in r.stderr
+
+
+# ---- the host solve against the oracle's, bit for bit (PartialPivLU, first of equal pivots, x = inv b in
+# increasing j, constructTransformationMatrix with correctly rounded sin / cos) --------------------------------------------------
+def _sums_of(M, b):
+    M = np.asarray(M, np.float64)
+    return np.concatenate([[100.0, 1.0], M[np.triu_indices(6)], b])
+
+
+def _pinned_systems():
+    rng = np.random.default_rng(11)
+    out = []
+    for _ in range(3000):                                               # random, any scale
+        out.append(rng.normal(size=29) * 10.0 ** rng.uniform(-4, 4, 29))
+    for _ in range(1500):                                               # small integers: equal pivot candidates at every step
+        M = rng.integers(-3, 4, size=(6, 6)).astype(np.float64)
+        out.append(_sums_of(M + M.T, rng.integers(-5, 6, 6)))
+    for _ in range(500):                                                # the largest entry of each column below the diagonal
+        M = rng.uniform(-1, 1, (6, 6))
+        M = M + M.T
+        M[np.arange(6), np.arange(6)[::-1]] = M[np.arange(6)[::-1], np.arange(6)] = 10.0 + rng.uniform(0, 1, 6)
+        out.append(_sums_of(M, rng.normal(size=6)))
+    for k in range(500):                                                # near-singular: rank 5 plus a perturbation of 1e-(8..15)
+        V = rng.normal(size=(5, 6))
+        M = V.T @ V + 10.0 ** -(8 + k % 8) * np.diag(rng.uniform(0.5, 1, 6))
+        out.append(_sums_of(M, rng.normal(size=6) * 1e-3))
+    for k in range(200):                                                # singular: one unknown without information
+        M = rng.normal(size=(6, 6))
+        M = M @ M.T
+        M[k % 6, :] = M[:, k % 6] = 0.0
+        out.append(_sums_of(M, rng.normal(size=6)))
+    for seed in range(6):                                               # the per-iteration sums of real alignments
+        src, tgt, _ = synth.make_pair(4000, 4000, seed=60 + seed)
+        out += [t["sums"] for t in oracle.p2plane_align(src, tgt)["trace"]]
+    return [s for s in out if oracle.p2plane_solve(s) is None or _angles_below_2e19(s)]
+
+
+def _angles_below_2e19(s):
+    """beyond |x| > 2^19 rad DESIGN.md section 3 leaves sin / cos to the platform (never a rotation angle): such systems are
+    left out (a margin: the angles estimated by least squares stay below 4e5 rad)"""
+    A = np.zeros((6, 6))
+    A[np.triu_indices(6)] = s[2:23]
+    x = np.linalg.lstsq(A + np.triu(A, 1).T, s[23:29], rcond=None)[0]
+    return bool(np.abs(x[:3]).max() < 4e5)
+
+
+def _lu_pivots(sums):
+    """(row swaps, steps with an exact tie for the pivot) of the partial-pivot LU restated here (counts only: coverage)."""
+    A = np.zeros((6, 6))
+    A[np.triu_indices(6)] = sums[2:23]
+    A = A + np.triu(A, 1).T
+    swaps = ties = 0
+    for k in range(6):
+        col = np.abs(A[k:, k])
+        if not col.max() > 0:
+            break
+        p = k + int(np.argmax(col))
+        ties += int((col == col.max()).sum() > 1)
+        swaps += p != k
+        A[[k, p]] = A[[p, k]]
+        A[k + 1:, k] /= A[k, k]
+        A[k + 1:, k + 1:] -= np.outer(A[k + 1:, k], A[k, k + 1:])
+    return swaps, ties
+
+
+def test_solve_equals_the_oracle_bit_for_bit(built):
+    systems = _pinned_systems()
+    solved = singular = all_swaps = tied = 0
+    for s in systems:
+        ref = oracle.p2plane_solve(s)
+        got = solve_point_to_plane(s)
+        assert (ref is None) == (got is None), s
+        if ref is None:
+            singular += 1
+            continue
+        assert np.array_equal(got.view(np.uint64), ref.view(np.uint64)), s
+        solved += 1
+        swaps, ties = _lu_pivots(s)
+        all_swaps += swaps >= 5
+        tied += ties > 0
+    assert solved > 5000 and singular >= 200 and all_swaps >= 200 and tied >= 500, (solved, singular, all_swaps, tied)
+
+
+def test_single_plane_is_singular_on_both_sides(built):
+    rng = np.random.default_rng(3)
+    s = np.column_stack([rng.uniform(-5, 5, 300), rng.uniform(-5, 5, 300), np.zeros(300), np.ones(300)]).astype(np.float32)
+    nrm = np.tile(np.array([0, 0, 1, 0], np.float32), (300, 1))
+    sums = oracle.p2plane_sums(s, s, nrm, np.eye(4), np.arange(300), np.zeros(300, np.float32), 1.0)
+    assert sums[0] == 300
+    assert oracle.p2plane_solve(sums) is None and solve_point_to_plane(sums) is None
