@@ -3,9 +3,9 @@
 Only what the hot path needs: csrc/ (HIP kernels + C-ABI, built into libicpgpu.so), the ctypes binding,
 the PCL-Registration-shaped host mirror and the synthetic scan generator.  No CPU fallback.
 """
-from ._lib import GICP, GICP_INNER_EXACT, P2PLANE, GICP_INNER_QUADRATIC, NN_AUTO, NN_BRUTE, NN_GRID, P2P_SVD, STATE_NAMES, IcpGpuError, Params, Profile, Result  # noqa: F401
-from .registration import Context, GeneralizedIterativeClosestPoint, IterativeClosestPoint, IterativeClosestPointWithNormals  # noqa: F401
+from ._lib import GICP, GICP_INNER_EXACT, NDT, P2PLANE, GICP_INNER_QUADRATIC, NN_AUTO, NN_BRUTE, NN_GRID, P2P_SVD, STATE_NAMES, IcpGpuError, Params, Profile, Result  # noqa: F401
+from .registration import Context, GeneralizedIterativeClosestPoint, IterativeClosestPoint, IterativeClosestPointWithNormals, NormalDistributionsTransform  # noqa: F401
 
-__all__ = ["Context", "IterativeClosestPoint", "GeneralizedIterativeClosestPoint", "IterativeClosestPointWithNormals", "IcpGpuError", "Params", "Result",
-           "Profile", "P2P_SVD", "GICP", "P2PLANE", "GICP_INNER_EXACT", "GICP_INNER_QUADRATIC",
+__all__ = ["Context", "IterativeClosestPoint", "GeneralizedIterativeClosestPoint", "IterativeClosestPointWithNormals", "NormalDistributionsTransform", "IcpGpuError", "Params", "Result",
+           "Profile", "P2P_SVD", "GICP", "P2PLANE", "NDT", "GICP_INNER_EXACT", "GICP_INNER_QUADRATIC",
            "NN_AUTO", "NN_BRUTE", "NN_GRID", "STATE_NAMES"]

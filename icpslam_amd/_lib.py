@@ -15,7 +15,7 @@ if os.environ.get("ICPGPU_LIB_PATH"):   # A/B builds of an experiment (scripts/)
     LIB_PATH = os.environ["ICPGPU_LIB_PATH"]
 
 OK, ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_NO_INPUT, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
-P2P_SVD, GICP, P2PLANE = 0, 1, 2
+P2P_SVD, GICP, P2PLANE, NDT = 0, 1, 2, 3
 GICP_INNER_EXACT, GICP_INNER_QUADRATIC = 0, 1
 GICP_SOLVER_NONE, GICP_SOLVER_HOST, GICP_SOLVER_DEVICE, GICP_SOLVER_QUADRATIC = 0, 1, 2, 3
 HEADER_VERSION = 1002          # the icpgpu.h these mirrors were written against (ICPGPU_HEADER_VERSION)
@@ -79,6 +79,8 @@ EXPORTS = [
     "icpgpu_map_set_search", "icpgpu_map_reset", "icpgpu_map_add_points", "icpgpu_map_add_source", "icpgpu_map_size", "icpgpu_map_get_points",
     "icpgpu_map_nn_target", "icpgpu_count_candidates", "icpgpu_count_candidates_read",
     "icpgpu_set_target_normals", "icpgpu_normals", "icpgpu_reduce_point_to_plane", "icpgpu_solve_point_to_plane",
+    "icpgpu_set_ndt_params", "icpgpu_get_ndt_params", "icpgpu_ndt_transformation_probability", "icpgpu_ndt_cells",
+    "icpgpu_ndt_derivatives", "icpgpu_ndt_step",
 ]
 
 _lib = None
@@ -146,6 +148,12 @@ def load():
     L.icpgpu_normals.argtypes = [vp, C.c_int, fp]
     L.icpgpu_reduce_point_to_plane.argtypes = [vp, fp, C.c_double, dp]
     L.icpgpu_solve_point_to_plane.argtypes = [dp, dp]
+    L.icpgpu_set_ndt_params.argtypes = [vp, C.c_double, C.c_double, C.c_double]
+    L.icpgpu_get_ndt_params.argtypes = [vp, dp, dp, dp]
+    L.icpgpu_ndt_transformation_probability.argtypes = [vp, dp]
+    L.icpgpu_ndt_cells.argtypes = [vp, C.c_size_t, fp, dp, dp, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]
+    L.icpgpu_ndt_derivatives.argtypes = [vp, dp, dp]
+    L.icpgpu_ndt_step.argtypes = [dp, dp, C.c_double, C.c_double, dp, dp, fp]
     L.icpgpu_voxel_grid.argtypes = [vp, fp, C.c_size_t, C.c_float, fp, C.POINTER(C.c_size_t)]
     L.icpgpu_voxel_grid_fetch.argtypes = [vp, fp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.icpgpu_voxel_grid_view.argtypes = [vp, fp, C.c_size_t, C.c_float, C.POINTER(fp), C.POINTER(C.c_size_t)]

@@ -241,6 +241,19 @@ struct icpgpu_ctx {
   uint64_t nrm_src_version = 0, nrm_tgt_version = 0;
   GridIndex nrm_grid;
   bool nrm_supplied = false;
+  // NDT mode (icpgpu_ndt.cpp): parameters, the target's cells (cached per target version and resolution; 0 = none), their
+  // scratch, the derivative pass's per-workgroup partials and the last alignment's transformation probability
+  double ndt_resolution = 1.0, ndt_step_size = 0.1, ndt_outlier_ratio = 0.55, ndt_probability = NAN;
+  struct NdtCells {
+    DeviceBuf keys, vals, flags, slots, temp, valid, vslots, ckey, cent, gauss, npts, cell_excess;  // scratch (n-sized)
+    DeviceBuf key, centroid, gauss_c, n_points, stats;                                      // the valid cells, key order
+    uint64_t version = 0;   // target version they were built for
+    double resolution = 0.0;
+    int n_cells = 0;
+    double excess = 0.0;
+    NdtLattice L{};
+  } ndt;
+  DeviceBuf ndt_partials;
   // Per-iteration result mailbox in pinned, mapped host memory: 17 sums + 17 sequence flags.  The final reduction
   // stores straight into it and the host polls the flags -- no copy engine and no stream synchronisation (whose wake-up
   // costs 20-70 us depending on how the process set up the runtime) on the iteration path.
@@ -556,5 +569,7 @@ int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_f
 // x = (A^T A)^-1 A^T r from the 29 sums (partial-pivot LU, float64) -> Tk = constructTransformationMatrix(x); false (Tk = identity)
 // when a pivot is zero or x is not finite
 bool solve_point_to_plane(const double sums[kP2planeTerms], Mat4d& Tk);
+// icpgpu_ndt.cpp
+int align_ndt(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitness, icpgpu_result* res);
 
 }  // namespace icpgpu_impl

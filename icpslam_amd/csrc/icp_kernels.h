@@ -340,6 +340,47 @@ int p2plane_blocks(int n_s);
 hipError_t launch_p2plane_reduce(const float4* src, int n_s, const float4* tgt, const float4* normals, const unsigned long long* keys,
                                  const Xform& T, float thr, double* partials, double* sums_out, unsigned long long* flags,
                                  unsigned long long seq, hipStream_t stream);
+// the p2plane final kernel alone: partials (n_blocks x 29 doubles, block-major) -> 29 sums, fixed order (NDT's derivative pass)
+hipError_t launch_terms29_final(const double* partials, int n_blocks, double* sums_out, unsigned long long* flags, unsigned long long seq,
+                                hipStream_t stream);
+
+// ---- NDT (icp_ndt.hip): pcl::NormalDistributionsTransform's target cells and derivative pass ----------------------------
+static constexpr int kNdtTerms = 29;         // pairs, score, gradient (6), Hessian upper triangle row by row (21)
+static constexpr int kNdtGaussDoubles = 10;  // per valid cell: mean (3), icov xx xy xz yy yz zz (6), pad
+static constexpr int kNdtMinPoints = 6;      // VoxelGridCovariance's min_points_per_voxel_
+static constexpr double kNdtEigRatio = 0.01; // VoxelGridCovariance's min_covar_eigvalue_mult_
+static constexpr int kNdtJacobiSweeps = 8;   // cyclic Jacobi sweeps of a cell's 3x3 covariance (converged well before)
+// the cell lattice: the voxel filter's min_b / div_b at leaf = resolution (key = ix + iy mul_y + iz mul_z, ix .. relative to minb)
+struct NdtLattice {
+  int minb[3], divb[3];
+  int mul_y, mul_z;
+  float inv_leaf_f;  // 1.0f / (float)resolution, as PCL's inverse_leaf_size_
+  double inv_leaf;   // the same value in double
+};
+// what an evaluation needs besides the clouds: radius, stencil widening, Gauss constants, the host's angle terms (PCL's j_ang_a.._h
+// and h_ang_a2 .. f3, in that order)
+struct NdtPass {
+  double r_wide;   // resolution * (1 + 1e-6): bounds |c - q| per axis for every pair the float radius test accepts
+  double excess;   // the cells' largest centroid excursion outside their own cell (cell units; ndt_stats_kernel)
+  double d1, d2;   // gauss_d1_, gauss_d2_
+  float r2f;       // float(resolution^2)
+  double j_ang[8][3];
+  double h_ang[15][3];
+};
+// keys / vals: 2 n ints each (sorted halves second); temp: radix_sort_scratch_ints(n) and exclusive_scan_scratch_ints(n) ints
+hipError_t launch_ndt_keys(const float4* pts, int n, const NdtLattice& L, int* keys, int* vals, int* temp, hipStream_t stream);
+// every cell of the sorted points -> per-cell records (n-sized scratch), the valid ones compacted into out_* in key order;
+// stats = {valid cells, largest excess as double bits (2 ints)}
+hipError_t launch_ndt_cells(const float4* pts, int n, const NdtLattice& L, const int* sorted_keys, const int* sorted_vals, int* flags,
+                            int* slots, int* temp, int* valid, int* vslots, int* ckey, float4* cent, double* gauss, int* npts,
+                            double* excess, int* out_key, float4* out_cent, double* out_gauss, int* out_n, int* stats,
+                            hipStream_t stream);
+int ndt_blocks(int n_s);
+// one evaluation: partials = ndt_blocks(n_s) x 29 doubles; with flags the sums go into the mailbox, else to sums_out (device)
+hipError_t launch_ndt_derivatives(const float4* src, int n_s, const Xform& T, const NdtLattice& L, const NdtPass& P, const int* ckey,
+                                  const float4* cent, const double* gauss, int n_cells, double* partials, double* sums_out,
+                                  unsigned long long* flags, unsigned long long seq, hipStream_t stream);
+
 
 // ---- the mapper's one-point-per-voxel map (icp_map.hip), SURVEY.md 8(f4) --------------------------------------------
 struct MapDesc {

@@ -191,6 +191,7 @@ static int align_batch_multi_impl(const int* devices, int n_devices, const icpgp
     return multi_fail(ICPGPU_ERR_INVALID_ARG, "bad communicator %d", communicator);
   if (communicator != ICPGPU_COMM_NONE && n_pairs && !records) return multi_fail(ICPGPU_ERR_INVALID_ARG, "records is null");
   if (params && params->method == ICPGPU_P2PLANE) return multi_fail(ICPGPU_ERR_UNSUPPORTED, "the point-to-plane method has no batch path");
+  if (params && params->method == ICPGPU_NDT) return multi_fail(ICPGPU_ERR_UNSUPPORTED, "the NDT method has no batch path");
   State& S = state();
   std::lock_guard<std::mutex> guard(S.m);
 

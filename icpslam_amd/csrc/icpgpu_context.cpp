@@ -667,6 +667,10 @@ int icpgpu_destroy(icpgpu_ctx* c) {
   release(c->tile_seed.stats);
   release(c->tile_seed.prev);
   release(c->fp_acc);
+  for (DeviceBuf* b : {&c->ndt.keys, &c->ndt.vals, &c->ndt.flags, &c->ndt.slots, &c->ndt.temp, &c->ndt.valid, &c->ndt.vslots, &c->ndt.ckey,
+                       &c->ndt.cent, &c->ndt.gauss, &c->ndt.npts, &c->ndt.cell_excess, &c->ndt.key, &c->ndt.centroid, &c->ndt.gauss_c,
+                       &c->ndt.n_points, &c->ndt.stats, &c->ndt_partials})
+    release(*b);
   release(c->batch_table);
   release(c->map.node_keys);
   release(c->map.node_vals);
@@ -717,7 +721,8 @@ int icpgpu_set_params(icpgpu_ctx* c, const icpgpu_params* user) {
   default_params_full(&full);
   std::memcpy(&full, user, std::min(c->abi_params, sizeof(full)));
   const icpgpu_params* p = &full;
-  if (p->method != ICPGPU_P2P_SVD && p->method != ICPGPU_GICP && p->method != ICPGPU_P2PLANE) return fail(c, ICPGPU_ERR_INVALID_ARG, "bad method");
+  if (p->method != ICPGPU_P2P_SVD && p->method != ICPGPU_GICP && p->method != ICPGPU_P2PLANE && p->method != ICPGPU_NDT)
+    return fail(c, ICPGPU_ERR_INVALID_ARG, "bad method");
   if (p->nn_mode < ICPGPU_NN_AUTO || p->nn_mode > ICPGPU_NN_GRID) return fail(c, ICPGPU_ERR_INVALID_ARG, "bad nn_mode");
   if (p->brute_variant < 0 || p->brute_variant > 2) return fail(c, ICPGPU_ERR_INVALID_ARG, "bad brute_variant");
   if (p->gicp_inner != ICPGPU_GICP_INNER_EXACT && p->gicp_inner != ICPGPU_GICP_INNER_QUADRATIC)

@@ -575,6 +575,7 @@ int icpgpu_align(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fi
   icpgpu_result* res = c->abi_result == sizeof(icpgpu_result) ? user_res : &own;
   const int rc = c->params.method == ICPGPU_GICP      ? align_gicp(c, guess, out_xyzw, want_fitness, res)
                  : c->params.method == ICPGPU_P2PLANE ? align_p2plane(c, guess, out_xyzw, want_fitness, res)
+                 : c->params.method == ICPGPU_NDT     ? align_ndt(c, guess, out_xyzw, want_fitness, res)
                                                       : align_p2p(c, guess, out_xyzw, want_fitness, res);
   if (res != user_res) {
     std::memset(user_res, 0, c->abi_result);
@@ -701,6 +702,7 @@ int icpgpu_align_view(icpgpu_ctx* c, const float* guess, int want_fitness, icpgp
   c->want_view = true;
   const int rc = c->params.method == ICPGPU_GICP      ? align_gicp(c, guess, nullptr, want_fitness, res)
                  : c->params.method == ICPGPU_P2PLANE ? align_p2plane(c, guess, nullptr, want_fitness, res)
+                 : c->params.method == ICPGPU_NDT     ? align_ndt(c, guess, nullptr, want_fitness, res)
                                                       : align_p2p(c, guess, nullptr, want_fitness, res);
   if (res != user_res) {
     std::memset(user_res, 0, c->abi_result);

@@ -272,6 +272,47 @@ class Context:
         """icpgpu_solve_point_to_plane: the 4x4 incremental transform from the 29 sums, or None for a singular system."""
         return solve_point_to_plane(sums)
 
+    # NDT mode (method NDT) -------------------------------------------------------------------------------------
+    def set_ndt_params(self, resolution: float = 1.0, step_size: float = 0.1, outlier_ratio: float = 0.55):
+        """icpgpu_set_ndt_params: setResolution / setStepSize / setOulierRatio (PCL's defaults)."""
+        self._check(self._L.icpgpu_set_ndt_params(self._h, float(resolution), float(step_size), float(outlier_ratio)))
+
+    def get_ndt_params(self) -> dict:
+        v = [C.c_double(), C.c_double(), C.c_double()]
+        self._check(self._L.icpgpu_get_ndt_params(self._h, *[C.byref(x) for x in v]))
+        return dict(resolution=v[0].value, step_size=v[1].value, outlier_ratio=v[2].value)
+
+    def ndt_transformation_probability(self) -> float:
+        """getTransformationProbability(): the last NDT alignment's score / the number of source points."""
+        out = C.c_double()
+        self._check(self._L.icpgpu_ndt_transformation_probability(self._h, C.byref(out)))
+        return out.value
+
+    def ndt_cells(self) -> dict:
+        """icpgpu_ndt_cells: the target's valid NDT cells in key order -- centroid (n, 4) float32, mean (n, 3), icov (n, 3, 3),
+        n_points (n,) int32."""
+        n = C.c_size_t()
+        self._check(self._L.icpgpu_ndt_cells(self._h, 0, None, None, None, None, C.byref(n)))
+        k = n.value
+        cent = np.zeros((k, 4), np.float32)
+        mean = np.zeros((k, 3), np.float64)
+        ic6 = np.zeros((k, 6), np.float64)
+        npts = np.zeros(k, np.int32)
+        dp = C.POINTER(C.c_double)
+        self._check(self._L.icpgpu_ndt_cells(self._h, k, _fp(cent), mean.ctypes.data_as(dp), ic6.ctypes.data_as(dp),
+                                             npts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)))
+        icov = ic6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(k, 3, 3)
+        return dict(centroid=cent, mean=mean, icov=icov, n_points=npts)
+
+    def ndt_derivatives(self, p) -> np.ndarray:
+        """icpgpu_ndt_derivatives: (29,) float64 = pairs, score, gradient (6), Hessian upper triangle row by row (21) at
+        p = (tx, ty, tz, roll, pitch, yaw)."""
+        p = np.ascontiguousarray(p, np.float64).reshape(6)
+        sums = np.zeros(29, np.float64)
+        dp = C.POINTER(C.c_double)
+        self._check(self._L.icpgpu_ndt_derivatives(self._h, p.ctypes.data_as(dp), sums.ctypes.data_as(dp)))
+        return sums
+
     def gicp_quadratic_sums(self, T=None) -> np.ndarray:
         """(75, 2) the sums of GICP's quadratic inner objective at transform T as (hi, lo) pairs (icp_gicp_quadratic.h) -- the
         device half of params.gicp_inner = GICP_INNER_QUADRATIC, for tests."""
@@ -336,6 +377,23 @@ class Context:
         v = C.c_uint64()
         self._check(self._L.icpgpu_count_candidates_read(self._h, C.byref(v)))
         return int(v.value)
+
+
+def ndt_step(sums, p, step_size: float, eps: float):
+    """icpgpu_ndt_step (host only): one Newton step of the NDT loop -> (status, p_out (6,), step, T_out 4x4 float32);
+    status 0 = a step, 1 = |delta| is 0, 2 = delta is NaN."""
+    L = _lib.load()
+    sums = np.ascontiguousarray(sums, np.float64).reshape(29)
+    p = np.ascontiguousarray(p, np.float64).reshape(6)
+    p_out = np.zeros(6, np.float64)
+    step = C.c_double()
+    T = np.zeros(16, np.float32)
+    dp = C.POINTER(C.c_double)
+    rc = L.icpgpu_ndt_step(sums.ctypes.data_as(dp), p.ctypes.data_as(dp), float(step_size), float(eps), p_out.ctypes.data_as(dp),
+                           C.byref(step), _fp(T))
+    if rc < 0:
+        raise IcpGpuError(rc, "ndt_step: bad argument")
+    return rc, p_out, step.value, T.reshape(4, 4).T.copy()
 
 
 def solve_point_to_plane(sums):
@@ -452,6 +510,53 @@ class GeneralizedIterativeClosestPoint(IterativeClosestPoint):
         """NOT a PCL method (the C++ shim has the same one): the inner minimisation on the quadratic form of each outer iteration,
         icpgpu_params.gicp_inner -- faster, within tolerance of the default's result instead of on its bits (include/icpgpu.h)."""
         self._params.gicp_inner = _lib.GICP_INNER_QUADRATIC if on else _lib.GICP_INNER_EXACT
+
+
+class NormalDistributionsTransform(IterativeClosestPoint):
+    """pcl::NormalDistributionsTransform<PointXYZ, PointXYZ>-shaped front end: the target's points in cells of `resolution` with one
+    Gaussian each, a Newton loop on the Gauss-fitted score (include/icpgpu.h, ICPGPU_NDT).  PCL's constructor defaults: resolution 1.0,
+    step size 0.1, outlier ratio 0.55, 35 iterations, transformation epsilon 0.1."""
+
+    METHOD = _lib.NDT
+
+    def __init__(self, device_id: int = 0, method: int | None = None):
+        super().__init__(device_id, method)
+        self._params.max_iterations = 35
+        self._params.transformation_epsilon = 0.1
+        self._ndt = dict(resolution=1.0, step_size=0.1, outlier_ratio=0.55)
+        self._probability = float("nan")
+
+    def setResolution(self, r):
+        self._ndt["resolution"] = float(r)
+
+    def getResolution(self) -> float:
+        return self._ndt["resolution"]
+
+    def setStepSize(self, s):
+        self._ndt["step_size"] = float(s)
+
+    def getStepSize(self) -> float:
+        return self._ndt["step_size"]
+
+    def setOulierRatio(self, r):                 # (PCL's spelling)
+        self._ndt["outlier_ratio"] = float(r)
+
+    def getOulierRatio(self) -> float:
+        return self._ndt["outlier_ratio"]
+
+    def align(self, guess=None) -> np.ndarray:
+        if self._source is None or self._target is None:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "align: setInputSource/setInputTarget first")
+        self._ctx.set_ndt_params(**self._ndt)
+        out = super().align(guess)
+        self._probability = self._ctx.ndt_transformation_probability()
+        return out
+
+    def getTransformationProbability(self) -> float:
+        return self._probability
+
+    def getFinalNumIteration(self) -> int:
+        return 0 if self._result is None else int(self._result["iterations"])
 
 
 class IterativeClosestPointWithNormals(IterativeClosestPoint):

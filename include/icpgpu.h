@@ -48,7 +48,8 @@ extern "C" {
  * nothing but a comment to protect an older caller; the unsized symbols of those versions (icpgpu_create, icpgpu_default_params,
  * icpgpu_align_batch_multi) are NOT exported any more, so a binary built against a 0.x header fails at load time instead of
  * overrunning its structs.  History: 1.2 ICPGPU_P2PLANE, icpgpu_set_target_normals, icpgpu_normals, icpgpu_reduce_point_to_plane,
- * icpgpu_solve_point_to_plane (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
+ * icpgpu_solve_point_to_plane; added under 1.2: ICPGPU_NDT, icpgpu_set_ndt_params, icpgpu_get_ndt_params,
+ * icpgpu_ndt_transformation_probability, icpgpu_ndt_cells, icpgpu_ndt_derivatives, icpgpu_ndt_step (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
  * icpgpu_profile.gicp_quadratic_solves; 0.3 icpgpu_profile (sources_adopted, gicp_host_solves, gicp_solver_choice). */
 
@@ -99,7 +100,21 @@ typedef enum {
  * solution: one plane and nothing else) -- undefined in PCL -- ends the alignment with converged = 0, ICPGPU_NOT_CONVERGED and
  * the last finite transform.  Single alignments only: icpgpu_align_batch* return ICPGPU_ERR_UNSUPPORTED.  Parity against PCL
  * binaries is unpinned, like every other mode's. */
-typedef enum { ICPGPU_P2P_SVD = 0, ICPGPU_GICP = 1, ICPGPU_P2PLANE = 2 } icpgpu_method;
+/* ICPGPU_NDT (added under 1.2) is pcl::NormalDistributionsTransform over pcl::VoxelGridCovariance (PCL 1.8): the target's points are
+ * binned into cells of the voxel filter's keys at leaf = resolution; every cell of >= 6 points gets a Gaussian (mean, PCL's
+ * covariance with its smallest eigenvalues raised to 0.01 x the largest, inverse); a Newton loop over p = (tx, ty, tz, roll, pitch,
+ * yaw) maximises the sum over source points and cells within `resolution` of the transformed point of the Gauss-fitted score.
+ * Parameters: icpgpu_set_ndt_params (resolution 1.0, step_size 0.1, outlier_ratio 0.55 by default) and icpgpu_params'
+ * max_iterations and transformation_epsilon (PCL's NDT sets 35 and 0.1; the C++ shim does the same); min_correspondences and
+ * max_correspondence_distance are not used (fitness keeps its own range).  Result: T = the float transform of the final p,
+ * iterations = getFinalNumIteration(), converged = 1 as PCL's, except 0 when the Newton step is NaN (T is then the last finite
+ * transform, state ICPGPU_NOT_CONVERGED); state ICPGPU_CONV_ITERATIONS on the iteration cap, ICPGPU_CONV_TRANSFORM on a step below
+ * epsilon or a zero step, ICPGPU_CONV_NO_CORRESPONDENCES (T = the guess) when no (point, cell) pair contributes at the guess;
+ * n_correspondences = the pairs of the last evaluation; mse_last = NaN.  Two deliberate deviations from PCL 1.8: cells with a
+ * negative or zero eigenvalue or a non-finite inverse are dropped (PCL keeps them searchable), and a target whose cell index
+ * would overflow int32 at this resolution is refused with ICPGPU_ERR_INVALID_ARG (PCL passes through).  DESIGN.md states the
+ * contract rule by rule.  Single alignments only: icpgpu_align_batch* return ICPGPU_ERR_UNSUPPORTED. */
+typedef enum { ICPGPU_P2P_SVD = 0, ICPGPU_GICP = 1, ICPGPU_P2PLANE = 2, ICPGPU_NDT = 3 } icpgpu_method;
 
 /* GICP's inner minimisation (PCL: estimateRigidTransformationBFGS, ~35 cost evaluations per outer iteration).
  *   EXACT      every evaluation is a pass over the correspondences with PCL's arithmetic (points transformed in float32); the
@@ -360,6 +375,29 @@ int icpgpu_reduce_point_to_plane(icpgpu_ctx* ctx, const float* T, double max_dis
  * Tk = constructTransformationMatrix(x0..x5) = [Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)] column-major with correctly rounded sin / cos.
  * A zero pivot or a non-finite x: ICPGPU_ERR_INVALID_ARG and Tk = identity (the singular-system rule above). */
 int icpgpu_solve_point_to_plane(const double sums[29], double Tk[16]);
+
+/* ---- NDT mode (ICPGPU_NDT, added under 1.2) --------------------------------------------------------------------- */
+/* setResolution / setStepSize / setOulierRatio.  resolution > 0, step_size > 0, 0 < outlier_ratio < 1, else ICPGPU_ERR_INVALID_ARG.
+ * A changed resolution rebuilds the target's cells at the next alignment; the cells are otherwise kept while the target is the same
+ * cloud (a target icpgpu_set_target recognises included; a new or promoted target rebuilds them). */
+int icpgpu_set_ndt_params(icpgpu_ctx* ctx, double resolution, double step_size, double outlier_ratio);
+int icpgpu_get_ndt_params(const icpgpu_ctx* ctx, double* resolution, double* step_size, double* outlier_ratio);
+/* getTransformationProbability(): the last NDT alignment's final score / the number of source points (NaN before one) */
+int icpgpu_ndt_transformation_probability(const icpgpu_ctx* ctx, double* out);
+/* the target's valid cells at the current resolution, ascending cell key: centroid_xyzw (float4: the voxel filter's centroid of the
+ * cell, w = 1), mean3 (double), icov6 (xx, xy, xz, yy, yz, zz), n_points.  *n_cells = their number; nothing is copied when it
+ * exceeds capacity (call with capacity 0 to size the buffers).  Any output pointer may be NULL. */
+int icpgpu_ndt_cells(icpgpu_ctx* ctx, size_t capacity, float* centroid_xyzw, double* mean3, double* icov6, int32_t* n_points,
+                     size_t* n_cells);
+/* one derivative pass at p = (tx, ty, tz, roll, pitch, yaw), the source transformed by the float T(p): sums = {pairs, score,
+ * gradient (6), Hessian upper triangle row by row (21)}.  Same kernels and bits as an alignment's evaluations. */
+int icpgpu_ndt_derivatives(icpgpu_ctx* ctx, const double p[6], double sums[29]);
+/* (host) one Newton step from the sums at p: delta = pseudo-inverse(H) (-g) (JacobiSVD's threshold), the direction flipped to
+ * descend, the step a = clamp(|delta|, eps / 2, step_size) -> p_out = p + a delta / |delta|, *step = a, T_out = T(p_out) (float,
+ * column-major).  Returns 0 for a step (a = 0, p_out = p when g . delta is exactly 0), 1 when |delta| is 0 and 2 when it is NaN
+ * (p_out = p, *step = 0, T_out = T(p): the loop stops). */
+int icpgpu_ndt_step(const double sums[29], const double p[6], double step_size, double eps, double p_out[6], double* step,
+                    float T_out[16]);
 
 /* ICPGPU_GICP_DEVICE=auto only: time GICP's two inner solvers on THIS box with the context's current source, target and parameters
  * (method GICP; a few alignments whose results are discarded) and keep the faster for the context's single alignments from now on.

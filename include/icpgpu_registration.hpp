@@ -283,10 +283,12 @@ class IterativeClosestPoint {
         bound_ = true;
       }
       if (icpgpu_set_params(ctx_, &params_) != ICPGPU_OK) return false;
+      if (params_.method == ICPGPU_NDT && icpgpu_set_ndt_params(ctx_, ndt_[0], ndt_[1], ndt_[2]) != ICPGPU_OK) return false;
       if (icpgpu_set_target(ctx_, nt ? reinterpret_cast<const float*>(&target_->points[0]) : nullptr, nt) != ICPGPU_OK) return false;
       // (after set_target, which drops the normals a target had: IterativeClosestPointWithNormals::setTargetNormals)
       if (target_normals_ && icpgpu_set_target_normals(ctx_, target_normals_, n_target_normals_) != ICPGPU_OK) return false;
-    } else if (icpgpu_set_params(ctx_, &params_) != ICPGPU_OK) {
+    } else if (icpgpu_set_params(ctx_, &params_) != ICPGPU_OK ||
+               (params_.method == ICPGPU_NDT && icpgpu_set_ndt_params(ctx_, ndt_[0], ndt_[1], ndt_[2]) != ICPGPU_OK)) {
       return false;
     }
     const std::size_t ns = source_->points.size();
@@ -341,6 +343,8 @@ class IterativeClosestPoint {
   icpgpu_params params_;  // (GeneralizedIterativeClosestPoint sets its solver options here)
   const float* target_normals_ = nullptr;  // (IterativeClosestPointWithNormals: the caller's target normals, n float4)
   std::size_t n_target_normals_ = 0;
+  double ndt_[3] = {1.0, 0.1, 0.55};  // (NormalDistributionsTransform: resolution, step size, outlier ratio)
+  icpgpu_ctx* context() const { return ctx_; }
 
  private:
   icpgpu_result result_;
@@ -380,6 +384,42 @@ class IterativeClosestPointWithNormals : public IterativeClosestPoint<CloudT> {
     this->target_normals_ = nxyzw;
     this->n_target_normals_ = nxyzw ? n : 0;
   }
+};
+
+// pcl::NormalDistributionsTransform<PointXYZ, PointXYZ>'s counterpart: same protocol, method = ICPGPU_NDT -- the target's points in
+// cells of `resolution` with one Gaussian each, a Newton loop on the Gauss-fitted score (include/icpgpu.h, ICPGPU_NDT).  PCL's
+// constructor defaults: resolution 1.0, step size 0.1, outlier ratio 0.55, 35 iterations, transformation epsilon 0.1.  The
+// reference's call sites swap the one type; their setMaxCorrespondenceDistance is accepted and not used by NDT.
+template <class CloudT>
+class NormalDistributionsTransform : public IterativeClosestPoint<CloudT> {
+ public:
+  explicit NormalDistributionsTransform(int device = 0) : IterativeClosestPoint<CloudT>(device, ICPGPU_NDT) {
+    this->params_.max_iterations = 35;
+    this->params_.transformation_epsilon = 0.1;
+  }
+  void setResolution(float resolution) { this->ndt_[0] = resolution; }
+  float getResolution() const { return static_cast<float>(this->ndt_[0]); }
+  void setStepSize(double step_size) { this->ndt_[1] = step_size; }
+  double getStepSize() const { return this->ndt_[1]; }
+  void setOulierRatio(double outlier_ratio) { this->ndt_[2] = outlier_ratio; }  // (PCL's spelling)
+  double getOulierRatio() const { return this->ndt_[2]; }
+  void align(CloudT& output) {
+    IterativeClosestPoint<CloudT>::align(output);
+    fetch_probability();
+  }
+  void align(CloudT& output, const Matrix4& guess) {
+    IterativeClosestPoint<CloudT>::align(output, guess);
+    fetch_probability();
+  }
+  double getTransformationProbability() const { return probability_; }
+  int getFinalNumIteration() const { return this->getResult().iterations; }
+
+ private:
+  void fetch_probability() {
+    probability_ = 0.0;
+    if (icpgpu_ndt_transformation_probability(this->context(), &probability_) != ICPGPU_OK) probability_ = 0.0;
+  }
+  double probability_ = 0.0;
 };
 
 // pcl::VoxelGrid<PointT>-shaped front end for the odometer's pre-step
