@@ -16,6 +16,9 @@ if os.environ.get("ICPGPU_LIB_PATH"):   # A/B builds of an experiment (scripts/)
 
 OK, ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_NO_INPUT, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
 P2P_SVD, GICP, P2PLANE, NDT = 0, 1, 2, 3
+NDT_LINE_SEARCH_PCL18, NDT_LINE_SEARCH_MORE_THUENTE = 0, 1      # icpgpu_ndt_line_search
+# icpgpu_ndt_mt_exit: how a More-Thuente search ends (TRIAL = not yet)
+MT_TRIAL, MT_WOLFE, MT_INTERVAL, MT_TRIAL_CAP, MT_NAN_STEP, MT_NON_FINITE = 0, 1, 2, 3, 4, 5
 GICP_INNER_EXACT, GICP_INNER_QUADRATIC = 0, 1
 GICP_SOLVER_NONE, GICP_SOLVER_HOST, GICP_SOLVER_DEVICE, GICP_SOLVER_QUADRATIC = 0, 1, 2, 3
 HEADER_VERSION = 1002          # the icpgpu.h these mirrors were written against (ICPGPU_HEADER_VERSION)
@@ -80,7 +83,8 @@ EXPORTS = [
     "icpgpu_map_nn_target", "icpgpu_count_candidates", "icpgpu_count_candidates_read",
     "icpgpu_set_target_normals", "icpgpu_normals", "icpgpu_reduce_point_to_plane", "icpgpu_solve_point_to_plane",
     "icpgpu_set_ndt_params", "icpgpu_get_ndt_params", "icpgpu_ndt_transformation_probability", "icpgpu_ndt_cells",
-    "icpgpu_ndt_derivatives", "icpgpu_ndt_step",
+    "icpgpu_ndt_derivatives", "icpgpu_ndt_step", "icpgpu_set_ndt_line_search", "icpgpu_get_ndt_line_search", "icpgpu_ndt_gradient",
+    "icpgpu_ndt_line_search_replay", "icpgpu_ndt_line_search_trace",
 ]
 
 _lib = None
@@ -154,6 +158,11 @@ def load():
     L.icpgpu_ndt_cells.argtypes = [vp, C.c_size_t, fp, dp, dp, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]
     L.icpgpu_ndt_derivatives.argtypes = [vp, dp, dp]
     L.icpgpu_ndt_step.argtypes = [dp, dp, C.c_double, C.c_double, dp, dp, fp]
+    L.icpgpu_set_ndt_line_search.argtypes = [vp, C.c_int]
+    L.icpgpu_get_ndt_line_search.argtypes = [vp, ip]
+    L.icpgpu_ndt_gradient.argtypes = [vp, dp, dp]
+    L.icpgpu_ndt_line_search_replay.argtypes = [C.c_double] * 5 + [dp, dp, C.c_int, dp, ip]
+    L.icpgpu_ndt_line_search_trace.argtypes = [vp, C.c_size_t, C.POINTER(C.c_int32), dp, dp, dp, C.POINTER(C.c_size_t)]
     L.icpgpu_voxel_grid.argtypes = [vp, fp, C.c_size_t, C.c_float, fp, C.POINTER(C.c_size_t)]
     L.icpgpu_voxel_grid_fetch.argtypes = [vp, fp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.icpgpu_voxel_grid_view.argtypes = [vp, fp, C.c_size_t, C.c_float, C.POINTER(fp), C.POINTER(C.c_size_t)]

@@ -254,6 +254,14 @@ struct icpgpu_ctx {
     NdtLattice L{};
   } ndt;
   DeviceBuf ndt_partials;
+  // the NDT step rule (icpgpu_ndt_line_search: 0 = PCL 1.8's clamped Newton step, 1 = More-Thuente) and the last alignment's
+  // line-search trials (More-Thuente only): Newton iteration, step, phi = -score, phi' = -(g . d)
+  int ndt_line_search = 0;
+  struct NdtTrialRec {
+    int iteration;
+    double a, phi, dphi;
+  };
+  std::vector<NdtTrialRec> ndt_trace;
   // Per-iteration result mailbox in pinned, mapped host memory: 17 sums + 17 sequence flags.  The final reduction
   // stores straight into it and the host polls the flags -- no copy engine and no stream synchronisation (whose wake-up
   // costs 20-70 us depending on how the process set up the runtime) on the iteration path.

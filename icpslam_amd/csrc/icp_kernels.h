@@ -340,12 +340,14 @@ int p2plane_blocks(int n_s);
 hipError_t launch_p2plane_reduce(const float4* src, int n_s, const float4* tgt, const float4* normals, const unsigned long long* keys,
                                  const Xform& T, float thr, double* partials, double* sums_out, unsigned long long* flags,
                                  unsigned long long seq, hipStream_t stream);
-// the p2plane final kernel alone: partials (n_blocks x 29 doubles, block-major) -> 29 sums, fixed order (NDT's derivative pass)
+// the p2plane final kernel alone: partials (n_blocks x 29 doubles, block-major) -> the first n_terms of the 29 sums, fixed order
+// (NDT's derivative and trial passes)
 hipError_t launch_terms29_final(const double* partials, int n_blocks, double* sums_out, unsigned long long* flags, unsigned long long seq,
-                                hipStream_t stream);
+                                hipStream_t stream, int n_terms = 29);
 
 // ---- NDT (icp_ndt.hip): pcl::NormalDistributionsTransform's target cells and derivative pass ----------------------------
 static constexpr int kNdtTerms = 29;         // pairs, score, gradient (6), Hessian upper triangle row by row (21)
+static constexpr int kNdtGradTerms = 8;      // the trial pass's: pairs, score, gradient (6) -- the first 8 of the 29
 static constexpr int kNdtGaussDoubles = 10;  // per valid cell: mean (3), icov xx xy xz yy yz zz (6), pad
 static constexpr int kNdtMinPoints = 6;      // VoxelGridCovariance's min_points_per_voxel_
 static constexpr double kNdtEigRatio = 0.01; // VoxelGridCovariance's min_covar_eigvalue_mult_
@@ -376,10 +378,11 @@ hipError_t launch_ndt_cells(const float4* pts, int n, const NdtLattice& L, const
                             double* excess, int* out_key, float4* out_cent, double* out_gauss, int* out_n, int* stats,
                             hipStream_t stream);
 int ndt_blocks(int n_s);
-// one evaluation: partials = ndt_blocks(n_s) x 29 doubles; with flags the sums go into the mailbox, else to sums_out (device)
+// one evaluation: partials = ndt_blocks(n_s) x 29 doubles; with flags the sums go into the mailbox, else to sums_out (device).
+// hessian: the 29 sums (ndt_deriv_kernel); else the first 8 only (ndt_grad_kernel), the same bits as the 29-term pass's first 8
 hipError_t launch_ndt_derivatives(const float4* src, int n_s, const Xform& T, const NdtLattice& L, const NdtPass& P, const int* ckey,
                                   const float4* cent, const double* gauss, int n_cells, double* partials, double* sums_out,
-                                  unsigned long long* flags, unsigned long long seq, hipStream_t stream);
+                                  unsigned long long* flags, unsigned long long seq, hipStream_t stream, bool hessian = true);
 
 
 // ---- the mapper's one-point-per-voxel map (icp_map.hip), SURVEY.md 8(f4) --------------------------------------------

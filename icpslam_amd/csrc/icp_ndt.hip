@@ -15,6 +15,9 @@
 //                        (dx^2 + dy^2) + dz^2 <= r^2 (the cells come from a per-axis range of lattice indices and a binary search of
 //                        the sorted keys per (y, z) row), then per pair PCL's updateDerivatives in double: 29 terms per lane
 //                        (pairs, score, gradient 6, Hessian upper triangle 21), one partial per workgroup (fixed shuffle + LDS tree)
+//   ndt_grad_kernel      the More-Thuente line search's trial pass (ICPGPU_NDT_LINE_SEARCH_MORE_THUENTE): the same lane, pair
+//                        arithmetic and tree for the first 8 terms only (pairs, score, gradient), without A, M and the Hessian --
+//                        its 8 sums are the bits of ndt_deriv_kernel's first 8 at the same pose (both are ndt_pass<>)
 //   p2plane_final_kernel (icp_p2plane.hip, launch_terms29_final) adds the partials in a fixed order into the result mailbox
 #include <math.h>
 
@@ -275,13 +278,17 @@ __device__ __forceinline__ bool axis_range(float q, const NdtLattice& L, const N
   return true;
 }
 
-__global__ __launch_bounds__(ND_BLOCK) void ndt_deriv_kernel(const float4* __restrict__ src, int n_s, Xform T, NdtLattice L, NdtPass P,
-                                                             const int* __restrict__ ckey, const float4* __restrict__ cent,
-                                                             const double* __restrict__ gauss, int n_cells,
-                                                             double* __restrict__ partials) {
-  double acc[kNdtTerms];
+// One lane per source point; kHessian: the 29 sums of computeDerivatives, else the first kNdtGradTerms of them (pairs, score,
+// gradient) with the same per-point arithmetic and the same reduction tree, so those 8 are the same bits in both passes.
+template <bool kHessian>
+__device__ __forceinline__ void ndt_pass(const float4* __restrict__ src, int n_s, const Xform& T, const NdtLattice& L, const NdtPass& P,
+                                         const int* __restrict__ ckey, const float4* __restrict__ cent, const double* __restrict__ gauss,
+                                         int n_cells, double* __restrict__ partials) {
+  constexpr int NT = kHessian ? kNdtTerms : kNdtGradTerms;
+  constexpr int NP = kHessian ? 17 : 5;  // per-point sums: pairs, score, b (3) [, A (6), M (6)]
+  double acc[NT];
 #pragma unroll
-  for (int k = 0; k < kNdtTerms; ++k) acc[k] = 0.0;
+  for (int k = 0; k < NT; ++k) acc[k] = 0.0;
   // (one lane per point: dealing a point's stencil rows out to 2, 4 or 8 lanes measured 1.0x, 1.5x, 2.4x SLOWER on 200k points)
   const int stride = gridDim.x * ND_BLOCK;
   for (int i = blockIdx.x * ND_BLOCK + threadIdx.x; i < n_s; i += stride) {
@@ -296,9 +303,9 @@ __global__ __launch_bounds__(ND_BLOCK) void ndt_deriv_kernel(const float4* __res
     // w (-d2 (q'^T icov J_k)(q'^T icov J_l) + q'^T icov H_kl + J_l^T icov J_k) to H_kl.  J and H depend on the point alone, so the
     // point's pairs are summed first -- b = sum w icq, A = sum w icov, M = sum w icq icq^T -- and then g = J^T b,
     // H_kl = -d2 J_k^T M J_l + b . H_kl + J_l^T A J_k: the same sums, ~60 flops per pair instead of ~300
-    double pt[17];  // pairs, score, b (3), A (6: xx xy xz yy yz zz), M (6)
+    double pt[NP];  // pairs, score, b (3), A (6: xx xy xz yy yz zz), M (6)
 #pragma unroll
-    for (int k = 0; k < 17; ++k) pt[k] = 0.0;
+    for (int k = 0; k < NP; ++k) pt[k] = 0.0;
     int pos = 0;
     for (int iz = lo[2]; iz <= hi[2]; ++iz)
       for (int iy = lo[1]; iy <= hi[1]; ++iy) {
@@ -323,15 +330,17 @@ __global__ __launch_bounds__(ND_BLOCK) void ndt_deriv_kernel(const float4* __res
           pt[1] += -P.d1 * e;
 #pragma unroll
           for (int a = 0; a < 3; ++a) pt[2 + a] += w * icq[a];
+          if constexpr (kHessian) {
 #pragma unroll
-          for (int a = 0; a < 6; ++a) pt[5 + a] += w * ic[a];
-          const double wq[3] = {w * icq[0], w * icq[1], w * icq[2]};
-          pt[11] += wq[0] * icq[0];
-          pt[12] += wq[0] * icq[1];
-          pt[13] += wq[0] * icq[2];
-          pt[14] += wq[1] * icq[1];
-          pt[15] += wq[1] * icq[2];
-          pt[16] += wq[2] * icq[2];
+            for (int a = 0; a < 6; ++a) pt[5 + a] += w * ic[a];
+            const double wq[3] = {w * icq[0], w * icq[1], w * icq[2]};
+            pt[11] += wq[0] * icq[0];
+            pt[12] += wq[0] * icq[1];
+            pt[13] += wq[0] * icq[2];
+            pt[14] += wq[1] * icq[1];
+            pt[15] += wq[1] * icq[2];
+            pt[16] += wq[2] * icq[2];
+          }
         }
       }
     if (pt[0] == 0.0) continue;
@@ -351,58 +360,76 @@ __global__ __launch_bounds__(ND_BLOCK) void ndt_deriv_kernel(const float4* __res
     J[5][0] = dot3(x, P.j_ang[5]);
     J[5][1] = dot3(x, P.j_ang[6]);
     J[5][2] = dot3(x, P.j_ang[7]);
-    // Hb[0..5] = the blocks a, b, c, d, e, f: H(3,3) = a, H(3,4) = b, H(3,5) = c, H(4,4) = d, H(4,5) = e, H(5,5) = f
-    double Hb[6][3];
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      Hb[b][0] = 0.0;
-      Hb[b][1] = dot3(x, P.h_ang[2 * b]);
-      Hb[b][2] = dot3(x, P.h_ang[2 * b + 1]);
-    }
-#pragma unroll
-    for (int b = 0; b < 3; ++b)
-#pragma unroll
-      for (int a = 0; a < 3; ++a) Hb[3 + b][a] = dot3(x, P.h_ang[6 + 3 * b + a]);
-    const double A[3][3] = {{pt[5], pt[6], pt[7]}, {pt[6], pt[8], pt[9]}, {pt[7], pt[9], pt[10]}};
-    const double M[3][3] = {{pt[11], pt[12], pt[13]}, {pt[12], pt[14], pt[15]}, {pt[13], pt[15], pt[16]}};
-    double AJ[6][3], MJ[6][3];
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        AJ[k][r] = dot3(A[r], J[k]);
-        MJ[k][r] = dot3(M[r], J[k]);
-      }
     acc[0] += pt[0];
     acc[1] += pt[1];
 #pragma unroll
     for (int k = 0; k < 6; ++k) acc[2 + k] += dot3(J[k], pt + 2);
-    int t = 8;
+    if constexpr (kHessian) {
+      // Hb[0..5] = the blocks a, b, c, d, e, f: H(3,3) = a, H(3,4) = b, H(3,5) = c, H(4,4) = d, H(4,5) = e, H(5,5) = f
+      double Hb[6][3];
 #pragma unroll
-    for (int k = 0; k < 6; ++k)
-#pragma unroll
-      for (int l = k; l < 6; ++l, ++t) {
-        double h = -P.d2 * dot3(J[l], MJ[k]);
-        if (k >= 3) h += dot3(pt + 2, Hb[k == 3 ? l - 3 : (k == 4 ? 3 + (l - 4) : 5)]);
-        h += dot3(J[l], AJ[k]);
-        acc[t] += h;
+      for (int b = 0; b < 3; ++b) {
+        Hb[b][0] = 0.0;
+        Hb[b][1] = dot3(x, P.h_ang[2 * b]);
+        Hb[b][2] = dot3(x, P.h_ang[2 * b + 1]);
       }
+#pragma unroll
+      for (int b = 0; b < 3; ++b)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) Hb[3 + b][a] = dot3(x, P.h_ang[6 + 3 * b + a]);
+      const double A[3][3] = {{pt[5], pt[6], pt[7]}, {pt[6], pt[8], pt[9]}, {pt[7], pt[9], pt[10]}};
+      const double M[3][3] = {{pt[11], pt[12], pt[13]}, {pt[12], pt[14], pt[15]}, {pt[13], pt[15], pt[16]}};
+      double AJ[6][3], MJ[6][3];
+#pragma unroll
+      for (int k = 0; k < 6; ++k)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          AJ[k][r] = dot3(A[r], J[k]);
+          MJ[k][r] = dot3(M[r], J[k]);
+        }
+      int t = 8;
+#pragma unroll
+      for (int k = 0; k < 6; ++k)
+#pragma unroll
+        for (int l = k; l < 6; ++l, ++t) {
+          double h = -P.d2 * dot3(J[l], MJ[k]);
+          if (k >= 3) h += dot3(pt + 2, Hb[k == 3 ? l - 3 : (k == 4 ? 3 + (l - 4) : 5)]);
+          h += dot3(J[l], AJ[k]);
+          acc[t] += h;
+        }
+    }
   }
-  // fixed-order block reduction: shuffle tree per wave, then the four waves in order
-  __shared__ double wsum[ND_BLOCK / 64][kNdtTerms];
+  // fixed-order block reduction: shuffle tree per wave, then the four waves in order; partials keep kNdtTerms doubles per
+  // workgroup in both passes (the final kernel reads the first NT columns)
+  __shared__ double wsum[ND_BLOCK / 64][NT];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int k = 0; k < kNdtTerms; ++k) {
+  for (int k = 0; k < NT; ++k) {
     const double v = wave_sum(acc[k]);
     if (lane == 0) wsum[wave][k] = v;
   }
   __syncthreads();
-  if (threadIdx.x < kNdtTerms) {
+  if (threadIdx.x < NT) {
     double v = 0.0;
 #pragma unroll
     for (int w = 0; w < ND_BLOCK / 64; ++w) v += wsum[w][threadIdx.x];
     partials[(size_t)blockIdx.x * kNdtTerms + threadIdx.x] = v;
   }
+}
+
+__global__ __launch_bounds__(ND_BLOCK) void ndt_deriv_kernel(const float4* __restrict__ src, int n_s, Xform T, NdtLattice L, NdtPass P,
+                                                             const int* __restrict__ ckey, const float4* __restrict__ cent,
+                                                             const double* __restrict__ gauss, int n_cells,
+                                                             double* __restrict__ partials) {
+  ndt_pass<true>(src, n_s, T, L, P, ckey, cent, gauss, n_cells, partials);
+}
+
+// the More-Thuente line search's trial pass: score and gradient only (no A, M or Hessian)
+__global__ __launch_bounds__(ND_BLOCK) void ndt_grad_kernel(const float4* __restrict__ src, int n_s, Xform T, NdtLattice L, NdtPass P,
+                                                            const int* __restrict__ ckey, const float4* __restrict__ cent,
+                                                            const double* __restrict__ gauss, int n_cells,
+                                                            double* __restrict__ partials) {
+  ndt_pass<false>(src, n_s, T, L, P, ckey, cent, gauss, n_cells, partials);
 }
 
 }  // namespace
@@ -447,15 +474,18 @@ int ndt_blocks(int n_s) {
 
 hipError_t launch_ndt_derivatives(const float4* src, int n_s, const Xform& T, const NdtLattice& L, const NdtPass& P, const int* ckey,
                                   const float4* cent, const double* gauss, int n_cells, double* partials, double* sums_out,
-                                  unsigned long long* flags, unsigned long long seq, hipStream_t stream) {
+                                  unsigned long long* flags, unsigned long long seq, hipStream_t stream, bool hessian) {
   const int blocks = ndt_blocks(n_s);
   if (n_s > 0 && n_cells > 0) {
-    hipLaunchKernelGGL(ndt_deriv_kernel, dim3(blocks), dim3(ND_BLOCK), 0, stream, src, n_s, T, L, P, ckey, cent, gauss, n_cells, partials);
+    if (hessian)
+      hipLaunchKernelGGL(ndt_deriv_kernel, dim3(blocks), dim3(ND_BLOCK), 0, stream, src, n_s, T, L, P, ckey, cent, gauss, n_cells, partials);
+    else
+      hipLaunchKernelGGL(ndt_grad_kernel, dim3(blocks), dim3(ND_BLOCK), 0, stream, src, n_s, T, L, P, ckey, cent, gauss, n_cells, partials);
   } else {
     const hipError_t e = hipMemsetAsync(partials, 0, (size_t)blocks * kNdtTerms * sizeof(double), stream);
     if (e != hipSuccess) return e;
   }
-  return launch_terms29_final(partials, blocks, sums_out, flags, seq, stream);
+  return launch_terms29_final(partials, blocks, sums_out, flags, seq, stream, hessian ? kNdtTerms : kNdtGradTerms);
 }
 
 }  // namespace icpgpu

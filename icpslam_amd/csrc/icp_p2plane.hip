@@ -146,8 +146,8 @@ hipError_t launch_p2plane_reduce(const float4* src, int n_s, const float4* tgt, 
 }
 
 hipError_t launch_terms29_final(const double* partials, int n_blocks, double* sums_out, unsigned long long* flags, unsigned long long seq,
-                                hipStream_t stream) {
-  hipLaunchKernelGGL(p2plane_final_kernel, dim3(kP2planeTerms), dim3(PP_FINAL_BLOCK), 0, stream, partials, n_blocks, sums_out, flags, seq);
+                                hipStream_t stream, int n_terms) {
+  hipLaunchKernelGGL(p2plane_final_kernel, dim3(n_terms), dim3(PP_FINAL_BLOCK), 0, stream, partials, n_blocks, sums_out, flags, seq);
   return hipGetLastError();
 }
 

@@ -3,7 +3,8 @@
 // voxel of >= 6 points) are built on the device once per target cloud and resolution (icp_ndt.hip); every Newton iteration is
 // one derivative pass (ndt_deriv_kernel + the fixed-order final sum into the result mailbox) -> the host solves the 6 x 6 system
 // by a pseudo-inverse, takes PCL 1.8's step (computeStepLengthMT without a More-Thuente trial: DESIGN.md) and builds the float
-// transform of the new pose.  The contract, rule by rule, is DESIGN.md's NDT section.
+// transform of the new pose.  Opt-in per context (icpgpu_set_ndt_line_search): the More-Thuente line search with its loop running,
+// whose loop trials are score-and-gradient passes (ndt_grad_kernel).  The contract, rule by rule, is DESIGN.md's NDT section.
 #include "icp_ctx.h"
 #include "icp_trig.h"
 
@@ -203,13 +204,12 @@ static void pinv_solve6(const double H[6][6], const double b[6], double x[6]) {
   }
 }
 
-// One Newton step of computeTransformation from an evaluation's 29 sums at p (PCL 1.8; computeStepLengthMT's line search makes no
-// More-Thuente trial: interval_converged starts true).  NDT_STEP: p_out = p + a d^, *step = a, T_out = T(p_out) (when g . d^ is
-// exactly 0: a = 0, p_out = p, T_out = T(p), and no evaluation follows); NDT_ZERO / NDT_NAN: |delta| is 0 / NaN, PCL returns.
+// The Newton direction of computeTransformation from an evaluation's 29 sums: delta = pseudo-inverse(H) (-g).  NDT_ZERO / NDT_NAN:
+// |delta| is 0 / NaN, PCL returns.  Else d = delta / |delta|, flipped when -(g . d) > 0 so that it descends, *norm = |delta|,
+// *d_phi_0 = -(g . d) before the flip (exactly 0: no descent, PCL's step is 0).
 enum { NDT_STEP = 0, NDT_ZERO = 1, NDT_NAN = 2 };
-int ndt_step_impl(const double sums[kNdtTerms], const double p[6], double step_size, double eps, double p_out[6], double* step,
-                  float T_out[16], bool* evaluate) {
-  double H[6][6], g[6], b[6], d[6];
+static int ndt_direction(const double sums[kNdtTerms], double d[6], double* norm_out, double* d_phi_0_out) {
+  double H[6][6], g[6], b[6];
   for (int k = 0; k < 6; ++k) g[k] = sums[2 + k];
   for (int i = 0, t = 8; i < 6; ++i)
     for (int j = i; j < 6; ++j, ++t) H[i][j] = H[j][i] = sums[t];
@@ -218,20 +218,33 @@ int ndt_step_impl(const double sums[kNdtTerms], const double p[6], double step_s
   double nn = 0.0;
   for (int k = 0; k < 6; ++k) nn += d[k] * d[k];
   const double norm = std::sqrt(nn);
-  for (int k = 0; k < 6; ++k) p_out[k] = p[k];
-  *step = 0.0;
-  *evaluate = false;
-  ndt_transform_float(p, T_out);
+  *norm_out = norm;
+  *d_phi_0_out = 0.0;
   if (norm == 0.0) return NDT_ZERO;
   if (norm != norm) return NDT_NAN;
   for (int k = 0; k < 6; ++k) d[k] /= norm;
   double gd = 0.0;
   for (int k = 0; k < 6; ++k) gd += g[k] * d[k];
   const double d_phi_0 = -gd;
-  if (d_phi_0 >= 0.0) {
-    if (d_phi_0 == 0.0) return NDT_STEP;  // step 0: p stays, nothing is evaluated
+  *d_phi_0_out = d_phi_0;
+  if (d_phi_0 > 0.0)
     for (int k = 0; k < 6; ++k) d[k] = -d[k];
-  }
+  return NDT_STEP;
+}
+
+// One Newton step of computeTransformation from an evaluation's 29 sums at p (PCL 1.8; computeStepLengthMT's line search makes no
+// More-Thuente trial: interval_converged starts true).  NDT_STEP: p_out = p + a d^, *step = a, T_out = T(p_out) (when g . d^ is
+// exactly 0: a = 0, p_out = p, T_out = T(p), and no evaluation follows); NDT_ZERO / NDT_NAN: |delta| is 0 / NaN, PCL returns.
+int ndt_step_impl(const double sums[kNdtTerms], const double p[6], double step_size, double eps, double p_out[6], double* step,
+                  float T_out[16], bool* evaluate) {
+  double d[6], norm, d_phi_0;
+  const int st = ndt_direction(sums, d, &norm, &d_phi_0);
+  for (int k = 0; k < 6; ++k) p_out[k] = p[k];
+  *step = 0.0;
+  *evaluate = false;
+  ndt_transform_float(p, T_out);
+  if (st != NDT_STEP) return st;
+  if (d_phi_0 == 0.0) return NDT_STEP;  // step 0: p stays, nothing is evaluated
   double a = std::min(norm, step_size);
   a = std::max(a, eps / 2.0);
   for (int k = 0; k < 6; ++k) p_out[k] = p[k] + d[k] * a;
@@ -240,6 +253,150 @@ int ndt_step_impl(const double sums[kNdtTerms], const double p[6], double step_s
   ndt_transform_float(p_out, T_out);
   return NDT_STEP;
 }
+
+// ---- the More-Thuente line search (ICPGPU_NDT_LINE_SEARCH_MORE_THUENTE): computeStepLengthMT with its loop running ----------------
+// The rule is DESIGN.md's (f6, "More-Thuente step rule"); the sequence of trial steps is a function of the observed (phi, phi')
+// alone, so the host replays it without a device (icpgpu_ndt_line_search_replay) and tests/ndt_line_search_restated.py restates it.
+namespace mt {
+
+constexpr double kMu = 1e-4, kNu = 0.9;
+constexpr int kMaxLoopTrials = 10;
+
+struct Search {
+  double phi_0, d_phi_0, step_max, step_min;
+  double a_l = 0.0, f_l = 0.0, g_l = 0.0, a_u = 0.0, f_u = 0.0, g_u = 0.0;
+  bool open = true, interval_converged = false;
+  int trials = 0;       // observed trials, the first included
+  int loop_trials = 0;  // observed trials of the loop (PCL's step_iterations)
+  double a_t = 0.0;     // the pending trial's step; after an exit, the accepted step
+  int final_trial = -1;
+  double a_prev = 0.0;  // the last observed trial's step
+};
+
+double psi(double a, double f_a, double f_0, double g_0) { return f_a - f_0 - kMu * g_0 * a; }  // auxilaryFunction_PsiMT
+double dpsi(double g_a, double g_0) { return g_a - kMu * g_0; }                                  // auxilaryFunction_dPsiMT
+
+double clamp_step(double a, double step_max, double step_min) {
+  a = std::min(a, step_max);
+  return std::max(a, step_min);
+}
+
+// trialValueSelectionMT (More & Thuente 1994, its four cases; the cubic and quadratic minimisers of Sun & Yuan 2006, 2.4.52 / 2.4.56,
+// 2.4.2 and 2.4.5)
+double trial_value(double a_l, double f_l, double g_l, double a_u, double f_u, double g_u, double a_t, double f_t, double g_t) {
+  if (f_t > f_l) {  // case 1
+    const double z = 3 * (f_t - f_l) / (a_t - a_l) - g_t - g_l;
+    const double w = std::sqrt(z * z - g_t * g_l);
+    const double a_c = a_l + (a_t - a_l) * (w - g_l - z) / (g_t - g_l + 2 * w);
+    const double a_q = a_l - 0.5 * (a_l - a_t) * g_l / (g_l - (f_l - f_t) / (a_l - a_t));
+    if (std::fabs(a_c - a_l) < std::fabs(a_q - a_l)) return a_c;
+    return 0.5 * (a_q + a_c);
+  }
+  if (g_t * (a_l - a_t) > 0) {  // case 2
+    const double z = 3 * (f_t - f_l) / (a_t - a_l) - g_t - g_l;
+    const double w = std::sqrt(z * z - g_t * g_l);
+    const double a_c = a_l + (a_t - a_l) * (w - g_l - z) / (g_t - g_l + 2 * w);
+    const double a_s = a_l - (a_l - a_t) / (g_l - g_t) * g_l;
+    if (std::fabs(a_c - a_t) >= std::fabs(a_s - a_t)) return a_c;
+    return a_s;
+  }
+  if (std::fabs(g_t) <= std::fabs(g_l)) {  // case 3
+    const double z = 3 * (f_t - f_l) / (a_t - a_l) - g_t - g_l;
+    const double w = std::sqrt(z * z - g_t * g_l);
+    const double a_c = a_l + (a_t - a_l) * (w - g_l - z) / (g_t - g_l + 2 * w);
+    const double a_s = a_l - (a_l - a_t) / (g_l - g_t) * g_l;
+    const double a_t_next = std::fabs(a_c - a_t) < std::fabs(a_s - a_t) ? a_c : a_s;
+    if (a_t > a_l) return std::min(a_t + 0.66 * (a_u - a_t), a_t_next);
+    return std::max(a_t + 0.66 * (a_u - a_t), a_t_next);
+  }
+  // case 4
+  const double z = 3 * (f_t - f_u) / (a_t - a_u) - g_t - g_u;
+  const double w = std::sqrt(z * z - g_t * g_u);
+  return a_u + (a_t - a_u) * (w - g_u - z) / (g_t - g_u + 2 * w);
+}
+
+// updateIntervalMT: cases U1 / a, U2 / b, U3 / c; true = the interval has converged
+bool update_interval(double& a_l, double& f_l, double& g_l, double& a_u, double& f_u, double& g_u, double a_t, double f_t, double g_t) {
+  if (f_t > f_l) {
+    a_u = a_t;
+    f_u = f_t;
+    g_u = g_t;
+    return false;
+  }
+  if (g_t * (a_l - a_t) > 0) {
+    a_l = a_t;
+    f_l = f_t;
+    g_l = g_t;
+    return false;
+  }
+  if (g_t * (a_l - a_t) < 0) {
+    a_u = a_l;
+    f_u = f_l;
+    g_u = g_l;
+    a_l = a_t;
+    f_l = f_t;
+    g_l = g_t;
+    return false;
+  }
+  return true;
+}
+
+// phi_0 = -score at x, d_phi_0 = -(g . d) < 0 (d already descends), step_init = |delta|; -> the first trial's step in S.a_t
+void start(Search& S, double phi_0, double d_phi_0, double step_init, double step_max, double step_min) {
+  S = Search{};
+  S.phi_0 = phi_0;
+  S.d_phi_0 = d_phi_0;
+  S.step_max = step_max;
+  S.step_min = step_min;
+  S.f_l = S.f_u = psi(0.0, phi_0, phi_0, d_phi_0);
+  S.g_l = S.g_u = dpsi(d_phi_0, d_phi_0);
+  S.interval_converged = (step_max - step_min) < 0;  // (PCL 1.8 tests > 0: always true, so its loop never runs)
+  S.a_t = clamp_step(step_init, step_max, step_min);
+}
+
+// the pending trial (step S.a_t) observed phi_t, d_phi_t -> ICPGPU_NDT_MT_TRIAL (S.a_t = the next trial's step) or an exit
+// (S.a_t = the accepted step, S.final_trial = its index)
+int observe(Search& S, double phi_t, double d_phi_t) {
+  const int k = S.trials++;
+  const double a_t = S.a_t;
+  if (!std::isfinite(phi_t) || !std::isfinite(d_phi_t)) {  // (deviation: PCL leaves it undefined)
+    if (k == 0) {  // the first trial stands, as under PCL 1.8's rule; the next Newton solve sees its sums
+      S.final_trial = 0;
+    } else {       // the previous trial stands
+      S.final_trial = k - 1;
+      S.a_t = S.a_prev;
+    }
+    return ICPGPU_NDT_MT_NON_FINITE;
+  }
+  S.a_prev = a_t;
+  const double psi_t = psi(a_t, phi_t, S.phi_0, S.d_phi_0);
+  const double d_psi_t = dpsi(d_phi_t, S.d_phi_0);
+  if (k > 0) {
+    if (S.open && (psi_t <= 0 && d_psi_t >= 0)) {
+      S.open = false;
+      S.f_l = S.f_l + S.phi_0 - kMu * S.d_phi_0 * S.a_l;
+      S.g_l = S.g_l + kMu * S.d_phi_0;
+      S.f_u = S.f_u + S.phi_0 - kMu * S.d_phi_0 * S.a_u;
+      S.g_u = S.g_u + kMu * S.d_phi_0;
+    }
+    S.interval_converged = S.open ? update_interval(S.a_l, S.f_l, S.g_l, S.a_u, S.f_u, S.g_u, a_t, psi_t, d_psi_t)
+                                  : update_interval(S.a_l, S.f_l, S.g_l, S.a_u, S.f_u, S.g_u, a_t, phi_t, d_phi_t);
+    ++S.loop_trials;
+  }
+  S.final_trial = k;
+  if (psi_t <= 0 && d_phi_t <= -kNu * S.d_phi_0) return ICPGPU_NDT_MT_WOLFE;
+  if (S.interval_converged) return ICPGPU_NDT_MT_INTERVAL;
+  if (S.loop_trials >= kMaxLoopTrials) return ICPGPU_NDT_MT_TRIAL_CAP;
+  double next = S.open ? trial_value(S.a_l, S.f_l, S.g_l, S.a_u, S.f_u, S.g_u, a_t, psi_t, d_psi_t)
+                       : trial_value(S.a_l, S.f_l, S.g_l, S.a_u, S.f_u, S.g_u, a_t, phi_t, d_phi_t);
+  next = clamp_step(next, S.step_max, S.step_min);
+  if (next != next) return ICPGPU_NDT_MT_NAN_STEP;  // (deviation: the search ends at this trial)
+  S.final_trial = -1;
+  S.a_t = next;
+  return ICPGPU_NDT_MT_TRIAL;
+}
+
+}  // namespace mt
 
 // The target's cells at the context's resolution: built when the target version or the resolution changed
 static int ensure_ndt_cells(icpgpu_ctx* c) {
@@ -313,8 +470,9 @@ static int ensure_ndt_cells(icpgpu_ctx* c) {
   return ICPGPU_OK;
 }
 
-// one derivative pass at the float transform T and the pose p: the 29 sums (computeDerivatives) -> sums (host)
-static int ndt_evaluate(icpgpu_ctx* c, const float T[16], const double p[6], double sums[kNdtTerms], bool mailbox) {
+// one derivative pass at the float transform T and the pose p: the 29 sums (computeDerivatives) -> sums (host); without hessian the
+// trial pass, whose 8 sums (pairs, score, gradient) are the first 8 of the 29 -- sums[8..28] are left as they were
+static int ndt_evaluate(icpgpu_ctx* c, const float T[16], const double p[6], double sums[kNdtTerms], bool mailbox, bool hessian = true) {
   const int n_s = (int)c->src.n;
   int rc = ensure(c, c->ndt_partials, (size_t)ndt_blocks(n_s) * kNdtTerms * sizeof(double));
   if (rc) return rc;
@@ -332,18 +490,64 @@ static int ndt_evaluate(icpgpu_ctx* c, const float T[16], const double p[6], dou
   HIP_TRY(c, launch_ndt_derivatives(c->src.data(), n_s, to_xform(T), N.L, P, static_cast<const int*>(N.key.ptr),
                                     static_cast<const float4*>(N.centroid.ptr), static_cast<const double*>(N.gauss_c.ptr), N.n_cells,
                                     static_cast<double*>(c->ndt_partials.ptr), mailbox ? nullptr : static_cast<double*>(c->sums.ptr),
-                                    mailbox ? c->h_flags_dev : nullptr, mailbox ? wire_seq(c, seq) : 0, c->stream));
+                                    mailbox ? c->h_flags_dev : nullptr, mailbox ? wire_seq(c, seq) : 0, c->stream, hessian));
   c->prof.reduce_launches += 1;
+  const int terms = hessian ? kNdtTerms : kNdtGradTerms;
   if (mailbox) {
-    if ((rc = wait_flags(c, c->h_flags, kNdtTerms, seq))) return rc;
-    for (int k = 0; k < kNdtTerms; ++k) {
+    if ((rc = wait_flags(c, c->h_flags, terms, seq))) return rc;
+    for (int k = 0; k < terms; ++k) {
       const unsigned long long bits = c->h_flags[2 * k];
       std::memcpy(&sums[k], &bits, sizeof bits);
     }
     return ICPGPU_OK;
   }
-  HIP_TRY(c, hipMemcpyAsync(sums, c->sums.ptr, kNdtTerms * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(sums, c->sums.ptr, terms * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return ICPGPU_OK;
+}
+
+// -(g . d) from an evaluation's gradient
+static double ndt_d_phi(const double sums[kNdtTerms], const double d[6]) {
+  double gd = 0.0;
+  for (int k = 0; k < 6; ++k) gd += sums[2 + k] * d[k];
+  return -gd;
+}
+
+// One Newton step under the More-Thuente rule: the direction as ndt_step_impl's, then computeStepLengthMT with its
+// loop running.  The first trial is a 29-term pass (PCL's computeDerivatives with the Hessian), every loop trial a trial pass (score
+// and gradient); when the search ends on a loop trial, one 29-term pass at that trial's pose gives the Hessian (PCL's
+// computeHessian).  On NDT_STEP: p, Tf and sums are those of the accepted trial and *a its step (a = 0 and nothing changes when
+// g . d is exactly 0).
+static int ndt_step_mt(icpgpu_ctx* c, int iteration, double eps, double p[6], float Tf[16], double sums[kNdtTerms], double* a, int* st) {
+  double d[6], norm, d_phi_0;
+  *a = 0.0;
+  *st = ndt_direction(sums, d, &norm, &d_phi_0);
+  if (*st != NDT_STEP || d_phi_0 == 0.0) return ICPGPU_OK;
+  if (d_phi_0 > 0.0) d_phi_0 = -d_phi_0;  // (ndt_direction flipped d)
+  struct Trial {
+    double x[6];
+    float T[16];
+    double sums[kNdtTerms];
+  } cur{}, prev{};
+  mt::Search S;
+  mt::start(S, -sums[1], d_phi_0, norm, c->ndt_step_size, eps / 2.0);
+  int rc, exit;
+  do {
+    const bool first = S.trials == 0;
+    prev = cur;
+    for (int k = 0; k < 6; ++k) cur.x[k] = p[k] + d[k] * S.a_t;
+    ndt_transform_float(cur.x, cur.T);
+    if ((rc = ndt_evaluate(c, cur.T, cur.x, cur.sums, true, /*hessian=*/first))) return rc;
+    const double phi_t = -cur.sums[1], d_phi_t = ndt_d_phi(cur.sums, d);
+    c->ndt_trace.push_back({iteration, S.a_t, phi_t, d_phi_t});
+    exit = mt::observe(S, phi_t, d_phi_t);
+  } while (exit == ICPGPU_NDT_MT_TRIAL);
+  const Trial& acc = S.final_trial == S.trials - 1 ? cur : prev;
+  std::memcpy(p, acc.x, sizeof acc.x);
+  std::memcpy(Tf, acc.T, sizeof acc.T);
+  std::memcpy(sums, acc.sums, sizeof acc.sums);
+  if (S.final_trial > 0 && (rc = ndt_evaluate(c, Tf, p, sums, true, /*hessian=*/true))) return rc;
+  *a = S.a_t;
   return ICPGPU_OK;
 }
 
@@ -356,6 +560,7 @@ int align_ndt(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitne
   c->dev_ms_accum = 0.0;
   c->call_sweeps = c->call_timed = 0;
   c->ndt_probability = NAN;
+  c->ndt_trace.clear();
   float Tf[16];
   for (int i = 0; i < 16; ++i) Tf[i] = guess ? guess[i] : (i % 5 == 0 ? 1.f : 0.f);
   const int n_s = (int)c->src.n, n_t = (int)c->tgt.n;
@@ -376,11 +581,18 @@ int align_ndt(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitne
       converged = true;
       state = ICPGPU_CONV_NO_CORRESPONDENCES;
     } else {
+      const bool more_thuente = c->ndt_line_search == ICPGPU_NDT_LINE_SEARCH_MORE_THUENTE;
       for (;;) {
         double p_new[6], a;
         float T_new[16];
-        bool evaluate;
-        const int st = ndt_step_impl(sums, p, c->ndt_step_size, eps, p_new, &a, T_new, &evaluate);
+        bool evaluate = false;
+        int st;
+        if (more_thuente) {
+          if ((rc = ndt_step_mt(c, nr, eps, p, Tf, sums, &a, &st))) return rc;
+          n_corr = (unsigned)sums[0];
+        } else {
+          st = ndt_step_impl(sums, p, c->ndt_step_size, eps, p_new, &a, T_new, &evaluate);
+        }
         if (st == NDT_ZERO) {
           converged = true;
           state = ICPGPU_CONV_TRANSFORM;
@@ -509,6 +721,67 @@ int icpgpu_ndt_step(const double sums[29], const double p[6], double step_size, 
   if (!sums || !p || !p_out || !step || !T_out) return ICPGPU_ERR_INVALID_ARG;
   bool evaluate;
   return ndt_step_impl(sums, p, step_size, eps, p_out, step, T_out, &evaluate);
+}
+
+int icpgpu_set_ndt_line_search(icpgpu_ctx* c, int mode) {
+  if (!c) return fail(nullptr, ICPGPU_ERR_INVALID_ARG, "null context");
+  if (mode != ICPGPU_NDT_LINE_SEARCH_PCL18 && mode != ICPGPU_NDT_LINE_SEARCH_MORE_THUENTE)
+    return fail(c, ICPGPU_ERR_INVALID_ARG, "NDT: unknown line search %d", mode);
+  c->ndt_line_search = mode;
+  return ICPGPU_OK;
+}
+
+int icpgpu_get_ndt_line_search(const icpgpu_ctx* c, int* mode) {
+  if (!c || !mode) return ICPGPU_ERR_INVALID_ARG;
+  *mode = c->ndt_line_search;
+  return ICPGPU_OK;
+}
+
+int icpgpu_ndt_gradient(icpgpu_ctx* c, const double p[6], double sums[8]) {
+  ENTER(c);
+  if (!p || !sums) return fail(c, ICPGPU_ERR_INVALID_ARG, "null argument");
+  if (!c->src.set || !c->tgt.set) return fail(c, ICPGPU_ERR_NO_INPUT, "ndt_gradient: source and target must be set first");
+  int rc = ensure_ndt_cells(c);
+  if (rc) return rc;
+  if ((rc = ensure(c, c->sums, kNdtTerms * sizeof(double)))) return rc;
+  float T[16];
+  ndt_transform_float(p, T);
+  double all[kNdtTerms];
+  if ((rc = ndt_evaluate(c, T, p, all, /*mailbox=*/false, /*hessian=*/false))) return rc;
+  std::memcpy(sums, all, kNdtGradTerms * sizeof(double));
+  return ICPGPU_OK;
+}
+
+int icpgpu_ndt_line_search_replay(double phi_0, double d_phi_0, double step_init, double step_max, double step_min, const double* phi,
+                                  const double* d_phi, int n, double* step, int* trial) {
+  if (!step || !trial || n < 0 || (n > 0 && (!phi || !d_phi))) return ICPGPU_ERR_INVALID_ARG;
+  if (!std::isfinite(phi_0) || !(d_phi_0 < 0.0) || !std::isfinite(d_phi_0)) return ICPGPU_ERR_INVALID_ARG;
+  mt::Search S;
+  mt::start(S, phi_0, d_phi_0, step_init, step_max, step_min);
+  int st = ICPGPU_NDT_MT_TRIAL;
+  for (int k = 0; k < n; ++k) {
+    if (st != ICPGPU_NDT_MT_TRIAL) return ICPGPU_ERR_INVALID_ARG;  // (an observation after the search has ended)
+    st = mt::observe(S, phi[k], d_phi[k]);
+  }
+  *step = S.a_t;
+  *trial = st == ICPGPU_NDT_MT_TRIAL ? n : S.final_trial;
+  return st;
+}
+
+int icpgpu_ndt_line_search_trace(const icpgpu_ctx* c, size_t capacity, int32_t* iteration, double* step, double* phi, double* d_phi,
+                                 size_t* n_trials) {
+  if (!c || !n_trials) return ICPGPU_ERR_INVALID_ARG;
+  const size_t n = c->ndt_trace.size();
+  *n_trials = n;
+  if (n > capacity) return ICPGPU_OK;  // (the count alone: size the buffers and call again)
+  for (size_t i = 0; i < n; ++i) {
+    const auto& t = c->ndt_trace[i];
+    if (iteration) iteration[i] = t.iteration;
+    if (step) step[i] = t.a;
+    if (phi) phi[i] = t.phi;
+    if (d_phi) d_phi[i] = t.dphi;
+  }
+  return ICPGPU_OK;
 }
 
 }  // extern "C"

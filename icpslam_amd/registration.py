@@ -273,9 +273,42 @@ class Context:
         return solve_point_to_plane(sums)
 
     # NDT mode (method NDT) -------------------------------------------------------------------------------------
-    def set_ndt_params(self, resolution: float = 1.0, step_size: float = 0.1, outlier_ratio: float = 0.55):
-        """icpgpu_set_ndt_params: setResolution / setStepSize / setOulierRatio (PCL's defaults)."""
+    def set_ndt_params(self, resolution: float = 1.0, step_size: float = 0.1, outlier_ratio: float = 0.55, line_search: int | None = None):
+        """icpgpu_set_ndt_params: setResolution / setStepSize / setOulierRatio (PCL's defaults); line_search (None: unchanged) =
+        icpgpu_set_ndt_line_search's mode, NDT_LINE_SEARCH_PCL18 or NDT_LINE_SEARCH_MORE_THUENTE."""
         self._check(self._L.icpgpu_set_ndt_params(self._h, float(resolution), float(step_size), float(outlier_ratio)))
+        if line_search is not None:
+            self.set_ndt_line_search(line_search)
+
+    def set_ndt_line_search(self, mode: int):
+        """icpgpu_set_ndt_line_search: the NDT step rule, NDT_LINE_SEARCH_PCL18 (default) or NDT_LINE_SEARCH_MORE_THUENTE."""
+        self._check(self._L.icpgpu_set_ndt_line_search(self._h, int(mode)))
+
+    def get_ndt_line_search(self) -> int:
+        v = C.c_int32()
+        self._check(self._L.icpgpu_get_ndt_line_search(self._h, C.byref(v)))
+        return v.value
+
+    def ndt_gradient(self, p) -> np.ndarray:
+        """icpgpu_ndt_gradient: the line search's trial pass at p -- (8,) float64 = pairs, score, gradient (6), the bits of
+        ndt_derivatives(p)[:8]."""
+        p = np.ascontiguousarray(p, np.float64).reshape(6)
+        sums = np.zeros(8, np.float64)
+        dp = C.POINTER(C.c_double)
+        self._check(self._L.icpgpu_ndt_gradient(self._h, p.ctypes.data_as(dp), sums.ctypes.data_as(dp)))
+        return sums
+
+    def ndt_line_search_trace(self) -> dict:
+        """icpgpu_ndt_line_search_trace: the last NDT alignment's More-Thuente trials -- iteration (n,) int32, step, phi, d_phi (n,)."""
+        n = C.c_size_t()
+        self._check(self._L.icpgpu_ndt_line_search_trace(self._h, 0, None, None, None, None, C.byref(n)))
+        k = n.value
+        it = np.zeros(k, np.int32)
+        a, phi, dphi = (np.zeros(k, np.float64) for _ in range(3))
+        dp = C.POINTER(C.c_double)
+        self._check(self._L.icpgpu_ndt_line_search_trace(self._h, k, it.ctypes.data_as(C.POINTER(C.c_int32)), a.ctypes.data_as(dp),
+                                                         phi.ctypes.data_as(dp), dphi.ctypes.data_as(dp), C.byref(n)))
+        return dict(iteration=it, step=a, phi=phi, d_phi=dphi)
 
     def get_ndt_params(self) -> dict:
         v = [C.c_double(), C.c_double(), C.c_double()]
@@ -394,6 +427,25 @@ def ndt_step(sums, p, step_size: float, eps: float):
     if rc < 0:
         raise IcpGpuError(rc, "ndt_step: bad argument")
     return rc, p_out, step.value, T.reshape(4, 4).T.copy()
+
+
+def ndt_line_search_replay(phi_0: float, d_phi_0: float, step_init: float, step_max: float, step_min: float, phi=(), d_phi=()):
+    """icpgpu_ndt_line_search_replay (host only): the More-Thuente search replayed from its trials' observations ->
+    (status, step, trial): status MT_TRIAL with the next trial's step and index, or the exit (MT_WOLFE ...) with the accepted step
+    and trial."""
+    L = _lib.load()
+    phi = np.ascontiguousarray(phi, np.float64).reshape(-1)
+    d_phi = np.ascontiguousarray(d_phi, np.float64).reshape(-1)
+    if len(phi) != len(d_phi):
+        raise ValueError("phi and d_phi differ in length")
+    step = C.c_double()
+    trial = C.c_int32()
+    dp = C.POINTER(C.c_double)
+    rc = L.icpgpu_ndt_line_search_replay(float(phi_0), float(d_phi_0), float(step_init), float(step_max), float(step_min),
+                                         phi.ctypes.data_as(dp), d_phi.ctypes.data_as(dp), len(phi), C.byref(step), C.byref(trial))
+    if rc < 0:
+        raise IcpGpuError(rc, "ndt_line_search_replay: bad argument")
+    return rc, step.value, trial.value
 
 
 def solve_point_to_plane(sums):
@@ -523,8 +575,16 @@ class NormalDistributionsTransform(IterativeClosestPoint):
         super().__init__(device_id, method)
         self._params.max_iterations = 35
         self._params.transformation_epsilon = 0.1
-        self._ndt = dict(resolution=1.0, step_size=0.1, outlier_ratio=0.55)
+        self._ndt = dict(resolution=1.0, step_size=0.1, outlier_ratio=0.55, line_search=_lib.NDT_LINE_SEARCH_PCL18)
         self._probability = float("nan")
+
+    def setMoreThuenteLineSearch(self, on: bool):
+        """NOT a PCL method (the C++ shim has the same one): the More-Thuente line search with its loop running instead of PCL 1.8's
+        clamped Newton step (icpgpu_set_ndt_line_search; include/icpgpu.h)."""
+        self._ndt["line_search"] = _lib.NDT_LINE_SEARCH_MORE_THUENTE if on else _lib.NDT_LINE_SEARCH_PCL18
+
+    def getMoreThuenteLineSearch(self) -> bool:
+        return self._ndt["line_search"] == _lib.NDT_LINE_SEARCH_MORE_THUENTE
 
     def setResolution(self, r):
         self._ndt["resolution"] = float(r)

@@ -49,7 +49,8 @@ extern "C" {
  * icpgpu_align_batch_multi) are NOT exported any more, so a binary built against a 0.x header fails at load time instead of
  * overrunning its structs.  History: 1.2 ICPGPU_P2PLANE, icpgpu_set_target_normals, icpgpu_normals, icpgpu_reduce_point_to_plane,
  * icpgpu_solve_point_to_plane; added under 1.2: ICPGPU_NDT, icpgpu_set_ndt_params, icpgpu_get_ndt_params,
- * icpgpu_ndt_transformation_probability, icpgpu_ndt_cells, icpgpu_ndt_derivatives, icpgpu_ndt_step (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
+ * icpgpu_ndt_transformation_probability, icpgpu_ndt_cells, icpgpu_ndt_derivatives, icpgpu_ndt_step, icpgpu_set_ndt_line_search,
+ * icpgpu_get_ndt_line_search, icpgpu_ndt_gradient, icpgpu_ndt_line_search_replay, icpgpu_ndt_line_search_trace (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
  * icpgpu_profile.gicp_quadratic_solves; 0.3 icpgpu_profile (sources_adopted, gicp_host_solves, gicp_solver_choice). */
 
@@ -398,6 +399,39 @@ int icpgpu_ndt_derivatives(icpgpu_ctx* ctx, const double p[6], double sums[29]);
  * (p_out = p, *step = 0, T_out = T(p): the loop stops). */
 int icpgpu_ndt_step(const double sums[29], const double p[6], double step_size, double eps, double p_out[6], double* step,
                     float T_out[16]);
+/* The step rule of the NDT Newton loop, per context (added under 1.2).  PCL18 (default): PCL 1.8's computeStepLengthMT, whose
+ * More-Thuente loop never runs -- the step is the Newton length clamped to [eps / 2, step_size], one derivative pass per iteration.
+ * MORE_THUENTE: the same function with its loop running (More & Thuente 1994; mu 1e-4, nu 0.9, at most 10 loop trials): the first
+ * trial is a 29-term pass, every further trial a score-and-gradient pass (icpgpu_ndt_gradient), and one 29-term pass at the accepted
+ * pose when a loop trial was accepted.  Everything else (direction, stopping test, result fields) is the same in both modes; DESIGN.md
+ * (f6) states the rule and its two deviations (a NaN candidate step, a non-finite trial).  Any other mode: ICPGPU_ERR_INVALID_ARG.
+ * icpgpu_align_batch* refuse NDT in both modes. */
+typedef enum { ICPGPU_NDT_LINE_SEARCH_PCL18 = 0, ICPGPU_NDT_LINE_SEARCH_MORE_THUENTE = 1 } icpgpu_ndt_line_search;
+int icpgpu_set_ndt_line_search(icpgpu_ctx* ctx, int mode);
+int icpgpu_get_ndt_line_search(const icpgpu_ctx* ctx, int* mode);
+/* the trial pass at p: sums = {pairs, score, gradient (6)}, the same bits as the first 8 of icpgpu_ndt_derivatives at p */
+int icpgpu_ndt_gradient(icpgpu_ctx* ctx, const double p[6], double sums[8]);
+/* How a More-Thuente search ends (icpgpu_ndt_line_search_replay's return value; TRIAL = not yet). */
+typedef enum {
+  ICPGPU_NDT_MT_TRIAL = 0,      /* not ended: *step is the next trial's step */
+  ICPGPU_NDT_MT_WOLFE = 1,      /* psi(a) <= 0 and phi'(a) <= -nu phi'(0) (PCL's sufficient decrease and curvature tests) */
+  ICPGPU_NDT_MT_INTERVAL = 2,   /* updateIntervalMT found the interval converged (or it starts converged: step_max < step_min) */
+  ICPGPU_NDT_MT_TRIAL_CAP = 3,  /* 10 loop trials */
+  ICPGPU_NDT_MT_NAN_STEP = 4,   /* the next candidate step is NaN: the last trial is accepted (deviation) */
+  ICPGPU_NDT_MT_NON_FINITE = 5  /* a trial's phi or phi' is not finite: the previous trial is accepted, the first trial itself
+                                   when it is the one (deviation) */
+} icpgpu_ndt_mt_exit;
+/* (host) the More-Thuente search replayed from what its trials observed: phi_0 = -score at p, d_phi_0 = -(g . d) < 0 for the
+ * descending unit direction d, step_init = |delta|, step_max = step_size, step_min = eps / 2; phi[i], d_phi[i] (i < n) = -score and
+ * -(g . d) at trial i.  Returns ICPGPU_NDT_MT_TRIAL with *step = trial n's step and *trial = n, or the exit with *step = the
+ * accepted step and *trial = the accepted trial's index; ICPGPU_ERR_INVALID_ARG for a non-finite phi_0, d_phi_0 >= 0 or not finite,
+ * a null pointer, or observations past the exit. */
+int icpgpu_ndt_line_search_replay(double phi_0, double d_phi_0, double step_init, double step_max, double step_min, const double* phi,
+                                  const double* d_phi, int n, double* step, int* trial);
+/* the last NDT alignment's line-search trials (MORE_THUENTE; none under PCL18), in order: the Newton iteration (0-based), the step,
+ * phi = -score and phi' = -(g . d).  *n_trials = their number; nothing is copied when it exceeds capacity.  Any output may be NULL. */
+int icpgpu_ndt_line_search_trace(const icpgpu_ctx* ctx, size_t capacity, int32_t* iteration, double* step, double* phi, double* d_phi,
+                                 size_t* n_trials);
 
 /* ICPGPU_GICP_DEVICE=auto only: time GICP's two inner solvers on THIS box with the context's current source, target and parameters
  * (method GICP; a few alignments whose results are discarded) and keep the faster for the context's single alignments from now on.

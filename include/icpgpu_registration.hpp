@@ -268,6 +268,11 @@ class IterativeClosestPoint {
   using PointT = typename std::remove_reference<decltype(std::declval<CloudT>().points[0])>::type;
   static_assert(sizeof(PointT) == 16, "point type must be the 16-byte pcl::PointXYZ layout");
 
+  bool apply_ndt() {
+    return icpgpu_set_ndt_params(ctx_, ndt_[0], ndt_[1], ndt_[2]) == ICPGPU_OK &&
+           icpgpu_set_ndt_line_search(ctx_, ndt_line_search_) == ICPGPU_OK;
+  }
+
   bool upload() {
     // the TARGET first: it is usually the cloud the context still holds as the previous scan's source
     // (`*prev_cloud_ = *curr_cloud_`, icp_odometer.cpp:209), which icpgpu_set_target recognises -- no upload, the grid
@@ -283,12 +288,12 @@ class IterativeClosestPoint {
         bound_ = true;
       }
       if (icpgpu_set_params(ctx_, &params_) != ICPGPU_OK) return false;
-      if (params_.method == ICPGPU_NDT && icpgpu_set_ndt_params(ctx_, ndt_[0], ndt_[1], ndt_[2]) != ICPGPU_OK) return false;
+      if (params_.method == ICPGPU_NDT && !apply_ndt()) return false;
       if (icpgpu_set_target(ctx_, nt ? reinterpret_cast<const float*>(&target_->points[0]) : nullptr, nt) != ICPGPU_OK) return false;
       // (after set_target, which drops the normals a target had: IterativeClosestPointWithNormals::setTargetNormals)
       if (target_normals_ && icpgpu_set_target_normals(ctx_, target_normals_, n_target_normals_) != ICPGPU_OK) return false;
     } else if (icpgpu_set_params(ctx_, &params_) != ICPGPU_OK ||
-               (params_.method == ICPGPU_NDT && icpgpu_set_ndt_params(ctx_, ndt_[0], ndt_[1], ndt_[2]) != ICPGPU_OK)) {
+               (params_.method == ICPGPU_NDT && !apply_ndt())) {
       return false;
     }
     const std::size_t ns = source_->points.size();
@@ -344,6 +349,7 @@ class IterativeClosestPoint {
   const float* target_normals_ = nullptr;  // (IterativeClosestPointWithNormals: the caller's target normals, n float4)
   std::size_t n_target_normals_ = 0;
   double ndt_[3] = {1.0, 0.1, 0.55};  // (NormalDistributionsTransform: resolution, step size, outlier ratio)
+  int ndt_line_search_ = ICPGPU_NDT_LINE_SEARCH_PCL18;  // (NormalDistributionsTransform::setMoreThuenteLineSearch)
   icpgpu_ctx* context() const { return ctx_; }
 
  private:
@@ -403,6 +409,12 @@ class NormalDistributionsTransform : public IterativeClosestPoint<CloudT> {
   double getStepSize() const { return this->ndt_[1]; }
   void setOulierRatio(double outlier_ratio) { this->ndt_[2] = outlier_ratio; }  // (PCL's spelling)
   double getOulierRatio() const { return this->ndt_[2]; }
+  // NOT a PCL method: the More-Thuente line search with its loop running instead of PCL 1.8's clamped Newton step
+  // (icpgpu_set_ndt_line_search; include/icpgpu.h)
+  void setMoreThuenteLineSearch(bool on) {
+    this->ndt_line_search_ = on ? ICPGPU_NDT_LINE_SEARCH_MORE_THUENTE : ICPGPU_NDT_LINE_SEARCH_PCL18;
+  }
+  bool getMoreThuenteLineSearch() const { return this->ndt_line_search_ == ICPGPU_NDT_LINE_SEARCH_MORE_THUENTE; }
   void align(CloudT& output) {
     IterativeClosestPoint<CloudT>::align(output);
     fetch_probability();
