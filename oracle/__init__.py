@@ -50,10 +50,23 @@ class P2planeTrace(C.Structure):
                 ("mse", C.c_double)]
 
 
+class NdtLattice(C.Structure):
+    _fields_ = [("minb", C.c_int32 * 3), ("divb", C.c_int32 * 3), ("mul_y", C.c_int32), ("mul_z", C.c_int32),
+                ("inv_leaf_f", C.c_float), ("has_cells", C.c_int32), ("max_excess", C.c_double)]
+
+
+# orc_ndt_cell, field for field
+NDT_CELL_DTYPE = np.dtype([("key", np.int32), ("n", np.int32), ("valid", np.int32), ("floored", np.int32),
+                           ("centroid", np.float32, 4), ("mean", np.float64, 3), ("cov", np.float64, (3, 3)),
+                           ("eig", np.float64, 3), ("icov", np.float64, (3, 3)), ("margin", np.float64),
+                           ("excess", np.float64), ("resid", np.float64)], align=True)
+NDT_SEARCH_BRUTE, NDT_SEARCH_HASH = 0, 1
+
+
 def build(force: bool = False) -> str:
     """Compile oracle/liboracle.so with the committed Makefile (gcc only)."""
-    srcs = [os.path.join(_HERE, f) for f in ("icp_oracle.c", "gicp_oracle.c", "map_oracle.c", "p2plane_oracle.c", "icp_oracle.h",
-                                            "Makefile")]
+    srcs = [os.path.join(_HERE, f) for f in ("icp_oracle.c", "gicp_oracle.c", "map_oracle.c", "p2plane_oracle.c", "ndt_oracle.c",
+                                            "icp_oracle.h", "Makefile")]
     stale = (not os.path.exists(_LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(_LIB_PATH) for s in srcs)
     if force or stale:
@@ -96,6 +109,16 @@ def lib():
         L.orc_p2plane_solve.argtypes = [dp, dp]
         L.orc_p2plane_align.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.POINTER(Params), fp, fp, C.c_int,
                                         C.POINTER(Result), C.POINTER(P2planeTrace)]
+        L.orc_ndt_transform.argtypes = [dp, fp]
+        L.orc_ndt_transform.restype = None
+        L.orc_ndt_angle_terms.argtypes = [dp, dp, dp]
+        L.orc_ndt_angle_terms.restype = None
+        L.orc_ndt_cells.argtypes = [fp, C.c_size_t, C.c_double, C.POINTER(NdtLattice), C.POINTER(C.c_void_p)]
+        L.orc_ndt_cells.restype = C.c_long
+        L.orc_ndt_free.argtypes = [C.c_void_p]
+        L.orc_ndt_free.restype = None
+        L.orc_ndt_derivatives.argtypes = [fp, dp, dp, C.c_size_t, fp, C.c_size_t, dp, C.c_double, C.c_double, C.c_int, dp, dp,
+                                          C.POINTER(C.c_int64), ip, ip, C.c_size_t]
         L.orc_map_create.argtypes = [C.c_double]
         L.orc_map_create.restype = C.c_void_p
         L.orc_map_destroy.argtypes = [C.c_void_p]
@@ -282,6 +305,82 @@ def p2plane_align(src, tgt, params: Params | None = None, guess=None, normals=No
     return dict(T=res.matrix(), converged=bool(res.converged), iterations=int(res.iterations),
                 state=int(res.convergence_state), n_corr=int(res.n_correspondences), mse=float(res.mse_last),
                 fitness=float(res.fitness), cloud=out, trace=steps)
+
+
+def ndt_transform(p) -> np.ndarray:
+    """T(p) = Translation3f * AngleAxisf(X) * AngleAxisf(Y) * AngleAxisf(Z), 4x4 float32 (sinf / cosf rounded once from binary128)"""
+    p = np.ascontiguousarray(p, np.float64).reshape(6)
+    T = np.zeros(16, np.float32)
+    lib().orc_ndt_transform(p.ctypes.data_as(C.POINTER(C.c_double)), T.ctypes.data_as(C.POINTER(C.c_float)))
+    return T.reshape(4, 4).T.copy()
+
+
+def ndt_angle_terms(p):
+    """PCL's j_ang (8, 3) and h_ang (15, 3) at the angles of p (binary128 sin / cos rounded to double, |angle| < 1e-4 rule)"""
+    p = np.ascontiguousarray(p, np.float64).reshape(6)
+    j, h = np.zeros(24), np.zeros(45)
+    dp = C.POINTER(C.c_double)
+    lib().orc_ndt_angle_terms(p.ctypes.data_as(dp), j.ctypes.data_as(dp), h.ctypes.data_as(dp))
+    return j.reshape(8, 3), h.reshape(15, 3)
+
+
+class NdtOverflow(ValueError):
+    """The cell index overflows int32 at this resolution (the library refuses the target)."""
+
+
+def ndt_cells(cloud, resolution: float) -> dict:
+    """Every occupied NDT cell of `cloud` in key order (oracle/ndt_oracle.c): a structured array (NDT_CELL_DTYPE) under "cells",
+    the lattice (minb, divb, mul_y, mul_z, inv_leaf_f) and max_excess (the largest e over the valid cells)."""
+    cloud, pc = _f32(cloud)
+    L = NdtLattice()
+    out = C.c_void_p()
+    n = lib().orc_ndt_cells(pc, cloud.shape[0], float(resolution), C.byref(L), C.byref(out))
+    if n == -1:
+        raise NdtOverflow(resolution)
+    if n < 0:
+        raise MemoryError("orc_ndt_cells")
+    cells = np.zeros(0, NDT_CELL_DTYPE)
+    if out.value:
+        try:
+            if n > 0:
+                buf = (C.c_char * (n * NDT_CELL_DTYPE.itemsize)).from_address(out.value)
+                cells = np.frombuffer(buf, NDT_CELL_DTYPE).copy()
+        finally:
+            lib().orc_ndt_free(out)
+    return dict(cells=cells, minb=list(L.minb), divb=list(L.divb), mul_y=L.mul_y, mul_z=L.mul_z, inv_leaf_f=np.float32(L.inv_leaf_f),
+                has_cells=bool(L.has_cells), max_excess=L.max_excess)
+
+
+def ndt_derivatives(cells, src, p, resolution: float, outlier_ratio: float = 0.55, search=NDT_SEARCH_HASH, pairs: int = 0):
+    """The 29 sums of one NDT pass at p over `cells` -- either ndt_cells()'s result (its valid cells) or a dict with centroid
+    (m, 4) float32, mean (m, 3) and icov (m, 3, 3) such as the library's ndt_cells() -- and the source.  -> dict(sums, mag,
+    pairs, skipped, near, accepted[, pair_pt, pair_cell: the first `pairs` pairs])."""
+    if "cells" in cells:
+        v = cells["cells"][cells["cells"]["valid"] != 0]
+        cent, mean, icov = v["centroid"], v["mean"], v["icov"]
+    else:
+        cent, mean, icov = cells["centroid"], cells["mean"], cells["icov"]
+    cent, pcent = _f32(np.asarray(cent).reshape(-1, 4))
+    mean = np.ascontiguousarray(mean, np.float64).reshape(-1, 3)
+    ic = np.asarray(icov, np.float64).reshape(-1, 3, 3)
+    ic6 = np.ascontiguousarray(ic.reshape(-1, 9)[:, [0, 1, 2, 4, 5, 8]])
+    src, ps = _f32(src)
+    p = np.ascontiguousarray(p, np.float64).reshape(6)
+    sums, mag = np.zeros(29), np.zeros(29)
+    stats = np.zeros(4, np.int64)
+    pp, pcl = np.zeros(max(pairs, 1), np.int32), np.zeros(max(pairs, 1), np.int32)
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    rc = lib().orc_ndt_derivatives(pcent, mean.ctypes.data_as(dp), ic6.ctypes.data_as(dp), cent.shape[0], ps, src.shape[0],
+                                   p.ctypes.data_as(dp), float(resolution), float(outlier_ratio), int(search), sums.ctypes.data_as(dp),
+                                   mag.ctypes.data_as(dp), stats.ctypes.data_as(C.POINTER(C.c_int64)), pp.ctypes.data_as(ip),
+                                   pcl.ctypes.data_as(ip), int(pairs))
+    if rc != 0:
+        raise MemoryError("orc_ndt_derivatives")
+    out = dict(sums=sums, mag=mag, pairs=int(stats[0]), skipped=int(stats[1]), near=int(stats[2]), accepted=int(stats[3]))
+    if pairs:
+        k = min(pairs, int(stats[0]))
+        out["pair_pt"], out["pair_cell"] = pp[:k].copy(), pcl[:k].copy()
+    return out
 
 
 def voxel_grid(cloud, leaf: float):
