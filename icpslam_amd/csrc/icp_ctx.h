@@ -462,7 +462,19 @@ struct P2PRun {
 
 // A GICP registration as a resumable run (icpgpu_gicp.cpp: gicp_run_begin / gicp_run_step): the counterpart of P2PRun for the
 // solver the reference instantiates, so that one host thread of icpgpu_align_batch keeps several registrations in flight.
-struct GicpRun {
+// What a GICP registration carries from one outer iteration to the next, whichever way it is driven: align_gicp keeps one on its
+// stack, a GicpRun is one plus what a run needs between its polls.  The steps over it are stated once (icpgpu_gicp.cpp).
+struct GicpState {
+  float guess[16], transformation[16], previous[16];
+  float thr = 0.f, thr_excl = 0.f;
+  int nr = 0, state = ICPGPU_NOT_CONVERGED;
+  bool converged = false;
+  unsigned n_corr = 0;
+  double mse = 0.0;
+  icpgpu_result* res = nullptr;
+  std::chrono::steady_clock::time_point t_start;
+};
+struct GicpRun : GicpState {
   enum Phase { Idle, Blocking, CovGrid, WantSolve, Solve, Quad, Fitness, Done } phase = Idle;  // Quad: waiting for the quadratic form's sums
   bool quadratic = false;  // icpgpu_params.gicp_inner = QUADRATIC: every outer iteration is search + one pass + BFGS on the host
   // combine: the run does not launch its outer iteration's solver itself -- it stops in WantSolve with `item` filled in, and the
@@ -470,18 +482,13 @@ struct GicpRun {
   bool combine = false;
   GicpSolveItem item{};
   hipStream_t solve_stream = nullptr;  // where the run's solver was launched (its own stream unless combined)
-  float guess[16], transformation[16], previous[16];
-  float thr = 0.f, thr_excl = 0.f;
-  int nr = 0, state = ICPGPU_NOT_CONVERGED, want_fitness = 0, cov_stage = 0;
-  bool converged = false, local = false;
-  unsigned n_corr = 0;
-  double mse = 0.0;
+  int want_fitness = 0, cov_stage = 0;
+  bool local = false;
   GridBuild gb;
   unsigned long long marker = 0, seq0 = 0;
   unsigned polls = 0;
   SweepTicket ticket;
-  icpgpu_result* res = nullptr;
-  std::chrono::steady_clock::time_point t_start, t_issue;
+  std::chrono::steady_clock::time_point t_issue;
 };
 
 // ---- helpers that cross unit boundaries -------------------------------------------------------------------------------------
@@ -571,7 +578,7 @@ int covariance_grid_check(icpgpu_ctx* c);
 int align_gicp(icpgpu_ctx* c, const float* guess_in, float* out_xyzw, int want_fitness, icpgpu_result* res);
 int gicp_run_begin(icpgpu_ctx* c, GicpRun& r, int want_fitness, icpgpu_result* res, bool combine = false);
 int gicp_run_step(icpgpu_ctx* c, GicpRun& r);  // < 0 error, 0 nothing yet, 1 moved on (r.phase == GicpRun::Done: finished)
-void gicp_run_solver_launched(icpgpu_ctx* c, GicpRun& r, hipStream_t solve_stream);  // WantSolve -> Solve (the scheduler launched r.item)
+void gicp_run_solver_launched(icpgpu_ctx*, GicpRun& r, hipStream_t solve_stream);  // WantSolve -> Solve (the scheduler launched r.item)
 // icpgpu_p2plane.cpp
 int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitness, icpgpu_result* res);
 // x = (A^T A)^-1 A^T r from the 29 sums (partial-pivot LU, float64) -> Tk = constructTransformationMatrix(x); false (Tk = identity)
@@ -581,3 +588,5 @@ bool solve_point_to_plane(const double sums[kP2planeTerms], Mat4d& Tk);
 int align_ndt(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitness, icpgpu_result* res);
 
 }  // namespace icpgpu_impl
+
+#include "icp_wait.h"

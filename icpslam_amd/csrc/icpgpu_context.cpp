@@ -106,32 +106,17 @@ unsigned long long sample_fingerprint(const float* xyzw, size_t n) {
 // (out may be null).  The stream is queried now and then so that a faulted kernel turns into an error instead of an endless wait,
 // and the clock so that a hung one does.  `what` names the thing waited for in those messages.
 int wait_posted(icpgpu_ctx* c, const volatile unsigned long long* box, int n, unsigned long long number, int* out, const char* what) {
-  std::chrono::steady_clock::time_point t0;
-  for (unsigned spins = 1;; ++spins) {
+  // (a drained stream does not end this wait, only the clock does: so it has been since the three loops this one replaced; kept)
+  return wait_mailbox(c, c->stream, what, [&] {
     bool all = true;
     for (int k = 0; k < n && all; ++k) all = (box[2 * k + 1] >> 24) == number;
-    if (all) {
-      unsigned long long bits;
-      for (int k = 0; k < n && all; ++k) {
-        all = mailbox_read(box + 2 * k, number, &bits);  // (a torn pair: looked at again)
-        if (all && out) out[k] = (int)(unsigned int)bits;
-      }
-      if (all) break;
+    unsigned long long bits;
+    for (int k = 0; k < n && all; ++k) {
+      all = mailbox_read(box + 2 * k, number, &bits);  // (a torn pair: looked at again)
+      if (all && out) out[k] = (int)(unsigned int)bits;
     }
-    if ((spins & 0x3FFu) == 0) {
-      const hipError_t q = hipStreamQuery(c->stream);
-      if (q != hipSuccess && q != hipErrorNotReady) return fail(c, ICPGPU_ERR_HIP, "HIP error while waiting for %s: %s", what, hipGetErrorString(q));
-      const auto now = std::chrono::steady_clock::now();
-      if (spins == 0x400u) t0 = now;
-      else if (std::chrono::duration<double, std::milli>(now - t0).count() > wait_timeout_ms())
-        return fail(c, ICPGPU_ERR_HIP, "timed out after %.0f ms waiting for %s (hung kernel?)", wait_timeout_ms(), what);
-    }
-#if defined(__x86_64__)
-    __builtin_ia32_pause();
-#endif
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return ICPGPU_OK;
+    return all;
+  }, WhenIdle::KeepWaiting);
 }
 
 int fetch_ints(icpgpu_ctx* c, const int* d_src, int n, int* host_dst) {

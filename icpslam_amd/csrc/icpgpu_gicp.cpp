@@ -325,77 +325,47 @@ __attribute__((always_inline)) static inline bool gicp_tags_ready_body(const dou
 __attribute__((target_clones("avx2", "default")))
 #endif
 static bool gicp_tags_ready(const double* mailbox, int n_blocks, unsigned long long seq) { return gicp_tags_ready_body(mailbox, n_blocks, seq); }
+// development flavour, ICPGPU_GICP_TIMING=1: host wall per stage of align_gicp and per part of an evaluation (printed by
+// icpgpu_destroy).  Read once, here; everything that times itself asks this.
+static bool gicp_timing() {
+  static const bool on = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_GICP_TIMING"); return e && std::atoi(e) != 0; }();
+  return on;
+}
 // 0 = all entries of evaluation `seq` are there, 1 = the stream went idle without them (the server gave up), < 0 = error
 static int wait_gicp_tags(icpgpu_ctx* c, int n_blocks, unsigned long long seq, bool server) {
-  std::chrono::steady_clock::time_point t0;
-  static const bool timing = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_GICP_TIMING"); return e && std::atoi(e) != 0; }();
+  const bool timing = gicp_timing();  // (when does the FIRST workgroup's result show up, when the last?)
   bool any_seen = false;
   std::chrono::steady_clock::time_point t_any;
-  for (unsigned spins = 1;; ++spins) {
-    if (timing && !any_seen) {  // (development flavour: when does the FIRST workgroup's result show up, when the last?)
+  const int w = wait_mailbox(c, c->stream, "a GICP evaluation", [&] {
+    if (timing && !any_seen) {
       const volatile unsigned long long* w = reinterpret_cast<const volatile unsigned long long*>(c->h_gicp);
       for (int b = 0; b < n_blocks && !any_seen; ++b) any_seen = (w[(size_t)b * kGicpPartialStride + 8 * (kGicpLines - 1) + 7] >> 24) == seq;
       if (any_seen) t_any = std::chrono::steady_clock::now();
     }
-    if (gicp_tags_ready(c->h_gicp, n_blocks, seq)) {
-      if (timing && any_seen) c->gt_trickle += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_any).count();
-      break;
-    }
-    if ((spins & 0x3FFu) == 0) {
-      const hipError_t q = hipStreamQuery(c->stream);
-      if (q == hipSuccess) {
-        if (gicp_tags_ready(c->h_gicp, n_blocks, seq)) break;
-        if (server) return 1;
-        return fail(c, ICPGPU_ERR_HIP, "GICP evaluation finished without publishing its result");
-      }
-      if (q != hipErrorNotReady) return fail(c, ICPGPU_ERR_HIP, "HIP error while waiting for a GICP evaluation: %s", hipGetErrorString(q));
-      const auto now = std::chrono::steady_clock::now();
-      if (spins == 0x400u) t0 = now;
-      else if (std::chrono::duration<double, std::milli>(now - t0).count() > wait_timeout_ms())
-        return fail(c, ICPGPU_ERR_HIP, "timed out after %.0f ms waiting for a GICP evaluation (hung kernel?)", wait_timeout_ms());
-    }
-#if defined(__x86_64__)
-    __builtin_ia32_pause();
-#endif
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return 0;
+    return gicp_tags_ready(c->h_gicp, n_blocks, seq);
+  });
+  if (w == 0 && timing && any_seen) c->gt_trickle += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_any).count();
+  // a drained stream: the server leaves after 50 ms without a command, and its caller evaluates by single launches from then on; a
+  // single launch that has retired without its answer is an error
+  if (w == 1 && !server) return fail(c, ICPGPU_ERR_HIP, "GICP evaluation finished without publishing its result");
+  return w;
 }
 
-// The device solver's result: kSolveOut granules carrying number `seq`.  0 = all there (values in out[]), 1 = the stream went
-// idle without them (the kernel gave up: the caller falls back to the host's solver), < 0 = error.
-static int wait_solve_result(icpgpu_ctx* c, unsigned long long seq, double* out) {
+// The device solver's result: kSolveOut granules carrying number `seq` (a resumable run polls the same read).
+static bool solve_result_read(const icpgpu_ctx* c, unsigned long long seq, double* out) {
   const int n = gicp_solve_out_granules();
-  auto all_there = [&]() {
-    bool all = true;
-    for (int k = 0; k < n; ++k) all = gicp_granule_read(c->h_solve + 2 * k, seq, &out[k]) && all;
-    return all;
-  };
-  std::chrono::steady_clock::time_point t0;
-  for (unsigned spins = 1;; ++spins) {
-    if (all_there()) break;
-    if ((spins & 0x3FFu) == 0) {
-      const hipError_t q = hipStreamQuery(c->stream);
-      if (q == hipSuccess) {
-        if (all_there()) break;
-        return 1;
-      }
-      if (q != hipErrorNotReady) return fail(c, ICPGPU_ERR_HIP, "HIP error while waiting for the GICP device solver: %s", hipGetErrorString(q));
-      const auto now = std::chrono::steady_clock::now();
-      if (spins == 0x400u) t0 = now;
-      else if (std::chrono::duration<double, std::milli>(now - t0).count() > wait_timeout_ms())
-        return fail(c, ICPGPU_ERR_HIP, "timed out after %.0f ms waiting for the GICP device solver (hung kernel?)", wait_timeout_ms());
-    }
-#if defined(__x86_64__)
-    __builtin_ia32_pause();
-#endif
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return 0;
+  bool all = true;
+  for (int k = 0; k < n; ++k) all = gicp_granule_read(c->h_solve + 2 * k, seq, &out[k]) && all;
+  return all;
+}
+// 0 = all there (values in out[]), 1 = the stream went idle without them (the kernel gave up: the caller falls back to the host's
+// solver), < 0 = error.
+static int wait_solve_result(icpgpu_ctx* c, unsigned long long seq, double* out) {
+  return wait_mailbox(c, c->stream, "the GICP device solver", [&] { return solve_result_read(c, seq, out); });
 }
 
-// The quadratic form of an outer iteration (gicp_quadratic_kernel): 2 x kGicpQuadSums result pairs numbered `seq`.  all_there()
-// is also what a resumable run polls.
+// The quadratic form of an outer iteration (gicp_quadratic_kernel): 2 x kGicpQuadSums result pairs numbered `seq`.
+// quad_sums_read is also what a resumable run polls.
 // launch one pass (numbered seq) on the context's stream
 static int quad_pass_launch(icpgpu_ctx* c, int n_s, const unsigned long long* keys, float thr_excl, const Rot3d& R, unsigned long long seq) {
   if (c->quad_pending) HIP_TRY(c, hipMemsetAsync(c->quad_done, 0, sizeof(unsigned int), c->stream));  // the last pass never reported: its counter may be mid-count
@@ -410,30 +380,14 @@ static bool quad_sums_read(const icpgpu_ctx* c, unsigned long long seq, double* 
   for (int k = 0; k < 2 * kGicpQuadSums; ++k) all = gicp_granule_read(c->h_quad + 2 * k, seq, &sums[k]) && all;
   return all;
 }
+// (the pass is one kernel: once the stream has drained nothing will post the sums any more -- an error for whoever waits)
+static int quad_sums_lost(icpgpu_ctx* c) { return fail(c, ICPGPU_ERR_HIP, "the GICP quadratic pass finished without publishing its sums"); }
 static int wait_quad_sums(icpgpu_ctx* c, unsigned long long seq, double* sums) {
-  std::chrono::steady_clock::time_point t0;
-  for (unsigned spins = 1;; ++spins) {
-    // (the last pair the kernel stores first: nothing else needs looking at until it is there)
-    double probe;
-    if (gicp_granule_read(c->h_quad + 2 * (2 * kGicpQuadSums - 1), seq, &probe) && quad_sums_read(c, seq, sums)) break;
-    if ((spins & 0x3FFu) == 0) {
-      const hipError_t q = hipStreamQuery(c->stream);
-      if (q == hipSuccess) {
-        if (quad_sums_read(c, seq, sums)) break;
-        return fail(c, ICPGPU_ERR_HIP, "the GICP quadratic pass finished without publishing its sums");
-      }
-      if (q != hipErrorNotReady) return fail(c, ICPGPU_ERR_HIP, "HIP error while waiting for the GICP quadratic pass: %s", hipGetErrorString(q));
-      const auto now = std::chrono::steady_clock::now();
-      if (spins == 0x400u) t0 = now;
-      else if (std::chrono::duration<double, std::milli>(now - t0).count() > wait_timeout_ms())
-        return fail(c, ICPGPU_ERR_HIP, "timed out after %.0f ms waiting for the GICP quadratic pass (hung kernel?)", wait_timeout_ms());
-    }
-#if defined(__x86_64__)
-    __builtin_ia32_pause();
-#endif
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return 0;
+  const int w = wait_mailbox(c, c->stream, "the GICP quadratic pass", [&] {
+    double probe;  // (the last pair the kernel stores first: nothing else needs looking at until it is there)
+    return gicp_granule_read(c->h_quad + 2 * (2 * kGicpQuadSums - 1), seq, &probe) && quad_sums_read(c, seq, sums);
+  });
+  return w == 1 ? quad_sums_lost(c) : w;
 }
 
 // workgroups of a device-solver run: one per 1024 correspondences while every lane's share stays one quad in registers; larger
@@ -472,399 +426,453 @@ static void gicp_compose_final(const float previous[16], const float guess[16], 
   }
 }
 
-int align_gicp(icpgpu_ctx* c, const float* guess_in, float* out_xyzw, int want_fitness, icpgpu_result* res) {
-  struct ServerGuard {  // whatever way this function is left, no server stays behind
-    icpgpu_ctx* c;
-    ~ServerGuard() { gicp_server_stop(c); }
-  } server_guard{c};
-  struct SpecGuard {  // ... and no covariance grid whose statistics nobody has looked at
-    icpgpu_ctx* c;
-    ~SpecGuard() {
-      if (c->spec_grid.pending) (void)covariance_grid_check(c);
-    }
-  } spec_guard{c};
-  const auto t_start = std::chrono::steady_clock::now();
-  // development flavour, ICPGPU_GICP_TIMING=1: host wall per stage (printed by icpgpu_destroy)
-  static const bool stage_timing = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_GICP_TIMING"); return e && std::atoi(e) != 0; }();
-  auto t_mark = t_start;
-  auto mark = [&](int stage) {
-    if (!stage_timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    c->gt_stage[stage] += std::chrono::duration<double, std::micro>(now - t_mark).count();
-    t_mark = now;
-  };
-  init_result(res);
-  {
-    const int grc = ensure_gicp_resources(c);
-    if (grc) return grc;
-  }
-  c->prof.aligns += 1;
-  const int n_s = (int)c->src.n, n_t = (int)c->tgt.n;
-  const icpgpu_params& P = c->params;
-  const bool quadratic = gicp_inner_quadratic(c);  // the inner minimisation on the quadratic form (icp_gicp_quadratic.h)
-  if (quadratic) {
-    const int qrc = ensure_gicp_quadratic_resources(c);
-    if (qrc) return qrc;
-  }
-  c->prev.valid = c->tile_seed.valid = false;  // every alignment starts cold
-  float guess[16];
-  if (guess_in) std::memcpy(guess, guess_in, sizeof(guess));
-  else mat4f_identity(guess);
+// the one-XCD variant of the device solver wherever the run fits one XCD's 32 CUs with its correspondences in registers (the
+// reference's voxel-filtered scans do: ~22k points)
+static bool gicp_fits_one_xcd(const icpgpu_ctx* c, int n_s, int nblk) {
+  return c->gicp_local_ok && nblk <= gicp_solve_local_blocks() && (long long)nblk * 1024 >= n_s;
+}
 
-  auto finish_early = [&]() {  // empty target / clouds smaller than k_correspondences_: PCL leaves converged_ = false, T = I
-    c->final_T = mat4_identity();
-    c->have_final = true;
-    int rc = write_output_cloud(c, to_xform(c->final_T), out_xyzw);
-    res->t_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-    return rc;
-  };
-  if (n_t == 0 || n_s < kGicpK || n_t < kGicpK) return finish_early();
+// ---- the steps of a registration over its state record (GicpState, icp_ctx.h) ----------------------------------------------------
+// Each is written once and called by both drivers: align_gicp, the blocking host loop, and a GicpRun, the same registration cut
+// at its waits (below).  Same kernels, same arguments, same host arithmetic in the same order => the same bits on either path
+// (tests/test_gpu_gicp.py compares); where the two differ on purpose, the call sites say so.
 
-  int rc;
-  if ((rc = ensure_covariances(c, c->tgt, c->tgt_version, c->cov_grid_tgt, c->cov_tgt, c->cov_tgt_version))) return rc;
-  if ((rc = ensure_covariances(c, c->src, c->src_version, c->cov_grid_src, c->cov_src, c->cov_src_version, /*allow_unchecked=*/true))) return rc;
-  mark(0);
+// every registration starts cold, from the identity, with PCL's strict threshold
+static void gicp_state_begin(icpgpu_ctx* c, GicpState& s, const float* guess_in) {
+  c->prev.valid = c->tile_seed.valid = false;
+  if (guess_in) std::memcpy(s.guess, guess_in, sizeof(s.guess));
+  else mat4f_identity(s.guess);
+  mat4f_identity(s.transformation);
+  mat4f_identity(s.previous);
+  s.nr = 0;
+  s.state = ICPGPU_NOT_CONVERGED;
+  s.converged = false;
+  s.n_corr = 0;
+  s.mse = 0.0;
   // GICP keeps d2 < r^2 (strict): the largest float below r^2
-  const double r2 = P.max_correspondence_distance * P.max_correspondence_distance;
-  float thr = threshold_from(r2);
-  if ((double)thr >= r2) thr = std::nextafterf(thr, -INFINITY);
-  const float thr_excl = std::nextafterf(thr, INFINITY);  // d2 < thr_excl  <=>  d2 <= thr
-  if ((rc = ensure_grid(c, thr))) return rc;
-  if ((rc = ensure(c, c->keys, (size_t)n_s * sizeof(unsigned long long)))) return rc;
-  if ((rc = ensure(c, c->maha, (size_t)n_s * 6 * sizeof(double)))) return rc;
-  if ((rc = ensure(c, c->partials, (size_t)kMaxReduceBlocks * kReduceTerms * sizeof(double)))) return rc;
-  auto* keys = static_cast<unsigned long long*>(c->keys.ptr);
-  auto* maha = static_cast<double*>(c->maha.ptr);
-  const Xform base = xform_from_f16(guess);
-  mark(1);
+  const double r2 = c->params.max_correspondence_distance * c->params.max_correspondence_distance;
+  s.thr = threshold_from(r2);
+  if ((double)s.thr >= r2) s.thr = std::nextafterf(s.thr, -INFINITY);
+  s.thr_excl = std::nextafterf(s.thr, INFINITY);  // d2 < thr_excl  <=>  d2 <= thr
+}
+static void gicp_stamp_total(const GicpState& s) {
+  s.res->t_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - s.t_start).count();
+}
 
-  float transformation[16], previous[16];
-  mat4f_identity(transformation);
-  mat4f_identity(previous);
-  int nr = 0, state = ICPGPU_NOT_CONVERGED;
-  bool converged = false;
-  unsigned n_corr = 0;
-  double mse = 0.0, dev_ms = 0.0;
-  const double rot_eps = 2e-3;  // PCL rotation_epsilon_ (never set by the reference)
+// empty target / clouds smaller than k_correspondences_: PCL leaves converged_ = false, T = I
+static bool gicp_too_small(const icpgpu_ctx* c) { return c->tgt.n == 0 || c->src.n < (size_t)kGicpK || c->tgt.n < (size_t)kGicpK; }
+static void gicp_finish_early(icpgpu_ctx* c) {
+  c->final_T = mat4_identity();
+  c->have_final = true;
+}
 
-  while (!converged) {
-    float TG[16];
-    mat4f_mul(transformation, guess, TG);
-    const Xform Tq = xform_from_f16(TG);
-    Rot3d R;
-    for (int r = 0; r < 3; ++r)
-      for (int cc = 0; cc < 3; ++cc) {
-        double s = 0.0;
-        for (int k = 0; k < 4; ++k) s += (double)transformation[k * 4 + r] * (double)guess[cc * 4 + k];
-        R.m[3 * r + cc] = s;
-      }
-    // correspondences: exact NN keys (only those with d2 < r^2 are used, so the grid's cutoff search is complete)
-    // (timed like the point-to-point sweeps: one outer iteration in `timing_every` -- two event records are barrier packets in
-    //  front of and behind the search, a few microseconds of every outer iteration when each is timed)
-    const bool timed = c->timing_every <= 1 || (c->sweep_counter++ % (unsigned)c->timing_every) == 0;
-    if (timed) HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
-    if (grid_ready(c)) {
-      unsigned int* prev = nullptr;  // each outer iteration's neighbours bound the next one's search
-      bool use_prev = false;
-      int prc = prev_neighbours(c, c->grid, c->src.data(), n_s, grid_flags(c->grid, false), prev, use_prev);
-      if (prc) return prc;
-      HIP_TRY(c, launch_nn_grid_search(c->src.data(), n_s, grid_flags(c->grid, false), Tq, static_cast<const float4*>(c->grid.sorted.ptr),
-                                       static_cast<const int*>(c->grid.cell_start.ptr), c->grid.g, thr, keys, nullptr, nullptr,
-                                       nullptr, c->stream, prev, use_prev));
-    } else {
-      if ((rc = nn_keys_brute(c, c->tgt.data(), n_t, Tq, keys))) return rc;
-    }
-    if (!quadratic)
-      HIP_TRY(c, launch_gicp_mahalanobis(n_s, keys, thr_excl, R, static_cast<const double*>(c->cov_src.ptr),
-                                         static_cast<const double*>(c->cov_tgt.ptr), maha, c->stream));
-    if (timed) HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
-    mark(2);
-    // the source's covariance grid was built ahead of its statistics (ensure_covariances): they have arrived by now -- the covariance
-    // pass, this search and the Mahalanobis kernel were queued behind them.  A grid that failed (a point outside the box it was
-    // given) is rebuilt the waiting way and the alignment starts over; nothing of it has reached the host yet.
-    if (c->spec_grid.pending) {
-      const int chk = covariance_grid_check(c);
-      if (chk < 0) return chk;
-      if (chk == 1) {
-        c->prof.aligns -= 1;
-        return align_gicp(c, guess_in, out_xyzw, want_fitness, res);
-      }
-    }
+// after the covariances: the search grid (adopts the one the target's covariances were computed over -- no build) and the scratch
+static int gicp_ensure_scratch(icpgpu_ctx* c, const GicpState& s) {
+  const size_t n_s = c->src.n;
+  int rc;
+  if ((rc = ensure_grid(c, s.thr))) return rc;
+  if ((rc = ensure(c, c->keys, n_s * sizeof(unsigned long long)))) return rc;
+  if ((rc = ensure(c, c->maha, n_s * 6 * sizeof(double)))) return rc;
+  return ensure(c, c->partials, (size_t)kMaxReduceBlocks * kReduceTerms * sizeof(double));
+}
+static unsigned long long* gicp_keys(const icpgpu_ctx* c) { return static_cast<unsigned long long*>(c->keys.ptr); }
+static double* gicp_maha(const icpgpu_ctx* c) { return static_cast<double*>(c->maha.ptr); }
 
-    // rigid_transformation_estimation_: BFGS over x = (t, roll, pitch, yaw), every evaluation one reduction on the device
-    double m_count = 0.0;
-    auto eval = [&](const Vec6& x, GicpEval& out) -> bool {
-      float T[16];
-      std::memcpy(T, guess, sizeof(T));
-      const gicp::Trig6 tr = gicp::trig6(x);  // the state's six sine / cosine pairs (correctly rounded, double-double: ~0.2 us on the
-      gicp::apply_state(T, x, tr);            //  host) once per evaluation: the transform here, the gradient below (as the device solver does)
-      // ~300 evaluations per align, each a dependent launch: ONE kernel of a few workgroups whose partial sums land in the
-      // polled host mailbox; the host adds them in workgroup order (deterministic)
-      const auto t_eval0 = std::chrono::steady_clock::now();
-      unsigned long long seq = ++c->sums_seq;
-      if ((unsigned int)seq == kGicpServerExit) seq = (c->sums_seq += 2);  // (never a command number; the server skips it too)
-      const int nblk = gicp_direct_blocks(n_s, c->gicp_blocks_most);
-      bool have = false;
-      static const bool timing = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_GICP_TIMING"); return e && std::atoi(e) != 0; }();
-      std::chrono::steady_clock::time_point tq0, tq1, tq2;
-      if (timing) {
-        tq0 = std::chrono::steady_clock::now();
-        if (c->gt_n && c->gicp_server_on) c->gt_between += std::chrono::duration<double, std::micro>(tq0 - c->gt_last).count();
-        if (c->gt_pending > 0) {  // the last evaluation's device stamps (icp_gicp.hip: gicp_server_kernel), 100 MHz ticks
-          double first_seen = 1e300, acc = 0, red = 0, poll = 0;
-          for (int b = 0; b < c->gt_pending; ++b) {
-            const double* o = c->h_gicp + (size_t)b * kGicpPartialStride;
-            const double seen = o[2 * 29], t_acc = o[2 * 30], done = o[2 * 31], loop = o[2 * 29 + 1];
-            first_seen = std::min(first_seen, seen);
-            acc += t_acc - seen;
-            red += done - t_acc;
-            poll += seen - loop;
-          }
-          if (c->gt_dev_n >= 1000 && c->gt_dev_n < 1003) {  // a few evaluations in full
-            fprintf(stderr, "[icpgpu] evaluation %llu, per workgroup (us after the first one saw the command): xcd | started polling | saw it | accumulated | stored | reads\n", c->gt_dev_n);
-            for (int b = 0; b < c->gt_pending; ++b) {
-              const double* o = c->h_gicp + (size_t)b * kGicpPartialStride;
-              fprintf(stderr, "[icpgpu]   %2d: %d | %7.2f | %5.2f | %5.2f | %5.2f | %3.0f\n", b, (int)o[2 * 31 + 1], (o[2 * 29 + 1] - first_seen) * 0.01,
-                      (o[2 * 29] - first_seen) * 0.01, (o[2 * 30] - first_seen) * 0.01, (o[2 * 31] - first_seen) * 0.01, o[2 * 30 + 1]);
-            }
-          }
-          c->gt_dev_wait += poll / c->gt_pending * 0.01;
-          c->gt_dev_work += acc / c->gt_pending * 0.01;
-          c->gt_dev_reduce += red / c->gt_pending * 0.01;
-          c->gt_dev_n += 1;
-          c->gt_pending = 0;
-        }
-      }
-      if (c->gicp_server_on) {  // the resident server evaluates; no launch
-        gicp_server_command(c, (unsigned int)seq, xform_from_f16(T));
-        if (timing) tq1 = std::chrono::steady_clock::now();
-        const int w = wait_gicp_tags(c, nblk, seq, /*server=*/true);
-        if (timing) tq2 = std::chrono::steady_clock::now();
-        if (w < 0) return false;
-        have = w == 0;
-        if (!have) c->gicp_server_on = false;  // it gave up (50 ms without a command): single launches from here on
-        if (!have && std::getenv("ICPGPU_DEBUG")) fprintf(stderr, "[icpgpu] gicp server gave up at evaluation %llu\n", seq);
-      }
-      if (!have) {
-        if (launch_gicp_cost_direct(nblk, c->src.data(), n_s, c->tgt.data(), keys, thr_excl, xform_from_f16(T), base, maha,
-                                    c->h_gicp_dev, c->h_gicp_flags_dev, wire_seq(c, seq), c->stream) != hipSuccess)
-          return false;
-        if (wait_gicp_tags(c, nblk, seq, /*server=*/false) != 0) return false;
-      }
-      gicp_merge_blocks(c->h_gicp, nblk, c->h_sums);  // workgroup by workgroup, in double-double: the 13 sums are rounded once, here
-      if (timing && have) {
-        const auto tq3 = std::chrono::steady_clock::now();
-        c->gt_cmd += std::chrono::duration<double, std::micro>(tq1 - tq0).count();
-        c->gt_wait += std::chrono::duration<double, std::micro>(tq2 - tq1).count();
-        c->gt_merge += std::chrono::duration<double, std::micro>(tq3 - tq2).count();
-        c->gt_pending = nblk;  // the workgroups' stamps of this evaluation are read when the next one starts (they trail the tags)
-        c->gt_n += 1;
-        c->gt_last = tq3;
-      }
-      c->prof.gicp_cost_launches += 1;
-      c->prof.gicp_eval_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_eval0).count();
-      const double* s = c->h_sums;
-      c->prof.gicp_eval_corr += (uint64_t)s[0];
-      m_count = s[0];
-      mse = s[0] > 0 ? s[14] / s[0] : 0.0;
-      gicp::eval_from_sums(tr, s, out);
-      return true;
-    };
-    // rigid_transformation_estimation_: the whole BFGS run on the device (gicp_solve_kernel), one result for the host to poll
-    Vec6 x = gicp_state_from_matrix(transformation);
-    bool solved = false, leave_outer_loop = false;
-    if (quadratic) {
-      // ... or on the host over the quadratic form: ONE pass over the correspondences (Mahalanobis matrices on the way), 150
-      // numbers to wait for, then BFGS without a device round trip
-      const auto t_q0 = std::chrono::steady_clock::now();
-      const unsigned long long seq = ++c->quad_seq;
-      if ((rc = quad_pass_launch(c, n_s, keys, thr_excl, R, seq))) return rc;
-      double sums[2 * kGicpQuadSums];
-      if ((rc = wait_quad_sums(c, seq, sums))) return rc;
-      c->quad_pending = false;
-      mark(3);
-      if (stage_timing) {  // the last workgroup's stamps (gicp_quadratic_kernel), 100 MHz ticks
-        double st[5];
-        bool all = true;
-        for (int u = 0; u < 5; ++u) all = gicp_granule_read(c->h_quad + 2 * (2 * kGicpQuadSums + u), seq, &st[u]) && all;
-        if (all) {
-          long long t[5];
-          for (int u = 0; u < 5; ++u) std::memcpy(&t[u], &st[u], sizeof(long long));
-          static double acc[4] = {0, 0, 0, 0};
-          static unsigned long long n = 0;
-          for (int u = 0; u < 4; ++u) acc[u] += (double)(t[u + 1] - t[u]) * 0.01;
-          if ((++n % 100) == 0)
-            fprintf(stderr, "[icpgpu] quadratic pass, last workgroup, mean of %llu (us): loads + Mahalanobis %.2f | six groups %.2f | fence + counter %.2f | partials of all workgroups %.2f\n",
-                    n, acc[0] / n, acc[1] / n, acc[2] / n, acc[3] / n);
-        }
-      }
-      const double m = sums[2 * 73], d2 = sums[2 * 74];
-      m_count = m;
-      mse = m > 0 ? d2 / m : 0.0;
-      n_corr = (unsigned)m;
-      std::memcpy(previous, transformation, sizeof(previous));
-      if (n_corr < 4) {  // NotEnoughPointsException -> the loop breaks with converged_ = false
-        state = ICPGPU_CONV_NO_CORRESPONDENCES;
-        break;
-      }
-      int evals = 0;
-      const GicpSolve sr = gicp_minimize_quadratic(sums, guess, x, 20, 1e-2, &evals);
-      mark(4);
-      c->prof.gicp_quadratic_solves += 1;
-      res->gicp_solver = ICPGPU_GICP_SOLVER_QUADRATIC;
-      c->prof.gicp_cost_launches += (uint64_t)evals;
-      c->prof.gicp_eval_corr += (uint64_t)(m * evals);
-      c->prof.gicp_eval_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_q0).count();
-      if (sr != GicpSolve::Ok) {  // SolverDidntConvergeException
-        state = ICPGPU_NOT_CONVERGED;
-        break;
-      }
-      solved = true;
+// queue an outer iteration's correspondences: exact NN keys at transformation * guess (only those with d2 < r^2 are used, so the
+// grid's cutoff search is complete).  R: the product's rotation in float64, as the Mahalanobis matrices want it.
+static int gicp_queue_search(icpgpu_ctx* c, const GicpState& s, Rot3d& R) {
+  const int n_s = (int)c->src.n, n_t = (int)c->tgt.n;
+  float TG[16];
+  mat4f_mul(s.transformation, s.guess, TG);
+  const Xform Tq = xform_from_f16(TG);
+  for (int r = 0; r < 3; ++r)
+    for (int cc = 0; cc < 3; ++cc) {
+      double sum = 0.0;
+      for (int k = 0; k < 4; ++k) sum += (double)s.transformation[k * 4 + r] * (double)s.guess[cc * 4 + k];
+      R.m[3 * r + cc] = sum;
     }
-    // which solver: forced by ICPGPU_GICP_DEVICE, or (default) the one this context has measured to be faster on this box --
-    // until it knows, inner minimisations alternate and are timed (same bits either way, so nothing but time depends on it)
-    bool try_device = !quadratic && c->gicp_device_ok && c->gicp_server_allowed;
-    bool timing_this_run = false;
-    if (try_device && gicp_device_solver_mode() == 2) {
-      const int nblk = gicp_solve_blocks(n_s, c->gicp_blocks_most);
-      const bool fits_one_xcd = c->gicp_local_ok && nblk <= gicp_solve_local_blocks() && (long long)nblk * 1024 >= n_s && 8 * nblk <= c->gicp_blocks_most;
-      if (!fits_one_xcd) try_device = false;  // (streamed shares, 13 us gathers: the device solver is 30 % slower there)
-      else if (c->gicp_choice == 0) {
-        timing_this_run = true;
-        try_device = c->gicp_cal_runs[1] <= c->gicp_cal_runs[0];  // the one that has run less
-      } else {
-        try_device = c->gicp_choice == 2;
-      }
-    }
-    const auto t_inner0 = std::chrono::steady_clock::now();
-    const uint64_t evals_before = c->prof.gicp_cost_launches;
-    for (int attempt = 0; attempt < 2 && !solved && try_device && c->gicp_device_ok && c->gicp_server_allowed; ++attempt) {
-      const auto t_solve0 = std::chrono::steady_clock::now();
-      const int nblk = gicp_solve_blocks(n_s, c->gicp_blocks_most);
-      // the one-XCD variant when the run fits one XCD's 32 CUs with its correspondences in registers (the reference's
-      // voxel-filtered scans do: ~22k points); it needs 8 x nblk workgroups launched, so the context must own the chip's share
-      const bool local = c->gicp_local_ok && nblk <= gicp_solve_local_blocks() && (long long)nblk * 1024 >= n_s &&
-                         8 * nblk <= c->gicp_blocks_most;
-      const unsigned long long seq0 = (c->gicp_solve_seq += 8192);  // evaluation e of the run carries seq0 + e (e < 8192: <= 20 steps of <= 200 trials)
-      HIP_TRY(c, launch_gicp_solve(nblk, c->src.data(), n_s, c->tgt.data(), keys, thr_excl, base, guess, maha, x.v, c->gicp_slots,
-                                   c->h_solve_dev, wire_seq(c, seq0), 20, 1e-2, c->stream, local ? c->gicp_slots_local : nullptr,
-                                   local ? c->gicp_owner : nullptr, c->gicp_xcc));
-      double out[24];
-      const int w = wait_solve_result(c, seq0, out);
-      if (w < 0) return w;
-      const int status = w == 0 ? (int)out[0] : (int)gicp::kDeviceError;
-      if (status == gicp::kDeviceError) {  // a gather timed out (or the kernel never answered)
-        if (local) c->gicp_local_ok = false;  // placement was not what the one-XCD variant needs: the any-placement variant from here on
-        else c->gicp_device_ok = false;       // ... and if that one fails too: the host's solver
-        if (std::getenv("ICPGPU_DEBUG"))
-          fprintf(stderr, "[icpgpu] gicp device solver%s gave up (%s, %d workgroups, record %.0f); falling back\n", local ? " (one XCD)" : "",
-                  w == 0 ? "a gather timed out" : "no answer", nblk, w == 0 ? out[11] : -1.0);
-        if (std::getenv("ICPGPU_DEBUG") && w == 0)
-          fprintf(stderr, "[icpgpu]   seq0 %llu: hi granule number %.0f checksum %.0f, lo granule number %.0f, checksum of the hi bits %.0f\n", seq0, out[12], out[13], out[14], out[15]);
-      } else {
-        solved = true;
-        c->prof.gicp_device_solves += 1;
-        res->gicp_solver = ICPGPU_GICP_SOLVER_DEVICE;
-        const double m = out[7], evals = out[10];
-        m_count = m;
-        mse = m > 0 ? out[8] / m : 0.0;
-        n_corr = (unsigned)m;
-        c->prof.gicp_cost_launches += (uint64_t)evals;
-        c->prof.gicp_eval_corr += (uint64_t)(m * evals);
-        c->prof.gicp_eval_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_solve0).count();
-        std::memcpy(previous, transformation, sizeof(previous));
-        if (status == gicp::kNotEnoughPoints) {  // NotEnoughPointsException -> the loop breaks with converged_ = false
-          state = ICPGPU_CONV_NO_CORRESPONDENCES;
-          leave_outer_loop = true;
-          break;
-        }
-        if (status != gicp::kOk) {  // SolverDidntConvergeException
-          state = ICPGPU_NOT_CONVERGED;
-          leave_outer_loop = true;
-          break;
-        }
-        for (int k = 0; k < 6; ++k) x[k] = out[1 + k];
-      }
-    }
-    if (leave_outer_loop) break;  // (the two exits above leave the attempt loop only: until round 4's last day the outer loop went on
-                                  //  and reported a converged alignment with the unchanged transform -- found when the device
-                                  //  solver became part of the default path; tests/test_gpu_gicp.py now runs the degenerate cases through it)
-    if (!solved) {
-      // the ~35 dependent evaluations of this outer iteration go to a resident kernel (queued behind the two kernels above)
-      if ((rc = gicp_server_start(c, n_s, keys, thr_excl, base, maha))) return rc;
-      // number of correspondences (one evaluation at the current state; it is also the BFGS start, cached by the solver)
-      x = gicp_state_from_matrix(transformation);
-      GicpEval probe;
-      if (!eval(x, probe)) return fail(c, ICPGPU_ERR_HIP, "GICP cost evaluation failed: %s", hipGetErrorString(hipGetLastError()));
-      mark(3);
-      n_corr = (unsigned)m_count;
-      std::memcpy(previous, transformation, sizeof(previous));
-      if (n_corr < 4) {  // NotEnoughPointsException -> the loop breaks with converged_ = false
-        state = ICPGPU_CONV_NO_CORRESPONDENCES;
-        break;
-      }
-      const GicpSolve sr = gicp_minimize(eval, x, 20, 1e-2, &probe);
-      c->prof.gicp_host_solves += 1;
-      res->gicp_solver = ICPGPU_GICP_SOLVER_HOST;
-      mark(4);
-      gicp_server_stop(c);
-      mark(5);
-      if (sr == GicpSolve::DeviceError) return fail(c, ICPGPU_ERR_HIP, "GICP cost evaluation failed: %s", hipGetErrorString(hipGetLastError()));
-      if (sr != GicpSolve::Ok) {  // SolverDidntConvergeException
-        state = ICPGPU_NOT_CONVERGED;
-        break;
-      }
-    }
-    if (timing_this_run) {
-      const int which = solved ? 1 : 0;
-      if (c->gicp_cal_runs[which]++ > 0) {  // (a solver's first run pays for code upload and first-touch: not counted)
-        c->gicp_cal_us[which] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_inner0).count();
-        c->gicp_cal_evals[which] += c->prof.gicp_cost_launches - evals_before;
-      }
-      if (!c->gicp_device_ok || (!c->gicp_local_ok && !solved)) {
-        c->gicp_choice = 1;  // the device solver gave up on this context
-      } else if (c->gicp_cal_evals[0] >= 150 && c->gicp_cal_evals[1] >= 150) {
-        const double host_us = c->gicp_cal_us[0] / (double)c->gicp_cal_evals[0], dev_us = c->gicp_cal_us[1] / (double)c->gicp_cal_evals[1];
-        c->gicp_choice = dev_us < 0.97 * host_us ? 2 : 1;  // (the host loop on a tie: it is the simpler machine)
-        if (std::getenv("ICPGPU_DEBUG"))
-          fprintf(stderr, "[icpgpu] GICP inner solver measured on this context: host loop %.2f us, device solver %.2f us per evaluation -> %s\n", host_us,
-                  dev_us, c->gicp_choice == 2 ? "device solver" : "host loop");
-      }
-    }
-    mat4f_identity(transformation);
-    gicp_apply_state(transformation, x);
-    float ms = 0.f;
-    if (timed) HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    dev_ms += ms;
-    c->prof.grid_launches += grid_ready(c) ? 1 : 0;
-    c->prof.grid_ms += grid_ready(c) ? ms : 0.0;
-    c->prof.grid_timed += (timed && grid_ready(c)) ? 1 : 0;
-    mark(6);
-    const double delta = gicp_outer_delta(previous, transformation, rot_eps, P.transformation_epsilon);
-    ++nr;
-    c->prof.iterations += 1;
-    if (nr >= P.max_iterations || (delta < 1 && !P.force_iterations)) {
-      converged = true;
-      state = nr >= P.max_iterations ? ICPGPU_CONV_ITERATIONS : ICPGPU_CONV_TRANSFORM;
-      std::memcpy(previous, transformation, sizeof(previous));
-    }
+  if (!grid_ready(c)) return nn_keys_brute(c, c->tgt.data(), n_t, Tq, gicp_keys(c));
+  unsigned int* prev = nullptr;  // each outer iteration's neighbours bound the next one's search
+  bool use_prev = false;
+  const int rc = prev_neighbours(c, c->grid, c->src.data(), n_s, grid_flags(c->grid, false), prev, use_prev);
+  if (rc) return rc;
+  HIP_TRY(c, launch_nn_grid_search(c->src.data(), n_s, grid_flags(c->grid, false), Tq, static_cast<const float4*>(c->grid.sorted.ptr),
+                                   static_cast<const int*>(c->grid.cell_start.ptr), c->grid.g, s.thr, gicp_keys(c), nullptr, nullptr,
+                                   nullptr, c->stream, prev, use_prev));
+  return ICPGPU_OK;
+}
+// ... and, for the exact inner solvers, their Mahalanobis matrices (the quadratic pass computes its own on the way)
+static int gicp_queue_mahalanobis(icpgpu_ctx* c, const GicpState& s, const Rot3d& R) {
+  HIP_TRY(c, launch_gicp_mahalanobis((int)c->src.n, gicp_keys(c), s.thr_excl, R, static_cast<const double*>(c->cov_src.ptr),
+                                     static_cast<const double*>(c->cov_tgt.ptr), gicp_maha(c), c->stream));
+  return ICPGPU_OK;
+}
+
+// launch the device solver (gicp_solve_kernel: the whole BFGS run, one result for the host to wait for) from the current state
+static int gicp_launch_solver(icpgpu_ctx* c, const GicpState& s, int nblk, bool local, unsigned long long seq0) {
+  Vec6 x = gicp_state_from_matrix(s.transformation);
+  HIP_TRY(c, launch_gicp_solve(nblk, c->src.data(), (int)c->src.n, c->tgt.data(), gicp_keys(c), s.thr_excl, xform_from_f16(s.guess), s.guess, gicp_maha(c), x.v,
+                               c->gicp_slots, c->h_solve_dev, wire_seq(c, seq0), 20, 1e-2, c->stream, local ? c->gicp_slots_local : nullptr,
+                               local ? c->gicp_owner : nullptr, c->gicp_xcc));
+  return ICPGPU_OK;
+}
+
+// The two steps below take an inner minimisation's outcome.  true: x is the minimiser and the outer iteration goes on; false: the
+// registration is over, s.state says why (the outer loop ends with converged_ = false: until round 4's last day the device solver's
+// two exits left only an inner loop, and a converged alignment with the unchanged transform was reported).
+// t_from: where the caller's eval_ms starts.
+
+// the device solver's answer (out: its result values, status not kDeviceError)
+static bool gicp_take_device_result(icpgpu_ctx* c, GicpState& s, const double* out, std::chrono::steady_clock::time_point t_from, Vec6& x) {
+  c->prof.gicp_device_solves += 1;
+  s.res->gicp_solver = ICPGPU_GICP_SOLVER_DEVICE;
+  const double m = out[7], evals = out[10];
+  s.mse = m > 0 ? out[8] / m : 0.0;
+  s.n_corr = (unsigned)m;
+  c->prof.gicp_cost_launches += (uint64_t)evals;
+  c->prof.gicp_eval_corr += (uint64_t)(m * evals);
+  c->prof.gicp_eval_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_from).count();
+  std::memcpy(s.previous, s.transformation, sizeof(s.previous));
+  const int status = (int)out[0];
+  if (status == gicp::kNotEnoughPoints) {  // NotEnoughPointsException
+    s.state = ICPGPU_CONV_NO_CORRESPONDENCES;
+    return false;
   }
-  float fin[16];
-  gicp_compose_final(previous, guess, fin);
-  std::memcpy(res->T, fin, sizeof(fin));
+  if (status != gicp::kOk) {  // SolverDidntConvergeException
+    s.state = ICPGPU_NOT_CONVERGED;
+    return false;
+  }
+  for (int k = 0; k < 6; ++k) x[k] = out[1 + k];
+  return true;
+}
+
+// the quadratic pass's sums, and BFGS over the form they describe: on the host, without a device round trip
+static bool gicp_take_quadratic_sums(icpgpu_ctx* c, GicpState& s, const double* sums, std::chrono::steady_clock::time_point t_from, Vec6& x) {
+  c->quad_pending = false;
+  const double m = sums[2 * 73], d2 = sums[2 * 74];
+  s.mse = m > 0 ? d2 / m : 0.0;
+  s.n_corr = (unsigned)m;
+  std::memcpy(s.previous, s.transformation, sizeof(s.previous));
+  if (s.n_corr < 4) {  // NotEnoughPointsException
+    s.state = ICPGPU_CONV_NO_CORRESPONDENCES;
+    return false;
+  }
+  x = gicp_state_from_matrix(s.transformation);
+  int evals = 0;
+  const GicpSolve sr = gicp_minimize_quadratic(sums, s.guess, x, 20, 1e-2, &evals);
+  c->prof.gicp_quadratic_solves += 1;
+  s.res->gicp_solver = ICPGPU_GICP_SOLVER_QUADRATIC;
+  c->prof.gicp_cost_launches += (uint64_t)evals;
+  c->prof.gicp_eval_corr += (uint64_t)(m * evals);
+  c->prof.gicp_eval_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_from).count();
+  if (sr != GicpSolve::Ok) {  // SolverDidntConvergeException
+    s.state = ICPGPU_NOT_CONVERGED;
+    return false;
+  }
+  return true;
+}
+
+// an outer iteration's minimiser is in: the new transformation and PCL's stop rule (s.converged)
+static void gicp_outer_advance(icpgpu_ctx* c, GicpState& s, const Vec6& x) {
+  const icpgpu_params& P = c->params;
+  const double rot_eps = 2e-3;  // PCL rotation_epsilon_ (never set by the reference)
+  mat4f_identity(s.transformation);
+  gicp_apply_state(s.transformation, x);
+  const double delta = gicp_outer_delta(s.previous, s.transformation, rot_eps, P.transformation_epsilon);
+  ++s.nr;
+  c->prof.iterations += 1;
+  if (s.nr >= P.max_iterations || (delta < 1 && !P.force_iterations)) {
+    s.converged = true;
+    s.state = s.nr >= P.max_iterations ? ICPGPU_CONV_ITERATIONS : ICPGPU_CONV_TRANSFORM;
+    std::memcpy(s.previous, s.transformation, sizeof(s.previous));
+  }
+}
+
+// the registration is over: compose the result (fin) and write the record
+static void gicp_write_result(icpgpu_ctx* c, const GicpState& s, float fin[16]) {
+  gicp_compose_final(s.previous, s.guess, fin);
+  std::memcpy(s.res->T, fin, 16 * sizeof(float));
   for (int i = 0; i < 16; ++i) c->final_T[i] = (double)fin[i];
   c->have_final = true;
-  res->converged = converged ? 1 : 0;
-  res->iterations = nr;
-  res->convergence_state = state;
-  res->n_correspondences = n_corr;
-  res->mse_last = mse;
+  s.res->converged = s.converged ? 1 : 0;
+  s.res->iterations = s.nr;
+  s.res->convergence_state = s.state;
+  s.res->n_correspondences = s.n_corr;
+  s.res->mse_last = s.mse;
+}
+
+// ---- align_gicp: the blocking driver ------------------------------------------------------------------------------------------------
+// what it keeps beside the state: an inner minimisation here is one of three solvers, two of them many host <-> device round trips
+struct GicpAlign {
+  GicpState s;
+  int n_s = 0;
+  bool quadratic = false;  // the inner minimisation on the quadratic form (icp_gicp_quadratic.h)
+  Xform base;              // the guess, as the evaluations take it
+  double m_count = 0.0;    // correspondences of the last evaluation
+  double dev_ms = 0.0;
+  std::chrono::steady_clock::time_point t_mark;  // (stage timing)
+};
+static void gicp_mark(icpgpu_ctx* c, GicpAlign& a, int stage) {  // development flavour: host wall per stage
+  if (!gicp_timing()) return;
+  const auto now = std::chrono::steady_clock::now();
+  c->gt_stage[stage] += std::chrono::duration<double, std::micro>(now - a.t_mark).count();
+  a.t_mark = now;
+}
+
+// development flavour: an evaluation over the server, timed -- before it the LAST evaluation's device stamps (icp_gicp.hip:
+// gicp_server_kernel, 100 MHz ticks: they trail the tags), behind it the host's own parts
+static std::chrono::steady_clock::time_point gicp_eval_timing_begin(icpgpu_ctx* c) {
+  const auto tq0 = std::chrono::steady_clock::now();
+  if (c->gt_n && c->gicp_server_on) c->gt_between += std::chrono::duration<double, std::micro>(tq0 - c->gt_last).count();
+  if (c->gt_pending > 0) {
+    double first_seen = 1e300, acc = 0, red = 0, poll = 0;
+    for (int b = 0; b < c->gt_pending; ++b) {
+      const double* o = c->h_gicp + (size_t)b * kGicpPartialStride;
+      const double seen = o[2 * 29], t_acc = o[2 * 30], done = o[2 * 31], loop = o[2 * 29 + 1];
+      first_seen = std::min(first_seen, seen);
+      acc += t_acc - seen;
+      red += done - t_acc;
+      poll += seen - loop;
+    }
+    if (c->gt_dev_n >= 1000 && c->gt_dev_n < 1003) {  // a few evaluations in full
+      fprintf(stderr, "[icpgpu] evaluation %llu, per workgroup (us after the first one saw the command): xcd | started polling | saw it | accumulated | stored | reads\n", c->gt_dev_n);
+      for (int b = 0; b < c->gt_pending; ++b) {
+        const double* o = c->h_gicp + (size_t)b * kGicpPartialStride;
+        fprintf(stderr, "[icpgpu]   %2d: %d | %7.2f | %5.2f | %5.2f | %5.2f | %3.0f\n", b, (int)o[2 * 31 + 1], (o[2 * 29 + 1] - first_seen) * 0.01,
+                (o[2 * 29] - first_seen) * 0.01, (o[2 * 30] - first_seen) * 0.01, (o[2 * 31] - first_seen) * 0.01, o[2 * 30 + 1]);
+      }
+    }
+    c->gt_dev_wait += poll / c->gt_pending * 0.01;
+    c->gt_dev_work += acc / c->gt_pending * 0.01;
+    c->gt_dev_reduce += red / c->gt_pending * 0.01;
+    c->gt_dev_n += 1;
+    c->gt_pending = 0;
+  }
+  return tq0;
+}
+static void gicp_eval_timing_end(icpgpu_ctx* c, int nblk, const std::chrono::steady_clock::time_point tq[3]) {
+  const auto tq3 = std::chrono::steady_clock::now();
+  c->gt_cmd += std::chrono::duration<double, std::micro>(tq[1] - tq[0]).count();
+  c->gt_wait += std::chrono::duration<double, std::micro>(tq[2] - tq[1]).count();
+  c->gt_merge += std::chrono::duration<double, std::micro>(tq3 - tq[2]).count();
+  c->gt_pending = nblk;  // the workgroups' stamps of this evaluation are read when the next one starts
+  c->gt_n += 1;
+  c->gt_last = tq3;
+}
+// development flavour: the quadratic pass's last workgroup's stamps (gicp_quadratic_kernel), 100 MHz ticks
+static void gicp_quad_stamps(const icpgpu_ctx* c, unsigned long long seq) {
+  double st[5];
+  bool all = true;
+  for (int u = 0; u < 5; ++u) all = gicp_granule_read(c->h_quad + 2 * (2 * kGicpQuadSums + u), seq, &st[u]) && all;
+  if (!all) return;
+  long long t[5];
+  for (int u = 0; u < 5; ++u) std::memcpy(&t[u], &st[u], sizeof(long long));
+  static double acc[4] = {0, 0, 0, 0};
+  static unsigned long long n = 0;
+  for (int u = 0; u < 4; ++u) acc[u] += (double)(t[u + 1] - t[u]) * 0.01;
+  if ((++n % 100) == 0)
+    fprintf(stderr, "[icpgpu] quadratic pass, last workgroup, mean of %llu (us): loads + Mahalanobis %.2f | six groups %.2f | fence + counter %.2f | partials of all workgroups %.2f\n",
+            n, acc[0] / n, acc[1] / n, acc[2] / n, acc[3] / n);
+}
+
+// One evaluation of cost and gradient at x (~300 per align, each dependent on the last): the resident server's, or ONE kernel of a
+// few workgroups; either way the partial sums land in the polled host mailbox and the host adds them in workgroup order
+// (deterministic).  false: a device error.
+static bool gicp_evaluate(icpgpu_ctx* c, GicpAlign& a, const Vec6& x, GicpEval& out) {
+  float T[16];
+  std::memcpy(T, a.s.guess, sizeof(T));
+  const gicp::Trig6 tr = gicp::trig6(x);  // the state's six sine / cosine pairs (correctly rounded, double-double: ~0.2 us on the
+  gicp::apply_state(T, x, tr);            //  host) once per evaluation: the transform here, the gradient below (as the device solver does)
+  const auto t_eval0 = std::chrono::steady_clock::now();
+  unsigned long long seq = ++c->sums_seq;
+  if ((unsigned int)seq == kGicpServerExit) seq = (c->sums_seq += 2);  // (never a command number; the server skips it too)
+  const int nblk = gicp_direct_blocks(a.n_s, c->gicp_blocks_most);
+  const bool timing = gicp_timing();
+  std::chrono::steady_clock::time_point tq[3];
+  if (timing) tq[0] = gicp_eval_timing_begin(c);
+  bool have = false;
+  if (c->gicp_server_on) {  // the resident server evaluates; no launch
+    gicp_server_command(c, (unsigned int)seq, xform_from_f16(T));
+    if (timing) tq[1] = std::chrono::steady_clock::now();
+    const int w = wait_gicp_tags(c, nblk, seq, /*server=*/true);
+    if (timing) tq[2] = std::chrono::steady_clock::now();
+    if (w < 0) return false;
+    have = w == 0;
+    if (!have) c->gicp_server_on = false;  // it gave up (50 ms without a command): single launches from here on
+    if (!have && std::getenv("ICPGPU_DEBUG")) fprintf(stderr, "[icpgpu] gicp server gave up at evaluation %llu\n", seq);
+  }
+  if (!have) {
+    if (launch_gicp_cost_direct(nblk, c->src.data(), a.n_s, c->tgt.data(), gicp_keys(c), a.s.thr_excl, xform_from_f16(T), a.base, gicp_maha(c),
+                                c->h_gicp_dev, c->h_gicp_flags_dev, wire_seq(c, seq), c->stream) != hipSuccess)
+      return false;
+    if (wait_gicp_tags(c, nblk, seq, /*server=*/false) != 0) return false;
+  }
+  gicp_merge_blocks(c->h_gicp, nblk, c->h_sums);  // workgroup by workgroup, in double-double: the 13 sums are rounded once, here
+  if (timing && have) gicp_eval_timing_end(c, nblk, tq);
+  c->prof.gicp_cost_launches += 1;
+  c->prof.gicp_eval_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_eval0).count();
+  const double* s = c->h_sums;
+  c->prof.gicp_eval_corr += (uint64_t)s[0];
+  a.m_count = s[0];
+  a.s.mse = s[0] > 0 ? s[14] / s[0] : 0.0;
+  gicp::eval_from_sums(tr, s, out);
+  return true;
+}
+
+// The inner solvers (rigid_transformation_estimation_: BFGS over x = (t, roll, pitch, yaw)).  Each returns < 0 on error, 0 when the
+// registration is over (s.state says why), 1 with the minimiser in x.
+
+// on the host over the quadratic form: ONE pass over the correspondences, 150 numbers to wait for
+static int gicp_solve_quadratic(icpgpu_ctx* c, GicpAlign& a, const Rot3d& R, Vec6& x) {
+  const auto t_q0 = std::chrono::steady_clock::now();
+  const unsigned long long seq = ++c->quad_seq;
+  int rc;
+  if ((rc = quad_pass_launch(c, a.n_s, gicp_keys(c), a.s.thr_excl, R, seq))) return rc;
+  double sums[2 * kGicpQuadSums];
+  if ((rc = wait_quad_sums(c, seq, sums))) return rc;
+  gicp_mark(c, a, 3);
+  if (gicp_timing()) gicp_quad_stamps(c, seq);
+  if (!gicp_take_quadratic_sums(c, a.s, sums, t_q0, x)) return 0;
+  gicp_mark(c, a, 4);
+  return 1;
+}
+
+// on the device; 2: the solver gave up or is switched off -- the host loop's turn.  A first failure of the one-XCD variant (placement
+// was not what it needs) is followed by the any-placement variant, a failure of that one switches the device solver off.
+static int gicp_solve_device(icpgpu_ctx* c, GicpAlign& a, Vec6& x) {
+  for (int attempt = 0; attempt < 2 && c->gicp_device_ok && c->gicp_server_allowed; ++attempt) {
+    const auto t_solve0 = std::chrono::steady_clock::now();
+    const int nblk = gicp_solve_blocks(a.n_s, c->gicp_blocks_most);
+    // (a lone blocking alignment sizes its evaluation server by the context's share of the chip, and the one-XCD variant needs
+    //  8 x nblk workgroups launched: the context must own that share.  A batch's runs sit on their contexts' own XCDs and do not ask.)
+    const bool local = gicp_fits_one_xcd(c, a.n_s, nblk) && 8 * nblk <= c->gicp_blocks_most;
+    const unsigned long long seq0 = (c->gicp_solve_seq += 8192);  // evaluation e of the run carries seq0 + e (e < 8192: <= 20 steps of <= 200 trials)
+    int rc;
+    if ((rc = gicp_launch_solver(c, a.s, nblk, local, seq0))) return rc;
+    double out[24];
+    const int w = wait_solve_result(c, seq0, out);
+    if (w < 0) return w;
+    if (w == 0 && (int)out[0] != gicp::kDeviceError) return gicp_take_device_result(c, a.s, out, t_solve0, x) ? 1 : 0;
+    // a gather timed out (or, w == 1, the kernel never answered)
+    if (local) c->gicp_local_ok = false;
+    else c->gicp_device_ok = false;
+    if (std::getenv("ICPGPU_DEBUG"))
+      fprintf(stderr, "[icpgpu] gicp device solver%s gave up (%s, %d workgroups, record %.0f); falling back\n", local ? " (one XCD)" : "",
+              w == 0 ? "a gather timed out" : "no answer", nblk, w == 0 ? out[11] : -1.0);
+    if (std::getenv("ICPGPU_DEBUG") && w == 0)
+      fprintf(stderr, "[icpgpu]   seq0 %llu: hi granule number %.0f checksum %.0f, lo granule number %.0f, checksum of the hi bits %.0f\n", seq0, out[12], out[13], out[14], out[15]);
+  }
+  return 2;
+}
+
+// on the host, every evaluation one reduction on the device: the ~35 dependent evaluations of this outer iteration go to a resident
+// kernel (queued behind the search and the Mahalanobis kernel)
+static int gicp_solve_host(icpgpu_ctx* c, GicpAlign& a, Vec6& x) {
+  GicpState& s = a.s;
+  int rc;
+  if ((rc = gicp_server_start(c, a.n_s, gicp_keys(c), s.thr_excl, a.base, gicp_maha(c)))) return rc;
+  auto eval = [&](const Vec6& at, GicpEval& out) { return gicp_evaluate(c, a, at, out); };
+  // number of correspondences (one evaluation at the current state; it is also the BFGS start, cached by the solver)
+  x = gicp_state_from_matrix(s.transformation);
+  GicpEval probe;
+  if (!eval(x, probe)) return fail(c, ICPGPU_ERR_HIP, "GICP cost evaluation failed: %s", hipGetErrorString(hipGetLastError()));
+  gicp_mark(c, a, 3);
+  s.n_corr = (unsigned)a.m_count;
+  std::memcpy(s.previous, s.transformation, sizeof(s.previous));
+  if (s.n_corr < 4) {  // NotEnoughPointsException
+    s.state = ICPGPU_CONV_NO_CORRESPONDENCES;
+    return 0;
+  }
+  const GicpSolve sr = gicp_minimize(eval, x, 20, 1e-2, &probe);
+  c->prof.gicp_host_solves += 1;
+  s.res->gicp_solver = ICPGPU_GICP_SOLVER_HOST;
+  gicp_mark(c, a, 4);
+  gicp_server_stop(c);
+  gicp_mark(c, a, 5);
+  if (sr == GicpSolve::DeviceError) return fail(c, ICPGPU_ERR_HIP, "GICP cost evaluation failed: %s", hipGetErrorString(hipGetLastError()));
+  if (sr != GicpSolve::Ok) {  // SolverDidntConvergeException
+    s.state = ICPGPU_NOT_CONVERGED;
+    return 0;
+  }
+  return 1;
+}
+
+// Which exact solver: forced by ICPGPU_GICP_DEVICE, or (default) the one this context has measured to be faster on this box --
+// until it knows, inner minimisations alternate and are timed (same bits either way, so nothing but time depends on it).
+static bool gicp_choose_device(const icpgpu_ctx* c, int n_s, bool& calibrating) {
+  calibrating = false;
+  if (!c->gicp_device_ok || !c->gicp_server_allowed) return false;
+  if (gicp_device_solver_mode() != 2) return true;
+  const int nblk = gicp_solve_blocks(n_s, c->gicp_blocks_most);
+  if (!(gicp_fits_one_xcd(c, n_s, nblk) && 8 * nblk <= c->gicp_blocks_most)) return false;  // (streamed shares, 13 us gathers: the device solver is 30 % slower there)
+  if (c->gicp_choice != 0) return c->gicp_choice == 2;
+  calibrating = true;
+  return c->gicp_cal_runs[1] <= c->gicp_cal_runs[0];  // the one that has run less
+}
+// ... and the measurement: one timed inner minimisation of solver `which` (0 host loop, 1 device) since t_inner0
+static void gicp_calibrate(icpgpu_ctx* c, int which, std::chrono::steady_clock::time_point t_inner0, uint64_t evals_before) {
+  if (c->gicp_cal_runs[which]++ > 0) {  // (a solver's first run pays for code upload and first-touch: not counted)
+    c->gicp_cal_us[which] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_inner0).count();
+    c->gicp_cal_evals[which] += c->prof.gicp_cost_launches - evals_before;
+  }
+  if (!c->gicp_device_ok || (!c->gicp_local_ok && which == 0)) {
+    c->gicp_choice = 1;  // the device solver gave up on this context
+  } else if (c->gicp_cal_evals[0] >= 150 && c->gicp_cal_evals[1] >= 150) {
+    const double host_us = c->gicp_cal_us[0] / (double)c->gicp_cal_evals[0], dev_us = c->gicp_cal_us[1] / (double)c->gicp_cal_evals[1];
+    c->gicp_choice = dev_us < 0.97 * host_us ? 2 : 1;  // (the host loop on a tie: it is the simpler machine)
+    if (std::getenv("ICPGPU_DEBUG"))
+      fprintf(stderr, "[icpgpu] GICP inner solver measured on this context: host loop %.2f us, device solver %.2f us per evaluation -> %s\n", host_us,
+              dev_us, c->gicp_choice == 2 ? "device solver" : "host loop");
+  }
+}
+static int gicp_solve_exact(icpgpu_ctx* c, GicpAlign& a, Vec6& x) {
+  bool calibrating = false;
+  const bool try_device = gicp_choose_device(c, a.n_s, calibrating);
+  const auto t_inner0 = std::chrono::steady_clock::now();
+  const uint64_t evals_before = c->prof.gicp_cost_launches;
+  int go = try_device ? gicp_solve_device(c, a, x) : 2;
+  const int which = go == 2 ? 0 : 1;
+  if (go == 2) go = gicp_solve_host(c, a, x);
+  if (go == 1 && calibrating) gicp_calibrate(c, which, t_inner0, evals_before);
+  return go;
+}
+
+// One attempt's preparation: the state, both clouds' covariances (the source's grid may be built ahead of its statistics), scratch.
+// 1: the clouds are too small, the registration has finished early.
+static int gicp_prepare(icpgpu_ctx* c, GicpAlign& a, const float* guess_in, float* out_xyzw) {
+  GicpState& s = a.s;
+  s.t_start = a.t_mark = std::chrono::steady_clock::now();
+  a.n_s = (int)c->src.n;
+  a.dev_ms = 0.0;
+  gicp_state_begin(c, s, guess_in);
+  a.base = xform_from_f16(s.guess);
+  int rc;
+  if (gicp_too_small(c)) {
+    gicp_finish_early(c);
+    rc = write_output_cloud(c, to_xform(c->final_T), out_xyzw);
+    gicp_stamp_total(s);
+    return rc ? rc : 1;
+  }
+  if ((rc = ensure_covariances(c, c->tgt, c->tgt_version, c->cov_grid_tgt, c->cov_tgt, c->cov_tgt_version))) return rc;
+  if ((rc = ensure_covariances(c, c->src, c->src_version, c->cov_grid_src, c->cov_src, c->cov_src_version, /*allow_unchecked=*/true))) return rc;
+  gicp_mark(c, a, 0);
+  if ((rc = gicp_ensure_scratch(c, s))) return rc;
+  gicp_mark(c, a, 1);
+  return ICPGPU_OK;
+}
+
+// The result record, then the aligned cloud and the fitness the reference asks for on every scan (icp_odometer.cpp:196-201), round 6:
+// the transform kernel writes the cloud into the pinned staging buffer, a marker follows, the fitness sweep is queued behind both --
+// and the host copies the cloud out while the sweep runs (it used to wait for the sweep, then for a transform, a copy engine and a
+// marker, then copy).
+static int gicp_finish(icpgpu_ctx* c, GicpAlign& a, float* out_xyzw, int want_fitness) {
+  icpgpu_result* res = a.s.res;
+  float fin[16];
+  gicp_write_result(c, a.s, fin);
   const Xform Tf = xform_from_f16(fin);
-  // The aligned cloud and the fitness the reference asks for on every scan (icp_odometer.cpp:196-201), round 6: the transform kernel
-  // writes the cloud into the pinned staging buffer, a marker follows, the fitness sweep is queued behind both -- and the host copies
-  // the cloud out while the sweep runs (it used to wait for the sweep, then for a transform, a copy engine and a marker, then copy).
   StageTicket out_ticket;
   bool out_done = false;
+  int rc;
   if (want_fitness) {
     if ((rc = resolve_sweep_timings(c))) return rc;
     c->dev_ms_accum = 0.0;
@@ -878,17 +886,83 @@ int align_gicp(icpgpu_ctx* c, const float* guess_in, float* out_xyzw, int want_f
     if ((rc = wait_sums(c, tk.seq))) return rc;
     if ((rc = sweep_complete(c, tk))) return rc;
     if ((rc = resolve_sweep_timings(c))) return rc;
-    dev_ms += c->dev_ms_accum;  // 0 when this sweep was not a timed one
+    a.dev_ms += c->dev_ms_accum;  // 0 when this sweep was not a timed one
     res->fitness = c->h_sums[0] > 0.0 ? c->h_sums[16] / c->h_sums[0] : DBL_MAX;
   }
-  mark(7);
+  gicp_mark(c, a, 7);
   if (!out_done && (rc = write_output_cloud(c, Tf, out_xyzw))) return rc;
-  mark(8);
+  gicp_mark(c, a, 8);
   if ((rc = resolve_cov_timing(c))) return rc;  // (long finished: the evaluations ran behind it)
-  if (stage_timing) c->gt_aligns += 1;
-  res->t_device_ms = dev_ms;
-  res->t_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+  if (gicp_timing()) c->gt_aligns += 1;
+  res->t_device_ms = a.dev_ms;
+  gicp_stamp_total(a.s);
   return ICPGPU_OK;
+}
+
+int align_gicp(icpgpu_ctx* c, const float* guess_in, float* out_xyzw, int want_fitness, icpgpu_result* res) {
+  struct ServerGuard {  // whatever way this function is left, no server stays behind
+    icpgpu_ctx* c;
+    ~ServerGuard() { gicp_server_stop(c); }
+  } server_guard{c};
+  struct SpecGuard {  // ... and no covariance grid whose statistics nobody has looked at
+    icpgpu_ctx* c;
+    ~SpecGuard() {
+      if (c->spec_grid.pending) (void)covariance_grid_check(c);
+    }
+  } spec_guard{c};
+  init_result(res);
+  int rc;
+  if ((rc = ensure_gicp_resources(c))) return rc;
+  c->prof.aligns += 1;
+  GicpAlign a;
+  GicpState& s = a.s;
+  s.res = res;
+  a.quadratic = gicp_inner_quadratic(c);
+  if (a.quadratic && (rc = ensure_gicp_quadratic_resources(c))) return rc;
+
+  // At most two attempts.  The source's covariance grid may have been built ahead of its statistics (ensure_covariances); a grid
+  // that then fails its check is rebuilt the waiting way and the registration starts over from its preparation -- nothing of the
+  // first attempt has reached the host or the result record by then, and spec_cooldown keeps the second from asking again.  (What
+  // the first attempt added to the profile counters stays added; its clock does not count.)
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    if ((rc = gicp_prepare(c, a, guess_in, out_xyzw))) return rc < 0 ? rc : ICPGPU_OK;
+    bool start_over = false;
+    while (!s.converged) {
+      // (timed like the point-to-point sweeps: one outer iteration in `timing_every` -- two event records are barrier packets in
+      //  front of and behind the search, a few microseconds of every outer iteration when each is timed)
+      const bool timed = c->timing_every <= 1 || (c->sweep_counter++ % (unsigned)c->timing_every) == 0;
+      if (timed) HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
+      Rot3d R;
+      if ((rc = gicp_queue_search(c, s, R))) return rc;
+      if (!a.quadratic && (rc = gicp_queue_mahalanobis(c, s, R))) return rc;
+      if (timed) HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
+      gicp_mark(c, a, 2);
+      // the statistics of a grid built ahead of them have arrived by now: the covariance pass, this search and the Mahalanobis
+      // kernel were queued behind them
+      if (c->spec_grid.pending) {
+        const int chk = covariance_grid_check(c);
+        if (chk < 0) return chk;
+        if (chk == 1) {
+          start_over = true;
+          break;
+        }
+      }
+      Vec6 x;
+      const int go = a.quadratic ? gicp_solve_quadratic(c, a, R, x) : gicp_solve_exact(c, a, x);
+      if (go < 0) return go;
+      if (go == 0) break;  // NotEnoughPoints / SolverDidntConverge: PCL's loop ends with converged_ = false
+      float ms = 0.f;  // (the search is counted here, with its event time; a resumable run counts it when it queues it)
+      if (timed) HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+      a.dev_ms += ms;
+      c->prof.grid_launches += grid_ready(c) ? 1 : 0;
+      c->prof.grid_ms += grid_ready(c) ? ms : 0.0;
+      c->prof.grid_timed += (timed && grid_ready(c)) ? 1 : 0;
+      gicp_outer_advance(c, s, x);
+      gicp_mark(c, a, 6);
+    }
+    if (!start_over) return gicp_finish(c, a, out_xyzw, want_fitness);
+  }
+  return fail(c, ICPGPU_ERR_HIP, "GICP: internal error (a second start-over)");
 }
 
 
@@ -896,9 +970,10 @@ int align_gicp(icpgpu_ctx* c, const float* guess_in, float* out_xyzw, int want_f
 // align_gicp above is a blocking host loop: the index builds wait for their read-backs, every inner minimisation is ~30 dependent
 // host <-> device round trips (or one wait for the device solver).  A GicpRun is the same registration cut at its waits: the
 // covariance grids go through their host round trips as posted markers the host POLLS, every outer iteration is search +
-// Mahalanobis + the whole BFGS run in ONE resident kernel (gicp_solve_kernel, as align_gicp's device-solver branch launches it),
-// whose result granules the host polls, and the fitness sweep is a SweepTicket like point-to-point's.  Same kernels, same
-// arguments, same host arithmetic between them as align_gicp => the same bits (tests/test_gpu_gicp.py compares).
+// Mahalanobis + the whole BFGS run in ONE resident kernel (gicp_solve_kernel, as gicp_solve_device launches it), whose result
+// granules the host polls, and the fitness sweep is a SweepTicket like point-to-point's.  Between its waits a run calls the steps
+// align_gicp calls (the section above): the two paths give the same bits because they run the same code, and
+// tests/test_gpu_gicp.py compares them all the same.
 // What a run cannot take -- a guess or an output cloud (the batch passes neither), a context without the device solver, a solver
 // that gives up (a gather timed out: co-residency lost) -- goes through align_gicp: gicp_run_begin says so (phase Blocking) and
 // gicp_run_step then runs the blocking function; results do not depend on the path, so a restart from scratch is safe.
@@ -916,106 +991,59 @@ static bool gicp_run_device_ok(const icpgpu_ctx* c) {
   return gicp_device_solver_mode() != 0 && c->gicp_device_ok && c->gicp_server_allowed && c->gicp_slots && c->h_solve;
 }
 
-static int gicp_run_finish_early(icpgpu_ctx* c, GicpRun& r) {  // empty target / clouds smaller than k_correspondences_
-  c->final_T = mat4_identity();
-  c->have_final = true;
-  r.res->t_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r.t_start).count();
-  r.phase = GicpRun::Done;
-  return ICPGPU_OK;
+// a wait begins: the next gicp_run_step polls for what was just queued
+static void gicp_run_await(GicpRun& r, GicpRun::Phase phase) {
+  r.phase = phase;
+  r.polls = 0;
+  r.t_issue = std::chrono::steady_clock::now();
 }
 
 // queue one outer iteration: correspondences, Mahalanobis matrices, the BFGS run
 static int gicp_run_queue_outer(icpgpu_ctx* c, GicpRun& r) {
-  const int n_s = (int)c->src.n, n_t = (int)c->tgt.n;
-  auto* keys = static_cast<unsigned long long*>(c->keys.ptr);
-  auto* maha = static_cast<double*>(c->maha.ptr);
-  float TG[16];
-  mat4f_mul(r.transformation, r.guess, TG);
-  const Xform Tq = xform_from_f16(TG);
+  const int n_s = (int)c->src.n;
   Rot3d R;
-  for (int rr = 0; rr < 3; ++rr)
-    for (int cc = 0; cc < 3; ++cc) {
-      double s = 0.0;
-      for (int k = 0; k < 4; ++k) s += (double)r.transformation[k * 4 + rr] * (double)r.guess[cc * 4 + k];
-      R.m[3 * rr + cc] = s;
-    }
   int rc;
-  if (grid_ready(c)) {
-    unsigned int* prev = nullptr;  // each outer iteration's neighbours bound the next one's search
-    bool use_prev = false;
-    if ((rc = prev_neighbours(c, c->grid, c->src.data(), n_s, grid_flags(c->grid, false), prev, use_prev))) return rc;
-    HIP_TRY(c, launch_nn_grid_search(c->src.data(), n_s, grid_flags(c->grid, false), Tq, static_cast<const float4*>(c->grid.sorted.ptr),
-                                     static_cast<const int*>(c->grid.cell_start.ptr), c->grid.g, r.thr, keys, nullptr, nullptr,
-                                     nullptr, c->stream, prev, use_prev));
-    c->prof.grid_launches += 1;
-  } else {
-    if ((rc = nn_keys_brute(c, c->tgt.data(), n_t, Tq, keys))) return rc;
-  }
+  if ((rc = gicp_queue_search(c, r, R))) return rc;
+  if (grid_ready(c)) c->prof.grid_launches += 1;  // (counted as it is queued: a run records no events around its searches)
+  r.solve_stream = c->stream;
   if (r.quadratic) {  // one pass for the quadratic form's sums (Mahalanobis matrices on the way); the run polls them (phase Quad)
     r.seq0 = ++c->quad_seq;
-    r.t_issue = std::chrono::steady_clock::now();
-    if ((rc = quad_pass_launch(c, n_s, keys, r.thr_excl, R, r.seq0))) return rc;
-    r.solve_stream = c->stream;
-    r.phase = GicpRun::Quad;
-    r.polls = 0;
-    return ICPGPU_OK;
+    gicp_run_await(r, GicpRun::Quad);
+    return quad_pass_launch(c, n_s, gicp_keys(c), r.thr_excl, R, r.seq0);
   }
-  HIP_TRY(c, launch_gicp_mahalanobis(n_s, keys, r.thr_excl, R, static_cast<const double*>(c->cov_src.ptr),
-                                     static_cast<const double*>(c->cov_tgt.ptr), maha, c->stream));
-  Vec6 x = gicp_state_from_matrix(r.transformation);
+  if ((rc = gicp_queue_mahalanobis(c, r, R))) return rc;
   const int nblk = gicp_solve_blocks(n_s, c->gicp_blocks_most);
+  r.seq0 = (c->gicp_solve_seq += 8192);
   if (r.combine && (long long)nblk * 1024 >= n_s) {  // the scheduler launches it together with the other runs that are ready
+    const Vec6 x = gicp_state_from_matrix(r.transformation);
     GicpSolveItem& it = r.item;
     it.src = c->src.data();
     it.n_s = n_s;
     it.tgt = c->tgt.data();
-    it.keys = keys;
+    it.keys = gicp_keys(c);
     it.thr = r.thr_excl;
     it.base = xform_from_f16(r.guess);
     std::memcpy(it.guess, r.guess, sizeof(it.guess));
-    it.maha6 = maha;
+    it.maha6 = gicp_maha(c);
     for (int k = 0; k < 6; ++k) it.x0[k] = x.v[k];
     it.slots = c->gicp_slots;
     it.host_out = c->h_solve_dev;
-    r.seq0 = (c->gicp_solve_seq += 8192);
     it.seq0 = wire_seq(c, r.seq0);
     it.blocks = nblk;
     r.local = false;
     r.phase = GicpRun::WantSolve;
     return ICPGPU_OK;
   }
-  // the one-XCD variant wherever the run fits one XCD with its correspondences in registers (align_gicp also asks for 8 x nblk <=
-  // the context's share of the chip: a lone blocking alignment sizes its evaluation server by that share; the runs of a batch
-  // sit on their contexts' own XCDs, c->gicp_xcc, and leave after every outer iteration)
-  r.local = c->gicp_local_ok && nblk <= gicp_solve_local_blocks() && (long long)nblk * 1024 >= n_s;
-  r.seq0 = (c->gicp_solve_seq += 8192);
-  r.t_issue = std::chrono::steady_clock::now();
-  HIP_TRY(c, launch_gicp_solve(nblk, c->src.data(), n_s, c->tgt.data(), keys, r.thr_excl, xform_from_f16(r.guess), r.guess, maha, x.v, c->gicp_slots,
-                               c->h_solve_dev, wire_seq(c, r.seq0), 20, 1e-2, c->stream, r.local ? c->gicp_slots_local : nullptr,
-                               r.local ? c->gicp_owner : nullptr, c->gicp_xcc));
-  r.solve_stream = c->stream;
-  r.phase = GicpRun::Solve;
-  r.polls = 0;
-  return ICPGPU_OK;
+  // (no "8 x nblk <= the context's share" here, as gicp_solve_device asks: the runs of a batch sit on their contexts' own XCDs,
+  //  c->gicp_xcc, and leave after every outer iteration)
+  r.local = gicp_fits_one_xcd(c, n_s, nblk);
+  gicp_run_await(r, GicpRun::Solve);
+  return gicp_launch_solver(c, r, nblk, r.local, r.seq0);
 }
 
-void gicp_run_solver_launched(icpgpu_ctx* c, GicpRun& r, hipStream_t solve_stream) {
-  (void)c;
+void gicp_run_solver_launched(icpgpu_ctx*, GicpRun& r, hipStream_t solve_stream) {
   r.solve_stream = solve_stream;
-  r.t_issue = std::chrono::steady_clock::now();
-  r.phase = GicpRun::Solve;
-  r.polls = 0;
-}
-
-// after the covariances: the search grid, the scratch, the first outer iteration
-static int gicp_run_start_outer(icpgpu_ctx* c, GicpRun& r) {
-  const int n_s = (int)c->src.n;
-  int rc;
-  if ((rc = ensure_grid(c, r.thr))) return rc;  // (GICP: adopts the grid the target's covariances were computed over -- no build)
-  if ((rc = ensure(c, c->keys, (size_t)n_s * sizeof(unsigned long long)))) return rc;
-  if ((rc = ensure(c, c->maha, (size_t)n_s * 6 * sizeof(double)))) return rc;
-  if ((rc = ensure(c, c->partials, (size_t)kMaxReduceBlocks * kReduceTerms * sizeof(double)))) return rc;
-  return gicp_run_queue_outer(c, r);
+  gicp_run_await(r, GicpRun::Solve);
 }
 
 // the next covariance grid that needs building (target first, then source), or on to the outer iterations
@@ -1034,15 +1062,14 @@ static int gicp_run_next_cov(icpgpu_ctx* c, GicpRun& r) {
     if (needed && r.gb.state != GridBuild::Done) {  // a read-back is queued: poll the marker behind it
       r.marker = run_post_marker(c, static_cast<const int*>(G.ints.ptr), &rc);
       if (rc) return rc;
-      r.phase = GicpRun::CovGrid;
-      r.polls = 0;
-      r.t_issue = std::chrono::steady_clock::now();
+      gicp_run_await(r, GicpRun::CovGrid);
       return ICPGPU_OK;
     }
     if (needed && (rc = cov_launch(c, cloud, version, G, cov, cov_version, /*timed=*/false))) return rc;
     r.cov_stage += 1;
   }
-  return gicp_run_start_outer(c, r);
+  if ((rc = gicp_ensure_scratch(c, r))) return rc;
+  return gicp_run_queue_outer(c, r);
 }
 
 int gicp_run_begin(icpgpu_ctx* c, GicpRun& r, int want_fitness, icpgpu_result* res, bool combine) {
@@ -1065,24 +1092,19 @@ int gicp_run_begin(icpgpu_ctx* c, GicpRun& r, int want_fitness, icpgpu_result* r
   }
   init_result(res);
   c->prof.aligns += 1;
-  c->prev.valid = c->tile_seed.valid = false;  // every alignment starts cold
-  mat4f_identity(r.guess);
-  mat4f_identity(r.transformation);
-  mat4f_identity(r.previous);
+  gicp_state_begin(c, r, /*guess_in=*/nullptr);  // (a run never takes a guess)
   {
     int rc = resolve_sweep_timings(c, /*block=*/false);
     if (rc) return rc;
     c->dev_ms_accum = 0.0;
     c->call_sweeps = c->call_timed = 0;
   }
-  const int n_s = (int)c->src.n, n_t = (int)c->tgt.n;
-  if (n_t == 0 || n_s < kGicpK || n_t < kGicpK) return gicp_run_finish_early(c, r);
-  // GICP keeps d2 < r^2 (strict): the largest float below r^2
-  const icpgpu_params& P = c->params;
-  const double r2 = P.max_correspondence_distance * P.max_correspondence_distance;
-  r.thr = threshold_from(r2);
-  if ((double)r.thr >= r2) r.thr = std::nextafterf(r.thr, -INFINITY);
-  r.thr_excl = std::nextafterf(r.thr, INFINITY);  // d2 < thr_excl  <=>  d2 <= thr
+  if (gicp_too_small(c)) {
+    gicp_finish_early(c);
+    gicp_stamp_total(r);
+    r.phase = GicpRun::Done;
+    return ICPGPU_OK;
+  }
   r.cov_stage = 0;
   return gicp_run_next_cov(c, r);
 }
@@ -1096,42 +1118,42 @@ static int gicp_run_restart_blocking(icpgpu_ctx* c, GicpRun& r) {
 // the registration is over: result record, fitness sweep or Done
 static int gicp_run_conclude(icpgpu_ctx* c, GicpRun& r) {
   float fin[16];
-  gicp_compose_final(r.previous, r.guess, fin);
-  std::memcpy(r.res->T, fin, sizeof(fin));
-  for (int i = 0; i < 16; ++i) c->final_T[i] = (double)fin[i];
-  c->have_final = true;
-  r.res->converged = r.converged ? 1 : 0;
-  r.res->iterations = r.nr;
-  r.res->convergence_state = r.state;
-  r.res->n_correspondences = r.n_corr;
-  r.res->mse_last = r.mse;
+  gicp_write_result(c, r, fin);
   if (r.want_fitness) {
-    r.phase = GicpRun::Fitness;
-    r.polls = 0;
-    r.t_issue = std::chrono::steady_clock::now();
+    gicp_run_await(r, GicpRun::Fitness);
     return sweep_issue(c, xform_from_f16(fin), FLT_MAX, /*open_range=*/true, r.ticket);
   }
-  r.res->t_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r.t_start).count();
+  gicp_stamp_total(r);
   r.phase = GicpRun::Done;
   return ICPGPU_OK;
 }
 
-// an outer iteration's minimiser is in: the new transformation, PCL's convergence test, then the end or the next outer iteration
-static int gicp_run_after_solve(icpgpu_ctx* c, GicpRun& r, const Vec6& x) {
-  const icpgpu_params& P = c->params;
-  mat4f_identity(r.transformation);
-  gicp_apply_state(r.transformation, x);
-  const double delta = gicp_outer_delta(r.previous, r.transformation, 2e-3, P.transformation_epsilon);
-  ++r.nr;
-  c->prof.iterations += 1;
-  if (r.nr >= P.max_iterations || (delta < 1 && !P.force_iterations)) {
-    r.converged = true;
-    r.state = r.nr >= P.max_iterations ? ICPGPU_CONV_ITERATIONS : ICPGPU_CONV_TRANSFORM;
-    std::memcpy(r.previous, r.transformation, sizeof(r.previous));
-    return gicp_run_conclude(c, r);
-  }
-  return gicp_run_queue_outer(c, r);
+// an inner minimisation is in (go_on: x is its minimiser; else the registration is over): the end, or the next outer iteration
+static int gicp_run_after_solve(icpgpu_ctx* c, GicpRun& r, bool go_on, const Vec6& x) {
+  if (go_on) gicp_outer_advance(c, r, x);
+  const int rc = (go_on && !r.converged) ? gicp_run_queue_outer(c, r) : gicp_run_conclude(c, r);
+  return rc ? rc : 1;
 }
+
+#if defined(ICPGPU_DEV_SWITCHES)
+// development flavour, ICPGPU_BATCH_TRACE=1: where the device solver's microseconds go with several runs in flight
+static void gicp_run_trace(const double* out, std::chrono::steady_clock::time_point t_issue) {
+  static const bool trace = [] { const char* e = std::getenv("ICPGPU_BATCH_TRACE"); return e && std::atoi(e) != 0; }();
+  if (!trace) return;
+  static std::atomic<unsigned long long> n_runs{0}, n_evals{0}, ph[7];
+  for (int k = 0; k < 6; ++k) ph[k].fetch_add((unsigned long long)(out[12 + k] * 100.0));
+  ph[6].fetch_add((unsigned long long)(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_issue).count() * 100.0));
+  n_evals.fetch_add((unsigned long long)out[10]);
+  if ((n_runs.fetch_add(1) & 1023u) == 1023u) {
+    const double ne = (double)n_evals.load();
+    fprintf(stderr, "[icpgpu] device solver, mean per evaluation over %llu runs: state -> transform %.2f | accumulate %.2f | reduce + publish %.2f | gather %.2f | "
+                    "gradient %.2f | kernel total %.2f us; host: launch -> result %.2f us\n", n_runs.load(), ph[0].load() * 0.01 / ne, ph[1].load() * 0.01 / ne,
+            ph[2].load() * 0.01 / ne, ph[3].load() * 0.01 / ne, ph[4].load() * 0.01 / ne, ph[5].load() * 0.01 / ne, ph[6].load() * 0.01 / ne);
+  }
+}
+#else
+static void gicp_run_trace(const double*, std::chrono::steady_clock::time_point) {}
+#endif
 
 // One non-blocking step.  Returns < 0 on error, 0 when nothing has arrived yet, 1 when the run moved on (r.phase == Done: finished).
 int gicp_run_step(icpgpu_ctx* c, GicpRun& r) {
@@ -1144,17 +1166,8 @@ int gicp_run_step(icpgpu_ctx* c, GicpRun& r) {
       r.phase = GicpRun::Done;
       return 1;
     case GicpRun::CovGrid: {
-      if (!run_marker_seen(c, r.marker)) {
-        if ((++r.polls & 0x3FFu) != 0) return 0;
-        const hipError_t q = hipStreamQuery(c->stream);
-        if (q != hipSuccess && q != hipErrorNotReady) return fail(c, ICPGPU_ERR_HIP, "HIP error while waiting for an index build: %s", hipGetErrorString(q));
-        if (q == hipErrorNotReady) {
-          if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r.t_issue).count() > wait_timeout_ms())
-            return fail(c, ICPGPU_ERR_HIP, "timed out after %.0f ms waiting for an index build (hung kernel?)", wait_timeout_ms());
-          return 0;
-        }
-        // (the stream has drained: the read-back is there whether or not the marker's pair shows -- the stream's word is as good)
-      }
+      // (a drained stream is as good as the marker: the read-back is there whether or not the marker's pair shows)
+      if (!run_marker_seen(c, r.marker) && (rc = poll_mailbox(c, c->stream, "an index build", r.polls, r.t_issue)) <= 0) return rc;
       std::atomic_thread_fence(std::memory_order_acquire);
       if ((rc = gb_advance(c, r.gb))) return rc;
       const bool tgt = r.cov_stage == 0;
@@ -1175,29 +1188,17 @@ int gicp_run_step(icpgpu_ctx* c, GicpRun& r) {
     }
     case GicpRun::Solve: {
       double out[24];
-      const int n = gicp_solve_out_granules();
-      bool all = true;
-      for (int k = 0; k < n; ++k) all = gicp_granule_read(c->h_solve + 2 * k, r.seq0, &out[k]) && all;
-      bool gave_up = false;
-      if (!all) {
-        if ((++r.polls & 0x3FFu) != 0) return 0;
-        const hipError_t q = hipStreamQuery(r.solve_stream ? r.solve_stream : c->stream);
-        if (q != hipSuccess && q != hipErrorNotReady) return fail(c, ICPGPU_ERR_HIP, "HIP error while waiting for the GICP device solver: %s", hipGetErrorString(q));
-        if (q == hipErrorNotReady) {
-          if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r.t_issue).count() > wait_timeout_ms())
-            return fail(c, ICPGPU_ERR_HIP, "timed out after %.0f ms waiting for the GICP device solver (hung kernel?)", wait_timeout_ms());
-          return 0;
-        }
-        all = true;
-        for (int k = 0; k < n; ++k) all = gicp_granule_read(c->h_solve + 2 * k, r.seq0, &out[k]) && all;
-        gave_up = !all;  // the stream went idle without an answer
+      bool answered = solve_result_read(c, r.seq0, out);
+      if (!answered) {
+        if ((rc = poll_mailbox(c, r.solve_stream ? r.solve_stream : c->stream, "the GICP device solver", r.polls, r.t_issue)) <= 0) return rc;
+        answered = solve_result_read(c, r.seq0, out);  // (a drained stream without an answer: the kernel gave up, as for wait_solve_result's caller)
       }
       std::atomic_thread_fence(std::memory_order_acquire);
-      const int status = gave_up ? (int)gicp::kDeviceError : (int)out[0];
-      if (status == gicp::kDeviceError) {  // a gather timed out (or the kernel never answered): this pair goes through the blocking path
+      if (!answered || (int)out[0] == gicp::kDeviceError) {  // a gather timed out (or the kernel never answered): this pair goes through the blocking path
         // Under a batch a timeout can be a scheduling accident (a run's workgroups waiting for CUs other launches hold), so ONE
-        // does not switch the worker's device solver off for good, as it did until round 6: three in a row do.  Said once per
-        // process on stderr either way -- the batch keeps its results (same bits) and loses speed, which nobody would notice otherwise.
+        // does not switch the worker's device solver off for good, as it does in align_gicp and did here until round 6: three in a
+        // row do.  Said once per process on stderr either way -- the batch keeps its results (same bits) and loses speed, which
+        // nobody would notice otherwise.
         static std::atomic<bool> said{false};
         if (!said.exchange(true) || std::getenv("ICPGPU_DEBUG"))
           fprintf(stderr, "[icpgpu] GICP batch: the device solver%s gave no answer for a run; that pair is solved through the blocking path "
@@ -1209,102 +1210,33 @@ int gicp_run_step(icpgpu_ctx* c, GicpRun& r) {
         return gicp_run_restart_blocking(c, r) ? -1 : 1;
       }
       c->gicp_device_failures = 0;
-      c->prof.gicp_device_solves += 1;
-      r.res->gicp_solver = ICPGPU_GICP_SOLVER_DEVICE;
-      const double m = out[7], evals = out[10];
-#if defined(ICPGPU_DEV_SWITCHES)
-      {  // development flavour, ICPGPU_BATCH_TRACE=1: where the device solver's microseconds go with several runs in flight
-        static const bool trace = [] { const char* e = std::getenv("ICPGPU_BATCH_TRACE"); return e && std::atoi(e) != 0; }();
-        if (trace) {
-          static std::atomic<unsigned long long> n_runs{0}, n_evals{0}, ph[7];
-          for (int k = 0; k < 6; ++k) ph[k].fetch_add((unsigned long long)(out[12 + k] * 100.0));
-          ph[6].fetch_add((unsigned long long)(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - r.t_issue).count() * 100.0));
-          n_evals.fetch_add((unsigned long long)evals);
-          if ((n_runs.fetch_add(1) & 1023u) == 1023u) {
-            const double ne = (double)n_evals.load();
-            fprintf(stderr, "[icpgpu] device solver, mean per evaluation over %llu runs: state -> transform %.2f | accumulate %.2f | reduce + publish %.2f | gather %.2f | "
-                            "gradient %.2f | kernel total %.2f us; host: launch -> result %.2f us\n", n_runs.load(), ph[0].load() * 0.01 / ne, ph[1].load() * 0.01 / ne,
-                    ph[2].load() * 0.01 / ne, ph[3].load() * 0.01 / ne, ph[4].load() * 0.01 / ne, ph[5].load() * 0.01 / ne, ph[6].load() * 0.01 / ne);
-          }
-        }
-      }
-#endif
-      r.mse = m > 0 ? out[8] / m : 0.0;
-      r.n_corr = (unsigned)m;
-      c->prof.gicp_cost_launches += (uint64_t)evals;
-      c->prof.gicp_eval_corr += (uint64_t)(m * evals);
-      c->prof.gicp_eval_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r.t_issue).count();
-      std::memcpy(r.previous, r.transformation, sizeof(r.previous));
-      if (status == gicp::kNotEnoughPoints) {  // NotEnoughPointsException -> the loop breaks with converged_ = false
-        r.state = ICPGPU_CONV_NO_CORRESPONDENCES;
-        if ((rc = gicp_run_conclude(c, r))) return rc;
-        return 1;
-      }
-      if (status != gicp::kOk) {  // SolverDidntConvergeException
-        r.state = ICPGPU_NOT_CONVERGED;
-        if ((rc = gicp_run_conclude(c, r))) return rc;
-        return 1;
-      }
+      gicp_run_trace(out, r.t_issue);
       Vec6 x;
-      for (int k = 0; k < 6; ++k) x[k] = out[1 + k];
-      if ((rc = gicp_run_after_solve(c, r, x))) return rc;
-      return 1;
+      const bool go_on = gicp_take_device_result(c, r, out, r.t_issue, x);  // (a run's eval_ms runs from the launch)
+      return gicp_run_after_solve(c, r, go_on, x);
     }
     case GicpRun::Quad: {
       double sums[2 * kGicpQuadSums];
       if (!quad_sums_read(c, r.seq0, sums)) {
-        if ((++r.polls & 0x3FFu) != 0) return 0;
-        const hipError_t q = hipStreamQuery(c->stream);
-        if (q != hipSuccess && q != hipErrorNotReady) return fail(c, ICPGPU_ERR_HIP, "HIP error while waiting for the GICP quadratic pass: %s", hipGetErrorString(q));
-        if (q == hipErrorNotReady) {
-          if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r.t_issue).count() > wait_timeout_ms())
-            return fail(c, ICPGPU_ERR_HIP, "timed out after %.0f ms waiting for the GICP quadratic pass (hung kernel?)", wait_timeout_ms());
-          return 0;
-        }
-        if (!quad_sums_read(c, r.seq0, sums)) return fail(c, ICPGPU_ERR_HIP, "the GICP quadratic pass finished without publishing its sums");
+        if ((rc = poll_mailbox(c, c->stream, "the GICP quadratic pass", r.polls, r.t_issue)) <= 0) return rc;
+        if (!quad_sums_read(c, r.seq0, sums)) return quad_sums_lost(c);
       }
       std::atomic_thread_fence(std::memory_order_acquire);
-      c->quad_pending = false;
-      const double m = sums[2 * 73], d2 = sums[2 * 74];
-      r.mse = m > 0 ? d2 / m : 0.0;
-      r.n_corr = (unsigned)m;
-      std::memcpy(r.previous, r.transformation, sizeof(r.previous));
-      if (r.n_corr < 4) {  // NotEnoughPointsException -> the loop breaks with converged_ = false
-        r.state = ICPGPU_CONV_NO_CORRESPONDENCES;
-        if ((rc = gicp_run_conclude(c, r))) return rc;
-        return 1;
-      }
-      Vec6 x = gicp_state_from_matrix(r.transformation);
-      int evals = 0;
-      const GicpSolve sr = gicp_minimize_quadratic(sums, r.guess, x, 20, 1e-2, &evals);
-      c->prof.gicp_quadratic_solves += 1;
-      r.res->gicp_solver = ICPGPU_GICP_SOLVER_QUADRATIC;
-      c->prof.gicp_cost_launches += (uint64_t)evals;
-      c->prof.gicp_eval_corr += (uint64_t)(m * evals);
-      c->prof.gicp_eval_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r.t_issue).count();
-      if (sr != GicpSolve::Ok) {  // SolverDidntConvergeException
-        r.state = ICPGPU_NOT_CONVERGED;
-        if ((rc = gicp_run_conclude(c, r))) return rc;
-        return 1;
-      }
-      if ((rc = gicp_run_after_solve(c, r, x))) return rc;
-      return 1;
+      Vec6 x;
+      const bool go_on = gicp_take_quadratic_sums(c, r, sums, r.t_issue, x);
+      return gicp_run_after_solve(c, r, go_on, x);
     }
     case GicpRun::Fitness: {
       if (!sweep_ready(c, r.ticket)) {
-        if ((++r.polls & 0x3FFu) == 0) {
-          const hipError_t q = hipStreamQuery(c->stream);
-          if (q != hipSuccess && q != hipErrorNotReady) return fail(c, ICPGPU_ERR_HIP, "HIP error while waiting for a reduction: %s", hipGetErrorString(q));
-          if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r.t_issue).count() > wait_timeout_ms())
-            return fail(c, ICPGPU_ERR_HIP, "timed out after %.0f ms waiting for a kernel's result (hung kernel?)", wait_timeout_ms());
-        }
-        return 0;
+        // (the stream is asked for errors only: drained or not, the clock decides -- as in wait_posted; kept)
+        rc = poll_mailbox(c, c->stream, {"a reduction", "a kernel's result"}, r.polls, r.t_issue, WhenIdle::KeepWaiting);
+        return rc < 0 ? rc : 0;
       }
       if ((rc = sweep_complete(c, r.ticket))) return rc;
       r.res->fitness = c->h_sums[0] > 0.0 ? c->h_sums[16] / c->h_sums[0] : DBL_MAX;
       if ((rc = resolve_sweep_timings(c, /*block=*/false))) return rc;
       r.res->t_device_ms = 0.0;  // (not sampled on this path)
-      r.res->t_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r.t_start).count();
+      gicp_stamp_total(r);
       r.phase = GicpRun::Done;
       return 1;
     }

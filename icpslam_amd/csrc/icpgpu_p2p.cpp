@@ -138,28 +138,11 @@ void take_sums(icpgpu_ctx* c) {
 // Spin on the mailbox flags until every term of sweep `seq` has landed.  The stream is queried now and then so that a
 // faulted kernel turns into an error instead of an endless wait, and the clock so that a hung one does.
 int wait_flags(icpgpu_ctx* c, const volatile unsigned long long* flags, int n_flags, unsigned long long seq) {
-  std::chrono::steady_clock::time_point t0;
-  for (unsigned spins = 1;; ++spins) {
-    if (flags_ready(flags, n_flags, seq)) break;
-    if ((spins & 0x3FFu) == 0) {
-      const hipError_t q = hipStreamQuery(c->stream);
-      if (q == hipSuccess) {  // everything retired: the flags must be there on the next look
-        if (flags_ready(flags, n_flags, seq)) break;
-        return fail(c, ICPGPU_ERR_HIP, "reduction finished without publishing its result");
-      }
-      if (q != hipErrorNotReady) return fail(c, ICPGPU_ERR_HIP, "HIP error while waiting for a reduction: %s", hipGetErrorString(q));
-      const auto now = std::chrono::steady_clock::now();
-      if (spins == 0x400u) t0 = now;
-      else if (std::chrono::duration<double, std::milli>(now - t0).count() > wait_timeout_ms())
-        return fail(c, ICPGPU_ERR_HIP, "timed out after %.0f ms waiting for a kernel's result (hung kernel?)", wait_timeout_ms());
-    }
-    if (spins > 8192u) std::this_thread::yield();  // a long (brute-force) sweep: stop monopolising the core
-#if defined(__x86_64__)
-    else __builtin_ia32_pause();
-#endif
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return ICPGPU_OK;
+  // (a long brute-force sweep stops monopolising the core after 8192 looks)
+  const int w = wait_mailbox(c, c->stream, {"a reduction", "a kernel's result"}, [&] { return flags_ready(flags, n_flags, seq); }, WhenIdle::Report, 8192u);
+  // a drained stream means the reduction's last kernel has retired: nothing will post the sums any more
+  if (w == 1) return fail(c, ICPGPU_ERR_HIP, "reduction finished without publishing its result");
+  return w;
 }
 
 int wait_sums(icpgpu_ctx* c, unsigned long long seq) {
