@@ -4,6 +4,8 @@ Only what the hot path needs: csrc/ (HIP kernels + C-ABI, built into libicpgpu.s
 the PCL-Registration-shaped host mirror and the synthetic scan generator.  No CPU fallback.
 """
 from ._lib import GICP, GICP_INNER_EXACT, NDT, NDT_LINE_SEARCH_MORE_THUENTE, NDT_LINE_SEARCH_PCL18, P2PLANE, GICP_INNER_QUADRATIC, NN_AUTO, NN_BRUTE, NN_GRID, P2P_SVD, STATE_NAMES, IcpGpuError, Params, Profile, Result  # noqa: F401
+from .registration import CorrespondenceRejectorMedianDistance, CorrespondenceRejectorOneToOne, CorrespondenceRejectorTrimmed  # noqa: F401
+from ._lib import REJECT_MEDIAN_DISTANCE, REJECT_ONE_TO_ONE, REJECT_TRIMMED, Rejector  # noqa: F401
 from .registration import Context, GeneralizedIterativeClosestPoint, IterativeClosestPoint, IterativeClosestPointWithNormals, NormalDistributionsTransform  # noqa: F401
 
 __all__ = ["Context", "IterativeClosestPoint", "GeneralizedIterativeClosestPoint", "IterativeClosestPointWithNormals", "NormalDistributionsTransform", "IcpGpuError", "Params", "Result",

@@ -23,6 +23,8 @@ GICP_INNER_EXACT, GICP_INNER_QUADRATIC = 0, 1
 GICP_SOLVER_NONE, GICP_SOLVER_HOST, GICP_SOLVER_DEVICE, GICP_SOLVER_QUADRATIC = 0, 1, 2, 3
 HEADER_VERSION = 1002          # the icpgpu.h these mirrors were written against (ICPGPU_HEADER_VERSION)
 NN_AUTO, NN_BRUTE, NN_GRID = 0, 1, 2
+REJECT_MEDIAN_DISTANCE, REJECT_TRIMMED, REJECT_ONE_TO_ONE = 1, 2, 3   # icpgpu_rejector_kind
+MAX_REJECTORS = 4
 STATE_NAMES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE",
                5: "NO_CORRESPONDENCES"}
 
@@ -61,6 +63,10 @@ class Profile(C.Structure):
                 ("cov_grids_unchecked", C.c_uint64), ("cov_grids_rebuilt", C.c_uint64), ("voxel_views_direct", C.c_uint64)]
 
 
+class Rejector(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("min_correspondences", C.c_int32), ("value", C.c_double)]
+
+
 class Pose(C.Structure):
     _fields_ = [("pos", C.c_double * 3), ("quat", C.c_double * 4)]
 
@@ -85,6 +91,7 @@ EXPORTS = [
     "icpgpu_set_ndt_params", "icpgpu_get_ndt_params", "icpgpu_ndt_transformation_probability", "icpgpu_ndt_cells",
     "icpgpu_ndt_derivatives", "icpgpu_ndt_step", "icpgpu_set_ndt_line_search", "icpgpu_get_ndt_line_search", "icpgpu_ndt_gradient",
     "icpgpu_ndt_line_search_replay", "icpgpu_ndt_line_search_trace",
+    "icpgpu_set_correspondence_rejectors", "icpgpu_get_correspondence_rejectors", "icpgpu_correspondences", "icpgpu_rejector_stats",
 ]
 
 _lib = None
@@ -163,6 +170,10 @@ def load():
     L.icpgpu_ndt_gradient.argtypes = [vp, dp, dp]
     L.icpgpu_ndt_line_search_replay.argtypes = [C.c_double] * 5 + [dp, dp, C.c_int, dp, ip]
     L.icpgpu_ndt_line_search_trace.argtypes = [vp, C.c_size_t, C.POINTER(C.c_int32), dp, dp, dp, C.POINTER(C.c_size_t)]
+    L.icpgpu_set_correspondence_rejectors.argtypes = [vp, C.POINTER(Rejector), C.c_size_t]
+    L.icpgpu_get_correspondence_rejectors.argtypes = [vp, C.POINTER(Rejector), C.POINTER(C.c_size_t)]
+    L.icpgpu_correspondences.argtypes = [vp, fp, ip, fp]
+    L.icpgpu_rejector_stats.argtypes = [vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), fp, C.POINTER(C.c_size_t)]
     L.icpgpu_voxel_grid.argtypes = [vp, fp, C.c_size_t, C.c_float, fp, C.POINTER(C.c_size_t)]
     L.icpgpu_voxel_grid_fetch.argtypes = [vp, fp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.icpgpu_voxel_grid_view.argtypes = [vp, fp, C.c_size_t, C.c_float, C.POINTER(fp), C.POINTER(C.c_size_t)]

@@ -3,6 +3,7 @@
 //   icpgpu_context.cpp  create / destroy, parameters, clouds (upload, recognition, promote), profile, stream
 //   icpgpu_index.cpp    the target's uniform grid: resumable builds, cell-size rules, the grid search's dispatch
 //   icpgpu_p2p.cpp      point-to-point ICP: sweeps (search + fused reduction), the mailbox, the resumable run, align / fitness
+//   icpgpu_reject.cpp   the correspondence rejectors: the chain, its sweep, icpgpu_correspondences
 //   icpgpu_gicp.cpp     GICP: covariances, the evaluation server, the BFGS outer loop
 //   icpgpu_batch.cpp    icpgpu_align_batch: lock-step groups and the round-robin scheduler
 //   icpgpu_voxel.cpp    the voxel-grid filter's host side
@@ -254,6 +255,17 @@ struct icpgpu_ctx {
     NdtLattice L{};
   } ndt;
   DeviceBuf ndt_partials;
+  // the correspondence rejectors (icpgpu_reject.cpp): the chain, the stages' histograms and statistics, the one-to-one winner
+  // array, and the statistics of the chain's last run as the host last fetched them (rej_ran: stages whose statistics in
+  // rej_state have not been fetched yet)
+  icpgpu_rejector rejectors[ICPGPU_MAX_REJECTORS] = {};
+  int n_rejectors = 0;
+  DeviceBuf rej_state, rej_winners, rej_post;
+  int rej_ran = 0;
+  struct RejStats {
+    uint32_t pairs_in, pairs_out, cut_bits;
+  } rej_stats[ICPGPU_MAX_REJECTORS] = {};
+  size_t rej_stats_n = 0;
   // the NDT step rule (icpgpu_ndt_line_search: 0 = PCL 1.8's clamped Newton step, 1 = More-Thuente) and the last alignment's
   // line-search trials (More-Thuente only): Newton iteration, step, phi = -score, phi' = -(g . d)
   int ndt_line_search = 0;
@@ -584,6 +596,11 @@ int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_f
 // x = (A^T A)^-1 A^T r from the 29 sums (partial-pivot LU, float64) -> Tk = constructTransformationMatrix(x); false (Tk = identity)
 // when a pivot is zero or x is not finite
 bool solve_point_to_plane(const double sums[kP2planeTerms], Mat4d& Tk);
+// icpgpu_reject.cpp
+int gated_keys(icpgpu_ctx* c, const Xform& T, float thr, unsigned long long* keys);
+int reject_run_chain(icpgpu_ctx* c, unsigned long long* keys, float thr);
+int reject_fetch_stats(icpgpu_ctx* c);
+int sweep_issue_rejected(icpgpu_ctx* c, const Xform& T, float thr, SweepTicket& tk);
 // icpgpu_ndt.cpp
 int align_ndt(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitness, icpgpu_result* res);
 

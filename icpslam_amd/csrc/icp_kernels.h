@@ -345,6 +345,25 @@ hipError_t launch_p2plane_reduce(const float4* src, int n_s, const float4* tgt, 
 hipError_t launch_terms29_final(const double* partials, int n_blocks, double* sums_out, unsigned long long* flags, unsigned long long seq,
                                 hipStream_t stream, int n_terms = 29);
 
+// ---- correspondence rejectors (icp_reject.hip): stages between a key-writing search and a keys reduction ---------------------
+// A stage rewrites the keys of the pairs it rejects to kEmptyKey; a pair is alive when its key names a target and its d2 <= thr.
+static constexpr int kRejectMedian = 1, kRejectTrimmed = 2, kRejectOneToOne = 3;  // = icpgpu_rejector_kind
+static constexpr int kRejectMaxStages = 4;
+struct RejectStage {
+  int kind;
+  unsigned int min_corr;  // trimmed
+  float ratio;            // trimmed: overlap ratio (float, as PCL holds it)
+  double factor;          // median
+};
+// per stage, unsigned ints of device memory: the radix select's three histograms (digits of 11, 11, 10 bits), then the statistics
+// {pairs in, pairs out, bits of the cut (float d2; 0 where a stage has none), 0}
+static constexpr int kRejectHist0 = 0, kRejectHist1 = 2048, kRejectHist2 = 4096, kRejectStats = 5120, kRejectStateInts = 5128;
+// state: n_stages x kRejectStateInts ints; winners: n_t 64-bit words (one-to-one stages only, else may be null)
+hipError_t launch_reject_chain(unsigned long long* keys, int n_s, int n_t, float thr, const RejectStage* stages, int n_stages,
+                               unsigned int* state, unsigned long long* winners, hipStream_t stream);
+// keys -> (idx, d2) for icpgpu_correspondences: idx = -1, d2 = +inf for a pair that is not alive
+hipError_t launch_reject_unpack(const unsigned long long* keys, int n, float thr, int32_t* idx, float* d2, hipStream_t stream);
+
 // ---- NDT (icp_ndt.hip): pcl::NormalDistributionsTransform's target cells and derivative pass ----------------------------
 static constexpr int kNdtTerms = 29;         // pairs, score, gradient (6), Hessian upper triangle row by row (21)
 static constexpr int kNdtGradTerms = 8;      // the trial pass's: pairs, score, gradient (6) -- the first 8 of the 29

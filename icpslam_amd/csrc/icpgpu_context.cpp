@@ -631,6 +631,7 @@ int icpgpu_destroy(icpgpu_ctx* c) {
   release(c->cov_tgt);
   for (DeviceBuf* b : {&c->nrm_src, &c->nrm_tgt, &c->nrm_raw, &c->nrm_user, &c->p2plane_partials}) release(*b);
   release(c->maha);
+  for (DeviceBuf* b : {&c->rej_state, &c->rej_winners, &c->rej_post}) release(*b);
   release(c->cov_list);
   release(c->vox_in);
   release(c->vox_out);

@@ -154,6 +154,7 @@ int wait_sums(icpgpu_ctx* c, unsigned long long seq) {
 
 
 int sweep_issue(icpgpu_ctx* c, const Xform& T, float thr, bool open_range, SweepTicket& tk) {
+  if (c->n_rejectors > 0 && !open_range) return sweep_issue_rejected(c, T, thr, tk);  // (getFitnessScore's sweep knows no rejectors)
   static const bool timing = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_P2P_TIMING"); return e && std::atoi(e) != 0; }();
   if (timing) {
     c->pt_issue_in = std::chrono::steady_clock::now();
@@ -407,6 +408,10 @@ void init_result(icpgpu_result* r) {
 
 int p2p_finish(icpgpu_ctx* c, P2PRun& r) {
   const Xform Tf = to_xform(r.final_T);
+  if (c->n_rejectors > 0) {  // the chain's statistics of the last iteration (icpgpu_rejector_stats)
+    const int rc_stats = reject_fetch_stats(c);
+    if (rc_stats) return rc_stats;
+  }
   // (the aligned cloud was queued in front of the fitness sweep when there was one: p2p_advance)
   int rc = r.out_done ? ICPGPU_OK
                       : (r.out_ticket.issued ? output_cloud_complete(c, r.out_ticket, r.out_xyzw) : write_output_cloud(c, Tf, r.out_xyzw));
@@ -433,6 +438,7 @@ int p2p_prepare(icpgpu_ctx* c, P2PRun& r, const float* guess, float* out_xyzw, i
     c->dev_ms_accum = 0.0;
     c->call_sweeps = c->call_timed = 0;
     c->prev.valid = c->tile_seed.valid = false;  // every alignment starts cold
+    c->rej_ran = 0;
   }
   if (guess)
     for (int i = 0; i < 16; ++i) r.final_T[i] = (double)guess[i];

@@ -121,28 +121,6 @@ static int wait_p2plane_sums(icpgpu_ctx* c, unsigned long long seq, double* sums
   return ICPGPU_OK;
 }
 
-// keys of T * source in the target, exact wherever d2 <= thr (the search GICP's outer iterations use)
-static int p2plane_keys(icpgpu_ctx* c, const Xform& T, float thr, unsigned long long* keys) {
-  const int n_s = (int)c->src.n, n_t = (int)c->tgt.n;
-  if (n_s <= 0) return ICPGPU_OK;
-  if (grid_ready(c)) {
-    unsigned int* prev = nullptr;  // each iteration's neighbours bound the next one's search
-    bool use_prev = false;
-    int rc = prev_neighbours(c, c->grid, c->src.data(), n_s, grid_flags(c->grid, false), prev, use_prev);
-    if (rc) return rc;
-    HIP_TRY(c, launch_nn_grid_search(c->src.data(), n_s, grid_flags(c->grid, false), T, static_cast<const float4*>(c->grid.sorted.ptr),
-                                     static_cast<const int*>(c->grid.cell_start.ptr), c->grid.g, thr, keys, nullptr, nullptr, nullptr,
-                                     c->stream, prev, use_prev));
-    c->prof.grid_launches += 1;
-    c->prof.grid_bytes += 16ull * ((uint64_t)n_s + (uint64_t)n_t) + 8ull * (uint64_t)n_s;
-    return ICPGPU_OK;
-  }
-  c->prof.nn_launches += 1;
-  c->prof.nn_pairs += (uint64_t)n_s * (uint64_t)n_t;
-  c->prof.nn_bytes += 16ull * ((uint64_t)n_s + (uint64_t)n_t) + 8ull * (uint64_t)n_s;
-  return nn_keys_brute(c, c->tgt.data(), n_t, T, keys);
-}
-
 int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitness, icpgpu_result* res) {
   const auto t_start = std::chrono::steady_clock::now();
   init_result(res);
@@ -152,6 +130,7 @@ int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_f
   c->dev_ms_accum = 0.0;
   c->call_sweeps = c->call_timed = 0;
   c->prev.valid = c->tile_seed.valid = false;  // every alignment starts cold
+  c->rej_ran = 0;
   Mat4d final_T = mat4_identity();
   if (guess)
     for (int i = 0; i < 16; ++i) final_T[i] = (double)guess[i];
@@ -175,7 +154,8 @@ int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_f
     double sums[kP2planeTerms];
     for (;;) {
       const Xform T = to_xform(final_T);
-      if ((rc = p2plane_keys(c, T, thr, keys))) return rc;
+      if ((rc = gated_keys(c, T, thr, keys))) return rc;
+      if ((rc = reject_run_chain(c, keys, thr))) return rc;  // (an empty chain: nothing)
       const unsigned long long seq = ++c->sums_seq;
       HIP_TRY(c, launch_p2plane_reduce(c->src.data(), n_s, c->tgt.data(), normals, keys, T, thr, static_cast<double*>(c->p2plane_partials.ptr),
                                        nullptr, c->h_flags_dev, wire_seq(c, seq), c->stream));
@@ -205,6 +185,7 @@ int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_f
       }
     }
   }
+  if (c->n_rejectors > 0 && (rc = reject_fetch_stats(c))) return rc;  // the chain's statistics of the last iteration
   c->final_T = final_T;
   c->have_final = true;
   mat4_to_float(final_T, res->T);

@@ -1,0 +1,179 @@
+// icpgpu_reject.cpp -- the correspondence rejectors' host side (PCL: Registration::addCorrespondenceRejector and
+// CorrespondenceRejectorMedianDistance / Trimmed / OneToOne): the context's chain, the gated key-writing search the chain runs
+// behind, the chain's launch (icp_reject.hip), the point-to-point sweep with a chain, and the entry points that show what a chain
+// keeps (icpgpu_correspondences, icpgpu_rejector_stats).  An iteration with a chain is search -> stages -> the method's keys
+// reduction, queued back to back: nothing of the chain is read by the host until the alignment ends (reject_fetch_stats: one
+// posted read-back of the last iteration's statistics through the result mailbox).
+#include "icp_ctx.h"
+
+namespace icpgpu_impl {
+
+// keys of T * source (the caller's order) in the target, exact wherever d2 <= thr: the gated grid search, or the brute-force keys
+int gated_keys(icpgpu_ctx* c, const Xform& T, float thr, unsigned long long* keys) {
+  const int n_s = (int)c->src.n, n_t = (int)c->tgt.n;
+  if (n_s <= 0) return ICPGPU_OK;
+  if (grid_ready(c)) {
+    unsigned int* prev = nullptr;  // each iteration's neighbours bound the next one's search
+    bool use_prev = false;
+    int rc = prev_neighbours(c, c->grid, c->src.data(), n_s, grid_flags(c->grid, false), prev, use_prev);
+    if (rc) return rc;
+    HIP_TRY(c, launch_nn_grid_search(c->src.data(), n_s, grid_flags(c->grid, false), T, static_cast<const float4*>(c->grid.sorted.ptr),
+                                     static_cast<const int*>(c->grid.cell_start.ptr), c->grid.g, thr, keys, nullptr, nullptr, nullptr,
+                                     c->stream, prev, use_prev));
+    c->prof.grid_launches += 1;
+    c->prof.grid_bytes += 16ull * ((uint64_t)n_s + (uint64_t)n_t) + 8ull * (uint64_t)n_s;
+    return ICPGPU_OK;
+  }
+  c->prof.nn_launches += 1;
+  c->prof.nn_pairs += (uint64_t)n_s * (uint64_t)n_t;
+  c->prof.nn_bytes += 16ull * ((uint64_t)n_s + (uint64_t)n_t) + 8ull * (uint64_t)n_s;
+  return nn_keys_brute(c, c->tgt.data(), n_t, T, keys);
+}
+
+int reject_run_chain(icpgpu_ctx* c, unsigned long long* keys, float thr) {
+  const int n = c->n_rejectors;
+  if (n <= 0) return ICPGPU_OK;
+  const int n_s = (int)c->src.n, n_t = (int)c->tgt.n;
+  RejectStage stages[kRejectMaxStages];
+  bool winners = false;
+  for (int s = 0; s < n; ++s) {
+    const icpgpu_rejector& r = c->rejectors[s];
+    stages[s].kind = r.kind;
+    stages[s].min_corr = (unsigned int)r.min_correspondences;
+    stages[s].ratio = (float)r.value;
+    stages[s].factor = r.value;
+    winners = winners || r.kind == ICPGPU_REJECT_ONE_TO_ONE;
+  }
+  int rc = ensure(c, c->rej_state, (size_t)kRejectMaxStages * kRejectStateInts * sizeof(unsigned int));
+  if (rc) return rc;
+  if (winners && (rc = ensure(c, c->rej_winners, (size_t)(n_t ? n_t : 1) * sizeof(unsigned long long)))) return rc;
+  HIP_TRY(c, launch_reject_chain(keys, n_s, n_t, thr, stages, n, static_cast<unsigned int*>(c->rej_state.ptr),
+                                 static_cast<unsigned long long*>(c->rej_winners.ptr), c->stream));
+  c->rej_ran = n;
+  return ICPGPU_OK;
+}
+
+// the statistics of the chain's last run -> c->rej_stats (zeroes when the chain has not run since they were last taken)
+int reject_fetch_stats(icpgpu_ctx* c) {
+  std::memset(c->rej_stats, 0, sizeof c->rej_stats);
+  c->rej_stats_n = c->n_rejectors;
+  if (c->rej_ran <= 0) return ICPGPU_OK;
+  const int n = c->rej_ran;
+  c->rej_ran = 0;
+  if ((int)c->rej_stats_n < n) c->rej_stats_n = n;
+  int rc = ensure(c, c->rej_post, (size_t)kRejectMaxStages * 3 * sizeof(int));
+  if (rc) return rc;
+  for (int s = 0; s < n; ++s)
+    HIP_TRY(c, hipMemcpyAsync(static_cast<int*>(c->rej_post.ptr) + 3 * s,
+                              static_cast<const unsigned int*>(c->rej_state.ptr) + (size_t)s * kRejectStateInts + kRejectStats, 3 * sizeof(int),
+                              hipMemcpyDeviceToDevice, c->stream));
+  int h[kRejectMaxStages * 3];
+  if ((rc = fetch_ints(c, static_cast<const int*>(c->rej_post.ptr), 3 * n, h))) return rc;
+  for (int s = 0; s < n; ++s) {
+    c->rej_stats[s].pairs_in = (uint32_t)h[3 * s];
+    c->rej_stats[s].pairs_out = (uint32_t)h[3 * s + 1];
+    c->rej_stats[s].cut_bits = (uint32_t)h[3 * s + 2];
+  }
+  return ICPGPU_OK;
+}
+
+// sweep_issue's counterpart for a context with a chain (gated sweeps only): the key-writing search over the source in the caller's
+// order (one-to-one breaks ties on the caller's source index), the chain, reduce_kernel over the keys that are left
+int sweep_issue_rejected(icpgpu_ctx* c, const Xform& T, float thr, SweepTicket& tk) {
+  const int n_s = (int)c->src.n;
+  int rc = ensure(c, c->keys, (size_t)(n_s ? n_s : 1) * sizeof(unsigned long long));
+  if (rc) return rc;
+  auto* keys = static_cast<unsigned long long*>(c->keys.ptr);
+  if ((rc = gated_keys(c, T, thr, keys))) return rc;
+  if ((rc = reject_run_chain(c, keys, thr))) return rc;
+  if ((rc = ensure(c, c->partials, (size_t)kMaxReduceBlocks * kReduceTerms * sizeof(double)))) return rc;
+  const unsigned long long seq = ++c->sums_seq;
+  HIP_TRY(c, launch_reduce(c->src.data(), n_s, c->tgt.data(), keys, T, thr, static_cast<double*>(c->partials.ptr), c->h_sums_dev,
+                           c->h_flags_dev, wire_seq(c, seq), c->stream));
+  c->call_sweeps += 1;
+  c->prof.reduce_launches += 1;
+  c->prof.reduce_bytes += 40ull * (uint64_t)n_s + 136;
+  tk = SweepTicket{};
+  tk.seq = seq;
+  tk.red_src = c->src.data();
+  tk.red_n = n_s;
+  tk.T = T;
+  tk.thr = thr;
+  return ICPGPU_OK;
+}
+
+static bool rejector_valid(const icpgpu_rejector& r) {
+  switch (r.kind) {
+    case ICPGPU_REJECT_MEDIAN_DISTANCE: return std::isfinite(r.value) && r.value >= 0.0;
+    case ICPGPU_REJECT_TRIMMED: return r.value >= 0.0 && r.value <= 1.0 && r.min_correspondences >= 0;
+    case ICPGPU_REJECT_ONE_TO_ONE: return true;
+    default: return false;
+  }
+}
+
+}  // namespace icpgpu_impl
+
+extern "C" {
+
+int icpgpu_set_correspondence_rejectors(icpgpu_ctx* c, const icpgpu_rejector* rejectors, size_t n) {
+  if (!c) return fail(nullptr, ICPGPU_ERR_INVALID_ARG, "null context");
+  if (n > (size_t)ICPGPU_MAX_REJECTORS) return fail(c, ICPGPU_ERR_INVALID_ARG, "set_correspondence_rejectors: %zu rejectors (at most %d)", n, ICPGPU_MAX_REJECTORS);
+  if (n && !rejectors) return fail(c, ICPGPU_ERR_INVALID_ARG, "set_correspondence_rejectors: null rejectors");
+  for (size_t s = 0; s < n; ++s)
+    if (!rejector_valid(rejectors[s]))
+      return fail(c, ICPGPU_ERR_INVALID_ARG, "set_correspondence_rejectors: rejector %zu (kind %d, value %g, min_correspondences %d) is not valid", s,
+                  (int)rejectors[s].kind, rejectors[s].value, (int)rejectors[s].min_correspondences);
+  for (size_t s = 0; s < n; ++s) c->rejectors[s] = rejectors[s];
+  c->n_rejectors = (int)n;
+  return ICPGPU_OK;
+}
+
+int icpgpu_get_correspondence_rejectors(const icpgpu_ctx* c, icpgpu_rejector* out, size_t* n) {
+  if (!c || !n) return ICPGPU_ERR_INVALID_ARG;
+  *n = (size_t)c->n_rejectors;
+  if (out)
+    for (int s = 0; s < c->n_rejectors; ++s) out[s] = c->rejectors[s];
+  return ICPGPU_OK;
+}
+
+int icpgpu_correspondences(icpgpu_ctx* c, const float* T, int32_t* idx, float* d2) {
+  ENTER(c);
+  if (!c->src.set || !c->tgt.set) return fail(c, ICPGPU_ERR_NO_INPUT, "correspondences: source and target must be set first");
+  const int n_s = (int)c->src.n;
+  if (n_s && (!idx || !d2)) return fail(c, ICPGPU_ERR_INVALID_ARG, "null output");
+  int rc = ensure(c, c->keys, (size_t)(n_s ? n_s : 1) * sizeof(unsigned long long));
+  if (rc) return rc;
+  if ((rc = ensure(c, c->idx, (size_t)(n_s ? n_s : 1) * sizeof(int32_t)))) return rc;
+  if ((rc = ensure(c, c->d2, (size_t)(n_s ? n_s : 1) * sizeof(float)))) return rc;
+  const float thr = threshold_from(c->params.max_correspondence_distance * c->params.max_correspondence_distance);
+  auto* keys = static_cast<unsigned long long*>(c->keys.ptr);
+  c->prev.valid = false;  // (as an alignment's first iteration: nothing carried over)
+  if (c->tgt.n == 0) {
+    HIP_TRY(c, launch_fill_keys(keys, n_s, c->stream));
+  } else {
+    if ((rc = ensure_grid(c, thr))) return rc;
+    if ((rc = gated_keys(c, T ? to_xform(T) : to_xform(mat4_identity()), thr, keys))) return rc;
+  }
+  if ((rc = reject_run_chain(c, keys, thr))) return rc;
+  HIP_TRY(c, launch_reject_unpack(keys, n_s, thr, static_cast<int32_t*>(c->idx.ptr), static_cast<float*>(c->d2.ptr), c->stream));
+  if (n_s) {
+    HIP_TRY(c, hipMemcpyAsync(idx, c->idx.ptr, (size_t)n_s * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d2, c->d2.ptr, (size_t)n_s * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return reject_fetch_stats(c);
+}
+
+int icpgpu_rejector_stats(const icpgpu_ctx* c, size_t capacity, uint32_t* pairs_in, uint32_t* pairs_out, float* cut, size_t* n_stages) {
+  if (!c || !n_stages) return ICPGPU_ERR_INVALID_ARG;
+  *n_stages = c->rej_stats_n;
+  if (c->rej_stats_n > capacity) return ICPGPU_OK;
+  for (size_t s = 0; s < c->rej_stats_n; ++s) {
+    if (pairs_in) pairs_in[s] = c->rej_stats[s].pairs_in;
+    if (pairs_out) pairs_out[s] = c->rej_stats[s].pairs_out;
+    if (cut) std::memcpy(&cut[s], &c->rej_stats[s].cut_bits, sizeof(float));
+  }
+  return ICPGPU_OK;
+}
+
+}  // extern "C"

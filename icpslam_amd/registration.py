@@ -20,7 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import IcpGpuError, Params, Profile, Result
+from ._lib import IcpGpuError, Params, Profile, Rejector, Result
 
 
 def _as_cloud(a) -> np.ndarray:
@@ -204,6 +204,42 @@ class Context:
         res = (Result * n)()
         self._check(self._L.icpgpu_align_batch(self._h, n, sp, ns, tp, nt, int(want_fitness), res))
         return [result_dict(r, None) for r in res]
+
+    # correspondence rejectors (pcl::Registration::addCorrespondenceRejector) ------------------------------------------
+    def set_correspondence_rejectors(self, chain=()):
+        """The context's chain, in order: (kind, value[, min_correspondences]) tuples or _lib.Rejector structs; () clears it."""
+        items = []
+        for r in chain:
+            if not isinstance(r, Rejector):
+                r = tuple(r)
+                r = Rejector(int(r[0]), int(r[2]) if len(r) > 2 else 0, float(r[1]) if len(r) > 1 else 0.0)
+            items.append(r)
+        arr = (Rejector * max(1, len(items)))(*items)
+        self._check(self._L.icpgpu_set_correspondence_rejectors(self._h, arr, len(items)))
+
+    def get_correspondence_rejectors(self):
+        arr = (Rejector * _lib.MAX_REJECTORS)()
+        n = C.c_size_t(0)
+        self._check(self._L.icpgpu_get_correspondence_rejectors(self._h, arr, C.byref(n)))
+        return [(int(r.kind), float(r.value), int(r.min_correspondences)) for r in arr[:n.value]]
+
+    def correspondences(self, T=np.eye(4)):
+        """What one iteration at T hands to the solve: (idx, d2) per source point, idx = -1 where the gate or the chain removed the pair."""
+        idx = np.empty(self.n_source, np.int32)
+        d2 = np.empty(self.n_source, np.float32)
+        Tb = _colmajor16(T)
+        self._check(self._L.icpgpu_correspondences(self._h, _fp(Tb), idx.ctypes.data_as(C.POINTER(C.c_int32)), _fp(d2)))
+        return idx, d2
+
+    def rejector_stats(self):
+        """Per stage of the chain's last run: dict(pairs_in, pairs_out, cut) (cut: float32 d2)."""
+        cap = _lib.MAX_REJECTORS
+        a, b = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        cut = np.zeros(cap, np.float32)
+        n = C.c_size_t(0)
+        u32 = C.POINTER(C.c_uint32)
+        self._check(self._L.icpgpu_rejector_stats(self._h, cap, a.ctypes.data_as(u32), b.ctypes.data_as(u32), _fp(cut), C.byref(n)))
+        return [dict(pairs_in=int(a[s]), pairs_out=int(b[s]), cut=np.float32(cut[s])) for s in range(n.value)]
 
     # kernel-level entry points ------------------------------------------------------------------------------
     def nn(self, T=np.eye(4)):
@@ -468,6 +504,67 @@ def result_dict(res: Result, cloud):
                 t_device_ms=float(res.t_device_ms), gicp_solver=int(res.gicp_solver))
 
 
+class CorrespondenceRejector:
+    """pcl::registration::CorrespondenceRejector-shaped base of the three rejectors a registration object's chain may hold
+    (addCorrespondenceRejector).  The objects carry parameters only: the stages run on the device inside align()."""
+
+    KIND = 0
+
+    def getClassName(self) -> str:
+        return type(self).__name__
+
+    def _entry(self) -> Rejector:
+        return Rejector(self.KIND, 0, 0.0)
+
+
+class CorrespondenceRejectorMedianDistance(CorrespondenceRejector):
+    KIND = _lib.REJECT_MEDIAN_DISTANCE
+
+    def __init__(self):
+        self._factor = 1.0
+        self._median = 0.0
+
+    def setMedianFactor(self, factor):
+        self._factor = float(factor)
+
+    def getMedianFactor(self) -> float:
+        return self._factor
+
+    def getMedianDistance(self) -> float:
+        """The median squared distance of the last iteration of the last align() this rejector took part in."""
+        return self._median
+
+    def _entry(self) -> Rejector:
+        return Rejector(self.KIND, 0, self._factor)
+
+
+class CorrespondenceRejectorTrimmed(CorrespondenceRejector):
+    KIND = _lib.REJECT_TRIMMED
+
+    def __init__(self):
+        self._ratio = 0.5
+        self._min = 0
+
+    def setOverlapRatio(self, ratio):
+        self._ratio = float(np.float32(ratio))      # (PCL holds a float)
+
+    def getOverlapRatio(self) -> float:
+        return self._ratio
+
+    def setMinCorrespondences(self, n):
+        self._min = int(n)
+
+    def getMinCorrespondences(self) -> int:
+        return self._min
+
+    def _entry(self) -> Rejector:
+        return Rejector(self.KIND, self._min, self._ratio)
+
+
+class CorrespondenceRejectorOneToOne(CorrespondenceRejector):
+    KIND = _lib.REJECT_ONE_TO_ONE
+
+
 class IterativeClosestPoint:
     """pcl::IterativeClosestPoint<PointXYZ, PointXYZ>-shaped front end (same method names as the reference uses):
     point-to-point ICP, the solver BASELINE.json's north_star specifies.  The class the reference literally instantiates
@@ -491,6 +588,7 @@ class IterativeClosestPoint:
         self._target = None
         self._result = None
         self._fitness = None
+        self._rejectors = []
 
     # setters used by the reference -----------------------------------------------------------------------------
     def setMaximumIterations(self, n):           # icp_odometer.cpp:189 (passes a double constant)
@@ -509,6 +607,32 @@ class IterativeClosestPoint:
     def setEuclideanFitnessEpsilon(self, eps):
         self._params.euclidean_fitness_epsilon = float(eps)
 
+    # pcl::Registration's rejector chain (the library ignores it for GICP and NDT, as PCL's classes do)
+    def addCorrespondenceRejector(self, rejector):
+        if len(self._rejectors) >= _lib.MAX_REJECTORS:
+            raise IcpGpuError(_lib.ERR_INVALID_ARG, f"at most {_lib.MAX_REJECTORS} correspondence rejectors")
+        self._rejectors.append(rejector)
+
+    def getCorrespondenceRejectors(self):
+        return list(self._rejectors)
+
+    def removeCorrespondenceRejector(self, i) -> bool:
+        if i >= len(self._rejectors):
+            return False
+        del self._rejectors[i]
+        return True
+
+    def clearCorrespondenceRejectors(self):
+        self._rejectors = []
+
+    def _set_chain(self):
+        self._ctx.set_correspondence_rejectors([r._entry() for r in self._rejectors])
+
+    def _take_rejector_stats(self):
+        for r, s in zip(self._rejectors, self._ctx.rejector_stats()):
+            if isinstance(r, CorrespondenceRejectorMedianDistance):
+                r._median = float(s["cut"])
+
     def setInputSource(self, cloud):             # icp_odometer.cpp:193
         self._source = _as_cloud(cloud)
 
@@ -522,7 +646,9 @@ class IterativeClosestPoint:
         self._ctx.set_params(self._params)
         self._ctx.set_source(self._source)
         self._ctx.set_target(self._target)
+        self._set_chain()
         self._result = self._ctx.align(guess=guess, want_cloud=True)
+        self._take_rejector_stats()
         self._ctx._last_user = self          # objects of one device share the cached context (see getFitnessScore)
         return self._result["cloud"]
 
@@ -646,7 +772,9 @@ class IterativeClosestPointWithNormals(IterativeClosestPoint):
         if self._source is None or self._target is None:
             raise IcpGpuError(_lib.ERR_NO_INPUT, "align: setInputSource/setInputTarget first")
         self._upload()
+        self._set_chain()
         self._result = self._ctx.align(guess=guess, want_cloud=True)
+        self._take_rejector_stats()
         self._ctx._last_user = self
         return self._result["cloud"]
 

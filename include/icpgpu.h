@@ -50,7 +50,9 @@ extern "C" {
  * overrunning its structs.  History: 1.2 ICPGPU_P2PLANE, icpgpu_set_target_normals, icpgpu_normals, icpgpu_reduce_point_to_plane,
  * icpgpu_solve_point_to_plane; added under 1.2: ICPGPU_NDT, icpgpu_set_ndt_params, icpgpu_get_ndt_params,
  * icpgpu_ndt_transformation_probability, icpgpu_ndt_cells, icpgpu_ndt_derivatives, icpgpu_ndt_step, icpgpu_set_ndt_line_search,
- * icpgpu_get_ndt_line_search, icpgpu_ndt_gradient, icpgpu_ndt_line_search_replay, icpgpu_ndt_line_search_trace (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
+ * icpgpu_get_ndt_line_search, icpgpu_ndt_gradient, icpgpu_ndt_line_search_replay, icpgpu_ndt_line_search_trace (no struct changed); also added under
+ * 1.2: the correspondence rejectors -- icpgpu_rejector, icpgpu_set_correspondence_rejectors, icpgpu_get_correspondence_rejectors,
+ * icpgpu_correspondences, icpgpu_rejector_stats (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
  * icpgpu_profile.gicp_quadratic_solves; 0.3 icpgpu_profile (sources_adopted, gicp_host_solves, gicp_solver_choice). */
 
@@ -376,6 +378,50 @@ int icpgpu_reduce_point_to_plane(icpgpu_ctx* ctx, const float* T, double max_dis
  * Tk = constructTransformationMatrix(x0..x5) = [Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)] column-major with correctly rounded sin / cos.
  * A zero pivot or a non-finite x: ICPGPU_ERR_INVALID_ARG and Tk = identity (the singular-system rule above). */
 int icpgpu_solve_point_to_plane(const double sums[29], double Tk[16]);
+
+/* ---- correspondence rejectors (added under 1.2) ------------------------------------------------------------------- */
+/* replaces pcl::Registration::addCorrespondenceRejector with pcl::registration::CorrespondenceRejectorMedianDistance, ...Trimmed and
+ * ...OneToOne (PCL 1.8).  A context holds an ordered chain of at most ICPGPU_MAX_REJECTORS rejectors, empty by default.  In every
+ * iteration of ICPGPU_P2P_SVD and ICPGPU_P2PLANE the chain runs on the correspondences that passed the distance gate
+ * ((double)d2 <= max_correspondence_distance^2), in the order given, each stage on what the one before it left; the solve,
+ * n_correspondences, mse_last, the convergence criteria and the min_correspondences test see what remains.  getFitnessScore
+ * (icpgpu_fitness, want_fitness) is untouched, as in PCL.  A correspondence's distance is the float32 squared distance of the search.
+ *   MEDIAN_DISTANCE  value = the median factor (finite, >= 0; PCL's default 1.0).  With the n surviving d2 sorted ascending,
+ *                    median = sorted[n / 2] (PCL's nth_element at size() / 2); a pair stays iff (double)d2 <= (double)median * factor.
+ *   TRIMMED          value = the overlap ratio in [0, 1] (PCL's default 0.5), min_correspondences >= 0 (PCL's default 0):
+ *                    m = min(n, max(min_correspondences, (unsigned)(ratio * (float)n))), ratio and product in float32; a pair stays
+ *                    iff d2 <= the m-th smallest d2; m = 0 keeps nothing.  DEVIATION: pairs that tie with the m-th smallest ALL stay,
+ *                    so more than m can remain; PCL keeps exactly m, and which of the tied ones is whatever std::nth_element leaves
+ *                    (unspecified).  The sets are equal whenever the m-th and (m + 1)-th distances differ.
+ *   ONE_TO_ONE       of the surviving pairs that share a target index the one with the smallest d2 stays.  DEVIATION: among equal
+ *                    d2 the lowest source index (the caller's order) stays; PCL's std::sort leaves that unspecified.
+ * With no surviving pair (n = 0) every rejector keeps nothing.  ICPGPU_GICP and ICPGPU_NDT ignore the chain, as PCL's
+ * GeneralizedIterativeClosestPoint::computeTransformation and NormalDistributionsTransform never read correspondence_rejectors_.
+ * icpgpu_align_batch with a non-empty chain returns ICPGPU_ERR_UNSUPPORTED for every method (the lock-step kernels fuse the
+ * reduction); icpgpu_align_batch_multi runs on contexts of the library's own, which never carry a chain.  With an empty chain an
+ * alignment launches exactly the kernels it launched before rejectors existed.  Not provided: setUseReciprocalCorrespondences, the
+ * surface-normal, var-trimmed, sample-consensus and feature rejectors. */
+typedef enum { ICPGPU_REJECT_MEDIAN_DISTANCE = 1, ICPGPU_REJECT_TRIMMED = 2, ICPGPU_REJECT_ONE_TO_ONE = 3 } icpgpu_rejector_kind;
+#define ICPGPU_MAX_REJECTORS 4
+typedef struct {
+  int32_t kind;                /* icpgpu_rejector_kind */
+  int32_t min_correspondences; /* TRIMMED only */
+  double value;                /* MEDIAN_DISTANCE: factor; TRIMMED: overlap ratio; ONE_TO_ONE: unused */
+} icpgpu_rejector;
+/* the whole chain at once; n = 0 clears it.  A bad kind or value, n > ICPGPU_MAX_REJECTORS or a null context:
+ * ICPGPU_ERR_INVALID_ARG, and the chain in force stays. */
+int icpgpu_set_correspondence_rejectors(icpgpu_ctx* ctx, const icpgpu_rejector* rejectors, size_t n);
+/* *n = the chain's length; out (nullable) must hold ICPGPU_MAX_REJECTORS entries */
+int icpgpu_get_correspondence_rejectors(const icpgpu_ctx* ctx, icpgpu_rejector* out, size_t* n);
+/* the chain's counterpart of icpgpu_nn: what one iteration at transform T (NULL = identity) hands to the solve, per source point in
+ * the caller's order -- idx[i] = the target index and d2[i] its squared distance, or idx = -1, d2 = +inf for a pair the gate or the
+ * chain removed.  Same kernels as an alignment's iterations; any method's context. */
+int icpgpu_correspondences(icpgpu_ctx* ctx, const float* T, int32_t* idx, float* d2);
+/* per stage of the chain, for the last iteration of the context's last P2P_SVD / P2PLANE alignment or its last
+ * icpgpu_correspondences call, whichever came later: the pairs that entered the stage, the pairs it kept, and its cut as a float d2
+ * (MEDIAN_DISTANCE: the median, getMedianDistance(); TRIMMED: the m-th smallest d2; 0 where there is none: ONE_TO_ONE, no pair in,
+ * m = 0).  *n_stages = their number; nothing is copied when it exceeds capacity.  Any output array may be NULL. */
+int icpgpu_rejector_stats(const icpgpu_ctx* ctx, size_t capacity, uint32_t* pairs_in, uint32_t* pairs_out, float* cut, size_t* n_stages);
 
 /* ---- NDT mode (ICPGPU_NDT, added under 1.2) --------------------------------------------------------------------- */
 /* setResolution / setStepSize / setOulierRatio.  resolution > 0, step_size > 0, 0 < outlier_ratio < 1, else ICPGPU_ERR_INVALID_ARG.

@@ -20,6 +20,7 @@
 // is at construction when no gfx950 device / libicpgpu is usable (there is no CPU fallback to hide that).
 #pragma once
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstddef>
@@ -194,9 +195,71 @@ inline void release_cached_contexts() {
   }
 }
 
+// --- pcl::registration::CorrespondenceRejector and the three rejectors a registration object's chain may hold (PCL 1.8's names;
+// include/icpgpu.h, "correspondence rejectors", states the rules and the two deviations).  The objects carry parameters: the
+// stages run on the device inside align(), which also leaves the last iteration's median in the median rejector.
+namespace registration {
+class CorrespondenceRejector {
+ public:
+  typedef std::shared_ptr<CorrespondenceRejector> Ptr;
+  typedef std::shared_ptr<const CorrespondenceRejector> ConstPtr;
+  virtual ~CorrespondenceRejector() {}
+  const std::string& getClassName() const { return rejection_name_; }
+  virtual icpgpu_rejector entry() const = 0;            // (no PCL counterpart: what the C-ABI takes)
+  virtual void takeCut(float /*d2*/) {}
+
+ protected:
+  std::string rejection_name_;
+};
+class CorrespondenceRejectorMedianDistance : public CorrespondenceRejector {
+ public:
+  typedef std::shared_ptr<CorrespondenceRejectorMedianDistance> Ptr;
+  CorrespondenceRejectorMedianDistance() : median_distance_(0), factor_(1.0) { rejection_name_ = "CorrespondenceRejectorMedianDistance"; }
+  void setMedianFactor(double factor) { factor_ = factor; }
+  double getMedianFactor() const { return factor_; }
+  double getMedianDistance() const { return median_distance_; }
+  icpgpu_rejector entry() const override { return icpgpu_rejector{ICPGPU_REJECT_MEDIAN_DISTANCE, 0, factor_}; }
+  void takeCut(float d2) override { median_distance_ = d2; }
+
+ private:
+  double median_distance_, factor_;
+};
+class CorrespondenceRejectorTrimmed : public CorrespondenceRejector {
+ public:
+  typedef std::shared_ptr<CorrespondenceRejectorTrimmed> Ptr;
+  CorrespondenceRejectorTrimmed() : overlap_ratio_(0.5f), nr_min_correspondences_(0) { rejection_name_ = "CorrespondenceRejectorTrimmed"; }
+  void setOverlapRatio(float ratio) { overlap_ratio_ = std::min(1.0f, std::max(0.0f, ratio)); }
+  float getOverlapRatio() const { return overlap_ratio_; }
+  void setMinCorrespondences(unsigned int min_correspondences) { nr_min_correspondences_ = min_correspondences; }
+  unsigned int getMinCorrespondences() const { return nr_min_correspondences_; }
+  icpgpu_rejector entry() const override { return icpgpu_rejector{ICPGPU_REJECT_TRIMMED, (int32_t)nr_min_correspondences_, (double)overlap_ratio_}; }
+
+ private:
+  float overlap_ratio_;
+  unsigned int nr_min_correspondences_;
+};
+class CorrespondenceRejectorOneToOne : public CorrespondenceRejector {
+ public:
+  typedef std::shared_ptr<CorrespondenceRejectorOneToOne> Ptr;
+  CorrespondenceRejectorOneToOne() { rejection_name_ = "CorrespondenceRejectorOneToOne"; }
+  icpgpu_rejector entry() const override { return icpgpu_rejector{ICPGPU_REJECT_ONE_TO_ONE, 0, 0.0}; }
+};
+}  // namespace registration
+
 template <class CloudT>
 class IterativeClosestPoint {
  public:
+  typedef registration::CorrespondenceRejector::Ptr CorrespondenceRejectorPtr;
+  // pcl::Registration's rejector chain (at most ICPGPU_MAX_REJECTORS; GICP and NDT ignore it, as PCL's classes do)
+  void addCorrespondenceRejector(const CorrespondenceRejectorPtr& rejector) { correspondence_rejectors_.push_back(rejector); }
+  std::vector<CorrespondenceRejectorPtr> getCorrespondenceRejectors() { return correspondence_rejectors_; }
+  bool removeCorrespondenceRejector(unsigned int i) {
+    if (i >= correspondence_rejectors_.size()) return false;
+    correspondence_rejectors_.erase(correspondence_rejectors_.begin() + i);
+    return true;
+  }
+  void clearCorrespondenceRejectors() { correspondence_rejectors_.clear(); }
+
   explicit IterativeClosestPoint(int device = 0, icpgpu_method method = ICPGPU_P2P_SVD)
       : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {
     icpgpu_default_params(&params_);
@@ -268,6 +331,19 @@ class IterativeClosestPoint {
   using PointT = typename std::remove_reference<decltype(std::declval<CloudT>().points[0])>::type;
   static_assert(sizeof(PointT) == 16, "point type must be the 16-byte pcl::PointXYZ layout");
 
+  std::vector<CorrespondenceRejectorPtr> correspondence_rejectors_;
+  bool apply_rejectors() {  // (always: an object without rejectors clears what another one left on a shared context)
+    std::vector<icpgpu_rejector> chain;
+    for (const auto& r : correspondence_rejectors_) chain.push_back(r->entry());
+    return icpgpu_set_correspondence_rejectors(ctx_, chain.empty() ? nullptr : chain.data(), chain.size()) == ICPGPU_OK;
+  }
+  void take_rejector_stats() {
+    float cut[ICPGPU_MAX_REJECTORS] = {0, 0, 0, 0};
+    std::size_t n = 0;
+    if (correspondence_rejectors_.empty() || icpgpu_rejector_stats(ctx_, ICPGPU_MAX_REJECTORS, nullptr, nullptr, cut, &n) != ICPGPU_OK) return;
+    for (std::size_t s = 0; s < n && s < correspondence_rejectors_.size(); ++s) correspondence_rejectors_[s]->takeCut(cut[s]);
+  }
+
   bool apply_ndt() {
     return icpgpu_set_ndt_params(ctx_, ndt_[0], ndt_[1], ndt_[2]) == ICPGPU_OK &&
            icpgpu_set_ndt_line_search(ctx_, ndt_line_search_) == ICPGPU_OK;
@@ -296,6 +372,7 @@ class IterativeClosestPoint {
                (params_.method == ICPGPU_NDT && !apply_ndt())) {
       return false;
     }
+    if (!apply_rejectors()) return false;
     const std::size_t ns = source_->points.size();
     return icpgpu_set_source(ctx_, ns ? reinterpret_cast<const float*>(&source_->points[0]) : nullptr, ns) == ICPGPU_OK;
   }
@@ -337,6 +414,7 @@ class IterativeClosestPoint {
     output.points.assign(first, first + nv);
     detail::set_cloud_shape(output, ns, 0);
     aligned_ = true;
+    take_rejector_stats();
     ICPGPU_SHIM_MARK(3);
   }
 
