@@ -408,10 +408,10 @@ void init_result(icpgpu_result* r) {
 
 int p2p_finish(icpgpu_ctx* c, P2PRun& r) {
   const Xform Tf = to_xform(r.final_T);
-  if (c->n_rejectors > 0) {  // the chain's statistics of the last iteration (icpgpu_rejector_stats)
-    const int rc_stats = reject_fetch_stats(c);
-    if (rc_stats) return rc_stats;
-  }
+  // the chain's statistics of the last iteration (icpgpu_rejector_stats); without a chain: no stage, and no device traffic -- an
+  // earlier alignment's stages must not outlive this one
+  const int rc_stats = reject_fetch_stats(c);
+  if (rc_stats) return rc_stats;
   // (the aligned cloud was queued in front of the fitness sweep when there was one: p2p_advance)
   int rc = r.out_done ? ICPGPU_OK
                       : (r.out_ticket.issued ? output_cloud_complete(c, r.out_ticket, r.out_xyzw) : write_output_cloud(c, Tf, r.out_xyzw));

@@ -185,7 +185,7 @@ int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_f
       }
     }
   }
-  if (c->n_rejectors > 0 && (rc = reject_fetch_stats(c))) return rc;  // the chain's statistics of the last iteration
+  if ((rc = reject_fetch_stats(c))) return rc;  // the chain's statistics of the last iteration (none, and nothing fetched, without a chain)
   c->final_T = final_T;
   c->have_final = true;
   mat4_to_float(final_T, res->T);
