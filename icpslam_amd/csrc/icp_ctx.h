@@ -67,6 +67,10 @@ struct Cloud {
   mutable uint64_t bbox_version = 0;
   mutable int bbox_enc[6] = {0, 0, 0, 0, 0, 0};
   mutable bool bbox_exact = false;  // from a bounding-box pass over these very points (no containment check needed)
+  // how many of the points are finite, valid while the owner's version counter equals finite_version (0 = not counted): a grid
+  // build's count pass finds it out (GICP's "fewer than 20 finite points is too small", icpgpu_gicp.cpp)
+  mutable uint64_t finite_version = 0;
+  mutable int n_finite = 0;
   const float4* data() const { return static_cast<const float4*>(buf.ptr); }
 };
 
@@ -79,6 +83,7 @@ struct GridIndex {
   bool adopted = false;      // c->grid only: this is the grid the target's GICP covariances were computed over (ensure_grid)
   GridDesc g{};
   int n_binned = 0, max_pop = 0;
+  int n_finite = -1;         // the cloud's finite points as this build counted them (-1: it ended before it knew)
   double point_population = 0.0;  // cell population seen by a random point (sum c^2 / sum c)
   DeviceBuf sorted, cell_start, cell_of_point, rank, block_sums, ints, unmatched, leftover;
   uint64_t serial = 0;       // unique per completed build (grids change hands between c->grid and c->src_grid)
@@ -584,8 +589,10 @@ int align_p2p(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitne
 int voxel_filter_device(icpgpu_ctx* c, const float4* d_in, int n, float leaf, DeviceBuf& out, int* n_out, bool* passthrough,
                         int* bbox_enc_out = nullptr, bool publish = false, bool* published = nullptr, unsigned long long* fp_sum = nullptr);
 // icpgpu_gicp.cpp (normals: the point-to-plane mode's normals of the cloud instead of its covariances -- cov is then scratch)
+// the finite points of a cloud where a grid build has counted them, -1 otherwise
+inline int cloud_finite_known(const Cloud& cl, uint64_t version) { return (version != 0 && cl.finite_version == version) ? cl.n_finite : -1; }
 int ensure_covariances(icpgpu_ctx* c, const Cloud& cloud, uint64_t version, GridIndex& G, DeviceBuf& cov, uint64_t& cov_version, bool allow_unchecked = false,
-                       float4* normals = nullptr);
+                       float4* normals = nullptr, bool* too_small = nullptr);
 int covariance_grid_check(icpgpu_ctx* c);
 int align_gicp(icpgpu_ctx* c, const float* guess_in, float* out_xyzw, int want_fitness, icpgpu_result* res);
 int gicp_run_begin(icpgpu_ctx* c, GicpRun& r, int want_fitness, icpgpu_result* res, bool combine = false);

@@ -941,6 +941,8 @@ int promote_internal(icpgpu_ctx* c) {
   else c->cov_grid_tgt.built = c->cov_grid_tgt.usable = false;
   c->cov_grid_src.built = c->cov_grid_src.usable = false;          // the old target's: never to be mistaken for a new source's
   c->tgt.bbox_version = box_follows ? c->tgt_version : 0;          // the box travels with the cloud, re-stamped for its new counter
+  c->tgt.finite_version = (c->tgt.finite_version != 0 && c->tgt.finite_version == c->src_version) ? c->tgt_version : 0;  // ... and so does its count
+  c->src.finite_version = 0;
   c->src.bbox_version = 0;
   c->cov_src_version = 0;
   c->src_version++;

@@ -92,20 +92,48 @@ static int cov_launch(icpgpu_ctx* c, const Cloud& cloud, uint64_t version, GridI
   return ICPGPU_OK;
 }
 
+// "Fewer than k_correspondences_ FINITE points is a cloud that is too small" (include/icpgpu.h; PCL has no usable behaviour there: its
+// kd-tree holds the finite points only and nearestKSearch(20) comes back short).  The count is the grid build's: its count pass bins
+// every finite point and reports how many there were, before any covariance kernel is queued -- no pass and no round trip of its
+// own.  Only a build that ended before it knew (a box or cell size that is not finite: coordinates near FLT_MAX) has the points
+// counted on the host, with a copy and a stream synchronisation, also inside a resumable run -- a corner no test reaches.
+// 1: too small, 0: large enough, < 0: error.
+static int cov_cloud_too_small(icpgpu_ctx* c, const Cloud& cloud, const GridIndex& G) {
+  int nf = G.n_finite;
+  if (nf < 0) {
+    std::vector<float> h(cloud.n * 4);
+    HIP_TRY(c, hipMemcpyAsync(h.data(), cloud.buf.ptr, cloud.n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    nf = 0;
+    for (size_t i = 0; i < cloud.n; ++i) nf += std::isfinite(h[4 * i]) && std::isfinite(h[4 * i + 1]) && std::isfinite(h[4 * i + 2]);
+  }
+  return nf < kGicpK ? 1 : 0;
+}
+static bool cov_cloud_known_too_small(const Cloud& cloud, uint64_t version) {
+  const int nf = cloud_finite_known(cloud, version);
+  return cloud.n < (size_t)kGicpK || (nf >= 0 && nf < kGicpK);
+}
+
+// too_small (GICP's callers; null: P2PLANE's normals, which have their own rule): set when the cloud has fewer than kGicpK finite
+// points -- nothing is launched over such a cloud, the caller finishes early or reports the argument.
 // allow_unchecked (align_gicp, the source cloud): when the cloud brings a containing box (the voxel filter's) and the context a proven
 // cell size (the last covariance grid's), the build does not wait for the count pass's statistics -- count, scan, scatter and the
 // covariance pass are queued in one go, the statistics are posted behind the count pass and checked by covariance_grid_check() when
 // the alignment first waits for the device anyway.  (Per scan of the reference's pipeline this was the one remaining host round trip
 // of the index build: ~110 us of host wall in front of a 96 us kernel)
 int ensure_covariances(icpgpu_ctx* c, const Cloud& cloud, uint64_t version, GridIndex& G, DeviceBuf& cov, uint64_t& cov_version, bool allow_unchecked,
-                       float4* normals) {
+                       float4* normals, bool* too_small) {
+  if (too_small && (*too_small = cov_cloud_known_too_small(cloud, version))) return ICPGPU_OK;
   GridBuild b;
   b.post = true;  // (the read-backs go through fetch_ints, as in build_grid)
   bool needed = false;
   int rc = cov_grid_begin(c, cloud, version, G, cov, cov_version, b, needed);
   if (rc || !needed) return rc;
   static const bool unchecked_enabled = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_COV_GRID_UNCHECKED"); return !e || std::atoi(e) != 0; }();
-  if (allow_unchecked && !normals && unchecked_enabled && b.state == GridBuild::WaitCount && b.h_start > 0.0 && !c->spec_grid.pending) {
+  // (a box from a pass over these very points comes with their count, and that count has passed the test above; a box the voxel
+  //  filter handed over belongs to means of finite points)
+  const bool count_open = cloud.bbox_exact && cloud_finite_known(cloud, version) < 0;
+  if (allow_unchecked && !normals && unchecked_enabled && b.state == GridBuild::WaitCount && b.h_start > 0.0 && !c->spec_grid.pending && !count_open) {
     if (c->spec_cooldown > 0) {
       c->spec_cooldown -= 1;
     } else {
@@ -131,6 +159,10 @@ int ensure_covariances(icpgpu_ctx* c, const Cloud& cloud, uint64_t version, Grid
     if (!rc) rc = gb_advance(c, b);
   }
   if (rc) return rc;
+  if (too_small) {
+    if ((rc = cov_cloud_too_small(c, cloud, G)) < 0) return rc;
+    if ((*too_small = rc == 1)) return ICPGPU_OK;
+  }
   return cov_launch(c, cloud, version, G, cov, cov_version, /*timed=*/true, normals);
 }
 
@@ -459,8 +491,12 @@ static void gicp_stamp_total(const GicpState& s) {
   s.res->t_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - s.t_start).count();
 }
 
-// empty target / clouds smaller than k_correspondences_: PCL leaves converged_ = false, T = I
-static bool gicp_too_small(const icpgpu_ctx* c) { return c->tgt.n == 0 || c->src.n < (size_t)kGicpK || c->tgt.n < (size_t)kGicpK; }
+// empty target / clouds of fewer than k_correspondences_ finite points: PCL leaves converged_ = false, T = I.  Here: what is known
+// before any work (the sizes, a count an earlier grid build left with the cloud); a count that is still open is settled by the
+// covariance grid's count pass (ensure_covariances, gicp_run_next_cov), with the same end.
+static bool gicp_too_small(const icpgpu_ctx* c) {
+  return c->tgt.n == 0 || cov_cloud_known_too_small(c->src, c->src_version) || cov_cloud_known_too_small(c->tgt, c->tgt_version);
+}
 static void gicp_finish_early(icpgpu_ctx* c) {
   c->final_T = mat4_identity();
   c->have_final = true;
@@ -847,14 +883,16 @@ static int gicp_prepare(icpgpu_ctx* c, GicpAlign& a, const float* guess_in, floa
   gicp_state_begin(c, s, guess_in);
   a.base = xform_from_f16(s.guess);
   int rc;
-  if (gicp_too_small(c)) {
+  bool small = gicp_too_small(c);
+  if (!small && (rc = ensure_covariances(c, c->tgt, c->tgt_version, c->cov_grid_tgt, c->cov_tgt, c->cov_tgt_version, false, nullptr, &small))) return rc;
+  if (!small && (rc = ensure_covariances(c, c->src, c->src_version, c->cov_grid_src, c->cov_src, c->cov_src_version, /*allow_unchecked=*/true, nullptr, &small)))
+    return rc;
+  if (small) {
     gicp_finish_early(c);
     rc = write_output_cloud(c, to_xform(c->final_T), out_xyzw);
     gicp_stamp_total(s);
     return rc ? rc : 1;
   }
-  if ((rc = ensure_covariances(c, c->tgt, c->tgt_version, c->cov_grid_tgt, c->cov_tgt, c->cov_tgt_version))) return rc;
-  if ((rc = ensure_covariances(c, c->src, c->src_version, c->cov_grid_src, c->cov_src, c->cov_src_version, /*allow_unchecked=*/true))) return rc;
   gicp_mark(c, a, 0);
   if ((rc = gicp_ensure_scratch(c, s))) return rc;
   gicp_mark(c, a, 1);
@@ -1046,6 +1084,13 @@ void gicp_run_solver_launched(icpgpu_ctx*, GicpRun& r, hipStream_t solve_stream)
   gicp_run_await(r, GicpRun::Solve);
 }
 
+// a cloud of fewer than k_correspondences_ finite points: the run ends as align_gicp ends (gicp_prepare)
+static void gicp_run_end_too_small(icpgpu_ctx* c, GicpRun& r) {
+  gicp_finish_early(c);
+  gicp_stamp_total(r);
+  r.phase = GicpRun::Done;
+}
+
 // the next covariance grid that needs building (target first, then source), or on to the outer iterations
 static int gicp_run_next_cov(icpgpu_ctx* c, GicpRun& r) {
   int rc;
@@ -1058,6 +1103,10 @@ static int gicp_run_next_cov(icpgpu_ctx* c, GicpRun& r) {
     const uint64_t version = tgt ? c->tgt_version : c->src_version;
     bool needed = false;
     r.gb = GridBuild{};
+    if (cov_cloud_known_too_small(cloud, version)) {
+      gicp_run_end_too_small(c, r);
+      return ICPGPU_OK;
+    }
     if ((rc = cov_grid_begin(c, cloud, version, G, cov, cov_version, r.gb, needed))) return rc;
     if (needed && r.gb.state != GridBuild::Done) {  // a read-back is queued: poll the marker behind it
       r.marker = run_post_marker(c, static_cast<const int*>(G.ints.ptr), &rc);
@@ -1065,7 +1114,14 @@ static int gicp_run_next_cov(icpgpu_ctx* c, GicpRun& r) {
       gicp_run_await(r, GicpRun::CovGrid);
       return ICPGPU_OK;
     }
-    if (needed && (rc = cov_launch(c, cloud, version, G, cov, cov_version, /*timed=*/false))) return rc;
+    if (needed) {
+      if ((rc = cov_cloud_too_small(c, cloud, G)) < 0) return rc;
+      if (rc == 1) {
+        gicp_run_end_too_small(c, r);
+        return ICPGPU_OK;
+      }
+      if ((rc = cov_launch(c, cloud, version, G, cov, cov_version, /*timed=*/false))) return rc;
+    }
     r.cov_stage += 1;
   }
   if ((rc = gicp_ensure_scratch(c, r))) return rc;
@@ -1179,6 +1235,11 @@ int gicp_run_step(icpgpu_ctx* c, GicpRun& r) {
         return 1;
       }
       const Cloud& cloud = tgt ? c->tgt : c->src;
+      if ((rc = cov_cloud_too_small(c, cloud, G)) < 0) return rc;
+      if (rc == 1) {
+        gicp_run_end_too_small(c, r);
+        return 1;
+      }
       if ((rc = cov_launch(c, cloud, tgt ? c->tgt_version : c->src_version, G, tgt ? c->cov_tgt : c->cov_src,
                            tgt ? c->cov_tgt_version : c->cov_src_version, /*timed=*/false)))
         return rc;
@@ -1255,9 +1316,11 @@ int icpgpu_gicp_covariances(icpgpu_ctx* c, int of_target, double* out6) {
   if (!cl.set) return fail(c, ICPGPU_ERR_NO_INPUT, "gicp_covariances: cloud not set");
   if (cl.n && !out6) return fail(c, ICPGPU_ERR_INVALID_ARG, "null output");
   if (cl.n < (size_t)kGicpK) return fail(c, ICPGPU_ERR_INVALID_ARG, "GICP needs at least %d points per cloud", kGicpK);
-  int rc = of_target ? ensure_covariances(c, c->tgt, c->tgt_version, c->cov_grid_tgt, c->cov_tgt, c->cov_tgt_version)
-                     : ensure_covariances(c, c->src, c->src_version, c->cov_grid_src, c->cov_src, c->cov_src_version);
+  bool small = false;
+  int rc = of_target ? ensure_covariances(c, c->tgt, c->tgt_version, c->cov_grid_tgt, c->cov_tgt, c->cov_tgt_version, false, nullptr, &small)
+                     : ensure_covariances(c, c->src, c->src_version, c->cov_grid_src, c->cov_src, c->cov_src_version, false, nullptr, &small);
   if (rc) return rc;
+  if (small) return fail(c, ICPGPU_ERR_INVALID_ARG, "GICP needs at least %d finite points per cloud", kGicpK);
   const DeviceBuf& cov = of_target ? c->cov_tgt : c->cov_src;
   HIP_TRY(c, hipMemcpyAsync(out6, cov.ptr, cl.n * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1272,8 +1335,10 @@ int icpgpu_gicp_quadratic_sums(icpgpu_ctx* c, const float* T, double* sums150) {
   if (n_s < kGicpK || n_t < kGicpK) return fail(c, ICPGPU_ERR_INVALID_ARG, "GICP needs at least %d points per cloud", kGicpK);
   int rc;
   if ((rc = ensure_gicp_resources(c)) || (rc = ensure_gicp_quadratic_resources(c))) return rc;
-  if ((rc = ensure_covariances(c, c->tgt, c->tgt_version, c->cov_grid_tgt, c->cov_tgt, c->cov_tgt_version))) return rc;
-  if ((rc = ensure_covariances(c, c->src, c->src_version, c->cov_grid_src, c->cov_src, c->cov_src_version))) return rc;
+  bool small = false;
+  if ((rc = ensure_covariances(c, c->tgt, c->tgt_version, c->cov_grid_tgt, c->cov_tgt, c->cov_tgt_version, false, nullptr, &small))) return rc;
+  if (!small && (rc = ensure_covariances(c, c->src, c->src_version, c->cov_grid_src, c->cov_src, c->cov_src_version, false, nullptr, &small))) return rc;
+  if (small) return fail(c, ICPGPU_ERR_INVALID_ARG, "GICP needs at least %d finite points per cloud", kGicpK);
   const double r2 = c->params.max_correspondence_distance * c->params.max_correspondence_distance;
   float thr = threshold_from(r2);
   if ((double)thr >= r2) thr = std::nextafterf(thr, -INFINITY);

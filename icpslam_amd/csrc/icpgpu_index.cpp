@@ -51,6 +51,7 @@ int gb_begin(icpgpu_ctx* c, GridBuild& b, const Cloud& cloud, uint64_t version, 
   G.version = version;
   G.cutoff = cutoff;
   G.cut_d = cut;
+  G.n_finite = -1;
   int rc = ensure(c, G.ints, (6 + kGridStatInts) * sizeof(int));
   if (rc) return rc;
   int* d_ints = static_cast<int*>(G.ints.ptr);
@@ -68,6 +69,7 @@ int gb_on_bbox(icpgpu_ctx* c, GridBuild& b) {
     std::memcpy(b.cloud->bbox_enc, c->h_ints, sizeof(b.cloud->bbox_enc));
     b.cloud->bbox_version = b.version;
     b.cloud->bbox_exact = true;
+    b.cloud->finite_version = 0;  // (until this build's count pass has reported: gb_on_count)
   }
   return gb_with_bbox(c, b, c->h_ints, false);
 }
@@ -84,6 +86,7 @@ static int gb_with_bbox(icpgpu_ctx* c, GridBuild& b, const int enc[6], bool cach
       }
     }
   if (!(b.lo[0] <= b.hi[0] && b.lo[1] <= b.hi[1] && b.lo[2] <= b.hi[2])) {  // no finite point
+    if (!cached) b.G->n_finite = 0;  // (the box of a pass over these very points)
     b.state = GridBuild::Done;
     return ICPGPU_OK;
   }
@@ -220,6 +223,12 @@ int gb_on_count(icpgpu_ctx* c, GridBuild& b) {
     return gb_issue_count(c, b);
   }
   G.n_binned = binned;
+  // every finite point is binned by now: an exact box contains them all, a box that was handed over has passed binned == n above
+  G.n_finite = binned;
+  if (b.version != 0) {
+    b.cloud->n_finite = binned;
+    b.cloud->finite_version = b.version;
+  }
   G.max_pop = c->h_ints[7];
   G.point_population = pop;
   if (std::getenv("ICPGPU_DEBUG")) fprintf(stderr, "[icpgpu] grid n=%d binned=%d h=%.4f dims=%dx%dx%d pop=%.1f max=%d attempt=%d\n", n_t, binned, h, b.g.nx, b.g.ny, b.g.nz, pop, G.max_pop, attempt);
@@ -252,6 +261,7 @@ int gb_finish_unchecked(icpgpu_ctx* c, GridBuild& b) {
   const int n_t = (int)b.cloud->n;
   int* d_ints = static_cast<int*>(G.ints.ptr);
   G.n_binned = n_t;
+  G.n_finite = n_t;  // (assumed with the rest; covariance_grid_check drops the grid when the count says otherwise)
   G.max_pop = 0;
   G.point_population = b.knn_population > 0.0 ? b.knn_population : kTargetCellPopulation;
   int rc;

@@ -224,7 +224,7 @@ int icpgpu_voxel_grid(icpgpu_ctx* c, const float* xyzw, size_t n, float leaf, fl
   int box[6];
   if ((rc = voxel_filter_device(c, static_cast<const float4*>(c->vox_in.ptr), (int)n, leaf, c->vox_out, &m, &pass, box))) return rc;
   c->vox_last_n = (size_t)m;  // out_xyzw == NULL: the filtered cloud waits in HBM for icpgpu_voxel_grid_fetch
-  if (m > 0) {
+  if (m > 0 && !pass) {  // (a pass-through hands the raw input on, non-finite points included: no box, its grids count for themselves)
     std::memcpy(c->vox_box, box, sizeof(box));
     c->vox_box_valid = true;
   }
@@ -253,8 +253,10 @@ int icpgpu_voxel_grid_view(icpgpu_ctx* c, const float* xyzw, size_t n, float lea
     return rc;
   c->vox_last_n = (size_t)m;
   if (m > 0) {
-    std::memcpy(c->vox_box, box, sizeof(box));
-    c->vox_box_valid = true;
+    if (!pass) {  // (as in icpgpu_voxel_grid)
+      std::memcpy(c->vox_box, box, sizeof(box));
+      c->vox_box_valid = true;
+    }
     if (published) {  // the points are in the staging buffer already: they arrived in front of the cell count
       c->vox_fp = fp_finish(fp_sum, (unsigned long long)m);
       c->vox_sample_fp = sample_fingerprint(static_cast<const float*>(c->h_stage), (size_t)m);
@@ -299,7 +301,10 @@ int icpgpu_set_source_voxel_filtered(icpgpu_ctx* c, const float* xyzw, size_t n,
   // The raw scan's bounding box contains every centroid (a mean of points inside a box lies inside it, up to a rounding the
   // grid's one-cell margin absorbs): the grids built over the filtered cloud start from it, without a pass and a round trip
   // of their own.  (An empty / non-finite input leaves lo > hi: a grid build then finds "no finite point", as its own pass would.)
-  if (m > 0) {
+  // Not after a pass-through (PCL's "leaf size too small": the raw input is handed on, non-finite points included): a handed-over box
+  // stands for "means of finite points" (ensure_covariances builds a grid ahead of its statistics on that), so such a cloud gets the
+  // bounding-box pass and the count of any other cloud.
+  if (m > 0 && !pass) {
     std::memcpy(c->src.bbox_enc, box, sizeof(box));
     c->src.bbox_version = c->src_version;
     c->src.bbox_exact = false;

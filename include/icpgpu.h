@@ -356,7 +356,10 @@ int icpgpu_solve(const double sums[17], double Tk[16]);
 int icpgpu_transform(icpgpu_ctx* ctx, const float* T, float* out_xyzw);
 
 /* a11 (GICP mode): per-point regularised covariances U diag(1,1,1e-3) U^T of the 20 nearest neighbours
- * (pcl::GeneralizedIterativeClosestPoint::computeCovariances); out6 = n x {xx, xy, xz, yy, yz, zz}. */
+ * (pcl::GeneralizedIterativeClosestPoint::computeCovariances); out6 = n x {xx, xy, xz, yy, yz, zz}.
+ * GICP needs at least 20 FINITE points per cloud: with fewer (PCL's kd-tree holds the finite points only, its nearestKSearch(20) then
+ * comes back short) the cloud is too small -- ICPGPU_ERR_INVALID_ARG here, and icpgpu_align / icpgpu_align_batch end as for a cloud
+ * of fewer than 20 points: not converged, T = I, 0 iterations. */
 int icpgpu_gicp_covariances(icpgpu_ctx* ctx, int of_target, double* out6);
 /* ---- point-to-plane mode (ICPGPU_P2PLANE, 1.2) ------------------------------------------------------ */
 /* replaces setInputTarget's normals: pcl::IterativeClosestPointWithNormals<PointNormal, PointNormal> reads them from the target

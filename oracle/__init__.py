@@ -397,7 +397,7 @@ def gicp_covariances(cloud, arith=ARITH_FMA, pcl_order=False) -> np.ndarray:
     out = np.zeros((cloud.shape[0], 9), np.float64)
     rc = lib().orc_gicp_covariances_ex(pc, cloud.shape[0], arith, int(pcl_order), out.ctypes.data_as(C.POINTER(C.c_double)))
     if rc != 0:
-        raise RuntimeError("orc_gicp_covariances: cloud smaller than k = 20")
+        raise RuntimeError("orc_gicp_covariances: fewer than k = 20 finite points")
     return out.reshape(-1, 3, 3)
 
 

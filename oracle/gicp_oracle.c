@@ -226,8 +226,17 @@ static void raw_covariance(const void* tree, const float* cloud, size_t i, int32
     }
 }
 
+/* The project's rule where PCL has none: a cloud is too small when fewer than k_correspondences_ of its points are FINITE.  (PCL
+ * tests the raw size -- "Number or points in cloud is less than k_correspondences_" -- but its kd-tree holds the finite points
+ * only, nearestKSearch(20) then comes back short and computeCovariances reads neighbour indices nobody wrote.) */
+static size_t count_finite(const float* cloud, size_t n) {
+  size_t m = 0;
+  for (size_t i = 0; i < n; ++i) m += isfinite(cloud[4 * i]) && isfinite(cloud[4 * i + 1]) && isfinite(cloud[4 * i + 2]);
+  return m;
+}
+
 int orc_gicp_covariances_ex(const float* cloud, size_t n, int arith, int pcl_order, double* cov_out /* n x 9 row-major */) {
-  if (n < GICP_K) return -1; /* PCL: "Number or points in cloud is less than k_correspondences_" */
+  if (count_finite(cloud, n) < GICP_K) return -1; /* too small: the neighbour list below always holds GICP_K entries */
   void* tree = orc_kd_build(cloud, n, arith);
   int32_t idx[GICP_K];
   for (size_t i = 0; i < n; ++i) {
@@ -268,12 +277,6 @@ int orc_gicp_covariances_ex(const float* cloud, size_t n, int arith, int pcl_ord
 
 int orc_gicp_covariances(const float* cloud, size_t n, int arith, double* cov_out) {
   return orc_gicp_covariances_ex(cloud, n, arith, 0, cov_out);
-}
-
-static size_t count_finite(const float* cloud, size_t n) {
-  size_t m = 0;
-  for (size_t i = 0; i < n; ++i) m += isfinite(cloud[4 * i]) && isfinite(cloud[4 * i + 1]) && isfinite(cloud[4 * i + 2]);
-  return m;
 }
 
 int orc_gicp_neighbours(const float* cloud, size_t n, int arith, int32_t* idx_out) {
@@ -890,7 +893,7 @@ int orc_gicp_align(const float* src, size_t n_s, const float* tgt, size_t n_t, c
     if (out_xyzw && n_s) orc_transform_cloud(src, n_s, res->T, out_xyzw);
     return 0;
   }
-  if (n_s < GICP_K || n_t < GICP_K) { /* computeCovariances refuses clouds smaller than k_correspondences_ */
+  if (count_finite(src, n_s) < GICP_K || count_finite(tgt, n_t) < GICP_K) { /* computeCovariances refuses clouds of fewer than k_correspondences_ (finite) points */
     if (out_xyzw && n_s) orc_transform_cloud(src, n_s, res->T, out_xyzw);
     return 0;
   }

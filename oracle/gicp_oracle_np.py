@@ -72,13 +72,17 @@ def transform_f32(pts, T):
 # ---------------------------------------------------------------------------------------------------------------------
 # computeCovariances
 # ---------------------------------------------------------------------------------------------------------------------
+def _count_finite(p32):
+    return int(np.isfinite(p32[:, :3]).all(axis=1).sum())
+
+
 def covariances(cloud):
     """(n, 3, 3) float64: per point, covariance of its 20 nearest neighbours (itself included), singular values replaced
     by (1, 1, gicp_epsilon)."""
     p32 = np.ascontiguousarray(cloud[:, :3], f32)
     n = p32.shape[0]
-    if n < K_CORR:
-        raise ValueError("cloud smaller than k_correspondences_")
+    if _count_finite(p32) < K_CORR:                        # (the project's rule: oracle/gicp_oracle.c, count_finite)
+        raise ValueError("fewer than k_correspondences_ finite points")
     _, nbr = cKDTree(p32.astype(np.float64)).query(p32.astype(np.float64), k=K_CORR)
     q = p32[nbr]                                           # (n, 20, 3) float32
     mean = q.astype(np.float64).sum(axis=1) / K_CORR       # sums of 20 float32 values are exact in float64
@@ -405,20 +409,55 @@ def _bfgs_minimize(cost, x):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# one outer iteration's problem, for tests that step through another implementation's iterations
+# ---------------------------------------------------------------------------------------------------------------------
+def problem_at(src, tgt, transformation, guess=None, max_correspondence_distance=1.0, sums="exact"):
+    """(cost, x, n_corr): the inner objective (_Cost; None below 4 correspondences) of the outer iteration that starts at
+    `transformation` -- correspondences of transformation * guess within the gate, their Mahalanobis matrices -- and the state
+    vector x of `transformation`, where its BFGS run starts.  The same steps as gicp_align's loop body."""
+    src32 = np.ascontiguousarray(src[:, :4], f32)
+    tgt32 = np.ascontiguousarray(tgt[:, :4], f32)
+    guess = np.eye(4, dtype=f32) if guess is None else np.asarray(guess, f32)
+    transformation = np.asarray(transformation, f32)
+    Cs, Ct = covariances(src32), covariances(tgt32)
+    TG = np.zeros((4, 4), f32)
+    for r in range(4):
+        for c in range(4):
+            s = f32(0)
+            for k in range(4):
+                s = f32(s + transformation[r, k] * guess[k, c])
+            TG[r, c] = s
+    R = transformation[:3, :].astype(np.float64) @ guess[:, :3].astype(np.float64)
+    q = transform_f32(src32, TG)
+    _, j = cKDTree(tgt32[:, :3].astype(np.float64)).query(q.astype(np.float64))
+    d64 = (tgt32[j, :3] - q).astype(np.float64)
+    d2 = (d64[:, 0] * d64[:, 0]).astype(f32).astype(np.float64)
+    d2 = (d64[:, 1] * d64[:, 1] + d2).astype(f32).astype(np.float64)
+    d2 = (d64[:, 2] * d64[:, 2] + d2).astype(f32).astype(np.float64)
+    keep = np.flatnonzero(d2 < max_correspondence_distance ** 2)
+    x = _state_from_matrix(transformation)
+    if keep.size < 4:
+        return None, x, int(keep.size)
+    maha = np.linalg.inv(Ct[j[keep]] + R[None] @ Cs[keep] @ R.T[None])
+    return _Cost(src32[keep], tgt32[j[keep], :3], maha, guess, sums), x, int(keep.size)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # computeTransformation
 # ---------------------------------------------------------------------------------------------------------------------
 def gicp_align(src, tgt, max_iterations=10, transformation_epsilon=1e-6, max_correspondence_distance=1.0, guess=None,
-               sums="sequential"):
-    """Returns dict(T 4x4 float32, converged, iterations, n_corr, evaluations)."""
+               sums="sequential", transformation0=None, covariances_st=None):
+    """Returns dict(T 4x4 float32, converged, iterations, n_corr, evaluations).  transformation0: the loop's `transformation_`
+    starts there instead of at the identity (a test steps through the outer iterations of another implementation with it)."""
     src32 = np.ascontiguousarray(src[:, :4], f32)
     tgt32 = np.ascontiguousarray(tgt[:, :4], f32)
     guess = np.eye(4, dtype=f32) if guess is None else np.asarray(guess, f32)
     out = dict(T=np.eye(4, dtype=f32), converged=False, iterations=0, n_corr=0, evaluations=0)
-    if tgt32.shape[0] < K_CORR or src32.shape[0] < K_CORR:
+    if _count_finite(tgt32) < K_CORR or _count_finite(src32) < K_CORR:
         return out
-    Ct, Cs = covariances(tgt32), covariances(src32)
+    Cs, Ct = (covariances(src32), covariances(tgt32)) if covariances_st is None else covariances_st
     tree = cKDTree(tgt32[:, :3].astype(np.float64))
-    transformation = np.eye(4, dtype=f32)
+    transformation = np.eye(4, dtype=f32) if transformation0 is None else np.array(transformation0, dtype=f32)
     previous = transformation.copy()
     r2 = max_correspondence_distance ** 2
     nr, converged, n_corr, evals = 0, False, 0, 0

@@ -117,6 +117,22 @@ def test_gicp_needs_twenty_points(ctx):
     with pytest.raises(IcpGpuError) as e:           # asked for explicitly, it is an argument error
         ctx.gicp_covariances(of_target=False)
     assert _code(e) == ERR_INVALID_ARG and "20" in str(e.value)
+    # ... and so is a cloud of 30 points of which 19 are finite: PCL's kd-tree holds the finite points only, nearestKSearch(20)
+    # comes back short -- the rule here is "fewer than 20 FINITE points is too small", as a source and as a target
+    few = src[100:130].copy()
+    few[::3, 0] = np.nan
+    few[1, 2] = np.inf
+    assert int(np.isfinite(few[:, :3]).all(axis=1).sum()) == 19
+    for as_target in (False, True):
+        ctx.set_source(src if as_target else few)
+        ctx.set_target(few if as_target else tgt)
+        for _ in range(2):   # (the second call meets the count the first one's grid build left with the cloud)
+            r = ctx.align()
+            assert not r["converged"] and r["iterations"] == 0 and r["n_corr"] == 0 and np.array_equal(r["T"], np.eye(4, dtype=np.float32))
+            with pytest.raises(IcpGpuError) as e:
+                ctx.gicp_covariances(of_target=as_target)
+            assert _code(e) == ERR_INVALID_ARG and "20" in str(e.value)
+    ctx.set_target(tgt)
     ctx.set_source(src)
     assert ctx.align()["iterations"] >= 1
 
