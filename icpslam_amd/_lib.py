@@ -92,6 +92,7 @@ EXPORTS = [
     "icpgpu_ndt_derivatives", "icpgpu_ndt_step", "icpgpu_set_ndt_line_search", "icpgpu_get_ndt_line_search", "icpgpu_ndt_gradient",
     "icpgpu_ndt_line_search_replay", "icpgpu_ndt_line_search_trace",
     "icpgpu_set_correspondence_rejectors", "icpgpu_get_correspondence_rejectors", "icpgpu_correspondences", "icpgpu_rejector_stats",
+    "icpgpu_set_reciprocal_correspondences", "icpgpu_get_reciprocal_correspondences", "icpgpu_reciprocal_stats",
 ]
 
 _lib = None
@@ -174,6 +175,9 @@ def load():
     L.icpgpu_get_correspondence_rejectors.argtypes = [vp, C.POINTER(Rejector), C.POINTER(C.c_size_t)]
     L.icpgpu_correspondences.argtypes = [vp, fp, ip, fp]
     L.icpgpu_rejector_stats.argtypes = [vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), fp, C.POINTER(C.c_size_t)]
+    L.icpgpu_set_reciprocal_correspondences.argtypes = [vp, C.c_int]
+    L.icpgpu_get_reciprocal_correspondences.argtypes = [vp, C.POINTER(C.c_int)]
+    L.icpgpu_reciprocal_stats.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.icpgpu_voxel_grid.argtypes = [vp, fp, C.c_size_t, C.c_float, fp, C.POINTER(C.c_size_t)]
     L.icpgpu_voxel_grid_fetch.argtypes = [vp, fp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.icpgpu_voxel_grid_view.argtypes = [vp, fp, C.c_size_t, C.c_float, C.POINTER(fp), C.POINTER(C.c_size_t)]

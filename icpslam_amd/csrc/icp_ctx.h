@@ -271,6 +271,13 @@ struct icpgpu_ctx {
     uint32_t pairs_in, pairs_out, cut_bits;
   } rej_stats[ICPGPU_MAX_REJECTORS] = {};
   size_t rej_stats_n = 0;
+  // reciprocal correspondences (icpgpu_set_reciprocal_correspondences; icp_reciprocal.hip): the flag, the stage's device state
+  // (its two counters), the transformed source binned into the target grid's lattice -- rebuilt by every iteration, nothing of it
+  // is read by a later one -- and the statistics as the host last fetched them with the chain's (rcp_ran: the stage has run since)
+  bool reciprocal = false;
+  DeviceBuf rcp_state, rcp_counts, rcp_cell_start, rcp_scan, rcp_cell_of_point, rcp_rank, rcp_binned;
+  bool rcp_ran = false;
+  uint32_t rcp_stats[2] = {0, 0};
   // the NDT step rule (icpgpu_ndt_line_search: 0 = PCL 1.8's clamped Newton step, 1 = More-Thuente) and the last alignment's
   // line-search trials (More-Thuente only): Newton iteration, step, phi = -score, phi' = -(g . d)
   int ndt_line_search = 0;
@@ -605,6 +612,9 @@ int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_f
 bool solve_point_to_plane(const double sums[kP2planeTerms], Mat4d& Tk);
 // icpgpu_reject.cpp
 int gated_keys(icpgpu_ctx* c, const Xform& T, float thr, unsigned long long* keys);
+// keys path: the alignment's iterations go search -> reciprocal stage -> chain -> the method's keys reduction
+inline bool keys_stages(const icpgpu_ctx* c) { return c->n_rejectors > 0 || c->reciprocal; }
+int reciprocal_run(icpgpu_ctx* c, const Xform& T, unsigned long long* keys, float thr);
 int reject_run_chain(icpgpu_ctx* c, unsigned long long* keys, float thr);
 int reject_fetch_stats(icpgpu_ctx* c);
 int sweep_issue_rejected(icpgpu_ctx* c, const Xform& T, float thr, SweepTicket& tk);

@@ -364,6 +364,22 @@ hipError_t launch_reject_chain(unsigned long long* keys, int n_s, int n_t, float
 // keys -> (idx, d2) for icpgpu_correspondences: idx = -1, d2 = +inf for a pair that is not alive
 hipError_t launch_reject_unpack(const unsigned long long* keys, int n, float thr, int32_t* idx, float* d2, hipStream_t stream);
 
+// ---- reciprocal correspondences (icp_reciprocal.hip): a stage in front of the rejector chain ---------------------------------
+// Empties the key of every alive pair (i, j) for which x_i = T * src[i] is not the nearest of all x_* to tgt[j] (dist2(tgt[j], x_k),
+// lowest k among equals).  state: kRecipStateInts unsigned ints of device memory = {pairs alive before, pairs kept, 0, 0};
+// winners: n_t 64-bit words of scratch.
+static constexpr int kRecipStateInts = 4;
+// grid flavour: x_* binned into the lattice g of the target's grid.  counts, cell_start: reciprocal_cells(g) + 1 ints each;
+// scan_scratch: exclusive_scan_scratch_ints(reciprocal_cells(g) + 1) ints; cell_of_point, rank: n_s ints each; binned: n_s float4
+size_t reciprocal_cells(const GridDesc& g);
+hipError_t launch_reciprocal_grid(const float4* src, int n_s, const float4* tgt, int n_t, const Xform& T, float thr,
+                                  unsigned long long* keys, const GridDesc& g, int* counts, int* cell_start, int* scan_scratch,
+                                  int* cell_of_point, int* rank, float4* binned, unsigned long long* winners, unsigned int* state,
+                                  hipStream_t stream);
+// brute flavour: every winner against all of x_* (no grid needed)
+hipError_t launch_reciprocal_brute(const float4* src, int n_s, const float4* tgt, int n_t, const Xform& T, float thr,
+                                   unsigned long long* keys, unsigned long long* winners, unsigned int* state, hipStream_t stream);
+
 // ---- NDT (icp_ndt.hip): pcl::NormalDistributionsTransform's target cells and derivative pass ----------------------------
 static constexpr int kNdtTerms = 29;         // pairs, score, gradient (6), Hessian upper triangle row by row (21)
 static constexpr int kNdtGradTerms = 8;      // the trial pass's: pairs, score, gradient (6) -- the first 8 of the 29

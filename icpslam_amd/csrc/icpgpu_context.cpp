@@ -632,6 +632,7 @@ int icpgpu_destroy(icpgpu_ctx* c) {
   for (DeviceBuf* b : {&c->nrm_src, &c->nrm_tgt, &c->nrm_raw, &c->nrm_user, &c->p2plane_partials}) release(*b);
   release(c->maha);
   for (DeviceBuf* b : {&c->rej_state, &c->rej_winners, &c->rej_post}) release(*b);
+  for (DeviceBuf* b : {&c->rcp_state, &c->rcp_counts, &c->rcp_cell_start, &c->rcp_scan, &c->rcp_cell_of_point, &c->rcp_rank, &c->rcp_binned}) release(*b);
   release(c->cov_list);
   release(c->vox_in);
   release(c->vox_out);

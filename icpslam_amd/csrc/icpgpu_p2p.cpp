@@ -154,7 +154,7 @@ int wait_sums(icpgpu_ctx* c, unsigned long long seq) {
 
 
 int sweep_issue(icpgpu_ctx* c, const Xform& T, float thr, bool open_range, SweepTicket& tk) {
-  if (c->n_rejectors > 0 && !open_range) return sweep_issue_rejected(c, T, thr, tk);  // (getFitnessScore's sweep knows no rejectors)
+  if (keys_stages(c) && !open_range) return sweep_issue_rejected(c, T, thr, tk);  // (getFitnessScore's sweep knows no rejectors and no reciprocal rule)
   static const bool timing = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_P2P_TIMING"); return e && std::atoi(e) != 0; }();
   if (timing) {
     c->pt_issue_in = std::chrono::steady_clock::now();
@@ -439,6 +439,7 @@ int p2p_prepare(icpgpu_ctx* c, P2PRun& r, const float* guess, float* out_xyzw, i
     c->call_sweeps = c->call_timed = 0;
     c->prev.valid = c->tile_seed.valid = false;  // every alignment starts cold
     c->rej_ran = 0;
+    c->rcp_ran = false;
   }
   if (guess)
     for (int i = 0; i < 16; ++i) r.final_T[i] = (double)guess[i];

@@ -131,6 +131,7 @@ int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_f
   c->call_sweeps = c->call_timed = 0;
   c->prev.valid = c->tile_seed.valid = false;  // every alignment starts cold
   c->rej_ran = 0;
+  c->rcp_ran = false;
   Mat4d final_T = mat4_identity();
   if (guess)
     for (int i = 0; i < 16; ++i) final_T[i] = (double)guess[i];
@@ -155,6 +156,7 @@ int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_f
     for (;;) {
       const Xform T = to_xform(final_T);
       if ((rc = gated_keys(c, T, thr, keys))) return rc;
+      if ((rc = reciprocal_run(c, T, keys, thr))) return rc;  // (flag off: nothing)
       if ((rc = reject_run_chain(c, keys, thr))) return rc;  // (an empty chain: nothing)
       const unsigned long long seq = ++c->sums_seq;
       HIP_TRY(c, launch_p2plane_reduce(c->src.data(), n_s, c->tgt.data(), normals, keys, T, thr, static_cast<double*>(c->p2plane_partials.ptr),

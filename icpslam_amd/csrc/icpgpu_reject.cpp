@@ -1,9 +1,10 @@
 // icpgpu_reject.cpp -- the correspondence rejectors' host side (PCL: Registration::addCorrespondenceRejector and
-// CorrespondenceRejectorMedianDistance / Trimmed / OneToOne): the context's chain, the gated key-writing search the chain runs
-// behind, the chain's launch (icp_reject.hip), the point-to-point sweep with a chain, and the entry points that show what a chain
-// keeps (icpgpu_correspondences, icpgpu_rejector_stats).  An iteration with a chain is search -> stages -> the method's keys
-// reduction, queued back to back: nothing of the chain is read by the host until the alignment ends (reject_fetch_stats: one
-// posted read-back of the last iteration's statistics through the result mailbox).
+// CorrespondenceRejectorMedianDistance / Trimmed / OneToOne) and that of reciprocal correspondences (setUseReciprocalCorrespondences):
+// the context's chain and flag, the gated key-writing search they run behind, the reciprocal stage's launch (icp_reciprocal.hip), the
+// chain's (icp_reject.hip), the point-to-point sweep with either, and the entry points that show what they keep
+// (icpgpu_correspondences, icpgpu_rejector_stats, icpgpu_reciprocal_stats).  An iteration on the keys path is search -> reciprocal
+// stage -> chain stages -> the method's keys reduction, queued back to back: nothing of the stages is read by the host until the
+// alignment ends (reject_fetch_stats: one posted read-back of the last iteration's statistics through the result mailbox).
 #include "icp_ctx.h"
 
 namespace icpgpu_impl {
@@ -30,6 +31,38 @@ int gated_keys(icpgpu_ctx* c, const Xform& T, float thr, unsigned long long* key
   return nn_keys_brute(c, c->tgt.data(), n_t, T, keys);
 }
 
+// The reciprocal stage over the keys of T * source (flag off: nothing).  Where the forward search used the target's grid the
+// transformed source is binned into that grid's lattice; otherwise every winner is tested against the whole source.  Everything
+// is queued: the stage reads nothing back.
+int reciprocal_run(icpgpu_ctx* c, const Xform& T, unsigned long long* keys, float thr) {
+  if (!c->reciprocal) return ICPGPU_OK;
+  const int n_s = (int)c->src.n, n_t = (int)c->tgt.n;
+  if (n_s <= 0 || n_t <= 0) return ICPGPU_OK;  // (no pair: the statistics read as zeroes)
+  int rc = ensure(c, c->rcp_state, kRecipStateInts * sizeof(unsigned int));
+  if (rc) return rc;
+  if ((rc = ensure(c, c->rej_winners, (size_t)n_t * sizeof(unsigned long long)))) return rc;  // (shared with one-to-one: stages run one after the other)
+  auto* state = static_cast<unsigned int*>(c->rcp_state.ptr);
+  auto* winners = static_cast<unsigned long long*>(c->rej_winners.ptr);
+  if (grid_ready(c)) {
+    const GridDesc& g = c->grid.g;
+    const size_t table = reciprocal_cells(g) + 1;
+    if ((rc = ensure(c, c->rcp_counts, table * sizeof(int)))) return rc;
+    if ((rc = ensure(c, c->rcp_cell_start, table * sizeof(int)))) return rc;
+    if ((rc = ensure(c, c->rcp_scan, exclusive_scan_scratch_ints((int)table) * sizeof(int)))) return rc;
+    if ((rc = ensure(c, c->rcp_cell_of_point, (size_t)n_s * sizeof(int)))) return rc;
+    if ((rc = ensure(c, c->rcp_rank, (size_t)n_s * sizeof(int)))) return rc;
+    if ((rc = ensure(c, c->rcp_binned, (size_t)n_s * sizeof(float4)))) return rc;
+    HIP_TRY(c, launch_reciprocal_grid(c->src.data(), n_s, c->tgt.data(), n_t, T, thr, keys, g, static_cast<int*>(c->rcp_counts.ptr),
+                                      static_cast<int*>(c->rcp_cell_start.ptr), static_cast<int*>(c->rcp_scan.ptr),
+                                      static_cast<int*>(c->rcp_cell_of_point.ptr), static_cast<int*>(c->rcp_rank.ptr),
+                                      static_cast<float4*>(c->rcp_binned.ptr), winners, state, c->stream));
+  } else {
+    HIP_TRY(c, launch_reciprocal_brute(c->src.data(), n_s, c->tgt.data(), n_t, T, thr, keys, winners, state, c->stream));
+  }
+  c->rcp_ran = true;
+  return ICPGPU_OK;
+}
+
 int reject_run_chain(icpgpu_ctx* c, unsigned long long* keys, float thr) {
   const int n = c->n_rejectors;
   if (n <= 0) return ICPGPU_OK;
@@ -53,38 +86,50 @@ int reject_run_chain(icpgpu_ctx* c, unsigned long long* keys, float thr) {
   return ICPGPU_OK;
 }
 
-// the statistics of the chain's last run -> c->rej_stats (zeroes when the chain has not run since they were last taken)
+// the statistics of the last run of the chain and of the reciprocal stage -> c->rej_stats, c->rcp_stats (zeroes for whichever has
+// not run since they were last taken); one read-back for both
 int reject_fetch_stats(icpgpu_ctx* c) {
   std::memset(c->rej_stats, 0, sizeof c->rej_stats);
   c->rej_stats_n = c->n_rejectors;
-  if (c->rej_ran <= 0) return ICPGPU_OK;
-  const int n = c->rej_ran;
+  c->rcp_stats[0] = c->rcp_stats[1] = 0;
+  const int n = c->rej_ran > 0 ? c->rej_ran : 0;
+  const bool rcp = c->rcp_ran;
+  if (n <= 0 && !rcp) return ICPGPU_OK;
   c->rej_ran = 0;
+  c->rcp_ran = false;
   if ((int)c->rej_stats_n < n) c->rej_stats_n = n;
-  int rc = ensure(c, c->rej_post, (size_t)kRejectMaxStages * 3 * sizeof(int));
+  int rc = ensure(c, c->rej_post, ((size_t)kRejectMaxStages * 3 + 2) * sizeof(int));
   if (rc) return rc;
   for (int s = 0; s < n; ++s)
     HIP_TRY(c, hipMemcpyAsync(static_cast<int*>(c->rej_post.ptr) + 3 * s,
                               static_cast<const unsigned int*>(c->rej_state.ptr) + (size_t)s * kRejectStateInts + kRejectStats, 3 * sizeof(int),
                               hipMemcpyDeviceToDevice, c->stream));
-  int h[kRejectMaxStages * 3];
-  if ((rc = fetch_ints(c, static_cast<const int*>(c->rej_post.ptr), 3 * n, h))) return rc;
+  if (rcp)
+    HIP_TRY(c, hipMemcpyAsync(static_cast<int*>(c->rej_post.ptr) + 3 * n, c->rcp_state.ptr, 2 * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+  int h[kRejectMaxStages * 3 + 2];
+  if ((rc = fetch_ints(c, static_cast<const int*>(c->rej_post.ptr), 3 * n + (rcp ? 2 : 0), h))) return rc;
   for (int s = 0; s < n; ++s) {
     c->rej_stats[s].pairs_in = (uint32_t)h[3 * s];
     c->rej_stats[s].pairs_out = (uint32_t)h[3 * s + 1];
     c->rej_stats[s].cut_bits = (uint32_t)h[3 * s + 2];
   }
+  if (rcp) {
+    c->rcp_stats[0] = (uint32_t)h[3 * n];
+    c->rcp_stats[1] = (uint32_t)h[3 * n + 1];
+  }
   return ICPGPU_OK;
 }
 
-// sweep_issue's counterpart for a context with a chain (gated sweeps only): the key-writing search over the source in the caller's
-// order (one-to-one breaks ties on the caller's source index), the chain, reduce_kernel over the keys that are left
+// sweep_issue's counterpart for a context with a chain or the reciprocal flag (gated sweeps only): the key-writing search over the
+// source in the caller's order (one-to-one and reciprocal break ties on the caller's source index), the reciprocal stage, the chain,
+// reduce_kernel over the keys that are left
 int sweep_issue_rejected(icpgpu_ctx* c, const Xform& T, float thr, SweepTicket& tk) {
   const int n_s = (int)c->src.n;
   int rc = ensure(c, c->keys, (size_t)(n_s ? n_s : 1) * sizeof(unsigned long long));
   if (rc) return rc;
   auto* keys = static_cast<unsigned long long*>(c->keys.ptr);
   if ((rc = gated_keys(c, T, thr, keys))) return rc;
+  if ((rc = reciprocal_run(c, T, keys, thr))) return rc;
   if ((rc = reject_run_chain(c, keys, thr))) return rc;
   if ((rc = ensure(c, c->partials, (size_t)kMaxReduceBlocks * kReduceTerms * sizeof(double)))) return rc;
   const unsigned long long seq = ++c->sums_seq;
@@ -136,6 +181,25 @@ int icpgpu_get_correspondence_rejectors(const icpgpu_ctx* c, icpgpu_rejector* ou
   return ICPGPU_OK;
 }
 
+int icpgpu_set_reciprocal_correspondences(icpgpu_ctx* c, int on) {
+  if (!c) return fail(nullptr, ICPGPU_ERR_INVALID_ARG, "null context");
+  c->reciprocal = on != 0;
+  return ICPGPU_OK;
+}
+
+int icpgpu_get_reciprocal_correspondences(const icpgpu_ctx* c, int* on) {
+  if (!c || !on) return ICPGPU_ERR_INVALID_ARG;
+  *on = c->reciprocal ? 1 : 0;
+  return ICPGPU_OK;
+}
+
+int icpgpu_reciprocal_stats(const icpgpu_ctx* c, uint32_t* pairs_in, uint32_t* pairs_out) {
+  if (!c) return ICPGPU_ERR_INVALID_ARG;
+  if (pairs_in) *pairs_in = c->rcp_stats[0];
+  if (pairs_out) *pairs_out = c->rcp_stats[1];
+  return ICPGPU_OK;
+}
+
 int icpgpu_correspondences(icpgpu_ctx* c, const float* T, int32_t* idx, float* d2) {
   ENTER(c);
   if (!c->src.set || !c->tgt.set) return fail(c, ICPGPU_ERR_NO_INPUT, "correspondences: source and target must be set first");
@@ -148,11 +212,14 @@ int icpgpu_correspondences(icpgpu_ctx* c, const float* T, int32_t* idx, float* d
   const float thr = threshold_from(c->params.max_correspondence_distance * c->params.max_correspondence_distance);
   auto* keys = static_cast<unsigned long long*>(c->keys.ptr);
   c->prev.valid = false;  // (as an alignment's first iteration: nothing carried over)
+  c->rcp_ran = false;
   if (c->tgt.n == 0) {
     HIP_TRY(c, launch_fill_keys(keys, n_s, c->stream));
   } else {
+    const Xform X = T ? to_xform(T) : to_xform(mat4_identity());
     if ((rc = ensure_grid(c, thr))) return rc;
-    if ((rc = gated_keys(c, T ? to_xform(T) : to_xform(mat4_identity()), thr, keys))) return rc;
+    if ((rc = gated_keys(c, X, thr, keys))) return rc;
+    if ((rc = reciprocal_run(c, X, keys, thr))) return rc;
   }
   if ((rc = reject_run_chain(c, keys, thr))) return rc;
   HIP_TRY(c, launch_reject_unpack(keys, n_s, thr, static_cast<int32_t*>(c->idx.ptr), static_cast<float*>(c->d2.ptr), c->stream));

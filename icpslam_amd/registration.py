@@ -224,7 +224,8 @@ class Context:
         return [(int(r.kind), float(r.value), int(r.min_correspondences)) for r in arr[:n.value]]
 
     def correspondences(self, T=np.eye(4)):
-        """What one iteration at T hands to the solve: (idx, d2) per source point, idx = -1 where the gate or the chain removed the pair."""
+        """What one iteration at T hands to the solve: (idx, d2) per source point, idx = -1 where the gate, the reciprocal test or
+        the chain removed the pair."""
         idx = np.empty(self.n_source, np.int32)
         d2 = np.empty(self.n_source, np.float32)
         Tb = _colmajor16(T)
@@ -240,6 +241,23 @@ class Context:
         u32 = C.POINTER(C.c_uint32)
         self._check(self._L.icpgpu_rejector_stats(self._h, cap, a.ctypes.data_as(u32), b.ctypes.data_as(u32), _fp(cut), C.byref(n)))
         return [dict(pairs_in=int(a[s]), pairs_out=int(b[s]), cut=np.float32(cut[s])) for s in range(n.value)]
+
+    # reciprocal correspondences (pcl::Registration::setUseReciprocalCorrespondences) -----------------------------------
+    def set_reciprocal_correspondences(self, on: bool):
+        """P2P_SVD / P2PLANE: keep a pair only if the target point's nearest transformed source point is the pair's own (the
+        lowest source index among equally near ones); in front of the rejector chain.  GICP and NDT ignore it."""
+        self._check(self._L.icpgpu_set_reciprocal_correspondences(self._h, 1 if on else 0))
+
+    def get_reciprocal_correspondences(self) -> bool:
+        on = C.c_int(0)
+        self._check(self._L.icpgpu_get_reciprocal_correspondences(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def reciprocal_stats(self):
+        """The reciprocal stage's last run: dict(pairs_in (past the gate), pairs_out (reciprocal)); zeroes when the flag was off."""
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._L.icpgpu_reciprocal_stats(self._h, C.byref(a), C.byref(b)))
+        return dict(pairs_in=int(a.value), pairs_out=int(b.value))
 
     # kernel-level entry points ------------------------------------------------------------------------------
     def nn(self, T=np.eye(4)):
@@ -589,6 +607,7 @@ class IterativeClosestPoint:
         self._result = None
         self._fitness = None
         self._rejectors = []
+        self._reciprocal = False
 
     # setters used by the reference -----------------------------------------------------------------------------
     def setMaximumIterations(self, n):           # icp_odometer.cpp:189 (passes a double constant)
@@ -625,8 +644,17 @@ class IterativeClosestPoint:
     def clearCorrespondenceRejectors(self):
         self._rejectors = []
 
+    # pcl::Registration::setUseReciprocalCorrespondences (read by IterativeClosestPoint and ...WithNormals only, as in PCL: the
+    # GICP and NDT mirrors store the flag and the library ignores it for their methods)
+    def setUseReciprocalCorrespondences(self, on: bool):
+        self._reciprocal = bool(on)
+
+    def getUseReciprocalCorrespondences(self) -> bool:
+        return self._reciprocal
+
     def _set_chain(self):
         self._ctx.set_correspondence_rejectors([r._entry() for r in self._rejectors])
+        self._ctx.set_reciprocal_correspondences(self._reciprocal)
 
     def _take_rejector_stats(self):
         for r, s in zip(self._rejectors, self._ctx.rejector_stats()):

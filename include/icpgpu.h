@@ -52,7 +52,8 @@ extern "C" {
  * icpgpu_ndt_transformation_probability, icpgpu_ndt_cells, icpgpu_ndt_derivatives, icpgpu_ndt_step, icpgpu_set_ndt_line_search,
  * icpgpu_get_ndt_line_search, icpgpu_ndt_gradient, icpgpu_ndt_line_search_replay, icpgpu_ndt_line_search_trace (no struct changed); also added under
  * 1.2: the correspondence rejectors -- icpgpu_rejector, icpgpu_set_correspondence_rejectors, icpgpu_get_correspondence_rejectors,
- * icpgpu_correspondences, icpgpu_rejector_stats (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
+ * icpgpu_correspondences, icpgpu_rejector_stats, and reciprocal correspondences -- icpgpu_set_reciprocal_correspondences,
+ * icpgpu_get_reciprocal_correspondences, icpgpu_reciprocal_stats (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
  * icpgpu_profile.gicp_quadratic_solves; 0.3 icpgpu_profile (sources_adopted, gicp_host_solves, gicp_solver_choice). */
 
@@ -402,8 +403,8 @@ int icpgpu_solve_point_to_plane(const double sums[29], double Tk[16]);
  * GeneralizedIterativeClosestPoint::computeTransformation and NormalDistributionsTransform never read correspondence_rejectors_.
  * icpgpu_align_batch with a non-empty chain returns ICPGPU_ERR_UNSUPPORTED for every method (the lock-step kernels fuse the
  * reduction); icpgpu_align_batch_multi runs on contexts of the library's own, which never carry a chain.  With an empty chain an
- * alignment launches exactly the kernels it launched before rejectors existed.  Not provided: setUseReciprocalCorrespondences, the
- * surface-normal, var-trimmed, sample-consensus and feature rejectors. */
+ * alignment launches exactly the kernels it launched before rejectors existed.  Not provided: the surface-normal, var-trimmed,
+ * sample-consensus and feature rejectors. */
 typedef enum { ICPGPU_REJECT_MEDIAN_DISTANCE = 1, ICPGPU_REJECT_TRIMMED = 2, ICPGPU_REJECT_ONE_TO_ONE = 3 } icpgpu_rejector_kind;
 #define ICPGPU_MAX_REJECTORS 4
 typedef struct {
@@ -425,6 +426,30 @@ int icpgpu_correspondences(icpgpu_ctx* ctx, const float* T, int32_t* idx, float*
  * (MEDIAN_DISTANCE: the median, getMedianDistance(); TRIMMED: the m-th smallest d2; 0 where there is none: ONE_TO_ONE, no pair in,
  * m = 0).  *n_stages = their number; nothing is copied when it exceeds capacity.  Any output array may be NULL. */
 int icpgpu_rejector_stats(const icpgpu_ctx* ctx, size_t capacity, uint32_t* pairs_in, uint32_t* pairs_out, float* cut, size_t* n_stages);
+
+/* ---- reciprocal correspondences (added under 1.2) ---------------------------------------------------------------- */
+/* replaces pcl::Registration::setUseReciprocalCorrespondences (PCL 1.8: CorrespondenceEstimation::determineReciprocalCorrespondences
+ * as IterativeClosestPoint drives it).  Off by default.  When on, in every iteration of ICPGPU_P2P_SVD and ICPGPU_P2PLANE, with
+ * x_i = T * source[i] rounded to float as the search and icpgpu_transform round it:
+ *   1. forward, as always: j = the nearest target point of x_i (lowest target index among equals), d2 its float32 squared distance;
+ *      the pair passes the gate iff (double)d2 <= max_correspondence_distance^2.
+ *   2. reverse: k = the nearest of ALL x_* of this iteration to target[j], by the same float32 expression (which is symmetric bit
+ *      for bit: the reverse distance of x_i is the pair's d2).  A non-finite x_k is nobody's neighbour.
+ *   3. the pair stays iff k == i.  (PCL's second test, reverse distance <= the gate, is implied: the reverse distance is <= d2.)
+ * DEVIATION: among x_* at equal distance from target[j] the lowest source index (the caller's order) is the neighbour; PCL's
+ * kd-tree leaves that unspecified.  The same kind of deviation as ONE_TO_ONE's, and the kept set is a subset of ONE_TO_ONE's.
+ * The rejector chain then runs on what is left, as PCL runs rejectors after estimation; the solve, n_correspondences, mse_last, the
+ * convergence criteria and the min_correspondences test see the remainder; getFitnessScore is untouched.  icpgpu_correspondences
+ * shows gate, then reciprocal, then chain.  ICPGPU_GICP and ICPGPU_NDT ignore the flag (PCL's classes never read
+ * use_reciprocal_correspondence_).  icpgpu_align_batch with the flag set returns ICPGPU_ERR_UNSUPPORTED for every method, as with a
+ * chain; icpgpu_align_batch_multi's own contexts never carry it.  With the flag off an alignment launches exactly the kernels it
+ * launched before the flag existed.  A null context (or a null `on` of the getter): ICPGPU_ERR_INVALID_ARG. */
+int icpgpu_set_reciprocal_correspondences(icpgpu_ctx* ctx, int on);
+int icpgpu_get_reciprocal_correspondences(const icpgpu_ctx* ctx, int* on);
+/* the pairs past the gate and the pairs past the reciprocal test, for the last iteration of the context's last P2P_SVD / P2PLANE
+ * alignment or its last icpgpu_correspondences call, whichever came later (the lifetime of icpgpu_rejector_stats); zeroes when that
+ * run had the flag off.  Either output may be NULL. */
+int icpgpu_reciprocal_stats(const icpgpu_ctx* ctx, uint32_t* pairs_in, uint32_t* pairs_out);
 
 /* ---- NDT mode (ICPGPU_NDT, added under 1.2) --------------------------------------------------------------------- */
 /* setResolution / setStepSize / setOulierRatio.  resolution > 0, step_size > 0, 0 < outlier_ratio < 1, else ICPGPU_ERR_INVALID_ARG.

@@ -259,6 +259,11 @@ class IterativeClosestPoint {
     return true;
   }
   void clearCorrespondenceRejectors() { correspondence_rejectors_.clear(); }
+  // pcl::Registration::setUseReciprocalCorrespondences (include/icpgpu.h, "reciprocal correspondences": the rule and its tie
+  // deviation).  Read by IterativeClosestPoint and IterativeClosestPointWithNormals; on GeneralizedIterativeClosestPoint and
+  // NormalDistributionsTransform the flag is stored and changes nothing, as in PCL.
+  void setUseReciprocalCorrespondences(bool use_reciprocal_correspondence) { use_reciprocal_correspondence_ = use_reciprocal_correspondence; }
+  bool getUseReciprocalCorrespondences() const { return use_reciprocal_correspondence_; }
 
   explicit IterativeClosestPoint(int device = 0, icpgpu_method method = ICPGPU_P2P_SVD)
       : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {
@@ -332,9 +337,11 @@ class IterativeClosestPoint {
   static_assert(sizeof(PointT) == 16, "point type must be the 16-byte pcl::PointXYZ layout");
 
   std::vector<CorrespondenceRejectorPtr> correspondence_rejectors_;
-  bool apply_rejectors() {  // (always: an object without rejectors clears what another one left on a shared context)
+  bool use_reciprocal_correspondence_ = false;
+  bool apply_rejectors() {  // (always: an object without rejectors clears what another one left on a shared context; the flag likewise)
     std::vector<icpgpu_rejector> chain;
     for (const auto& r : correspondence_rejectors_) chain.push_back(r->entry());
+    if (icpgpu_set_reciprocal_correspondences(ctx_, use_reciprocal_correspondence_ ? 1 : 0) != ICPGPU_OK) return false;
     return icpgpu_set_correspondence_rejectors(ctx_, chain.empty() ? nullptr : chain.data(), chain.size()) == ICPGPU_OK;
   }
   void take_rejector_stats() {
