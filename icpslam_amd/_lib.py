@@ -79,7 +79,7 @@ EXPORTS = [
     "icpgpu_fingerprint", "icpgpu_cloud_sizes", "icpgpu_align_batch_multi_sz", "icpgpu_multi_last_error",
     "icpgpu_fitness", "icpgpu_align_batch", "icpgpu_nn", "icpgpu_reduce", "icpgpu_solve", "icpgpu_transform",
     "icpgpu_profile_reset", "icpgpu_profile_get", "icpgpu_profile_set_sampling", "icpgpu_get_stream", "icpgpu_synchronize",
-    "icpgpu_voxel_grid", "icpgpu_voxel_grid_fetch", "icpgpu_voxel_grid_view", "icpgpu_set_source_voxel_filtered", "icpgpu_gicp_covariances",
+    "icpgpu_voxel_grid", "icpgpu_voxel_plan", "icpgpu_voxel_grid_fetch", "icpgpu_voxel_grid_view", "icpgpu_set_source_voxel_filtered", "icpgpu_gicp_covariances",
     "icpgpu_gicp_quadratic_eval", "icpgpu_gicp_quadratic_sums",
     "icpgpu_pose_from_matrix", "icpgpu_pose_to_matrix", "icpgpu_pose_compose", "icpgpu_pose_inverse", "icpgpu_posegraph_create",
     "icpgpu_posegraph_destroy", "icpgpu_posegraph_set_initial_pose", "icpgpu_posegraph_push",
@@ -156,6 +156,7 @@ def load():
     L.icpgpu_gicp_covariances.argtypes = [vp, C.c_int, dp]
     L.icpgpu_gicp_quadratic_eval.argtypes = [dp, fp, dp, dp, dp]
     L.icpgpu_gicp_quadratic_sums.argtypes = [vp, fp, dp]
+    L.icpgpu_voxel_plan.argtypes = [fp, fp, C.c_float, ip, ip, ip]
     L.icpgpu_set_target_normals.argtypes = [vp, fp, C.c_size_t]
     L.icpgpu_normals.argtypes = [vp, C.c_int, fp]
     L.icpgpu_reduce_point_to_plane.argtypes = [vp, fp, C.c_double, dp]

@@ -494,7 +494,8 @@ hipError_t launch_map_nn_unique(const unsigned long long* keys, const int* flags
 // ---- voxel-grid down-sampling (icp_voxel.hip), SURVEY.md 8(f2) -------------------------------------------------
 size_t voxel_temp_bytes(int n);
 // keys/vals: 2*n ints each, flags/slots: n ints each, d_n_out: 2 ints whose sum is the number of cells written to `out`.
-hipError_t launch_voxel_grid(const float4* pts, int n, float inv_leaf, const int minb[3], const int divb[3], int* keys,
+// minb / divb / wraps: voxel_grid_plan's (icp_voxel_plan.h), wraps = its verdict was kVoxelPlanWrap.
+hipError_t launch_voxel_grid(const float4* pts, int n, float inv_leaf, const int minb[3], const int divb[3], bool wraps, int* keys,
                              int* vals, int* flags, int* slots, void* temp, size_t temp_bytes, float4* out, int* d_n_out,
                              hipStream_t stream);
 

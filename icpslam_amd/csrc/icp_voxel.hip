@@ -23,6 +23,7 @@
 
 
 #include "icp_kernels.h"
+#include "icp_voxel_plan.h"
 
 namespace icpgpu {
 namespace {
@@ -37,10 +38,11 @@ __global__ __launch_bounds__(256) void voxel_key_kernel(const float4* __restrict
   const float4 p = pts[i];
   int key = kVoxelSentinel;
   if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
-    const int ix = (int)floorf(p.x * inv_leaf) - minb_x;
-    const int iy = (int)floorf(p.y * inv_leaf) - minb_y;
-    const int iz = (int)floorf(p.z * inv_leaf) - minb_z;
-    key = ix + iy * mul_y + iz * mul_z;
+    // (modulo 2^32, as PCL's int arithmetic comes out: under kVoxelPlanWrap these differences and products exceed int32)
+    const unsigned int ix = (unsigned int)(int)floorf(p.x * inv_leaf) - (unsigned int)minb_x;
+    const unsigned int iy = (unsigned int)(int)floorf(p.y * inv_leaf) - (unsigned int)minb_y;
+    const unsigned int iz = (unsigned int)(int)floorf(p.z * inv_leaf) - (unsigned int)minb_z;
+    key = (int)(ix + iy * (unsigned int)mul_y + iz * (unsigned int)mul_z);
   }
   keys[i] = key;
   vals[i] = i;
@@ -146,10 +148,10 @@ struct VoxelPlan {
   int minb[3], mul_y, mul_z;
   unsigned int cpb;
   int nbins;
-  int pre;  // 0: the direct path runs; 1: no finite point; 2: PCL's "leaf size too small" (input returned); 3: the index may wrap (sort path)
+  int pre;  // icp_voxel_plan.h's verdict -- 0: the direct path runs; 1: no finite point; 2: PCL's "leaf size too small" (input returned); 3: the index wraps (sort path)
 };
 
-// (inv_leaf = 1 / leaf in float, as PCL's inverse_leaf_size_; the arithmetic is voxel_filter_device's, operation for operation)
+// (inv_leaf = 1 / leaf in float, as PCL's inverse_leaf_size_; the arithmetic is voxel_grid_plan's, which the host calls too)
 // bbox6 is handed on to bbox_keep[0..5] (what the host reads) and left INITIALISED for the next bounding-box pass (its own init
 // launch is then not needed: voxel_filter_device).
 __global__ void voxel_plan_kernel(int* __restrict__ bbox6, float inv_leaf, VoxelPlan* __restrict__ plan, int* __restrict__ d_n_out,
@@ -165,31 +167,19 @@ __global__ void voxel_plan_kernel(int* __restrict__ bbox6, float inv_leaf, Voxel
     lo[a] = __int_as_float(el >= 0 ? el : el ^ 0x7FFFFFFF);
     hi[a] = __int_as_float(eh >= 0 ? eh : eh ^ 0x7FFFFFFF);
   }
+  // the ONE definition of the plan (icp_voxel_plan.h): the host takes this verdict, it derives none of its own
   VoxelPlan p;
-  p.pre = 0;
+  int divb[3];
+  long long ncells;
+  p.pre = voxel_grid_plan(lo, hi, inv_leaf, p.minb, divb, &ncells);
   p.cpb = 1u;
   p.nbins = 1;
   p.mul_y = p.mul_z = 0;
-  p.minb[0] = p.minb[1] = p.minb[2] = 0;
-  if (!(lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2])) {
-    p.pre = 1;
-  } else {
-    long long d[3];
-    int divb[3];
-    for (int a = 0; a < 3; ++a) {
-      d[a] = (long long)((hi[a] - lo[a]) * inv_leaf) + 1;
-      p.minb[a] = (int)floorf(lo[a] * inv_leaf);
-      divb[a] = (int)floorf(hi[a] * inv_leaf) - p.minb[a] + 1;
-    }
-    const long long ncells = (long long)divb[0] * divb[1] * divb[2];
-    if (d[0] * d[1] * d[2] > (long long)INT32_MAX) p.pre = 2;
-    else if (ncells > (long long)INT32_MAX) p.pre = 3;
-    else {
-      p.mul_y = divb[0];
-      p.mul_z = divb[0] * divb[1];
-      p.cpb = (unsigned int)((ncells + VX_BINS - 1) / VX_BINS);
-      p.nbins = (int)((ncells - 1) / p.cpb) + 1;
-    }
+  if (p.pre == kVoxelPlanDirect) {  // 1 <= ncells <= INT32_MAX
+    p.mul_y = divb[0];
+    p.mul_z = divb[0] * divb[1];
+    p.cpb = (unsigned int)((ncells + VX_BINS - 1) / VX_BINS);
+    p.nbins = (int)((ncells - 1) / p.cpb) + 1;
   }
   *plan = p;
   if (p.pre != 0) {  // nothing below runs: an empty result, the host reads `pre`
@@ -794,22 +784,23 @@ size_t voxel_temp_bytes(int n) {
 }
 
 // keys/vals: 2*n ints each (ping-pong), flags/slots: n ints each, d_n_out: 1 int (cells written).
-hipError_t launch_voxel_grid(const float4* pts, int n, float inv_leaf, const int minb[3], const int divb[3], int* keys,
+// wraps: voxel_grid_plan said kVoxelPlanWrap (divb is then modulo 2^32 and says nothing about the keys' range).
+hipError_t launch_voxel_grid(const float4* pts, int n, float inv_leaf, const int minb[3], const int divb[3], bool wraps, int* keys,
                              int* vals, int* flags, int* slots, void* temp, size_t temp_bytes, float4* out, int* d_n_out,
                              hipStream_t stream) {
   if (n <= 0) return hipMemsetAsync(d_n_out, 0, sizeof(int), stream);
   const int blocks = (n + 255) / 256;
   hipLaunchKernelGGL(voxel_key_kernel, dim3(blocks), dim3(256), 0, stream, pts, n, inv_leaf, minb[0], minb[1], minb[2], divb[0],
-                     divb[0] * divb[1], keys, vals);
+                     (int)((unsigned int)divb[0] * (unsigned int)divb[1]), keys, vals);
   // only the bits the cell indices of THIS cloud can have (+1: the sentinel of non-finite points has bit 30 set and must
   // still sort last): a raw scan at 0.2 m needs 25 of the 31, one digit pass fewer
   unsigned int end_bit = 1;
-  const long long ncells = (long long)divb[0] * divb[1] * divb[2];
+  const long long ncells = wraps ? 0x80000000ll : (long long)divb[0] * divb[1] * divb[2];  // (not wrapping: <= INT32_MAX)
   while (end_bit < 31 && (1ll << end_bit) < ncells) ++end_bit;
   end_bit = end_bit < 31 ? end_bit + 1 : 31;
   // PCL tests the float extents for overflow and indexes with the integer ones: when those are a cell wider the topmost
   // cells' index wraps negative, and PCL's sort (signed) puts them first -- the sign bit must take part then
-  if (ncells > 0x7FFFFFFFll) end_bit = 32;
+  if (wraps) end_bit = 32;
   hipError_t e = launch_radix_sort_pairs(keys, vals, n, end_bit, static_cast<int*>(temp), stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(voxel_flag_kernel, dim3(blocks), dim3(256), 0, stream, keys + n, n, flags);

@@ -108,14 +108,18 @@ int gb_issue_count(icpgpu_ctx* c, GridBuild& b) {
   double& h = b.h;
   const float *lo = b.lo, *hi = b.hi;
   GridDesc& g = b.g;
-  long long nx, ny, nz;
+  long long nx = 0, ny = 0, nz = 0;
   for (;;) {
-    nx = (long long)std::floor((hi[0] - lo[0]) / h) + 3;
-    ny = (long long)std::floor((hi[1] - lo[1]) / h) + 3;
-    nz = (long long)std::floor((hi[2] - lo[2]) / h) + 3;
+    // (the extents in double first: a box of 1e30 m has more cells than an int64 holds, and hi - lo may be inf -- neither is cast)
+    const double ex = std::floor((hi[0] - lo[0]) / h) + 3, ey = std::floor((hi[1] - lo[1]) / h) + 3, ez = std::floor((hi[2] - lo[2]) / h) + 3;
     // at most 2^14 cells per axis: the float cell coordinates the search reasons with are then exact to 2^-9 of a
     // cell, well inside the 1/64 safety margin of its distance tests (icp_grid_device.h)
-    if (nx * ny * nz <= kMaxGridCells && nx < (1 << 14) && ny < (1 << 14) && nz < (1 << 14)) break;
+    if (ex < (double)(1 << 14) && ey < (double)(1 << 14) && ez < (double)(1 << 14)) {
+      nx = (long long)ex;
+      ny = (long long)ey;
+      nz = (long long)ez;
+      if (nx * ny * nz <= kMaxGridCells) break;  // (< 2^42)
+    }
     h *= 1.15;
     if (!std::isfinite(h)) {
       b.state = GridBuild::Done;

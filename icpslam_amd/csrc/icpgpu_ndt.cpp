@@ -6,6 +6,7 @@
 // transform of the new pose.  Opt-in per context (icpgpu_set_ndt_line_search): the More-Thuente line search with its loop running,
 // whose loop trials are score-and-gradient passes (ndt_grad_kernel).  The contract, rule by rule, is DESIGN.md's NDT section.
 #include "icp_ctx.h"
+#include "icp_voxel_plan.h"
 #include "icp_trig.h"
 
 namespace icpgpu_impl {
@@ -422,15 +423,10 @@ static int ensure_ndt_cells(icpgpu_ctx* c) {
       const float leaf = (float)c->ndt_resolution;
       const float inv = 1.0f / leaf;
       NdtLattice L{};
-      long long dd[3];
-      for (int a = 0; a < 3; ++a) {
-        dd[a] = (long long)((hi[a] - lo[a]) * inv) + 1;
-        L.minb[a] = (int)std::floor(lo[a] * inv);
-        L.divb[a] = (int)std::floor(hi[a] * inv) - L.minb[a] + 1;
-      }
-      // (products in double: three extents of up to 2^31 each overflow an int64)
-      if ((double)dd[0] * (double)dd[1] * (double)dd[2] > (double)INT32_MAX ||
-          (double)L.divb[0] * (double)L.divb[1] * (double)L.divb[2] > (double)INT32_MAX)
+      // the voxel filter's plan (icp_voxel_plan.h: exact staged products, no out-of-range cast); what PCL would pass through, and an
+      // index that wraps, are refused here
+      long long ncells = 0;
+      if (voxel_grid_plan(lo, hi, inv, L.minb, L.divb, &ncells) != kVoxelPlanDirect)
         return fail(c, ICPGPU_ERR_INVALID_ARG, "NDT: the cell index overflows at resolution %g for this target", c->ndt_resolution);
       L.mul_y = L.divb[0];
       L.mul_z = L.divb[0] * L.divb[1];

@@ -1,5 +1,6 @@
 // icpgpu_voxel.cpp -- host side of the voxel-grid filter (pcl::VoxelGrid as called at icp_odometer.cpp:96-101; kernels: icp_voxel.hip).
 #include "icp_ctx.h"
+#include "icp_voxel_plan.h"
 
 
 namespace icpgpu_impl {
@@ -36,8 +37,8 @@ int voxel_filter_device(icpgpu_ctx* c, const float4* d_in, int n, float leaf, De
   // Round 6: the direct path is queued BEHIND the bounding-box pass without the host having seen the box -- the device derives the
   // filter's parameters itself (voxel_plan_kernel) -- so a scan's filter is ONE wait for the device (box, plan, counts, status and
   // the published cloud's fingerprint arrive together) where it was two.  The rare clouds that are not the direct path's (PCL's
-  // pass-through, an index that may wrap, no finite point) show in the plan; the host then goes the old way with the box it has by
-  // then.  (development flavour, ICPGPU_VOXEL_PLANNED=0: the box first, as until round 5)
+  // pass-through, an index that wraps, no finite point) show in the plan's verdict; the host then goes the old way with the box it
+  // has by then.  (development flavour, ICPGPU_VOXEL_PLANNED=0: the box first, as until round 5)
   static const bool planned_enabled = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_VOXEL_PLANNED"); return !e || std::atoi(e) != 0; }();
   const bool direct_size = !force_sort && n <= (1 << 21);
   auto direct_scratch = [&]() -> int {
@@ -65,7 +66,13 @@ int voxel_filter_device(icpgpu_ctx* c, const float4* d_in, int n, float leaf, De
   auto direct_launch = [&](const int* minb, const int* divb) -> int {
     // (the staging buffer is sized for the input: a filter's result is never longer)
     stage_points = 0;
-    if (publish && (size_t)n * sizeof(float4) <= kStageMaxBytes && !ensure_stage(c, (size_t)n * sizeof(float4))) stage_points = n;
+    if (publish && (size_t)n * sizeof(float4) <= kStageMaxBytes) {
+      if (!ensure_stage(c, (size_t)n * sizeof(float4))) stage_points = n;
+      else {  // no staging buffer: the result comes through the copy engine instead -- not this call's error
+        c->err.clear();
+        (void)hipGetLastError();
+      }
+    }
     HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
     hipError_t le = launch_voxel_grid_direct(d_in, n, inv, minb, divb, static_cast<int*>(c->vox_bins.ptr),
                                              static_cast<unsigned long long*>(c->vox_pub.ptr),
@@ -112,16 +119,16 @@ int voxel_filter_device(icpgpu_ctx* c, const float4* d_in, int n, float leaf, De
   float lo[3], hi[3];
   decode_bbox(hv, lo, hi);
   if (bbox_enc_out) std::memcpy(bbox_enc_out, hv, 6 * sizeof(int));  // the input's box: it contains every centroid
-  if (!(lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2])) return ICPGPU_OK;  // no finite point
+  // The plan -- minb, divb and the verdict -- has ONE definition (icp_voxel_plan.h: PCL's rule, defined for every box and leaf).
+  // The planned path takes the device's verdict (hv[23], voxel_plan_kernel called the same function on the same box) and derives
+  // minb / divb for the sort path only; nothing is compared, there is nothing that could disagree.
   int minb[3], divb[3];
-  long long d[3];
-  for (int a = 0; a < 3; ++a) {
-    d[a] = (long long)((hi[a] - lo[a]) * inv) + 1;
-    minb[a] = (int)std::floor(lo[a] * inv);
-    divb[a] = (int)std::floor(hi[a] * inv) - minb[a] + 1;
-  }
+  long long ncells = 0;
+  int verdict = voxel_grid_plan(lo, hi, inv, minb, divb, &ncells);
+  if (planned) verdict = hv[23];
+  if (verdict == kVoxelPlanNoFinite) return ICPGPU_OK;
   if ((rc = ensure(c, out, (size_t)n * sizeof(float4)))) return rc;
-  if (d[0] * d[1] * d[2] > (long long)INT32_MAX) {  // PCL warns and returns the input unchanged
+  if (verdict == kVoxelPlanPassThrough) {  // PCL warns and returns the input unchanged
     HIP_TRY(c, hipMemcpyAsync(out.ptr, d_in, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     *n_out = n;
@@ -133,17 +140,14 @@ int voxel_filter_device(icpgpu_ctx* c, const float4* d_in, int n, float leaf, De
   bool done = false;
   // (PCL's overflow test uses the float extents, its cell index the integer ones: when these are one cell wider the index of
   // the topmost cells can wrap in int32 and PCL -- and the sort path, on signed keys -- puts them first.  The direct path's
-  // buckets assume keys in [0, number of cells): leave that corner to the sort path.)
-  const bool keys_may_wrap = (long long)divb[0] * divb[1] * divb[2] > (long long)INT32_MAX;
+  // buckets assume keys in [0, number of cells): kVoxelPlanWrap leaves that corner to the sort path.)
+  const bool wraps = verdict == kVoxelPlanWrap;
   if (planned) {
-    // the device decided by the same arithmetic: its verdict and the host's must agree
-    const int pre = hv[23];
-    if ((pre == 0) != !keys_may_wrap) return fail(c, ICPGPU_ERR_HIP, "voxel filter: the device's plan (%d) and the host's disagree (internal error)", pre);
-    if (pre == 0) {
+    if (!wraps) {
       if ((rc = direct_time())) return rc;
       done = hv[8] == 0;
     }
-  } else if (direct_size && !keys_may_wrap) {
+  } else if (direct_size && !wraps) {
     if ((rc = direct_scratch())) return rc;
     if ((rc = direct_launch(minb, divb))) return rc;
     if ((rc = fetch_ints(c, d_ints + 6, stage_points ? 6 : 3, hv + 6))) {
@@ -164,7 +168,7 @@ int voxel_filter_device(icpgpu_ctx* c, const float4* d_in, int n, float leaf, De
     if ((rc = ensure(c, c->vox_slots, (size_t)n * sizeof(int)))) return rc;
     if ((rc = ensure(c, c->vox_temp, tb))) return rc;
     HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
-    HIP_TRY(c, launch_voxel_grid(d_in, n, inv, minb, divb, static_cast<int*>(c->vox_keys.ptr), static_cast<int*>(c->vox_vals.ptr),
+    HIP_TRY(c, launch_voxel_grid(d_in, n, inv, minb, divb, wraps, static_cast<int*>(c->vox_keys.ptr), static_cast<int*>(c->vox_vals.ptr),
                                  static_cast<int*>(c->vox_flags.ptr), static_cast<int*>(c->vox_slots.ptr), c->vox_temp.ptr, tb,
                                  static_cast<float4*>(out.ptr), d_ints + 6, c->stream));
     HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
@@ -208,6 +212,15 @@ static int fetch_filtered(icpgpu_ctx* c, float* out_xyzw, size_t m) {
 }  // namespace icpgpu_impl
 
 extern "C" {
+
+int icpgpu_voxel_plan(const float* lo3, const float* hi3, float leaf, int32_t* verdict, int32_t* minb3, int32_t* divb3) {
+  if (!lo3 || !hi3 || !verdict || !minb3 || !divb3 || !(leaf > 0.f) || !std::isfinite(leaf)) return ICPGPU_ERR_INVALID_ARG;
+  int minb[3], divb[3];
+  long long ncells = 0;
+  *verdict = icpgpu::voxel_grid_plan(lo3, hi3, 1.0f / leaf, minb, divb, &ncells);
+  for (int a = 0; a < 3; ++a) minb3[a] = minb[a], divb3[a] = divb[a];
+  return ICPGPU_OK;
+}
 
 int icpgpu_voxel_grid(icpgpu_ctx* c, const float* xyzw, size_t n, float leaf, float* out_xyzw, size_t* n_out) {
   ENTER(c);

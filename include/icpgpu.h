@@ -527,6 +527,13 @@ int icpgpu_gicp_quadratic_sums(icpgpu_ctx* ctx, const float* T, double* sums150)
  * non-finite points are skipped; if the cell index space overflows int32 the input is returned
  * unchanged (PCL's "leaf size is too small" behaviour). out_xyzw must hold n points. */
 int icpgpu_voxel_grid(icpgpu_ctx* ctx, const float* xyzw, size_t n, float leaf, float* out_xyzw, size_t* n_out);
+/* (host, no device) the filter's plan for a cloud whose finite points have the bounding box [lo3, hi3]: *verdict = 0 the cell index
+ * fits int32 and the cloud is filtered, 1 no finite point (lo > hi on an axis; empty result), 2 PCL's "leaf size is too small" (the
+ * input is returned), 3 filtered although the index wraps in int32 as PCL's does (the float extents pass PCL's test, the integer
+ * ones are a cell wider); minb3 / divb3 = PCL's min_b_ / div_b_ for 0 and 3.  The one definition the filter itself uses on host
+ * and device (icpslam_amd/csrc/icp_voxel_plan.h; DESIGN.md section 2 states the rule).  A diagnostic entry: tests check the rule
+ * with it.  leaf must be positive and finite, no pointer null: ICPGPU_ERR_INVALID_ARG otherwise. */
+int icpgpu_voxel_plan(const float* lo3, const float* hi3, float leaf, int32_t* verdict, int32_t* minb3, int32_t* divb3);
 /* two-step form for callers that size their output by the result (pcl::VoxelGrid::filter resizes `output`): pass
  * out_xyzw = NULL above -- *n_out is the number of voxels, the filtered cloud stays in HBM -- then fetch it into a
  * buffer of `capacity` >= *n_out points.  Valid until the context's next voxel-filter call. */

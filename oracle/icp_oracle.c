@@ -829,32 +829,61 @@ static int cmp_cell_pt(const void* a, const void* b) {
   return x->pt < y->pt ? -1 : (x->pt > y->pt);
 }
 
-long orc_voxel_grid(const float* in, size_t n, float leaf, float* out) {
-  if (n == 0) return 0;
+/* PCL's "leaf size is too small for the input dataset. Integer indices would overflow": 1 = the input is returned unchanged.
+ * PCL's own test, dx * dy * dz > INT32_MAX over int64 extents d = (int64)((max - min) * inv) + 1, wraps for three ordinary extents
+ * (2^22 cells each) and casts floats no integer holds.  This project's definition is PCL's wherever that
+ * arithmetic is defined and its stated intent elsewhere -- the input comes back when
+ *   the span in cells, (max - min) * inv, is NaN, infinite or 2^63 and more on an axis, or
+ *   the first or last cell, floorf(min * inv) / floorf(max * inv), is not an int32 on an axis, or
+ *   the exact product of the three extents is above INT32_MAX (128-bit arithmetic).
+ * Otherwise first[] / count[] receive min_b and div_b, the latter modulo 2^32 as int arithmetic leaves it. */
+static int vox_leaf_too_small(const float mn[3], const float mx[3], float inv, int32_t first[3], uint32_t count[3]) {
+  unsigned __int128 cells = 1;
+  for (int a = 0; a < 3; ++a) {
+    const float span = (mx[a] - mn[a]) * inv;
+    if (isnan(span) || isinf(span) || span >= 0x1p63f) return 1;
+    const float b0 = floorf(mn[a] * inv), b1 = floorf(mx[a] * inv);
+    if (isnan(b0) || isnan(b1) || b0 < -0x1p31f || b0 >= 0x1p31f || b1 < -0x1p31f || b1 >= 0x1p31f) return 1;
+    cells *= (unsigned __int128)((uint64_t)span + 1u); /* <= 2^63 each: two factors fit 128 bits, the check below keeps it so */
+    if (cells > (unsigned __int128)INT32_MAX) return 1;
+    first[a] = (int32_t)b0;
+    count[a] = (uint32_t)(int32_t)b1 - (uint32_t)first[a] + 1u;
+  }
+  return 0;
+}
+
+/* Non-finite points take no part (PCL's filter skips them in a cloud that is not dense); a pass-through returns -1 and the
+ * caller hands the input back as it is, such points included. */
+long orc_voxel_grid(const float* in, size_t n_in, float leaf, float* out) {
+  if (n_in == 0) return 0;
   float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  for (size_t i = 0; i < n; ++i)
+  size_t n = 0;
+  for (size_t i = 0; i < n_in; ++i) {
+    if (!(isfinite(in[4 * i]) && isfinite(in[4 * i + 1]) && isfinite(in[4 * i + 2]))) continue;
+    ++n;
     for (int a = 0; a < 3; ++a) {
       float v = in[4 * i + a];
       if (v < mn[a]) mn[a] = v;
       if (v > mx[a]) mx[a] = v;
     }
-  float inv = 1.0f / leaf; /* PCL: inverse_leaf_size_ = 1/leaf_size_ (float) */
-  int64_t dxyz[3];
-  int32_t minb[3], maxb[3], divb[3];
-  for (int a = 0; a < 3; ++a) {
-    dxyz[a] = (int64_t)((mx[a] - mn[a]) * inv) + 1;
-    minb[a] = (int32_t)floorf(mn[a] * inv);
-    maxb[a] = (int32_t)floorf(mx[a] * inv);
-    divb[a] = maxb[a] - minb[a] + 1;
   }
-  if (dxyz[0] * dxyz[1] * dxyz[2] > (int64_t)INT32_MAX) return -1;
-  int32_t mul[3] = {1, divb[0], divb[0] * divb[1]};
+  if (n == 0) return 0;
+  float inv = 1.0f / leaf; /* PCL: inverse_leaf_size_ = 1/leaf_size_ (float) */
+  int32_t minb[3];
+  uint32_t divb[3];
+  if (vox_leaf_too_small(mn, mx, inv, minb, divb)) return -1;
+  /* PCL indexes in int: divb_mul = (1, div_x, div_x * div_y), whatever these come to -- written modulo 2^32 here, which is what
+   * int arithmetic gives on PCL's platforms and is defined in C */
+  uint32_t mul[3] = {1u, divb[0], divb[0] * divb[1]};
   cell_pt* cp = (cell_pt*)malloc(n * sizeof(cell_pt));
-  for (size_t i = 0; i < n; ++i) {
-    int32_t c = 0;
-    for (int a = 0; a < 3; ++a) c += ((int32_t)floorf(in[4 * i + a] * inv) - minb[a]) * mul[a];
-    cp[i].cell = c;
-    cp[i].pt = (int32_t)i;
+  n = 0;
+  for (size_t i = 0; i < n_in; ++i) {
+    if (!(isfinite(in[4 * i]) && isfinite(in[4 * i + 1]) && isfinite(in[4 * i + 2]))) continue;
+    uint32_t c = 0;
+    for (int a = 0; a < 3; ++a) c += ((uint32_t)(int32_t)floorf(in[4 * i + a] * inv) - (uint32_t)minb[a]) * mul[a];
+    cp[n].cell = (int32_t)c;
+    cp[n].pt = (int32_t)i;
+    ++n;
   }
   qsort(cp, n, sizeof(cell_pt), cmp_cell_pt);
   long n_out = 0;

@@ -265,3 +265,62 @@ def p2plane_align(src, tgt, nrm, max_iterations=10, transformation_epsilon=1e-6,
         ok = np.isfinite(d2)
         out["fitness"] = float(d2[ok].astype(np.float64).mean()) if ok.any() else float(np.finfo(np.float64).max)
     return out
+
+
+# ---- pcl::VoxelGrid<PointXYZ>::filter, third statement (oracle/icp_oracle.c: orc_voxel_grid; the library: icp_voxel_plan.h) ----
+INT32_MAX = 2**31 - 1
+VOXEL_FILTER, VOXEL_NO_FINITE_POINT, VOXEL_PASS_THROUGH = "filter", "no finite point", "pass-through"
+
+
+def voxel_plan_np(lo, hi, leaf):
+    """What the filter does with a cloud whose finite points have the bounding box [lo, hi]: (verdict, min_b, div_b), the last two
+    as Python integers (None unless the verdict is VOXEL_FILTER).  float32 where PCL computes in float, Python integers -- which
+    cannot wrap -- everywhere else.  The input comes back unchanged (PCL: "leaf size is too small ... integer indices would
+    overflow") exactly when, on some axis, (hi - lo) * inv is not finite or reaches 2^63, or floor(lo * inv) / floor(hi * inv) is
+    no int32, or when the product of the extents int((hi - lo) * inv) + 1 exceeds INT32_MAX (PCL's rule where
+    PCL's int64 / int32 arithmetic is defined, its stated intent where it is not)."""
+    f32 = np.float32
+    lo, hi = np.asarray(lo, f32), np.asarray(hi, f32)
+    if not bool((lo <= hi).all()):
+        return VOXEL_NO_FINITE_POINT, None, None
+    with np.errstate(all="ignore"):
+        inv = f32(1.0) / f32(leaf)
+        span = (hi - lo) * inv
+        first, last = np.floor(lo * inv), np.floor(hi * inv)
+    assert span.dtype == first.dtype == last.dtype == f32
+    if not np.isfinite(span).all() or not np.isfinite(first).all() or not np.isfinite(last).all():
+        return VOXEL_PASS_THROUGH, None, None
+    d = [int(v) + 1 for v in span]                        # a finite float32 is an integer-valued fraction: int() is exact
+    first, last = [int(v) for v in first], [int(v) for v in last]
+    if max(d) - 1 >= 2**63 or min(first) < -2**31 or max(last) > INT32_MAX or max(first) > INT32_MAX or min(last) < -2**31:
+        return VOXEL_PASS_THROUGH, None, None
+    if d[0] * d[1] * d[2] > INT32_MAX:
+        return VOXEL_PASS_THROUGH, None, None
+    return VOXEL_FILTER, first, [b - a + 1 for a, b in zip(first, last)]
+
+
+def voxel_grid_np(cloud, leaf):
+    """The filter itself for small clouds: one float32 mean per occupied cell, members added in input order, cells ascending by
+    PCL's int32 index (reduced from the exact integer index: it wraps when the integer extents exceed the float ones)."""
+    f32 = np.float32
+    cloud = np.ascontiguousarray(cloud, f32)
+    fin = np.isfinite(cloud[:, :3]).all(axis=1)
+    pts = cloud[fin, :3]
+    if not len(pts):
+        return np.empty((0, 4), f32)
+    verdict, minb, divb = voxel_plan_np(pts.min(axis=0), pts.max(axis=0), leaf)
+    if verdict == VOXEL_PASS_THROUGH:
+        return cloud.copy()
+    inv = f32(1.0) / f32(leaf)
+    cells = {}
+    for p in pts:
+        ijk = [int(v) - m for v, m in zip(np.floor(p * inv), minb)]
+        idx = (ijk[0] + ijk[1] * divb[0] + ijk[2] * divb[0] * divb[1]) % 2**32
+        cells.setdefault(idx - 2**32 if idx >= 2**31 else idx, []).append(p)
+    out = np.ones((len(cells), 4), f32)
+    for row, key in enumerate(sorted(cells)):
+        acc = np.zeros(3, f32)
+        for p in cells[key]:
+            acc = acc + p
+        out[row, :3] = acc / f32(len(cells[key]))
+    return out

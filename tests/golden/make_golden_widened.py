@@ -49,6 +49,9 @@ def voxel_grid_np(cloud, leaf):
     minb = np.floor(mn * inv).astype(np.int64)
     maxb = np.floor(mx * inv).astype(np.int64)
     div = maxb - minb + 1
+    # PCL's "leaf size is too small" (the input comes back): the fixtures' clouds are nowhere near it -- the rule itself, for every box
+    # and leaf, is restated in oracle/icp_oracle_np.py: voxel_plan_np
+    assert int(div[0]) * int(div[1]) * int(div[2]) < 2**30
     ijk = np.floor(pts * inv).astype(np.int64) - minb
     cell = ijk[:, 0] + ijk[:, 1] * div[0] + ijk[:, 2] * div[0] * div[1]
     out = []

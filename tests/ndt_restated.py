@@ -147,6 +147,10 @@ def lattice(pts, resolution):
     leaf = F32(resolution)
     inv = F32(1.0) / leaf
     lo, hi = xyz[fin].min(axis=0), xyz[fin].max(axis=0)
+    with np.errstate(over="ignore", invalid="ignore"):
+        scaled = [F32(F32(hi[a] - lo[a]) * inv) for a in range(3)] + [F32(lo[a] * inv) for a in range(3)] + [F32(hi[a] * inv) for a in range(3)]
+    if not all(np.isfinite(v) for v in scaled):      # an extent or a bound beyond float: beyond every integer index too
+        raise Overflow(resolution)
     d = [int(F32((hi[a] - lo[a]) * inv)) + 1 for a in range(3)]
     minb = [int(np.floor(F32(lo[a] * inv))) for a in range(3)]
     divb = [int(np.floor(F32(hi[a] * inv))) - minb[a] + 1 for a in range(3)]

@@ -112,6 +112,19 @@ def test_cells_overflow_is_refused():
             assert e.value.code == _lib.ERR_INVALID_ARG
         ctx.set_ndt_params(1000.0, 0.1, 0.55)                            # a coarser lattice fits
         assert len(ctx.ndt_cells()["n_points"]) == 0
+    # extents beyond int64 on ONE axis (2e30 cells: a float-to-int64 cast of that is undefined, and negative where it is not), beyond
+    # float on one axis (hi - lo = inf), and three ordinary extents whose int64 product wraps (2^22 cells cubed, times 8): all refused
+    for box, res in (([[-1e30, 0, 0], [1e30, 1, 1]], 1.0), ([[-3e38, 0, 0], [3e38, 1, 1]], 1.0), ([[-4e4, -4e4, -4e4], [4e4, 4e4, 4e4]], 0.01)):
+        far = _cloud(box * 6)
+        with pytest.raises(nr.Overflow):
+            nr.cells(far, res)
+        with _ctx(resolution=res) as ctx:
+            ctx.set_target(far)
+            ctx.set_source(far)
+            for call in (ctx.ndt_cells, ctx.align):
+                with pytest.raises(IcpGpuError) as e:
+                    call()
+                assert e.value.code == _lib.ERR_INVALID_ARG
 
 
 # ---- derivatives ----------------------------------------------------------------------------------------------------------------
