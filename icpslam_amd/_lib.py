@@ -25,6 +25,7 @@ HEADER_VERSION = 1002          # the icpgpu.h these mirrors were written against
 NN_AUTO, NN_BRUTE, NN_GRID = 0, 1, 2
 REJECT_MEDIAN_DISTANCE, REJECT_TRIMMED, REJECT_ONE_TO_ONE = 1, 2, 3   # icpgpu_rejector_kind
 MAX_REJECTORS = 4
+SOR_MAX_K = 63                 # ICPGPU_SOR_MAX_K
 STATE_NAMES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE",
                5: "NO_CORRESPONDENCES"}
 
@@ -93,6 +94,8 @@ EXPORTS = [
     "icpgpu_ndt_line_search_replay", "icpgpu_ndt_line_search_trace",
     "icpgpu_set_correspondence_rejectors", "icpgpu_get_correspondence_rejectors", "icpgpu_correspondences", "icpgpu_rejector_stats",
     "icpgpu_set_reciprocal_correspondences", "icpgpu_get_reciprocal_correspondences", "icpgpu_reciprocal_stats",
+    "icpgpu_statistical_outlier_removal", "icpgpu_statistical_outlier_removal_view", "icpgpu_radius_outlier_removal",
+    "icpgpu_radius_outlier_removal_view", "icpgpu_outlier_stats", "icpgpu_outlier_fetch",
 ]
 
 _lib = None
@@ -183,6 +186,12 @@ def load():
     L.icpgpu_voxel_grid_fetch.argtypes = [vp, fp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.icpgpu_voxel_grid_view.argtypes = [vp, fp, C.c_size_t, C.c_float, C.POINTER(fp), C.POINTER(C.c_size_t)]
     L.icpgpu_set_source_voxel_filtered.argtypes = [vp, fp, C.c_size_t, C.c_float, C.POINTER(C.c_size_t)]
+    L.icpgpu_statistical_outlier_removal.argtypes = [vp, fp, C.c_size_t, C.c_int, C.c_double, C.c_int, fp, C.POINTER(C.c_size_t)]
+    L.icpgpu_statistical_outlier_removal_view.argtypes = [vp, fp, C.c_size_t, C.c_int, C.c_double, C.c_int, C.POINTER(fp), C.POINTER(C.c_size_t)]
+    L.icpgpu_radius_outlier_removal.argtypes = [vp, fp, C.c_size_t, C.c_double, C.c_int, C.c_int, fp, C.POINTER(C.c_size_t)]
+    L.icpgpu_radius_outlier_removal_view.argtypes = [vp, fp, C.c_size_t, C.c_double, C.c_int, C.c_int, C.POINTER(fp), C.POINTER(C.c_size_t)]
+    L.icpgpu_outlier_stats.argtypes = [vp, dp, dp, dp, C.POINTER(C.c_size_t)]
+    L.icpgpu_outlier_fetch.argtypes = [vp, C.c_size_t, fp, ip, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     pp, lp = C.POINTER(Pose), C.POINTER(C.c_long)
     L.icpgpu_pose_from_matrix.argtypes = [fp, pp]
     L.icpgpu_pose_to_matrix.argtypes = [pp, fp]

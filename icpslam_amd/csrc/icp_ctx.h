@@ -389,6 +389,16 @@ struct icpgpu_ctx {
   size_t vox_bins_zeroed_cap = 0;
   void* vox_pub_zeroed = nullptr;
   size_t vox_pub_zeroed_cap = 0;
+  // the outlier filters (icpgpu_outlier.cpp): the filtered cloud is neither the source nor the target -- its own buffer, its own
+  // grid, its own scratch -- and what the observers (icpgpu_outlier_stats / _fetch) report of the last call
+  struct Outlier {
+    Cloud cloud;
+    GridIndex grid;
+    DeviceBuf measure, flags, pos, scan, kept, far, ints;
+    int kind = 0;  // 0 none (or the last call was refused), 1 SOR, 2 ROR
+    size_t n_in = 0, n_kept = 0, n_valid = 0;
+    double mean = 0.0, stddev = 0.0, threshold = 0.0;
+  } outlier;
   std::vector<icpgpu_ctx*> workers;  // align_batch: one sub-context (own stream + scratch) per host worker thread
   DeviceBuf batch_table;             // lock-step batch: the BatchPair table of the group this context leads
   std::atomic<size_t> batch_table_cells{0};   // align_batch: the largest cell table any worker has needed (icpgpu_index.cpp)

@@ -514,4 +514,21 @@ hipError_t launch_voxel_grid_direct(const float4* pts, int n, float inv_leaf, co
 // plan[8..13] = the box, d_bbox6 itself is left as bbox_init_kernel leaves it: the next launch_bbox on it may skip its init)
 // (clear_word, optional: a 64-bit word of device memory the last kernel sets to zero -- launch_publish_cloud's accumulator)
 
+// ---- outlier removal (icp_outlier.hip): pcl::StatisticalOutlierRemoval / pcl::RadiusOutlierRemoval -----------------------------
+// (sorted, cell_start, g, n_binned: the cloud's own grid, or sorted == null when it has none)
+// dist[i] = PCL's mean distance to the mean_k nearest neighbours (0 for a non-finite point); far: n_binned + 2 ints of scratch.
+// Without a grid every point takes the whole-cloud kernel: the caller caps n (kGicpCovFarMost).
+hipError_t launch_sor_distances(const float4* cloud, int n, const float4* sorted, const int* cell_start, const GridDesc& g, int n_binned,
+                                int mean_k, float* dist, int* far, hipStream_t stream);
+// stats (4 doubles) = mean, stddev, threshold, n_valid over dist[]; flags[i] = 1 where point i is kept
+hipError_t launch_sor_flags(const float4* cloud, const float* dist, int n, double stddev_mult, int negative, double* stats, int* flags,
+                            hipStream_t stream);
+// measure[i] = (float)(finite points j with d2(i, j) < r2) and flags[i]; brute: no grid, every point against the whole cloud
+hipError_t launch_ror_counts(const float4* cloud, int n, const float4* sorted, const int* cell_start, const GridDesc& g, int n_binned, float r2,
+                             int min_pts, int negative, bool brute, float* measure, int* flags, hipStream_t stream);
+// the flagged points in input order into out (device-visible memory, n points of room), their indices into kept, their number
+// into *n_kept; pos: n ints, scan_scratch: exclusive_scan_scratch_ints(n) ints
+hipError_t launch_outlier_compact(const float4* cloud, int n, const int* flags, int* pos, int* scan_scratch, float4* out, int* kept, int* n_kept,
+                                  hipStream_t stream);
+
 }  // namespace icpgpu

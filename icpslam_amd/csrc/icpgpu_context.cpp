@@ -667,7 +667,10 @@ int icpgpu_destroy(icpgpu_ctx* c) {
                        &c->map.flags, &c->map.rank, &c->map.temp, &c->map.counter, &c->map.nn_keys, &c->map.first_user,
                        &c->map.uflags, &c->map.urank, &c->map.uniq_index, &c->map.uniq.buf})
     release(*b);
-  for (GridIndex* G : {&c->grid, &c->src_grid, &c->map.grid}) {
+  for (DeviceBuf* b : {&c->outlier.cloud.buf, &c->outlier.measure, &c->outlier.flags, &c->outlier.pos, &c->outlier.scan, &c->outlier.kept,
+                       &c->outlier.far, &c->outlier.ints})
+    release(*b);
+  for (GridIndex* G : {&c->grid, &c->src_grid, &c->map.grid, &c->outlier.grid}) {
     release(G->sorted);
     release(G->cell_start);
     release(G->cell_of_point);

@@ -434,6 +434,47 @@ class Context:
         self.n_source = int(n_out.value)
         return self.n_source
 
+    # outlier removal (pcl::StatisticalOutlierRemoval / pcl::RadiusOutlierRemoval; rules: include/icpgpu.h) -------------
+    def _outlier(self, view: bool, fn, cloud, *args) -> np.ndarray:
+        cloud = _as_cloud(cloud)
+        n_out = C.c_size_t()
+        if view:
+            ptr = C.POINTER(C.c_float)()
+            self._check(fn(self._h, _fp(cloud), cloud.shape[0], *args, C.byref(ptr), C.byref(n_out)))
+            if n_out.value == 0:
+                return np.empty((0, 4), np.float32)
+            return np.ctypeslib.as_array(ptr, shape=(n_out.value, 4)).copy()
+        out = np.empty_like(cloud)
+        self._check(fn(self._h, _fp(cloud), cloud.shape[0], *args, _fp(out), C.byref(n_out)))
+        return out[: n_out.value].copy()
+
+    def statistical_outlier_removal(self, cloud, mean_k: int, stddev_mult: float, negative: bool = False, view: bool = False) -> np.ndarray:
+        """The kept points in input order (view: through icpgpu_statistical_outlier_removal_view, copied out of the staging buffer)."""
+        fn = self._L.icpgpu_statistical_outlier_removal_view if view else self._L.icpgpu_statistical_outlier_removal
+        return self._outlier(view, fn, cloud, int(mean_k), float(stddev_mult), int(bool(negative)))
+
+    def radius_outlier_removal(self, cloud, radius: float, min_pts: int, negative: bool = False, view: bool = False) -> np.ndarray:
+        fn = self._L.icpgpu_radius_outlier_removal_view if view else self._L.icpgpu_radius_outlier_removal
+        return self._outlier(view, fn, cloud, float(radius), int(min_pts), int(bool(negative)))
+
+    def outlier_stats(self) -> dict:
+        """mean, stddev, threshold (float64) and n_valid of the context's last statistical filter call."""
+        m, s, t, nv = C.c_double(), C.c_double(), C.c_double(), C.c_size_t()
+        self._check(self._L.icpgpu_outlier_stats(self._h, C.byref(m), C.byref(s), C.byref(t), C.byref(nv)))
+        return {"mean": m.value, "stddev": s.value, "threshold": t.value, "n_valid": int(nv.value)}
+
+    def outlier_fetch(self) -> dict:
+        """The last outlier filter call's measure per input point (SOR: dist; ROR: k as float32) and the kept / removed indices."""
+        n_in, n_kept = C.c_size_t(), C.c_size_t()
+        self._check(self._L.icpgpu_outlier_fetch(self._h, 0, None, None, C.byref(n_in), C.byref(n_kept)))  # (both NULL: the sizes alone)
+        measure = np.zeros(n_in.value, np.float32)
+        kept = np.zeros(n_kept.value, np.int32)
+        self._check(self._L.icpgpu_outlier_fetch(self._h, n_in.value, _fp(measure), kept.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n_in),
+                                                 C.byref(n_kept)))
+        mask = np.ones(n_in.value, bool)
+        mask[kept] = False
+        return {"measure": measure, "kept": kept, "removed": np.flatnonzero(mask).astype(np.int32)}
+
     # measurement -----------------------------------------------------------------------------------------------
     def calibrate(self) -> int:
         """icpgpu_calibrate: time GICP's two inner solvers on the clouds this context holds and keep the faster (GICP_SOLVER_*)."""
@@ -581,6 +622,89 @@ class CorrespondenceRejectorTrimmed(CorrespondenceRejector):
 
 class CorrespondenceRejectorOneToOne(CorrespondenceRejector):
     KIND = _lib.REJECT_ONE_TO_ONE
+
+
+class _OutlierFilter:
+    """What pcl::StatisticalOutlierRemoval and pcl::RadiusOutlierRemoval share: the input cloud, `negative`, the removed indices."""
+
+    def __init__(self, device_id: int = 0):
+        self._ctx = Context(device_id)
+        self._cloud = np.empty((0, 4), np.float32)
+        self._negative = False
+        self._removed = np.empty(0, np.int32)
+
+    def setInputCloud(self, cloud):
+        self._cloud = _as_cloud(cloud)
+
+    def setNegative(self, negative: bool):
+        self._negative = bool(negative)
+
+    def getNegative(self) -> bool:
+        return self._negative
+
+    def getRemovedIndices(self) -> np.ndarray:
+        return self._removed
+
+    def _run(self, cloud) -> np.ndarray:
+        raise NotImplementedError
+
+    def filter(self) -> np.ndarray:
+        """The filtered cloud; a refused call returns an empty one, as PCL's error path leaves `output`."""
+        self._removed = np.empty(0, np.int32)
+        try:
+            out = self._run(self._cloud)
+        except IcpGpuError:
+            return np.empty((0, 4), np.float32)
+        self._removed = self._ctx.outlier_fetch()["removed"]
+        return out
+
+
+class StatisticalOutlierRemoval(_OutlierFilter):
+    """pcl::StatisticalOutlierRemoval<PointXYZ> (PCL's defaults: mean_k 1, stddev_mult 0)."""
+
+    def __init__(self, device_id: int = 0):
+        super().__init__(device_id)
+        self._mean_k = 1
+        self._stddev_mult = 0.0
+
+    def setMeanK(self, k: int):
+        self._mean_k = int(k)
+
+    def getMeanK(self) -> int:
+        return self._mean_k
+
+    def setStddevMulThresh(self, m: float):
+        self._stddev_mult = float(m)
+
+    def getStddevMulThresh(self) -> float:
+        return self._stddev_mult
+
+    def _run(self, cloud) -> np.ndarray:
+        return self._ctx.statistical_outlier_removal(cloud, self._mean_k, self._stddev_mult, self._negative, view=True)
+
+
+class RadiusOutlierRemoval(_OutlierFilter):
+    """pcl::RadiusOutlierRemoval<PointXYZ> (PCL's defaults: radius 0, min_pts 1)."""
+
+    def __init__(self, device_id: int = 0):
+        super().__init__(device_id)
+        self._radius = 0.0
+        self._min_pts = 1
+
+    def setRadiusSearch(self, r: float):
+        self._radius = float(r)
+
+    def getRadiusSearch(self) -> float:
+        return self._radius
+
+    def setMinNeighborsInRadius(self, n: int):
+        self._min_pts = int(n)
+
+    def getMinNeighborsInRadius(self) -> int:
+        return self._min_pts
+
+    def _run(self, cloud) -> np.ndarray:
+        return self._ctx.radius_outlier_removal(cloud, self._radius, self._min_pts, self._negative, view=True)
 
 
 class IterativeClosestPoint:

@@ -53,7 +53,8 @@ extern "C" {
  * icpgpu_get_ndt_line_search, icpgpu_ndt_gradient, icpgpu_ndt_line_search_replay, icpgpu_ndt_line_search_trace (no struct changed); also added under
  * 1.2: the correspondence rejectors -- icpgpu_rejector, icpgpu_set_correspondence_rejectors, icpgpu_get_correspondence_rejectors,
  * icpgpu_correspondences, icpgpu_rejector_stats, and reciprocal correspondences -- icpgpu_set_reciprocal_correspondences,
- * icpgpu_get_reciprocal_correspondences, icpgpu_reciprocal_stats (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
+ * icpgpu_get_reciprocal_correspondences, icpgpu_reciprocal_stats, and the outlier filters -- icpgpu_statistical_outlier_removal,
+ * icpgpu_radius_outlier_removal, their _view forms, icpgpu_outlier_stats, icpgpu_outlier_fetch (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
  * icpgpu_profile.gicp_quadratic_solves; 0.3 icpgpu_profile (sources_adopted, gicp_host_solves, gicp_solver_choice). */
 
@@ -547,6 +548,55 @@ int icpgpu_voxel_grid_view(icpgpu_ctx* ctx, const float* xyzw, size_t n, float l
 /* the odometer's pre-step fused with setInputSource: upload, filter on the device, and make the
  * filtered cloud the source without a round trip to the host (icp_odometer.cpp:177 then :193). */
 int icpgpu_set_source_voxel_filtered(icpgpu_ctx* ctx, const float* xyzw, size_t n, float leaf, size_t* n_out);
+
+/* ---- outlier removal (added under 1.2) ---------------------------------------------------------------------------- */
+/* replaces pcl::StatisticalOutlierRemoval<PointXYZ>::filter and pcl::RadiusOutlierRemoval<PointXYZ>::filter (PCL 1.8), the filters a
+ * LIDAR front end puts between VoxelGrid and the registration.  The rules below restate PCL 1.8; parity with PCL binaries is
+ * unpinned, as for every solver here (tests/outlier_restated.py is what the kernels are compared with, bit for bit).
+ * COMMON.  Points are float4; a point is finite when x, y and z are.  d2(i, j) is the squared distance of DESIGN.md section 3 with no
+ * transform: dx = q.x - p.x, ...; d2 = fma(dz, dz, fma(dy, dy, dx * dx)) in float32.  Only finite points are searchable.  The output
+ * is the kept points in input order (copyPointCloud over the kept indices), the w component carried through.
+ * STATISTICAL (mean_k, stddev_mult, negative; PCL's constructor defaults 1, 0.0, false).  For a finite point i take the mean_k + 1
+ * smallest d2(i, j) over all finite j, i itself included; drop the smallest (PCL's nn_dists[0], the query); add sqrtf (float32,
+ * correctly rounded) of the rest in ascending order into a double; divide by mean_k in double and round to float32: dist[i].  Only
+ * the multiset of distances enters: there is no tie rule to define.  A non-finite point gets dist = 0 and is not counted in n_valid
+ * (PCL's behaviour: such a point compares against the threshold like any other, so it usually stays).  mean = sum / n_valid,
+ * var = (sq_sum - sum * sum / n_valid) / (n_valid - 1), stddev = sqrt(var), threshold = mean + stddev_mult * stddev, all float64,
+ * IEEE, each operation rounded on its own.  sum and sq_sum are the EXACT sums of dist[i] and dist[i] * dist[i] (exact in float64)
+ * over all i, rounded once -- a stated deviation: PCL adds sequentially in index order.  Point i is removed when
+ * (!negative && dist[i] > threshold) || (negative && dist[i] <= threshold), dist widened to double, IEEE comparisons: a NaN
+ * threshold (a variance rounded below zero) removes nothing in either mode.
+ *   DEVIATION 1: fewer than mean_k + 1 finite points is ICPGPU_ERR_INVALID_ARG (PCL reads past the end of nn_dists there).
+ *   DEVIATION 2: mean_k outside 1 .. ICPGPU_SOR_MAX_K (one candidate per lane of a wave) is ICPGPU_ERR_INVALID_ARG.
+ * A cloud the k-NN grid cannot index (tight clusters in a wide volume) is searched without it up to 65536 points, as GICP's
+ * covariances are; beyond that ICPGPU_ERR_UNSUPPORTED.
+ * RADIUS (radius, min_pts, negative; PCL's defaults 0.0, 1, false).  r2 = (float)(radius * radius), the product in double
+ * (KdTreeFLANN::radiusSearch).  For a finite point, k = the number of finite j, itself included, with d2(i, j) < r2 -- strict, as in
+ * FLANN's radius result set.  A non-finite point has k = 0 (DEVIATION: PCL asserts there).  Point i is removed when
+ * (!negative && k <= min_pts) || (negative && k > min_pts).  A radius that is not finite or is negative, or min_pts < 0, is
+ * ICPGPU_ERR_INVALID_ARG.  radius = 0 is legal: r2 = 0 and k = 0 for every point.
+ * n = 0 is ICPGPU_OK with *n_out = 0.  out_xyzw must hold n points (NULL: only the count; icpgpu_outlier_fetch has the indices).  A
+ * view points at *n_out points in the context's pinned staging buffer and is valid until the context's next call, like the voxel
+ * filter's.  The filters leave the context's source, target, grids, covariances, NDT cells, voxel-filter result and recognition
+ * fingerprints as they were: an alignment after a filter call returns the bits it returned before it.  Not provided:
+ * keep_organized / setUserFilterValue. */
+#define ICPGPU_SOR_MAX_K 63
+int icpgpu_statistical_outlier_removal(icpgpu_ctx* ctx, const float* xyzw, size_t n, int mean_k, double stddev_mult, int negative,
+                                       float* out_xyzw, size_t* n_out);
+int icpgpu_statistical_outlier_removal_view(icpgpu_ctx* ctx, const float* xyzw, size_t n, int mean_k, double stddev_mult, int negative,
+                                            const float** view_xyzw, size_t* n_out);
+int icpgpu_radius_outlier_removal(icpgpu_ctx* ctx, const float* xyzw, size_t n, double radius, int min_pts, int negative,
+                                  float* out_xyzw, size_t* n_out);
+int icpgpu_radius_outlier_removal_view(icpgpu_ctx* ctx, const float* xyzw, size_t n, double radius, int min_pts, int negative,
+                                       const float** view_xyzw, size_t* n_out);
+/* observers of the LAST outlier filter call on this context (what getRemovedIndices and a debugger would want); a refused call
+ * leaves nothing to observe (ICPGPU_ERR_INVALID_ARG).  icpgpu_outlier_stats: the statistical filter's mean, stddev, threshold and
+ * n_valid (zeroes after n = 0); after the radius filter ICPGPU_ERR_INVALID_ARG.  Any output may be NULL. */
+int icpgpu_outlier_stats(const icpgpu_ctx* ctx, double* mean, double* stddev, double* threshold, size_t* n_valid);
+/* measure[i] for every input point (STATISTICAL: dist[i]; RADIUS: (float)k) and the kept points' indices, ascending.  *n_in and
+ * *n_kept are always set.  measure / kept_index may be NULL; with both NULL the call only reports the sizes (ICPGPU_OK whatever the
+ * capacity).  Otherwise nothing is copied when n_in exceeds capacity (ICPGPU_ERR_INVALID_ARG). */
+int icpgpu_outlier_fetch(icpgpu_ctx* ctx, size_t capacity, float* measure, int32_t* kept_index, size_t* n_in, size_t* n_kept);
 
 /* ---- the mapper's target: a one-point-per-voxel map and its "nn cloud"  -------- */
 /* replaces OctreeMapper's pcl::octree::OctreePointCloudSearch map

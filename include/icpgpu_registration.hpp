@@ -560,6 +560,93 @@ class VoxelGrid {
   float leaf_ = 0.1f;
 };
 
+// What pcl::StatisticalOutlierRemoval and pcl::RadiusOutlierRemoval share (the filters a front end puts between VoxelGrid and the
+// registration): the input cloud, `negative`, filter(output) from the view, getRemovedIndices().  Rules and deviations:
+// include/icpgpu.h, "outlier removal".  A refused call leaves `output` empty, as PCL's error path does.
+template <class CloudT, class Derived>
+class OutlierFilterBase {
+ public:
+  explicit OutlierFilterBase(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {}
+  template <class CloudPtr>
+  void setInputCloud(const CloudPtr& cloud) { input_ = &*cloud; }
+  void setNegative(bool negative) { negative_ = negative; }
+  bool getNegative() const { return negative_; }
+  // the indices of the points the last filter() removed, ascending (PCL: extract_removed_indices = true, then getRemovedIndices())
+  const std::vector<int>& getRemovedIndices() const { return removed_; }
+  void filter(CloudT& output) {
+    removed_.clear();
+    if (!input_) return;
+    typedef typename std::remove_reference<decltype(output.points[0])>::type PointT;
+    static_assert(sizeof(PointT) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+    const std::size_t n = input_->points.size();
+    std::size_t m = 0;
+    const float* view = nullptr;
+    const int rc = static_cast<Derived*>(this)->run(ctx_, n ? reinterpret_cast<const float*>(&input_->points[0]) : nullptr, n, &view, &m);
+    if (rc == ICPGPU_OK && m) {
+      const PointT* first = reinterpret_cast<const PointT*>(view);
+      output.points.assign(first, first + m);
+    } else {
+      output.points.resize(0);
+    }
+    detail::set_cloud_shape(output, output.points.size(), 0);
+    if (rc != ICPGPU_OK || n == 0) return;
+    std::vector<int32_t> kept(m);
+    std::size_t n_in = 0, n_kept = 0;
+    if (icpgpu_outlier_fetch(ctx_, n, nullptr, m ? &kept[0] : nullptr, &n_in, &n_kept) != ICPGPU_OK) return;
+    removed_.reserve(n - m);
+    std::size_t k = 0;
+    for (std::size_t i = 0; i < n; ++i) {
+      if (k < m && (std::size_t)kept[k] == i) ++k;
+      else removed_.push_back((int)i);
+    }
+  }
+
+ protected:
+  detail::ContextPtr ctx_holder_;
+  icpgpu_ctx* ctx_;
+  const CloudT* input_ = nullptr;
+  bool negative_ = false;
+  std::vector<int> removed_;
+};
+
+//   pcl::StatisticalOutlierRemoval<pcl::PointXYZ> sor;  ->  icpgpu::StatisticalOutlierRemoval<pcl::PointCloud<pcl::PointXYZ>> sor;
+//   sor.setInputCloud(in); sor.setMeanK(50); sor.setStddevMulThresh(1.0); sor.filter(out);
+template <class CloudT>
+class StatisticalOutlierRemoval : public OutlierFilterBase<CloudT, StatisticalOutlierRemoval<CloudT>> {
+ public:
+  explicit StatisticalOutlierRemoval(int device = 0) : OutlierFilterBase<CloudT, StatisticalOutlierRemoval<CloudT>>(device) {}
+  void setMeanK(int k) { mean_k_ = k; }
+  int getMeanK() const { return mean_k_; }
+  void setStddevMulThresh(double m) { stddev_mult_ = m; }
+  double getStddevMulThresh() const { return stddev_mult_; }
+  int run(icpgpu_ctx* ctx, const float* xyzw, std::size_t n, const float** view, std::size_t* m) {
+    return icpgpu_statistical_outlier_removal_view(ctx, xyzw, n, mean_k_, stddev_mult_, this->negative_ ? 1 : 0, view, m);
+  }
+
+ private:
+  int mean_k_ = 1;  // (PCL's constructor defaults)
+  double stddev_mult_ = 0.0;
+};
+
+//   pcl::RadiusOutlierRemoval<pcl::PointXYZ> ror;  ->  icpgpu::RadiusOutlierRemoval<pcl::PointCloud<pcl::PointXYZ>> ror;
+//   ror.setInputCloud(in); ror.setRadiusSearch(0.3); ror.setMinNeighborsInRadius(5); ror.filter(out);
+template <class CloudT>
+class RadiusOutlierRemoval : public OutlierFilterBase<CloudT, RadiusOutlierRemoval<CloudT>> {
+ public:
+  explicit RadiusOutlierRemoval(int device = 0) : OutlierFilterBase<CloudT, RadiusOutlierRemoval<CloudT>>(device) {}
+  void setRadiusSearch(double r) { radius_ = r; }
+  double getRadiusSearch() const { return radius_; }
+  void setMinNeighborsInRadius(int n) { min_pts_ = n; }
+  int getMinNeighborsInRadius() const { return min_pts_; }
+  int run(icpgpu_ctx* ctx, const float* xyzw, std::size_t n, const float** view, std::size_t* m) {
+    return icpgpu_radius_outlier_removal_view(ctx, xyzw, n, radius_, min_pts_, this->negative_ ? 1 : 0, view, m);
+  }
+
+ private:
+  double radius_ = 0.0;  // (PCL's constructor defaults)
+  int min_pts_ = 1;
+};
+
 // The mapper's map (/root/reference/src/icpslam/octree_mapper.cpp:55-90): replaces the pair
 //   pcl::octree::OctreePointCloudSearch<pcl::PointXYZ>::Ptr map_octree_;  pcl::PointCloud<pcl::PointXYZ>::Ptr map_cloud_;
 // Poses are the float 4x4 that pcl_ros::transformPointCloud applies (icpgpu_pose_to_matrix gives it for a Pose6DOF);
