@@ -26,6 +26,7 @@ NN_AUTO, NN_BRUTE, NN_GRID = 0, 1, 2
 REJECT_MEDIAN_DISTANCE, REJECT_TRIMMED, REJECT_ONE_TO_ONE = 1, 2, 3   # icpgpu_rejector_kind
 MAX_REJECTORS = 4
 SOR_MAX_K = 63                 # ICPGPU_SOR_MAX_K
+SEARCH_MAX_K = 64              # ICPGPU_SEARCH_MAX_K
 STATE_NAMES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE",
                5: "NO_CORRESPONDENCES"}
 
@@ -96,6 +97,7 @@ EXPORTS = [
     "icpgpu_set_reciprocal_correspondences", "icpgpu_get_reciprocal_correspondences", "icpgpu_reciprocal_stats",
     "icpgpu_statistical_outlier_removal", "icpgpu_statistical_outlier_removal_view", "icpgpu_radius_outlier_removal",
     "icpgpu_radius_outlier_removal_view", "icpgpu_outlier_stats", "icpgpu_outlier_fetch",
+    "icpgpu_search_set_input", "icpgpu_search_size", "icpgpu_search_knn", "icpgpu_search_radius",
 ]
 
 _lib = None
@@ -192,6 +194,10 @@ def load():
     L.icpgpu_radius_outlier_removal_view.argtypes = [vp, fp, C.c_size_t, C.c_double, C.c_int, C.c_int, C.POINTER(fp), C.POINTER(C.c_size_t)]
     L.icpgpu_outlier_stats.argtypes = [vp, dp, dp, dp, C.POINTER(C.c_size_t)]
     L.icpgpu_outlier_fetch.argtypes = [vp, C.c_size_t, fp, ip, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.icpgpu_search_set_input.argtypes = [vp, fp, C.c_size_t]
+    L.icpgpu_search_size.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.icpgpu_search_knn.argtypes = [vp, fp, C.c_size_t, C.c_int, ip, fp, ip]
+    L.icpgpu_search_radius.argtypes = [vp, fp, C.c_size_t, C.c_double, C.c_int, C.c_size_t, C.POINTER(C.c_int64), ip, fp, C.POINTER(C.c_size_t)]
     pp, lp = C.POINTER(Pose), C.POINTER(C.c_long)
     L.icpgpu_pose_from_matrix.argtypes = [fp, pp]
     L.icpgpu_pose_to_matrix.argtypes = [pp, fp]

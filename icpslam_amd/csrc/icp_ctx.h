@@ -399,6 +399,16 @@ struct icpgpu_ctx {
     size_t n_in = 0, n_kept = 0, n_valid = 0;
     double mean = 0.0, stddev = 0.0, threshold = 0.0;
   } outlier;
+  // the neighbour search (icpgpu_search.cpp): the search cloud is neither the source, the target nor the filters' cloud -- its own
+  // buffer and its own k-NN grid, replaced as a whole by icpgpu_search_set_input -- and the scratch of a query call
+  struct Search {
+    Cloud cloud;
+    GridIndex grid;
+    bool set = false;   // a search cloud is in place (n = 0 included)
+    size_t n = 0;
+    int n_finite = 0;
+    DeviceBuf queries, idx, d2, n_found, far, counts, longs, row_start, scratch_start, scan, scratch, totals, row_start64;
+  } search;
   std::vector<icpgpu_ctx*> workers;  // align_batch: one sub-context (own stream + scratch) per host worker thread
   DeviceBuf batch_table;             // lock-step batch: the BatchPair table of the group this context leads
   std::atomic<size_t> batch_table_cells{0};   // align_batch: the largest cell table any worker has needed (icpgpu_index.cpp)
@@ -628,6 +638,8 @@ int reciprocal_run(icpgpu_ctx* c, const Xform& T, unsigned long long* keys, floa
 int reject_run_chain(icpgpu_ctx* c, unsigned long long* keys, float thr);
 int reject_fetch_stats(icpgpu_ctx* c);
 int sweep_issue_rejected(icpgpu_ctx* c, const Xform& T, float thr, SweepTicket& tk);
+// icpgpu_outlier.cpp: a cloud's k-NN grid, its first cell size taken from the cloud's own box (the filters and the neighbour search)
+int build_knn_grid(icpgpu_ctx* c, const Cloud& cloud, GridIndex& G);
 // icpgpu_ndt.cpp
 int align_ndt(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitness, icpgpu_result* res);
 

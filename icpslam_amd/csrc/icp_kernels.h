@@ -531,4 +531,25 @@ hipError_t launch_ror_counts(const float4* cloud, int n, const float4* sorted, c
 hipError_t launch_outlier_compact(const float4* cloud, int n, const int* flags, int* pos, int* scan_scratch, float4* out, int* kept, int* n_kept,
                                   hipStream_t stream);
 
+// ---- neighbour search (icp_search.hip): pcl::search::KdTree's nearestKSearch / radiusSearch ------------------------------------
+// (cloud, n: the search cloud; sorted, cell_start, g: its k-NN grid, or sorted == null when it has none -- the caller caps n then)
+// Row q of idx / d2 (k entries each, k <= 64) = the k smallest keys (d2 bits << 32 | index) of queries[q] over the finite cloud
+// points, ascending, padded with -1 / +inf; n_found[q] = how many there are.  far: n_q + 2 ints of scratch.
+hipError_t launch_search_knn(const float4* queries, int n_q, const float4* cloud, int n, const float4* sorted, const int* cell_start,
+                             const GridDesc& g, int k, int32_t* idx, float* d2, int32_t* n_found, int* far, hipStream_t stream);
+// Radius search, first half: per query the number of finite cloud points with d2 < r2, cut at max_nn when max_nn > 0, and its
+// exclusive scan row_start (n_q + 1 ints; row_start64: the same as int64).  shells: the cube of that many cells around a query's
+// cell contains its ball (< 0: sweep the whole cloud instead).  counts, longs, scratch_start: n_q + 1 ints each; scan_scratch:
+// exclusive_scan_scratch_ints(n_q + 1); totals: [0] the rows' total length, [1] the 64-bit words of scratch the second half needs
+// -- 64-bit sums: a total that does not fit an int32 makes row_start meaningless and the caller must stop there.
+static constexpr int kSearchRadiusShells = 8;  // a ball of more cells than this (17^3 in the cube) is searched without the grid
+hipError_t launch_search_radius_count(const float4* queries, int n_q, const float4* cloud, int n, const float4* sorted, const int* cell_start,
+                                      const GridDesc& g, int shells, float r2, int max_nn, int* counts, int* longs, int* row_start,
+                                      int* scratch_start, int* scan_scratch, unsigned long long* totals, long long* row_start64,
+                                      hipStream_t stream);
+// ... second half: row q of idx / d2 = [row_start[q], row_start[q + 1]), ascending by key
+hipError_t launch_search_radius_fill(const float4* queries, int n_q, const float4* cloud, int n, const float4* sorted, const int* cell_start,
+                                     const GridDesc& g, int shells, float r2, const int* row_start, const int* scratch_start,
+                                     unsigned long long* scratch, int32_t* idx, float* d2, hipStream_t stream);
+
 }  // namespace icpgpu

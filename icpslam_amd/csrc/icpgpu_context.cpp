@@ -670,7 +670,11 @@ int icpgpu_destroy(icpgpu_ctx* c) {
   for (DeviceBuf* b : {&c->outlier.cloud.buf, &c->outlier.measure, &c->outlier.flags, &c->outlier.pos, &c->outlier.scan, &c->outlier.kept,
                        &c->outlier.far, &c->outlier.ints})
     release(*b);
-  for (GridIndex* G : {&c->grid, &c->src_grid, &c->map.grid, &c->outlier.grid}) {
+  for (DeviceBuf* b : {&c->search.cloud.buf, &c->search.queries, &c->search.idx, &c->search.d2, &c->search.n_found, &c->search.far,
+                       &c->search.counts, &c->search.longs, &c->search.row_start, &c->search.scratch_start, &c->search.scan,
+                       &c->search.scratch, &c->search.totals, &c->search.row_start64})
+    release(*b);
+  for (GridIndex* G : {&c->grid, &c->src_grid, &c->map.grid, &c->outlier.grid, &c->search.grid}) {
     release(G->sorted);
     release(G->cell_start);
     release(G->cell_of_point);

@@ -29,6 +29,8 @@ int count_finite_host(const float* xyzw, size_t n) {
 // ~32 others; the neighbours are exact whatever the cells), but the first cell size comes from the CLOUD -- its box filled evenly
 // would put 32 points in a cell of that size -- and not from the registration's correspondence gate, which has nothing to do with
 // a filter.  The count pass then corrects it once, as for every k-NN grid (down to a 16th for points on surfaces, up to 8 times).
+// (Shared with the neighbour search, icpgpu_search.cpp: declared in icp_ctx.h.)
+}  // namespace
 int build_knn_grid(icpgpu_ctx* c, const Cloud& cloud, GridIndex& G) {
   constexpr double kKnnPopulation = 32.0;
   GridBuild b;
@@ -58,6 +60,7 @@ int build_knn_grid(icpgpu_ctx* c, const Cloud& cloud, GridIndex& G) {
   }
   return rc;
 }
+namespace {
 
 // One filter call: upload, the cloud's own grid, the measure, flags, compaction.  The kept points are written by the last kernel
 // into the pinned staging buffer, in front of the count the host waits for -- one wait per call, as icpgpu_voxel_grid_view has it.

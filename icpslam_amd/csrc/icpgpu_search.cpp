@@ -1,0 +1,211 @@
+// icpgpu_search.cpp -- host side of the neighbour search (pcl::search::KdTree / pcl::KdTreeFLANN: nearestKSearch, radiusSearch;
+// rules: include/icpgpu.h "neighbour search"; kernels: icp_search.hip).
+#include "icp_ctx.h"
+
+namespace icpgpu_impl {
+namespace {
+
+int count_finite(const float* xyzw, size_t n) {
+  int nf = 0;
+  for (size_t i = 0; i < n; ++i) nf += std::isfinite(xyzw[4 * i]) && std::isfinite(xyzw[4 * i + 1]) && std::isfinite(xyzw[4 * i + 2]);
+  return nf;
+}
+
+// what a query call needs of the search cloud
+struct SearchView {
+  const float4* cloud = nullptr;
+  int n = 0;
+  const float4* sorted = nullptr;  // null: no grid
+  const int* cell_start = nullptr;
+  GridDesc g{};
+};
+
+SearchView view_of(const icpgpu_ctx* c) {
+  const auto& S = c->search;
+  SearchView v;
+  v.cloud = S.cloud.data();
+  v.n = (int)S.n;
+  if (S.n && S.grid.usable) {
+    v.sorted = static_cast<const float4*>(S.grid.sorted.ptr);
+    v.cell_start = static_cast<const int*>(S.grid.cell_start.ptr);
+    v.g = S.grid.g;
+  }
+  return v;
+}
+
+// the queries of a call in device memory: the caller's (uploaded into the call's scratch) or the search cloud's own points
+int stage_queries(icpgpu_ctx* c, const char* what, const float* queries_xyzw, size_t n_q, const float4*& d_queries) {
+  auto& S = c->search;
+  if (!S.set) return fail(c, ICPGPU_ERR_INVALID_ARG, "%s: no search cloud (icpgpu_search_set_input)", what);
+  if (!queries_xyzw) {
+    if (n_q != 0 && n_q != S.n) return fail(c, ICPGPU_ERR_INVALID_ARG, "%s: null queries mean the search cloud's %zu points, n_q = %zu", what, S.n, n_q);
+    d_queries = S.cloud.data();
+    return ICPGPU_OK;
+  }
+  if (n_q > (size_t)INT32_MAX - 4096) return fail(c, ICPGPU_ERR_INVALID_ARG, "%s: too many queries: %zu", what, n_q);
+  if (n_q == 0) return ICPGPU_OK;
+  int rc;
+  if ((rc = ensure(c, S.queries, n_q * sizeof(float4)))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(S.queries.ptr, queries_xyzw, n_q * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+  d_queries = static_cast<const float4*>(S.queries.ptr);
+  return ICPGPU_OK;
+}
+
+// Results on their way to the caller's (pageable) arrays: up to three device arrays copied into consecutive slices of the pinned
+// staging buffer -- copies the stream really queues -- ONE wait for the stream, then a memcpy each.  Results that do not fit the
+// staging buffer (kStageMaxBytes) are copied straight into the caller's memory, where the runtime may wait inside every copy.
+struct Delivery {
+  void* dst;
+  const void* d_src;
+  size_t bytes;
+};
+int deliver(icpgpu_ctx* c, const Delivery* parts, int n_parts) {
+  size_t total = 0;
+  for (int i = 0; i < n_parts; ++i) total += (parts[i].bytes + 15) & ~(size_t)15;
+  if (total == 0) return ICPGPU_OK;
+  if (total > kStageMaxBytes) {
+    for (int i = 0; i < n_parts; ++i)
+      if (parts[i].bytes) HIP_TRY(c, hipMemcpyAsync(parts[i].dst, parts[i].d_src, parts[i].bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return ICPGPU_OK;
+  }
+  int rc;
+  if ((rc = ensure_stage(c, total))) return rc;
+  size_t at = 0;
+  for (int i = 0; i < n_parts; ++i) {
+    if (parts[i].bytes) HIP_TRY(c, hipMemcpyAsync(static_cast<char*>(c->h_stage) + at, parts[i].d_src, parts[i].bytes, hipMemcpyDeviceToHost, c->stream));
+    at += (parts[i].bytes + 15) & ~(size_t)15;
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  at = 0;
+  for (int i = 0; i < n_parts; ++i) {
+    if (parts[i].bytes) std::memcpy(parts[i].dst, static_cast<const char*>(c->h_stage) + at, parts[i].bytes);
+    at += (parts[i].bytes + 15) & ~(size_t)15;
+  }
+  return ICPGPU_OK;
+}
+
+}  // namespace
+}  // namespace icpgpu_impl
+
+extern "C" {
+
+// Copies the cloud and builds its k-NN grid.  Nothing of the context's source, target, their grids, the covariances, the NDT cells
+// or the filters' results is touched; the previous search cloud is gone whatever this call returns.
+int icpgpu_search_set_input(icpgpu_ctx* c, const float* xyzw, size_t n) {
+  ENTER(c);
+  auto& S = c->search;
+  S.set = false;
+  S.n = 0;
+  S.n_finite = 0;
+  S.grid.built = S.grid.usable = false;  // (version 0: a build never stands for the next cloud)
+  if (n && !xyzw) return fail(c, ICPGPU_ERR_INVALID_ARG, "null cloud pointer with n = %zu", n);
+  if (n > (size_t)INT32_MAX - 4096) return fail(c, ICPGPU_ERR_INVALID_ARG, "cloud too large: %zu points", n);
+  if (n) {
+    int rc;
+    if ((rc = ensure(c, S.cloud.buf, n * sizeof(float4)))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(S.cloud.buf.ptr, xyzw, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    S.cloud.n = n;
+    S.cloud.set = true;
+    S.cloud.bbox_version = 0;
+    S.cloud.finite_version = 0;
+    if ((rc = build_knn_grid(c, S.cloud, S.grid))) return rc;
+    if (!S.grid.usable && n > (size_t)kGicpCovFarMost)
+      return fail(c, ICPGPU_ERR_UNSUPPORTED, "neighbour search: cannot index this cloud of %zu points", n);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the caller's buffer is free from here on)
+    S.n_finite = S.grid.n_finite >= 0 ? S.grid.n_finite : count_finite(xyzw, n);
+  }
+  S.n = n;
+  S.set = true;
+  return ICPGPU_OK;
+}
+
+int icpgpu_search_size(const icpgpu_ctx* c, size_t* n, size_t* n_finite) {
+  if (!c) return ICPGPU_ERR_INVALID_ARG;
+  if (n) *n = c->search.set ? c->search.n : 0;
+  if (n_finite) *n_finite = c->search.set ? (size_t)c->search.n_finite : 0;
+  return c->search.set ? ICPGPU_OK : ICPGPU_ERR_INVALID_ARG;
+}
+
+// One wait per call (deliver): the kernels, the rows into the staging buffer, the stream.
+int icpgpu_search_knn(icpgpu_ctx* c, const float* queries_xyzw, size_t n_q, int k, int32_t* idx, float* d2, int32_t* n_found) {
+  ENTER(c);
+  auto& S = c->search;
+  const float4* d_queries = nullptr;
+  int rc;
+  if (k < 1 || k > ICPGPU_SEARCH_MAX_K) return fail(c, ICPGPU_ERR_INVALID_ARG, "search_knn: k %d outside 1..%d", k, ICPGPU_SEARCH_MAX_K);
+  if ((rc = stage_queries(c, "search_knn", queries_xyzw, n_q, d_queries))) return rc;
+  if (n_q == 0) return ICPGPU_OK;
+  if (!idx || !d2) return fail(c, ICPGPU_ERR_INVALID_ARG, "search_knn: null result pointer");
+  const size_t cells = n_q * (size_t)k;
+  if ((rc = ensure(c, S.idx, cells * sizeof(int32_t)))) return rc;
+  if ((rc = ensure(c, S.d2, cells * sizeof(float)))) return rc;
+  if ((rc = ensure(c, S.n_found, n_q * sizeof(int32_t)))) return rc;
+  if ((rc = ensure(c, S.far, (n_q + 2) * sizeof(int)))) return rc;
+  const SearchView v = view_of(c);
+  HIP_TRY(c, launch_search_knn(d_queries, (int)n_q, v.cloud, v.n, v.sorted, v.cell_start, v.g, k, static_cast<int32_t*>(S.idx.ptr),
+                               static_cast<float*>(S.d2.ptr), static_cast<int32_t*>(S.n_found.ptr), static_cast<int*>(S.far.ptr), c->stream));
+  const Delivery out[3] = {{idx, S.idx.ptr, cells * sizeof(int32_t)}, {d2, S.d2.ptr, cells * sizeof(float)},
+                           {n_found, S.n_found.ptr, n_found ? n_q * sizeof(int32_t) : 0}};
+  return deliver(c, out, 3);
+}
+
+// Two waits at most (deliver): the totals with row_start, then the rows.
+int icpgpu_search_radius(icpgpu_ctx* c, const float* queries_xyzw, size_t n_q, double radius, int max_nn, size_t capacity, int64_t* row_start,
+                         int32_t* idx, float* d2, size_t* n_total) {
+  ENTER(c);
+  auto& S = c->search;
+  if (n_total) *n_total = 0;
+  const float4* d_queries = nullptr;
+  int rc;
+  if (!std::isfinite(radius) || radius < 0.0) return fail(c, ICPGPU_ERR_INVALID_ARG, "search_radius: radius must be finite and >= 0");
+  if (max_nn < 0) return fail(c, ICPGPU_ERR_INVALID_ARG, "search_radius: max_nn %d < 0", max_nn);
+  if (!row_start || !n_total) return fail(c, ICPGPU_ERR_INVALID_ARG, "search_radius: null row_start or n_total");
+  if ((rc = stage_queries(c, "search_radius", queries_xyzw, n_q, d_queries))) return rc;
+  row_start[0] = 0;
+  if (n_q == 0) return ICPGPU_OK;
+  const size_t rows = n_q + 1;
+  if ((rc = ensure(c, S.counts, rows * sizeof(int)))) return rc;
+  if ((rc = ensure(c, S.longs, rows * sizeof(int)))) return rc;
+  if ((rc = ensure(c, S.row_start, rows * sizeof(int)))) return rc;
+  if ((rc = ensure(c, S.scratch_start, rows * sizeof(int)))) return rc;
+  if ((rc = ensure(c, S.scan, exclusive_scan_scratch_ints((int)rows) * sizeof(int)))) return rc;
+  if ((rc = ensure(c, S.totals, 2 * sizeof(unsigned long long)))) return rc;
+  if ((rc = ensure(c, S.row_start64, rows * sizeof(long long)))) return rc;
+  const SearchView v = view_of(c);
+  const float r2 = (float)(radius * radius);
+  // the cube of `shells` cells around a query's cell contains its ball (shells * h * kGridSafety >= radius: the grid search's bound);
+  // a ball of more than kSearchRadiusShells cells is searched without the grid
+  int shells = -1;
+  if (v.sorted) {
+    const double s = std::ceil(radius / ((double)v.g.h * (double)kGridSafety));
+    if (s <= (double)kSearchRadiusShells) shells = (int)s;
+  }
+  int* d_row_start = static_cast<int*>(S.row_start.ptr);
+  int* d_scratch_start = static_cast<int*>(S.scratch_start.ptr);
+  HIP_TRY(c, launch_search_radius_count(d_queries, (int)n_q, v.cloud, S.n_finite > 0 ? v.n : 0, v.sorted, v.cell_start, v.g, shells, r2, max_nn,
+                                        static_cast<int*>(S.counts.ptr), static_cast<int*>(S.longs.ptr), d_row_start, d_scratch_start,
+                                        static_cast<int*>(S.scan.ptr), static_cast<unsigned long long*>(S.totals.ptr),
+                                        static_cast<long long*>(S.row_start64.ptr), c->stream));
+  unsigned long long totals[2] = {0, 0};
+  const Delivery first[2] = {{totals, S.totals.ptr, sizeof totals}, {row_start, S.row_start64.ptr, rows * sizeof(int64_t)}};
+  if ((rc = deliver(c, first, 2))) return rc;
+  if (totals[0] > (unsigned long long)INT32_MAX || totals[1] > (unsigned long long)INT32_MAX) {
+    for (size_t i = 0; i < rows; ++i) row_start[i] = 0;  // (the int32 scan has wrapped)
+    return fail(c, ICPGPU_ERR_UNSUPPORTED, "search_radius: %llu neighbours in all, more than the int32 scans carry", totals[0]);
+  }
+  const size_t total = (size_t)totals[0];
+  *n_total = total;
+  if (total == 0) return ICPGPU_OK;
+  if (total > capacity || !idx || !d2) return fail(c, ICPGPU_ERR_INVALID_ARG, "search_radius: %zu neighbours, room for %zu", total, idx && d2 ? capacity : (size_t)0);
+  if ((rc = ensure(c, S.idx, total * sizeof(int32_t)))) return rc;
+  if ((rc = ensure(c, S.d2, total * sizeof(float)))) return rc;
+  if ((rc = ensure(c, S.scratch, std::max<size_t>((size_t)totals[1], 1) * sizeof(unsigned long long)))) return rc;
+  HIP_TRY(c, launch_search_radius_fill(d_queries, (int)n_q, v.cloud, v.n, v.sorted, v.cell_start, v.g, shells, r2, d_row_start, d_scratch_start,
+                                       static_cast<unsigned long long*>(S.scratch.ptr), static_cast<int32_t*>(S.idx.ptr),
+                                       static_cast<float*>(S.d2.ptr), c->stream));
+  const Delivery second[2] = {{idx, S.idx.ptr, total * sizeof(int32_t)}, {d2, S.d2.ptr, total * sizeof(float)}};
+  return deliver(c, second, 2);
+}
+
+}  // extern "C"

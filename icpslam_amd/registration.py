@@ -475,6 +475,61 @@ class Context:
         mask[kept] = False
         return {"measure": measure, "kept": kept, "removed": np.flatnonzero(mask).astype(np.int32)}
 
+    # neighbour search (pcl::search::KdTree / pcl::KdTreeFLANN; rules: include/icpgpu.h) --------------------------------
+    def search_set_input(self, cloud) -> None:
+        """setInputCloud: the context's search cloud (its own buffer and k-NN grid, apart from source, target and the filters)."""
+        cloud = _as_cloud(cloud)
+        self._check(self._L.icpgpu_search_set_input(self._h, _fp(cloud), cloud.shape[0]))
+
+    def search_size(self) -> tuple:
+        """(points, finite points) of the search cloud."""
+        n, nf = C.c_size_t(), C.c_size_t()
+        self._check(self._L.icpgpu_search_size(self._h, C.byref(n), C.byref(nf)))
+        return int(n.value), int(nf.value)
+
+    def _search_queries(self, queries, n_q):
+        if queries is None:
+            return None, (self.search_size()[0] if n_q is None else int(n_q))
+        queries = _as_cloud(queries)
+        return queries, queries.shape[0]
+
+    def search_knn(self, queries, k: int, n_q: int | None = None):
+        """(idx (n_q, k) int32, d2 (n_q, k) float32, n_found (n_q,) int32): every query's k nearest cloud points, ascending by
+        (d2, index), padded with -1 / +inf.  queries None: the search cloud's own points (n_q: only to test the refusal)."""
+        queries, n_q = self._search_queries(queries, n_q)
+        kk = max(int(k), 0)
+        idx = np.empty((n_q, kk), np.int32)
+        d2 = np.empty((n_q, kk), np.float32)
+        n_found = np.empty(n_q, np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._check(self._L.icpgpu_search_knn(self._h, None if queries is None else _fp(queries), n_q, int(k), idx.ctypes.data_as(ip), _fp(d2),
+                                              n_found.ctypes.data_as(ip)))
+        return idx, d2, n_found
+
+    def search_radius_raw(self, queries, radius: float, max_nn: int, capacity: int, n_q: int | None = None):
+        """One icpgpu_search_radius call with room for `capacity` neighbours: (rc, row_start, idx, d2, n_total); rc is the status
+        code (ERR_INVALID_ARG when the rows did not fit: row_start and n_total are valid, idx / d2 untouched)."""
+        queries, n_q = self._search_queries(queries, n_q)
+        row_start = np.full(n_q + 1, -1, np.int64)
+        idx = np.full(capacity, -2, np.int32)
+        d2 = np.full(capacity, np.nan, np.float32)
+        n_total = C.c_size_t()
+        rc = self._L.icpgpu_search_radius(self._h, None if queries is None else _fp(queries), n_q, float(radius), int(max_nn), int(capacity),
+                                          row_start.ctypes.data_as(C.POINTER(C.c_int64)), idx.ctypes.data_as(C.POINTER(C.c_int32)) if capacity else None,
+                                          _fp(d2) if capacity else None, C.byref(n_total))
+        return rc, row_start, idx, d2, int(n_total.value)
+
+    def search_radius(self, queries, radius: float, max_nn: int = 0, n_q: int | None = None):
+        """(row_start (n_q + 1,) int64, idx, d2): CSR rows of every query's neighbours with d2 < float32(radius^2), ascending by
+        (d2, index), at most max_nn each when max_nn > 0.  Two calls: the first sizes the arrays."""
+        rc, row_start, idx, d2, total = self.search_radius_raw(queries, radius, max_nn, 0, n_q)
+        if rc == 0 or rc != _lib.ERR_INVALID_ARG or total == 0:
+            self._check(rc)
+            return row_start, idx, d2
+        rc, row_start, idx, d2, total = self.search_radius_raw(queries, radius, max_nn, total, n_q)
+        self._check(rc)
+        return row_start, idx, d2
+
     # measurement -----------------------------------------------------------------------------------------------
     def calibrate(self) -> int:
         """icpgpu_calibrate: time GICP's two inner solvers on the clouds this context holds and keep the faster (GICP_SOLVER_*)."""
@@ -705,6 +760,52 @@ class RadiusOutlierRemoval(_OutlierFilter):
 
     def _run(self, cloud) -> np.ndarray:
         return self._ctx.radius_outlier_removal(cloud, self._radius, self._min_pts, self._negative, view=True)
+
+
+class KdTree:
+    """pcl::search::KdTree<PointXYZ> / pcl::KdTreeFLANN<PointXYZ>-shaped front end: exact k-nearest and radius search over one cloud
+    (include/icpgpu.h, "neighbour search": results ascending by (d2, index)).  A query is a point (x, y, z[, w]) or an index into the
+    input cloud; the batched forms take a whole query cloud (None: the input cloud's own points) and are what a GPU user should
+    call."""
+
+    def __init__(self, device_id: int = 0):
+        self._ctx = Context(device_id)
+        self._cloud = np.empty((0, 4), np.float32)
+
+    def setInputCloud(self, cloud):
+        self._cloud = _as_cloud(cloud).copy()
+        self._ctx.search_set_input(self._cloud)
+
+    def getInputCloud(self) -> np.ndarray:
+        return self._cloud
+
+    def _query(self, point) -> np.ndarray:
+        if isinstance(point, (int, np.integer)):
+            return self._cloud[int(point):int(point) + 1]
+        q = np.ones((1, 4), np.float32)
+        p = np.asarray(point, np.float32).reshape(-1)
+        q[0, :min(p.size, 4)] = p[:4]
+        return q
+
+    def nearestKSearch(self, point, k: int):
+        """(indices, squared distances) of the k nearest; their number is len(indices), as PCL's return value."""
+        idx, d2, n = self._ctx.search_knn(self._query(point), k)
+        return idx[0, :n[0]].copy(), d2[0, :n[0]].copy()
+
+    def radiusSearch(self, point, radius: float, max_nn: int = 0):
+        _, idx, d2 = self._ctx.search_radius(self._query(point), radius, max_nn)
+        return idx, d2
+
+    def nearestKSearchBatch(self, queries, k: int):
+        """(idx (n_q, k), d2 (n_q, k), n_found (n_q,)) for a whole query cloud (None: the input cloud's own points)."""
+        return self._ctx.search_knn(queries, k)
+
+    def radiusSearchBatch(self, queries, radius: float, max_nn: int = 0):
+        """(row_start (n_q + 1,), idx, d2): CSR rows for a whole query cloud (None: the input cloud's own points)."""
+        return self._ctx.search_radius(queries, radius, max_nn)
+
+
+KdTreeFLANN = KdTree
 
 
 class IterativeClosestPoint:

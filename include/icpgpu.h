@@ -54,7 +54,8 @@ extern "C" {
  * 1.2: the correspondence rejectors -- icpgpu_rejector, icpgpu_set_correspondence_rejectors, icpgpu_get_correspondence_rejectors,
  * icpgpu_correspondences, icpgpu_rejector_stats, and reciprocal correspondences -- icpgpu_set_reciprocal_correspondences,
  * icpgpu_get_reciprocal_correspondences, icpgpu_reciprocal_stats, and the outlier filters -- icpgpu_statistical_outlier_removal,
- * icpgpu_radius_outlier_removal, their _view forms, icpgpu_outlier_stats, icpgpu_outlier_fetch (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
+ * icpgpu_radius_outlier_removal, their _view forms, icpgpu_outlier_stats, icpgpu_outlier_fetch, and the neighbour search --
+ * icpgpu_search_set_input, icpgpu_search_size, icpgpu_search_knn, icpgpu_search_radius (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
  * icpgpu_profile.gicp_quadratic_solves; 0.3 icpgpu_profile (sources_adopted, gicp_host_solves, gicp_solver_choice). */
 
@@ -597,6 +598,48 @@ int icpgpu_outlier_stats(const icpgpu_ctx* ctx, double* mean, double* stddev, do
  * *n_kept are always set.  measure / kept_index may be NULL; with both NULL the call only reports the sizes (ICPGPU_OK whatever the
  * capacity).  Otherwise nothing is copied when n_in exceeds capacity (ICPGPU_ERR_INVALID_ARG). */
 int icpgpu_outlier_fetch(icpgpu_ctx* ctx, size_t capacity, float* measure, int32_t* kept_index, size_t* n_in, size_t* n_kept);
+
+/* ---- neighbour search (added under 1.2) ---------------------------------------------------------------------------- */
+/* replaces pcl::search::KdTree<PointXYZ> / pcl::KdTreeFLANN<PointXYZ>: setInputCloud, nearestKSearch, radiusSearch -- "which points of
+ * this cloud are the k nearest to this point" and "which lie within r of it", for any number of queries in one call.  A context
+ * holds one SEARCH CLOUD of its own (icpgpu_search_set_input), separate from source, target and the filters' scratch.  The rules
+ * restate FLANN's exact search as PCL calls it; parity with PCL binaries is unpinned (tests/search_restated.py is what the kernels are
+ * compared with, bit for bit).
+ * COMMON.  Points and queries are float4; a point is finite when x, y and z are.  d2 is the squared distance of DESIGN.md section 3
+ * with no transform, the query as p and the cloud point as q: dx = q.x - p.x, ...; d2 = fma(dz, dz, fma(dy, dy, dx * dx)) in float32
+ * (the outlier filters' d2).  Only finite cloud points are searchable.
+ *   ORDER: a neighbour's key is ((uint64)bits(d2) << 32) | index.  Results are ascending by key: by distance, and among equal
+ *   distances the lowest cloud index first.  DEVIATION: FLANN leaves the order of equal distances unspecified (and so which of
+ *   several equidistant points make a list of k); this is the rule icpgpu_nn follows for its one neighbour.
+ *   queries_xyzw == NULL means "the search cloud's own points, in its order"; n_q must then be 0 or n.
+ *   A non-finite query finds nothing (DEVIATION: PCL asserts).  n_q = 0 is ICPGPU_OK.
+ * SET_INPUT copies the cloud (the caller's buffer is free on return) and builds its k-NN grid, whose cells come from the cloud's own
+ * density as for the statistical outlier filter; the neighbours are exact whatever the cells.  n = 0 is legal: every query then
+ * finds nothing.  A cloud the grid cannot index (tight clusters in a wide volume) is searched without it up to 65536 points; beyond
+ * that ICPGPU_ERR_UNSUPPORTED, and the context has no search cloud.  A call replaces the previous search cloud whatever it returns.
+ * icpgpu_search_knn / _radius without a search cloud: ICPGPU_ERR_INVALID_ARG.  icpgpu_search_size: the search cloud's points and how
+ * many of them are finite (either may be NULL; ICPGPU_ERR_INVALID_ARG and zeroes without a search cloud).
+ * K-NEAREST.  k must be in 1 .. ICPGPU_SEARCH_MAX_K, else ICPGPU_ERR_INVALID_ARG.  Row i of idx / d2 (k entries, row-major; both must
+ * hold n_q * k) holds the m = min(k, n_finite) smallest keys of query i; the other slots hold idx = -1, d2 = +inf.  n_found[i] = m,
+ * or 0 for a non-finite query; n_found may be NULL.  Fewer than k finite points is not an error: PCL returns a short list too.  A
+ * query that is a cloud point finds itself first (d2 = 0), as in PCL.
+ * RADIUS.  r2 = (float)(radius * radius), the product in double; a neighbour qualifies iff d2 < r2, strict (both as for
+ * icpgpu_radius_outlier_removal).  radius not finite or negative, or max_nn < 0: ICPGPU_ERR_INVALID_ARG.  radius = 0 finds nothing.
+ * max_nn = 0 keeps every qualifying neighbour; max_nn > 0 keeps the max_nn smallest keys among them, for any positive value.
+ * The output is CSR: row_start has n_q + 1 entries, row_start[0] = 0; row i is idx / d2 [row_start[i], row_start[i + 1]), ascending
+ * by key; *n_total = row_start[n_q].  row_start and n_total must not be NULL.  When *n_total > capacity, or idx / d2 are NULL and
+ * *n_total > 0, row_start and *n_total are still written, nothing goes to idx / d2, and the call returns ICPGPU_ERR_INVALID_ARG: the
+ * caller sizes its arrays and calls again (a call that finds nothing at all has nothing to deliver and is ICPGPU_OK).  A total
+ * beyond INT32_MAX is ICPGPU_ERR_UNSUPPORTED (row_start is then all zero and *n_total 0).
+ * ISOLATION.  The search calls leave the context's source, target, every grid, the covariances, the NDT cells, the voxel-filter and
+ * outlier-filter results and the recognition fingerprints as they were, and a search's answers depend on the search cloud and the
+ * call's arguments alone, not on anything the context did before. */
+#define ICPGPU_SEARCH_MAX_K 64
+int icpgpu_search_set_input(icpgpu_ctx* ctx, const float* xyzw, size_t n);
+int icpgpu_search_size(const icpgpu_ctx* ctx, size_t* n, size_t* n_finite);
+int icpgpu_search_knn(icpgpu_ctx* ctx, const float* queries_xyzw, size_t n_q, int k, int32_t* idx, float* d2, int32_t* n_found);
+int icpgpu_search_radius(icpgpu_ctx* ctx, const float* queries_xyzw, size_t n_q, double radius, int max_nn, size_t capacity,
+                         int64_t* row_start, int32_t* idx, float* d2, size_t* n_total);
 
 /* ---- the mapper's target: a one-point-per-voxel map and its "nn cloud"  -------- */
 /* replaces OctreeMapper's pcl::octree::OctreePointCloudSearch map

@@ -647,6 +647,116 @@ class RadiusOutlierRemoval : public OutlierFilterBase<CloudT, RadiusOutlierRemov
   int min_pts_ = 1;
 };
 
+// pcl::search::KdTree<PointT> / pcl::KdTreeFLANN<PointT>-shaped front end of the neighbour search (rules and deviations:
+// include/icpgpu.h, "neighbour search": exact, results ascending by (squared distance, index)):
+//   pcl::search::KdTree<pcl::PointXYZ> tree;  ->  icpgpu::search::KdTree<pcl::PointCloud<pcl::PointXYZ>> tree;
+//   tree.setInputCloud(cloud); tree.nearestKSearch(p, k, indices, sqr_distances); tree.radiusSearch(p, r, indices, sqr_distances);
+// Every call returns the number of neighbours found, as PCL does (0 when the library refuses the call).  A single-point call is a
+// whole round trip to the device: code that queries many points should use the batched forms, which take a query cloud and
+// return rows.
+namespace search {
+template <class CloudT>
+class KdTree {
+ public:
+  explicit KdTree(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {}
+  template <class CloudPtr>
+  void setInputCloud(const CloudPtr& cloud) {
+    input_ = &*cloud;
+    const std::size_t n = input_->points.size();
+    static_assert(sizeof(input_->points[0]) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+    ready_ = icpgpu_search_set_input(ctx_, n ? reinterpret_cast<const float*>(&input_->points[0]) : nullptr, n) == ICPGPU_OK;
+  }
+  template <class PointT>
+  int nearestKSearch(const PointT& point, int k, std::vector<int>& k_indices, std::vector<float>& k_sqr_distances) {
+    const float q[4] = {point.x, point.y, point.z, 1.0f};
+    return knn_one(q, k, k_indices, k_sqr_distances);
+  }
+  int nearestKSearch(int index, int k, std::vector<int>& k_indices, std::vector<float>& k_sqr_distances) {
+    if (!input_ || index < 0 || (std::size_t)index >= input_->points.size()) return clear(k_indices, k_sqr_distances);
+    return knn_one(reinterpret_cast<const float*>(&input_->points[index]), k, k_indices, k_sqr_distances);
+  }
+  template <class PointT>
+  int radiusSearch(const PointT& point, double radius, std::vector<int>& k_indices, std::vector<float>& k_sqr_distances, unsigned int max_nn = 0) {
+    const float q[4] = {point.x, point.y, point.z, 1.0f};
+    return radius_one(q, radius, max_nn, k_indices, k_sqr_distances);
+  }
+  int radiusSearch(int index, double radius, std::vector<int>& k_indices, std::vector<float>& k_sqr_distances, unsigned int max_nn = 0) {
+    if (!input_ || index < 0 || (std::size_t)index >= input_->points.size()) return clear(k_indices, k_sqr_distances);
+    return radius_one(reinterpret_cast<const float*>(&input_->points[index]), radius, max_nn, k_indices, k_sqr_distances);
+  }
+  // Batched forms (not PCL's): every point of `queries` in one call.  Row i of k_indices / k_sqr_distances has k entries, the
+  // first n_found[i] of them neighbours (the rest -1 / +inf); returns the number of queries answered.
+  int nearestKSearch(const CloudT& queries, int k, std::vector<int>& k_indices, std::vector<float>& k_sqr_distances, std::vector<int>& n_found) {
+    const std::size_t nq = queries.points.size();
+    k_indices.assign(k > 0 ? nq * (std::size_t)k : 0, -1);
+    k_sqr_distances.resize(k_indices.size());
+    n_found.assign(nq, 0);
+    if (!ready_ || nq == 0 || k <= 0) return 0;
+    static_assert(sizeof(int) == sizeof(int32_t), "icpgpu: 32-bit int");
+    const int rc = icpgpu_search_knn(ctx_, reinterpret_cast<const float*>(&queries.points[0]), nq, k, reinterpret_cast<int32_t*>(&k_indices[0]),
+                                     &k_sqr_distances[0], reinterpret_cast<int32_t*>(&n_found[0]));
+    if (rc != ICPGPU_OK) {
+      k_indices.clear(), k_sqr_distances.clear(), n_found.assign(nq, 0);
+      return 0;
+    }
+    return (int)nq;
+  }
+  // Row i is k_indices / k_sqr_distances [row_start[i], row_start[i + 1]); returns the number of queries answered.
+  int radiusSearch(const CloudT& queries, double radius, std::vector<long long>& row_start, std::vector<int>& k_indices,
+                   std::vector<float>& k_sqr_distances, unsigned int max_nn = 0) {
+    const std::size_t nq = queries.points.size();
+    return radius_rows(nq ? reinterpret_cast<const float*>(&queries.points[0]) : nullptr, nq, radius, max_nn, row_start, k_indices, k_sqr_distances)
+               ? (int)nq : 0;
+  }
+
+ private:
+  static int clear(std::vector<int>& a, std::vector<float>& b) {
+    a.clear(), b.clear();
+    return 0;
+  }
+  int knn_one(const float* q, int k, std::vector<int>& k_indices, std::vector<float>& k_sqr_distances) {
+    if (!ready_ || k <= 0) return clear(k_indices, k_sqr_distances);
+    k_indices.resize((std::size_t)k), k_sqr_distances.resize((std::size_t)k);
+    int32_t found = 0;
+    if (icpgpu_search_knn(ctx_, q, 1, k, reinterpret_cast<int32_t*>(&k_indices[0]), &k_sqr_distances[0], &found) != ICPGPU_OK)
+      return clear(k_indices, k_sqr_distances);
+    k_indices.resize((std::size_t)found), k_sqr_distances.resize((std::size_t)found);  // (PCL returns a short list too)
+    return (int)found;
+  }
+  // the two-call protocol of icpgpu_search_radius: the first call sizes the arrays
+  bool radius_rows(const float* q, std::size_t nq, double radius, unsigned int max_nn, std::vector<long long>& row_start, std::vector<int>& k_indices,
+                   std::vector<float>& k_sqr_distances) {
+    static_assert(sizeof(long long) == sizeof(int64_t), "icpgpu: 64-bit long long");
+    row_start.assign(nq + 1, 0);
+    clear(k_indices, k_sqr_distances);
+    if (!ready_ || nq == 0 || max_nn > 0x7FFFFFFFu) return false;
+    std::size_t total = 0;
+    int rc = icpgpu_search_radius(ctx_, q, nq, radius, (int)max_nn, 0, reinterpret_cast<int64_t*>(&row_start[0]), nullptr, nullptr, &total);
+    if (rc == ICPGPU_OK) return true;  // (nothing found)
+    if (rc != ICPGPU_ERR_INVALID_ARG || total == 0) return false;
+    k_indices.resize(total), k_sqr_distances.resize(total);
+    rc = icpgpu_search_radius(ctx_, q, nq, radius, (int)max_nn, total, reinterpret_cast<int64_t*>(&row_start[0]),
+                              reinterpret_cast<int32_t*>(&k_indices[0]), &k_sqr_distances[0], &total);
+    if (rc == ICPGPU_OK) return true;
+    row_start.assign(nq + 1, 0);
+    clear(k_indices, k_sqr_distances);
+    return false;
+  }
+  int radius_one(const float* q, double radius, unsigned int max_nn, std::vector<int>& k_indices, std::vector<float>& k_sqr_distances) {
+    std::vector<long long> row_start;
+    radius_rows(q, 1, radius, max_nn, row_start, k_indices, k_sqr_distances);
+    return (int)k_indices.size();
+  }
+
+  detail::ContextPtr ctx_holder_;
+  icpgpu_ctx* ctx_;
+  const CloudT* input_ = nullptr;
+  bool ready_ = false;
+};
+}  // namespace search
+template <class CloudT>
+using KdTreeFLANN = search::KdTree<CloudT>;
+
 // The mapper's map (/root/reference/src/icpslam/octree_mapper.cpp:55-90): replaces the pair
 //   pcl::octree::OctreePointCloudSearch<pcl::PointXYZ>::Ptr map_octree_;  pcl::PointCloud<pcl::PointXYZ>::Ptr map_cloud_;
 // Poses are the float 4x4 that pcl_ros::transformPointCloud applies (icpgpu_pose_to_matrix gives it for a Pose6DOF);

@@ -1,0 +1,173 @@
+"""The neighbour search's rules (include/icpgpu.h, "neighbour search") without a device: the NumPy restatement against a literal
+per-pair loop, answers known by hand, and the C-ABI's new symbols."""
+import math
+import os
+import subprocess
+import time
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+import search_restated as R
+from icpslam_amd import _lib, synth
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+F32 = np.float32
+NEW_SYMBOLS = ["icpgpu_search_set_input", "icpgpu_search_size", "icpgpu_search_knn", "icpgpu_search_radius"]
+
+
+def fmaf(a, b, c):
+    """fmaf on three float32 scalars through exact rational arithmetic."""
+    exact = Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c))
+    lo = F32(float(exact))  # (float() of a Fraction rounds correctly to float64; narrowing may double-round: fix below)
+    cands = [lo, np.nextafter(lo, F32(np.inf)), np.nextafter(lo, F32(-np.inf))]
+    return min(cands, key=lambda v: (abs(Fraction(float(v)) - exact), int(F32(v).view(np.int32)) & 1))
+
+
+def literal_d2(p, q):
+    dx, dy, dz = F32(q[0] - p[0]), F32(q[1] - p[1]), F32(q[2] - p[2])
+    return fmaf(dz, dz, fmaf(dy, dy, F32(dx * dx)))
+
+
+def literal_neighbours(cloud, p):
+    """Every finite cloud point as (bits of d2, index, d2), ascending: pair by pair, as the rule is written."""
+    if not all(math.isfinite(v) for v in p[:3]):
+        return []
+    out = []
+    for j, q in enumerate(cloud):
+        if all(math.isfinite(v) for v in q[:3]):
+            d = literal_d2(p, q)
+            out.append((int(F32(d).view(np.uint32)), j, d))
+    return sorted(out)
+
+
+def small_cloud(n, seed):
+    c = synth.scan(synth.make_scene(3), np.eye(4), n, seed).copy()
+    c[3, 1] = np.nan
+    return c
+
+
+def same(a, b):
+    return all(np.asarray(x).dtype == np.asarray(y).dtype and np.asarray(x).tobytes() == np.asarray(y).tobytes() for x, y in zip(a, b))
+
+
+def test_restatement_against_a_literal_loop():
+    cloud = small_cloud(300, 4)
+    cloud[40:44] = cloud[39]  # coincident points: the index decides
+    queries = np.concatenate([cloud[:25], small_cloud(12, 9), F32([[np.inf, 0, 0, 1], [500, 500, 500, 1]])])
+    lists = [literal_neighbours(cloud, p) for p in queries]
+    for k in (1, 5, 20, 64):
+        idx, d2, n_found = R.knn(cloud, queries, k)
+        for i, full in enumerate(lists):
+            want = full[:k]
+            assert n_found[i] == len(want)
+            assert idx[i, :len(want)].tolist() == [j for _, j, _ in want] and (idx[i, len(want):] == -1).all()
+            assert d2[i, :len(want)].tolist() == [float(d) for _, _, d in want] and np.isinf(d2[i, len(want):]).all()
+        assert same(R.knn_literal(cloud, queries, k), (idx, d2, n_found))
+    for radius, max_nn in ((0.0, 0), (0.3, 0), (3.0, 0), (3.0, 2), (1e3, 70), (1e3, 0)):
+        row_start, idx, d2 = R.radius(cloud, queries, radius, max_nn)
+        r2 = F32(radius * radius)
+        for i, full in enumerate(lists):
+            want = [e for e in full if e[2] < r2]
+            want = want[:max_nn] if max_nn else want
+            a, b = row_start[i], row_start[i + 1]
+            assert idx[a:b].tolist() == [j for _, j, _ in want] and d2[a:b].tolist() == [float(d) for _, _, d in want]
+        assert row_start[-1] == len(idx) == len(d2)
+        assert same(R.radius_literal(cloud, queries, radius, max_nn), (row_start, idx, d2))
+
+
+def test_narrowing_pass_changes_nothing():
+    """The chunked forms against the exact expression on every pair, on clouds with ties: duplicates, a lattice."""
+    cloud = small_cloud(700, 8)
+    cloud[100:140] = cloud[99]
+    g = np.arange(6, dtype=F32) * F32(0.25)
+    lattice = np.ones((216, 4), F32)
+    lattice[:, :3] = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+    for c in (cloud, lattice):
+        for k in (1, 8, 27, 64):
+            assert same(R.knn(c, None, k), R.knn_literal(c, None, k))
+        for radius, max_nn in ((0.05, 0), (0.25, 0), (0.2500001, 0), (0.3, 3), (2.0, 0), (2.0, 65)):
+            assert same(R.radius(c, None, radius, max_nn), R.radius_literal(c, None, radius, max_nn))
+
+
+def lattice3():
+    g = np.arange(3, dtype=F32)
+    c = np.ones((27, 4), F32)
+    c[:, :3] = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+    return c
+
+
+def test_lattice_by_hand():
+    """3 x 3 x 3 integer lattice queried at its centre (index 13): itself, then 6 neighbours at d2 = 1, 12 at 2, 8 at 3, each group in
+    index order."""
+    c = lattice3()
+    idx, d2, n_found = R.knn(c, c[13:14], 27)
+    assert n_found.tolist() == [27] and idx[0, 0] == 13 and d2[0].tolist() == [0.0] + [1.0] * 6 + [2.0] * 12 + [3.0] * 8
+    manhattan = np.abs(c[:, :3] - 1).sum(axis=1)
+    for lo, hi, dist in ((1, 7, 1), (7, 19, 2), (19, 27, 3)):
+        assert idx[0, lo:hi].tolist() == np.flatnonzero(manhattan == dist).tolist()
+    idx7, d7, _ = R.knn(c, c[13:14], 5)  # a cut inside a group of equals keeps the lowest indices
+    assert idx7[0].tolist() == [13, 4, 10, 12, 14]
+    row_start, ridx, rd2 = R.radius(c, c[13:14], math.sqrt(2.0))  # float32(2.0) exactly: d2 == r2 does not qualify
+    assert row_start.tolist() == [0, 7] and ridx.tolist() == idx[0, :7].tolist()
+    row_start, ridx, rd2 = R.radius(c, c[13:14], 1.5, max_nn=4)
+    assert row_start.tolist() == [0, 4] and ridx.tolist() == [13, 4, 10, 12] and rd2.tolist() == [0, 1, 1, 1]
+    assert R.radius(c, c[13:14], 1.0)[1].tolist() == [13]  # strict at d2 == r2 = 1
+    assert R.radius(c, None, 0.0)[0].tolist() == [0] * 28  # radius 0 finds nothing, not even the query itself
+
+
+def test_coincident_points_and_short_lists():
+    c = np.tile(F32([4.0, 5.0, -6.0, 1.0]), (70, 1))
+    idx, d2, n_found = R.knn(c, c[:2], 64)
+    assert idx[0].tolist() == list(range(64)) and not d2.any() and n_found.tolist() == [64, 64]
+    c[5, 0] = np.nan
+    idx, d2, n_found = R.knn(c[:10], c[:3], 20)  # k > n_finite: a short list, no error
+    assert n_found.tolist() == [9, 9, 9] and idx[0, :9].tolist() == [0, 1, 2, 3, 4, 6, 7, 8, 9] and (idx[:, 9:] == -1).all() and np.isinf(d2[:, 9:]).all()
+    idx, d2, n_found = R.knn(c[:10], c[5:6], 3)  # a non-finite query
+    assert n_found.tolist() == [0] and (idx == -1).all() and np.isinf(d2).all()
+    assert R.radius(c[:10], c[4:7], 1.0)[0].tolist() == [0, 9, 9, 18]
+    empty = np.zeros((0, 4), F32)
+    assert R.knn(empty, c[:2], 3)[2].tolist() == [0, 0] and R.radius(empty, c[:2], 1.0)[0].tolist() == [0, 0, 0]
+    assert R.knn(c, empty, 3)[0].shape == (0, 3) and R.radius(c, empty, 1.0)[0].tolist() == [0]
+
+
+def test_refusals():
+    c = lattice3()
+    for k in (0, 65, -1):
+        with pytest.raises(R.Refused):
+            R.knn(c, None, k)
+    for radius, max_nn in ((-1.0, 0), (float("nan"), 0), (float("inf"), 0), (0.3, -1)):
+        with pytest.raises(R.Refused):
+            R.radius(c, None, radius, max_nn)
+
+
+def test_restatement_is_cheap_at_the_largest_device_case():
+    """3 000 x 3 000 is the largest exact pass any device test asks for: the restatement answers it (seconds on an idle host; the
+    time is printed, not asserted: a loaded host says nothing about the code), one row chunk never holds more than 2^21 pairs, and the
+    whole-cloud radius returns every pair."""
+    cloud = synth.scan(synth.make_scene(3), np.eye(4), 3000, 5)
+    assert all((b - a) * 3000 <= 1 << 21 for a, b in R._chunks(3000, 3000))
+    t0 = time.perf_counter()
+    idx, d2, n_found = R.knn(cloud, None, 64)
+    R.radius(cloud, None, 0.5)
+    row_start = R.radius(cloud, None, 1e4)[0]
+    print(f"restatement, 3000 x 3000: knn 64 + radius 0.5 + whole-cloud radius in {time.perf_counter() - t0:.1f} s")
+    assert row_start[-1] == 3000 * 3000 and (n_found == 64).all() and (idx[:, 0] == np.arange(3000)).all()
+
+
+def test_new_symbols_are_exported_and_declared(built):
+    names = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    header = open(os.path.join(os.path.dirname(HERE), "include", "icpgpu.h")).read()
+    for s in NEW_SYMBOLS:
+        assert f" T {s}\n" in names, s
+        assert f"int {s}(" in header and s in _lib.EXPORTS
+    assert "#define ICPGPU_SEARCH_MAX_K 64" in header and _lib.SEARCH_MAX_K == R.SEARCH_MAX_K == 64
+
+
+def test_entry_points_refuse_a_null_context(built):
+    L = _lib.load()
+    assert L.icpgpu_search_set_input(None, None, 0) == _lib.ERR_INVALID_ARG
+    assert L.icpgpu_search_size(None, None, None) == _lib.ERR_INVALID_ARG
+    assert L.icpgpu_search_knn(None, None, 0, 1, None, None, None) == _lib.ERR_INVALID_ARG
+    assert L.icpgpu_search_radius(None, None, 0, 1.0, 0, 0, None, None, None, None) == _lib.ERR_INVALID_ARG
