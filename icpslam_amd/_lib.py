@@ -98,6 +98,7 @@ EXPORTS = [
     "icpgpu_statistical_outlier_removal", "icpgpu_statistical_outlier_removal_view", "icpgpu_radius_outlier_removal",
     "icpgpu_radius_outlier_removal_view", "icpgpu_outlier_stats", "icpgpu_outlier_fetch",
     "icpgpu_search_set_input", "icpgpu_search_size", "icpgpu_search_knn", "icpgpu_search_radius",
+    "icpgpu_normal_estimation",
 ]
 
 _lib = None
@@ -198,6 +199,7 @@ def load():
     L.icpgpu_search_size.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.icpgpu_search_knn.argtypes = [vp, fp, C.c_size_t, C.c_int, ip, fp, ip]
     L.icpgpu_search_radius.argtypes = [vp, fp, C.c_size_t, C.c_double, C.c_int, C.c_size_t, C.POINTER(C.c_int64), ip, fp, C.POINTER(C.c_size_t)]
+    L.icpgpu_normal_estimation.argtypes = [vp, fp, C.c_size_t, C.c_int, C.c_double, fp, fp, ip, fp]
     pp, lp = C.POINTER(Pose), C.POINTER(C.c_long)
     L.icpgpu_pose_from_matrix.argtypes = [fp, pp]
     L.icpgpu_pose_to_matrix.argtypes = [pp, fp]

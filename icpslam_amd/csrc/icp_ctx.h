@@ -408,6 +408,7 @@ struct icpgpu_ctx {
     size_t n = 0;
     int n_finite = 0;
     DeviceBuf queries, idx, d2, n_found, far, counts, longs, row_start, scratch_start, scan, scratch, totals, row_start64;
+    DeviceBuf normals, moments;  // icpgpu_normal_estimation: the results on their way to the staging buffer
   } search;
   std::vector<icpgpu_ctx*> workers;  // align_batch: one sub-context (own stream + scratch) per host worker thread
   DeviceBuf batch_table;             // lock-step batch: the BatchPair table of the group this context leads

@@ -25,6 +25,7 @@
 // did with each cloud), ICPGPU_VOXEL_PLANNED=0 (the voxel filter waits for the bounding box), ICPGPU_STAGE_DIRECT=0 (result clouds
 // through device memory and the copy engine), ICPGPU_COV_GRID_UNCHECKED=0|2 (the covariance grid waits for its statistics / every
 // check fails).
+// The normal estimation's: ICPGPU_NORMALS_WAVE=1 (a wave per query instead of a lane per query: icp_normals.hip, EXPERIMENTS.md).
 #pragma once
 #include <cstdlib>
 

@@ -552,4 +552,11 @@ hipError_t launch_search_radius_fill(const float4* queries, int n_q, const float
                                      const GridDesc& g, int shells, float r2, const int* row_start, const int* scratch_start,
                                      unsigned long long* scratch, int32_t* idx, float* d2, hipStream_t stream);
 
+// ---- normal estimation (icp_normals.hip): pcl::NormalEstimation over neighbour rows still in device memory --------------------
+// out[i] = {nx, ny, nz, curvature} of query i from its row of cloud indices (ascending by key, as the launchers above leave them):
+// dense rows of stride k with n_found (row_start == null), or CSR rows with row_start (n_found == null).  moments (optional):
+// n_q x {xx, xy, xz, yy, yz, zz, cx, cy, cz}.  Rows shorter than 3 give NaN.
+hipError_t launch_normals_from_rows(const float4* queries, int n_q, const float4* cloud, int n, const int32_t* idx, const int32_t* n_found, int k,
+                                    const int* row_start, const float viewpoint[3], float4* out, float* moments, hipStream_t stream);
+
 }  // namespace icpgpu

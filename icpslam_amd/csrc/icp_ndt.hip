@@ -22,6 +22,7 @@
 #include <math.h>
 
 #include "icp_device.h"
+#include "icp_jacobi3.h"
 #include "icp_kernels.h"
 
 namespace icpgpu {
@@ -54,37 +55,7 @@ __global__ __launch_bounds__(256) void ndt_flag_kernel(const int* __restrict__ k
   flags[i] = (k != kNdtSentinel && (i == 0 || keys[i - 1] != k)) ? 1 : 0;
 }
 
-// Cyclic Jacobi on a symmetric 3x3 (a[i][j], double): on return a's diagonal holds the eigenvalues, v's columns the eigenvectors.
-// A rotation is skipped when its off-diagonal entry is exactly zero (an axis-aligned degenerate cell keeps exact zeros).  The
-// NumPy restatement (tests/ndt_restated.py) runs the same sweeps with the same expressions.
-__device__ __forceinline__ void jacobi3(double (&a)[3][3], double (&v)[3][3]) {
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) v[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < kNdtJacobiSweeps; ++sweep) {
-#pragma unroll
-    for (int pq = 0; pq < 3; ++pq) {
-      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
-      const double apq = a[p][q];
-      if (apq == 0.0) continue;
-      const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-      const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-      const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-      const int r = 3 - p - q;
-      const double arp = a[r][p], arq = a[r][q];
-      a[p][p] = a[p][p] - t * apq;
-      a[q][q] = a[q][q] + t * apq;
-      a[p][q] = a[q][p] = 0.0;
-      a[r][p] = a[p][r] = c * arp - s * arq;
-      a[r][q] = a[q][r] = s * arp + c * arq;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const double vkp = v[k][p], vkq = v[k][q];
-        v[k][p] = c * vkp - s * vkq;
-        v[k][q] = s * vkp + c * vkq;
-      }
-    }
-  }
-}
+// (the cells' eigen-decomposition, jacobi3: icp_jacobi3.h -- shared with icp_normals.hip)
 
 // one lane per cell (the first sorted position of its points); every cell's record goes to slot slots[i]
 __global__ __launch_bounds__(256) void ndt_cell_kernel(const float4* __restrict__ pts, const int* __restrict__ keys,

@@ -672,7 +672,7 @@ int icpgpu_destroy(icpgpu_ctx* c) {
     release(*b);
   for (DeviceBuf* b : {&c->search.cloud.buf, &c->search.queries, &c->search.idx, &c->search.d2, &c->search.n_found, &c->search.far,
                        &c->search.counts, &c->search.longs, &c->search.row_start, &c->search.scratch_start, &c->search.scan,
-                       &c->search.scratch, &c->search.totals, &c->search.row_start64})
+                       &c->search.scratch, &c->search.totals, &c->search.row_start64, &c->search.normals, &c->search.moments})
     release(*b);
   for (GridIndex* G : {&c->grid, &c->src_grid, &c->map.grid, &c->outlier.grid, &c->search.grid}) {
     release(G->sorted);

@@ -85,6 +85,49 @@ int deliver(icpgpu_ctx* c, const Delivery* parts, int n_parts) {
   return ICPGPU_OK;
 }
 
+// Radius search, first half, queued: the rows' lengths, their scans and the totals (launch_search_radius_count) for n_q > 0 queries.
+// shells / r2: what the second half (launch_search_radius_fill) must be given again.
+int queue_radius_count(icpgpu_ctx* c, const float4* d_queries, size_t n_q, double radius, int max_nn, int& shells, float& r2) {
+  auto& S = c->search;
+  const size_t rows = n_q + 1;
+  int rc;
+  if ((rc = ensure(c, S.counts, rows * sizeof(int)))) return rc;
+  if ((rc = ensure(c, S.longs, rows * sizeof(int)))) return rc;
+  if ((rc = ensure(c, S.row_start, rows * sizeof(int)))) return rc;
+  if ((rc = ensure(c, S.scratch_start, rows * sizeof(int)))) return rc;
+  if ((rc = ensure(c, S.scan, exclusive_scan_scratch_ints((int)rows) * sizeof(int)))) return rc;
+  if ((rc = ensure(c, S.totals, 2 * sizeof(unsigned long long)))) return rc;
+  if ((rc = ensure(c, S.row_start64, rows * sizeof(long long)))) return rc;
+  const SearchView v = view_of(c);
+  r2 = (float)(radius * radius);
+  // the cube of `shells` cells around a query's cell contains its ball (shells * h * kGridSafety >= radius: the grid search's bound);
+  // a ball of more than kSearchRadiusShells cells is searched without the grid
+  shells = -1;
+  if (v.sorted) {
+    const double s = std::ceil(radius / ((double)v.g.h * (double)kGridSafety));
+    if (s <= (double)kSearchRadiusShells) shells = (int)s;
+  }
+  HIP_TRY(c, launch_search_radius_count(d_queries, (int)n_q, v.cloud, S.n_finite > 0 ? v.n : 0, v.sorted, v.cell_start, v.g, shells, r2, max_nn,
+                                        static_cast<int*>(S.counts.ptr), static_cast<int*>(S.longs.ptr), static_cast<int*>(S.row_start.ptr),
+                                        static_cast<int*>(S.scratch_start.ptr), static_cast<int*>(S.scan.ptr),
+                                        static_cast<unsigned long long*>(S.totals.ptr), static_cast<long long*>(S.row_start64.ptr), c->stream));
+  return ICPGPU_OK;
+}
+
+// ... second half, queued: `total` (> 0) neighbours into S.idx / S.d2, `scratch_words` 64-bit words of scratch for the long rows
+int queue_radius_fill(icpgpu_ctx* c, const float4* d_queries, size_t n_q, int shells, float r2, size_t total, size_t scratch_words) {
+  auto& S = c->search;
+  int rc;
+  if ((rc = ensure(c, S.idx, total * sizeof(int32_t)))) return rc;
+  if ((rc = ensure(c, S.d2, total * sizeof(float)))) return rc;
+  if ((rc = ensure(c, S.scratch, std::max<size_t>(scratch_words, 1) * sizeof(unsigned long long)))) return rc;
+  const SearchView v = view_of(c);
+  HIP_TRY(c, launch_search_radius_fill(d_queries, (int)n_q, v.cloud, v.n, v.sorted, v.cell_start, v.g, shells, r2, static_cast<int*>(S.row_start.ptr),
+                                       static_cast<int*>(S.scratch_start.ptr), static_cast<unsigned long long*>(S.scratch.ptr),
+                                       static_cast<int32_t*>(S.idx.ptr), static_cast<float*>(S.d2.ptr), c->stream));
+  return ICPGPU_OK;
+}
+
 }  // namespace
 }  // namespace icpgpu_impl
 
@@ -165,28 +208,9 @@ int icpgpu_search_radius(icpgpu_ctx* c, const float* queries_xyzw, size_t n_q, d
   row_start[0] = 0;
   if (n_q == 0) return ICPGPU_OK;
   const size_t rows = n_q + 1;
-  if ((rc = ensure(c, S.counts, rows * sizeof(int)))) return rc;
-  if ((rc = ensure(c, S.longs, rows * sizeof(int)))) return rc;
-  if ((rc = ensure(c, S.row_start, rows * sizeof(int)))) return rc;
-  if ((rc = ensure(c, S.scratch_start, rows * sizeof(int)))) return rc;
-  if ((rc = ensure(c, S.scan, exclusive_scan_scratch_ints((int)rows) * sizeof(int)))) return rc;
-  if ((rc = ensure(c, S.totals, 2 * sizeof(unsigned long long)))) return rc;
-  if ((rc = ensure(c, S.row_start64, rows * sizeof(long long)))) return rc;
-  const SearchView v = view_of(c);
-  const float r2 = (float)(radius * radius);
-  // the cube of `shells` cells around a query's cell contains its ball (shells * h * kGridSafety >= radius: the grid search's bound);
-  // a ball of more than kSearchRadiusShells cells is searched without the grid
-  int shells = -1;
-  if (v.sorted) {
-    const double s = std::ceil(radius / ((double)v.g.h * (double)kGridSafety));
-    if (s <= (double)kSearchRadiusShells) shells = (int)s;
-  }
-  int* d_row_start = static_cast<int*>(S.row_start.ptr);
-  int* d_scratch_start = static_cast<int*>(S.scratch_start.ptr);
-  HIP_TRY(c, launch_search_radius_count(d_queries, (int)n_q, v.cloud, S.n_finite > 0 ? v.n : 0, v.sorted, v.cell_start, v.g, shells, r2, max_nn,
-                                        static_cast<int*>(S.counts.ptr), static_cast<int*>(S.longs.ptr), d_row_start, d_scratch_start,
-                                        static_cast<int*>(S.scan.ptr), static_cast<unsigned long long*>(S.totals.ptr),
-                                        static_cast<long long*>(S.row_start64.ptr), c->stream));
+  int shells;
+  float r2;
+  if ((rc = queue_radius_count(c, d_queries, n_q, radius, max_nn, shells, r2))) return rc;
   unsigned long long totals[2] = {0, 0};
   const Delivery first[2] = {{totals, S.totals.ptr, sizeof totals}, {row_start, S.row_start64.ptr, rows * sizeof(int64_t)}};
   if ((rc = deliver(c, first, 2))) return rc;
@@ -198,14 +222,70 @@ int icpgpu_search_radius(icpgpu_ctx* c, const float* queries_xyzw, size_t n_q, d
   *n_total = total;
   if (total == 0) return ICPGPU_OK;
   if (total > capacity || !idx || !d2) return fail(c, ICPGPU_ERR_INVALID_ARG, "search_radius: %zu neighbours, room for %zu", total, idx && d2 ? capacity : (size_t)0);
-  if ((rc = ensure(c, S.idx, total * sizeof(int32_t)))) return rc;
-  if ((rc = ensure(c, S.d2, total * sizeof(float)))) return rc;
-  if ((rc = ensure(c, S.scratch, std::max<size_t>((size_t)totals[1], 1) * sizeof(unsigned long long)))) return rc;
-  HIP_TRY(c, launch_search_radius_fill(d_queries, (int)n_q, v.cloud, v.n, v.sorted, v.cell_start, v.g, shells, r2, d_row_start, d_scratch_start,
-                                       static_cast<unsigned long long*>(S.scratch.ptr), static_cast<int32_t*>(S.idx.ptr),
-                                       static_cast<float*>(S.d2.ptr), c->stream));
+  if ((rc = queue_radius_fill(c, d_queries, n_q, shells, r2, total, (size_t)totals[1]))) return rc;
   const Delivery second[2] = {{idx, S.idx.ptr, total * sizeof(int32_t)}, {d2, S.d2.ptr, total * sizeof(float)}};
   return deliver(c, second, 2);
+}
+
+// pcl::NormalEstimation over the search cloud (rules: include/icpgpu.h "normal estimation").  The neighbour rows never leave the
+// device: the search's launchers write them into the search state's buffers and normals_from_rows_kernel (icp_normals.hip) reads
+// them there.  One wait per call with k (deliver), two at most with a radius: the totals that size the rows, then the results.
+int icpgpu_normal_estimation(icpgpu_ctx* c, const float* queries_xyzw, size_t n_q, int k, double radius, const float* viewpoint3, float* out_nxyzc,
+                             int32_t* n_neighbours, float* moments9) {
+  ENTER(c);
+  auto& S = c->search;
+  const float4* d_queries = nullptr;
+  int rc;
+  const bool by_k = k != 0, by_radius = radius != 0.0;
+  if (by_k == by_radius) return fail(c, ICPGPU_ERR_INVALID_ARG, "normal_estimation: exactly one of k and radius must be set (k %d, radius %g)", k, radius);
+  if (by_k && (k < 1 || k > ICPGPU_SEARCH_MAX_K)) return fail(c, ICPGPU_ERR_INVALID_ARG, "normal_estimation: k %d outside 1..%d", k, ICPGPU_SEARCH_MAX_K);
+  if (by_radius && !(std::isfinite(radius) && radius > 0.0)) return fail(c, ICPGPU_ERR_INVALID_ARG, "normal_estimation: radius must be finite and > 0");
+  float vp[3] = {0.f, 0.f, 0.f};
+  if (viewpoint3) {
+    for (int a = 0; a < 3; ++a) vp[a] = viewpoint3[a];
+    if (!std::isfinite(vp[0]) || !std::isfinite(vp[1]) || !std::isfinite(vp[2])) return fail(c, ICPGPU_ERR_INVALID_ARG, "normal_estimation: non-finite viewpoint");
+  }
+  if ((rc = stage_queries(c, "normal_estimation", queries_xyzw, n_q, d_queries))) return rc;
+  if (n_q == 0) return ICPGPU_OK;
+  if (!out_nxyzc) return fail(c, ICPGPU_ERR_INVALID_ARG, "normal_estimation: null result pointer");
+  if ((rc = ensure(c, S.normals, n_q * sizeof(float4)))) return rc;
+  if (moments9 && (rc = ensure(c, S.moments, n_q * 9 * sizeof(float)))) return rc;
+  float* d_moments = moments9 ? static_cast<float*>(S.moments.ptr) : nullptr;
+  const SearchView v = view_of(c);
+  const void* d_counts = nullptr;
+  if (by_k) {
+    const size_t cells = n_q * (size_t)k;
+    if ((rc = ensure(c, S.idx, cells * sizeof(int32_t)))) return rc;
+    if ((rc = ensure(c, S.d2, cells * sizeof(float)))) return rc;
+    if ((rc = ensure(c, S.n_found, n_q * sizeof(int32_t)))) return rc;
+    if ((rc = ensure(c, S.far, (n_q + 2) * sizeof(int)))) return rc;
+    HIP_TRY(c, launch_search_knn(d_queries, (int)n_q, v.cloud, v.n, v.sorted, v.cell_start, v.g, k, static_cast<int32_t*>(S.idx.ptr),
+                                 static_cast<float*>(S.d2.ptr), static_cast<int32_t*>(S.n_found.ptr), static_cast<int*>(S.far.ptr), c->stream));
+    HIP_TRY(c, launch_normals_from_rows(d_queries, (int)n_q, v.cloud, v.n, static_cast<const int32_t*>(S.idx.ptr), static_cast<const int32_t*>(S.n_found.ptr),
+                                        k, nullptr, vp, static_cast<float4*>(S.normals.ptr), d_moments, c->stream));
+    d_counts = S.n_found.ptr;
+  } else {
+    int shells;
+    float r2;
+    if ((rc = queue_radius_count(c, d_queries, n_q, radius, 0, shells, r2))) return rc;
+    unsigned long long totals[2] = {0, 0};
+    const Delivery first[1] = {{totals, S.totals.ptr, sizeof totals}};
+    if ((rc = deliver(c, first, 1))) return rc;
+    if (totals[0] > (unsigned long long)INT32_MAX || totals[1] > (unsigned long long)INT32_MAX)
+      return fail(c, ICPGPU_ERR_UNSUPPORTED, "normal_estimation: %llu neighbours in all, more than the int32 scans carry", totals[0]);
+    if (totals[0]) {
+      if ((rc = queue_radius_fill(c, d_queries, n_q, shells, r2, (size_t)totals[0], (size_t)totals[1]))) return rc;
+    } else if ((rc = ensure(c, S.idx, sizeof(int32_t)))) {  // (every row is empty: nothing is read through the pointer)
+      return rc;
+    }
+    HIP_TRY(c, launch_normals_from_rows(d_queries, (int)n_q, v.cloud, v.n, static_cast<const int32_t*>(S.idx.ptr), nullptr, 0,
+                                        static_cast<const int*>(S.row_start.ptr), vp, static_cast<float4*>(S.normals.ptr), d_moments, c->stream));
+    d_counts = S.counts.ptr;
+  }
+  const Delivery out[3] = {{out_nxyzc, S.normals.ptr, n_q * sizeof(float4)},
+                           {n_neighbours, d_counts, n_neighbours ? n_q * sizeof(int32_t) : 0},
+                           {moments9, d_moments, moments9 ? n_q * 9 * sizeof(float) : 0}};
+  return deliver(c, out, 3);
 }
 
 }  // extern "C"

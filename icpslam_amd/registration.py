@@ -530,6 +530,23 @@ class Context:
         self._check(rc)
         return row_start, idx, d2
 
+    # normal estimation (pcl::NormalEstimation; rules: include/icpgpu.h) ------------------------------------------------
+    def normal_estimation(self, queries, k: int = 0, radius: float = 0.0, viewpoint=(0.0, 0.0, 0.0), want_moments: bool = False,
+                          n_q: int | None = None):
+        """(normals (n_q, 4) float32 {nx, ny, nz, curvature}, n_neighbours (n_q,) int32[, moments (n_q, 9) float32]): the surface
+        normal of every query from its k nearest points of the search cloud, or from those within `radius` (exactly one of the
+        two), turned towards `viewpoint`; NaN rows where fewer than three neighbours were found.  queries None: the search cloud's
+        own points (n_q: only to test the refusal)."""
+        queries, n_q = self._search_queries(queries, n_q)
+        normals = np.empty((n_q, 4), np.float32)
+        count = np.empty(n_q, np.int32)
+        moments = np.empty((n_q, 9), np.float32) if want_moments else None
+        vp = None if viewpoint is None else np.ascontiguousarray(np.asarray(viewpoint, np.float32).reshape(3))
+        self._check(self._L.icpgpu_normal_estimation(self._h, None if queries is None else _fp(queries), n_q, int(k), float(radius),
+                                                     None if vp is None else _fp(vp), _fp(normals), count.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                     None if moments is None else _fp(moments)))
+        return (normals, count, moments) if want_moments else (normals, count)
+
     # measurement -----------------------------------------------------------------------------------------------
     def calibrate(self) -> int:
         """icpgpu_calibrate: time GICP's two inner solvers on the clouds this context holds and keep the faster (GICP_SOLVER_*)."""
@@ -808,6 +825,65 @@ class KdTree:
 KdTreeFLANN = KdTree
 
 
+class NormalEstimation:
+    """pcl::NormalEstimation<PointXYZ, Normal>-shaped front end (include/icpgpu.h, "normal estimation"): setInputCloud, optionally
+    setSearchSurface (the default is the input cloud), setKSearch or setRadiusSearch, setViewPoint, compute() -> (n, 4) float32
+    {normal_x, normal_y, normal_z, curvature}, NaN rows where PCL clears is_dense.  What compute() returns can be handed to
+    IterativeClosestPointWithNormals.setInputTarget(cloud, normals) as it is."""
+
+    def __init__(self, device_id: int = 0):
+        self._ctx = Context(device_id)
+        self._input = None
+        self._surface = None
+        self._k = 0
+        self._radius = 0.0
+        self._viewpoint = (0.0, 0.0, 0.0)
+        self._n_neighbours = np.empty(0, np.int32)
+
+    def setInputCloud(self, cloud):
+        self._input = _as_cloud(cloud).copy()
+
+    def setSearchSurface(self, cloud):
+        self._surface = None if cloud is None else _as_cloud(cloud).copy()
+
+    def setSearchMethod(self, tree=None):
+        """Accepted and ignored: the search is the library's own (exact, ascending by (d2, index))."""
+
+    def setKSearch(self, k: int):
+        self._k = int(k)
+
+    def getKSearch(self) -> int:
+        return self._k
+
+    def setRadiusSearch(self, radius: float):
+        self._radius = float(radius)
+
+    def getRadiusSearch(self) -> float:
+        return self._radius
+
+    def setViewPoint(self, vpx: float, vpy: float, vpz: float):
+        self._viewpoint = (float(vpx), float(vpy), float(vpz))
+
+    def getViewPoint(self) -> tuple:
+        return self._viewpoint
+
+    def getNeighbourCounts(self) -> np.ndarray:
+        """How many neighbours the last compute() used for every point (not PCL's)."""
+        return self._n_neighbours
+
+    def compute(self) -> np.ndarray:
+        if self._input is None:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "compute: setInputCloud first")
+        if self._surface is None:
+            self._ctx.search_set_input(self._input)
+            queries = None
+        else:
+            self._ctx.search_set_input(self._surface)
+            queries = self._input
+        normals, self._n_neighbours = self._ctx.normal_estimation(queries, self._k, self._radius, self._viewpoint)
+        return normals
+
+
 class IterativeClosestPoint:
     """pcl::IterativeClosestPoint<PointXYZ, PointXYZ>-shaped front end (same method names as the reference uses):
     point-to-point ICP, the solver BASELINE.json's north_star specifies.  The class the reference literally instantiates
@@ -1002,7 +1078,7 @@ class IterativeClosestPointWithNormals(IterativeClosestPoint):
     """pcl::IterativeClosestPointWithNormals<PointNormal, PointNormal>-shaped front end (TransformationEstimationPointToPlaneLLS): the
     point-to-point loop with the linearised point-to-plane solve.  setInputTarget(cloud, normals) hands the target's normals over as
     a PointNormal cloud carries them; without them the target's normals are estimated on the device (GICP's plane: include/icpgpu.h,
-    ICPGPU_P2PLANE -- not pcl::NormalEstimation's)."""
+    ICPGPU_P2PLANE -- not pcl::NormalEstimation's: the NormalEstimation class above computes those)."""
 
     METHOD = _lib.P2PLANE
 

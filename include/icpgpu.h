@@ -55,7 +55,8 @@ extern "C" {
  * icpgpu_correspondences, icpgpu_rejector_stats, and reciprocal correspondences -- icpgpu_set_reciprocal_correspondences,
  * icpgpu_get_reciprocal_correspondences, icpgpu_reciprocal_stats, and the outlier filters -- icpgpu_statistical_outlier_removal,
  * icpgpu_radius_outlier_removal, their _view forms, icpgpu_outlier_stats, icpgpu_outlier_fetch, and the neighbour search --
- * icpgpu_search_set_input, icpgpu_search_size, icpgpu_search_knn, icpgpu_search_radius (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
+ * icpgpu_search_set_input, icpgpu_search_size, icpgpu_search_knn, icpgpu_search_radius, and normal estimation --
+ * icpgpu_normal_estimation (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
  * icpgpu_profile.gicp_quadratic_solves; 0.3 icpgpu_profile (sources_adopted, gicp_host_solves, gicp_solver_choice). */
 
@@ -97,7 +98,8 @@ typedef enum {
  * ICPGPU_P2PLANE (1.2) is pcl::IterativeClosestPointWithNormals with TransformationEstimationPointToPlaneLLS -- the "ICP that uses
  * the surface" the reference wonders about at icp_odometer.cpp:187: the point-to-point loop (correspondences, rejection, convergence
  * criteria, result fields) with the linearised point-to-plane solve in place of Umeyama.  The target's normals are the caller's
- * (icpgpu_set_target_normals: PCL's semantics exactly, for PointNormal clouds) or ESTIMATED on the device: NOT
+ * (icpgpu_set_target_normals: PCL's semantics exactly, for PointNormal clouds -- icpgpu_normal_estimation below computes them as
+ * pcl::NormalEstimation does, with k or a radius, a viewpoint and the curvature) or ESTIMATED on the device: NOT
  * pcl::NormalEstimation's eigen33 solve but GICP's plane -- the 20 nearest neighbours and the raw covariance computeCovariances
  * forms, the same Eigen JacobiSVD restatement, the third left singular vector (the one computeCovariances scales by epsilon), rounded
  * to float and turned towards the viewpoint (0, 0, 0) as flipNormalTowardsViewpoint does; points that get GICP's identity marker
@@ -373,6 +375,7 @@ int icpgpu_gicp_covariances(icpgpu_ctx* ctx, int of_target, double* out6);
 int icpgpu_set_target_normals(icpgpu_ctx* ctx, const float* nxyzw, size_t n);
 /* the normals P2PLANE uses for the target (of_target != 0: the caller's if set, else the estimate) or the source's estimate;
  * out_nxyzw = n float4 {nx, ny, nz, 0}, NaN for marker points (pcl::NormalEstimation's output slot; see ICPGPU_P2PLANE).
+ * (pcl::NormalEstimation itself -- k or radius neighbourhoods, a viewpoint, curvature -- is icpgpu_normal_estimation.)
  * Estimating needs >= 20 points: ICPGPU_ERR_INVALID_ARG otherwise, as icpgpu_gicp_covariances. */
 int icpgpu_normals(icpgpu_ctx* ctx, int of_target, float* out_nxyzw);
 /* the counterpart of icpgpu_reduce: over pairs of the last icpgpu_nn sweep with (double)d2 <= max_dist^2, s = T * source[i] (float),
@@ -640,6 +643,51 @@ int icpgpu_search_size(const icpgpu_ctx* ctx, size_t* n, size_t* n_finite);
 int icpgpu_search_knn(icpgpu_ctx* ctx, const float* queries_xyzw, size_t n_q, int k, int32_t* idx, float* d2, int32_t* n_found);
 int icpgpu_search_radius(icpgpu_ctx* ctx, const float* queries_xyzw, size_t n_q, double radius, int max_nn, size_t capacity,
                          int64_t* row_start, int32_t* idx, float* d2, size_t* n_total);
+
+/* ---- normal estimation (added under 1.2) --------------------------------------------------------------------------- */
+/* replaces pcl::NormalEstimation<PointXYZ, Normal>: setInputCloud, setSearchSurface, setKSearch / setRadiusSearch, setViewPoint,
+ * compute -- a surface normal and a curvature per query point from the neighbours the neighbour search finds for it.  The context's
+ * SEARCH CLOUD (icpgpu_search_set_input) is the search surface; the queries are the input cloud.  queries_xyzw == NULL means the
+ * search cloud's own points (n_q must then be 0 or n), as in icpgpu_search_knn.  Parity with PCL binaries is unpinned;
+ * tests/normals_restated.py is what the kernels are compared with, bit for bit.
+ * MODE.  Exactly one of k (1 .. ICPGPU_SEARCH_MAX_K) and radius (finite, > 0) is set, the other is 0: both set, neither set, or a
+ * value outside its range is ICPGPU_ERR_INVALID_ARG (PCL refuses both set as well).
+ * NEIGHBOURS.  For query i the neighbours j_0 .. j_(m-1) are exactly the row icpgpu_search_knn(k) returns, or the row
+ * icpgpu_search_radius(radius, max_nn = 0) returns: the same set in the same order -- ascending by the key (bits(d2) << 32 | index),
+ * d2 < r2 strict with r2 = (float)(radius * radius); a cloud point among the queries finds itself first.  The order matters: the
+ * sums below are float32 and sequential.
+ * MOMENTS.  PCL's computeMeanAndCovarianceMatrix with Matrix3f, taken about the first neighbour.  DEVIATION from PCL 1.8, which
+ * takes the moments about the origin: its float32 cancellation turns the normal of a 0.3 m planar patch 120 m from the sensor by more
+ * than a radian (0.05 rad at 50 m; tests/test_normals_host.py measures both), about the first neighbour it stays within 1e-3 rad.
+ * With K = cloud point j_0 (for a cloud's own point: the point itself) and q = cloud point j_t, for t = 0 .. m-1 in order:
+ *   dx = q.x - K.x, dy = q.y - K.y, dz = q.z - K.z; nine float32 accumulators from 0:
+ *   a0 += dx*dx, a1 += dx*dy, a2 += dx*dz, a3 += dy*dy, a4 += dy*dz, a5 += dz*dz, a6 += dx, a7 += dy, a8 += dz;
+ * then a_i /= (float)m, and xx = a0 - a6*a6, xy = a1 - a6*a7, xz = a2 - a6*a8, yy = a3 - a7*a7, yz = a4 - a7*a8, zz = a5 - a8*a8;
+ * centroid = (a6 + K.x, a7 + K.y, a8 + K.z).  Every product, sum, difference and quotient is float32 and rounded on its own.
+ * PLANE.  DEVIATION: not pcl::eigen33's closed form (its atan2f / cosf / sinf are not portable bit for bit).  The six entries are
+ * widened to float64 and decomposed by the NDT cells' cyclic Jacobi (8 sweeps over (0,1), (0,2), (1,2); a rotation whose
+ * off-diagonal entry is exactly 0 is skipped).  lambda_min is the smallest diagonal entry, the lowest index among equals; the normal
+ * is that column of V rounded to float32; tr = (xx + yy) + zz in float32; curvature = tr != 0 ? fabsf((float)lambda_min / tr) : 0
+ * (PCL's solvePlaneParameters).
+ * ORIENTATION.  flipNormalTowardsViewpoint with the QUERY point p: vx = vp.x - p.x, ...; cos = (vx*nx + vy*ny) + vz*nz in float32,
+ * every operation rounded; all three components are negated when cos < 0, cos == 0 leaves them.  viewpoint3 == NULL means (0, 0, 0);
+ * a non-finite viewpoint is ICPGPU_ERR_INVALID_ARG (DEVIATION: PCL computes on).
+ * NO NORMAL.  {nx, ny, nz, curvature} are all NaN when the query is non-finite, when m < 3 (k = 1, k = 2, an empty ball, fewer than
+ * three finite cloud points), or when one of the six covariance entries is not finite -- where PCL writes NaN and clears is_dense.
+ * Coincident neighbours are defined, not refused: the zero matrix gives V = I, the normal (1, 0, 0) before orientation, curvature 0.
+ * OUTPUT.  out_nxyzc: n_q float4 {nx, ny, nz, curvature}, required when n_q > 0 -- pcl::Normal's content; it can be handed to
+ * icpgpu_set_target_normals as it is (the fourth float is ignored there).  n_neighbours (may be NULL): n_q counts, m always, 0 for
+ * a non-finite query.  moments9 (may be NULL): n_q x {xx, xy, xz, yy, yz, zz, cx, cy, cz}; NaN when m < 3 or the query is
+ * non-finite, otherwise the computed values even where they are not finite.
+ * LIMITS.  No search cloud, a null out_nxyzc, n_q against null queries: ICPGPU_ERR_INVALID_ARG.  With a radius, neighbours beyond
+ * INT32_MAX in all: ICPGPU_ERR_UNSUPPORTED.  A cloud the grid refuses is searched without it up to 65536 points (beyond that
+ * icpgpu_search_set_input has already refused it).  n_q = 0 is ICPGPU_OK.  Radius rows of thousands of entries (a raw scan's near
+ * field) are slow, as in icpgpu_search_radius.
+ * ISOLATION.  Like the search calls: the source, the target, every grid, the covariances, P2PLANE's cached normals
+ * (icpgpu_normals), the NDT cells and the filters' results stay as they were, and the answers depend on the search cloud and the
+ * arguments alone.  One host wait per call with k, two at most with a radius. */
+int icpgpu_normal_estimation(icpgpu_ctx* ctx, const float* queries_xyzw, size_t n_q, int k, double radius, const float* viewpoint3,
+                             float* out_nxyzc, int32_t* n_neighbours, float* moments9);
 
 /* ---- the mapper's target: a one-point-per-voxel map and its "nn cloud"  -------- */
 /* replaces OctreeMapper's pcl::octree::OctreePointCloudSearch map

@@ -465,7 +465,8 @@ class GeneralizedIterativeClosestPoint : public IterativeClosestPoint<CloudT> {
 // protocol, method = ICPGPU_P2PLANE -- the point-to-point loop with the linearised point-to-plane solve (the alternative the reference
 // names at icp_odometer.cpp:187).  The clouds stay 16-byte points; a PointNormal cloud's normals come separately through
 // setTargetNormals (n float4 {nx, ny, nz, pad}, n == the target's size, valid until align() returns).  Without them the target's normals are
-// estimated on the device: GICP's plane, not pcl::NormalEstimation's solve (include/icpgpu.h, ICPGPU_P2PLANE).
+// estimated on the device: GICP's plane, not pcl::NormalEstimation's solve (include/icpgpu.h, ICPGPU_P2PLANE).  icpgpu::NormalEstimation
+// below computes pcl::NormalEstimation's normals (k or radius, viewpoint, curvature); its getNormalsXYZC() is what setTargetNormals takes.
 template <class CloudT>
 class IterativeClosestPointWithNormals : public IterativeClosestPoint<CloudT> {
  public:
@@ -756,6 +757,81 @@ class KdTree {
 }  // namespace search
 template <class CloudT>
 using KdTreeFLANN = search::KdTree<CloudT>;
+
+// pcl::NormalEstimation<PointInT, PointOutT>-shaped front end (rules and deviations: include/icpgpu.h, "normal estimation"):
+//   pcl::NormalEstimation<pcl::PointXYZ, pcl::Normal> ne;
+//     ->  icpgpu::NormalEstimation<pcl::PointCloud<pcl::PointXYZ>, pcl::PointCloud<pcl::Normal>> ne;
+//   ne.setInputCloud(cloud); ne.setSearchSurface(raw); ne.setKSearch(20) or ne.setRadiusSearch(0.5); ne.setViewPoint(x, y, z);
+//   ne.compute(normals);
+// The output point type only needs normal_x, normal_y, normal_z and curvature (pcl::Normal, pcl::PointNormal).  A point without a
+// normal (fewer than three neighbours, a non-finite point) gets NaN in all four and clears is_dense, as in PCL; a refused call
+// (both or neither of k and radius set, ...) leaves the output empty.  getNormalsXYZC() is what
+// IterativeClosestPointWithNormals::setTargetNormals takes: the chain VoxelGrid -> StatisticalOutlierRemoval -> NormalEstimation ->
+// IterativeClosestPointWithNormals stays on the device's rules end to end.
+template <class CloudInT, class CloudOutT>
+class NormalEstimation {
+ public:
+  explicit NormalEstimation(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {}
+  template <class CloudPtr>
+  void setInputCloud(const CloudPtr& cloud) { input_ = &*cloud; }
+  // the cloud the neighbours are taken from (PCL: a denser cloud than the input); without it the input cloud itself
+  template <class CloudPtr>
+  void setSearchSurface(const CloudPtr& cloud) { surface_ = &*cloud; }
+  template <class TreePtr>
+  void setSearchMethod(const TreePtr&) {}  // accepted and ignored: the search is the library's own (exact)
+  void setKSearch(int k) { k_ = k; }
+  int getKSearch() const { return k_; }
+  void setRadiusSearch(double radius) { radius_ = radius; }
+  double getRadiusSearch() const { return radius_; }
+  void setViewPoint(float vpx, float vpy, float vpz) { vp_[0] = vpx, vp_[1] = vpy, vp_[2] = vpz; }
+  void getViewPoint(float& vpx, float& vpy, float& vpz) const { vpx = vp_[0], vpy = vp_[1], vpz = vp_[2]; }
+  void compute(CloudOutT& output) {
+    normals_.clear();
+    output.points.resize(0);
+    detail::set_cloud_shape(output, 0, 0);
+    if (!input_) return;
+    static_assert(sizeof(input_->points[0]) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+    const CloudInT* surface = surface_ ? surface_ : input_;
+    const std::size_t n = input_->points.size(), ns = surface->points.size();
+    if (icpgpu_search_set_input(ctx_, ns ? reinterpret_cast<const float*>(&surface->points[0]) : nullptr, ns) != ICPGPU_OK) return;
+    normals_.resize(4 * n);
+    const float* queries = surface == input_ ? nullptr : (n ? reinterpret_cast<const float*>(&input_->points[0]) : nullptr);
+    if (surface != input_ && n == 0) return;  // (null queries would mean the surface's own points)
+    if (icpgpu_normal_estimation(ctx_, queries, n, k_, radius_, vp_, n ? &normals_[0] : nullptr, nullptr, nullptr) != ICPGPU_OK) {
+      normals_.clear();
+      return;
+    }
+    output.points.resize(n);
+    detail::set_cloud_shape(output, n, 0);
+    bool dense = true;
+    for (std::size_t i = 0; i < n; ++i) {
+      const float* v = &normals_[4 * i];
+      output.points[i].normal_x = v[0];
+      output.points[i].normal_y = v[1];
+      output.points[i].normal_z = v[2];
+      output.points[i].curvature = v[3];
+      dense = dense && v[0] == v[0] && v[1] == v[1] && v[2] == v[2] && v[3] == v[3];
+    }
+    set_dense(output, dense, 0);
+  }
+  // NOT a PCL method: the last compute()'s normals as n float4 {nx, ny, nz, curvature} (empty after a refused call)
+  const std::vector<float>& getNormalsXYZC() const { return normals_; }
+
+ private:
+  template <class C>
+  static auto set_dense(C& c, bool dense, int) -> decltype(c.is_dense = true, void()) { c.is_dense = dense; }
+  template <class C>
+  static void set_dense(C&, bool, long) {}
+
+  detail::ContextPtr ctx_holder_;
+  icpgpu_ctx* ctx_;
+  const CloudInT* input_ = nullptr;
+  const CloudInT* surface_ = nullptr;
+  int k_ = 0;
+  double radius_ = 0.0;
+  float vp_[3] = {0.f, 0.f, 0.f};
+  std::vector<float> normals_;
+};
 
 // The mapper's map (/root/reference/src/icpslam/octree_mapper.cpp:55-90): replaces the pair
 //   pcl::octree::OctreePointCloudSearch<pcl::PointXYZ>::Ptr map_octree_;  pcl::PointCloud<pcl::PointXYZ>::Ptr map_cloud_;
