@@ -23,7 +23,7 @@ GICP_INNER_EXACT, GICP_INNER_QUADRATIC = 0, 1
 GICP_SOLVER_NONE, GICP_SOLVER_HOST, GICP_SOLVER_DEVICE, GICP_SOLVER_QUADRATIC = 0, 1, 2, 3
 HEADER_VERSION = 1002          # the icpgpu.h these mirrors were written against (ICPGPU_HEADER_VERSION)
 NN_AUTO, NN_BRUTE, NN_GRID = 0, 1, 2
-REJECT_MEDIAN_DISTANCE, REJECT_TRIMMED, REJECT_ONE_TO_ONE = 1, 2, 3   # icpgpu_rejector_kind
+REJECT_MEDIAN_DISTANCE, REJECT_TRIMMED, REJECT_ONE_TO_ONE, REJECT_SURFACE_NORMAL = 1, 2, 3, 4   # icpgpu_rejector_kind
 MAX_REJECTORS = 4
 SOR_MAX_K = 63                 # ICPGPU_SOR_MAX_K
 SEARCH_MAX_K = 64              # ICPGPU_SEARCH_MAX_K
@@ -99,6 +99,8 @@ EXPORTS = [
     "icpgpu_radius_outlier_removal_view", "icpgpu_outlier_stats", "icpgpu_outlier_fetch",
     "icpgpu_search_set_input", "icpgpu_search_size", "icpgpu_search_knn", "icpgpu_search_radius",
     "icpgpu_normal_estimation",
+    "icpgpu_set_source_normals", "icpgpu_set_p2plane_symmetric", "icpgpu_get_p2plane_symmetric",
+    "icpgpu_reduce_symmetric_point_to_plane", "icpgpu_solve_symmetric_point_to_plane",
 ]
 
 _lib = None
@@ -167,6 +169,11 @@ def load():
     L.icpgpu_normals.argtypes = [vp, C.c_int, fp]
     L.icpgpu_reduce_point_to_plane.argtypes = [vp, fp, C.c_double, dp]
     L.icpgpu_solve_point_to_plane.argtypes = [dp, dp]
+    L.icpgpu_set_source_normals.argtypes = [vp, fp, C.c_size_t]
+    L.icpgpu_set_p2plane_symmetric.argtypes = [vp, C.c_int, C.c_int]
+    L.icpgpu_get_p2plane_symmetric.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.icpgpu_reduce_symmetric_point_to_plane.argtypes = [vp, fp, C.c_double, C.c_int, dp]
+    L.icpgpu_solve_symmetric_point_to_plane.argtypes = [dp, dp]
     L.icpgpu_set_ndt_params.argtypes = [vp, C.c_double, C.c_double, C.c_double]
     L.icpgpu_get_ndt_params.argtypes = [vp, dp, dp, dp]
     L.icpgpu_ndt_transformation_probability.argtypes = [vp, dp]

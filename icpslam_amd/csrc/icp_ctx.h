@@ -247,6 +247,12 @@ struct icpgpu_ctx {
   uint64_t nrm_src_version = 0, nrm_tgt_version = 0;
   GridIndex nrm_grid;
   bool nrm_supplied = false;
+  // the caller's source normals (icpgpu_set_source_normals): in force while the source's version counter equals
+  // nrm_src_user_version (0 = none) -- every call that replaces the source moves the counter on and so drops them;
+  // icpgpu_promote_source_to_target hands them to nrm_user.  The symmetric objective's switches (icpgpu_set_p2plane_symmetric).
+  DeviceBuf nrm_src_user;
+  uint64_t nrm_src_user_version = 0;
+  bool p2plane_symmetric = false, p2plane_enforce_same_direction = true;
   // NDT mode (icpgpu_ndt.cpp): parameters, the target's cells (cached per target version and resolution; 0 = none), their
   // scratch, the derivative pass's per-workgroup partials and the last alignment's transformation probability
   double ndt_resolution = 1.0, ndt_step_size = 0.1, ndt_outlier_ratio = 0.55, ndt_probability = NAN;
@@ -631,12 +637,20 @@ int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_f
 // x = (A^T A)^-1 A^T r from the 29 sums (partial-pivot LU, float64) -> Tk = constructTransformationMatrix(x); false (Tk = identity)
 // when a pivot is zero or x is not finite
 bool solve_point_to_plane(const double sums[kP2planeTerms], Mat4d& Tk);
+// the symmetric objective's: the same x, Tk = [R | 0] [I | (x3, x4, x5)] [R | 0] with R = Rz(x2) Ry(x1) Rx(x0)
+bool solve_symmetric_point_to_plane(const double sums[kP2planeTerms], Mat4d& Tk);
+// the normals of the target or the source: the caller's when set, else estimated when the cloud's are not cached -> *out (device)
+int ensure_normals(icpgpu_ctx* c, bool of_target, const float4** out);
+inline bool source_normals_supplied(const icpgpu_ctx* c) { return c->nrm_src_user_version != 0 && c->nrm_src_user_version == c->src_version; }
 // icpgpu_reject.cpp
 int gated_keys(icpgpu_ctx* c, const Xform& T, float thr, unsigned long long* keys);
 // keys path: the alignment's iterations go search -> reciprocal stage -> chain -> the method's keys reduction
 inline bool keys_stages(const icpgpu_ctx* c) { return c->n_rejectors > 0 || c->reciprocal; }
 int reciprocal_run(icpgpu_ctx* c, const Xform& T, unsigned long long* keys, float thr);
-int reject_run_chain(icpgpu_ctx* c, unsigned long long* keys, float thr);
+// T: the iteration's transform (a surface-normal stage rotates the source's normals by it).  reject_prepare: what the chain needs
+// besides keys -- both clouds' normals where it has a surface-normal stage -- brought about BEFORE the iteration's kernels are queued
+int reject_run_chain(icpgpu_ctx* c, unsigned long long* keys, float thr, const Xform& T);
+int reject_prepare(icpgpu_ctx* c);
 int reject_fetch_stats(icpgpu_ctx* c);
 int sweep_issue_rejected(icpgpu_ctx* c, const Xform& T, float thr, SweepTicket& tk);
 // icpgpu_outlier.cpp: a cloud's k-NN grid, its first cell size taken from the cloud's own box (the filters and the neighbour search)

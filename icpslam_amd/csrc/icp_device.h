@@ -14,6 +14,19 @@ __device__ __forceinline__ void xform_point(const Xform& T, float x, float y, fl
   pz = __builtin_fmaf(T.m[10], z, __builtin_fmaf(T.m[9], y, __builtin_fmaf(T.m[8], x, T.m[11])));
 }
 
+// R(T) * n: xform_point's rows without the translation (a normal is rotated, not renormalised, as PCL does)
+__device__ __forceinline__ void xform_normal(const Xform& T, float x, float y, float z, float& nx, float& ny, float& nz) {
+  nx = __builtin_fmaf(T.m[2], z, __builtin_fmaf(T.m[1], y, __fmul_rn(T.m[0], x)));
+  ny = __builtin_fmaf(T.m[6], z, __builtin_fmaf(T.m[5], y, __fmul_rn(T.m[4], x)));
+  nz = __builtin_fmaf(T.m[10], z, __builtin_fmaf(T.m[9], y, __fmul_rn(T.m[8], x)));
+}
+
+// (a.x b.x + a.y b.y) + a.z b.z, every product and sum rounded on its own: the dot of two normals as the symmetric objective and
+// the surface-normal rejector judge it
+__device__ __forceinline__ float normal_dot(float ax, float ay, float az, float bx, float by, float bz) {
+  return __fadd_rn(__fadd_rn(__fmul_rn(ax, bx), __fmul_rn(ay, by)), __fmul_rn(az, bz));
+}
+
 __device__ __forceinline__ float dist2(float qx, float qy, float qz, float px, float py, float pz) {
   const float dx = qx - px, dy = qy - py, dz = qz - pz;
   return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));

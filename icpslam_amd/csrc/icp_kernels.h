@@ -340,6 +340,12 @@ int p2plane_blocks(int n_s);
 hipError_t launch_p2plane_reduce(const float4* src, int n_s, const float4* tgt, const float4* normals, const unsigned long long* keys,
                                  const Xform& T, float thr, double* partials, double* sums_out, unsigned long long* flags,
                                  unsigned long long seq, hipStream_t stream);
+// the symmetric objective's sums in the same layout (TransformationEstimationSymmetricPointToPlaneLLS): src_normals = the source's
+// normals as stored (n_s float4; the kernel rotates them by T), v = ((p + q) x n, n), r = (q - p) . n with n = n1 + n2, or n1 - n2
+// where enforce is set and !(n1 . n2 >= 0); a pair whose n is not finite counts in [0] and [1] only.  Same partials, same final kernel.
+hipError_t launch_p2plane_sym_reduce(const float4* src, const float4* src_normals, int n_s, const float4* tgt, const float4* normals,
+                                     const unsigned long long* keys, const Xform& T, float thr, bool enforce, double* partials,
+                                     double* sums_out, unsigned long long* flags, unsigned long long seq, hipStream_t stream);
 // the p2plane final kernel alone: partials (n_blocks x 29 doubles, block-major) -> the first n_terms of the 29 sums, fixed order
 // (NDT's derivative and trial passes)
 hipError_t launch_terms29_final(const double* partials, int n_blocks, double* sums_out, unsigned long long* flags, unsigned long long seq,
@@ -347,20 +353,23 @@ hipError_t launch_terms29_final(const double* partials, int n_blocks, double* su
 
 // ---- correspondence rejectors (icp_reject.hip): stages between a key-writing search and a keys reduction ---------------------
 // A stage rewrites the keys of the pairs it rejects to kEmptyKey; a pair is alive when its key names a target and its d2 <= thr.
-static constexpr int kRejectMedian = 1, kRejectTrimmed = 2, kRejectOneToOne = 3;  // = icpgpu_rejector_kind
+static constexpr int kRejectMedian = 1, kRejectTrimmed = 2, kRejectOneToOne = 3, kRejectSurfaceNormal = 4;  // = icpgpu_rejector_kind
 static constexpr int kRejectMaxStages = 4;
 struct RejectStage {
   int kind;
   unsigned int min_corr;  // trimmed
   float ratio;            // trimmed: overlap ratio (float, as PCL holds it)
-  double factor;          // median
+  double factor;          // median: the factor; surface normal: the threshold (cosine of the largest accepted angle)
 };
 // per stage, unsigned ints of device memory: the radix select's three histograms (digits of 11, 11, 10 bits), then the statistics
 // {pairs in, pairs out, bits of the cut (float d2; 0 where a stage has none), 0}
 static constexpr int kRejectHist0 = 0, kRejectHist1 = 2048, kRejectHist2 = 4096, kRejectStats = 5120, kRejectStateInts = 5128;
-// state: n_stages x kRejectStateInts ints; winners: n_t 64-bit words (one-to-one stages only, else may be null)
+// state: n_stages x kRejectStateInts ints; winners: n_t 64-bit words (one-to-one stages only, else may be null); src_normals
+// (n_s float4, as stored), tgt_normals (n_t float4) and T (the iteration's transform: it rotates the source's normals): surface-normal
+// stages only
 hipError_t launch_reject_chain(unsigned long long* keys, int n_s, int n_t, float thr, const RejectStage* stages, int n_stages,
-                               unsigned int* state, unsigned long long* winners, hipStream_t stream);
+                               unsigned int* state, unsigned long long* winners, hipStream_t stream, const float4* src_normals = nullptr,
+                               const float4* tgt_normals = nullptr, const Xform* T = nullptr);
 // keys -> (idx, d2) for icpgpu_correspondences: idx = -1, d2 = +inf for a pair that is not alive
 hipError_t launch_reject_unpack(const unsigned long long* keys, int n, float thr, int32_t* idx, float* d2, hipStream_t stream);
 

@@ -16,7 +16,11 @@
 //   One-to-one.  reject_winner_kernel: 64-bit atomicMin of (d2 bits << 32 | source index) into winners[target index] (all ones
 //   before); reject_winner_apply_kernel keeps a pair iff it is its target's winner.
 //
-// Per stage: 4 launches (order statistic) or 2 (one-to-one); 8 B read per pair and pass, 8 B written per rejected pair by the
+//   Surface normal.  reject_normal_kernel: one launch; per alive pair the source's normal (coalesced) rotated by the iteration's T
+//   (xform_normal) and the gathered target normal; the pair stays iff (double)dot > threshold (normal_dot: float32, strict; a NaN
+//   dot is rejected).  8 B + 16 B + 16 B read per alive pair, 8 B written per rejected pair.
+//
+// Per stage: 4 launches (order statistic), 2 (one-to-one) or 1 (surface normal); 8 B read per pair and pass, 8 B written per rejected pair by the
 // apply pass; 8 B per target point set and 8 B per alive pair updated for the winner array.  The statistics of a stage (pairs
 // in, pairs out, the cut's bits) stay in device memory behind its histograms (RejectState) until the host asks for them.
 #include "icp_device.h"
@@ -211,6 +215,30 @@ __global__ __launch_bounds__(RJ_BLOCK) void reject_winner_apply_kernel(unsigned 
   block_count_add(kept, state + kRejectStats + 1);
 }
 
+__global__ __launch_bounds__(RJ_BLOCK) void reject_normal_kernel(unsigned long long* __restrict__ keys, int n, float thr, int n_t,
+                                                                 const float4* __restrict__ src_normals,
+                                                                 const float4* __restrict__ tgt_normals, Xform T, double threshold,
+                                                                 unsigned int* __restrict__ state) {
+  unsigned int alive = 0, kept = 0;
+  for (int i = blockIdx.x * RJ_BLOCK + threadIdx.x; i < n; i += gridDim.x * RJ_BLOCK) {
+    const unsigned long long key = keys[i];
+    if (!key_alive(key, thr)) continue;
+    alive += 1;
+    const unsigned int j = (unsigned int)key;
+    bool keep = false;
+    if (j < (unsigned int)n_t) {
+      const float4 a = src_normals[i], b = tgt_normals[j];
+      float n1x, n1y, n1z;
+      xform_normal(T, a.x, a.y, a.z, n1x, n1y, n1z);
+      keep = (double)normal_dot(n1x, n1y, n1z, b.x, b.y, b.z) > threshold;
+    }
+    if (keep) kept += 1;
+    else keys[i] = kEmptyKey;
+  }
+  block_count_add(alive, state + kRejectStats + 0);
+  block_count_add(kept, state + kRejectStats + 1);
+}
+
 __global__ __launch_bounds__(RJ_BLOCK) void reject_unpack_kernel(const unsigned long long* __restrict__ keys, int n, float thr,
                                                                  int32_t* __restrict__ idx, float* __restrict__ d2) {
   const int i = blockIdx.x * RJ_BLOCK + threadIdx.x;
@@ -230,7 +258,8 @@ int reject_blocks(int n) {
 }  // namespace
 
 hipError_t launch_reject_chain(unsigned long long* keys, int n_s, int n_t, float thr, const RejectStage* stages, int n_stages,
-                               unsigned int* state, unsigned long long* winners, hipStream_t stream) {
+                               unsigned int* state, unsigned long long* winners, hipStream_t stream, const float4* src_normals,
+                               const float4* tgt_normals, const Xform* T) {
   if (n_stages <= 0) return hipSuccess;
   if (n_stages > kRejectMaxStages) return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(state, 0, (size_t)n_stages * kRejectStateInts * sizeof(unsigned int), stream);
@@ -243,6 +272,9 @@ hipError_t launch_reject_chain(unsigned long long* keys, int n_s, int n_t, float
       if (n_t > 0 && (e = hipMemsetAsync(winners, 0xFF, (size_t)n_t * sizeof(unsigned long long), stream)) != hipSuccess) return e;
       hipLaunchKernelGGL(reject_winner_kernel, grid, block, 0, stream, keys, n_s, thr, n_t, winners, st);
       hipLaunchKernelGGL(reject_winner_apply_kernel, grid, block, 0, stream, keys, n_s, thr, n_t, winners, st);
+    } else if (S.kind == kRejectSurfaceNormal) {
+      if (!T || (n_s > 0 && n_t > 0 && (!src_normals || !tgt_normals))) return hipErrorInvalidValue;
+      hipLaunchKernelGGL(reject_normal_kernel, grid, block, 0, stream, keys, n_s, thr, n_t, src_normals, tgt_normals, *T, S.factor, st);
     } else {
       hipLaunchKernelGGL(reject_hist_kernel<0>, grid, block, 0, stream, keys, n_s, thr, S, st);
       hipLaunchKernelGGL(reject_hist_kernel<1>, grid, block, 0, stream, keys, n_s, thr, S, st);

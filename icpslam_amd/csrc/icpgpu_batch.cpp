@@ -112,6 +112,7 @@ int icpgpu_align_batch(icpgpu_ctx* c, size_t n_pairs, const float* const* src, c
   if (c->params.method == ICPGPU_P2PLANE) return fail(c, ICPGPU_ERR_UNSUPPORTED, "align_batch: the point-to-plane method has no batch path");
   if (c->params.method == ICPGPU_NDT) return fail(c, ICPGPU_ERR_UNSUPPORTED, "align_batch: the NDT method has no batch path");
   if (c->n_rejectors > 0) return fail(c, ICPGPU_ERR_UNSUPPORTED, "align_batch: correspondence rejectors have no batch path (the lock-step kernels fuse the reduction)");
+  if (c->p2plane_symmetric) return fail(c, ICPGPU_ERR_UNSUPPORTED, "align_batch: the symmetric point-to-plane objective has no batch path");
   if (c->reciprocal) return fail(c, ICPGPU_ERR_UNSUPPORTED, "align_batch: reciprocal correspondences have no batch path (the lock-step kernels fuse the reduction)");
   if (n_pairs == 0) return ICPGPU_OK;
   if (c->abi_result == sizeof(icpgpu_result)) return align_batch_impl(c, n_pairs, src, n_src, tgt, n_tgt, want_fitness, results);

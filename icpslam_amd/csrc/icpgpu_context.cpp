@@ -629,7 +629,7 @@ int icpgpu_destroy(icpgpu_ctx* c) {
   }
   release(c->cov_src);
   release(c->cov_tgt);
-  for (DeviceBuf* b : {&c->nrm_src, &c->nrm_tgt, &c->nrm_raw, &c->nrm_user, &c->p2plane_partials}) release(*b);
+  for (DeviceBuf* b : {&c->nrm_src, &c->nrm_tgt, &c->nrm_raw, &c->nrm_user, &c->nrm_src_user, &c->p2plane_partials}) release(*b);
   release(c->maha);
   for (DeviceBuf* b : {&c->rej_state, &c->rej_winners, &c->rej_post}) release(*b);
   for (DeviceBuf* b : {&c->rcp_state, &c->rcp_counts, &c->rcp_cell_start, &c->rcp_scan, &c->rcp_cell_of_point, &c->rcp_rank, &c->rcp_binned}) release(*b);
@@ -819,6 +819,11 @@ int icpgpu_set_target(icpgpu_ctx* c, const float* xyzw, size_t n) {
           c->src.bbox_version = 0;
           c->src_fp = fp;
           c->src_fp_version = c->src_version;
+          if (c->nrm_supplied) {  // the caller's source normals stay with the source: set_target hands the target none
+            std::swap(c->nrm_user, c->nrm_src_user);
+            c->nrm_supplied = false;
+            c->nrm_src_user_version = c->src_version;
+          }
           return ICPGPU_OK;
         }
       }
@@ -926,7 +931,11 @@ int icpgpu_cloud_sizes(const icpgpu_ctx* c, size_t* n_source, size_t* n_target) 
 namespace icpgpu_impl {
 int promote_internal(icpgpu_ctx* c) {
   if (!c->src.set) return fail(c, ICPGPU_ERR_NO_INPUT, "promote_source_to_target: no source set");
-  c->nrm_supplied = false;  // (estimated normals are per cloud version: the new target's are estimated when first needed)
+  // the caller's source normals go with their cloud and become the target's; without them the new target's normals are estimated
+  // when first needed (estimated normals are per cloud version)
+  c->nrm_supplied = source_normals_supplied(c);
+  if (c->nrm_supplied) std::swap(c->nrm_user, c->nrm_src_user);
+  c->nrm_src_user_version = 0;
   std::swap(c->src, c->tgt);
   c->tgt_fp = c->src_fp;  // (versions are re-stamped below)
   const bool fp_follows = c->src_fp_version == c->src_version;

@@ -63,12 +63,35 @@ int reciprocal_run(icpgpu_ctx* c, const Xform& T, unsigned long long* keys, floa
   return ICPGPU_OK;
 }
 
-int reject_run_chain(icpgpu_ctx* c, unsigned long long* keys, float thr) {
+static bool chain_reads_normals(const icpgpu_ctx* c) {
+  for (int s = 0; s < c->n_rejectors; ++s)
+    if (c->rejectors[s].kind == ICPGPU_REJECT_SURFACE_NORMAL) return true;
+  return false;
+}
+
+// both clouds' normals for a surface-normal stage: the caller's or the estimate (cached per cloud version: the first call pays).
+// Without a pair (an empty cloud) the stage reads none.
+static int chain_normals(icpgpu_ctx* c, const float4** src_normals, const float4** tgt_normals) {
+  *src_normals = *tgt_normals = nullptr;
+  if (!chain_reads_normals(c) || c->src.n == 0 || c->tgt.n == 0) return ICPGPU_OK;
+  const int rc = ensure_normals(c, /*of_target=*/false, src_normals);
+  return rc ? rc : ensure_normals(c, /*of_target=*/true, tgt_normals);
+}
+
+int reject_prepare(icpgpu_ctx* c) {
+  const float4 *a, *b;
+  return chain_normals(c, &a, &b);
+}
+
+int reject_run_chain(icpgpu_ctx* c, unsigned long long* keys, float thr, const Xform& T) {
   const int n = c->n_rejectors;
   if (n <= 0) return ICPGPU_OK;
   const int n_s = (int)c->src.n, n_t = (int)c->tgt.n;
   RejectStage stages[kRejectMaxStages];
   bool winners = false;
+  const float4 *src_normals, *tgt_normals;
+  int rc = chain_normals(c, &src_normals, &tgt_normals);  // (cached by reject_prepare: nothing is launched here)
+  if (rc) return rc;
   for (int s = 0; s < n; ++s) {
     const icpgpu_rejector& r = c->rejectors[s];
     stages[s].kind = r.kind;
@@ -77,11 +100,10 @@ int reject_run_chain(icpgpu_ctx* c, unsigned long long* keys, float thr) {
     stages[s].factor = r.value;
     winners = winners || r.kind == ICPGPU_REJECT_ONE_TO_ONE;
   }
-  int rc = ensure(c, c->rej_state, (size_t)kRejectMaxStages * kRejectStateInts * sizeof(unsigned int));
-  if (rc) return rc;
+  if ((rc = ensure(c, c->rej_state, (size_t)kRejectMaxStages * kRejectStateInts * sizeof(unsigned int)))) return rc;
   if (winners && (rc = ensure(c, c->rej_winners, (size_t)(n_t ? n_t : 1) * sizeof(unsigned long long)))) return rc;
   HIP_TRY(c, launch_reject_chain(keys, n_s, n_t, thr, stages, n, static_cast<unsigned int*>(c->rej_state.ptr),
-                                 static_cast<unsigned long long*>(c->rej_winners.ptr), c->stream));
+                                 static_cast<unsigned long long*>(c->rej_winners.ptr), c->stream, src_normals, tgt_normals, &T));
   c->rej_ran = n;
   return ICPGPU_OK;
 }
@@ -128,9 +150,10 @@ int sweep_issue_rejected(icpgpu_ctx* c, const Xform& T, float thr, SweepTicket& 
   int rc = ensure(c, c->keys, (size_t)(n_s ? n_s : 1) * sizeof(unsigned long long));
   if (rc) return rc;
   auto* keys = static_cast<unsigned long long*>(c->keys.ptr);
+  if ((rc = reject_prepare(c))) return rc;
   if ((rc = gated_keys(c, T, thr, keys))) return rc;
   if ((rc = reciprocal_run(c, T, keys, thr))) return rc;
-  if ((rc = reject_run_chain(c, keys, thr))) return rc;
+  if ((rc = reject_run_chain(c, keys, thr, T))) return rc;
   if ((rc = ensure(c, c->partials, (size_t)kMaxReduceBlocks * kReduceTerms * sizeof(double)))) return rc;
   const unsigned long long seq = ++c->sums_seq;
   HIP_TRY(c, launch_reduce(c->src.data(), n_s, c->tgt.data(), keys, T, thr, static_cast<double*>(c->partials.ptr), c->h_sums_dev,
@@ -152,6 +175,7 @@ static bool rejector_valid(const icpgpu_rejector& r) {
     case ICPGPU_REJECT_MEDIAN_DISTANCE: return std::isfinite(r.value) && r.value >= 0.0;
     case ICPGPU_REJECT_TRIMMED: return r.value >= 0.0 && r.value <= 1.0 && r.min_correspondences >= 0;
     case ICPGPU_REJECT_ONE_TO_ONE: return true;
+    case ICPGPU_REJECT_SURFACE_NORMAL: return std::isfinite(r.value);
     default: return false;
   }
 }
@@ -213,15 +237,16 @@ int icpgpu_correspondences(icpgpu_ctx* c, const float* T, int32_t* idx, float* d
   auto* keys = static_cast<unsigned long long*>(c->keys.ptr);
   c->prev.valid = false;  // (as an alignment's first iteration: nothing carried over)
   c->rcp_ran = false;
+  const Xform X = T ? to_xform(T) : to_xform(mat4_identity());
   if (c->tgt.n == 0) {
     HIP_TRY(c, launch_fill_keys(keys, n_s, c->stream));
   } else {
-    const Xform X = T ? to_xform(T) : to_xform(mat4_identity());
+    if ((rc = reject_prepare(c))) return rc;
     if ((rc = ensure_grid(c, thr))) return rc;
     if ((rc = gated_keys(c, X, thr, keys))) return rc;
     if ((rc = reciprocal_run(c, X, keys, thr))) return rc;
   }
-  if ((rc = reject_run_chain(c, keys, thr))) return rc;
+  if ((rc = reject_run_chain(c, keys, thr, X))) return rc;
   HIP_TRY(c, launch_reject_unpack(keys, n_s, thr, static_cast<int32_t*>(c->idx.ptr), static_cast<float*>(c->d2.ptr), c->stream));
   if (n_s) {
     HIP_TRY(c, hipMemcpyAsync(idx, c->idx.ptr, (size_t)n_s * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));

@@ -306,9 +306,38 @@ class Context:
         normals = _as_cloud(normals)
         self._check(self._L.icpgpu_set_target_normals(self._h, _fp(normals), normals.shape[0]))
 
+    def set_source_normals(self, normals):
+        """icpgpu_set_source_normals: (n_source, 4) float32 {nx, ny, nz, pad} -- read by the symmetric objective and the
+        surface-normal rejector; dropped whenever the source is replaced, moved to the target by promote_source_to_target()."""
+        normals = _as_cloud(normals)
+        self._check(self._L.icpgpu_set_source_normals(self._h, _fp(normals), normals.shape[0]))
+
+    def set_p2plane_symmetric(self, on: bool, enforce_same_direction: bool = True):
+        """icpgpu_set_p2plane_symmetric: setUseSymmetricObjective / setEnforceSameDirectionNormals of the P2PLANE method."""
+        self._check(self._L.icpgpu_set_p2plane_symmetric(self._h, int(bool(on)), int(bool(enforce_same_direction))))
+
+    def get_p2plane_symmetric(self) -> tuple:
+        """(on, enforce_same_direction)"""
+        on, enforce = C.c_int(0), C.c_int(0)
+        self._check(self._L.icpgpu_get_p2plane_symmetric(self._h, C.byref(on), C.byref(enforce)))
+        return bool(on.value), bool(enforce.value)
+
+    def reduce_symmetric_point_to_plane(self, T, max_dist: float, enforce_same_direction: bool = True) -> np.ndarray:
+        """icpgpu_reduce_symmetric_point_to_plane over the last nn() sweep: (29,) float64 in reduce_point_to_plane's layout over
+        v = ((p + q) x n, n), r = (q - p) . n."""
+        sums = np.zeros(29, np.float64)
+        Tb = _colmajor16(T)
+        self._check(self._L.icpgpu_reduce_symmetric_point_to_plane(self._h, _fp(Tb), float(max_dist), int(bool(enforce_same_direction)),
+                                                                   sums.ctypes.data_as(C.POINTER(C.c_double))))
+        return sums
+
+    def solve_symmetric_point_to_plane(self, sums):
+        """icpgpu_solve_symmetric_point_to_plane: the 4x4 incremental transform R Tr R from the 29 sums, or None when singular."""
+        return solve_symmetric_point_to_plane(sums)
+
     def normals(self, of_target: bool = True) -> np.ndarray:
-        """(n, 4) float32: the normals the point-to-plane mode uses for the target (the caller's, else estimated) or the source's
-        estimate; NaN rows for points without a neighbourhood (include/icpgpu.h, ICPGPU_P2PLANE)."""
+        """(n, 4) float32: the normals the point-to-plane mode uses for the target or the source (the caller's, else
+        estimated); NaN rows for points without a neighbourhood (include/icpgpu.h, ICPGPU_P2PLANE)."""
         n = self.n_target if of_target else self.n_source
         out = np.zeros((n, 4), np.float32)
         self._check(self._L.icpgpu_normals(self._h, int(of_target), _fp(out) if n else None))
@@ -615,17 +644,26 @@ def ndt_line_search_replay(phi_0: float, d_phi_0: float, step_init: float, step_
     return rc, step.value, trial.value
 
 
-def solve_point_to_plane(sums):
-    """icpgpu_solve_point_to_plane (host only): (AᵀA)⁻¹Aᵀr -> constructTransformationMatrix, 4x4 float64; None when singular."""
+def _solve29(name, sums):
     L = _lib.load()
     sums = np.ascontiguousarray(sums, np.float64)
     if sums.shape != (29,):
         raise ValueError("sums must be the 29 float64 terms of icpgpu_reduce_point_to_plane")
     Tk = np.zeros(16, np.float64)
     dp = C.POINTER(C.c_double)
-    if L.icpgpu_solve_point_to_plane(sums.ctypes.data_as(dp), Tk.ctypes.data_as(dp)) != 0:
+    if getattr(L, name)(sums.ctypes.data_as(dp), Tk.ctypes.data_as(dp)) != 0:
         return None
     return Tk.reshape(4, 4).T.copy()
+
+
+def solve_point_to_plane(sums):
+    """icpgpu_solve_point_to_plane (host only): (AᵀA)⁻¹Aᵀr -> constructTransformationMatrix, 4x4 float64; None when singular."""
+    return _solve29("icpgpu_solve_point_to_plane", sums)
+
+
+def solve_symmetric_point_to_plane(sums):
+    """icpgpu_solve_symmetric_point_to_plane (host only): the same x -> R Tr R, 4x4 float64; None when singular."""
+    return _solve29("icpgpu_solve_symmetric_point_to_plane", sums)
 
 
 def result_dict(res: Result, cloud):
@@ -636,7 +674,7 @@ def result_dict(res: Result, cloud):
 
 
 class CorrespondenceRejector:
-    """pcl::registration::CorrespondenceRejector-shaped base of the three rejectors a registration object's chain may hold
+    """pcl::registration::CorrespondenceRejector-shaped base of the four rejectors a registration object's chain may hold
     (addCorrespondenceRejector).  The objects carry parameters only: the stages run on the device inside align()."""
 
     KIND = 0
@@ -694,6 +732,26 @@ class CorrespondenceRejectorTrimmed(CorrespondenceRejector):
 
 class CorrespondenceRejectorOneToOne(CorrespondenceRejector):
     KIND = _lib.REJECT_ONE_TO_ONE
+
+
+class CorrespondenceRejectorSurfaceNormal(CorrespondenceRejector):
+    """A pair stays iff the dot of the source's normal (rotated by the iteration's transform) and the target's is above the
+    threshold, the cosine of the largest accepted angle (PCL's default 1.0).  The normals are the registration object's
+    (setSourceNormals / setTargetNormals) or estimated on the device."""
+
+    KIND = _lib.REJECT_SURFACE_NORMAL
+
+    def __init__(self):
+        self._threshold = 1.0
+
+    def setThreshold(self, threshold):
+        self._threshold = float(threshold)
+
+    def getThreshold(self) -> float:
+        return self._threshold
+
+    def _entry(self) -> Rejector:
+        return Rejector(self.KIND, 0, self._threshold)
 
 
 class _OutlierFilter:
@@ -909,6 +967,8 @@ class IterativeClosestPoint:
         self._fitness = None
         self._rejectors = []
         self._reciprocal = False
+        self._source_normals = None
+        self._target_normals = None
 
     # setters used by the reference -----------------------------------------------------------------------------
     def setMaximumIterations(self, n):           # icp_odometer.cpp:189 (passes a double constant)
@@ -964,17 +1024,34 @@ class IterativeClosestPoint:
 
     def setInputSource(self, cloud):             # icp_odometer.cpp:193
         self._source = _as_cloud(cloud)
+        self._source_normals = None
 
     def setInputTarget(self, cloud):             # icp_odometer.cpp:194
         self._target = _as_cloud(cloud)
+        self._target_normals = None
+
+    # the clouds' normals as PointNormal clouds carry them (after setInputSource / setInputTarget: a new cloud drops the normals it
+    # had); read by the surface-normal rejector and by IterativeClosestPointWithNormals, estimated on the device where missing
+    def setSourceNormals(self, normals):
+        self._source_normals = None if normals is None else _as_cloud(normals)
+
+    def setTargetNormals(self, normals):
+        self._target_normals = None if normals is None else _as_cloud(normals)
+
+    def _upload(self):
+        self._ctx.set_params(self._params)
+        self._ctx.set_source(self._source)
+        self._ctx.set_target(self._target)
+        if self._source_normals is not None:
+            self._ctx.set_source_normals(self._source_normals)
+        if self._target_normals is not None:
+            self._ctx.set_target_normals(self._target_normals)   # (after set_target: a new target drops the normals it had)
 
     # the call ------------------------------------------------------------------------------------------------------
     def align(self, guess=None) -> np.ndarray:   # icp_odometer.cpp:198; returns the aligned source cloud
         if self._source is None or self._target is None:
             raise IcpGpuError(_lib.ERR_NO_INPUT, "align: setInputSource/setInputTarget first")
-        self._ctx.set_params(self._params)
-        self._ctx.set_source(self._source)
-        self._ctx.set_target(self._target)
+        self._upload()
         self._set_chain()
         self._result = self._ctx.align(guess=guess, want_cloud=True)
         self._take_rejector_stats()
@@ -1084,28 +1161,29 @@ class IterativeClosestPointWithNormals(IterativeClosestPoint):
 
     def __init__(self, device_id: int = 0, method: int | None = None):
         super().__init__(device_id, method)
-        self._target_normals = None
+        self._symmetric = False
+        self._enforce_same_direction = True
 
     def setInputTarget(self, cloud, normals=None):
-        self._target = _as_cloud(cloud)
-        self._target_normals = None if normals is None else _as_cloud(normals)
+        super().setInputTarget(cloud)
+        self.setTargetNormals(normals)
+
+    # TransformationEstimationSymmetricPointToPlaneLLS in place of ...PointToPlaneLLS (PCL >= 1.10)
+    def setUseSymmetricObjective(self, on: bool):
+        self._symmetric = bool(on)
+
+    def getUseSymmetricObjective(self) -> bool:
+        return self._symmetric
+
+    def setEnforceSameDirectionNormals(self, on: bool):
+        self._enforce_same_direction = bool(on)
+
+    def getEnforceSameDirectionNormals(self) -> bool:
+        return self._enforce_same_direction
 
     def _upload(self):
-        self._ctx.set_params(self._params)
-        self._ctx.set_source(self._source)
-        self._ctx.set_target(self._target)
-        if self._target_normals is not None:
-            self._ctx.set_target_normals(self._target_normals)   # (after set_target: a new target drops the normals it had)
-
-    def align(self, guess=None) -> np.ndarray:
-        if self._source is None or self._target is None:
-            raise IcpGpuError(_lib.ERR_NO_INPUT, "align: setInputSource/setInputTarget first")
-        self._upload()
-        self._set_chain()
-        self._result = self._ctx.align(guess=guess, want_cloud=True)
-        self._take_rejector_stats()
-        self._ctx._last_user = self
-        return self._result["cloud"]
+        super()._upload()
+        self._ctx.set_p2plane_symmetric(self._symmetric, self._enforce_same_direction)
 
     def getFitnessScore(self, max_range: float = float(np.finfo(np.float64).max)) -> float:
         if self._result is not None and getattr(self._ctx, "_last_user", None) is not self:

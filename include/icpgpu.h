@@ -56,7 +56,9 @@ extern "C" {
  * icpgpu_get_reciprocal_correspondences, icpgpu_reciprocal_stats, and the outlier filters -- icpgpu_statistical_outlier_removal,
  * icpgpu_radius_outlier_removal, their _view forms, icpgpu_outlier_stats, icpgpu_outlier_fetch, and the neighbour search --
  * icpgpu_search_set_input, icpgpu_search_size, icpgpu_search_knn, icpgpu_search_radius, and normal estimation --
- * icpgpu_normal_estimation (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
+ * icpgpu_normal_estimation, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
+ * icpgpu_set_p2plane_symmetric, icpgpu_get_p2plane_symmetric, icpgpu_reduce_symmetric_point_to_plane,
+ * icpgpu_solve_symmetric_point_to_plane, ICPGPU_REJECT_SURFACE_NORMAL (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
  * icpgpu_profile.gicp_quadratic_solves; 0.3 icpgpu_profile (sources_adopted, gicp_host_solves, gicp_solver_choice). */
 
@@ -373,7 +375,17 @@ int icpgpu_gicp_covariances(icpgpu_ctx* ctx, int of_target, double* out6);
  * them).  Without them P2PLANE estimates the target's normals at its first alignment after the target changed and keeps them while
  * the target is the same cloud (a target icpgpu_set_target recognises included). */
 int icpgpu_set_target_normals(icpgpu_ctx* ctx, const float* nxyzw, size_t n);
-/* the normals P2PLANE uses for the target (of_target != 0: the caller's if set, else the estimate) or the source's estimate;
+/* the mirror for the source (added under 1.2): n float4 {nx, ny, nz, pad}, n == the source's size; copied.  They are read by the
+ * symmetric objective and by the surface-normal rejector (below), never by plain P2PLANE.  No source set: ICPGPU_ERR_NO_INPUT; another
+ * n or a null pointer: ICPGPU_ERR_INVALID_ARG.  The normals belong to the cloud they came with: every call that replaces the source
+ * drops them (icpgpu_set_source -- adopted from the voxel filter or not --, icpgpu_set_source_device,
+ * icpgpu_set_source_voxel_filtered).  icpgpu_promote_source_to_target MOVES them: they become the new target's supplied normals
+ * (as if icpgpu_set_target_normals had been called), so the odometer's per-scan protocol computes a scan's normals once; without
+ * supplied source normals promote drops the target's as before.  An icpgpu_set_target that recognises the source's content leaves
+ * them with the source and hands the target none.  Where source normals are needed and none were supplied they are estimated as
+ * P2PLANE estimates the target's (GICP's plane; >= 20 points, else ICPGPU_ERR_INVALID_ARG). */
+int icpgpu_set_source_normals(icpgpu_ctx* ctx, const float* nxyzw, size_t n);
+/* the normals P2PLANE uses for the target (of_target != 0: the caller's if set, else the estimate) or the source's (the caller's if set, else the estimate);
  * out_nxyzw = n float4 {nx, ny, nz, 0}, NaN for marker points (pcl::NormalEstimation's output slot; see ICPGPU_P2PLANE).
  * (pcl::NormalEstimation itself -- k or radius neighbourhoods, a viewpoint, curvature -- is icpgpu_normal_estimation.)
  * Estimating needs >= 20 points: ICPGPU_ERR_INVALID_ARG otherwise, as icpgpu_gicp_covariances. */
@@ -388,9 +400,42 @@ int icpgpu_reduce_point_to_plane(icpgpu_ctx* ctx, const float* T, double max_dis
  * A zero pivot or a non-finite x: ICPGPU_ERR_INVALID_ARG and Tk = identity (the singular-system rule above). */
 int icpgpu_solve_point_to_plane(const double sums[29], double Tk[16]);
 
+/* ---- symmetric objective for ICPGPU_P2PLANE (added under 1.2) ----------------------------------------------------- */
+/* replaces IterativeClosestPointWithNormals::setUseSymmetricObjective / setEnforceSameDirectionNormals over
+ * TransformationEstimationSymmetricPointToPlaneLLS (PCL >= 1.10; Rusinkiewicz 2019).  Defaults: off, enforce_same_direction = 1
+ * (PCL's).  ICPGPU_P2P_SVD, ICPGPU_GICP and ICPGPU_NDT ignore the flag (PCL's other classes have no such setter); icpgpu_align_batch
+ * returns ICPGPU_ERR_UNSUPPORTED with the flag on, as for a rejector chain.  The loop is P2PLANE's untouched -- search, accept rule,
+ * reciprocal test, rejector chain, min_correspondences, convergence criteria, result fields, fitness -- only the reduction and the
+ * solve differ.  With the flag off an alignment launches exactly the kernels it launched before the flag existed.
+ *   Per pair past the gate and the chain, with the float transform T of the iteration:
+ *     p = T * source[i] (as everywhere), q = target[j], n2 = the target's normal[j],
+ *     n1 = R(T) * the source's normal[i]: n1.x = fma(m02, nz, fma(m01, ny, m00 * nx)), ... (rotated, not renormalised, as PCL)
+ *   and then in float32, every product, sum and difference rounded on its own:
+ *     dot = (n1.x n2.x + n1.y n2.y) + n1.z n2.z
+ *     n   = (enforce_same_direction && !(dot >= 0)) ? n1 - n2 : n1 + n2          m = p + q
+ *     c   = (m.y n.z - m.z n.y,  m.z n.x - m.x n.z,  m.x n.y - m.y n.x)
+ *     r   = ((q.x - p.x) n.x + (q.y - p.y) n.y) + (q.z - p.z) n.z               v = (c.x, c.y, c.z, n.x, n.y, n.z)
+ *   sums = {count, sum d2, the 21 upper-triangle entries of sum v v^T row by row, the 6 of sum v r}: icpgpu_reduce_point_to_plane's
+ *   layout, float64 sums of float64 products of the widened floats.  A pair whose n has a non-finite component adds to count and
+ *   sum d2 only (PCL's `continue`; P2PLANE's rule).
+ *   Solve (host, float64): x = (sum v v^T)^-1 sum v r by icpgpu_solve_point_to_plane's linear algebra (the same code); with
+ *   R = Rz(x2) Ry(x1) Rx(x0) as constructTransformationMatrix writes it (correctly rounded sin / cos),
+ *   Tk = ([R | 0] * [I | (x3, x4, x5)]) * [R | 0] -- rotation R R, translation R t -- two 4x4 products in that order: PCL's
+ *   rotation_z * rotation_y * rotation_x * translation * rotation_z * rotation_y * rotation_x.  A zero or NaN pivot or a non-finite
+ *   x is the singular-system rule: ICPGPU_ERR_INVALID_ARG and Tk = identity from icpgpu_solve_symmetric_point_to_plane,
+ *   NOT_CONVERGED with the last finite transform from an alignment.
+ *   DEVIATION: PCL solves this system with ldlt().solve(); the partial-pivot LU inverse differs from it in rounding only, and one
+ *   restatement of the linear algebra serves both objectives.
+ * A null context: ICPGPU_ERR_INVALID_ARG (the getter: also when both outputs are NULL; either may be). */
+int icpgpu_set_p2plane_symmetric(icpgpu_ctx* ctx, int on, int enforce_same_direction);
+int icpgpu_get_p2plane_symmetric(const icpgpu_ctx* ctx, int* on, int* enforce_same_direction);
+/* icpgpu_reduce_point_to_plane's counterpart: the symmetric sums over the last icpgpu_nn sweep (the context's flag is not read) */
+int icpgpu_reduce_symmetric_point_to_plane(icpgpu_ctx* ctx, const float* T, double max_dist, int enforce_same_direction, double sums[29]);
+int icpgpu_solve_symmetric_point_to_plane(const double sums[29], double Tk[16]); /* host only */
+
 /* ---- correspondence rejectors (added under 1.2) ------------------------------------------------------------------- */
-/* replaces pcl::Registration::addCorrespondenceRejector with pcl::registration::CorrespondenceRejectorMedianDistance, ...Trimmed and
- * ...OneToOne (PCL 1.8).  A context holds an ordered chain of at most ICPGPU_MAX_REJECTORS rejectors, empty by default.  In every
+/* replaces pcl::Registration::addCorrespondenceRejector with pcl::registration::CorrespondenceRejectorMedianDistance, ...Trimmed,
+ * ...OneToOne and ...SurfaceNormal (PCL 1.8).  A context holds an ordered chain of at most ICPGPU_MAX_REJECTORS rejectors, empty by default.  In every
  * iteration of ICPGPU_P2P_SVD and ICPGPU_P2PLANE the chain runs on the correspondences that passed the distance gate
  * ((double)d2 <= max_correspondence_distance^2), in the order given, each stage on what the one before it left; the solve,
  * n_correspondences, mse_last, the convergence criteria and the min_correspondences test see what remains.  getFitnessScore
@@ -404,18 +449,29 @@ int icpgpu_solve_point_to_plane(const double sums[29], double Tk[16]);
  *                    (unspecified).  The sets are equal whenever the m-th and (m + 1)-th distances differ.
  *   ONE_TO_ONE       of the surviving pairs that share a target index the one with the smallest d2 stays.  DEVIATION: among equal
  *                    d2 the lowest source index (the caller's order) stays; PCL's std::sort leaves that unspecified.
+ *   SURFACE_NORMAL   value = the threshold, the cosine of the largest accepted angle between the normals (PCL's setThreshold; finite).
+ *                    With n1 = R(T) * the source's normal[i] (this iteration's T; the symmetric objective's expression above),
+ *                    n2 = the target's normal[j] and dot = (n1.x n2.x + n1.y n2.y) + n1.z n2.z in float32, a pair stays iff
+ *                    (double)dot > value: strict, as in PCL; a NaN dot is rejected.  Normals are the caller's
+ *                    (icpgpu_set_source_normals / icpgpu_set_target_normals) or estimated (>= 20 points per cloud, else the
+ *                    alignment or icpgpu_correspondences returns ICPGPU_ERR_INVALID_ARG).  One launch per stage; cut = 0.
  * With no surviving pair (n = 0) every rejector keeps nothing.  ICPGPU_GICP and ICPGPU_NDT ignore the chain, as PCL's
  * GeneralizedIterativeClosestPoint::computeTransformation and NormalDistributionsTransform never read correspondence_rejectors_.
  * icpgpu_align_batch with a non-empty chain returns ICPGPU_ERR_UNSUPPORTED for every method (the lock-step kernels fuse the
  * reduction); icpgpu_align_batch_multi runs on contexts of the library's own, which never carry a chain.  With an empty chain an
- * alignment launches exactly the kernels it launched before rejectors existed.  Not provided: the surface-normal, var-trimmed,
+ * alignment launches exactly the kernels it launched before rejectors existed.  Not provided: the var-trimmed,
  * sample-consensus and feature rejectors. */
-typedef enum { ICPGPU_REJECT_MEDIAN_DISTANCE = 1, ICPGPU_REJECT_TRIMMED = 2, ICPGPU_REJECT_ONE_TO_ONE = 3 } icpgpu_rejector_kind;
+typedef enum {
+  ICPGPU_REJECT_MEDIAN_DISTANCE = 1,
+  ICPGPU_REJECT_TRIMMED = 2,
+  ICPGPU_REJECT_ONE_TO_ONE = 3,
+  ICPGPU_REJECT_SURFACE_NORMAL = 4
+} icpgpu_rejector_kind;
 #define ICPGPU_MAX_REJECTORS 4
 typedef struct {
   int32_t kind;                /* icpgpu_rejector_kind */
   int32_t min_correspondences; /* TRIMMED only */
-  double value;                /* MEDIAN_DISTANCE: factor; TRIMMED: overlap ratio; ONE_TO_ONE: unused */
+  double value;                /* MEDIAN_DISTANCE: factor; TRIMMED: overlap ratio; ONE_TO_ONE: unused; SURFACE_NORMAL: threshold */
 } icpgpu_rejector;
 /* the whole chain at once; n = 0 clears it.  A bad kind or value, n > ICPGPU_MAX_REJECTORS or a null context:
  * ICPGPU_ERR_INVALID_ARG, and the chain in force stays. */
@@ -429,7 +485,7 @@ int icpgpu_correspondences(icpgpu_ctx* ctx, const float* T, int32_t* idx, float*
 /* per stage of the chain, for the last iteration of the context's last P2P_SVD / P2PLANE alignment or its last
  * icpgpu_correspondences call, whichever came later: the pairs that entered the stage, the pairs it kept, and its cut as a float d2
  * (MEDIAN_DISTANCE: the median, getMedianDistance(); TRIMMED: the m-th smallest d2; 0 where there is none: ONE_TO_ONE, no pair in,
- * m = 0).  *n_stages = their number; nothing is copied when it exceeds capacity.  Any output array may be NULL. */
+ * m = 0, SURFACE_NORMAL).  *n_stages = their number; nothing is copied when it exceeds capacity.  Any output array may be NULL. */
 int icpgpu_rejector_stats(const icpgpu_ctx* ctx, size_t capacity, uint32_t* pairs_in, uint32_t* pairs_out, float* cut, size_t* n_stages);
 
 /* ---- reciprocal correspondences (added under 1.2) ---------------------------------------------------------------- */

@@ -195,7 +195,7 @@ inline void release_cached_contexts() {
   }
 }
 
-// --- pcl::registration::CorrespondenceRejector and the three rejectors a registration object's chain may hold (PCL 1.8's names;
+// --- pcl::registration::CorrespondenceRejector and the four rejectors a registration object's chain may hold (PCL 1.8's names;
 // include/icpgpu.h, "correspondence rejectors", states the rules and the two deviations).  The objects carry parameters: the
 // stages run on the device inside align(), which also leaves the last iteration's median in the median rejector.
 namespace registration {
@@ -243,6 +243,20 @@ class CorrespondenceRejectorOneToOne : public CorrespondenceRejector {
   typedef std::shared_ptr<CorrespondenceRejectorOneToOne> Ptr;
   CorrespondenceRejectorOneToOne() { rejection_name_ = "CorrespondenceRejectorOneToOne"; }
   icpgpu_rejector entry() const override { return icpgpu_rejector{ICPGPU_REJECT_ONE_TO_ONE, 0, 0.0}; }
+};
+// a pair stays iff the dot of the source's normal (rotated by the iteration's transform) and the target's is above the threshold,
+// the cosine of the largest accepted angle.  The normals are the registration object's (setSourceNormals / setTargetNormals: PCL
+// reads them from PointNormal clouds) or estimated on the device.
+class CorrespondenceRejectorSurfaceNormal : public CorrespondenceRejector {
+ public:
+  typedef std::shared_ptr<CorrespondenceRejectorSurfaceNormal> Ptr;
+  CorrespondenceRejectorSurfaceNormal() : threshold_(1.0) { rejection_name_ = "CorrespondenceRejectorSurfaceNormal"; }
+  void setThreshold(double threshold) { threshold_ = threshold; }
+  double getThreshold() const { return threshold_; }
+  icpgpu_rejector entry() const override { return icpgpu_rejector{ICPGPU_REJECT_SURFACE_NORMAL, 0, threshold_}; }
+
+ private:
+  double threshold_;
 };
 }  // namespace registration
 
@@ -298,6 +312,18 @@ class IterativeClosestPoint {
       ctx_holder_ = map_context;
       ctx_ = ctx_holder_->ctx;
     }
+  }
+
+  // NOT PCL methods (PCL reads normal_x/y/z of PointNormal clouds): n float4 {nx, ny, nz, pad}, n == the cloud's size, valid until
+  // align() returns; nullptr goes back to the estimated normals.  The surface-normal rejector reads both on any registration
+  // object; IterativeClosestPointWithNormals reads the target's, and the source's for the symmetric objective.
+  void setSourceNormals(const float* nxyzw, std::size_t n) {
+    source_normals_ = nxyzw;
+    n_source_normals_ = nxyzw ? n : 0;
+  }
+  void setTargetNormals(const float* nxyzw, std::size_t n) {
+    target_normals_ = nxyzw;
+    n_target_normals_ = nxyzw ? n : 0;
   }
 
   void setFitnessWithAlign(bool on) { fitness_with_align_ = on; }  // no PCL counterpart
@@ -373,15 +399,17 @@ class IterativeClosestPoint {
       if (icpgpu_set_params(ctx_, &params_) != ICPGPU_OK) return false;
       if (params_.method == ICPGPU_NDT && !apply_ndt()) return false;
       if (icpgpu_set_target(ctx_, nt ? reinterpret_cast<const float*>(&target_->points[0]) : nullptr, nt) != ICPGPU_OK) return false;
-      // (after set_target, which drops the normals a target had: IterativeClosestPointWithNormals::setTargetNormals)
+      // (after set_target, which drops the normals a target had: setTargetNormals)
       if (target_normals_ && icpgpu_set_target_normals(ctx_, target_normals_, n_target_normals_) != ICPGPU_OK) return false;
     } else if (icpgpu_set_params(ctx_, &params_) != ICPGPU_OK ||
                (params_.method == ICPGPU_NDT && !apply_ndt())) {
       return false;
     }
     if (!apply_rejectors()) return false;
+    if (icpgpu_set_p2plane_symmetric(ctx_, p2plane_symmetric_ ? 1 : 0, enforce_same_direction_normals_ ? 1 : 0) != ICPGPU_OK) return false;
     const std::size_t ns = source_->points.size();
-    return icpgpu_set_source(ctx_, ns ? reinterpret_cast<const float*>(&source_->points[0]) : nullptr, ns) == ICPGPU_OK;
+    if (icpgpu_set_source(ctx_, ns ? reinterpret_cast<const float*>(&source_->points[0]) : nullptr, ns) != ICPGPU_OK) return false;
+    return !source_normals_ || icpgpu_set_source_normals(ctx_, source_normals_, n_source_normals_) == ICPGPU_OK;
   }
 
   // fitness through the kernel-level entry points, for a transform that is not the context's last one
@@ -431,8 +459,7 @@ class IterativeClosestPoint {
 
  protected:
   icpgpu_params params_;  // (GeneralizedIterativeClosestPoint sets its solver options here)
-  const float* target_normals_ = nullptr;  // (IterativeClosestPointWithNormals: the caller's target normals, n float4)
-  std::size_t n_target_normals_ = 0;
+  bool p2plane_symmetric_ = false, enforce_same_direction_normals_ = true;  // (IterativeClosestPointWithNormals::setUseSymmetricObjective)
   double ndt_[3] = {1.0, 0.1, 0.55};  // (NormalDistributionsTransform: resolution, step size, outlier ratio)
   int ndt_line_search_ = ICPGPU_NDT_LINE_SEARCH_PCL18;  // (NormalDistributionsTransform::setMoreThuenteLineSearch)
   icpgpu_ctx* context() const { return ctx_; }
@@ -445,6 +472,9 @@ class IterativeClosestPoint {
   bool aligned_ = false;
   bool target_from_map_ = false;
   bool fitness_with_align_ = true;
+  const float* source_normals_ = nullptr;  // the caller's normals, n float4 each (setSourceNormals / setTargetNormals)
+  const float* target_normals_ = nullptr;
+  std::size_t n_source_normals_ = 0, n_target_normals_ = 0;
   bool bound_ = false;  // the pool has been asked once for the context that suits this object's target
 };
 
@@ -464,18 +494,20 @@ class GeneralizedIterativeClosestPoint : public IterativeClosestPoint<CloudT> {
 // pcl::IterativeClosestPointWithNormals<PointNormal, PointNormal>'s counterpart (TransformationEstimationPointToPlaneLLS): same
 // protocol, method = ICPGPU_P2PLANE -- the point-to-point loop with the linearised point-to-plane solve (the alternative the reference
 // names at icp_odometer.cpp:187).  The clouds stay 16-byte points; a PointNormal cloud's normals come separately through
-// setTargetNormals (n float4 {nx, ny, nz, pad}, n == the target's size, valid until align() returns).  Without them the target's normals are
+// setTargetNormals / setSourceNormals (n float4 {nx, ny, nz, pad}, n == the cloud's size, valid until align() returns).  Without them the target's normals are
 // estimated on the device: GICP's plane, not pcl::NormalEstimation's solve (include/icpgpu.h, ICPGPU_P2PLANE).  icpgpu::NormalEstimation
 // below computes pcl::NormalEstimation's normals (k or radius, viewpoint, curvature); its getNormalsXYZC() is what setTargetNormals takes.
 template <class CloudT>
 class IterativeClosestPointWithNormals : public IterativeClosestPoint<CloudT> {
  public:
   explicit IterativeClosestPointWithNormals(int device = 0) : IterativeClosestPoint<CloudT>(device, ICPGPU_P2PLANE) {}
-  // NOT a PCL method (PCL reads normal_x/y/z of the target cloud): nxyzw = nullptr goes back to the estimated normals
-  void setTargetNormals(const float* nxyzw, std::size_t n) {
-    this->target_normals_ = nxyzw;
-    this->n_target_normals_ = nxyzw ? n : 0;
-  }
+  // (setTargetNormals / setSourceNormals: the base class's)
+  // TransformationEstimationSymmetricPointToPlaneLLS in place of ...PointToPlaneLLS (PCL >= 1.10; include/icpgpu.h, "symmetric
+  // objective"): it reads the source's normals too -- setSourceNormals, else estimated like the target's
+  void setUseSymmetricObjective(bool use_symmetric_objective) { this->p2plane_symmetric_ = use_symmetric_objective; }
+  bool getUseSymmetricObjective() const { return this->p2plane_symmetric_; }
+  void setEnforceSameDirectionNormals(bool enforce_same_direction_normals) { this->enforce_same_direction_normals_ = enforce_same_direction_normals; }
+  bool getEnforceSameDirectionNormals() const { return this->enforce_same_direction_normals_; }
 };
 
 // pcl::NormalDistributionsTransform<PointXYZ, PointXYZ>'s counterpart: same protocol, method = ICPGPU_NDT -- the target's points in
