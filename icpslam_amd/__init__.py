@@ -10,8 +10,9 @@ from ._lib import REJECT_MEDIAN_DISTANCE, REJECT_ONE_TO_ONE, REJECT_SURFACE_NORM
 from .registration import RadiusOutlierRemoval, StatisticalOutlierRemoval  # noqa: F401
 from .registration import KdTree, KdTreeFLANN  # noqa: F401
 from .registration import NormalEstimation  # noqa: F401
+from .registration import EuclideanClusterExtraction  # noqa: F401
 from .registration import Context, GeneralizedIterativeClosestPoint, IterativeClosestPoint, IterativeClosestPointWithNormals, NormalDistributionsTransform  # noqa: F401
 
-__all__ = ["Context", "IterativeClosestPoint", "GeneralizedIterativeClosestPoint", "IterativeClosestPointWithNormals", "NormalDistributionsTransform", "StatisticalOutlierRemoval", "RadiusOutlierRemoval", "KdTree", "KdTreeFLANN", "NormalEstimation", "IcpGpuError", "Params", "Result",
+__all__ = ["Context", "IterativeClosestPoint", "GeneralizedIterativeClosestPoint", "IterativeClosestPointWithNormals", "NormalDistributionsTransform", "StatisticalOutlierRemoval", "RadiusOutlierRemoval", "KdTree", "KdTreeFLANN", "NormalEstimation", "EuclideanClusterExtraction", "IcpGpuError", "Params", "Result",
            "Profile", "P2P_SVD", "GICP", "P2PLANE", "NDT", "NDT_LINE_SEARCH_PCL18", "NDT_LINE_SEARCH_MORE_THUENTE", "GICP_INNER_EXACT", "GICP_INNER_QUADRATIC",
            "NN_AUTO", "NN_BRUTE", "NN_GRID", "STATE_NAMES"]

@@ -416,6 +416,13 @@ struct icpgpu_ctx {
     DeviceBuf queries, idx, d2, n_found, far, counts, longs, row_start, scratch_start, scan, scratch, totals, row_start64;
     DeviceBuf normals, moments;  // icpgpu_normal_estimation: the results on their way to the staging buffer
   } search;
+  // euclidean clustering (icpgpu_search.cpp, icp_cluster.hip): the last call's result over the search cloud and its scratch, in
+  // buffers no other call writes -- an unfetched result outlives later search and normal calls; icpgpu_search_set_input drops it
+  struct Cluster {
+    bool have = false;
+    size_t n = 0, n_clusters = 0, n_clustered = 0;
+    DeviceBuf parent, sizes, component, labels, rank_of, csize, cstart, cstart64, keys, vals, scratch, counts;
+  } cluster;
   std::vector<icpgpu_ctx*> workers;  // align_batch: one sub-context (own stream + scratch) per host worker thread
   DeviceBuf batch_table;             // lock-step batch: the BatchPair table of the group this context leads
   std::atomic<size_t> batch_table_cells{0};   // align_batch: the largest cell table any worker has needed (icpgpu_index.cpp)

@@ -561,6 +561,19 @@ hipError_t launch_search_radius_fill(const float4* queries, int n_q, const float
                                      const GridDesc& g, int shells, float r2, const int* row_start, const int* scratch_start,
                                      unsigned long long* scratch, int32_t* idx, float* d2, hipStream_t stream);
 
+// ---- euclidean clustering (icp_cluster.hip): pcl::EuclideanClusterExtraction over the search cloud ------------------------------
+// The connected components of the graph "d2(i, j) < r2" over the cloud's finite points (shells, r2: as for the radius search;
+// any_finite: the cloud has a finite point), the components of min_size .. max_size points as clusters by size descending, the
+// lowest component name first among equal sizes.  component, labels: n ints (-1: none); cstart64: the clusters' starts, n + 1 entries
+// of which the first counts[0] + 1 count; vals[n .. n + counts[1]): the clusters' points, ascending inside a cluster; counts: 2 ints.
+// parent, sizes, rank_of: n ints each; csize, cstart: n + 1 ints; keys, vals: 2 n ints; scratch: cluster_scratch_ints(n) ints.
+// n = 0 writes counts and cstart64[0] alone.  The number of launches depends on n's bit length only.
+size_t cluster_scratch_ints(int n);
+hipError_t launch_cluster_extract(const float4* cloud, int n, bool any_finite, const float4* sorted, const int* cell_start, const GridDesc& g,
+                                  int shells, float r2, int min_size, int max_size, int* parent, int* sizes, int* component, int* labels,
+                                  int* rank_of, int* csize, int* cstart, long long* cstart64, int* keys, int* vals, int* scratch, int* counts,
+                                  hipStream_t stream);
+
 // ---- normal estimation (icp_normals.hip): pcl::NormalEstimation over neighbour rows still in device memory --------------------
 // out[i] = {nx, ny, nz, curvature} of query i from its row of cloud indices (ascending by key, as the launchers above leave them):
 // dense rows of stride k with n_found (row_start == null), or CSR rows with row_start (n_found == null).  moments (optional):

@@ -674,6 +674,9 @@ int icpgpu_destroy(icpgpu_ctx* c) {
                        &c->search.counts, &c->search.longs, &c->search.row_start, &c->search.scratch_start, &c->search.scan,
                        &c->search.scratch, &c->search.totals, &c->search.row_start64, &c->search.normals, &c->search.moments})
     release(*b);
+  for (DeviceBuf* b : {&c->cluster.parent, &c->cluster.sizes, &c->cluster.component, &c->cluster.labels, &c->cluster.rank_of, &c->cluster.csize,
+                       &c->cluster.cstart, &c->cluster.cstart64, &c->cluster.keys, &c->cluster.vals, &c->cluster.scratch, &c->cluster.counts})
+    release(*b);
   for (GridIndex* G : {&c->grid, &c->src_grid, &c->map.grid, &c->outlier.grid, &c->search.grid}) {
     release(G->sorted);
     release(G->cell_start);

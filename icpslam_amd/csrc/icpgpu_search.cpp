@@ -1,5 +1,6 @@
 // icpgpu_search.cpp -- host side of the neighbour search (pcl::search::KdTree / pcl::KdTreeFLANN: nearestKSearch, radiusSearch;
-// rules: include/icpgpu.h "neighbour search"; kernels: icp_search.hip).
+// rules: include/icpgpu.h "neighbour search"; kernels: icp_search.hip) and of what runs over the search cloud: normal estimation
+// (icp_normals.hip) and euclidean clustering (icp_cluster.hip).
 #include "icp_ctx.h"
 
 namespace icpgpu_impl {
@@ -134,7 +135,7 @@ int queue_radius_fill(icpgpu_ctx* c, const float4* d_queries, size_t n_q, int sh
 extern "C" {
 
 // Copies the cloud and builds its k-NN grid.  Nothing of the context's source, target, their grids, the covariances, the NDT cells
-// or the filters' results is touched; the previous search cloud is gone whatever this call returns.
+// or the filters' results is touched; the previous search cloud, and a clustering result over it, is gone whatever this call returns.
 int icpgpu_search_set_input(icpgpu_ctx* c, const float* xyzw, size_t n) {
   ENTER(c);
   auto& S = c->search;
@@ -142,6 +143,7 @@ int icpgpu_search_set_input(icpgpu_ctx* c, const float* xyzw, size_t n) {
   S.n = 0;
   S.n_finite = 0;
   S.grid.built = S.grid.usable = false;  // (version 0: a build never stands for the next cloud)
+  c->cluster.have = false;               // (a clustering result is a result over the cloud that goes)
   if (n && !xyzw) return fail(c, ICPGPU_ERR_INVALID_ARG, "null cloud pointer with n = %zu", n);
   if (n > (size_t)INT32_MAX - 4096) return fail(c, ICPGPU_ERR_INVALID_ARG, "cloud too large: %zu points", n);
   if (n) {
@@ -286,6 +288,70 @@ int icpgpu_normal_estimation(icpgpu_ctx* c, const float* queries_xyzw, size_t n_
                            {n_neighbours, d_counts, n_neighbours ? n_q * sizeof(int32_t) : 0},
                            {moments9, d_moments, moments9 ? n_q * 9 * sizeof(float) : 0}};
   return deliver(c, out, 3);
+}
+
+// pcl::EuclideanClusterExtraction over the search cloud (rules: include/icpgpu.h "euclidean clustering"; kernels: icp_cluster.hip).
+// Everything the call writes is the cluster state's own: the search state's scratch, and so a later search or normal estimation,
+// never meets it.  One wait (deliver): the two counts.
+int icpgpu_euclidean_cluster_extraction(icpgpu_ctx* c, double tolerance, int min_size, int max_size, size_t* n_clusters, size_t* n_clustered) {
+  ENTER(c);
+  auto& S = c->search;
+  auto& K = c->cluster;
+  K.have = false;
+  if (n_clusters) *n_clusters = 0;
+  if (n_clustered) *n_clustered = 0;
+  if (!S.set) return fail(c, ICPGPU_ERR_INVALID_ARG, "euclidean_cluster_extraction: no search cloud (icpgpu_search_set_input)");
+  if (!std::isfinite(tolerance) || tolerance < 0.0) return fail(c, ICPGPU_ERR_INVALID_ARG, "euclidean_cluster_extraction: tolerance must be finite and >= 0");
+  if (!n_clusters || !n_clustered) return fail(c, ICPGPU_ERR_INVALID_ARG, "euclidean_cluster_extraction: null n_clusters or n_clustered");
+  const size_t n = S.n, ints = std::max<size_t>(n, 1) * sizeof(int);
+  int rc;
+  for (DeviceBuf* b : {&K.parent, &K.sizes, &K.component, &K.labels, &K.rank_of})
+    if ((rc = ensure(c, *b, ints))) return rc;
+  for (DeviceBuf* b : {&K.csize, &K.cstart})
+    if ((rc = ensure(c, *b, (n + 1) * sizeof(int)))) return rc;
+  for (DeviceBuf* b : {&K.keys, &K.vals})
+    if ((rc = ensure(c, *b, 2 * ints))) return rc;
+  if ((rc = ensure(c, K.cstart64, (n + 1) * sizeof(long long)))) return rc;
+  if ((rc = ensure(c, K.scratch, cluster_scratch_ints((int)n) * sizeof(int)))) return rc;
+  if ((rc = ensure(c, K.counts, 2 * sizeof(int)))) return rc;
+  const SearchView v = view_of(c);
+  const float r2 = (float)(tolerance * tolerance);
+  int shells = -1;  // (as queue_radius_count: the cube of `shells` cells contains the ball, or the whole cloud is swept)
+  if (v.sorted) {
+    const double s = std::ceil(tolerance / ((double)v.g.h * (double)kGridSafety));
+    if (s <= (double)kSearchRadiusShells) shells = (int)s;
+  }
+  HIP_TRY(c, launch_cluster_extract(v.cloud, v.n, S.n_finite > 0, v.sorted, v.cell_start, v.g, shells, r2, min_size, max_size,
+                                    static_cast<int*>(K.parent.ptr), static_cast<int*>(K.sizes.ptr), static_cast<int*>(K.component.ptr),
+                                    static_cast<int*>(K.labels.ptr), static_cast<int*>(K.rank_of.ptr), static_cast<int*>(K.csize.ptr),
+                                    static_cast<int*>(K.cstart.ptr), static_cast<long long*>(K.cstart64.ptr), static_cast<int*>(K.keys.ptr),
+                                    static_cast<int*>(K.vals.ptr), static_cast<int*>(K.scratch.ptr), static_cast<int*>(K.counts.ptr), c->stream));
+  int counts[2] = {0, 0};
+  const Delivery out[1] = {{counts, K.counts.ptr, sizeof counts}};
+  if ((rc = deliver(c, out, 1))) return rc;
+  K.n = n;
+  K.n_clusters = (size_t)counts[0];
+  K.n_clustered = (size_t)counts[1];
+  K.have = true;
+  *n_clusters = K.n_clusters;
+  *n_clustered = K.n_clustered;
+  return ICPGPU_OK;
+}
+
+int icpgpu_cluster_fetch(icpgpu_ctx* c, size_t capacity_clusters, size_t capacity_indices, int64_t* cluster_start, int32_t* indices, int32_t* labels,
+                         int32_t* component) {
+  ENTER(c);
+  const auto& K = c->cluster;
+  if (!K.have) return fail(c, ICPGPU_ERR_INVALID_ARG, "cluster_fetch: no result (icpgpu_euclidean_cluster_extraction)");
+  if (!cluster_start) return fail(c, ICPGPU_ERR_INVALID_ARG, "cluster_fetch: null cluster_start");
+  if (K.n_clusters > capacity_clusters || K.n_clustered > capacity_indices || (K.n_clustered && !indices))
+    return fail(c, ICPGPU_ERR_INVALID_ARG, "cluster_fetch: %zu clusters of %zu points, room for %zu and %zu", K.n_clusters, K.n_clustered,
+                capacity_clusters, indices ? capacity_indices : (size_t)0);
+  const Delivery out[4] = {{cluster_start, K.cstart64.ptr, (K.n_clusters + 1) * sizeof(int64_t)},
+                           {indices, static_cast<const int*>(K.vals.ptr) + K.n, K.n_clustered * sizeof(int32_t)},
+                           {labels, K.labels.ptr, labels ? K.n * sizeof(int32_t) : 0},
+                           {component, K.component.ptr, component ? K.n * sizeof(int32_t) : 0}};
+  return deliver(c, out, 4);
 }
 
 }  // extern "C"

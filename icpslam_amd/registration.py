@@ -576,6 +576,38 @@ class Context:
                                                      None if moments is None else _fp(moments)))
         return (normals, count, moments) if want_moments else (normals, count)
 
+    # euclidean clustering (pcl::EuclideanClusterExtraction; rules: include/icpgpu.h) --------------------------------------
+    def cluster_extract_raw(self, tolerance: float, min_size: int, max_size: int) -> tuple:
+        """One icpgpu_euclidean_cluster_extraction call: (rc, n_clusters, n_clustered); the result stays in the context."""
+        nc, np_ = C.c_size_t(), C.c_size_t()
+        rc = self._L.icpgpu_euclidean_cluster_extraction(self._h, float(tolerance), int(min_size), int(max_size), C.byref(nc), C.byref(np_))
+        return rc, int(nc.value), int(np_.value)
+
+    def cluster_fetch_raw(self, capacity_clusters: int, capacity_indices: int, want_labels: bool = True, want_component: bool = True) -> tuple:
+        """One icpgpu_cluster_fetch call into arrays pre-filled with -2: (rc, cluster_start, indices, labels, component)."""
+        n_c = C.c_size_t()
+        self._L.icpgpu_search_size(self._h, C.byref(n_c), None)  # (0 without a search cloud)
+        n = int(n_c.value)
+        start = np.full(capacity_clusters + 1, -2, np.int64)
+        indices = np.full(capacity_indices, -2, np.int32)
+        labels = np.full(n, -2, np.int32) if want_labels else None
+        component = np.full(n, -2, np.int32) if want_component else None
+        ip = C.POINTER(C.c_int32)
+        rc = self._L.icpgpu_cluster_fetch(self._h, int(capacity_clusters), int(capacity_indices), start.ctypes.data_as(C.POINTER(C.c_int64)),
+                                          indices.ctypes.data_as(ip), None if labels is None else labels.ctypes.data_as(ip),
+                                          None if component is None else component.ctypes.data_as(ip))
+        return rc, start, indices, labels, component
+
+    def euclidean_cluster_extraction(self, tolerance: float, min_size: int = 1, max_size: int = 2**31 - 1) -> tuple:
+        """(cluster_start (n_clusters + 1,) int64, indices (n_clustered,) int32, labels (n,) int32, component (n,) int32): the
+        connected components of the search cloud's graph d2 < float32(tolerance^2) with min_size .. max_size points, by size
+        descending (the lowest index first among equal sizes), indices ascending inside a cluster; labels / component -1 where none."""
+        rc, n_clusters, n_clustered = self.cluster_extract_raw(tolerance, min_size, max_size)
+        self._check(rc)
+        rc, start, indices, labels, component = self.cluster_fetch_raw(n_clusters, n_clustered)
+        self._check(rc)
+        return start, indices, labels, component
+
     # measurement -----------------------------------------------------------------------------------------------
     def calibrate(self) -> int:
         """icpgpu_calibrate: time GICP's two inner solvers on the clouds this context holds and keep the faster (GICP_SOLVER_*)."""
@@ -940,6 +972,55 @@ class NormalEstimation:
             queries = self._input
         normals, self._n_neighbours = self._ctx.normal_estimation(queries, self._k, self._radius, self._viewpoint)
         return normals
+
+
+class EuclideanClusterExtraction:
+    """pcl::EuclideanClusterExtraction<PointXYZ>-shaped front end (include/icpgpu.h, "euclidean clustering"): setInputCloud,
+    setClusterTolerance, setMinClusterSize, setMaxClusterSize, extract() -> a list of int32 index arrays, the largest cluster first,
+    ascending inside a cluster.  The defaults are PCL's constructor's (0, 1, INT_MAX).  setIndices is not provided."""
+
+    def __init__(self, device_id: int = 0):
+        self._ctx = Context(device_id)
+        self._input = None
+        self._tolerance = 0.0
+        self._min = 1
+        self._max = 2**31 - 1
+        self._labels = np.empty(0, np.int32)
+
+    def setInputCloud(self, cloud):
+        self._input = _as_cloud(cloud).copy()
+
+    def setSearchMethod(self, tree=None):
+        """Accepted and ignored: the search is the library's own (exact)."""
+
+    def setClusterTolerance(self, tolerance: float):
+        self._tolerance = float(tolerance)
+
+    def getClusterTolerance(self) -> float:
+        return self._tolerance
+
+    def setMinClusterSize(self, min_cluster_size: int):
+        self._min = int(min_cluster_size)
+
+    def getMinClusterSize(self) -> int:
+        return self._min
+
+    def setMaxClusterSize(self, max_cluster_size: int):
+        self._max = int(max_cluster_size)
+
+    def getMaxClusterSize(self) -> int:
+        return self._max
+
+    def getLabels(self) -> np.ndarray:
+        """The last extract()'s cluster rank of every input point, -1 where it is in none (not PCL's)."""
+        return self._labels
+
+    def extract(self) -> list:
+        if self._input is None:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "extract: setInputCloud first")
+        self._ctx.search_set_input(self._input)
+        start, indices, self._labels, _ = self._ctx.euclidean_cluster_extraction(self._tolerance, self._min, self._max)
+        return [indices[start[r]:start[r + 1]].copy() for r in range(start.size - 1)]
 
 
 class IterativeClosestPoint:

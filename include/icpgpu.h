@@ -56,7 +56,7 @@ extern "C" {
  * icpgpu_get_reciprocal_correspondences, icpgpu_reciprocal_stats, and the outlier filters -- icpgpu_statistical_outlier_removal,
  * icpgpu_radius_outlier_removal, their _view forms, icpgpu_outlier_stats, icpgpu_outlier_fetch, and the neighbour search --
  * icpgpu_search_set_input, icpgpu_search_size, icpgpu_search_knn, icpgpu_search_radius, and normal estimation --
- * icpgpu_normal_estimation, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
+ * icpgpu_normal_estimation, and euclidean clustering -- icpgpu_euclidean_cluster_extraction, icpgpu_cluster_fetch, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
  * icpgpu_set_p2plane_symmetric, icpgpu_get_p2plane_symmetric, icpgpu_reduce_symmetric_point_to_plane,
  * icpgpu_solve_symmetric_point_to_plane, ICPGPU_REJECT_SURFACE_NORMAL (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
@@ -744,6 +744,46 @@ int icpgpu_search_radius(icpgpu_ctx* ctx, const float* queries_xyzw, size_t n_q,
  * arguments alone.  One host wait per call with k, two at most with a radius. */
 int icpgpu_normal_estimation(icpgpu_ctx* ctx, const float* queries_xyzw, size_t n_q, int k, double radius, const float* viewpoint3,
                              float* out_nxyzc, int32_t* n_neighbours, float* moments9);
+
+/* ---- euclidean clustering (added under 1.2) ------------------------------------------------------------------------ */
+/* replaces pcl::EuclideanClusterExtraction<PointXYZ>: setInputCloud, setClusterTolerance, setMinClusterSize, setMaxClusterSize,
+ * extract -- "which points of this cloud belong together".  The call works on the context's SEARCH CLOUD (icpgpu_search_set_input), as
+ * normal estimation does.  Parity with PCL binaries is unpinned; tests/cluster_restated.py is what the kernels are compared with, bit
+ * for bit -- the answer is a partition of integers and there is no tolerance anywhere.
+ * GRAPH.  The vertices are the search cloud's finite points.  Points i != j are joined iff d2(i, j) < r2, strict, with the search
+ * section's d2 = fma(dz, dz, fma(dy, dy, dx * dx)) in float32 and r2 = (float)(tolerance * tolerance), the product in double: the rule
+ * of icpgpu_search_radius.  d2 is exactly symmetric in its two points (the differences change sign, the squares do not), so the graph
+ * is undirected and its connected components are well defined.  Coincident points have d2 = 0 and are joined for any tolerance whose
+ * r2 is above 0.  With tolerance = 0 every finite point is a component of its own (PCL's radiusSearch finds nothing there and the
+ * seed stays alone).
+ * COMPONENT.  A connected component of that graph; its name is the lowest cloud index in it.  As sets these are exactly what PCL
+ * 1.8's extractEuclideanClusters collects with its seed queue (tests/cluster_restated.py: pcl_literal).  Non-finite points are in no
+ * component and cannot bridge two of them; their component and label are -1 (DEVIATION: PCL asserts or misbehaves on a non-finite
+ * seed).
+ * CLUSTER.  A component is emitted iff min_size <= size <= max_size.  All values of the two ints are accepted, as in PCL; with
+ * max_size < min_size nothing is emitted.  A component larger than max_size is dropped whole, never truncated.
+ * ORDER.  Clusters come out by size descending (PCL's extract() sorts by size); DEVIATION: among equal sizes, which PCL leaves to
+ * std::sort, the lowest component name comes first.  Inside a cluster the indices are ascending (DEVIATION: PCL 1.8 leaves them in
+ * queue order).  labels[i] is the rank of i's cluster in that order, -1 when i's component was not emitted or i is not finite.
+ * CALLS.  icpgpu_euclidean_cluster_extraction computes and KEEPS the result in buffers of its own in the context, and returns the
+ * number of clusters and of points in them after one host wait; icpgpu_cluster_fetch copies it out, any number of times.
+ * cluster_start / indices are CSR like the radius search's rows: cluster_start has n_clusters + 1 entries, cluster_start[0] = 0, and
+ * cluster r is indices[cluster_start[r], cluster_start[r + 1]).  labels and component hold n entries each; either may be NULL.
+ * ICPGPU_ERR_INVALID_ARG: no search cloud; a tolerance that is not finite or is negative; a null count pointer; a fetch without a
+ * result (none computed, the last call refused, or the search cloud replaced since); a fetch with capacity_clusters < n_clusters or
+ * capacity_indices < n_clustered, or null cluster_start, or null indices with n_clustered > 0 -- nothing is written then.  An empty
+ * cloud is ICPGPU_OK with zero clusters, and so is a cloud with no finite point.
+ * LIMITS.  A cloud the grid refuses is clustered without it (up to the 65536 points icpgpu_search_set_input admits then).  A tolerance
+ * whose ball spans more than 8 grid cells is handled as in icpgpu_search_radius: the whole cloud is swept per point, which is slow.
+ * Not provided: setIndices.
+ * ISOLATION.  The result depends on the search cloud and the three arguments alone.  The call leaves the
+ * source, the target, every grid, the covariances, the cached normals, the NDT cells, the filters' results and the search cloud itself
+ * as they were.  A later icpgpu_search_* or icpgpu_normal_estimation call does not disturb a result that has not been fetched yet;
+ * icpgpu_search_set_input drops it, whatever it returns. */
+int icpgpu_euclidean_cluster_extraction(icpgpu_ctx* ctx, double tolerance, int min_size, int max_size, size_t* n_clusters,
+                                        size_t* n_clustered);
+int icpgpu_cluster_fetch(icpgpu_ctx* ctx, size_t capacity_clusters, size_t capacity_indices, int64_t* cluster_start /* n_clusters + 1 */,
+                         int32_t* indices /* n_clustered */, int32_t* labels /* n, may be NULL */, int32_t* component /* n, may be NULL */);
 
 /* ---- the mapper's target: a one-point-per-voxel map and its "nn cloud"  -------- */
 /* replaces OctreeMapper's pcl::octree::OctreePointCloudSearch map

@@ -691,6 +691,8 @@ namespace search {
 template <class CloudT>
 class KdTree {
  public:
+  typedef std::shared_ptr<KdTree> Ptr;
+  typedef std::shared_ptr<const KdTree> ConstPtr;
   explicit KdTree(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {}
   template <class CloudPtr>
   void setInputCloud(const CloudPtr& cloud) {
@@ -863,6 +865,65 @@ class NormalEstimation {
   double radius_ = 0.0;
   float vp_[3] = {0.f, 0.f, 0.f};
   std::vector<float> normals_;
+};
+
+// pcl::PointIndices and pcl::EuclideanClusterExtraction<PointT>-shaped front end (rules and deviations: include/icpgpu.h,
+// "euclidean clustering"):
+//   pcl::EuclideanClusterExtraction<pcl::PointXYZ> ec;  ->  icpgpu::EuclideanClusterExtraction<pcl::PointCloud<pcl::PointXYZ>> ec;
+//   ec.setClusterTolerance(0.5); ec.setMinClusterSize(10); ec.setMaxClusterSize(25000); ec.setSearchMethod(tree);
+//   ec.setInputCloud(cloud); std::vector<icpgpu::PointIndices> clusters; ec.extract(clusters);
+// The clusters come out by size descending (the lowest index first among equal sizes), the indices ascending inside each; the
+// defaults are PCL's constructor's (0, 1, INT_MAX).  A refused call leaves `clusters` empty.  setIndices is not provided.
+struct PointIndices {
+  std::vector<int> indices;
+};
+
+template <class CloudT>
+class EuclideanClusterExtraction {
+ public:
+  explicit EuclideanClusterExtraction(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {}
+  template <class CloudPtr>
+  void setInputCloud(const CloudPtr& cloud) { input_ = &*cloud; }
+  template <class TreePtr>
+  void setSearchMethod(const TreePtr&) {}  // accepted and ignored: the search is the library's own (exact)
+  void setClusterTolerance(double tolerance) { tolerance_ = tolerance; }
+  double getClusterTolerance() const { return tolerance_; }
+  void setMinClusterSize(int min_cluster_size) { min_ = min_cluster_size; }
+  int getMinClusterSize() const { return min_; }
+  void setMaxClusterSize(int max_cluster_size) { max_ = max_cluster_size; }
+  int getMaxClusterSize() const { return max_; }
+  void extract(std::vector<PointIndices>& clusters) {
+    clusters.clear();
+    labels_.clear();
+    if (!input_) return;
+    static_assert(sizeof(input_->points[0]) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+    static_assert(sizeof(int) == sizeof(int32_t) && sizeof(long long) == sizeof(int64_t), "icpgpu: 32-bit int, 64-bit long long");
+    const std::size_t n = input_->points.size();
+    if (icpgpu_search_set_input(ctx_, n ? reinterpret_cast<const float*>(&input_->points[0]) : nullptr, n) != ICPGPU_OK) return;
+    std::size_t n_clusters = 0, n_clustered = 0;
+    if (icpgpu_euclidean_cluster_extraction(ctx_, tolerance_, min_, max_, &n_clusters, &n_clustered) != ICPGPU_OK) return;
+    std::vector<long long> start(n_clusters + 1, 0);
+    std::vector<int> indices(n_clustered);
+    labels_.assign(n, -1);
+    if (icpgpu_cluster_fetch(ctx_, n_clusters, n_clustered, reinterpret_cast<int64_t*>(&start[0]),
+                             n_clustered ? reinterpret_cast<int32_t*>(&indices[0]) : nullptr, n ? reinterpret_cast<int32_t*>(&labels_[0]) : nullptr,
+                             nullptr) != ICPGPU_OK) {
+      labels_.clear();
+      return;
+    }
+    clusters.resize(n_clusters);
+    for (std::size_t r = 0; r < n_clusters; ++r) clusters[r].indices.assign(indices.begin() + start[r], indices.begin() + start[r + 1]);
+  }
+  // NOT a PCL method: the last extract()'s cluster rank of every input point, -1 where it is in none (empty after a refused call)
+  const std::vector<int>& getLabels() const { return labels_; }
+
+ private:
+  detail::ContextPtr ctx_holder_;
+  icpgpu_ctx* ctx_;
+  const CloudT* input_ = nullptr;
+  double tolerance_ = 0.0;
+  int min_ = 1, max_ = 0x7FFFFFFF;
+  std::vector<int> labels_;
 };
 
 // The mapper's map (/root/reference/src/icpslam/octree_mapper.cpp:55-90): replaces the pair
