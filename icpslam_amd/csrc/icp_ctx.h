@@ -423,6 +423,20 @@ struct icpgpu_ctx {
     size_t n = 0, n_clusters = 0, n_clustered = 0;
     DeviceBuf parent, sizes, component, labels, rank_of, csize, cstart, cstart64, keys, vals, scratch, counts;
   } cluster;
+  // plane segmentation (icpgpu_sac.cpp, icp_sac.hip): the last call's result over the search cloud and its scratch, in buffers no other
+  // call writes -- an unfetched result outlives later search, normal and clustering calls; icpgpu_search_set_input drops it
+  struct Sac {
+    bool have = false;
+    size_t n = 0, n_inliers = 0, n_unrefined = 0;
+    int found = 0, iterations = 0, best_t = -1, waits = 0;
+    int sample[3] = {-1, -1, -1};
+    float thr = 0.f;  // the threshold's float32 image the kernels compare with
+    float coeff[4] = {0.f, 0.f, 0.f, 0.f}, coeff_unrefined[4] = {0.f, 0.f, 0.f, 0.f};
+    double moments[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<int32_t> counts;  // count[0 .. iterations)
+    DeviceBuf batch, flags, pos, scan, inliers, ints, sums;
+    DeviceBuf xflags, xpos, kept;  // icpgpu_sac_extract's own
+  } sac;
   std::vector<icpgpu_ctx*> workers;  // align_batch: one sub-context (own stream + scratch) per host worker thread
   DeviceBuf batch_table;             // lock-step batch: the BatchPair table of the group this context leads
   std::atomic<size_t> batch_table_cells{0};   // align_batch: the largest cell table any worker has needed (icpgpu_index.cpp)

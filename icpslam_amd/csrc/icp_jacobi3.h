@@ -1,6 +1,7 @@
 // icp_jacobi3.h -- the cyclic Jacobi eigen-decomposition of a symmetric 3x3 in float64: ONE definition for the NDT cells
-// (icp_ndt.hip: ndt_cell_kernel) and the surface normals (icp_normals.hip: normals_from_rows_kernel).  Its expressions are part of
-// both rules: tests/ndt_restated.py (_jacobi3) and tests/normals_restated.py (jacobi3) run the same sweeps with the same expressions.
+// (icp_ndt.hip: ndt_cell_kernel), the surface normals (icp_normals.hip: normals_from_rows_kernel) and, on the host, the plane
+// refinement (icpgpu_sac.cpp).  Its expressions are part of
+// those rules: tests/ndt_restated.py (_jacobi3) and tests/normals_restated.py (jacobi3) run the same sweeps with the same expressions.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,7 +14,7 @@ namespace icpgpu {
 // Cyclic Jacobi on a symmetric 3x3 (a[i][j], double): on return a's diagonal holds the eigenvalues, v's columns the eigenvectors.
 // A rotation is skipped when its off-diagonal entry is exactly zero (an axis-aligned degenerate cell keeps exact zeros).  The
 // NumPy restatement (tests/ndt_restated.py) runs the same sweeps with the same expressions.
-__device__ __forceinline__ void jacobi3(double (&a)[3][3], double (&v)[3][3]) {
+__host__ __device__ __forceinline__ void jacobi3(double (&a)[3][3], double (&v)[3][3]) {
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) v[i][j] = i == j ? 1.0 : 0.0;
   for (int sweep = 0; sweep < kNdtJacobiSweeps; ++sweep) {

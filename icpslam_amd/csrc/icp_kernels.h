@@ -574,6 +574,29 @@ hipError_t launch_cluster_extract(const float4* cloud, int n, bool any_finite, c
                                   int* rank_of, int* csize, int* cstart, long long* cstart64, int* keys, int* vals, int* scratch, int* counts,
                                   hipStream_t stream);
 
+// ---- plane segmentation (icp_sac.hip): pcl::SACSegmentation's RANSAC over the search cloud ---------------------------------------
+// A batch of kSacBatch hypotheses t0 .. t0 + 63 (hypothesis t0 + h is lane h's): the model kernel fills plane / sample and sets
+// count to 0, or to -1 for an INVALID hypothesis (and for t >= max_iterations), the counting kernel adds the inliers.  thr: the
+// smallest float32 not below the double threshold.  The counting grid is capped at kSacGridCap workgroups of kSacBlockPoints points
+// a step.  n > 0.
+static constexpr int kSacBatch = 64, kSacBlockPoints = 512, kSacGridCap = 1024;
+struct SacBatch {
+  int count[kSacBatch];
+  float4 plane[kSacBatch];
+  int sample[kSacBatch][3];
+};
+hipError_t launch_sac_batch(const float4* cloud, int n, unsigned long long seed, int t0, int max_iterations, bool use_axis, const double axis[3],
+                            double cos_eps, float thr, SacBatch* batch, hipStream_t stream);
+// flags[i] = 1 where point i is an inlier of `plane` (nowhere when !found), the other way round with `invert`
+hipError_t launch_sac_flags(const float4* cloud, int n, const float plane[4], float thr, bool found, bool invert, int* flags, hipStream_t stream);
+// the inliers of `plane` in ascending order into inliers (n ints), their number into *n_inliers; flags, pos: n ints; scan_scratch:
+// exclusive_scan_scratch_ints(n) ints
+hipError_t launch_sac_select(const float4* cloud, int n, const float plane[4], float thr, int* flags, int* pos, int* scan_scratch, int* inliers,
+                             int* n_inliers, hipStream_t stream);
+// sums12[0 .. 9): the exact sums, rounded once, of dx dx, dx dy, dx dz, dy dy, dy dz, dz dz, dx, dy, dz over the m > 0 listed points
+// about K = cloud[k_index] (d = q - K in float32); sums12[9 .. 12): K.  One workgroup, a fixed order.
+hipError_t launch_sac_sums(const float4* cloud, int n, const int* inliers, int m, int k_index, double* sums12, hipStream_t stream);
+
 // ---- normal estimation (icp_normals.hip): pcl::NormalEstimation over neighbour rows still in device memory --------------------
 // out[i] = {nx, ny, nz, curvature} of query i from its row of cloud indices (ascending by key, as the launchers above leave them):
 // dense rows of stride k with n_found (row_start == null), or CSR rows with row_start (n_found == null).  moments (optional):

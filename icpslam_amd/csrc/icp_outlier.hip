@@ -17,6 +17,7 @@
 // (icp_scan.hip) and an ordered scatter that writes the kept points where the host will read them.
 #include <hip/hip_runtime.h>
 
+#include "icp_dd.h"
 #include "icp_device.h"
 #include "icp_grid_device.h"
 #include "icp_kernels.h"
@@ -242,28 +243,7 @@ __global__ __launch_bounds__(OL_BLOCK) void ror_brute_kernel(const float4* __res
 }
 
 // ---- SOR's statistics ---------------------------------------------------------------------------------------------------
-// double-double accumulation as icp_gicp.hip has it: the high parts by TwoSum, the low parts in plain float64
-struct DD {
-  double hi, lo;
-};
-__device__ __forceinline__ void two_sum(double a, double b, double& s, double& e) {
-  s = a + b;
-  const double bb = s - a;
-  e = (a - (s - bb)) + (b - bb);
-}
-__device__ __forceinline__ void dd_add_term(DD& a, double t) {
-  double s, e;
-  two_sum(a.hi, t, s, e);
-  a.hi = s;
-  a.lo += e;
-}
-__device__ __forceinline__ DD dd_add(const DD& a, const DD& b) {
-  DD r;
-  double e;
-  two_sum(a.hi, b.hi, r.hi, e);
-  r.lo = (a.lo + b.lo) + e;
-  return r;
-}
+// (double-double accumulation: icp_dd.h, shared with the plane refinement's sums in icp_sac.hip)
 
 // ONE workgroup, a fixed order (thread t takes i = t, t + 1024, ...; then a binary tree): sum and sq_sum of dist[] as exact sums
 // rounded once, n_valid = the finite points; then the threshold, every operation an IEEE float64 operation on its own.

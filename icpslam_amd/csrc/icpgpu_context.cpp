@@ -677,6 +677,9 @@ int icpgpu_destroy(icpgpu_ctx* c) {
   for (DeviceBuf* b : {&c->cluster.parent, &c->cluster.sizes, &c->cluster.component, &c->cluster.labels, &c->cluster.rank_of, &c->cluster.csize,
                        &c->cluster.cstart, &c->cluster.cstart64, &c->cluster.keys, &c->cluster.vals, &c->cluster.scratch, &c->cluster.counts})
     release(*b);
+  for (DeviceBuf* b : {&c->sac.batch, &c->sac.flags, &c->sac.pos, &c->sac.scan, &c->sac.inliers, &c->sac.ints, &c->sac.sums, &c->sac.xflags,
+                       &c->sac.xpos, &c->sac.kept})
+    release(*b);
   for (GridIndex* G : {&c->grid, &c->src_grid, &c->map.grid, &c->outlier.grid, &c->search.grid}) {
     release(G->sorted);
     release(G->cell_start);

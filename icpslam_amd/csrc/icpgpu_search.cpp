@@ -135,7 +135,8 @@ int queue_radius_fill(icpgpu_ctx* c, const float4* d_queries, size_t n_q, int sh
 extern "C" {
 
 // Copies the cloud and builds its k-NN grid.  Nothing of the context's source, target, their grids, the covariances, the NDT cells
-// or the filters' results is touched; the previous search cloud, and a clustering result over it, is gone whatever this call returns.
+// or the filters' results is touched; the previous search cloud, and a clustering or
+// plane segmentation result over it, is gone whatever this call returns.
 int icpgpu_search_set_input(icpgpu_ctx* c, const float* xyzw, size_t n) {
   ENTER(c);
   auto& S = c->search;
@@ -144,6 +145,7 @@ int icpgpu_search_set_input(icpgpu_ctx* c, const float* xyzw, size_t n) {
   S.n_finite = 0;
   S.grid.built = S.grid.usable = false;  // (version 0: a build never stands for the next cloud)
   c->cluster.have = false;               // (a clustering result is a result over the cloud that goes)
+  c->sac.have = false;                   // (and so is a plane segmentation)
   if (n && !xyzw) return fail(c, ICPGPU_ERR_INVALID_ARG, "null cloud pointer with n = %zu", n);
   if (n > (size_t)INT32_MAX - 4096) return fail(c, ICPGPU_ERR_INVALID_ARG, "cloud too large: %zu points", n);
   if (n) {

@@ -50,6 +50,7 @@ class Context:
         self._h = h
         self.n_source = 0
         self.n_target = 0
+        self._sac_last = (0, 0)  # (n_inliers, iterations) of the last sac_segment_raw call: what sac_fetch sizes its arrays by
 
     def close(self):
         if getattr(self, "_h", None):
@@ -608,6 +609,72 @@ class Context:
         self._check(rc)
         return start, indices, labels, component
 
+    # plane segmentation (pcl::SACSegmentation, pcl::ExtractIndices; rules: include/icpgpu.h) ----------------------------------
+    def sac_segment_raw(self, distance_threshold: float, max_iterations: int = 50, probability: float = 0.99, seed: int = 0,
+                        optimize_coefficients: bool = True, axis=None, eps_angle: float = 0.0) -> tuple:
+        """One icpgpu_sac_plane_segmentation call: (rc, coefficients (4,) float32, n_inliers, iterations, found); the result stays
+        in the context."""
+        coeff = np.full(4, -2, np.float32)
+        n_in, it, found = C.c_size_t(), C.c_int32(), C.c_int32()
+        ax = None if axis is None else (C.c_double * 3)(*[float(v) for v in axis])
+        rc = self._L.icpgpu_sac_plane_segmentation(self._h, float(distance_threshold), int(max_iterations), float(probability),
+                                                   int(seed) & (2**64 - 1), int(bool(optimize_coefficients)), ax, float(eps_angle), _fp(coeff),
+                                                   C.byref(n_in), C.byref(it), C.byref(found))
+        self._sac_last = (int(n_in.value), int(it.value))
+        return rc, coeff, int(n_in.value), int(it.value), int(found.value)
+
+    def sac_fetch_raw(self, capacity_inliers: int, capacity_counts: int) -> tuple:
+        """One icpgpu_sac_fetch call into arrays pre-filled with -2: (rc, dict of everything the fetch hands out)."""
+        ip = C.POINTER(C.c_int32)
+        inliers = np.full(capacity_inliers, -2, np.int32)
+        counts = np.full(capacity_counts, -2, np.int32)
+        sample = np.full(3, -2, np.int32)
+        best_t, n_unref = C.c_int32(-2), C.c_size_t(0)
+        coeff = np.full(4, -2, np.float32)
+        moments = np.full(9, -2, np.float64)
+        rc = self._L.icpgpu_sac_fetch(self._h, int(capacity_inliers), int(capacity_counts), inliers.ctypes.data_as(ip), counts.ctypes.data_as(ip),
+                                      sample.ctypes.data_as(ip), C.byref(best_t), _fp(coeff), moments.ctypes.data_as(C.POINTER(C.c_double)),
+                                      C.byref(n_unref))
+        return rc, {"inliers": inliers, "counts": counts, "sample": sample, "best_t": int(best_t.value), "coeff_unrefined": coeff,
+                    "moments": moments, "n_unrefined": int(n_unref.value)}
+
+    def sac_plane_segmentation(self, distance_threshold: float, max_iterations: int = 50, probability: float = 0.99, seed: int = 0,
+                               optimize_coefficients: bool = True, axis=None, eps_angle: float = 0.0) -> tuple:
+        """(inliers (m,) int32 ascending, coefficients (4,) float32, iterations, found) of the dominant plane of the search cloud:
+        RANSAC over counter-based samples (seed), PCL's refinement when optimize_coefficients; axis: SACMODEL_PERPENDICULAR_PLANE."""
+        rc, coeff, n_in, it, found = self.sac_segment_raw(distance_threshold, max_iterations, probability, seed, optimize_coefficients, axis,
+                                                          eps_angle)
+        self._check(rc)
+        return self.sac_fetch(n_in, it)["inliers"], coeff, it, found
+
+    def sac_fetch(self, n_inliers: int | None = None, n_counts: int | None = None) -> dict:
+        """Everything icpgpu_sac_fetch hands out of the last segmentation: inliers, counts (one per iteration), sample, best_t,
+        coeff_unrefined, moments (the refinement's nine sums), n_unrefined.  Sizes that are not given are the last call's."""
+        n_inliers = self._sac_last[0] if n_inliers is None else n_inliers
+        n_counts = self._sac_last[1] if n_counts is None else n_counts
+        rc, out = self.sac_fetch_raw(n_inliers, n_counts)
+        self._check(rc)
+        return out
+
+    def sac_extract(self, negative: bool = False, view: bool = False) -> np.ndarray:
+        """pcl::ExtractIndices over the last segmentation: the search cloud's points in (negative: not in) the inliers, in order."""
+        n_out = C.c_size_t()
+        if view:
+            ptr = C.POINTER(C.c_float)()
+            self._check(self._L.icpgpu_sac_extract_view(self._h, int(bool(negative)), C.byref(ptr), C.byref(n_out)))
+            if n_out.value == 0:
+                return np.empty((0, 4), np.float32)
+            return np.ctypeslib.as_array(ptr, shape=(n_out.value, 4)).copy()
+        out = np.empty((self.search_size()[0], 4), np.float32)
+        self._check(self._L.icpgpu_sac_extract(self._h, int(bool(negative)), _fp(out), C.byref(n_out)))
+        return out[: n_out.value].copy()
+
+    def sac_host_waits(self) -> int:
+        """The host waits of the last segmentation (icpgpu_sac_stats)."""
+        w = C.c_int32()
+        self._check(self._L.icpgpu_sac_stats(self._h, C.byref(w)))
+        return int(w.value)
+
     # measurement -----------------------------------------------------------------------------------------------
     def calibrate(self) -> int:
         """icpgpu_calibrate: time GICP's two inner solvers on the clouds this context holds and keep the faster (GICP_SOLVER_*)."""
@@ -1021,6 +1088,128 @@ class EuclideanClusterExtraction:
         self._ctx.search_set_input(self._input)
         start, indices, self._labels, _ = self._ctx.euclidean_cluster_extraction(self._tolerance, self._min, self._max)
         return [indices[start[r]:start[r + 1]].copy() for r in range(start.size - 1)]
+
+
+class SACSegmentation:
+    """pcl::SACSegmentation<PointXYZ>-shaped front end (include/icpgpu.h, "plane segmentation"): setInputCloud, setModelType
+    (SACMODEL_PLANE, SACMODEL_PERPENDICULAR_PLANE), setMethodType (SAC_RANSAC: anything else raises), setDistanceThreshold,
+    setMaxIterations, setProbability, setOptimizeCoefficients, setAxis, setEpsAngle, our own setSeed, and
+    segment() -> (inliers int32 ascending, coefficients (4,) float32; both empty when no model was found).  The defaults are PCL's
+    (threshold 0, 50 iterations, probability 0.99, optimize true).  setIndices is not provided."""
+
+    def __init__(self, device_id: int = 0):
+        self._ctx = Context(device_id)
+        self._input = None
+        self._model = _lib.SACMODEL_PLANE
+        self._threshold = 0.0
+        self._max_iterations = 50
+        self._probability = 0.99
+        self._optimize = True
+        self._axis = (0.0, 0.0, 0.0)
+        self._eps_angle = 0.0
+        self._seed = 0
+        self.iterations = 0
+
+    def setInputCloud(self, cloud):
+        self._input = _as_cloud(cloud).copy()
+
+    def setModelType(self, model: int):
+        if model not in (_lib.SACMODEL_PLANE, _lib.SACMODEL_PERPENDICULAR_PLANE):
+            raise IcpGpuError(_lib.ERR_UNSUPPORTED, "setModelType: SACMODEL_PLANE or SACMODEL_PERPENDICULAR_PLANE")
+        self._model = int(model)
+
+    def getModelType(self) -> int:
+        return self._model
+
+    def setMethodType(self, method: int):
+        if method != _lib.SAC_RANSAC:
+            raise IcpGpuError(_lib.ERR_UNSUPPORTED, "setMethodType: SAC_RANSAC is the only method")
+
+    def getMethodType(self) -> int:
+        return _lib.SAC_RANSAC
+
+    def setDistanceThreshold(self, threshold: float):
+        self._threshold = float(threshold)
+
+    def getDistanceThreshold(self) -> float:
+        return self._threshold
+
+    def setMaxIterations(self, max_iterations: int):
+        self._max_iterations = int(max_iterations)
+
+    def getMaxIterations(self) -> int:
+        return self._max_iterations
+
+    def setProbability(self, probability: float):
+        self._probability = float(probability)
+
+    def getProbability(self) -> float:
+        return self._probability
+
+    def setOptimizeCoefficients(self, optimize: bool):
+        self._optimize = bool(optimize)
+
+    def getOptimizeCoefficients(self) -> bool:
+        return self._optimize
+
+    def setAxis(self, axis):
+        self._axis = tuple(float(v) for v in np.asarray(axis, np.float64).reshape(3))
+
+    def getAxis(self) -> tuple:
+        return self._axis
+
+    def setEpsAngle(self, eps_angle: float):
+        self._eps_angle = float(eps_angle)
+
+    def getEpsAngle(self) -> float:
+        return self._eps_angle
+
+    def setSeed(self, seed: int):
+        """NOT a PCL method: the counter-based generator's seed (PCL seeds rand() with a constant)."""
+        self._seed = int(seed)
+
+    def segment(self) -> tuple:
+        if self._input is None:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "segment: setInputCloud first")
+        self._ctx.search_set_input(self._input)
+        axis = self._axis if self._model == _lib.SACMODEL_PERPENDICULAR_PLANE else None
+        inliers, coeff, self.iterations, found = self._ctx.sac_plane_segmentation(self._threshold, self._max_iterations, self._probability,
+                                                                                 self._seed, self._optimize, axis, self._eps_angle)
+        if not found:
+            return np.empty(0, np.int32), np.empty(0, np.float32)
+        return inliers, coeff
+
+
+class ExtractIndices:
+    """pcl::ExtractIndices<PointXYZ>-shaped front end: setInputCloud, setIndices, setNegative, filter() -> the cloud's points whose
+    index is (negative: is not) among the indices, in cloud order.  A plain host selection."""
+
+    def __init__(self):
+        self._input = None
+        self._indices = np.empty(0, np.int64)
+        self._negative = False
+
+    def setInputCloud(self, cloud):
+        self._input = _as_cloud(cloud).copy()
+
+    def setIndices(self, indices):
+        self._indices = np.asarray(indices, np.int64).reshape(-1)
+
+    def setNegative(self, negative: bool):
+        self._negative = bool(negative)
+
+    def getNegative(self) -> bool:
+        return self._negative
+
+    def filter(self) -> np.ndarray:
+        if self._input is None:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "filter: setInputCloud first")
+        n = self._input.shape[0]
+        if self._indices.size and (self._indices.min() < 0 or self._indices.max() >= n):
+            raise IcpGpuError(_lib.ERR_INVALID_ARG, "filter: an index outside the cloud")
+        mask = np.zeros(n, bool)
+        mask[self._indices] = True
+        return self._input[~mask if self._negative else mask].copy()
 
 
 class IterativeClosestPoint:

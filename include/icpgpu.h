@@ -56,7 +56,8 @@ extern "C" {
  * icpgpu_get_reciprocal_correspondences, icpgpu_reciprocal_stats, and the outlier filters -- icpgpu_statistical_outlier_removal,
  * icpgpu_radius_outlier_removal, their _view forms, icpgpu_outlier_stats, icpgpu_outlier_fetch, and the neighbour search --
  * icpgpu_search_set_input, icpgpu_search_size, icpgpu_search_knn, icpgpu_search_radius, and normal estimation --
- * icpgpu_normal_estimation, and euclidean clustering -- icpgpu_euclidean_cluster_extraction, icpgpu_cluster_fetch, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
+ * icpgpu_normal_estimation, and euclidean clustering -- icpgpu_euclidean_cluster_extraction, icpgpu_cluster_fetch, and plane segmentation --
+ * icpgpu_sac_plane_segmentation, icpgpu_sac_fetch, icpgpu_sac_stats, icpgpu_sac_extract, icpgpu_sac_extract_view, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
  * icpgpu_set_p2plane_symmetric, icpgpu_get_p2plane_symmetric, icpgpu_reduce_symmetric_point_to_plane,
  * icpgpu_solve_symmetric_point_to_plane, ICPGPU_REJECT_SURFACE_NORMAL (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
@@ -784,6 +785,78 @@ int icpgpu_euclidean_cluster_extraction(icpgpu_ctx* ctx, double tolerance, int m
                                         size_t* n_clustered);
 int icpgpu_cluster_fetch(icpgpu_ctx* ctx, size_t capacity_clusters, size_t capacity_indices, int64_t* cluster_start /* n_clusters + 1 */,
                          int32_t* indices /* n_clustered */, int32_t* labels /* n, may be NULL */, int32_t* component /* n, may be NULL */);
+
+/* ---- plane segmentation (added under 1.2) --------------------------------------------------------------------------- */
+/* replaces pcl::SACSegmentation<PointXYZ> with SACMODEL_PLANE or SACMODEL_PERPENDICULAR_PLANE and SAC_RANSAC -- setInputCloud,
+ * setDistanceThreshold, setMaxIterations, setProbability, setOptimizeCoefficients, setAxis, setEpsAngle, segment -- and
+ * pcl::ExtractIndices<PointXYZ> over its result: "which points lie on the dominant plane", the ground of a driving scan, to be taken
+ * away before icpgpu_euclidean_cluster_extraction.  The call works on the context's SEARCH CLOUD (icpgpu_search_set_input), as normal
+ * estimation and clustering do.  Parity with PCL binaries is unpinned; tests/sac_restated.py is what the kernels are compared with,
+ * bit for bit.
+ * HYPOTHESES.  DEVIATION: RANSAC's samples come from a counter-based generator and not from rand(): hypothesis t is a pure function of
+ * (seed, t, n), so a batch of hypotheses can be evaluated at once and still equal the sequential loop.  For t = 0, 1, ... and c = 0,
+ * 1, 2, in uint64 arithmetic modulo 2^64:
+ *     z = seed + (3 t + c + 1) * 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *     z ^= z >> 31;  sample[c] = ((z >> 32) * n) >> 32
+ * with n the search cloud's size, NaN rows included.  A hypothesis is INVALID when two of its indices are equal, when one of its
+ * points is not finite, or when the cross product below has a squared norm that is 0 or not finite (DEVIATION: a restatement of
+ * PCL's collinearity test).
+ * MODEL.  Every operation is float32 and rounded on its own: u = p1 - p0, v = p2 - p0, c = (u.y v.z - u.z v.y, u.z v.x - u.x v.z,
+ * u.x v.y - u.y v.x), l2 = (c.x c.x + c.y c.y) + c.z c.z, l = sqrtf(l2), n = c / l (a division per component),
+ * d = -((n.x p0.x + n.y p0.y) + n.z p0.z).  The coefficients are (n.x, n.y, n.z, d).
+ * AXIS.  With axis3 != NULL (SACMODEL_PERPENDICULAR_PLANE) the axis is normalised in double, a = axis / sqrt((x x + y y) + z z), and a
+ * hypothesis is also INVALID unless |(a.x n.x + a.y n.y) + a.z n.z| >= cos(eps_angle), everything in double and cos the C library's:
+ * PCL's isModelValid without its acos.  eps_angle is ignored without an axis.
+ * INLIER.  s = fmaf(n.z, q.z, fmaf(n.y, q.y, n.x * q.x)) + d; a finite point q is an inlier iff (double)fabsf(s) < distance_threshold,
+ * strict, as in PCL's countWithinDistance.  Non-finite points are never inliers.  count[t] is the number of inliers of hypothesis t, or
+ * -1 for an INVALID one.
+ * LOOP.  The answer equals this sequential loop: k = +inf, no best; for t = 0, 1, ...: stop before t when t >= max_iterations or
+ * (double)t >= k; if count[t] > 0 and count[t] > the best count so far (strictly), t becomes the best and, with that count,
+ * w = count / (double)n, p = 1 - (w w) w clamped to [DBL_EPSILON, 1 - DBL_EPSILON], k = log(1 - probability) / log(p) with the C
+ * library's log.  `iterations` is the t at which the loop stopped.  DEVIATIONS: an INVALID sample counts as an iteration (PCL skips
+ * up to 10 max_iterations of them); k starts at infinity, not at 1; (w w) w stands for pow(w, 3).  No best means no model: the call
+ * is ICPGPU_OK with zero inliers, zero coefficients and found = 0 (PCL prints an error and returns empty outputs).
+ * REFINEMENT (PCL's optimize_coefficients; runs when optimize_coefficients != 0 and the best hypothesis has at least 3 inliers).
+ * K = cloud[sample[0]] of the best hypothesis; for every inlier q, (dx, dy, dz) = q - K in float32; the nine sums of dx dx, dx dy,
+ * dx dz, dy dy, dy dz, dz dz, dx, dy, dz take their terms in double, where each term is exact, and each sum is the EXACT sum rounded
+ * once (the statistical outlier filter's rule for sum and sq_sum): moments9.  Then in double, every operation rounded, with m the
+ * number of inliers: the means m_a = S_a / m, the covariances cov_ab = S_ab / m - m_a m_b, the cyclic Jacobi of normal estimation
+ * (8 sweeps, the smallest diagonal entry, the lowest index among equals, that column rounded to float32).  The refined normal is
+ * negated when its float32 dot product with the unrefined normal, (x x' + y y') + z z', is below 0 (PCL leaves the sign to the eigen
+ * solver).  d = (float)-((n.x c.x + n.y c.y) + n.z c.z) in double with c = K + mean in double.  The inliers are then selected again
+ * with the refined coefficients under the same inlier rule, as PCL's segment() re-selects: those coefficients and inliers are the
+ * answer.  With an axis the refined model is not validated again.
+ * OUTPUT.  The inlier indices are ascending.  icpgpu_sac_plane_segmentation computes and KEEPS the result in the context and returns
+ * the coefficients, the number of inliers, the iterations and found; icpgpu_sac_fetch copies the rest out, any number of times: the
+ * inliers, count[0 .. iterations), the best hypothesis' sample and t (-1 without a model), the unrefined coefficients, moments9
+ * (zeros when no refinement ran) and the unrefined inlier count.  Any output of the fetch may be NULL; with inliers and
+ * capacity_inliers < n_inliers, or counts and capacity_counts < iterations, nothing is written.  icpgpu_sac_stats reports the host waits
+ * of the last call (one per batch of 64 hypotheses, two more for a refinement).
+ * EXTRACT.  icpgpu_sac_extract copies out the search cloud's points that are (negative = 0) or are not (negative = 1) among the
+ * inliers, in cloud order: pcl::ExtractIndices with setNegative.  With negative = 1 non-finite rows are kept: they are "not
+ * inliers".  out_xyzw may be NULL (the count alone).  The _view form hands out a view of the pinned staging buffer under the outlier
+ * filters' view rule: valid until the next call on the context; NULL for an empty result.
+ * ICPGPU_ERR_INVALID_ARG: no search cloud; a threshold that is not finite or is negative; max_iterations outside
+ * 0 .. ICPGPU_SAC_MAX_ITERATIONS; probability not strictly inside (0, 1); with an axis: an axis that is not finite or has zero length, an
+ * eps_angle that is not finite or is negative; a null coeff4, n_inliers, iterations or found; a fetch or an extract without a result
+ * (none computed, the last call refused, or the search cloud replaced since); a null n_out or view pointer.  max_iterations = 0,
+ * fewer than three finite points, a threshold of 0 and an empty cloud are all ICPGPU_OK with no model.
+ * Not provided: models other than planes, SAC_LMEDS / MSAC, setIndices, normals-based plane models.
+ * ISOLATION.  The result depends on the search cloud and the arguments alone; the call needs no grid and works
+ * on a cloud the grid refuses.  It leaves the source, the target, every grid, the covariances, the cached normals, the NDT cells, the
+ * filters' results, the search cloud and a clustering result as they were; an unfetched clustering result survives a segmentation and
+ * an unfetched segmentation result survives a clustering, a search and a normal estimation.  icpgpu_search_set_input drops it,
+ * whatever it returns. */
+#define ICPGPU_SAC_MAX_ITERATIONS (1 << 20)
+int icpgpu_sac_plane_segmentation(icpgpu_ctx* ctx, double distance_threshold, int max_iterations, double probability, uint64_t seed,
+                                  int optimize_coefficients, const double* axis3 /* NULL: SACMODEL_PLANE */, double eps_angle, float coeff4[4],
+                                  size_t* n_inliers, int32_t* iterations, int32_t* found);
+int icpgpu_sac_fetch(icpgpu_ctx* ctx, size_t capacity_inliers, size_t capacity_counts, int32_t* inliers /* n_inliers */,
+                     int32_t* counts /* iterations */, int32_t best_sample3[3], int32_t* best_t, float coeff_unrefined4[4], double moments9[9],
+                     size_t* n_unrefined_inliers);
+int icpgpu_sac_stats(const icpgpu_ctx* ctx, int32_t* host_waits);
+int icpgpu_sac_extract(icpgpu_ctx* ctx, int negative, float* out_xyzw, size_t* n_out);
+int icpgpu_sac_extract_view(icpgpu_ctx* ctx, int negative, const float** view_xyzw, size_t* n_out);
 
 /* ---- the mapper's target: a one-point-per-voxel map and its "nn cloud"  -------- */
 /* replaces OctreeMapper's pcl::octree::OctreePointCloudSearch map

@@ -875,6 +875,8 @@ class NormalEstimation {
 // The clusters come out by size descending (the lowest index first among equal sizes), the indices ascending inside each; the
 // defaults are PCL's constructor's (0, 1, INT_MAX).  A refused call leaves `clusters` empty.  setIndices is not provided.
 struct PointIndices {
+  typedef std::shared_ptr<PointIndices> Ptr;
+  typedef std::shared_ptr<const PointIndices> ConstPtr;
   std::vector<int> indices;
 };
 
@@ -924,6 +926,119 @@ class EuclideanClusterExtraction {
   double tolerance_ = 0.0;
   int min_ = 1, max_ = 0x7FFFFFFF;
   std::vector<int> labels_;
+};
+
+// pcl::ModelCoefficients, pcl::SACSegmentation<PointT> and pcl::ExtractIndices<PointT>-shaped front ends (rules and deviations:
+// include/icpgpu.h, "plane segmentation") -- the ground removal in front of EuclideanClusterExtraction:
+//   pcl::SACSegmentation<pcl::PointXYZ> seg;  ->  icpgpu::SACSegmentation<pcl::PointCloud<pcl::PointXYZ>> seg;
+//   seg.setOptimizeCoefficients(true); seg.setModelType(icpgpu::SACMODEL_PLANE); seg.setMethodType(icpgpu::SAC_RANSAC);
+//   seg.setMaxIterations(100); seg.setDistanceThreshold(0.2); seg.setInputCloud(cloud); seg.segment(*inliers, *coefficients);
+//   pcl::ExtractIndices<pcl::PointXYZ> extract;  ->  icpgpu::ExtractIndices<pcl::PointCloud<pcl::PointXYZ>> extract;
+//   extract.setInputCloud(cloud); extract.setIndices(inliers); extract.setNegative(true); extract.filter(*objects);
+// The defaults are PCL's (threshold 0, 50 iterations, probability 0.99, optimize true).  No model, or a refused call, leaves the
+// inliers and the coefficients empty, as PCL does.  setSeed is ours: the samples come from a counter-based generator.
+enum SacModel { SACMODEL_PLANE = 0, SACMODEL_PERPENDICULAR_PLANE = 15 };  // (pcl::SacModel's values)
+enum { SAC_RANSAC = 0 };                                                  // (pcl's method_types.h)
+
+struct ModelCoefficients {
+  typedef std::shared_ptr<ModelCoefficients> Ptr;
+  std::vector<float> values;
+};
+
+template <class CloudT>
+class SACSegmentation {
+ public:
+  explicit SACSegmentation(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {}
+  template <class CloudPtr>
+  void setInputCloud(const CloudPtr& cloud) { input_ = &*cloud; }
+  void setModelType(int model) {
+    if (model != SACMODEL_PLANE && model != SACMODEL_PERPENDICULAR_PLANE) throw std::invalid_argument("icpgpu::SACSegmentation: plane models only");
+    model_ = model;
+  }
+  int getModelType() const { return model_; }
+  void setMethodType(int method) {
+    if (method != SAC_RANSAC) throw std::invalid_argument("icpgpu::SACSegmentation: SAC_RANSAC is the only method");
+  }
+  int getMethodType() const { return SAC_RANSAC; }
+  void setDistanceThreshold(double threshold) { threshold_ = threshold; }
+  double getDistanceThreshold() const { return threshold_; }
+  void setMaxIterations(int max_iterations) { max_iterations_ = max_iterations; }
+  int getMaxIterations() const { return max_iterations_; }
+  void setProbability(double probability) { probability_ = probability; }
+  double getProbability() const { return probability_; }
+  void setOptimizeCoefficients(bool optimize) { optimize_ = optimize; }
+  bool getOptimizeCoefficients() const { return optimize_; }
+  template <class Vec3>
+  void setAxis(const Vec3& axis) { axis_[0] = axis[0], axis_[1] = axis[1], axis_[2] = axis[2]; }  // (Eigen::Vector3f, or any [] of three)
+  void setEpsAngle(double eps_angle) { eps_angle_ = eps_angle; }
+  double getEpsAngle() const { return eps_angle_; }
+  void setSeed(uint64_t seed) { seed_ = seed; }  // NOT a PCL method
+  int getIterations() const { return iterations_; }   // NOT a PCL method: the iterations of the last segment()
+  void segment(PointIndices& inliers, ModelCoefficients& coefficients) {
+    inliers.indices.clear();
+    coefficients.values.clear();
+    iterations_ = 0;
+    if (!input_) return;
+    static_assert(sizeof(input_->points[0]) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+    static_assert(sizeof(int) == sizeof(int32_t), "icpgpu: 32-bit int");
+    const std::size_t n = input_->points.size();
+    if (icpgpu_search_set_input(ctx_, n ? reinterpret_cast<const float*>(&input_->points[0]) : nullptr, n) != ICPGPU_OK) return;
+    float coeff[4];
+    std::size_t n_inliers = 0;
+    int32_t iterations = 0, found = 0;
+    if (icpgpu_sac_plane_segmentation(ctx_, threshold_, max_iterations_, probability_, seed_, optimize_ ? 1 : 0,
+                                      model_ == SACMODEL_PERPENDICULAR_PLANE ? axis_ : nullptr, eps_angle_, coeff, &n_inliers, &iterations,
+                                      &found) != ICPGPU_OK)
+      return;
+    iterations_ = iterations;
+    if (!found) return;
+    std::vector<int> indices(n_inliers);
+    if (icpgpu_sac_fetch(ctx_, n_inliers, 0, n_inliers ? reinterpret_cast<int32_t*>(&indices[0]) : nullptr, nullptr, nullptr, nullptr, nullptr,
+                         nullptr, nullptr) != ICPGPU_OK)
+      return;
+    inliers.indices.swap(indices);
+    coefficients.values.assign(coeff, coeff + 4);
+  }
+
+ private:
+  detail::ContextPtr ctx_holder_;
+  icpgpu_ctx* ctx_;
+  const CloudT* input_ = nullptr;
+  int model_ = SACMODEL_PLANE, max_iterations_ = 50, iterations_ = 0;
+  double threshold_ = 0.0, probability_ = 0.99, eps_angle_ = 0.0;
+  double axis_[3] = {0.0, 0.0, 0.0};
+  bool optimize_ = true;
+  uint64_t seed_ = 0;
+};
+
+// (a plain host loop over the caller's indices: nothing here needs the device)
+template <class CloudT>
+class ExtractIndices {
+ public:
+  template <class CloudPtr>
+  void setInputCloud(const CloudPtr& cloud) { input_ = &*cloud; }
+  template <class IndicesPtr>
+  void setIndices(const IndicesPtr& indices) { indices_ = &indices->indices; }  // (a pointer to pcl::PointIndices, as PCL takes it)
+  void setNegative(bool negative) { negative_ = negative; }
+  bool getNegative() const { return negative_; }
+  void filter(CloudT& output) {
+    output.points.resize(0);
+    if (input_) {
+      const std::size_t n = input_->points.size();
+      std::vector<char> in(n, 0);
+      if (indices_)
+        for (std::size_t k = 0; k < indices_->size(); ++k)
+          if ((*indices_)[k] >= 0 && (std::size_t)(*indices_)[k] < n) in[(std::size_t)(*indices_)[k]] = 1;
+      for (std::size_t i = 0; i < n; ++i)
+        if ((in[i] != 0) != negative_) output.points.push_back(input_->points[i]);
+    }
+    detail::set_cloud_shape(output, output.points.size(), 0);
+  }
+
+ private:
+  const CloudT* input_ = nullptr;
+  const std::vector<int>* indices_ = nullptr;
+  bool negative_ = false;
 };
 
 // The mapper's map (/root/reference/src/icpslam/octree_mapper.cpp:55-90): replaces the pair
