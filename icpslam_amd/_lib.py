@@ -102,6 +102,7 @@ EXPORTS = [
     "icpgpu_radius_outlier_removal_view", "icpgpu_outlier_stats", "icpgpu_outlier_fetch",
     "icpgpu_search_set_input", "icpgpu_search_size", "icpgpu_search_knn", "icpgpu_search_radius",
     "icpgpu_normal_estimation",
+    "icpgpu_fpfh_estimation",
     "icpgpu_euclidean_cluster_extraction", "icpgpu_cluster_fetch",
     "icpgpu_sac_plane_segmentation", "icpgpu_sac_fetch", "icpgpu_sac_stats", "icpgpu_sac_extract", "icpgpu_sac_extract_view",
     "icpgpu_set_source_normals", "icpgpu_set_p2plane_symmetric", "icpgpu_get_p2plane_symmetric",
@@ -212,6 +213,7 @@ def load():
     L.icpgpu_search_knn.argtypes = [vp, fp, C.c_size_t, C.c_int, ip, fp, ip]
     L.icpgpu_search_radius.argtypes = [vp, fp, C.c_size_t, C.c_double, C.c_int, C.c_size_t, C.POINTER(C.c_int64), ip, fp, C.POINTER(C.c_size_t)]
     L.icpgpu_normal_estimation.argtypes = [vp, fp, C.c_size_t, C.c_int, C.c_double, fp, fp, ip, fp]
+    L.icpgpu_fpfh_estimation.argtypes = [vp, fp, fp, C.c_size_t, C.c_int, C.c_double, fp, ip, fp]
     L.icpgpu_euclidean_cluster_extraction.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.icpgpu_cluster_fetch.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_int64), ip, ip, ip]
     szp = C.POINTER(C.c_size_t)

@@ -415,6 +415,7 @@ struct icpgpu_ctx {
     int n_finite = 0;
     DeviceBuf queries, idx, d2, n_found, far, counts, longs, row_start, scratch_start, scan, scratch, totals, row_start64;
     DeviceBuf normals, moments;  // icpgpu_normal_estimation: the results on their way to the staging buffer
+    DeviceBuf fpfh_normals, spfh, fpfh;  // icpgpu_fpfh_estimation: the caller's normals and the two histograms
   } search;
   // euclidean clustering (icpgpu_search.cpp, icp_cluster.hip): the last call's result over the search cloud and its scratch, in
   // buffers no other call writes -- an unfetched result outlives later search and normal calls; icpgpu_search_set_input drops it

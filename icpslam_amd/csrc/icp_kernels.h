@@ -604,4 +604,13 @@ hipError_t launch_sac_sums(const float4* cloud, int n, const int* inliers, int m
 hipError_t launch_normals_from_rows(const float4* queries, int n_q, const float4* cloud, int n, const int32_t* idx, const int32_t* n_found, int k,
                                     const int* row_start, const float viewpoint[3], float4* out, float* moments, hipStream_t stream);
 
+// ---- fast point feature histograms (icp_fpfh.hip): pcl::FPFHEstimation over neighbour rows still in device memory -------------
+// Rows as for launch_normals_from_rows (dense with n_found, or CSR with row_start).  spfh[p] (n x 33): the simplified histogram of
+// cloud point p from ITS row over the cloud and the cloud's normals (float4, the fourth float ignored); rows shorter than 2 give
+// zeros.  out[q] (n_q x 33): the queries' rows (idx with their d2) weighted over spfh; a non-finite query gives NaN.
+hipError_t launch_spfh_from_rows(const float4* cloud, int n, const float4* normals, const int32_t* idx, const int32_t* n_found, int k,
+                                 const int* row_start, float* spfh, hipStream_t stream);
+hipError_t launch_fpfh_from_rows(const float4* queries, int n_q, int n, const float* spfh, const int32_t* idx, const float* d2, const int32_t* n_found,
+                                 int k, const int* row_start, float* out, hipStream_t stream);
+
 }  // namespace icpgpu

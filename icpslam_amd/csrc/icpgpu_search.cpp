@@ -1,6 +1,6 @@
 // icpgpu_search.cpp -- host side of the neighbour search (pcl::search::KdTree / pcl::KdTreeFLANN: nearestKSearch, radiusSearch;
 // rules: include/icpgpu.h "neighbour search"; kernels: icp_search.hip) and of what runs over the search cloud: normal estimation
-// (icp_normals.hip) and euclidean clustering (icp_cluster.hip).
+// (icp_normals.hip), fast point feature histograms (icp_fpfh.hip) and euclidean clustering (icp_cluster.hip).
 #include "icp_ctx.h"
 
 namespace icpgpu_impl {
@@ -86,11 +86,10 @@ int deliver(icpgpu_ctx* c, const Delivery* parts, int n_parts) {
   return ICPGPU_OK;
 }
 
-// Radius search, first half, queued: the rows' lengths, their scans and the totals (launch_search_radius_count) for n_q > 0 queries.
-// shells / r2: what the second half (launch_search_radius_fill) must be given again.
-int queue_radius_count(icpgpu_ctx* c, const float4* d_queries, size_t n_q, double radius, int max_nn, int& shells, float& r2) {
+// what launch_search_radius_count writes for `rows` = n_q + 1 row starts (a buffer that grows is freed first, which waits for the
+// device: a call that queues two searches reserves the larger one before the first)
+int reserve_radius_rows(icpgpu_ctx* c, size_t rows) {
   auto& S = c->search;
-  const size_t rows = n_q + 1;
   int rc;
   if ((rc = ensure(c, S.counts, rows * sizeof(int)))) return rc;
   if ((rc = ensure(c, S.longs, rows * sizeof(int)))) return rc;
@@ -99,6 +98,15 @@ int queue_radius_count(icpgpu_ctx* c, const float4* d_queries, size_t n_q, doubl
   if ((rc = ensure(c, S.scan, exclusive_scan_scratch_ints((int)rows) * sizeof(int)))) return rc;
   if ((rc = ensure(c, S.totals, 2 * sizeof(unsigned long long)))) return rc;
   if ((rc = ensure(c, S.row_start64, rows * sizeof(long long)))) return rc;
+  return ICPGPU_OK;
+}
+
+// Radius search, first half, queued: the rows' lengths, their scans and the totals (launch_search_radius_count) for n_q > 0 queries.
+// shells / r2: what the second half (launch_search_radius_fill) must be given again.
+int queue_radius_count(icpgpu_ctx* c, const float4* d_queries, size_t n_q, double radius, int max_nn, int& shells, float& r2) {
+  auto& S = c->search;
+  int rc;
+  if ((rc = reserve_radius_rows(c, n_q + 1))) return rc;
   const SearchView v = view_of(c);
   r2 = (float)(radius * radius);
   // the cube of `shells` cells around a query's cell contains its ball (shells * h * kGridSafety >= radius: the grid search's bound);
@@ -289,6 +297,88 @@ int icpgpu_normal_estimation(icpgpu_ctx* c, const float* queries_xyzw, size_t n_
   const Delivery out[3] = {{out_nxyzc, S.normals.ptr, n_q * sizeof(float4)},
                            {n_neighbours, d_counts, n_neighbours ? n_q * sizeof(int32_t) : 0},
                            {moments9, d_moments, moments9 ? n_q * 9 * sizeof(float) : 0}};
+  return deliver(c, out, 3);
+}
+
+// pcl::FPFHEstimation over the search cloud (rules: include/icpgpu.h "fast point feature histograms"; kernels: icp_fpfh.hip).  The
+// cloud's own rows feed spfh_from_rows_kernel; the queries' rows -- the same rows when the queries are the cloud's points, a second
+// search behind the first otherwise -- feed fpfh_from_rows_kernel.  The rows never leave the device.  Host waits: one with k (the
+// results); with a radius one more per search for the totals that size its rows -- two without queries, three with.
+int icpgpu_fpfh_estimation(icpgpu_ctx* c, const float* normals_nxyzc, const float* queries_xyzw, size_t n_q, int k, double radius, float* out_fpfh,
+                           int32_t* n_neighbours, float* spfh) {
+  ENTER(c);
+  auto& S = c->search;
+  const float4* d_queries = nullptr;
+  int rc;
+  const bool by_k = k != 0, by_radius = radius != 0.0;
+  if (by_k == by_radius) return fail(c, ICPGPU_ERR_INVALID_ARG, "fpfh_estimation: exactly one of k and radius must be set (k %d, radius %g)", k, radius);
+  if (by_k && (k < 2 || k > ICPGPU_SEARCH_MAX_K)) return fail(c, ICPGPU_ERR_INVALID_ARG, "fpfh_estimation: k %d outside 2..%d", k, ICPGPU_SEARCH_MAX_K);
+  if (by_radius && !(std::isfinite(radius) && radius > 0.0)) return fail(c, ICPGPU_ERR_INVALID_ARG, "fpfh_estimation: radius must be finite and > 0");
+  if ((rc = stage_queries(c, "fpfh_estimation", queries_xyzw, n_q, d_queries))) return rc;
+  const size_t n = S.n;
+  if (n && !normals_nxyzc) return fail(c, ICPGPU_ERR_INVALID_ARG, "fpfh_estimation: null normals for a search cloud of %zu points", n);
+  if (n_q && !out_fpfh) return fail(c, ICPGPU_ERR_INVALID_ARG, "fpfh_estimation: null result pointer");
+  if (n_q == 0) return ICPGPU_OK;
+  const bool own = !queries_xyzw;  // the queries' rows are the cloud's own rows
+  const size_t most = std::max(n, n_q);
+  if ((rc = ensure(c, S.fpfh_normals, std::max<size_t>(n, 1) * sizeof(float4)))) return rc;
+  if ((rc = ensure(c, S.spfh, std::max<size_t>(n, 1) * ICPGPU_FPFH_BINS * sizeof(float)))) return rc;
+  if ((rc = ensure(c, S.fpfh, std::max<size_t>(n_q, 1) * ICPGPU_FPFH_BINS * sizeof(float)))) return rc;
+  if (n) HIP_TRY(c, hipMemcpyAsync(S.fpfh_normals.ptr, normals_nxyzc, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+  const SearchView v = view_of(c);
+  const float4* d_normals = static_cast<const float4*>(S.fpfh_normals.ptr);
+  float* d_spfh = static_cast<float*>(S.spfh.ptr);
+  float* d_fpfh = static_cast<float*>(S.fpfh.ptr);
+  const void* d_counts = nullptr;
+  if (by_k) {
+    const size_t cells = most * (size_t)k;
+    if ((rc = ensure(c, S.idx, cells * sizeof(int32_t)))) return rc;
+    if ((rc = ensure(c, S.d2, cells * sizeof(float)))) return rc;
+    if ((rc = ensure(c, S.n_found, most * sizeof(int32_t)))) return rc;
+    if ((rc = ensure(c, S.far, (most + 2) * sizeof(int)))) return rc;
+    int32_t* d_idx = static_cast<int32_t*>(S.idx.ptr);
+    float* d_d2 = static_cast<float*>(S.d2.ptr);
+    int32_t* d_found = static_cast<int32_t*>(S.n_found.ptr);
+    if (n) {
+      HIP_TRY(c, launch_search_knn(v.cloud, (int)n, v.cloud, v.n, v.sorted, v.cell_start, v.g, k, d_idx, d_d2, d_found, static_cast<int*>(S.far.ptr), c->stream));
+      HIP_TRY(c, launch_spfh_from_rows(v.cloud, v.n, d_normals, d_idx, d_found, k, nullptr, d_spfh, c->stream));
+    }
+    if (!own)
+      HIP_TRY(c, launch_search_knn(d_queries, (int)n_q, v.cloud, v.n, v.sorted, v.cell_start, v.g, k, d_idx, d_d2, d_found, static_cast<int*>(S.far.ptr), c->stream));
+    HIP_TRY(c, launch_fpfh_from_rows(d_queries, (int)n_q, v.n, d_spfh, d_idx, d_d2, d_found, k, nullptr, d_fpfh, c->stream));
+    d_counts = S.n_found.ptr;
+  } else {
+    if ((rc = reserve_radius_rows(c, most + 1))) return rc;
+    // one search: its rows into S.idx / S.d2 (CSR by S.row_start), after the wait for the totals that size them
+    auto rows_of = [&](const float4* d_points, size_t n_points) -> int {
+      int shells;
+      float r2;
+      int rc2;
+      if ((rc2 = queue_radius_count(c, d_points, n_points, radius, 0, shells, r2))) return rc2;
+      unsigned long long totals[2] = {0, 0};
+      const Delivery first[1] = {{totals, S.totals.ptr, sizeof totals}};
+      if ((rc2 = deliver(c, first, 1))) return rc2;
+      if (totals[0] > (unsigned long long)INT32_MAX || totals[1] > (unsigned long long)INT32_MAX)
+        return fail(c, ICPGPU_ERR_UNSUPPORTED, "fpfh_estimation: %llu neighbours in all, more than the int32 scans carry", totals[0]);
+      if (totals[0]) return queue_radius_fill(c, d_points, n_points, shells, r2, (size_t)totals[0], (size_t)totals[1]);
+      if ((rc2 = ensure(c, S.idx, sizeof(int32_t)))) return rc2;  // (every row is empty: nothing is read through the pointers)
+      return ensure(c, S.d2, sizeof(float));
+    };
+    if (n) {
+      if ((rc = rows_of(v.cloud, n))) return rc;
+      HIP_TRY(c, launch_spfh_from_rows(v.cloud, v.n, d_normals, static_cast<const int32_t*>(S.idx.ptr), nullptr, 0, static_cast<const int*>(S.row_start.ptr),
+                                       d_spfh, c->stream));
+    }
+    if (!own) {
+      if ((rc = rows_of(d_queries, n_q))) return rc;
+    }
+    HIP_TRY(c, launch_fpfh_from_rows(d_queries, (int)n_q, v.n, d_spfh, static_cast<const int32_t*>(S.idx.ptr), static_cast<const float*>(S.d2.ptr), nullptr, 0,
+                                     static_cast<const int*>(S.row_start.ptr), d_fpfh, c->stream));
+    d_counts = S.counts.ptr;
+  }
+  const Delivery out[3] = {{out_fpfh, d_fpfh, n_q * ICPGPU_FPFH_BINS * sizeof(float)},
+                           {n_neighbours, d_counts, n_neighbours ? n_q * sizeof(int32_t) : 0},
+                           {spfh, d_spfh, spfh ? n * ICPGPU_FPFH_BINS * sizeof(float) : 0}};
   return deliver(c, out, 3);
 }
 

@@ -23,6 +23,9 @@ from . import _lib
 from ._lib import IcpGpuError, Params, Profile, Rejector, Result
 
 
+FPFH_BINS = 33  # ICPGPU_FPFH_BINS: pcl::FPFHSignature33
+
+
 def _as_cloud(a) -> np.ndarray:
     a = np.ascontiguousarray(a, dtype=np.float32)
     if a.ndim != 2 or a.shape[1] != 4:
@@ -577,6 +580,24 @@ class Context:
                                                      None if moments is None else _fp(moments)))
         return (normals, count, moments) if want_moments else (normals, count)
 
+    # fast point feature histograms (pcl::FPFHEstimation; rules: include/icpgpu.h) ---------------------------------------
+    def fpfh_estimation(self, normals, queries, k: int = 0, radius: float = 0.0, want_spfh: bool = False, n_q: int | None = None):
+        """(fpfh (n_q, 33) float32, n_neighbours (n_q,) int32[, spfh (n, 33) float32]): pcl::FPFHSignature33 of every query from its
+        k nearest points of the search cloud, or from those within `radius` (exactly one of the two).  normals: the search cloud's,
+        (n, 4) float32 as normal_estimation returns them.  queries None: the search cloud's own points (n_q: only to test the
+        refusal).  NaN rows for non-finite queries."""
+        queries, n_q = self._search_queries(queries, n_q)
+        n = self.search_size()[0]
+        if normals is not None:
+            normals = _as_cloud(normals)
+        fpfh = np.empty((n_q, FPFH_BINS), np.float32)
+        count = np.empty(n_q, np.int32)
+        spfh = np.empty((n, FPFH_BINS), np.float32) if want_spfh else None
+        self._check(self._L.icpgpu_fpfh_estimation(self._h, None if normals is None else _fp(normals), None if queries is None else _fp(queries), n_q,
+                                                   int(k), float(radius), _fp(fpfh), count.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                   None if spfh is None else _fp(spfh)))
+        return (fpfh, count, spfh) if want_spfh else (fpfh, count)
+
     # euclidean clustering (pcl::EuclideanClusterExtraction; rules: include/icpgpu.h) --------------------------------------
     def cluster_extract_raw(self, tolerance: float, min_size: int, max_size: int) -> tuple:
         """One icpgpu_euclidean_cluster_extraction call: (rc, n_clusters, n_clustered); the result stays in the context."""
@@ -1039,6 +1060,60 @@ class NormalEstimation:
             queries = self._input
         normals, self._n_neighbours = self._ctx.normal_estimation(queries, self._k, self._radius, self._viewpoint)
         return normals
+
+
+class FPFHEstimation:
+    """pcl::FPFHEstimation<PointXYZ, Normal, FPFHSignature33>-shaped front end (include/icpgpu.h, "fast point feature histograms"):
+    setInputCloud, setInputNormals (the normals of the search surface -- of the input cloud when no surface is set -- as
+    NormalEstimation.compute() returns them), optionally setSearchSurface, setKSearch or setRadiusSearch, compute() -> (n, 33)
+    float32, NaN rows for non-finite input points."""
+
+    def __init__(self, device_id: int = 0):
+        self._ctx = Context(device_id)
+        self._input = None
+        self._normals = None
+        self._surface = None
+        self._k = 0
+        self._radius = 0.0
+        self._n_neighbours = np.empty(0, np.int32)
+
+    def setInputCloud(self, cloud):
+        self._input = _as_cloud(cloud).copy()
+
+    def setInputNormals(self, normals):
+        self._normals = _as_cloud(normals).copy()
+
+    def setSearchSurface(self, cloud):
+        self._surface = None if cloud is None else _as_cloud(cloud).copy()
+
+    def setSearchMethod(self, tree=None):
+        """Accepted and ignored: the search is the library's own (exact, ascending by (d2, index))."""
+
+    def setKSearch(self, k: int):
+        self._k = int(k)
+
+    def getKSearch(self) -> int:
+        return self._k
+
+    def setRadiusSearch(self, radius: float):
+        self._radius = float(radius)
+
+    def getRadiusSearch(self) -> float:
+        return self._radius
+
+    def getNeighbourCounts(self) -> np.ndarray:
+        """How many neighbours the last compute() found for every point (not PCL's)."""
+        return self._n_neighbours
+
+    def compute(self) -> np.ndarray:
+        if self._input is None or self._normals is None:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "compute: setInputCloud and setInputNormals first")
+        surface = self._input if self._surface is None else self._surface
+        if self._normals.shape[0] != surface.shape[0]:
+            raise IcpGpuError(_lib.ERR_INVALID_ARG, f"compute: {self._normals.shape[0]} normals for a search surface of {surface.shape[0]} points")
+        self._ctx.search_set_input(surface)
+        fpfh, self._n_neighbours = self._ctx.fpfh_estimation(self._normals, None if self._surface is None else self._input, self._k, self._radius)
+        return fpfh
 
 
 class EuclideanClusterExtraction:

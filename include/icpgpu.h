@@ -57,7 +57,7 @@ extern "C" {
  * icpgpu_radius_outlier_removal, their _view forms, icpgpu_outlier_stats, icpgpu_outlier_fetch, and the neighbour search --
  * icpgpu_search_set_input, icpgpu_search_size, icpgpu_search_knn, icpgpu_search_radius, and normal estimation --
  * icpgpu_normal_estimation, and euclidean clustering -- icpgpu_euclidean_cluster_extraction, icpgpu_cluster_fetch, and plane segmentation --
- * icpgpu_sac_plane_segmentation, icpgpu_sac_fetch, icpgpu_sac_stats, icpgpu_sac_extract, icpgpu_sac_extract_view, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
+ * icpgpu_sac_plane_segmentation, icpgpu_sac_fetch, icpgpu_sac_stats, icpgpu_sac_extract, icpgpu_sac_extract_view, and fast point feature histograms -- icpgpu_fpfh_estimation, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
  * icpgpu_set_p2plane_symmetric, icpgpu_get_p2plane_symmetric, icpgpu_reduce_symmetric_point_to_plane,
  * icpgpu_solve_symmetric_point_to_plane, ICPGPU_REJECT_SURFACE_NORMAL (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
@@ -745,6 +745,76 @@ int icpgpu_search_radius(icpgpu_ctx* ctx, const float* queries_xyzw, size_t n_q,
  * arguments alone.  One host wait per call with k, two at most with a radius. */
 int icpgpu_normal_estimation(icpgpu_ctx* ctx, const float* queries_xyzw, size_t n_q, int k, double radius, const float* viewpoint3,
                              float* out_nxyzc, int32_t* n_neighbours, float* moments9);
+
+/* ---- fast point feature histograms (added under 1.2) --------------------------------------------------------------- */
+/* replaces pcl::FPFHEstimation<PointXYZ, Normal, FPFHSignature33>: setInputCloud, setInputNormals, setSearchSurface, setKSearch /
+ * setRadiusSearch, compute -- a 33-bin descriptor per query point from the angles between its neighbours' normals, the feature that
+ * global registration (re-localisation, loop closure) matches where no initial guess exists.  The context's SEARCH CLOUD
+ * (icpgpu_search_set_input) is the search surface; normals_nxyzc are ITS normals, n float4 in icpgpu_normal_estimation's output format
+ * (the fourth float is ignored); the queries are the input cloud.  queries_xyzw == NULL means the search cloud's own points (n_q must
+ * then be 0 or n), as in icpgpu_normal_estimation.  Parity with PCL binaries is unpinned; tests/fpfh_restated.py is what the kernels
+ * are compared with, bit for bit.  The rules are PCL 1.8's (fpfh.hpp, pfh_tools.cpp), made order-independent or portable where PCL is
+ * not.
+ * MODE.  Exactly one of k (2 .. ICPGPU_SEARCH_MAX_K) and radius (finite, > 0) is set, the other is 0: both set, neither set, or a
+ * value outside its range is ICPGPU_ERR_INVALID_ARG.
+ * ROWS.  The row of cloud point p is exactly icpgpu_search_knn(k)'s or icpgpu_search_radius(radius, max_nn = 0)'s row for p over the
+ * search cloud: the same set in the same order, p (or a coincident point of lower index) first; its length is m_p.  With queries
+ * given, the row of query q is the same call's row for q, of length m_q; without, it is the cloud point's row.
+ * PAIR FEATURES of (p, j), j an entry of p's row whose index is not p.  Every operation is float32 and rounded on its own; dots are
+ * (x x' + y y') + z z'; P are points, n normals:
+ *   1. d = P_j - P_p; f4 = sqrtf((d.x d.x + d.y d.y) + d.z d.z).
+ *   2. The pair is SKIPPED when f4 == 0 (a coincident point), or when a component of n_p or n_j is not finite.
+ *   3. a1 = (n_p . d) / f4, a2 = (n_j . d) / f4.
+ *   4. Swap iff fabsf(a1) < fabsf(a2): then n1 = n_j, n2 = n_p, d = -d, f3 = -a2; otherwise n1 = n_p, n2 = n_j, f3 = a1.
+ *      DEVIATION: PCL compares acos(fabs(a1)) > acos(fabs(a2)) -- the same order without the libm call, differing only where acos
+ *      rounds two arguments together or an argument exceeds 1.
+ *   5. v = d x n1 = (d.y n1.z - d.z n1.y, d.z n1.x - d.x n1.z, d.x n1.y - d.y n1.x); vn = sqrtf((v.x v.x + v.y v.y) + v.z v.z).  The
+ *      pair is SKIPPED when vn == 0 (d parallel to n1).
+ *   6. v /= vn, a division per component; w = n1 x v, written as v above.
+ *   7. f2 = v . n2; y = w . n2; x = n1 . n2.  (PCL's f1 is atan2f(y, x).)
+ * BINS.  b2 = clamp((int)floor(11.0 * (((double)f2 + 1.0) * 0.5)), 0, 10) and the same for b3 from f3: float64, as PCL's expression
+ * promotes; the clamp is taken on the double, and a NaN lands in bin 0.  b1 is PCL's floor(11 (atan2f(y, x) + pi) / (2 pi)) computed
+ * WITHOUT atan2f, whose bits are not portable: a sector test against the ten interior bin edges.  The edge directions
+ * (c_k, s_k) = (cos, sin)(2 pi k / 11), k = 1 .. 10, are the float32 constants ICPGPU_FPFH_EDGE_COS / _SIN below.  With
+ * (a, b) = (-x, -y), edge k counts as passed iff c_k * b - s_k * a >= 0, the two products and the difference float32 and rounded on
+ * their own.  When b >= 0 (true for -0) the test runs on edges 1 .. 5; otherwise (b < 0, or b NaN) edges 1 .. 5 count as passed and
+ * the test runs on edges 6 .. 10.  b1 is the number of passed edges.  x = y = 0 of either sign gives bin 5, as atan2f(0, 0) = 0 does.
+ *   DEVIATION: pairs within rounding of an edge may land in the neighbouring bin, and an angle of exactly +pi (y = +0, x < 0) lands
+ *   in bin 0, where PCL clamps it into bin 10.
+ * SPFH of cloud point p: 33 floats.  c[b] are the integer counts of the non-skipped pairs' bins b1, 11 + b2 and 22 + b3;
+ * incr = 100.0f / (float)(m_p - 1); spfh[b] = c[b] == 0 ? 0 : (float)c[b] * incr.  DEVIATION: PCL adds incr c times; this differs by
+ * rounding only, and the counts do not depend on the order of the pairs.  A row with m_p < 2 (and so a non-finite point, whose row is
+ * empty) has an all-zero SPFH.  The SPFH is computed for EVERY cloud point; PCL computes it for the union of the queries'
+ * neighbours, which gives the same values where they are used.
+ * FPFH of query q, over its row in row order: entries with d2 == 0 are skipped (PCL's rule: the point itself, every coincident point
+ * and with them the point's own SPFH); w = 1.0f / d2; for each bin h[b] += spfh[j][b] * w, product and sum in float32.  Then per
+ * sub-histogram (bins 0 .. 10, 11 .. 21, 22 .. 32) s = ((..((double)h[0] + h[1]) + ..) + h[10]) in float64, and when s != 0 every bin
+ * of it is multiplied by (float)(100.0 / s), in float32.  DEVIATION: PCL sums the products as they are made, in float32; this sums
+ * the finished bins and differs by rounding only.  Nothing else is special-cased: a subnormal d2 gives whatever inf / NaN the
+ * arithmetic yields.  A non-finite query gives 33 NaN and n_neighbours = 0; an empty row, or a row of only coincident entries, gives
+ * 33 zeros.
+ * OUTPUT.  out_fpfh: n_q x 33 floats, required when n_q > 0 -- pcl::FPFHSignature33's histogram.  n_neighbours (may be NULL): m_q.
+ * spfh (may be NULL): n x 33, every cloud point's SPFH.
+ * LIMITS.  ICPGPU_ERR_INVALID_ARG: no search cloud; null normals with n > 0; null out_fpfh with n_q > 0; n_q against null queries;
+ * both or neither of k and radius, or one outside its range.  With a radius, neighbours beyond INT32_MAX in all (of the cloud's rows
+ * or of the queries'): ICPGPU_ERR_UNSUPPORTED.  A cloud the grid refuses is searched without it, as in icpgpu_normal_estimation.
+ * n_q = 0 is ICPGPU_OK and writes nothing.  Not provided: setIndices, other bin counts.
+ * ISOLATION.  The call has buffers of its own in the context's search state for the normals and the two histograms, and otherwise
+ * uses the search calls' scratch.  Its answers depend on the search cloud and the arguments alone; it leaves
+ * the source, the target, every grid, the covariances, the cached normals, the NDT cells, the filters' results and the search cloud
+ * as they were, and an unfetched clustering or plane segmentation result survives it.
+ * HOST WAITS.  With k: one, with or without queries.  With a radius: one more per search, for the totals that size its rows -- two
+ * without queries, three with. */
+#define ICPGPU_FPFH_BINS 33 /* 11 + 11 + 11: pcl::FPFHSignature33 */
+#define ICPGPU_FPFH_EDGE_COS                                                                                                         \
+  { 0x1.aeb8c8p-1f, 0x1.a9628ep-2f, -0x1.2375f6p-3f, -0x1.4f49e8p-1f, -0x1.eb42aap-1f, -0x1.eb42aap-1f, -0x1.4f49e8p-1f, -0x1.2375f6p-3f, \
+    0x1.a9628ep-2f, 0x1.aeb8c8p-1f }
+#define ICPGPU_FPFH_EDGE_SIN                                                                                                         \
+  { 0x1.14ceep-1f, 0x1.d1bb48p-1f, 0x1.fac9ep-1f, 0x1.82f19cp-1f, 0x1.207e8p-2f, -0x1.207e8p-2f, -0x1.82f19cp-1f, -0x1.fac9ep-1f,      \
+    -0x1.d1bb48p-1f, -0x1.14ceep-1f }
+int icpgpu_fpfh_estimation(icpgpu_ctx* ctx, const float* normals_nxyzc /* n float4, the search cloud's */, const float* queries_xyzw, size_t n_q,
+                           int k, double radius, float* out_fpfh /* n_q x 33 */, int32_t* n_neighbours /* n_q, may be NULL */,
+                           float* spfh /* n x 33, may be NULL */);
 
 /* ---- euclidean clustering (added under 1.2) ------------------------------------------------------------------------ */
 /* replaces pcl::EuclideanClusterExtraction<PointXYZ>: setInputCloud, setClusterTolerance, setMinClusterSize, setMaxClusterSize,

@@ -867,6 +867,86 @@ class NormalEstimation {
   std::vector<float> normals_;
 };
 
+// pcl::FPFHSignature33 and the pcl::FPFHEstimation<PointInT, PointNT, PointOutT>-shaped front end (rules and deviations:
+// include/icpgpu.h, "fast point feature histograms"):
+//   pcl::FPFHEstimation<pcl::PointXYZ, pcl::Normal, pcl::FPFHSignature33> fpfh;
+//     ->  icpgpu::FPFHEstimation<pcl::PointCloud<pcl::PointXYZ>, pcl::PointCloud<pcl::Normal>, pcl::PointCloud<pcl::FPFHSignature33>> fpfh;
+//   fpfh.setInputCloud(keypoints); fpfh.setSearchSurface(cloud); fpfh.setInputNormals(normals); fpfh.setKSearch(10) or
+//   fpfh.setRadiusSearch(0.5); fpfh.compute(signatures);
+// The normals are the search surface's -- the input cloud's when no surface is set -- one per point, as in PCL; the class takes
+// icpgpu::NormalEstimation's output cloud directly (any point type with normal_x, normal_y, normal_z).  The output point type only
+// needs float histogram[33] (pcl::FPFHSignature33, icpgpu::FPFHSignature33).  A non-finite input point gets 33 NaN and clears
+// is_dense; a refused call (both or neither of k and radius set, normals that do not match the surface, ...) leaves the output empty.
+struct FPFHSignature33 {
+  float histogram[ICPGPU_FPFH_BINS];
+  static int descriptorSize() { return ICPGPU_FPFH_BINS; }
+};
+
+template <class CloudInT, class CloudNT, class CloudOutT>
+class FPFHEstimation {
+ public:
+  explicit FPFHEstimation(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {}
+  template <class CloudPtr>
+  void setInputCloud(const CloudPtr& cloud) { input_ = &*cloud; }
+  template <class NormalsPtr>
+  void setInputNormals(const NormalsPtr& normals) { normals_ = &*normals; }
+  // the cloud the neighbours and their normals are taken from (PCL: a denser cloud than the input); without it the input cloud itself
+  template <class CloudPtr>
+  void setSearchSurface(const CloudPtr& cloud) { surface_ = &*cloud; }
+  template <class TreePtr>
+  void setSearchMethod(const TreePtr&) {}  // accepted and ignored: the search is the library's own (exact)
+  void setKSearch(int k) { k_ = k; }
+  int getKSearch() const { return k_; }
+  void setRadiusSearch(double radius) { radius_ = radius; }
+  double getRadiusSearch() const { return radius_; }
+  void compute(CloudOutT& output) {
+    output.points.resize(0);
+    detail::set_cloud_shape(output, 0, 0);
+    if (!input_ || !normals_) return;
+    static_assert(sizeof(input_->points[0]) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+    static_assert(sizeof(output.points[0].histogram) == ICPGPU_FPFH_BINS * sizeof(float), "icpgpu: float histogram[33] (pcl::FPFHSignature33)");
+    const CloudInT* surface = surface_ ? surface_ : input_;
+    const std::size_t n = input_->points.size(), ns = surface->points.size();
+    if (normals_->points.size() != ns) return;  // (PCL refuses normals that do not match the surface as well)
+    if (surface != input_ && n == 0) return;    // (null queries would mean the surface's own points)
+    if (icpgpu_search_set_input(ctx_, ns ? reinterpret_cast<const float*>(&surface->points[0]) : nullptr, ns) != ICPGPU_OK) return;
+    std::vector<float> nxyzc(4 * ns), hist(static_cast<std::size_t>(ICPGPU_FPFH_BINS) * n);
+    for (std::size_t i = 0; i < ns; ++i) {
+      nxyzc[4 * i] = normals_->points[i].normal_x;
+      nxyzc[4 * i + 1] = normals_->points[i].normal_y;
+      nxyzc[4 * i + 2] = normals_->points[i].normal_z;
+      nxyzc[4 * i + 3] = 0.f;
+    }
+    const float* queries = surface == input_ ? nullptr : reinterpret_cast<const float*>(&input_->points[0]);
+    if (icpgpu_fpfh_estimation(ctx_, ns ? &nxyzc[0] : nullptr, queries, n, k_, radius_, n ? &hist[0] : nullptr, nullptr, nullptr) != ICPGPU_OK) return;
+    output.points.resize(n);
+    detail::set_cloud_shape(output, n, 0);
+    bool dense = true;
+    for (std::size_t i = 0; i < n; ++i) {
+      for (int b = 0; b < ICPGPU_FPFH_BINS; ++b) {
+        const float v = hist[static_cast<std::size_t>(ICPGPU_FPFH_BINS) * i + b];
+        output.points[i].histogram[b] = v;
+        dense = dense && v == v;
+      }
+    }
+    set_dense(output, dense, 0);
+  }
+
+ private:
+  template <class C>
+  static auto set_dense(C& c, bool dense, int) -> decltype(c.is_dense = true, void()) { c.is_dense = dense; }
+  template <class C>
+  static void set_dense(C&, bool, long) {}
+
+  detail::ContextPtr ctx_holder_;
+  icpgpu_ctx* ctx_;
+  const CloudInT* input_ = nullptr;
+  const CloudNT* normals_ = nullptr;
+  const CloudInT* surface_ = nullptr;
+  int k_ = 0;
+  double radius_ = 0.0;
+};
+
 // pcl::PointIndices and pcl::EuclideanClusterExtraction<PointT>-shaped front end (rules and deviations: include/icpgpu.h,
 // "euclidean clustering"):
 //   pcl::EuclideanClusterExtraction<pcl::PointXYZ> ec;  ->  icpgpu::EuclideanClusterExtraction<pcl::PointCloud<pcl::PointXYZ>> ec;
