@@ -28,6 +28,10 @@ MAX_REJECTORS = 4
 SOR_MAX_K = 63                 # ICPGPU_SOR_MAX_K
 SEARCH_MAX_K = 64              # ICPGPU_SEARCH_MAX_K
 SAC_MAX_ITERATIONS = 1 << 20   # ICPGPU_SAC_MAX_ITERATIONS
+SCP_MAX_ITERATIONS = 1 << 20   # ICPGPU_SCP_MAX_ITERATIONS
+SCP_CHUNK = 65536              # ICPGPU_SCP_CHUNK
+SCP_MAX_SAMPLES = 8            # ICPGPU_SCP_MAX_SAMPLES
+SCP_INVALID, SCP_PREREJECTED, SCP_NO_TRANSFORM, SCP_EVALUATED = 0, 1, 2, 3   # ICPGPU_SCP_*
 SACMODEL_PLANE, SACMODEL_PERPENDICULAR_PLANE = 0, 15   # pcl::SacModel's values
 SAC_RANSAC = 0                 # pcl's method_types.h
 STATE_NAMES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE",
@@ -103,7 +107,9 @@ EXPORTS = [
     "icpgpu_search_set_input", "icpgpu_search_size", "icpgpu_search_knn", "icpgpu_search_radius",
     "icpgpu_normal_estimation",
     "icpgpu_fpfh_estimation",
+    "icpgpu_feature_knn",
     "icpgpu_euclidean_cluster_extraction", "icpgpu_cluster_fetch",
+    "icpgpu_scp_align", "icpgpu_scp_fetch", "icpgpu_scp_stats",
     "icpgpu_sac_plane_segmentation", "icpgpu_sac_fetch", "icpgpu_sac_stats", "icpgpu_sac_extract", "icpgpu_sac_extract_view",
     "icpgpu_set_source_normals", "icpgpu_set_p2plane_symmetric", "icpgpu_get_p2plane_symmetric",
     "icpgpu_reduce_symmetric_point_to_plane", "icpgpu_solve_symmetric_point_to_plane",
@@ -214,6 +220,7 @@ def load():
     L.icpgpu_search_radius.argtypes = [vp, fp, C.c_size_t, C.c_double, C.c_int, C.c_size_t, C.POINTER(C.c_int64), ip, fp, C.POINTER(C.c_size_t)]
     L.icpgpu_normal_estimation.argtypes = [vp, fp, C.c_size_t, C.c_int, C.c_double, fp, fp, ip, fp]
     L.icpgpu_fpfh_estimation.argtypes = [vp, fp, fp, C.c_size_t, C.c_int, C.c_double, fp, ip, fp]
+    L.icpgpu_feature_knn.argtypes = [vp, fp, C.c_size_t, fp, C.c_size_t, C.c_int, ip, fp, ip]
     L.icpgpu_euclidean_cluster_extraction.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.icpgpu_cluster_fetch.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_int64), ip, ip, ip]
     szp = C.POINTER(C.c_size_t)
@@ -222,6 +229,9 @@ def load():
     L.icpgpu_sac_stats.argtypes = [vp, ip]
     L.icpgpu_sac_extract.argtypes = [vp, C.c_int, fp, szp]
     L.icpgpu_sac_extract_view.argtypes = [vp, C.c_int, C.POINTER(fp), szp]
+    L.icpgpu_scp_align.argtypes = [vp, fp, C.c_size_t, fp, fp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64, fp, szp, fp, ip, fp]
+    L.icpgpu_scp_fetch.argtypes = [vp, C.c_size_t, C.c_size_t, ip, ip, ip, fp, ip, dp, fp, ip, ip]
+    L.icpgpu_scp_stats.argtypes = [vp, ip, ip, dp]
     pp, lp = C.POINTER(Pose), C.POINTER(C.c_long)
     L.icpgpu_pose_from_matrix.argtypes = [fp, pp]
     L.icpgpu_pose_to_matrix.argtypes = [pp, fp]

@@ -8,6 +8,7 @@
 //   icpgpu_batch.cpp    icpgpu_align_batch: lock-step groups and the round-robin scheduler
 //   icpgpu_voxel.cpp    the voxel-grid filter's host side
 //   icpgpu_map.cpp      the mapper's map and its nn cloud
+//   icpgpu_feature.cpp  feature-space k-nearest and the sample-consensus alignment over it
 // (until round 4 all of this was one 3 200-line icpgpu_api.cpp).
 #pragma once
 
@@ -438,6 +439,28 @@ struct icpgpu_ctx {
     DeviceBuf batch, flags, pos, scan, inliers, ints, sums;
     DeviceBuf xflags, xpos, kept;  // icpgpu_sac_extract's own
   } sac;
+  // feature-space k-nearest (icpgpu_feature.cpp, icp_feature.hip): the call's descriptors and rows, in buffers no other call reads or
+  // writes -- it neither uses nor touches the search cloud, and an unfetched clustering or segmentation result survives it
+  struct Feature {
+    DeviceBuf target, query, finite, idx, d2, n_found;
+  } feature;
+  // sample-consensus alignment (icpgpu_feature.cpp, icp_feature.hip): the last call's result over the search cloud and its scratch, in
+  // buffers no other call writes -- an unfetched result outlives later search, normal, FPFH, feature, clustering and segmentation
+  // calls; icpgpu_search_set_input drops it
+  struct Scp {
+    bool have = false;
+    size_t n = 0, n_s = 0, n_inliers = 0;
+    int nr = 0, max_iterations = 0, converged = 0, best_t = -1, waits = 0, evaluated = 0;
+    double solve_ms = 0.0;
+    float fitness = FLT_MAX;
+    float T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    std::vector<int32_t> status, sidx, tidx, count;  // per hypothesis (sidx / tidx: nr each)
+    std::vector<float> transforms, error;            // 16 each, column-major; FLT_MAX without inliers
+    std::vector<double> sum;
+    DeviceBuf source, sfeat, tfeat, finite, rows, rows_d2, found;     // the inputs and the correspondence rows
+    DeviceBuf c_status, c_sidx, c_tidx, c_sums, xforms, partials, results;  // a chunk's
+    DeviceBuf flags, pos, scan, inliers, ints, aligned;              // the best hypothesis'
+  } scp;
   std::vector<icpgpu_ctx*> workers;  // align_batch: one sub-context (own stream + scratch) per host worker thread
   DeviceBuf batch_table;             // lock-step batch: the BatchPair table of the group this context leads
   std::atomic<size_t> batch_table_cells{0};   // align_batch: the largest cell table any worker has needed (icpgpu_index.cpp)
@@ -677,6 +700,13 @@ int reject_fetch_stats(icpgpu_ctx* c);
 int sweep_issue_rejected(icpgpu_ctx* c, const Xform& T, float thr, SweepTicket& tk);
 // icpgpu_outlier.cpp: a cloud's k-NN grid, its first cell size taken from the cloud's own box (the filters and the neighbour search)
 int build_knn_grid(icpgpu_ctx* c, const Cloud& cloud, GridIndex& G);
+// icpgpu_search.cpp: up to a few device arrays into the caller's (pageable) arrays through the pinned staging buffer, ONE wait
+struct Delivery {
+  void* dst;
+  const void* d_src;
+  size_t bytes;
+};
+int deliver(icpgpu_ctx* c, const Delivery* parts, int n_parts);
 // icpgpu_ndt.cpp
 int align_ndt(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitness, icpgpu_result* res);
 

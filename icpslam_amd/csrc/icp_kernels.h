@@ -613,4 +613,48 @@ hipError_t launch_spfh_from_rows(const float4* cloud, int n, const float4* norma
 hipError_t launch_fpfh_from_rows(const float4* queries, int n_q, int n, const float* spfh, const int32_t* idx, const float* d2, const int32_t* n_found,
                                  int k, const int* row_start, float* out, hipStream_t stream);
 
+// ---- feature-space k-nearest (icp_feature.hip): pcl::KdTreeFLANN<FPFHSignature33>::nearestKSearch -----------------------------------
+// Row q of idx / d2 (k entries each, k <= 64) = the k smallest keys (d2 bits << 32 | target row) of query row q over the target rows
+// whose 33 components are all finite, ascending, padded with -1 / +inf; n_found[q] = how many there are (0 for a query row with a
+// non-finite component).  d2 is the 33-term fma chain of include/icpgpu.h.  target_finite: n_t ints of scratch (written first).
+static constexpr int kFeatureBins = 33;   // = ICPGPU_FPFH_BINS
+static constexpr int kFeatureTile = 256;  // target rows a workgroup stages at a time (the tests' tile edge)
+hipError_t launch_feature_knn(const float* target, int n_t, const float* query, int n_q, int k, int* target_finite, int32_t* idx, float* d2,
+                              int32_t* n_found, hipStream_t stream);
+
+// ---- sample-consensus alignment with pre-rejection (icp_feature.hip): pcl::SampleConsensusPrerejective ------------------------------
+static constexpr int kScpChunk = 65536;     // = ICPGPU_SCP_CHUNK: hypotheses sampled per launch (and per host wait)
+static constexpr int kScpBatch = 64;        // surviving hypotheses per evaluation launch
+static constexpr int kScpMaxSamples = 8;    // = ICPGPU_SCP_MAX_SAMPLES
+static constexpr int kScpBlockPoints = 64;  // source points per workgroup of the evaluation
+static constexpr int kScpInvalid = 0, kScpPrerejected = 1, kScpNoTransform = 2, kScpEvaluated = 3;  // = ICPGPU_SCP_*
+struct ScpBox {  // the target's box grown by the correspondence distance: an image outside it is no inlier (use = 0: no box known)
+  float lo[3], hi[3];
+  int use;
+};
+struct ScpPartial {
+  long long count;
+  double hi, lo;
+};
+struct ScpResult {
+  long long count;
+  double sum;
+};
+// hypotheses t0 .. t0 + m - 1 (m <= kScpChunk): status[e] (kScpEvaluated = survived the pre-rejection), the nr source and target indices
+// (-1 where there is none), and for a survivor the 17 sums of solve_umeyama over its pairs (sum d2 = 0).  rows / found: the source's
+// feature rows (kc entries each) over the target's descriptors.
+hipError_t launch_scp_sample(const float4* source, int n_s, const float4* cloud, int n, const int32_t* rows, const int32_t* found, int kc,
+                             unsigned long long seed, int t0, int m, int nr, float sim2, int32_t* status, int32_t* sidx, int32_t* tidx, double* sums,
+                             hipStream_t stream);
+// results[h] = {inliers, the exact sum of their d2 rounded once} of xforms[h], h < n_h <= kScpBatch, over the search cloud (cloud, n,
+// sorted, cell_start, g, shells: as launch_search_radius_count).  partials: scp_eval_blocks(n_s) x kScpBatch.
+int scp_eval_blocks(int n_s);
+hipError_t launch_scp_eval(const float4* source, int n_s, const Xform* xforms, int n_h, const float4* cloud, int n, const float4* sorted,
+                           const int* cell_start, const GridDesc& g, int shells, const ScpBox& box, float r2, ScpPartial* partials, ScpResult* results,
+                           hipStream_t stream);
+// the inliers of T, ascending, and their number; flags, pos, inliers: n_s ints each; scan_scratch: exclusive_scan_scratch_ints(n_s)
+hipError_t launch_scp_select(const float4* source, int n_s, const Xform& T, const float4* cloud, int n, const float4* sorted, const int* cell_start,
+                             const GridDesc& g, int shells, const ScpBox& box, float r2, int* flags, int* pos, int* scan_scratch, int* inliers,
+                             int* n_inliers, hipStream_t stream);
+
 }  // namespace icpgpu

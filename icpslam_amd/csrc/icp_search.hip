@@ -47,40 +47,7 @@ namespace {
 constexpr int SR_BLOCK = 256, SR_WAVES = SR_BLOCK / 64;
 constexpr int kSearchShells = 6;    // shells 0..6 (13^3 cells at most) before a query is left to the far list
 
-__device__ __forceinline__ u64 shfl_xor_key(u64 v, int j) {  // a key moves in two halves
-  const unsigned int lo = (unsigned int)__shfl_xor((int)(unsigned int)v, j, 64), hi = (unsigned int)__shfl_xor((int)(unsigned int)(v >> 32), j, 64);
-  return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 readlane_key(u64 v, int lane) {  // lane must be wave-uniform
-  const unsigned int lo = (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)v, lane),
-                     hi = (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)(v >> 32), lane);
-  return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 key_min(u64 a, u64 b) { return a < b ? a : b; }
-__device__ __forceinline__ u64 key_max(u64 a, u64 b) { return a < b ? b : a; }
-
-// ---- the keyed selection ---------------------------------------------------------------------------------------------
-// keep: ascending over the lanes (kEmptyKey = nothing yet); cand: one candidate per lane (kEmptyKey = none).  K - 1 (wave-uniform)
-// is the lane of the worst key that still counts.  Whole keys are compared everywhere.
-__device__ __forceinline__ void key_offer(u64 cand, u64& keep, int K, unsigned int lane) {
-  const u64 worst = readlane_key(keep, K - 1);
-  if (__ballot(cand < worst) == 0ull) return;
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const u64 o = shfl_xor_key(cand, j);
-      const bool desc = (lane & (unsigned int)k) == 0u, lower = (lane & (unsigned int)j) == 0u;
-      cand = (lower == desc) ? key_max(cand, o) : key_min(cand, o);
-    }
-  }
-  keep = key_min(keep, cand);  // ascending against descending: the 64 smallest of both, a bitonic sequence
-#pragma unroll
-  for (int j = 32; j > 0; j >>= 1) {
-    const u64 o = shfl_xor_key(keep, j);
-    keep = (lane & (unsigned int)j) == 0u ? key_min(keep, o) : key_max(keep, o);
-  }
-}
+// (the keyed selection -- shfl_xor_key, readlane_key, key_offer -- and write_knn_row: icp_search_device.h)
 
 // (where candidates come from -- segment_batches, cube_batches, sweep_batches, query_cell, ball_batches: icp_search_device.h)
 
@@ -121,18 +88,6 @@ __device__ __forceinline__ void shell_batches(const float4* __restrict__ sorted,
       }
     }
   }
-}
-
-// the first k lanes of a kept list as row `q` of idx / d2 (k entries, row-major) and n_found[q]
-__device__ __forceinline__ void write_knn_row(u64 keep, int k, size_t q, unsigned int lane, int32_t* __restrict__ idx, float* __restrict__ d2,
-                                              int32_t* __restrict__ n_found) {
-  const bool mine = (int)lane < k, found = mine && keep != kEmptyKey;
-  if (mine) {
-    idx[q * (size_t)k + lane] = found ? (int32_t)(unsigned int)keep : -1;
-    d2[q * (size_t)k + lane] = found ? __uint_as_float((unsigned int)(keep >> 32)) : __builtin_inff();
-  }
-  const int m = __popcll(__ballot(found));
-  if (n_found && lane == 0) n_found[q] = m;
 }
 
 // ---- k-nearest -------------------------------------------------------------------------------------------------------

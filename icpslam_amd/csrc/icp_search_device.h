@@ -1,5 +1,6 @@
 // icp_search_device.h -- device helpers of the neighbour search that more than one unit walks a ball with (internal): the keys and
-// the walk of icp_search.hip's radius search, shared with icp_cluster.hip.  Moved here unchanged from icp_search.hip.
+// the walk of icp_search.hip's radius search, shared with icp_cluster.hip, and the keyed selection of its k-nearest search, shared
+// with icp_feature.hip.  Moved here unchanged from icp_search.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,6 +17,53 @@ typedef unsigned long long u64;
 constexpr int kSearchOutside = 64;  // cells a query may lie outside the grid and still be walked from its clamped cell
 
 __device__ __forceinline__ u64 make_key(float d, unsigned int index) { return ((u64)__float_as_uint(d) << 32) | index; }
+
+__device__ __forceinline__ u64 shfl_xor_key(u64 v, int j) {  // a key moves in two halves
+  const unsigned int lo = (unsigned int)__shfl_xor((int)(unsigned int)v, j, 64), hi = (unsigned int)__shfl_xor((int)(unsigned int)(v >> 32), j, 64);
+  return ((u64)hi << 32) | lo;
+}
+__device__ __forceinline__ u64 readlane_key(u64 v, int lane) {  // lane must be wave-uniform
+  const unsigned int lo = (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)v, lane),
+                     hi = (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)(v >> 32), lane);
+  return ((u64)hi << 32) | lo;
+}
+__device__ __forceinline__ u64 key_min(u64 a, u64 b) { return a < b ? a : b; }
+__device__ __forceinline__ u64 key_max(u64 a, u64 b) { return a < b ? b : a; }
+
+// ---- the keyed selection ---------------------------------------------------------------------------------------------
+// keep: ascending over the lanes (kEmptyKey = nothing yet); cand: one candidate per lane (kEmptyKey = none).  K - 1 (wave-uniform)
+// is the lane of the worst key that still counts.  Whole keys are compared everywhere.
+__device__ __forceinline__ void key_offer(u64 cand, u64& keep, int K, unsigned int lane) {
+  const u64 worst = readlane_key(keep, K - 1);
+  if (__ballot(cand < worst) == 0ull) return;
+#pragma unroll
+  for (int k = 2; k <= 64; k <<= 1) {
+#pragma unroll
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const u64 o = shfl_xor_key(cand, j);
+      const bool desc = (lane & (unsigned int)k) == 0u, lower = (lane & (unsigned int)j) == 0u;
+      cand = (lower == desc) ? key_max(cand, o) : key_min(cand, o);
+    }
+  }
+  keep = key_min(keep, cand);  // ascending against descending: the 64 smallest of both, a bitonic sequence
+#pragma unroll
+  for (int j = 32; j > 0; j >>= 1) {
+    const u64 o = shfl_xor_key(keep, j);
+    keep = (lane & (unsigned int)j) == 0u ? key_min(keep, o) : key_max(keep, o);
+  }
+}
+
+// the first k lanes of a kept list as row `q` of idx / d2 (k entries, row-major) and n_found[q]
+__device__ __forceinline__ void write_knn_row(u64 keep, int k, size_t q, unsigned int lane, int32_t* __restrict__ idx, float* __restrict__ d2,
+                                              int32_t* __restrict__ n_found) {
+  const bool mine = (int)lane < k, found = mine && keep != kEmptyKey;
+  if (mine) {
+    idx[q * (size_t)k + lane] = found ? (int32_t)(unsigned int)keep : -1;
+    d2[q * (size_t)k + lane] = found ? __uint_as_float((unsigned int)(keep >> 32)) : __builtin_inff();
+  }
+  const int m = __popcll(__ballot(found));
+  if (n_found && lane == 0) n_found[q] = m;
+}
 
 // ---- where candidates come from --------------------------------------------------------------------------------------
 // f(key) is called by the whole wave once per batch of 64 candidates: the candidate's key in its lane, kEmptyKey in a lane that

@@ -680,6 +680,12 @@ int icpgpu_destroy(icpgpu_ctx* c) {
   for (DeviceBuf* b : {&c->sac.batch, &c->sac.flags, &c->sac.pos, &c->sac.scan, &c->sac.inliers, &c->sac.ints, &c->sac.sums, &c->sac.xflags,
                        &c->sac.xpos, &c->sac.kept})
     release(*b);
+  for (DeviceBuf* b : {&c->scp.source, &c->scp.sfeat, &c->scp.tfeat, &c->scp.finite, &c->scp.rows, &c->scp.rows_d2, &c->scp.found, &c->scp.c_status,
+                       &c->scp.c_sidx, &c->scp.c_tidx, &c->scp.c_sums, &c->scp.xforms, &c->scp.partials, &c->scp.results, &c->scp.flags, &c->scp.pos,
+                       &c->scp.scan, &c->scp.inliers, &c->scp.ints, &c->scp.aligned})
+    release(*b);
+  for (DeviceBuf* b : {&c->feature.target, &c->feature.query, &c->feature.finite, &c->feature.idx, &c->feature.d2, &c->feature.n_found})
+    release(*b);
   for (GridIndex* G : {&c->grid, &c->src_grid, &c->map.grid, &c->outlier.grid, &c->search.grid}) {
     release(G->sorted);
     release(G->cell_start);

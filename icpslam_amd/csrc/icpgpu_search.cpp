@@ -52,40 +52,6 @@ int stage_queries(icpgpu_ctx* c, const char* what, const float* queries_xyzw, si
   return ICPGPU_OK;
 }
 
-// Results on their way to the caller's (pageable) arrays: up to three device arrays copied into consecutive slices of the pinned
-// staging buffer -- copies the stream really queues -- ONE wait for the stream, then a memcpy each.  Results that do not fit the
-// staging buffer (kStageMaxBytes) are copied straight into the caller's memory, where the runtime may wait inside every copy.
-struct Delivery {
-  void* dst;
-  const void* d_src;
-  size_t bytes;
-};
-int deliver(icpgpu_ctx* c, const Delivery* parts, int n_parts) {
-  size_t total = 0;
-  for (int i = 0; i < n_parts; ++i) total += (parts[i].bytes + 15) & ~(size_t)15;
-  if (total == 0) return ICPGPU_OK;
-  if (total > kStageMaxBytes) {
-    for (int i = 0; i < n_parts; ++i)
-      if (parts[i].bytes) HIP_TRY(c, hipMemcpyAsync(parts[i].dst, parts[i].d_src, parts[i].bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return ICPGPU_OK;
-  }
-  int rc;
-  if ((rc = ensure_stage(c, total))) return rc;
-  size_t at = 0;
-  for (int i = 0; i < n_parts; ++i) {
-    if (parts[i].bytes) HIP_TRY(c, hipMemcpyAsync(static_cast<char*>(c->h_stage) + at, parts[i].d_src, parts[i].bytes, hipMemcpyDeviceToHost, c->stream));
-    at += (parts[i].bytes + 15) & ~(size_t)15;
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  at = 0;
-  for (int i = 0; i < n_parts; ++i) {
-    if (parts[i].bytes) std::memcpy(parts[i].dst, static_cast<const char*>(c->h_stage) + at, parts[i].bytes);
-    at += (parts[i].bytes + 15) & ~(size_t)15;
-  }
-  return ICPGPU_OK;
-}
-
 // what launch_search_radius_count writes for `rows` = n_q + 1 row starts (a buffer that grows is freed first, which waits for the
 // device: a call that queues two searches reserves the larger one before the first)
 int reserve_radius_rows(icpgpu_ctx* c, size_t rows) {
@@ -138,13 +104,43 @@ int queue_radius_fill(icpgpu_ctx* c, const float4* d_queries, size_t n_q, int sh
 }
 
 }  // namespace
+
+// (Delivery: icp_ctx.h)  Results on their way to the caller's (pageable) arrays: up to three device arrays copied into consecutive slices of the pinned
+// staging buffer -- copies the stream really queues -- ONE wait for the stream, then a memcpy each.  Results that do not fit the
+// staging buffer (kStageMaxBytes) are copied straight into the caller's memory, where the runtime may wait inside every copy.
+int deliver(icpgpu_ctx* c, const Delivery* parts, int n_parts) {
+  size_t total = 0;
+  for (int i = 0; i < n_parts; ++i) total += (parts[i].bytes + 15) & ~(size_t)15;
+  if (total == 0) return ICPGPU_OK;
+  if (total > kStageMaxBytes) {
+    for (int i = 0; i < n_parts; ++i)
+      if (parts[i].bytes) HIP_TRY(c, hipMemcpyAsync(parts[i].dst, parts[i].d_src, parts[i].bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return ICPGPU_OK;
+  }
+  int rc;
+  if ((rc = ensure_stage(c, total))) return rc;
+  size_t at = 0;
+  for (int i = 0; i < n_parts; ++i) {
+    if (parts[i].bytes) HIP_TRY(c, hipMemcpyAsync(static_cast<char*>(c->h_stage) + at, parts[i].d_src, parts[i].bytes, hipMemcpyDeviceToHost, c->stream));
+    at += (parts[i].bytes + 15) & ~(size_t)15;
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  at = 0;
+  for (int i = 0; i < n_parts; ++i) {
+    if (parts[i].bytes) std::memcpy(parts[i].dst, static_cast<const char*>(c->h_stage) + at, parts[i].bytes);
+    at += (parts[i].bytes + 15) & ~(size_t)15;
+  }
+  return ICPGPU_OK;
+}
+
 }  // namespace icpgpu_impl
 
 extern "C" {
 
 // Copies the cloud and builds its k-NN grid.  Nothing of the context's source, target, their grids, the covariances, the NDT cells
-// or the filters' results is touched; the previous search cloud, and a clustering or
-// plane segmentation result over it, is gone whatever this call returns.
+// or the filters' results is touched; the previous search cloud, and a clustering,
+// plane segmentation or sample-consensus alignment result over it, is gone whatever this call returns.
 int icpgpu_search_set_input(icpgpu_ctx* c, const float* xyzw, size_t n) {
   ENTER(c);
   auto& S = c->search;
@@ -154,6 +150,7 @@ int icpgpu_search_set_input(icpgpu_ctx* c, const float* xyzw, size_t n) {
   S.grid.built = S.grid.usable = false;  // (version 0: a build never stands for the next cloud)
   c->cluster.have = false;               // (a clustering result is a result over the cloud that goes)
   c->sac.have = false;                   // (and so is a plane segmentation)
+  c->scp.have = false;                   // (and a sample-consensus alignment)
   if (n && !xyzw) return fail(c, ICPGPU_ERR_INVALID_ARG, "null cloud pointer with n = %zu", n);
   if (n > (size_t)INT32_MAX - 4096) return fail(c, ICPGPU_ERR_INVALID_ARG, "cloud too large: %zu points", n);
   if (n) {

@@ -53,6 +53,7 @@ class Context:
         self._h = h
         self.n_source = 0
         self.n_target = 0
+        self._scp_last = (0, 3, 0)  # (max_iterations, nr_samples, n_inliers) of the last scp_align_raw call: what scp_fetch sizes its arrays by
         self._sac_last = (0, 0)  # (n_inliers, iterations) of the last sac_segment_raw call: what sac_fetch sizes its arrays by
 
     def close(self):
@@ -598,6 +599,95 @@ class Context:
                                                    None if spfh is None else _fp(spfh)))
         return (fpfh, count, spfh) if want_spfh else (fpfh, count)
 
+    # feature-space k-nearest (pcl::KdTreeFLANN<FPFHSignature33>; rules: include/icpgpu.h) --------------------------------------
+    def feature_knn_raw(self, target_feat, query_feat, k: int, n_t: int | None = None, n_q: int | None = None) -> tuple:
+        """One icpgpu_feature_knn call into arrays pre-filled with -2 / NaN: (rc, idx, d2, n_found).  target_feat / query_feat may be
+        None and n_t / n_q given (only to test the refusals)."""
+        tf = None if target_feat is None else np.ascontiguousarray(target_feat, np.float32).reshape(-1, FPFH_BINS)
+        qf = None if query_feat is None else np.ascontiguousarray(query_feat, np.float32).reshape(-1, FPFH_BINS)
+        n_t = (0 if tf is None else tf.shape[0]) if n_t is None else int(n_t)
+        n_q = (0 if qf is None else qf.shape[0]) if n_q is None else int(n_q)
+        kk = max(int(k), 0)
+        idx = np.full((n_q, kk), -2, np.int32)
+        d2 = np.full((n_q, kk), np.nan, np.float32)
+        n_found = np.full(n_q, -2, np.int32)
+        ip = C.POINTER(C.c_int32)
+        rc = self._L.icpgpu_feature_knn(self._h, None if tf is None else _fp(tf), n_t, None if qf is None else _fp(qf), n_q, int(k),
+                                        idx.ctypes.data_as(ip), _fp(d2), n_found.ctypes.data_as(ip))
+        return rc, idx, d2, n_found
+
+    def feature_knn(self, target_feat, query_feat, k: int):
+        """(idx (n_q, k) int32, d2 (n_q, k) float32, n_found (n_q,) int32): every query descriptor's k nearest target descriptors
+        (rows of 33 floats, as fpfh_estimation returns them), ascending by (d2, index), padded with -1 / +inf.  Rows with a
+        non-finite component are never neighbours and find nothing."""
+        rc, idx, d2, n_found = self.feature_knn_raw(target_feat, query_feat, k)
+        self._check(rc)
+        return idx, d2, n_found
+
+    # sample-consensus alignment (pcl::SampleConsensusPrerejective; rules: include/icpgpu.h) ------------------------------------
+    def scp_align_raw(self, source, source_feat, target_feat, nr_samples: int = 3, k_correspondences: int = 2, similarity_threshold: float = 0.9,
+                      max_correspondence_distance: float = 1.0, inlier_fraction: float = 0.25, max_iterations: int = 1000, seed: int = 0,
+                      want_cloud: bool = True) -> tuple:
+        """One icpgpu_scp_align call over the search cloud (the target): (rc, T (4, 4) float32, n_inliers, fitness, converged, aligned
+        cloud or None); the result stays in the context.  source / source_feat / target_feat may be None (only to test the refusals)."""
+        src = None if source is None else _as_cloud(source)
+        sf = None if source_feat is None else np.ascontiguousarray(source_feat, np.float32).reshape(-1, FPFH_BINS)
+        tf = None if target_feat is None else np.ascontiguousarray(target_feat, np.float32).reshape(-1, FPFH_BINS)
+        n_s = 0 if src is None else src.shape[0]
+        if sf is not None and sf.shape[0] != n_s:
+            raise IcpGpuError(_lib.ERR_INVALID_ARG, f"scp_align: {sf.shape[0]} descriptors for {n_s} source points")
+        if tf is not None and tf.shape[0] != self.search_size()[0]:
+            raise IcpGpuError(_lib.ERR_INVALID_ARG, f"scp_align: {tf.shape[0]} descriptors for a search cloud of {self.search_size()[0]} points")
+        T = np.full(16, -2, np.float32)
+        out = np.full((n_s, 4), np.nan, np.float32) if want_cloud else None
+        n_in, fit, conv = C.c_size_t(), C.c_float(), C.c_int32()
+        rc = self._L.icpgpu_scp_align(self._h, None if src is None else _fp(src), n_s, None if sf is None else _fp(sf), None if tf is None else _fp(tf),
+                                      int(nr_samples), int(k_correspondences), float(similarity_threshold), float(max_correspondence_distance),
+                                      float(inlier_fraction), int(max_iterations), int(seed) & (2**64 - 1), _fp(T), C.byref(n_in), C.byref(fit),
+                                      C.byref(conv), None if out is None else _fp(out))
+        self._scp_last = (max(int(max_iterations), 0), int(nr_samples), int(n_in.value))
+        return rc, T.reshape(4, 4).T.copy(), int(n_in.value), float(fit.value), int(conv.value), out
+
+    def scp_fetch_raw(self, capacity_hypotheses: int, capacity_inliers: int, nr_samples: int) -> tuple:
+        """One icpgpu_scp_fetch call into arrays pre-filled with -2: (rc, dict of everything the fetch hands out)."""
+        ip = C.POINTER(C.c_int32)
+        h, nr = int(capacity_hypotheses), int(nr_samples)
+        status, counts = np.full(h, -2, np.int32), np.full(h, -2, np.int32)
+        sidx, tidx = np.full((h, nr), -2, np.int32), np.full((h, nr), -2, np.int32)
+        transforms = np.full((h, 16), -2, np.float32)
+        sums, errors = np.full(h, -2, np.float64), np.full(h, -2, np.float32)
+        inliers = np.full(int(capacity_inliers), -2, np.int32)
+        best_t = C.c_int32(-2)
+        rc = self._L.icpgpu_scp_fetch(self._h, h, int(capacity_inliers), status.ctypes.data_as(ip), sidx.ctypes.data_as(ip), tidx.ctypes.data_as(ip),
+                                      _fp(transforms), counts.ctypes.data_as(ip), sums.ctypes.data_as(C.POINTER(C.c_double)), _fp(errors),
+                                      C.byref(best_t), inliers.ctypes.data_as(ip))
+        return rc, {"status": status, "source_idx": sidx, "target_idx": tidx, "transforms": transforms, "count": counts, "sum": sums, "error": errors,
+                    "best_t": int(best_t.value), "inliers": inliers}
+
+    def scp_align(self, source, source_feat, target_feat, **kw) -> dict:
+        """The pose of `source` in the search cloud without a guess: dict(T (4, 4) float32, converged, fitness, inliers (ascending int32),
+        cloud (the aligned source)).  Keywords as scp_align_raw."""
+        rc, T, n_in, fit, conv, cloud = self.scp_align_raw(source, source_feat, target_feat, **kw)
+        self._check(rc)
+        inliers = np.empty(n_in, np.int32)                     # the inliers alone: no per-hypothesis array is allocated or copied
+        self._check(self._L.icpgpu_scp_fetch(self._h, 0, n_in, None, None, None, None, None, None, None, None,
+                                             inliers.ctypes.data_as(C.POINTER(C.c_int32))))
+        return {"T": T, "converged": bool(conv), "fitness": fit, "inliers": inliers, "cloud": cloud}
+
+    def scp_fetch(self) -> dict:
+        """Everything icpgpu_scp_fetch hands out of the last alignment: per hypothesis status, source_idx, target_idx, transforms (16,
+        column-major), count, sum, error; best_t and the inliers."""
+        it, nr, n_in = self._scp_last
+        rc, out = self.scp_fetch_raw(it, n_in, nr)
+        self._check(rc)
+        return out
+
+    def scp_stats(self) -> dict:
+        """host_waits, evaluated hypotheses and the host's solve time (ms) of the last alignment (icpgpu_scp_stats)."""
+        w, e, ms = C.c_int32(), C.c_int32(), C.c_double()
+        self._check(self._L.icpgpu_scp_stats(self._h, C.byref(w), C.byref(e), C.byref(ms)))
+        return {"host_waits": int(w.value), "evaluated": int(e.value), "host_solve_ms": float(ms.value)}
+
     # euclidean clustering (pcl::EuclideanClusterExtraction; rules: include/icpgpu.h) --------------------------------------
     def cluster_extract_raw(self, tolerance: float, min_size: int, max_size: int) -> tuple:
         """One icpgpu_euclidean_cluster_extraction call: (rc, n_clusters, n_clustered); the result stays in the context."""
@@ -1114,6 +1204,115 @@ class FPFHEstimation:
         self._ctx.search_set_input(surface)
         fpfh, self._n_neighbours = self._ctx.fpfh_estimation(self._normals, None if self._surface is None else self._input, self._k, self._radius)
         return fpfh
+
+
+class FeatureKdTree:
+    """pcl::KdTreeFLANN<pcl::FPFHSignature33>-shaped front end (include/icpgpu.h, "feature-space k-nearest"): setInputCloud with
+    (n, 33) descriptors, nearestKSearch(queries, k) -> (idx (n_q, k) int32, d2 (n_q, k) float32), padded with -1 / +inf."""
+
+    def __init__(self, device_id: int = 0):
+        self._ctx = Context(device_id)
+        self._input = None
+
+    def setInputCloud(self, features):
+        self._input = np.ascontiguousarray(features, np.float32).reshape(-1, FPFH_BINS).copy()
+
+    def nearestKSearch(self, queries, k: int):
+        if self._input is None:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "nearestKSearch: setInputCloud first")
+        idx, d2, _ = self._ctx.feature_knn(self._input, np.ascontiguousarray(queries, np.float32).reshape(-1, FPFH_BINS), k)
+        return idx, d2
+
+
+class SampleConsensusPrerejective:
+    """pcl::SampleConsensusPrerejective<PointXYZ, PointXYZ, FPFHSignature33>-shaped front end (include/icpgpu.h, "sample-consensus
+    alignment"): setInputSource, setSourceFeatures, setInputTarget, setTargetFeatures, setNumberOfSamples, setCorrespondenceRandomness,
+    setSimilarityThreshold, setMaxCorrespondenceDistance, setInlierFraction, setMaximumIterations, our own setSeed, align() -> the
+    aligned source, hasConverged, getFinalTransformation, getInliers, getFitnessScore.  The defaults are PCL's (3 samples, randomness
+    2, similarity 0.9, inlier fraction 0; Registration's 10 iterations and sqrt(DBL_MAX) distance are replaced by 1000 and 1.0: the
+    call refuses a distance whose square is not a float).  A guess is not provided."""
+
+    def __init__(self, device_id: int = 0):
+        self._ctx = Context(device_id)
+        self._source = self._target = self._sf = self._tf = None
+        self._nr, self._k, self._sim, self._dist, self._frac, self._it, self._seed = 3, 2, 0.9, 1.0, 0.0, 1000, 0
+        self._T = np.eye(4, dtype=np.float32)
+        self._converged = False
+        self._fitness = float(np.finfo(np.float32).max)
+        self._inliers = np.empty(0, np.int32)
+
+    def setInputSource(self, cloud):
+        self._source = _as_cloud(cloud).copy()
+
+    def setSourceFeatures(self, features):
+        self._sf = np.ascontiguousarray(features, np.float32).reshape(-1, FPFH_BINS).copy()
+
+    def setInputTarget(self, cloud):
+        self._target = _as_cloud(cloud).copy()
+
+    def setTargetFeatures(self, features):
+        self._tf = np.ascontiguousarray(features, np.float32).reshape(-1, FPFH_BINS).copy()
+
+    def setNumberOfSamples(self, nr_samples: int):
+        self._nr = int(nr_samples)
+
+    def getNumberOfSamples(self) -> int:
+        return self._nr
+
+    def setCorrespondenceRandomness(self, k: int):
+        self._k = int(k)
+
+    def getCorrespondenceRandomness(self) -> int:
+        return self._k
+
+    def setSimilarityThreshold(self, similarity_threshold: float):
+        self._sim = float(similarity_threshold)
+
+    def getSimilarityThreshold(self) -> float:
+        return self._sim
+
+    def setMaxCorrespondenceDistance(self, distance: float):
+        self._dist = float(distance)
+
+    def getMaxCorrespondenceDistance(self) -> float:
+        return self._dist
+
+    def setInlierFraction(self, inlier_fraction: float):
+        self._frac = float(inlier_fraction)
+
+    def getInlierFraction(self) -> float:
+        return self._frac
+
+    def setMaximumIterations(self, max_iterations: int):
+        self._it = int(max_iterations)
+
+    def getMaximumIterations(self) -> int:
+        return self._it
+
+    def setSeed(self, seed: int):
+        """The seed of the counter-based generator the samples come from (not PCL's, whose samples come from rand())."""
+        self._seed = int(seed)
+
+    def align(self) -> np.ndarray:
+        if self._source is None or self._target is None or self._sf is None or self._tf is None:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "align: setInputSource, setSourceFeatures, setInputTarget and setTargetFeatures first")
+        self._ctx.search_set_input(self._target)
+        r = self._ctx.scp_align(self._source, self._sf, self._tf, nr_samples=self._nr, k_correspondences=self._k, similarity_threshold=self._sim,
+                                max_correspondence_distance=self._dist, inlier_fraction=self._frac, max_iterations=self._it, seed=self._seed)
+        self._T, self._converged, self._fitness, self._inliers = r["T"], r["converged"], r["fitness"], r["inliers"]
+        return r["cloud"]
+
+    def hasConverged(self) -> bool:
+        return self._converged
+
+    def getFinalTransformation(self) -> np.ndarray:
+        return self._T
+
+    def getInliers(self) -> np.ndarray:
+        return self._inliers
+
+    def getFitnessScore(self) -> float:
+        return self._fitness
 
 
 class EuclideanClusterExtraction:

@@ -816,6 +816,35 @@ int icpgpu_fpfh_estimation(icpgpu_ctx* ctx, const float* normals_nxyzc /* n floa
                            int k, double radius, float* out_fpfh /* n_q x 33 */, int32_t* n_neighbours /* n_q, may be NULL */,
                            float* spfh /* n x 33, may be NULL */);
 
+/* ---- feature-space k-nearest (added under 1.2) -------------------------------------------------------------------- */
+/* replaces pcl::KdTreeFLANN<pcl::FPFHSignature33>: setInputCloud, nearestKSearch -- and, with it, feature-space
+ * pcl::registration::CorrespondenceEstimation: "which descriptors of that cloud are the k nearest to this descriptor", for any number
+ * of query descriptors in one call.  It is the matching step of global registration, between icpgpu_fpfh_estimation and a
+ * sample-consensus alignment.  The rules restate FLANN's exact search with the L2 distance; parity with PCL binaries is unpinned
+ * (tests/scp_restated.py: feature_knn is what the kernel is compared with, bit for bit).
+ * ROWS.  target_feat holds n_t rows and query_feat n_q rows of ICPGPU_FPFH_BINS = 33 floats, row-major, as icpgpu_fpfh_estimation
+ * writes them.  The dimension is fixed.  A row is finite when all 33 of its components are.
+ * DISTANCE.  For query row q and target row t, every operation float32 and rounded on its own except the fused ones:
+ *     d_b = q[b] - t[b];  d2 = d_0 * d_0;  d2 = fmaf(d_b, d_b, d2) for b = 1, 2, ... 32, in that order.
+ * This is ONE definition per pair, whatever the kernel's tiling.  A d2 that overflows is +inf, and the pair is still a neighbour.
+ * ORDER.  A neighbour's key is the search section's: ((uint64)bits(d2) << 32) | target row index.  Row i of idx / d2 (k entries,
+ * row-major; both must hold n_q * k) holds the m = min(k, finite target rows) smallest keys of query i, ascending: by distance, and
+ * among equal distances the lowest target index first (DEVIATION: FLANN leaves the order of equal distances unspecified).  The other
+ * slots hold idx = -1, d2 = +inf.  n_found[i] = m; n_found may be NULL.
+ * NON-FINITE ROWS.  A target row with a non-finite component is never a neighbour.  A query row with a non-finite component finds
+ * nothing: n_found = 0, the whole row -1 / +inf (DEVIATION: PCL asserts).  icpgpu_fpfh_estimation writes such rows (33 NaN) for
+ * non-finite points.
+ * LIMITS.  k must be in 1 .. ICPGPU_SEARCH_MAX_K, else ICPGPU_ERR_INVALID_ARG.  n_t = 0 (every query finds nothing) and n_q = 0
+ * (nothing is written) are ICPGPU_OK.  A null target_feat with n_t > 0, a null query_feat, idx or d2 with n_q > 0:
+ * ICPGPU_ERR_INVALID_ARG.  The search is exhaustive: n_q * n_t chains of 33 terms on the vector ALUs.  A certified low-precision
+ * pre-filter on the matrix cores, as the brute-force nearest neighbour has, is not provided.
+ * ISOLATION.  The call neither uses nor touches the search cloud: its descriptors and rows live in buffers of its own.  It leaves the
+ * source, the target, every grid, the covariances, the cached normals, the NDT cells, the filters' results and the search cloud as
+ * they were; an unfetched clustering or plane segmentation result survives it; and its answers depend on its arguments alone
+ * (DESIGN.md section 9b).  One host wait per call. */
+int icpgpu_feature_knn(icpgpu_ctx* ctx, const float* target_feat /* n_t x 33 */, size_t n_t, const float* query_feat /* n_q x 33 */,
+                       size_t n_q, int k, int32_t* idx /* n_q x k */, float* d2 /* n_q x k */, int32_t* n_found /* n_q, may be NULL */);
+
 /* ---- euclidean clustering (added under 1.2) ------------------------------------------------------------------------ */
 /* replaces pcl::EuclideanClusterExtraction<PointXYZ>: setInputCloud, setClusterTolerance, setMinClusterSize, setMaxClusterSize,
  * extract -- "which points of this cloud belong together".  The call works on the context's SEARCH CLOUD (icpgpu_search_set_input), as
@@ -927,6 +956,92 @@ int icpgpu_sac_fetch(icpgpu_ctx* ctx, size_t capacity_inliers, size_t capacity_c
 int icpgpu_sac_stats(const icpgpu_ctx* ctx, int32_t* host_waits);
 int icpgpu_sac_extract(icpgpu_ctx* ctx, int negative, float* out_xyzw, size_t* n_out);
 int icpgpu_sac_extract_view(icpgpu_ctx* ctx, int negative, const float** view_xyzw, size_t* n_out);
+
+/* ---- sample-consensus alignment with pre-rejection (added under 1.2) ------------------------------------------------ */
+/* replaces pcl::SampleConsensusPrerejective<PointXYZ, PointXYZ, FPFHSignature33>: setInputSource, setSourceFeatures, setInputTarget,
+ * setTargetFeatures, setNumberOfSamples, setCorrespondenceRandomness, setSimilarityThreshold, setMaxCorrespondenceDistance,
+ * setInlierFraction, setMaximumIterations, align, hasConverged, getFinalTransformation, getInliers, getFitnessScore -- the pose of one
+ * cloud in another WITHOUT an initial guess, from matched descriptors: re-localisation and loop closure, and the start every ICP of
+ * this library needs.  The chain icpgpu_voxel_grid -> icpgpu_normal_estimation -> icpgpu_fpfh_estimation -> icpgpu_scp_align -> ICP is
+ * a global registration.  The TARGET is the context's SEARCH CLOUD (icpgpu_search_set_input), whose grid scores a hypothesis;
+ * target_feat are its n descriptors (n x 33 floats); the source cloud (n_s float4) and its n_s descriptors are arguments.  Parity
+ * with PCL binaries is unpinned; tests/scp_restated.py is what the kernels are compared with, bit for bit.  The rules are PCL 1.8's
+ * loop (sample_consensus_prerejective.hpp); each departure is a DEVIATION.
+ * CORRESPONDENCES.  Row i of the source is exactly icpgpu_feature_knn(target_feat, n, source_feat, n_s, k_correspondences)'s row, of
+ * length m_i = n_found[i].  DEVIATION: the rows are computed for every source point up front (and stay on the device); PCL fills
+ * them lazily per sampled point.  The values are the same.
+ * HYPOTHESIS t = 0 .. max_iterations - 1.  DEVIATION, as in plane segmentation: the draws come from that section's counter-based
+ * generator, so a hypothesis is a pure function of (seed, t, sizes).  With nr = nr_samples, draw c = 0 .. 2 nr - 1 is
+ *     z = seed + ((2 nr) t + c + 1) * 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *     z ^= z >> 31;  u_c = z >> 32
+ * in uint64 arithmetic modulo 2^64.  Source index s_c = (u_c * n_s) >> 32 for c < nr; target pick j_c = (u_(nr + c) * m_(s_c)) >> 32,
+ * and the target index is entry j_c of row s_c (-1 when m_(s_c) = 0).  PCL draws without repetition; here a repetition makes the
+ * hypothesis INVALID.  Per-hypothesis status:
+ *   ICPGPU_SCP_INVALID       two equal source indices, a sampled source or target point that is not finite, or an m of 0;
+ *   ICPGPU_SCP_PREREJECTED   the polygon test below failed;
+ *   ICPGPU_SCP_NO_TRANSFORM  the solve below gave no finite transform;
+ *   ICPGPU_SCP_EVALUATED     scored.
+ * An INVALID sample counts as an iteration.
+ * PRE-REJECTION (CorrespondenceRejectorPoly::thresholdPolygon).  For the nr edges (c, (c + 1) mod nr): ds and dt are the squared
+ * lengths between the two sampled source points and between the two sampled target points, the search section's
+ * d2 = fma(dz, dz, fma(dy, dy, dx * dx)) in float32; lo = the smaller, hi = the larger; the edge passes iff
+ * lo / hi >= (float)(similarity_threshold * similarity_threshold), ONE float32 division, the product in double.  A NaN (0 / 0) fails.
+ * All edges must pass.
+ * TRANSFORM.  The 17 sums of icpgpu_solve {nr, sum p, sum q, sum q p^T, 0} over the nr pairs (p the source point, q the target
+ * point), every term and sum in double, accumulated in sample order, go through the host's Umeyama solve (icpgpu_solve); the result
+ * is rounded to float32, column-major.  The DEVICE does not solve: the host does, for every hypothesis that survives the
+ * pre-rejection.  KNOWN COST: with a low similarity threshold that is up to 65536 small SVDs per chunk on one host thread.
+ * FITNESS (getFitness).  For every source point p: p' = T p by the fma chain of DESIGN.md section 3; the nearest finite target point
+ * by key over the search cloud; p is an INLIER iff d2 < r2, strictly, with r2 = (float)(d * d), d = max_correspondence_distance, the
+ * product in double (the radius search's rule).  A non-finite source point, or one with a non-finite image, is never an inlier, but
+ * counts in n_s.  count_t is an exact integer.  S_t is the sum of the inliers' d2 taken in double: the EXACT sum rounded once (the
+ * outlier filter's and the plane refinement's rule), accumulated in double-double in a fixed order.  RANGE: the sum is exact whenever
+ * count^2 * (the largest inlier d2 / the smallest non-zero inlier d2) < 2^80 -- 2^20 inliers between 1e-8 and 1e4 m^2 are inside it;
+ * beyond it S_t is that fixed order's double-double result, within an ulp of the exact sum.  error_t = (float)(S_t / (double)count_t)
+ * when count_t > 0, FLT_MAX otherwise.
+ * CHOICE.  Going through t ascending, t becomes the best iff count_t > 0, (float)count_t / (float)n_s >= (float)inlier_fraction, and
+ * error_t < the best error so far, strictly, starting from FLT_MAX.  PCL has no early stop and neither does this: max_iterations
+ * hypotheses are always considered.  No best: converged = 0, T = identity, zero inliers, fitness = FLT_MAX, and out_xyzw is the
+ * source under the identity.  Otherwise converged = 1 and T16 (column-major), the inlier indices (ascending), fitness = error and the
+ * aligned source out_xyzw (n_s float4, w = 1; may be NULL) are the best hypothesis'.  DEVIATION: a guess is not provided.
+ * CALLS.  icpgpu_scp_align computes and KEEPS the result in the context.  It runs in chunks of ICPGPU_SCP_CHUNK hypotheses: the device
+ * samples and pre-rejects a chunk; one host wait; the host solves the survivors; the device scores them 64 at a time, every launch
+ * queued; one host wait; after the last chunk one pass over the best hypothesis and one more wait.  Host waits: two per chunk (one
+ * where nothing survives) plus one for the best hypothesis' pass; an empty source has no chunks and no pass: 0 waits, and
+ * max_iterations = 0 with a source has the pass alone: 1.  icpgpu_scp_stats reports them, the number of EVALUATED hypotheses and the
+ * host's solve time in ms.  The per-chunk results reach pageable host memory, where the runtime may wait inside a copy: the count is of
+ * the call's own waits.
+ * icpgpu_scp_fetch hands out, any number of times, per hypothesis t in [0, max_iterations): status, the nr source and the nr target
+ * indices (t-major), the float transform (16, column-major; zeros unless EVALUATED), count, S and error; best_t (-1 without one) and
+ * the inliers.  Any output may be NULL; with a per-hypothesis output and capacity_hypotheses < max_iterations, or inliers and
+ * capacity_inliers < n_inliers, nothing is written and the call is ICPGPU_ERR_INVALID_ARG.
+ * ICPGPU_ERR_INVALID_ARG: no search cloud; nr_samples outside 3 .. ICPGPU_SCP_MAX_SAMPLES; k_correspondences outside
+ * 1 .. ICPGPU_SEARCH_MAX_K; a similarity_threshold or inlier_fraction outside [0, 1] or not finite; a distance that is not finite or is
+ * negative; max_iterations outside 0 .. ICPGPU_SCP_MAX_ITERATIONS; a null cloud or descriptor array against a non-zero size; a null
+ * T16, n_inliers, fitness or converged; a fetch or stats without a result (none computed, the last call refused, or the search cloud
+ * replaced since).  max_iterations = 0, an empty source and an empty target are ICPGPU_OK with converged = 0.
+ * LIMITS.  A target the grid refuses is scored without it (up to the 65536 points icpgpu_search_set_input admits then): every source
+ * point sweeps the whole cloud per hypothesis.  So does a correspondence distance whose ball spans more than 8 grid cells, as in
+ * icpgpu_search_radius: both are slow.
+ * ISOLATION.  As plane segmentation: the result lives in buffers of its own, depends on the search cloud and the arguments alone
+ * (DESIGN.md section 9b), survives searches, normal and FPFH estimations, feature searches, clusterings and segmentations, and they
+ * survive it; icpgpu_search_set_input drops it, whatever it returns.  The source, the target, every grid and everything an alignment
+ * reads stay as they were. */
+#define ICPGPU_SCP_CHUNK 65536
+#define ICPGPU_SCP_MAX_ITERATIONS (1 << 20)
+#define ICPGPU_SCP_MAX_SAMPLES 8
+#define ICPGPU_SCP_INVALID 0
+#define ICPGPU_SCP_PREREJECTED 1
+#define ICPGPU_SCP_NO_TRANSFORM 2
+#define ICPGPU_SCP_EVALUATED 3
+int icpgpu_scp_align(icpgpu_ctx* ctx, const float* source_xyzw, size_t n_s, const float* source_feat /* n_s x 33 */,
+                     const float* target_feat /* n x 33, the search cloud's */, int nr_samples, int k_correspondences,
+                     double similarity_threshold, double max_correspondence_distance, double inlier_fraction, int max_iterations, uint64_t seed,
+                     float T16[16], size_t* n_inliers, float* fitness, int32_t* converged, float* out_xyzw /* n_s float4, may be NULL */);
+int icpgpu_scp_fetch(icpgpu_ctx* ctx, size_t capacity_hypotheses, size_t capacity_inliers, int32_t* status, int32_t* source_idx /* it x nr */,
+                     int32_t* target_idx /* it x nr */, float* transforms /* it x 16 */, int32_t* counts, double* sums, float* errors,
+                     int32_t* best_t, int32_t* inliers /* n_inliers */);
+int icpgpu_scp_stats(const icpgpu_ctx* ctx, int32_t* host_waits, int32_t* evaluated, double* host_solve_ms);
 
 /* ---- the mapper's target: a one-point-per-voxel map and its "nn cloud"  -------- */
 /* replaces OctreeMapper's pcl::octree::OctreePointCloudSearch map

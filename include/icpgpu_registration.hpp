@@ -1121,6 +1121,153 @@ class ExtractIndices {
   bool negative_ = false;
 };
 
+// pcl::KdTreeFLANN<pcl::FPFHSignature33> and pcl::SampleConsensusPrerejective<PointSource, PointTarget, FeatureT>-shaped front ends
+// (rules and deviations: include/icpgpu.h, "feature-space k-nearest" and "sample-consensus alignment") -- the pose of a cloud in
+// another WITHOUT a guess, the end of the chain VoxelGrid -> NormalEstimation -> FPFHEstimation and the start ICP needs:
+//   pcl::KdTreeFLANN<pcl::FPFHSignature33> tree;  ->  icpgpu::FeatureKdTree<pcl::PointCloud<pcl::FPFHSignature33>> tree;
+//   tree.setInputCloud(features); tree.nearestKSearch(features->points[i], k, indices, sqr_distances);
+//   pcl::SampleConsensusPrerejective<pcl::PointXYZ, pcl::PointXYZ, pcl::FPFHSignature33> align;
+//     ->  icpgpu::SampleConsensusPrerejective<pcl::PointCloud<pcl::PointXYZ>, pcl::PointCloud<pcl::FPFHSignature33>> align;
+//   align.setInputSource(object); align.setSourceFeatures(object_features); align.setInputTarget(scene);
+//   align.setTargetFeatures(scene_features); align.setMaximumIterations(50000); align.setNumberOfSamples(3);
+//   align.setCorrespondenceRandomness(5); align.setSimilarityThreshold(0.9f); align.setMaxCorrespondenceDistance(0.5);
+//   align.setInlierFraction(0.25f); align.align(aligned); align.hasConverged(); align.getFinalTransformation(); align.getInliers();
+// (the shim's KdTreeFLANN is an alias over POINT clouds, which cannot be specialised for a feature type: the feature tree is a named
+// class.)  The feature point type only needs float histogram[33].  The defaults are PCL's (3 samples, randomness 2, similarity 0.9,
+// inlier fraction 0) except the two PCL inherits from Registration: 1000 iterations instead of 10, and a correspondence distance of
+// 1 m instead of sqrt(DBL_MAX), whose square is not a float.  A refused call leaves the output empty and hasConverged() false.
+// setSeed is ours: the samples come from a counter-based generator.  A guess is not provided.
+template <class FeatureCloudT>
+class FeatureKdTree {
+ public:
+  typedef std::shared_ptr<FeatureKdTree> Ptr;
+  typedef std::shared_ptr<const FeatureKdTree> ConstPtr;
+  explicit FeatureKdTree(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {}
+  template <class CloudPtr>
+  void setInputCloud(const CloudPtr& features) {
+    input_ = &*features;
+    static_assert(sizeof(input_->points[0]) == ICPGPU_FPFH_BINS * sizeof(float), "icpgpu: float histogram[33] and nothing else (pcl::FPFHSignature33)");
+  }
+  template <class FeatureT>
+  int nearestKSearch(const FeatureT& feature, int k, std::vector<int>& k_indices, std::vector<float>& k_sqr_distances) {
+    static_assert(sizeof(feature.histogram) == ICPGPU_FPFH_BINS * sizeof(float), "icpgpu: float histogram[33] (pcl::FPFHSignature33)");
+    return knn(feature.histogram, 1, k, k_indices, k_sqr_distances, nullptr) ? (int)k_indices.size() : 0;
+  }
+  int nearestKSearch(int index, int k, std::vector<int>& k_indices, std::vector<float>& k_sqr_distances) {
+    if (!input_ || index < 0 || (std::size_t)index >= input_->points.size()) return (k_indices.clear(), k_sqr_distances.clear(), 0);
+    return nearestKSearch(input_->points[index], k, k_indices, k_sqr_distances);
+  }
+  // Batched form (not PCL's): every row of `queries` in one call.  Row i of k_indices / k_sqr_distances has k entries, the first
+  // n_found[i] of them neighbours (the rest -1 / +inf); returns the number of queries answered.
+  int nearestKSearch(const FeatureCloudT& queries, int k, std::vector<int>& k_indices, std::vector<float>& k_sqr_distances, std::vector<int>& n_found) {
+    const std::size_t nq = queries.points.size();
+    n_found.assign(nq, 0);
+    if (nq == 0) return (k_indices.clear(), k_sqr_distances.clear(), 0);
+    return knn(queries.points[0].histogram, nq, k, k_indices, k_sqr_distances, &n_found) ? (int)nq : 0;
+  }
+
+ private:
+  bool knn(const float* rows, std::size_t nq, int k, std::vector<int>& k_indices, std::vector<float>& k_sqr_distances, std::vector<int>* n_found) {
+    static_assert(sizeof(int) == sizeof(int32_t), "icpgpu: 32-bit int");
+    k_indices.clear(), k_sqr_distances.clear();
+    if (!input_ || k <= 0) return false;
+    const std::size_t n = input_->points.size();
+    k_indices.assign(nq * (std::size_t)k, -1), k_sqr_distances.resize(nq * (std::size_t)k);
+    int32_t found = 0;
+    const int rc = icpgpu_feature_knn(ctx_, n ? input_->points[0].histogram : nullptr, n, rows, nq, k, reinterpret_cast<int32_t*>(&k_indices[0]),
+                                      &k_sqr_distances[0], n_found ? reinterpret_cast<int32_t*>(&(*n_found)[0]) : &found);
+    if (rc != ICPGPU_OK) {
+      k_indices.clear(), k_sqr_distances.clear();
+      return false;
+    }
+    if (!n_found) k_indices.resize((std::size_t)found), k_sqr_distances.resize((std::size_t)found);  // (PCL returns a short list too)
+    return true;
+  }
+  detail::ContextPtr ctx_holder_;
+  icpgpu_ctx* ctx_;
+  const FeatureCloudT* input_ = nullptr;
+};
+
+template <class CloudT, class FeatureCloudT>
+class SampleConsensusPrerejective {
+ public:
+  explicit SampleConsensusPrerejective(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {
+    const float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    std::memcpy(T_, eye, sizeof T_);
+  }
+  template <class CloudPtr>
+  void setInputSource(const CloudPtr& cloud) { source_ = &*cloud; }
+  template <class CloudPtr>
+  void setInputTarget(const CloudPtr& cloud) { target_ = &*cloud; }
+  template <class FeaturesPtr>
+  void setSourceFeatures(const FeaturesPtr& features) { source_features_ = &*features; }
+  template <class FeaturesPtr>
+  void setTargetFeatures(const FeaturesPtr& features) { target_features_ = &*features; }
+  void setNumberOfSamples(int nr_samples) { nr_samples_ = nr_samples; }
+  int getNumberOfSamples() const { return nr_samples_; }
+  void setCorrespondenceRandomness(int k) { k_correspondences_ = k; }
+  int getCorrespondenceRandomness() const { return k_correspondences_; }
+  void setSimilarityThreshold(float similarity_threshold) { similarity_ = similarity_threshold; }
+  float getSimilarityThreshold() const { return similarity_; }
+  void setMaxCorrespondenceDistance(double distance) { distance_ = distance; }
+  double getMaxCorrespondenceDistance() const { return distance_; }
+  void setInlierFraction(float inlier_fraction) { inlier_fraction_ = inlier_fraction; }
+  float getInlierFraction() const { return inlier_fraction_; }
+  void setMaximumIterations(int max_iterations) { max_iterations_ = max_iterations; }
+  int getMaximumIterations() const { return max_iterations_; }
+  void setSeed(uint64_t seed) { seed_ = seed; }  // NOT a PCL method
+  void align(CloudT& output) {
+    const float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    std::memcpy(T_, eye, sizeof T_);
+    converged_ = false;
+    fitness_ = FLT_MAX;
+    inliers_.clear();
+    output.points.resize(0);
+    detail::set_cloud_shape(output, 0, 0);
+    if (!source_ || !target_ || !source_features_ || !target_features_) return;
+    static_assert(sizeof(source_->points[0]) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+    static_assert(sizeof(source_features_->points[0]) == ICPGPU_FPFH_BINS * sizeof(float), "icpgpu: float histogram[33] and nothing else (pcl::FPFHSignature33)");
+    static_assert(sizeof(int) == sizeof(int32_t), "icpgpu: 32-bit int");
+    const std::size_t ns = source_->points.size(), n = target_->points.size();
+    if (source_features_->points.size() != ns || target_features_->points.size() != n) return;  // (PCL refuses features that do not match as well)
+    if (icpgpu_search_set_input(ctx_, n ? reinterpret_cast<const float*>(&target_->points[0]) : nullptr, n) != ICPGPU_OK) return;
+    output.points.resize(ns);
+    std::size_t n_inliers = 0;
+    int32_t converged = 0;
+    if (icpgpu_scp_align(ctx_, ns ? reinterpret_cast<const float*>(&source_->points[0]) : nullptr, ns, ns ? source_features_->points[0].histogram : nullptr,
+                         n ? target_features_->points[0].histogram : nullptr, nr_samples_, k_correspondences_, (double)similarity_, distance_,
+                         (double)inlier_fraction_, max_iterations_, seed_, T_, &n_inliers, &fitness_, &converged,
+                         ns ? reinterpret_cast<float*>(&output.points[0]) : nullptr) != ICPGPU_OK) {
+      output.points.resize(0);
+      return;
+    }
+    detail::set_cloud_shape(output, ns, 0);
+    std::vector<int> inliers(n_inliers);
+    if (n_inliers && icpgpu_scp_fetch(ctx_, 0, n_inliers, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                      reinterpret_cast<int32_t*>(&inliers[0])) != ICPGPU_OK)
+      return;
+    inliers_.swap(inliers);
+    converged_ = converged != 0;
+  }
+  bool hasConverged() const { return converged_; }
+  Matrix4 getFinalTransformation() const { return make_matrix4(T_); }
+  const std::vector<int>& getInliers() const { return inliers_; }
+  double getFitnessScore() const { return (double)fitness_; }  // the inliers' mean squared distance (FLT_MAX without a pose)
+
+ private:
+  detail::ContextPtr ctx_holder_;
+  icpgpu_ctx* ctx_;
+  const CloudT *source_ = nullptr, *target_ = nullptr;
+  const FeatureCloudT *source_features_ = nullptr, *target_features_ = nullptr;
+  int nr_samples_ = 3, k_correspondences_ = 2, max_iterations_ = 1000;
+  float similarity_ = 0.9f, inlier_fraction_ = 0.0f, fitness_ = FLT_MAX;
+  double distance_ = 1.0;
+  uint64_t seed_ = 0;
+  bool converged_ = false;
+  float T_[16];
+  std::vector<int> inliers_;
+};
+
 // The mapper's map (/root/reference/src/icpslam/octree_mapper.cpp:55-90): replaces the pair
 //   pcl::octree::OctreePointCloudSearch<pcl::PointXYZ>::Ptr map_octree_;  pcl::PointCloud<pcl::PointXYZ>::Ptr map_cloud_;
 // Poses are the float 4x4 that pcl_ros::transformPointCloud applies (icpgpu_pose_to_matrix gives it for a Pose6DOF);
