@@ -461,6 +461,16 @@ struct icpgpu_ctx {
     DeviceBuf c_status, c_sidx, c_tidx, c_sums, xforms, partials, results;  // a chunk's
     DeviceBuf flags, pos, scan, inliers, ints, aligned;              // the best hypothesis'
   } scp;
+  // ISS keypoints (icpgpu_iss.cpp, icp_iss.hip): the last call's result over the search cloud and its scratch, in buffers no other
+  // call writes -- an unfetched result outlives later search, normal, FPFH, clustering, segmentation and sample-consensus calls;
+  // icpgpu_search_set_input drops it
+  struct Iss {
+    bool have = false;
+    size_t n = 0, n_keypoints = 0;
+    int waits = 0;
+    DeviceBuf n_salient, scatter, eig, saliency;  // per point
+    DeviceBuf flags, pos, scan, kept, points, ints;  // the compaction's; kept / points: the keypoints
+  } iss;
   std::vector<icpgpu_ctx*> workers;  // align_batch: one sub-context (own stream + scratch) per host worker thread
   DeviceBuf batch_table;             // lock-step batch: the BatchPair table of the group this context leads
   std::atomic<size_t> batch_table_cells{0};   // align_batch: the largest cell table any worker has needed (icpgpu_index.cpp)

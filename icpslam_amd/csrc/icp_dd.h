@@ -1,5 +1,5 @@
 // icp_dd.h -- double-double accumulation for the sums whose rule is "the EXACT sum rounded once" (the statistical outlier filter's sum
-// and sq_sum, icp_outlier.hip; the plane refinement's nine sums, icp_sac.hip): the high parts by TwoSum, the low parts in plain
+// and sq_sum, icp_outlier.hip; the plane refinement's nine sums, icp_sac.hip; the ISS scatter's six, icp_iss.hip): the high parts by TwoSum, the low parts in plain
 // float64, as icp_gicp.hip has it.
 #pragma once
 

@@ -1,6 +1,6 @@
 // icp_jacobi3.h -- the cyclic Jacobi eigen-decomposition of a symmetric 3x3 in float64: ONE definition for the NDT cells
-// (icp_ndt.hip: ndt_cell_kernel), the surface normals (icp_normals.hip: normals_from_rows_kernel) and, on the host, the plane
-// refinement (icpgpu_sac.cpp).  Its expressions are part of
+// (icp_ndt.hip: ndt_cell_kernel), the surface normals (icp_normals.hip: normals_from_rows_kernel), the ISS scatter matrices
+// (icp_iss.hip: iss_scatter_kernel) and, on the host, the plane refinement (icpgpu_sac.cpp).  Its expressions are part of
 // those rules: tests/ndt_restated.py (_jacobi3) and tests/normals_restated.py (jacobi3) run the same sweeps with the same expressions.
 #pragma once
 

@@ -574,6 +574,16 @@ hipError_t launch_cluster_extract(const float4* cloud, int n, bool any_finite, c
                                   int* rank_of, int* csize, int* cstart, long long* cstart64, int* keys, int* vals, int* scratch, int* counts,
                                   hipStream_t stream);
 
+// ---- ISS keypoints (icp_iss.hip): pcl::ISSKeypoint3D without border estimation, over the search cloud --------------------------------
+// Per point of `cloud` (sorted, cell_start, g, shells_*: as launch_search_radius_count, one `shells` per radius; any_finite: the cloud
+// has a finite point): n_salient (n), scatter6 (n x 6), eig3 (n x 3, descending) and saliency (n) from the salient ball, then the
+// 0 / 1 keypoint flags from the non-max ball, the keypoints' indices ascending into kept, their points into points (n of room each)
+// and their number into *n_kept.  flags, pos: n ints; scan_scratch: exclusive_scan_scratch_ints(n) ints.  n = 0 writes *n_kept alone.
+hipError_t launch_iss_keypoints(const float4* cloud, int n, bool any_finite, const float4* sorted, const int* cell_start, const GridDesc& g,
+                                int shells_salient, float r2_salient, int shells_non_max, float r2_non_max, int min_neighbors, double gamma_21,
+                                double gamma_32, int32_t* n_salient, double* scatter6, double* eig3, double* saliency, int* flags, int* pos,
+                                int* scan_scratch, float4* points, int* kept, int* n_kept, hipStream_t stream);
+
 // ---- plane segmentation (icp_sac.hip): pcl::SACSegmentation's RANSAC over the search cloud ---------------------------------------
 // A batch of kSacBatch hypotheses t0 .. t0 + 63 (hypothesis t0 + h is lane h's): the model kernel fills plane / sample and sets
 // count to 0, or to -1 for an INVALID hypothesis (and for t >= max_iterations), the counting kernel adds the inliers.  thr: the

@@ -1,5 +1,5 @@
 // icp_search_device.h -- device helpers of the neighbour search that more than one unit walks a ball with (internal): the keys and
-// the walk of icp_search.hip's radius search, shared with icp_cluster.hip, and the keyed selection of its k-nearest search, shared
+// the walk of icp_search.hip's radius search, shared with icp_cluster.hip and icp_iss.hip, and the keyed selection of its k-nearest search, shared
 // with icp_feature.hip.  Moved here unchanged from icp_search.hip.
 #pragma once
 

@@ -684,6 +684,9 @@ int icpgpu_destroy(icpgpu_ctx* c) {
                        &c->scp.c_sidx, &c->scp.c_tidx, &c->scp.c_sums, &c->scp.xforms, &c->scp.partials, &c->scp.results, &c->scp.flags, &c->scp.pos,
                        &c->scp.scan, &c->scp.inliers, &c->scp.ints, &c->scp.aligned})
     release(*b);
+  for (DeviceBuf* b : {&c->iss.n_salient, &c->iss.scatter, &c->iss.eig, &c->iss.saliency, &c->iss.flags, &c->iss.pos, &c->iss.scan, &c->iss.kept,
+                       &c->iss.points, &c->iss.ints})
+    release(*b);
   for (DeviceBuf* b : {&c->feature.target, &c->feature.query, &c->feature.finite, &c->feature.idx, &c->feature.d2, &c->feature.n_found})
     release(*b);
   for (GridIndex* G : {&c->grid, &c->src_grid, &c->map.grid, &c->outlier.grid, &c->search.grid}) {

@@ -151,6 +151,7 @@ int icpgpu_search_set_input(icpgpu_ctx* c, const float* xyzw, size_t n) {
   c->cluster.have = false;               // (a clustering result is a result over the cloud that goes)
   c->sac.have = false;                   // (and so is a plane segmentation)
   c->scp.have = false;                   // (and a sample-consensus alignment)
+  c->iss.have = false;                   // (and the ISS keypoints)
   if (n && !xyzw) return fail(c, ICPGPU_ERR_INVALID_ARG, "null cloud pointer with n = %zu", n);
   if (n > (size_t)INT32_MAX - 4096) return fail(c, ICPGPU_ERR_INVALID_ARG, "cloud too large: %zu points", n);
   if (n) {

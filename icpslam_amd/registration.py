@@ -720,6 +720,49 @@ class Context:
         self._check(rc)
         return start, indices, labels, component
 
+    # ISS keypoints (pcl::ISSKeypoint3D without border estimation; rules: include/icpgpu.h) ----------------------------------------
+    def iss_keypoints_raw(self, salient_radius: float, non_max_radius: float, gamma_21: float = 0.975, gamma_32: float = 0.975,
+                          min_neighbors: int = 5) -> tuple:
+        """One icpgpu_iss_keypoints call: (rc, n_keypoints); the result stays in the context."""
+        nk = C.c_size_t()
+        rc = self._L.icpgpu_iss_keypoints(self._h, float(salient_radius), float(non_max_radius), float(gamma_21), float(gamma_32),
+                                          int(min_neighbors), C.byref(nk))
+        return rc, int(nk.value)
+
+    def iss_fetch_raw(self, capacity_keypoints: int, want=("keypoint_index", "keypoints", "n_salient", "scatter6", "eigenvalues3", "saliency")) -> tuple:
+        """One icpgpu_iss_fetch call into arrays pre-filled with -2: (rc, dict of the outputs named in `want`; the others get NULL)."""
+        n_c = C.c_size_t()
+        self._L.icpgpu_search_size(self._h, C.byref(n_c), None)  # (0 without a search cloud)
+        n, cap = int(n_c.value), int(capacity_keypoints)
+        shapes = {"keypoint_index": ((cap,), np.int32), "keypoints": ((cap, 4), np.float32), "n_salient": ((n,), np.int32),
+                  "scatter6": ((n, 6), np.float64), "eigenvalues3": ((n, 3), np.float64), "saliency": ((n,), np.float64)}
+        out = {name: np.full(shape, -2, dtype) for name, (shape, dtype) in shapes.items() if name in want}
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+
+        def ptr(name, kind):
+            return out[name].ctypes.data_as(kind) if name in out else None
+
+        rc = self._L.icpgpu_iss_fetch(self._h, cap, ptr("keypoint_index", ip), ptr("keypoints", C.POINTER(C.c_float)), ptr("n_salient", ip),
+                                      ptr("scatter6", dp), ptr("eigenvalues3", dp), ptr("saliency", dp))
+        return rc, out
+
+    def iss_stats(self) -> int:
+        """The host waits of the last iss_keypoints call."""
+        waits = C.c_int32(-1)
+        self._check(self._L.icpgpu_iss_stats(self._h, C.byref(waits)))
+        return int(waits.value)
+
+    def iss_keypoints(self, salient_radius: float, non_max_radius: float, gamma_21: float = 0.975, gamma_32: float = 0.975,
+                      min_neighbors: int = 5) -> dict:
+        """The search cloud's ISS keypoints: dict(n_keypoints, keypoint_index (m,) int32 ascending, keypoints (m, 4) float32,
+        n_salient (n,) int32, scatter6 (n, 6), eigenvalues3 (n, 3) descending, saliency (n,) float64)."""
+        rc, m = self.iss_keypoints_raw(salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors)
+        self._check(rc)
+        rc, out = self.iss_fetch_raw(m)
+        self._check(rc)
+        out["n_keypoints"] = m
+        return out
+
     # plane segmentation (pcl::SACSegmentation, pcl::ExtractIndices; rules: include/icpgpu.h) ----------------------------------
     def sac_segment_raw(self, distance_threshold: float, max_iterations: int = 50, probability: float = 0.99, seed: int = 0,
                         optimize_coefficients: bool = True, axis=None, eps_angle: float = 0.0) -> tuple:
@@ -1362,6 +1405,78 @@ class EuclideanClusterExtraction:
         self._ctx.search_set_input(self._input)
         start, indices, self._labels, _ = self._ctx.euclidean_cluster_extraction(self._tolerance, self._min, self._max)
         return [indices[start[r]:start[r + 1]].copy() for r in range(start.size - 1)]
+
+
+class ISSKeypoint3D:
+    """pcl::ISSKeypoint3D<PointXYZ, PointXYZ>-shaped front end (include/icpgpu.h, "ISS keypoints"): setInputCloud, setSalientRadius,
+    setNonMaxRadius, setThreshold21, setThreshold32, setMinNeighbors, compute() -> the keypoint cloud, getKeypointsIndices().  The
+    defaults are PCL's constructor's (radii 0, gammas 0.975, 5 neighbours), so compute() refuses until both radii are set.  Border
+    estimation is not provided: setBorderRadius with a radius above 0 raises; setNormalRadius and setNumberOfThreads are stored and
+    have no effect.  setIndices and setSearchSurface are not provided."""
+
+    def __init__(self, device_id: int = 0):
+        self._ctx = Context(device_id)
+        self._input = None
+        self._salient = 0.0
+        self._non_max = 0.0
+        self._gamma_21 = 0.975
+        self._gamma_32 = 0.975
+        self._min_neighbors = 5
+        self._border = 0.0
+        self._normal_radius = 0.0
+        self._threads = 0
+        self._indices = np.empty(0, np.int32)
+        self._last = None
+
+    def setInputCloud(self, cloud):
+        self._input = _as_cloud(cloud).copy()
+
+    def setSearchMethod(self, tree=None):
+        """Accepted and ignored: the search is the library's own (exact)."""
+
+    def setSalientRadius(self, salient_radius: float):
+        self._salient = float(salient_radius)
+
+    def setNonMaxRadius(self, non_max_radius: float):
+        self._non_max = float(non_max_radius)
+
+    def setThreshold21(self, gamma_21: float):
+        self._gamma_21 = float(gamma_21)
+
+    def setThreshold32(self, gamma_32: float):
+        self._gamma_32 = float(gamma_32)
+
+    def setMinNeighbors(self, min_neighbors: int):
+        self._min_neighbors = int(min_neighbors)
+
+    def setBorderRadius(self, border_radius: float):
+        if float(border_radius) > 0.0:
+            raise IcpGpuError(_lib.ERR_UNSUPPORTED, "setBorderRadius: border estimation is not provided")
+        self._border = float(border_radius)
+
+    def setNormalRadius(self, normal_radius: float):
+        """Stored; without border estimation it has no effect."""
+        self._normal_radius = float(normal_radius)
+
+    def setNumberOfThreads(self, nr_threads: int = 0):
+        """Stored; the kernels' parallelism is the device's."""
+        self._threads = int(nr_threads)
+
+    def getKeypointsIndices(self) -> np.ndarray:
+        """The last compute()'s keypoints as ascending indices into the input cloud."""
+        return self._indices
+
+    def getLastResult(self):
+        """Everything the last compute() produced (Context.iss_keypoints' dict; not PCL's)."""
+        return self._last
+
+    def compute(self) -> np.ndarray:
+        if self._input is None:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "compute: setInputCloud first")
+        self._ctx.search_set_input(self._input)
+        self._last = self._ctx.iss_keypoints(self._salient, self._non_max, self._gamma_21, self._gamma_32, self._min_neighbors)
+        self._indices = self._last["keypoint_index"]
+        return self._last["keypoints"]
 
 
 class SACSegmentation:

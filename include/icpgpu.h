@@ -57,7 +57,8 @@ extern "C" {
  * icpgpu_radius_outlier_removal, their _view forms, icpgpu_outlier_stats, icpgpu_outlier_fetch, and the neighbour search --
  * icpgpu_search_set_input, icpgpu_search_size, icpgpu_search_knn, icpgpu_search_radius, and normal estimation --
  * icpgpu_normal_estimation, and euclidean clustering -- icpgpu_euclidean_cluster_extraction, icpgpu_cluster_fetch, and plane segmentation --
- * icpgpu_sac_plane_segmentation, icpgpu_sac_fetch, icpgpu_sac_stats, icpgpu_sac_extract, icpgpu_sac_extract_view, and fast point feature histograms -- icpgpu_fpfh_estimation, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
+ * icpgpu_sac_plane_segmentation, icpgpu_sac_fetch, icpgpu_sac_stats, icpgpu_sac_extract, icpgpu_sac_extract_view, and ISS keypoints --
+ * icpgpu_iss_keypoints, icpgpu_iss_fetch, icpgpu_iss_stats, and fast point feature histograms -- icpgpu_fpfh_estimation, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
  * icpgpu_set_p2plane_symmetric, icpgpu_get_p2plane_symmetric, icpgpu_reduce_symmetric_point_to_plane,
  * icpgpu_solve_symmetric_point_to_plane, ICPGPU_REJECT_SURFACE_NORMAL (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
@@ -1042,6 +1043,56 @@ int icpgpu_scp_fetch(icpgpu_ctx* ctx, size_t capacity_hypotheses, size_t capacit
                      int32_t* target_idx /* it x nr */, float* transforms /* it x 16 */, int32_t* counts, double* sums, float* errors,
                      int32_t* best_t, int32_t* inliers /* n_inliers */);
 int icpgpu_scp_stats(const icpgpu_ctx* ctx, int32_t* host_waits, int32_t* evaluated, double* host_solve_ms);
+
+/* ---- ISS keypoints (added under 1.2) -------------------------------------------------------------------------------- */
+/* replaces pcl::ISSKeypoint3D<PointXYZ, PointXYZ> (PCL 1.8, keypoints/impl/iss_3d.hpp) without border estimation: setInputCloud,
+ * setSalientRadius, setNonMaxRadius, setThreshold21, setThreshold32, setMinNeighbors, compute -- "at which points of this cloud are
+ * descriptors worth computing", the stage in front of icpgpu_fpfh_estimation at keypoints.  The call works on the context's SEARCH
+ * CLOUD (icpgpu_search_set_input), as clustering and plane segmentation do.  Parity with PCL binaries is unpinned;
+ * tests/iss_restated.py is what the kernels are compared with, bit for bit.
+ * BALLS.  For both radii r2 = (float)(radius * radius), the product in double.  A finite cloud point j is in the ball of point i iff
+ * d2(i, j) < r2, strict, with the search section's float32 d2.  The point itself and points coincident with it are in its ball.
+ * Non-finite points are in no ball and have an empty one.  As sets these are exactly the rows of icpgpu_search_radius(radius,
+ * max_nn = 0) with the cloud's own points as queries; no row is ever materialised, and memory is O(n) whatever the radii.
+ * SCATTER (PCL's getScatterMatrix).  For each j in the salient ball of i, (dx, dy, dz) = P_j - P_i in float32.  The six products
+ * dx dx, dx dy, dx dz, dy dy, dy dz, dz dz are taken in double, where each is exact, and each of the six sums is the EXACT sum rounded
+ * once (the rule of the plane refinement's nine sums and the statistical outlier filter's sum and sq_sum): scatter6, in that order.
+ * DEVIATION: PCL takes the differences in double and adds rounded products in the neighbours' order; this rule does not depend on
+ * any order.  The sums are not divided by the count, as in PCL.  n_salient[i] is the size of the salient ball.  When
+ * n_salient[i] < min_neighbors the scatter is reported as six zeros and the point has no saliency.
+ * EIGENVALUES.  The cyclic Jacobi of normal estimation on the symmetric matrix of the six sums: 8 sweeps, the same expressions.
+ * DEVIATION: PCL uses Eigen's SelfAdjointEigenSolver.  eigenvalues3[i] = the diagonal (d0, d1, d2) sorted descending by the network
+ * "swap (d0, d1) if d0 < d1; swap (d1, d2) if d1 < d2; swap (d0, d1) if d0 < d1": (e1, e2, e3).  saliency[i] = e3 iff all three
+ * eigenvalues are finite, e3 >= 0, n_salient[i] >= min_neighbors, e2 / e1 < gamma_21 and e3 / e2 < gamma_32 -- double divisions,
+ * strict comparisons, a NaN quotient fails -- and 0 otherwise.  A skipped point (non-finite, or with too few neighbours) reports the
+ * eigenvalues 0, 0, 0.
+ * NON-MAXIMA SUPPRESSION.  Point i is a keypoint iff saliency[i] > 0, its non-max ball holds at least min_neighbors points, and no j
+ * in that ball has saliency[j] > saliency[i].  The comparison is strict, so equal maxima within one ball are all keypoints, as in
+ * PCL.  Neither the non-max ball's size nor the maximum is an output.
+ * OUTPUT.  The keypoint indices are ascending; keypoints_xyzw holds those rows of the search cloud, bit for bit.
+ * icpgpu_iss_keypoints computes and KEEPS the result in buffers of its own in the context and returns the number of keypoints after
+ * one host wait; icpgpu_iss_fetch copies out any subset of it, any number of times: every pointer may be NULL.  n_salient and saliency
+ * hold n entries, scatter6 n x 6, eigenvalues3 n x 3.  With keypoint_index or keypoints_xyzw requested and capacity_keypoints <
+ * n_keypoints nothing is written and the fetch returns ICPGPU_ERR_INVALID_ARG.  icpgpu_iss_stats reports the host waits of the last
+ * compute call: one, for the count.
+ * ICPGPU_ERR_INVALID_ARG: no search cloud; a radius that is not finite or is <= 0; a gamma that is not finite; min_neighbors < 0; a
+ * null n_keypoints; a fetch or stats without a result (none computed, the last call refused, or the search cloud replaced since).  An
+ * empty cloud and a cloud with no finite point are ICPGPU_OK with no keypoints.
+ * LIMITS.  A cloud the grid refuses is walked without it (up to the 65536 points icpgpu_search_set_input admits then), and a radius
+ * whose ball spans more than 8 grid cells is handled as in icpgpu_search_radius: the whole cloud is swept per point, which is slow.
+ * All three paths give the same bits.
+ * Not provided: border estimation (setBorderRadius / setNormalRadius / setNormals), setIndices, and a search surface other than the
+ * input (PCL indexes input_ with surface_'s indices and is only meaningful when the two are one cloud).
+ * ISOLATION.  The result depends on the search cloud and the arguments alone.  The call leaves the source, the
+ * target, every grid, the covariances, the cached normals, the NDT cells, the filters' results and the search cloud as they were.
+ * Unfetched clustering, segmentation and sample-consensus results survive it, and its own result survives searches, normal and FPFH
+ * estimations, clusterings and segmentations.  icpgpu_search_set_input drops it, whatever it returns. */
+int icpgpu_iss_keypoints(icpgpu_ctx* ctx, double salient_radius, double non_max_radius, double gamma_21, double gamma_32,
+                         int min_neighbors, size_t* n_keypoints);
+int icpgpu_iss_fetch(icpgpu_ctx* ctx, size_t capacity_keypoints, int32_t* keypoint_index /* n_keypoints */,
+                     float* keypoints_xyzw /* n_keypoints float4 */, int32_t* n_salient /* n */, double* scatter6 /* n x 6 */,
+                     double* eigenvalues3 /* n x 3 */, double* saliency /* n */);
+int icpgpu_iss_stats(const icpgpu_ctx* ctx, int32_t* host_waits);
 
 /* ---- the mapper's target: a one-point-per-voxel map and its "nn cloud"  -------- */
 /* replaces OctreeMapper's pcl::octree::OctreePointCloudSearch map

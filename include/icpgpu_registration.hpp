@@ -1008,6 +1008,69 @@ class EuclideanClusterExtraction {
   std::vector<int> labels_;
 };
 
+// pcl::ISSKeypoint3D<PointT, PointT>-shaped front end (rules and deviations: include/icpgpu.h, "ISS keypoints") -- the keypoints at
+// which FPFHEstimation computes its descriptors (fpfh.setInputCloud(keypoints); fpfh.setSearchSurface(cloud)):
+//   pcl::ISSKeypoint3D<pcl::PointXYZ, pcl::PointXYZ> iss;  ->  icpgpu::ISSKeypoint3D<pcl::PointCloud<pcl::PointXYZ>> iss;
+//   iss.setSalientRadius(1.2); iss.setNonMaxRadius(0.8); iss.setThreshold21(0.975); iss.setThreshold32(0.975); iss.setMinNeighbors(5);
+//   iss.setInputCloud(cloud); iss.compute(keypoints); iss.getKeypointsIndices();
+// The defaults are PCL's constructor's (radii 0, gammas 0.975, 5 neighbours): compute() leaves the output empty until both radii are
+// set, and after any refused call.  The keypoints come out in the input's order.  Border estimation is not provided: setBorderRadius
+// with a radius above 0 throws; setNormalRadius and setNumberOfThreads are stored and have no effect.  setIndices, setNormals and a
+// search surface other than the input are not provided.
+template <class CloudT>
+class ISSKeypoint3D {
+ public:
+  explicit ISSKeypoint3D(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx), indices_(new PointIndices) {}
+  template <class CloudPtr>
+  void setInputCloud(const CloudPtr& cloud) { input_ = &*cloud; }
+  template <class TreePtr>
+  void setSearchMethod(const TreePtr&) {}  // accepted and ignored: the search is the library's own (exact)
+  void setSalientRadius(double salient_radius) { salient_ = salient_radius; }
+  void setNonMaxRadius(double non_max_radius) { non_max_ = non_max_radius; }
+  void setThreshold21(double gamma_21) { gamma_21_ = gamma_21; }
+  void setThreshold32(double gamma_32) { gamma_32_ = gamma_32; }
+  void setMinNeighbors(int min_neighbors) { min_neighbors_ = min_neighbors; }
+  void setBorderRadius(double border_radius) {
+    if (border_radius > 0.0) throw std::invalid_argument("icpgpu::ISSKeypoint3D: border estimation is not provided");
+    border_ = border_radius;
+  }
+  void setNormalRadius(double normal_radius) { normal_radius_ = normal_radius; }  // stored: without border estimation it has no effect
+  void setNumberOfThreads(unsigned int nr_threads = 0) { threads_ = nr_threads; }  // stored: the kernels' parallelism is the device's
+  void compute(CloudT& output) {
+    output.points.resize(0);
+    detail::set_cloud_shape(output, 0, 0);
+    indices_.reset(new PointIndices);
+    if (!input_) return;
+    typedef typename std::remove_reference<decltype(input_->points[0])>::type PointT;
+    static_assert(sizeof(PointT) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+    static_assert(sizeof(int) == sizeof(int32_t), "icpgpu: 32-bit int");
+    const std::size_t n = input_->points.size();
+    if (icpgpu_search_set_input(ctx_, n ? reinterpret_cast<const float*>(&input_->points[0]) : nullptr, n) != ICPGPU_OK) return;
+    std::size_t m = 0;
+    if (icpgpu_iss_keypoints(ctx_, salient_, non_max_, gamma_21_, gamma_32_, min_neighbors_, &m) != ICPGPU_OK || m == 0) return;
+    indices_->indices.resize(m);
+    output.points.resize(m);
+    if (icpgpu_iss_fetch(ctx_, m, reinterpret_cast<int32_t*>(&indices_->indices[0]), reinterpret_cast<float*>(&output.points[0]), nullptr, nullptr,
+                         nullptr, nullptr) != ICPGPU_OK) {
+      indices_->indices.clear();
+      output.points.resize(0);
+      return;
+    }
+    detail::set_cloud_shape(output, m, 0);
+  }
+  // the last compute()'s keypoints as ascending indices into the input cloud
+  PointIndices::ConstPtr getKeypointsIndices() const { return indices_; }
+
+ private:
+  detail::ContextPtr ctx_holder_;
+  icpgpu_ctx* ctx_;
+  const CloudT* input_ = nullptr;
+  double salient_ = 0.0, non_max_ = 0.0, gamma_21_ = 0.975, gamma_32_ = 0.975, border_ = 0.0, normal_radius_ = 0.0;
+  int min_neighbors_ = 5;
+  unsigned int threads_ = 0;
+  PointIndices::Ptr indices_;
+};
+
 // pcl::ModelCoefficients, pcl::SACSegmentation<PointT> and pcl::ExtractIndices<PointT>-shaped front ends (rules and deviations:
 // include/icpgpu.h, "plane segmentation") -- the ground removal in front of EuclideanClusterExtraction:
 //   pcl::SACSegmentation<pcl::PointXYZ> seg;  ->  icpgpu::SACSegmentation<pcl::PointCloud<pcl::PointXYZ>> seg;
