@@ -417,6 +417,7 @@ struct icpgpu_ctx {
     DeviceBuf queries, idx, d2, n_found, far, counts, longs, row_start, scratch_start, scan, scratch, totals, row_start64;
     DeviceBuf normals, moments;  // icpgpu_normal_estimation: the results on their way to the staging buffer
     DeviceBuf fpfh_normals, spfh, fpfh;  // icpgpu_fpfh_estimation: the caller's normals and the two histograms
+    DeviceBuf bnd_normals, bnd_flags, bnd_dirs, bnd_witness;  // icpgpu_boundary_estimation: the caller's normals and the results
   } search;
   // euclidean clustering (icpgpu_search.cpp, icp_cluster.hip): the last call's result over the search cloud and its scratch, in
   // buffers no other call writes -- an unfetched result outlives later search and normal calls; icpgpu_search_set_input drops it
@@ -468,7 +469,9 @@ struct icpgpu_ctx {
     bool have = false;
     size_t n = 0, n_keypoints = 0;
     int waits = 0;
+    bool with_border = false;                     // the last call estimated borders: edge and border hold its flags
     DeviceBuf n_salient, scatter, eig, saliency;  // per point
+    DeviceBuf normals, edge, border;              // border estimation's, per point
     DeviceBuf flags, pos, scan, kept, points, ints;  // the compaction's; kept / points: the keypoints
   } iss;
   std::vector<icpgpu_ctx*> workers;  // align_batch: one sub-context (own stream + scratch) per host worker thread
@@ -717,6 +720,19 @@ struct Delivery {
   size_t bytes;
 };
 int deliver(icpgpu_ctx* c, const Delivery* parts, int n_parts);
+// ... what a query call needs of the search cloud
+struct SearchView {
+  const float4* cloud = nullptr;
+  int n = 0;
+  const float4* sorted = nullptr;  // null: no grid
+  const int* cell_start = nullptr;
+  GridDesc g{};
+};
+SearchView view_of(const icpgpu_ctx* c);
+// ... the queries of a call in device memory: the caller's (uploaded into the search state's scratch) or the search cloud's own points
+int stage_queries(icpgpu_ctx* c, const char* what, const float* queries_xyzw, size_t n_q, const float4*& d_queries);
+// ... a radius search (max_nn = 0) whose rows stay on the device: search.idx / d2 by search.row_start, lengths in search.counts; ONE wait
+int radius_rows_on_device(icpgpu_ctx* c, const char* what, const float4* d_points, size_t n_points, double radius);
 // icpgpu_ndt.cpp
 int align_ndt(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitness, icpgpu_result* res);
 

@@ -1,6 +1,7 @@
-// icp_iss.hip -- intrinsic shape signature keypoints over the search cloud (pcl::ISSKeypoint3D without border estimation; rules:
-// include/icpgpu.h "ISS keypoints").  Two walks of a ball per point, a wave each, and no neighbour rows anywhere: memory is O(n)
-// whatever the radii.
+// icp_iss.hip -- intrinsic shape signature keypoints over the search cloud (pcl::ISSKeypoint3D; rules: include/icpgpu.h "ISS
+// keypoints").  Two walks of a ball per point, a wave each, and no neighbour rows in this unit: without border estimation memory is
+// O(n) whatever the radii.  With it, the edge flags come from icp_boundary.hip over the border radius's rows (icpgpu_iss.cpp), and
+// iss_border_kernel here spreads them over the border ball by a third walk.
 //   * iss_scatter_kernel walks the salient ball over icp_search_device.h's ball_batches -- the cube of `shells` cells, or the whole
 //     cloud, exactly as search_radius_count_kernel chooses.  A lane takes one candidate per batch and adds the six exact products of
 //     an in-ball candidate into double-double accumulators of its own (icp_dd.h); the 64 lanes' accumulators are folded by dd_add in
@@ -33,12 +34,14 @@ __device__ __forceinline__ double shfl_xor_double(double v, int j) {  // a doubl
 // is written).
 __global__ __launch_bounds__(ISS_BLOCK) void iss_scatter_kernel(const float4* __restrict__ cloud, int n, const float4* __restrict__ sorted,
                                                                 const int* __restrict__ cell_start, GridDesc g, int R, float r2, int min_neighbors,
-                                                                int32_t* __restrict__ n_salient, double* __restrict__ scatter6) {
+                                                                const int32_t* __restrict__ border, int32_t* __restrict__ n_salient,
+                                                                double* __restrict__ scatter6) {
   const unsigned int lane = threadIdx.x & 63u;
   const int i = blockIdx.x * ISS_WAVES + (int)(threadIdx.x >> 6);
   if (i >= n) return;  // (wave-uniform)
   const float4 p = cloud[i];
   if (!finite3(p.x, p.y, p.z)) return;
+  const bool skip = border && border[i] != 0;  // (wave-uniform) a border point: its ball is counted, nothing else
   DD acc[6];
 #pragma unroll
   for (int e = 0; e < 6; ++e) acc[e].hi = acc[e].lo = 0.0;
@@ -46,7 +49,7 @@ __global__ __launch_bounds__(ISS_BLOCK) void iss_scatter_kernel(const float4* __
   ball_batches(cloud, n, sorted, cell_start, g, R, p, lane, [&](u64 key) {
     const bool in = key_in_ball(key, r2);
     c += __popcll(__ballot(in));
-    if (in) {
+    if (in && !skip) {
       const float4 q = cloud[min((unsigned int)key, (unsigned int)(n - 1))];  // (the key names a cloud point)
       const double dx = (double)(q.x - p.x), dy = (double)(q.y - p.y), dz = (double)(q.z - p.z);
       dd_add_term(acc[0], dx * dx);  // (24 x 24 bits: exact)
@@ -58,7 +61,7 @@ __global__ __launch_bounds__(ISS_BLOCK) void iss_scatter_kernel(const float4* __
     }
   });
   if (lane == 0) n_salient[i] = c;
-  if (c < min_neighbors) return;  // (wave-uniform)
+  if (c < min_neighbors || skip) return;  // (wave-uniform)
   double s[6];
 #pragma unroll
   for (int e = 0; e < 6; ++e) {
@@ -81,13 +84,13 @@ __global__ __launch_bounds__(ISS_BLOCK) void iss_scatter_kernel(const float4* __
 // point and a point with too few neighbours keep.  (In the scatter kernel this would be one lane's work under a wave's exec mask: at
 // 19k points it was three quarters of that kernel's time.)
 __global__ __launch_bounds__(ISS_BLOCK) void iss_eigen_kernel(const float4* __restrict__ cloud, int n, int min_neighbors, double gamma_21,
-                                                              double gamma_32, const int32_t* __restrict__ n_salient,
-                                                              const double* __restrict__ scatter6, double* __restrict__ eig3,
+                                                              double gamma_32, const int32_t* __restrict__ border,
+                                                              const int32_t* __restrict__ n_salient, const double* __restrict__ scatter6, double* __restrict__ eig3,
                                                               double* __restrict__ saliency) {
   const int i = blockIdx.x * ISS_BLOCK + (int)threadIdx.x;
   if (i >= n) return;
   const float4 p = cloud[i];
-  if (!finite3(p.x, p.y, p.z) || n_salient[i] < min_neighbors) return;
+  if (!finite3(p.x, p.y, p.z) || n_salient[i] < min_neighbors || (border && border[i] != 0)) return;
   double s[6];
 #pragma unroll
   for (int e = 0; e < 6; ++e) s[e] = scatter6[(size_t)i * 6 + e];
@@ -185,12 +188,40 @@ __global__ __launch_bounds__(ISS_BLOCK) void iss_suppress_kernel(const float4* _
   if (lane == 0) flags[i] = keep;
 }
 
+// border[i] = 1 iff point i is finite and some point of its border ball, itself included, is an edge point.  The walk leaves at the
+// first one.
+__global__ __launch_bounds__(ISS_BLOCK) void iss_border_kernel(const float4* __restrict__ cloud, int n, const float4* __restrict__ sorted,
+                                                               const int* __restrict__ cell_start, GridDesc g, int R, float r2,
+                                                               const int32_t* __restrict__ edge, int32_t* __restrict__ border) {
+  const unsigned int lane = threadIdx.x & 63u;
+  const int i = blockIdx.x * ISS_WAVES + (int)(threadIdx.x >> 6);
+  if (i >= n) return;  // (wave-uniform)
+  const float4 p = cloud[i];
+  bool found = false;
+  if (finite3(p.x, p.y, p.z)) {  // (wave-uniform)
+    ball_batches_while(cloud, n, sorted, cell_start, g, R, p, lane, [&](u64 key) {
+      const bool hit = key_in_ball(key, r2) && edge[min((unsigned int)key, (unsigned int)(n - 1))] != 0;
+      found = __ballot(hit) != 0ull;
+      return !found;
+    });
+  }
+  if (lane == 0) border[i] = found ? 1 : 0;
+}
+
 }  // namespace
+
+hipError_t launch_iss_border(const float4* cloud, int n, const float4* sorted, const int* cell_start, const GridDesc& g, int shells, float r2,
+                             const int32_t* edge, int32_t* border, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(iss_border_kernel, dim3((n + ISS_WAVES - 1) / ISS_WAVES), dim3(ISS_BLOCK), 0, stream, cloud, n, sorted, cell_start, g, shells, r2,
+                     edge, border);
+  return hipGetLastError();
+}
 
 hipError_t launch_iss_keypoints(const float4* cloud, int n, bool any_finite, const float4* sorted, const int* cell_start, const GridDesc& g,
                                 int shells_salient, float r2_salient, int shells_non_max, float r2_non_max, int min_neighbors, double gamma_21,
-                                double gamma_32, int32_t* n_salient, double* scatter6, double* eig3, double* saliency, int* flags, int* pos,
-                                int* scan_scratch, float4* points, int* kept, int* n_kept, hipStream_t stream) {
+                                double gamma_32, const int32_t* border, int32_t* n_salient, double* scatter6, double* eig3, double* saliency,
+                                int* flags, int* pos, int* scan_scratch, float4* points, int* kept, int* n_kept, hipStream_t stream) {
   hipError_t e;
   if ((e = hipMemsetAsync(n_kept, 0, sizeof(int), stream)) != hipSuccess) return e;
   if (n <= 0) return hipSuccess;
@@ -200,10 +231,10 @@ hipError_t launch_iss_keypoints(const float4* cloud, int n, bool any_finite, con
   if ((e = hipMemsetAsync(saliency, 0, (size_t)n * sizeof(double), stream)) != hipSuccess) return e;
   const dim3 grid((n + ISS_WAVES - 1) / ISS_WAVES), block(ISS_BLOCK);
   if (any_finite) {
-    hipLaunchKernelGGL(iss_scatter_kernel, grid, block, 0, stream, cloud, n, sorted, cell_start, g, shells_salient, r2_salient, min_neighbors, n_salient,
-                       scatter6);
-    hipLaunchKernelGGL(iss_eigen_kernel, dim3((n + ISS_BLOCK - 1) / ISS_BLOCK), block, 0, stream, cloud, n, min_neighbors, gamma_21, gamma_32, n_salient,
-                       scatter6, eig3, saliency);
+    hipLaunchKernelGGL(iss_scatter_kernel, grid, block, 0, stream, cloud, n, sorted, cell_start, g, shells_salient, r2_salient, min_neighbors, border,
+                       n_salient, scatter6);
+    hipLaunchKernelGGL(iss_eigen_kernel, dim3((n + ISS_BLOCK - 1) / ISS_BLOCK), block, 0, stream, cloud, n, min_neighbors, gamma_21, gamma_32, border,
+                       n_salient, scatter6, eig3, saliency);
   }
   hipLaunchKernelGGL(iss_suppress_kernel, grid, block, 0, stream, cloud, n, sorted, cell_start, g, shells_non_max, r2_non_max, min_neighbors, saliency,
                      flags);

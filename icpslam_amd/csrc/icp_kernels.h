@@ -574,15 +574,19 @@ hipError_t launch_cluster_extract(const float4* cloud, int n, bool any_finite, c
                                   int* rank_of, int* csize, int* cstart, long long* cstart64, int* keys, int* vals, int* scratch, int* counts,
                                   hipStream_t stream);
 
-// ---- ISS keypoints (icp_iss.hip): pcl::ISSKeypoint3D without border estimation, over the search cloud --------------------------------
+// ---- ISS keypoints (icp_iss.hip): pcl::ISSKeypoint3D over the search cloud ------------------------------------------------------------
 // Per point of `cloud` (sorted, cell_start, g, shells_*: as launch_search_radius_count, one `shells` per radius; any_finite: the cloud
 // has a finite point): n_salient (n), scatter6 (n x 6), eig3 (n x 3, descending) and saliency (n) from the salient ball, then the
 // 0 / 1 keypoint flags from the non-max ball, the keypoints' indices ascending into kept, their points into points (n of room each)
 // and their number into *n_kept.  flags, pos: n ints; scan_scratch: exclusive_scan_scratch_ints(n) ints.  n = 0 writes *n_kept alone.
+// border (n ints, or null: no border estimation): a point with border[i] != 0 keeps its n_salient and has zeros otherwise.
 hipError_t launch_iss_keypoints(const float4* cloud, int n, bool any_finite, const float4* sorted, const int* cell_start, const GridDesc& g,
                                 int shells_salient, float r2_salient, int shells_non_max, float r2_non_max, int min_neighbors, double gamma_21,
-                                double gamma_32, int32_t* n_salient, double* scatter6, double* eig3, double* saliency, int* flags, int* pos,
-                                int* scan_scratch, float4* points, int* kept, int* n_kept, hipStream_t stream);
+                                double gamma_32, const int32_t* border, int32_t* n_salient, double* scatter6, double* eig3, double* saliency,
+                                int* flags, int* pos, int* scan_scratch, float4* points, int* kept, int* n_kept, hipStream_t stream);
+// border[i] = 1 iff point i is finite and a point j of its ball (shells, r2: as above; itself included) has edge[j] != 0, else 0
+hipError_t launch_iss_border(const float4* cloud, int n, const float4* sorted, const int* cell_start, const GridDesc& g, int shells, float r2,
+                             const int32_t* edge, int32_t* border, hipStream_t stream);
 
 // ---- plane segmentation (icp_sac.hip): pcl::SACSegmentation's RANSAC over the search cloud ---------------------------------------
 // A batch of kSacBatch hypotheses t0 .. t0 + 63 (hypothesis t0 + h is lane h's): the model kernel fills plane / sample and sets
@@ -613,6 +617,15 @@ hipError_t launch_sac_sums(const float4* cloud, int n, const int* inliers, int m
 // n_q x {xx, xy, xz, yy, yz, zz, cx, cy, cz}.  Rows shorter than 3 give NaN.
 hipError_t launch_normals_from_rows(const float4* queries, int n_q, const float4* cloud, int n, const int32_t* idx, const int32_t* n_found, int k,
                                     const int* row_start, const float viewpoint[3], float4* out, float* moments, hipStream_t stream);
+
+// ---- boundary estimation (icp_boundary.hip): pcl::BoundaryEstimation over neighbour rows still in device memory ---------------
+// Rows as for launch_normals_from_rows.  normals: the QUERIES' normals (float4, the fourth float ignored).  A row of at least
+// max(min_row, 3) entries of a finite query is tested against cos_threshold = cos(angle_threshold); boundary (n_q bytes) and flag32
+// (n_q ints) receive the same 0 / 1, n_directions the row's directions, witness the lowest cloud index among the directions with an
+// empty sector, or -1.  Each of the four may be null.
+hipError_t launch_boundary_from_rows(const float4* queries, int n_q, const float4* normals, const float4* cloud, int n, const int32_t* idx,
+                                     const int32_t* n_found, int k, const int* row_start, int min_row, double cos_threshold, uint8_t* boundary,
+                                     int32_t* flag32, int32_t* n_directions, int32_t* witness, hipStream_t stream);
 
 // ---- fast point feature histograms (icp_fpfh.hip): pcl::FPFHEstimation over neighbour rows still in device memory -------------
 // Rows as for launch_normals_from_rows (dense with n_found, or CSR with row_start).  spfh[p] (n x 33): the simplified histogram of

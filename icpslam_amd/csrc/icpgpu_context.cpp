@@ -672,7 +672,8 @@ int icpgpu_destroy(icpgpu_ctx* c) {
     release(*b);
   for (DeviceBuf* b : {&c->search.cloud.buf, &c->search.queries, &c->search.idx, &c->search.d2, &c->search.n_found, &c->search.far,
                        &c->search.counts, &c->search.longs, &c->search.row_start, &c->search.scratch_start, &c->search.scan,
-                       &c->search.scratch, &c->search.totals, &c->search.row_start64, &c->search.normals, &c->search.moments})
+                       &c->search.scratch, &c->search.totals, &c->search.row_start64, &c->search.normals, &c->search.moments,
+                       &c->search.bnd_normals, &c->search.bnd_flags, &c->search.bnd_dirs, &c->search.bnd_witness})
     release(*b);
   for (DeviceBuf* b : {&c->cluster.parent, &c->cluster.sizes, &c->cluster.component, &c->cluster.labels, &c->cluster.rank_of, &c->cluster.csize,
                        &c->cluster.cstart, &c->cluster.cstart64, &c->cluster.keys, &c->cluster.vals, &c->cluster.scratch, &c->cluster.counts})
@@ -685,7 +686,7 @@ int icpgpu_destroy(icpgpu_ctx* c) {
                        &c->scp.scan, &c->scp.inliers, &c->scp.ints, &c->scp.aligned})
     release(*b);
   for (DeviceBuf* b : {&c->iss.n_salient, &c->iss.scatter, &c->iss.eig, &c->iss.saliency, &c->iss.flags, &c->iss.pos, &c->iss.scan, &c->iss.kept,
-                       &c->iss.points, &c->iss.ints})
+                       &c->iss.points, &c->iss.ints, &c->iss.normals, &c->iss.edge, &c->iss.border})
     release(*b);
   for (DeviceBuf* b : {&c->feature.target, &c->feature.query, &c->feature.finite, &c->feature.idx, &c->feature.d2, &c->feature.n_found})
     release(*b);

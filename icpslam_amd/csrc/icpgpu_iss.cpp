@@ -1,7 +1,9 @@
-// icpgpu_iss.cpp -- host side of the intrinsic shape signature keypoints (pcl::ISSKeypoint3D without border estimation; rules:
-// include/icpgpu.h "ISS keypoints"; kernels: icp_iss.hip).  The call works on the search cloud and its grid (icpgpu_search.cpp) and
-// writes nothing but the ISS state's own buffers: the search state's scratch, and so a later search, normal estimation, FPFH,
-// clustering or segmentation, never meets it.  One wait: the count.
+// icpgpu_iss.cpp -- host side of the intrinsic shape signature keypoints (pcl::ISSKeypoint3D; rules: include/icpgpu.h "ISS
+// keypoints"; kernels: icp_iss.hip, icp_boundary.hip).  The calls work on the search cloud and its grid (icpgpu_search.cpp).  Without
+// border estimation a call writes nothing but the ISS state's own buffers and waits once, for the count.  With it
+// (icpgpu_iss_keypoints_border, border_radius > 0) the border radius's rows -- and the normal radius's, when the normals are computed
+// -- go through the search calls' scratch, as a radius search's do, at one more wait each; the normals, the edge and border flags and
+// everything else the result consists of stay in the ISS state's own buffers.
 #include "icp_ctx.h"
 
 namespace icpgpu_impl {
@@ -17,20 +19,25 @@ int shells_of(const icpgpu_ctx* c, double radius) {
   return s <= (double)kSearchRadiusShells ? (int)s : -1;
 }
 
-}  // namespace
-}  // namespace icpgpu_impl
-
-extern "C" {
-
-int icpgpu_iss_keypoints(icpgpu_ctx* c, double salient_radius, double non_max_radius, double gamma_21, double gamma_32, int min_neighbors,
-                         size_t* n_keypoints) {
-  ENTER(c);
+// both compute calls; border_radius == 0: no border estimation (normals, normal_radius and angle_threshold are not looked at)
+int iss_compute(icpgpu_ctx* c, double salient_radius, double non_max_radius, double gamma_21, double gamma_32, int min_neighbors,
+                double border_radius, double angle_threshold, const float* normals_nxyzc, double normal_radius, size_t* n_keypoints) {
   auto& S = c->search;
   auto& K = c->iss;
   K.have = false;
+  K.with_border = false;
   K.waits = 0;
   if (n_keypoints) *n_keypoints = 0;
   if (!S.set) return fail(c, ICPGPU_ERR_INVALID_ARG, "iss_keypoints: no search cloud (icpgpu_search_set_input)");
+  if (!(std::isfinite(border_radius) && border_radius >= 0.0))
+    return fail(c, ICPGPU_ERR_INVALID_ARG, "iss_keypoints: border_radius must be finite and >= 0 (%g)", border_radius);
+  const bool with_border = border_radius > 0.0;
+  if (with_border) {
+    if (!(std::isfinite(angle_threshold) && angle_threshold > 0.0 && angle_threshold <= M_PI))
+      return fail(c, ICPGPU_ERR_INVALID_ARG, "iss_keypoints: angle_threshold %g outside (0, pi]", angle_threshold);
+    if (!normals_nxyzc && !(std::isfinite(normal_radius) && normal_radius > 0.0))
+      return fail(c, ICPGPU_ERR_INVALID_ARG, "iss_keypoints: border estimation needs normals or a finite normal_radius > 0 (%g)", normal_radius);
+  }
   if (!(std::isfinite(salient_radius) && salient_radius > 0.0) || !(std::isfinite(non_max_radius) && non_max_radius > 0.0))
     return fail(c, ICPGPU_ERR_INVALID_ARG, "iss_keypoints: both radii must be finite and > 0 (salient %g, non-max %g)", salient_radius, non_max_radius);
   if (!std::isfinite(gamma_21) || !std::isfinite(gamma_32)) return fail(c, ICPGPU_ERR_INVALID_ARG, "iss_keypoints: the gammas must be finite");
@@ -53,21 +60,84 @@ int icpgpu_iss_keypoints(icpgpu_ctx* c, double salient_radius, double non_max_ra
   const GridDesc g = grid ? S.grid.g : GridDesc{};
   const float r2_salient = (float)(salient_radius * salient_radius), r2_non_max = (float)(non_max_radius * non_max_radius);
   int* d_count = static_cast<int*>(K.ints.ptr);
+  int waits = 1;
+  const int32_t* d_border = nullptr;
+  if (with_border) {
+    if ((rc = ensure(c, K.normals, m * sizeof(float4)))) return rc;
+    if ((rc = ensure(c, K.edge, m * sizeof(int32_t)))) return rc;
+    if ((rc = ensure(c, K.border, m * sizeof(int32_t)))) return rc;
+    HIP_TRY(c, hipMemsetAsync(K.edge.ptr, 0, m * sizeof(int32_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(K.border.ptr, 0, m * sizeof(int32_t), c->stream));
+    if (n) {
+      float4* d_normals = static_cast<float4*>(K.normals.ptr);
+      const float origin[3] = {0.f, 0.f, 0.f};
+      if (normals_nxyzc) {
+        HIP_TRY(c, hipMemcpyAsync(d_normals, normals_nxyzc, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+      } else {  // icpgpu_normal_estimation(NULL, n, 0, normal_radius, NULL)'s normals, kept on the device
+        if ((rc = radius_rows_on_device(c, "iss_keypoints", S.cloud.data(), n, normal_radius))) return rc;
+        ++waits;
+        HIP_TRY(c, launch_normals_from_rows(S.cloud.data(), (int)n, S.cloud.data(), (int)n, static_cast<const int32_t*>(S.idx.ptr), nullptr, 0,
+                                            static_cast<const int*>(S.row_start.ptr), origin, d_normals, nullptr, c->stream));
+      }
+      if ((rc = radius_rows_on_device(c, "iss_keypoints", S.cloud.data(), n, border_radius))) return rc;
+      ++waits;
+      HIP_TRY(c, launch_boundary_from_rows(S.cloud.data(), (int)n, d_normals, S.cloud.data(), (int)n, static_cast<const int32_t*>(S.idx.ptr), nullptr, 0,
+                                           static_cast<const int*>(S.row_start.ptr), min_neighbors, std::cos(angle_threshold), nullptr,
+                                           static_cast<int32_t*>(K.edge.ptr), nullptr, nullptr, c->stream));
+      HIP_TRY(c, launch_iss_border(S.cloud.data(), (int)n, sorted, cell_start, g, shells_of(c, border_radius), (float)(border_radius * border_radius),
+                                   static_cast<const int32_t*>(K.edge.ptr), static_cast<int32_t*>(K.border.ptr), c->stream));
+    }
+    d_border = static_cast<const int32_t*>(K.border.ptr);
+  }
   HIP_TRY(c, launch_iss_keypoints(S.cloud.data(), (int)n, S.n_finite > 0, sorted, cell_start, g, shells_of(c, salient_radius), r2_salient,
-                                  shells_of(c, non_max_radius), r2_non_max, min_neighbors, gamma_21, gamma_32,
+                                  shells_of(c, non_max_radius), r2_non_max, min_neighbors, gamma_21, gamma_32, d_border,
                                   static_cast<int32_t*>(K.n_salient.ptr), static_cast<double*>(K.scatter.ptr), static_cast<double*>(K.eig.ptr),
                                   static_cast<double*>(K.saliency.ptr), static_cast<int*>(K.flags.ptr), static_cast<int*>(K.pos.ptr),
                                   static_cast<int*>(K.scan.ptr), static_cast<float4*>(K.points.ptr), static_cast<int*>(K.kept.ptr), d_count,
                                   c->stream));
   int count = 0;
   if ((rc = fetch_ints(c, d_count, 1, &count))) return rc;
-  K.waits = 1;
+  K.waits = waits;
   if (count < 0 || (size_t)count > n) return fail(c, ICPGPU_ERR_HIP, "iss_keypoints: %d keypoints of %zu points (internal error)", count, n);
   K.n = n;
   K.n_keypoints = (size_t)count;
+  K.with_border = with_border;
   K.have = true;
   *n_keypoints = K.n_keypoints;
   return ICPGPU_OK;
+}
+
+}  // namespace
+}  // namespace icpgpu_impl
+
+extern "C" {
+
+int icpgpu_iss_keypoints(icpgpu_ctx* c, double salient_radius, double non_max_radius, double gamma_21, double gamma_32, int min_neighbors,
+                         size_t* n_keypoints) {
+  ENTER(c);
+  return iss_compute(c, salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors, 0.0, 0.0, nullptr, 0.0, n_keypoints);
+}
+
+int icpgpu_iss_keypoints_border(icpgpu_ctx* c, double salient_radius, double non_max_radius, double gamma_21, double gamma_32, int min_neighbors,
+                                double border_radius, double angle_threshold, const float* normals_nxyzc, double normal_radius,
+                                size_t* n_keypoints) {
+  ENTER(c);
+  return iss_compute(c, salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors, border_radius, angle_threshold, normals_nxyzc,
+                     normal_radius, n_keypoints);
+}
+
+// zeros after a call without border estimation
+int icpgpu_iss_fetch_border(icpgpu_ctx* c, int32_t* edge, int32_t* border) {
+  ENTER(c);
+  const auto& K = c->iss;
+  if (!K.have) return fail(c, ICPGPU_ERR_INVALID_ARG, "iss_fetch_border: no result (icpgpu_iss_keypoints, icpgpu_iss_keypoints_border)");
+  if (!K.with_border) {
+    if (edge) std::memset(edge, 0, K.n * sizeof(int32_t));
+    if (border) std::memset(border, 0, K.n * sizeof(int32_t));
+    return ICPGPU_OK;
+  }
+  const Delivery out[2] = {{edge, K.edge.ptr, edge ? K.n * sizeof(int32_t) : 0}, {border, K.border.ptr, border ? K.n * sizeof(int32_t) : 0}};
+  return deliver(c, out, 2);
 }
 
 int icpgpu_iss_fetch(icpgpu_ctx* c, size_t capacity_keypoints, int32_t* keypoint_index, float* keypoints_xyzw, int32_t* n_salient, double* scatter6,

@@ -12,15 +12,9 @@ int count_finite(const float* xyzw, size_t n) {
   return nf;
 }
 
-// what a query call needs of the search cloud
-struct SearchView {
-  const float4* cloud = nullptr;
-  int n = 0;
-  const float4* sorted = nullptr;  // null: no grid
-  const int* cell_start = nullptr;
-  GridDesc g{};
-};
+}  // namespace
 
+// (SearchView and the helpers below are shared with icpgpu_boundary.cpp and icpgpu_iss.cpp: icp_ctx.h)
 SearchView view_of(const icpgpu_ctx* c) {
   const auto& S = c->search;
   SearchView v;
@@ -103,7 +97,22 @@ int queue_radius_fill(icpgpu_ctx* c, const float4* d_queries, size_t n_q, int sh
   return ICPGPU_OK;
 }
 
-}  // namespace
+// One radius search, queued, its rows left on the device: S.idx / S.d2 in CSR form by S.row_start, the lengths in S.counts.  One host
+// wait, for the totals that size the rows.
+int radius_rows_on_device(icpgpu_ctx* c, const char* what, const float4* d_points, size_t n_points, double radius) {
+  auto& S = c->search;
+  int shells, rc;
+  float r2;
+  if ((rc = queue_radius_count(c, d_points, n_points, radius, 0, shells, r2))) return rc;
+  unsigned long long totals[2] = {0, 0};
+  const Delivery first[1] = {{totals, S.totals.ptr, sizeof totals}};
+  if ((rc = deliver(c, first, 1))) return rc;
+  if (totals[0] > (unsigned long long)INT32_MAX || totals[1] > (unsigned long long)INT32_MAX)
+    return fail(c, ICPGPU_ERR_UNSUPPORTED, "%s: %llu neighbours in all, more than the int32 scans carry", what, totals[0]);
+  if (totals[0]) return queue_radius_fill(c, d_points, n_points, shells, r2, (size_t)totals[0], (size_t)totals[1]);
+  if ((rc = ensure(c, S.idx, sizeof(int32_t)))) return rc;  // (every row is empty: nothing is read through the pointers)
+  return ensure(c, S.d2, sizeof(float));
+}
 
 // (Delivery: icp_ctx.h)  Results on their way to the caller's (pageable) arrays: up to three device arrays copied into consecutive slices of the pinned
 // staging buffer -- copies the stream really queues -- ONE wait for the stream, then a memcpy each.  Results that do not fit the

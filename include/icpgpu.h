@@ -58,7 +58,8 @@ extern "C" {
  * icpgpu_search_set_input, icpgpu_search_size, icpgpu_search_knn, icpgpu_search_radius, and normal estimation --
  * icpgpu_normal_estimation, and euclidean clustering -- icpgpu_euclidean_cluster_extraction, icpgpu_cluster_fetch, and plane segmentation --
  * icpgpu_sac_plane_segmentation, icpgpu_sac_fetch, icpgpu_sac_stats, icpgpu_sac_extract, icpgpu_sac_extract_view, and ISS keypoints --
- * icpgpu_iss_keypoints, icpgpu_iss_fetch, icpgpu_iss_stats, and fast point feature histograms -- icpgpu_fpfh_estimation, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
+ * icpgpu_iss_keypoints, icpgpu_iss_fetch, icpgpu_iss_stats, icpgpu_iss_keypoints_border, icpgpu_iss_fetch_border, and boundary
+ * estimation -- icpgpu_boundary_estimation, and fast point feature histograms -- icpgpu_fpfh_estimation, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
  * icpgpu_set_p2plane_symmetric, icpgpu_get_p2plane_symmetric, icpgpu_reduce_symmetric_point_to_plane,
  * icpgpu_solve_symmetric_point_to_plane, ICPGPU_REJECT_SURFACE_NORMAL (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
@@ -817,6 +818,59 @@ int icpgpu_fpfh_estimation(icpgpu_ctx* ctx, const float* normals_nxyzc /* n floa
                            int k, double radius, float* out_fpfh /* n_q x 33 */, int32_t* n_neighbours /* n_q, may be NULL */,
                            float* spfh /* n x 33, may be NULL */);
 
+/* ---- boundary estimation (added under 1.2) ------------------------------------------------------------------------- */
+/* replaces pcl::BoundaryEstimation<PointXYZ, Normal, Boundary>: setInputCloud, setInputNormals, setSearchSurface, setKSearch /
+ * setRadiusSearch, setAngleThreshold, compute -- "does this point lie on the rim of the sampled surface": an occlusion shadow, the
+ * edge of the field of view, the end of a wall.  PCL's isBoundaryPoint projects a point's neighbours onto its tangent plane, takes
+ * atan2f of each, sorts the angles and tests "largest gap > angle_threshold".  atan2f's bits are not portable (the problem of FPFH's
+ * bin 1), so the rule is restated here without it and without any dependence on order.  Parity with PCL binaries is unpinned;
+ * tests/boundary_restated.py is what the kernel is compared with, bit for bit.
+ * ROWS.  The context's SEARCH CLOUD (icpgpu_search_set_input) is the search surface; the queries are the input cloud;
+ * queries_xyzw == NULL means the search cloud's own points (n_q must then be 0 or n).  Exactly one of k (1 .. ICPGPU_SEARCH_MAX_K)
+ * and radius (finite, > 0) is set, the other is 0.  The row of query q is exactly icpgpu_search_knn(k)'s or
+ * icpgpu_search_radius(radius, max_nn = 0)'s row for q: the same entries; m_q is its length (n_neighbours[q]).
+ * NORMALS.  normals_nxyzc are the QUERIES' normals: n_q float4 in icpgpu_normal_estimation's output format, the fourth float ignored
+ * (PCL indexes normals_ by the input cloud as well).  They are taken as given and are not normalised.
+ * FRAME.  PCL's getCoordinateSystemOnPlane (Eigen's unitOrthogonal) in float32, every operation rounded on its own.  With n the
+ * normal: near = |n.x| <= 1e-5f * |n.z| and |n.y| <= 1e-5f * |n.z|.  If not near: inv = 1.0f / sqrtf(n.x n.x + n.y n.y) and
+ * v = (-n.y * inv, n.x * inv, 0).  Otherwise inv = 1.0f / sqrtf(n.y n.y + n.z n.z) and v = (0, -n.z * inv, n.y * inv).  Then
+ * u = n x v = (n.y v.z - n.z v.y, n.z v.x - n.x v.z, n.x v.y - n.y v.x), two products and a difference per component.
+ * DIRECTIONS.  For every entry j of the row: d = P_j - P_q per component in float32; x_j = (u.x d.x + u.y d.y) + u.z d.z and y_j the
+ * same with v.  The entry is SKIPPED when all three components of d are 0 (the point itself and coincident points, as in PCL), when
+ * x_j or y_j is not finite (what a zero or a non-finite normal produces), or when x_j == 0 and y_j == 0 (a neighbour straight along
+ * the normal; DEVIATION: PCL gives it the angle atan2f(0, 0) = 0).  The remaining entries are the row's directions;
+ * n_directions[q] is their number.  It is reported as 0 where the rule below does not look at the row: a non-finite query and m_q < 3.
+ * SECTOR TEST.  c = cos(angle_threshold), taken once on the host in double (the plane segmentation's eps_angle is the precedent);
+ * c2 = c * c.  For directions a and b every product below is taken in double from the float32 values, where it is exact, and each
+ * sum or difference is rounded once (the library is built with -ffp-contract=off):
+ *   cr = xa yb - ya xb,  dt = xa xb + ya yb,  na = xa xa + ya ya,  nb = xb xb + yb yb.
+ * b lies IN a's SECTOR iff cr >= 0, and not (cr == 0 and dt > 0) -- the same direction -- and
+ *   for c >= 0:  dt >= 0 and dt * dt >= (c2 * na) * nb;     for c < 0:  dt >= 0 or dt * dt <= (c2 * na) * nb
+ * (double products, rounded).  Mathematically: the angle from a to b, turning from u towards v, lies in (0, angle_threshold].  The
+ * signs of cr and dt are exact.
+ * BOUNDARY.  boundary[q] = 1 iff the query is finite, m_q >= 3 (PCL's indices.size() < 3 rule), n_directions[q] >= 1, and some
+ * direction a has no direction b in its sector; else 0.  This is PCL's "largest gap between angularly consecutive neighbours >
+ * angle_threshold", a single direction counting as a gap of 2 pi, and it does not depend on any order.  witness[q] is the lowest
+ * cloud index among such a, or -1 where boundary[q] = 0: an output so that tests compare more than one bit per point.
+ * DEVIATIONS from PCL 1.8.  No atan2f and no sort: results differ from PCL only where a gap is within rounding of the threshold.  A
+ * lattice's gap of exactly pi / 2 counts as ABOVE angle_threshold = M_PI / 2 (the double is below pi / 2: cos(M_PI / 2) > 0), where
+ * PCL's float32 comparison says the opposite.  angle_threshold must be finite and in (0, pi]; anything else is
+ * ICPGPU_ERR_INVALID_ARG.  An empty row gives 0, where PCL writes NaN.
+ * OUTPUT.  boundary: n_q bytes, required when n_q > 0 -- pcl::Boundary's boundary_point.  n_neighbours, n_directions, witness (each
+ * may be NULL): n_q int32.
+ * LIMITS.  ICPGPU_ERR_INVALID_ARG: no search cloud; null normals or a null boundary with n_q > 0; n_q against null queries; both or
+ * neither of k and radius, or one outside its range.  With a radius, neighbours beyond INT32_MAX in all: ICPGPU_ERR_UNSUPPORTED.  A
+ * cloud the grid refuses is searched without it, as in icpgpu_normal_estimation.  n_q = 0 is ICPGPU_OK and writes nothing.  The test
+ * is quadratic in the row (an interior point leaves after a fraction of its pairs): rows of thousands of entries are slow.
+ * ISOLATION.  As icpgpu_fpfh_estimation: the call has buffers of its own in the context's search state for the normals and the
+ * results and otherwise uses the search calls' scratch.  Its answers depend on the search cloud and the arguments alone (DESIGN.md
+ * section 9b); it leaves the source, the target, every grid, the covariances, the cached normals, the NDT cells, the filters' results
+ * and the search cloud as they were, and unfetched clustering, segmentation, sample-consensus and ISS results survive it.
+ * HOST WAITS.  One with k, two with a radius (the totals that size the rows, then the results). */
+int icpgpu_boundary_estimation(icpgpu_ctx* ctx, const float* normals_nxyzc /* n_q float4 */, const float* queries_xyzw, size_t n_q, int k,
+                               double radius, double angle_threshold, uint8_t* boundary /* n_q */, int32_t* n_neighbours /* may be NULL */,
+                               int32_t* n_directions /* may be NULL */, int32_t* witness /* may be NULL */);
+
 /* ---- feature-space k-nearest (added under 1.2) -------------------------------------------------------------------- */
 /* replaces pcl::KdTreeFLANN<pcl::FPFHSignature33>: setInputCloud, nearestKSearch -- and, with it, feature-space
  * pcl::registration::CorrespondenceEstimation: "which descriptors of that cloud are the k nearest to this descriptor", for any number
@@ -1045,8 +1099,9 @@ int icpgpu_scp_fetch(icpgpu_ctx* ctx, size_t capacity_hypotheses, size_t capacit
 int icpgpu_scp_stats(const icpgpu_ctx* ctx, int32_t* host_waits, int32_t* evaluated, double* host_solve_ms);
 
 /* ---- ISS keypoints (added under 1.2) -------------------------------------------------------------------------------- */
-/* replaces pcl::ISSKeypoint3D<PointXYZ, PointXYZ> (PCL 1.8, keypoints/impl/iss_3d.hpp) without border estimation: setInputCloud,
- * setSalientRadius, setNonMaxRadius, setThreshold21, setThreshold32, setMinNeighbors, compute -- "at which points of this cloud are
+/* replaces pcl::ISSKeypoint3D<PointXYZ, PointXYZ> (PCL 1.8, keypoints/impl/iss_3d.hpp): setInputCloud, setSalientRadius,
+ * setNonMaxRadius, setThreshold21, setThreshold32, setMinNeighbors, compute, and -- through icpgpu_iss_keypoints_border, BORDER
+ * ESTIMATION below -- setBorderRadius, setNormalRadius, setNormals, setAngleThreshold -- "at which points of this cloud are
  * descriptors worth computing", the stage in front of icpgpu_fpfh_estimation at keypoints.  The call works on the context's SEARCH
  * CLOUD (icpgpu_search_set_input), as clustering and plane segmentation do.  Parity with PCL binaries is unpinned;
  * tests/iss_restated.py is what the kernels are compared with, bit for bit.
@@ -1074,25 +1129,50 @@ int icpgpu_scp_stats(const icpgpu_ctx* ctx, int32_t* host_waits, int32_t* evalua
  * one host wait; icpgpu_iss_fetch copies out any subset of it, any number of times: every pointer may be NULL.  n_salient and saliency
  * hold n entries, scatter6 n x 6, eigenvalues3 n x 3.  With keypoint_index or keypoints_xyzw requested and capacity_keypoints <
  * n_keypoints nothing is written and the fetch returns ICPGPU_ERR_INVALID_ARG.  icpgpu_iss_stats reports the host waits of the last
- * compute call: one, for the count.
+ * compute call: one, for the count (more with border estimation: below).
  * ICPGPU_ERR_INVALID_ARG: no search cloud; a radius that is not finite or is <= 0; a gamma that is not finite; min_neighbors < 0; a
  * null n_keypoints; a fetch or stats without a result (none computed, the last call refused, or the search cloud replaced since).  An
  * empty cloud and a cloud with no finite point are ICPGPU_OK with no keypoints.
  * LIMITS.  A cloud the grid refuses is walked without it (up to the 65536 points icpgpu_search_set_input admits then), and a radius
  * whose ball spans more than 8 grid cells is handled as in icpgpu_search_radius: the whole cloud is swept per point, which is slow.
  * All three paths give the same bits.
- * Not provided: border estimation (setBorderRadius / setNormalRadius / setNormals), setIndices, and a search surface other than the
- * input (PCL indexes input_ with surface_'s indices and is only meaningful when the two are one cloud).
- * ISOLATION.  The result depends on the search cloud and the arguments alone.  The call leaves the source, the
- * target, every grid, the covariances, the cached normals, the NDT cells, the filters' results and the search cloud as they were.
- * Unfetched clustering, segmentation and sample-consensus results survive it, and its own result survives searches, normal and FPFH
- * estimations, clusterings and segmentations.  icpgpu_search_set_input drops it, whatever it returns. */
+ * BORDER ESTIMATION (icpgpu_iss_keypoints_border; PCL 1.8's getBoundaryPoints and detectKeypoints).  With border_radius > 0, points
+ * near the rim of the scan are no keypoints: a half-empty ball has an anisotropic scatter matrix wherever it lies.
+ *   NORMALS.  normals_nxyzc: the cloud's normals, n float4 as icpgpu_normal_estimation returns them; or NULL with normal_radius > 0
+ *   (finite): exactly what icpgpu_normal_estimation(NULL, n, k = 0, normal_radius, viewpoint NULL) returns, computed and kept on the
+ *   device.  NULL normals with a normal_radius that is not > 0 is ICPGPU_ERR_INVALID_ARG.
+ *   EDGE.  edge[i] = 1 iff point i is finite, its border ball (d2 < (float)(border_radius * border_radius): the cloud's own radius row)
+ *   holds at least min_neighbors points, and the boundary rule of the section "boundary estimation" on that row, with the normal n_i
+ *   and angle_threshold, says 1 (so the row also holds at least 3).  The kernel is icpgpu_boundary_estimation's.
+ *   BORDER.  border[i] = 1 iff point i is finite and some j in its border ball, itself included, has edge[j] = 1.
+ *   A border point is skipped as PCL skips it: its scatter6, eigenvalues3 and saliency are zeros; n_salient[i] is still the size of
+ *   its salient ball.  Non-maxima suppression, the count and icpgpu_iss_fetch are unchanged; icpgpu_iss_fetch serves either compute
+ *   call.  icpgpu_iss_fetch_border copies out edge and border (n int32 each, either may be NULL); after icpgpu_iss_keypoints, or with
+ *   border_radius == 0, both are zeros.
+ *   border_radius == 0 gives icpgpu_iss_keypoints' result bit for bit; normals, normal_radius and angle_threshold are then ignored.
+ *   Refused (ICPGPU_ERR_INVALID_ARG): a border_radius that is negative or not finite; with border_radius > 0, an angle_threshold that
+ *   is not finite or outside (0, pi].  The border radius's neighbours beyond INT32_MAX in all: ICPGPU_ERR_UNSUPPORTED.
+ *   HOST WAITS, as icpgpu_iss_stats reports them: border_radius == 0: one (the count).  Normals given: two (the totals that size the
+ *   border radius's rows, the count).  Normals computed: three (the totals of the normal radius's rows as well).
+ *   MEMORY.  The border path materialises the border radius's rows (and the normal radius's): it is O(n + neighbours), not O(n).
+ * Not provided: setIndices, and a search surface other than the input (PCL indexes input_ with surface_'s indices and is only
+ * meaningful when the two are one cloud).
+ * ISOLATION.  The result depends on the search cloud and the arguments alone.  Both compute calls leave the
+ * source, the target, every grid, the covariances, the cached normals, the NDT cells, the filters' results and the search cloud as
+ * they were.  Unfetched clustering, segmentation and sample-consensus results survive them, and their own result -- edge and border
+ * included -- survives searches, normal, FPFH and boundary estimations, clusterings and segmentations: the border path's rows go
+ * through the search calls' scratch, everything it keeps lives in the ISS state's own buffers.  icpgpu_search_set_input drops it,
+ * whatever it returns. */
 int icpgpu_iss_keypoints(icpgpu_ctx* ctx, double salient_radius, double non_max_radius, double gamma_21, double gamma_32,
                          int min_neighbors, size_t* n_keypoints);
 int icpgpu_iss_fetch(icpgpu_ctx* ctx, size_t capacity_keypoints, int32_t* keypoint_index /* n_keypoints */,
                      float* keypoints_xyzw /* n_keypoints float4 */, int32_t* n_salient /* n */, double* scatter6 /* n x 6 */,
                      double* eigenvalues3 /* n x 3 */, double* saliency /* n */);
 int icpgpu_iss_stats(const icpgpu_ctx* ctx, int32_t* host_waits);
+int icpgpu_iss_keypoints_border(icpgpu_ctx* ctx, double salient_radius, double non_max_radius, double gamma_21, double gamma_32,
+                                int min_neighbors, double border_radius, double angle_threshold,
+                                const float* normals_nxyzc /* n float4 or NULL */, double normal_radius, size_t* n_keypoints);
+int icpgpu_iss_fetch_border(icpgpu_ctx* ctx, int32_t* edge /* n, may be NULL */, int32_t* border /* n, may be NULL */);
 
 /* ---- the mapper's target: a one-point-per-voxel map and its "nn cloud"  -------- */
 /* replaces OctreeMapper's pcl::octree::OctreePointCloudSearch map

@@ -947,6 +947,77 @@ class FPFHEstimation {
   double radius_ = 0.0;
 };
 
+// pcl::Boundary and pcl::BoundaryEstimation<PointInT, PointNT, pcl::Boundary>-shaped front end (rules and deviations:
+// include/icpgpu.h, "boundary estimation") -- which points lie on the rim of the sampled surface:
+//   pcl::BoundaryEstimation<pcl::PointXYZ, pcl::Normal, pcl::Boundary> be;
+//     ->  icpgpu::BoundaryEstimation<pcl::PointCloud<pcl::PointXYZ>, pcl::PointCloud<pcl::Normal>> be;
+//   be.setInputCloud(cloud); be.setInputNormals(normals); be.setSearchSurface(surface); be.setKSearch(30) or be.setRadiusSearch(0.5);
+//   be.setAngleThreshold(M_PI / 2); be.compute(boundaries);
+// The normals are the INPUT cloud's, one per point, as in PCL (any point type with normal_x, normal_y, normal_z).  The output point
+// type only needs boundary_point (pcl::Boundary, icpgpu::Boundary).  A refused call (both or neither of k and radius set, normals
+// that do not match the input, a threshold outside (0, pi], ...) leaves the output empty.
+struct Boundary {
+  uint8_t boundary_point;
+};
+
+template <class CloudInT, class CloudNT>
+class BoundaryEstimation {
+ public:
+  explicit BoundaryEstimation(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {}
+  template <class CloudPtr>
+  void setInputCloud(const CloudPtr& cloud) { input_ = &*cloud; }
+  template <class NormalsPtr>
+  void setInputNormals(const NormalsPtr& normals) { normals_ = &*normals; }
+  // the cloud the neighbours are taken from; without it the input cloud itself
+  template <class CloudPtr>
+  void setSearchSurface(const CloudPtr& cloud) { surface_ = &*cloud; }
+  template <class TreePtr>
+  void setSearchMethod(const TreePtr&) {}  // accepted and ignored: the search is the library's own (exact)
+  void setKSearch(int k) { k_ = k; }
+  int getKSearch() const { return k_; }
+  void setRadiusSearch(double radius) { radius_ = radius; }
+  double getRadiusSearch() const { return radius_; }
+  void setAngleThreshold(float angle) { angle_ = angle; }
+  float getAngleThreshold() const { return angle_; }
+  template <class CloudOutT>
+  void compute(CloudOutT& output) {
+    output.points.resize(0);
+    detail::set_cloud_shape(output, 0, 0);
+    if (!input_ || !normals_) return;
+    static_assert(sizeof(input_->points[0]) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+    const CloudInT* surface = surface_ ? surface_ : input_;
+    const std::size_t n = input_->points.size(), ns = surface->points.size();
+    if (normals_->points.size() != n) return;  // (PCL refuses normals that do not match the input as well)
+    if (n == 0) return;
+    if (icpgpu_search_set_input(ctx_, ns ? reinterpret_cast<const float*>(&surface->points[0]) : nullptr, ns) != ICPGPU_OK) return;
+    std::vector<float> nxyzc(4 * n);
+    std::vector<uint8_t> flags(n);
+    for (std::size_t i = 0; i < n; ++i) {
+      nxyzc[4 * i] = normals_->points[i].normal_x;
+      nxyzc[4 * i + 1] = normals_->points[i].normal_y;
+      nxyzc[4 * i + 2] = normals_->points[i].normal_z;
+      nxyzc[4 * i + 3] = 0.f;
+    }
+    const float* queries = surface == input_ ? nullptr : reinterpret_cast<const float*>(&input_->points[0]);
+    // (float -> double: PCL keeps the threshold as a float; M_PI as a float lies above pi, which the library refuses)
+    const double angle = angle_ == static_cast<float>(3.14159265358979323846) ? 3.14159265358979323846 : static_cast<double>(angle_);
+    if (icpgpu_boundary_estimation(ctx_, &nxyzc[0], queries, n, k_, radius_, angle, &flags[0], nullptr, nullptr, nullptr) != ICPGPU_OK) return;
+    output.points.resize(n);
+    detail::set_cloud_shape(output, n, 0);
+    for (std::size_t i = 0; i < n; ++i) output.points[i].boundary_point = flags[i];
+  }
+
+ private:
+  detail::ContextPtr ctx_holder_;
+  icpgpu_ctx* ctx_;
+  const CloudInT* input_ = nullptr;
+  const CloudNT* normals_ = nullptr;
+  const CloudInT* surface_ = nullptr;
+  int k_ = 0;
+  double radius_ = 0.0;
+  float angle_ = 1.57079632679489661923f;  // PCL's default: M_PI / 2
+};
+
 // pcl::PointIndices and pcl::EuclideanClusterExtraction<PointT>-shaped front end (rules and deviations: include/icpgpu.h,
 // "euclidean clustering"):
 //   pcl::EuclideanClusterExtraction<pcl::PointXYZ> ec;  ->  icpgpu::EuclideanClusterExtraction<pcl::PointCloud<pcl::PointXYZ>> ec;
@@ -1014,9 +1085,9 @@ class EuclideanClusterExtraction {
 //   iss.setSalientRadius(1.2); iss.setNonMaxRadius(0.8); iss.setThreshold21(0.975); iss.setThreshold32(0.975); iss.setMinNeighbors(5);
 //   iss.setInputCloud(cloud); iss.compute(keypoints); iss.getKeypointsIndices();
 // The defaults are PCL's constructor's (radii 0, gammas 0.975, 5 neighbours): compute() leaves the output empty until both radii are
-// set, and after any refused call.  The keypoints come out in the input's order.  Border estimation is not provided: setBorderRadius
-// with a radius above 0 throws; setNormalRadius and setNumberOfThreads are stored and have no effect.  setIndices, setNormals and a
-// search surface other than the input are not provided.
+// set, and after any refused call.  The keypoints come out in the input's order.  Border estimation is
+// ISSKeypoint3DBorder's, below: on this class setBorderRadius with a radius above 0 throws; setNormalRadius and setNumberOfThreads
+// are stored and have no effect.  setIndices and a search surface other than the input are not provided.
 template <class CloudT>
 class ISSKeypoint3D {
  public:
@@ -1061,7 +1132,7 @@ class ISSKeypoint3D {
   // the last compute()'s keypoints as ascending indices into the input cloud
   PointIndices::ConstPtr getKeypointsIndices() const { return indices_; }
 
- private:
+ protected:  // (ISSKeypoint3DBorder below)
   detail::ContextPtr ctx_holder_;
   icpgpu_ctx* ctx_;
   const CloudT* input_ = nullptr;
@@ -1069,6 +1140,74 @@ class ISSKeypoint3D {
   int min_neighbors_ = 5;
   unsigned int threads_ = 0;
   PointIndices::Ptr indices_;
+};
+
+// ISSKeypoint3D with PCL's border estimation (include/icpgpu.h, "ISS keypoints", BORDER ESTIMATION): setBorderRadius,
+// setNormalRadius, setNormals and setAngleThreshold work as in pcl::ISSKeypoint3D, and compute() refuses every keypoint within the
+// border radius of a boundary point of the cloud.  Beyond PCL: getEdgePoints() and getBorderPoints().  NormalCloudT: any cloud
+// whose points have normal_x, normal_y, normal_z (icpgpu::NormalEstimation's output).  It is a class of its own, and not
+// ISSKeypoint3D itself, because the tests of the change that added ISSKeypoint3D pin that its setBorderRadius(r > 0) throws;
+// folding the two is left to a change that may edit them.
+template <class CloudT, class NormalCloudT>
+class ISSKeypoint3DBorder : public ISSKeypoint3D<CloudT> {
+  typedef ISSKeypoint3D<CloudT> Base;
+
+ public:
+  explicit ISSKeypoint3DBorder(int device = 0) : Base(device), edge_(new PointIndices), border_points_(new PointIndices) {}
+  void setBorderRadius(double border_radius) { this->border_ = border_radius; }
+  void setNormalRadius(double normal_radius) { this->normal_radius_ = normal_radius; }
+  template <class NormalsPtr>
+  void setNormals(const NormalsPtr& normals) { normals_ = &*normals; }
+  void setAngleThreshold(float angle) { angle_ = angle; }
+  void compute(CloudT& output) {
+    output.points.resize(0);
+    detail::set_cloud_shape(output, 0, 0);
+    this->indices_.reset(new PointIndices);
+    edge_.reset(new PointIndices);
+    border_points_.reset(new PointIndices);
+    if (!this->input_) return;
+    static_assert(sizeof(this->input_->points[0]) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+    static_assert(sizeof(int) == sizeof(int32_t), "icpgpu: 32-bit int");
+    const std::size_t n = this->input_->points.size();
+    if (normals_ && normals_->points.size() != n) return;
+    if (icpgpu_search_set_input(this->ctx_, n ? reinterpret_cast<const float*>(&this->input_->points[0]) : nullptr, n) != ICPGPU_OK) return;
+    std::vector<float> nxyzc(normals_ ? 4 * n : 0);
+    for (std::size_t i = 0; i < nxyzc.size() / 4; ++i) {
+      nxyzc[4 * i] = normals_->points[i].normal_x;
+      nxyzc[4 * i + 1] = normals_->points[i].normal_y;
+      nxyzc[4 * i + 2] = normals_->points[i].normal_z;
+      nxyzc[4 * i + 3] = 0.f;
+    }
+    const double angle = angle_ == static_cast<float>(3.14159265358979323846) ? 3.14159265358979323846 : static_cast<double>(angle_);
+    std::size_t m = 0;
+    if (icpgpu_iss_keypoints_border(this->ctx_, this->salient_, this->non_max_, this->gamma_21_, this->gamma_32_, this->min_neighbors_, this->border_,
+                                    angle, nxyzc.empty() ? nullptr : &nxyzc[0], this->normal_radius_, &m) != ICPGPU_OK)
+      return;
+    std::vector<int32_t> edge(n), border(n);
+    if (n && icpgpu_iss_fetch_border(this->ctx_, &edge[0], &border[0]) != ICPGPU_OK) return;
+    for (std::size_t i = 0; i < n; ++i) {
+      if (edge[i]) edge_->indices.push_back(static_cast<int>(i));
+      if (border[i]) border_points_->indices.push_back(static_cast<int>(i));
+    }
+    if (m == 0) return;
+    this->indices_->indices.resize(m);
+    output.points.resize(m);
+    if (icpgpu_iss_fetch(this->ctx_, m, reinterpret_cast<int32_t*>(&this->indices_->indices[0]), reinterpret_cast<float*>(&output.points[0]), nullptr,
+                         nullptr, nullptr, nullptr) != ICPGPU_OK) {
+      this->indices_->indices.clear();
+      output.points.resize(0);
+      return;
+    }
+    detail::set_cloud_shape(output, m, 0);
+  }
+  // the last compute()'s boundary points, and the points it skipped for lying within the border radius of one (ascending indices)
+  PointIndices::ConstPtr getEdgePoints() const { return edge_; }
+  PointIndices::ConstPtr getBorderPoints() const { return border_points_; }
+
+ private:
+  const NormalCloudT* normals_ = nullptr;
+  float angle_ = 1.57079632679489661923f;  // PCL's default: M_PI / 2
+  PointIndices::Ptr edge_, border_points_;
 };
 
 // pcl::ModelCoefficients, pcl::SACSegmentation<PointT> and pcl::ExtractIndices<PointT>-shaped front ends (rules and deviations:
