@@ -6,8 +6,16 @@
 //   icpgpu_reject.cpp   the correspondence rejectors: the chain, its sweep, icpgpu_correspondences
 //   icpgpu_gicp.cpp     GICP: covariances, the evaluation server, the BFGS outer loop
 //   icpgpu_batch.cpp    icpgpu_align_batch: lock-step groups and the round-robin scheduler
+//   icpgpu_p2plane.cpp  point-to-plane ICP (plain and symmetric): the clouds' normals, the 29-sum reduction, the solve
+//   icpgpu_ndt.cpp      NDT: the target's cells, the derivative passes, Newton with either step rule
 //   icpgpu_voxel.cpp    the voxel-grid filter's host side
 //   icpgpu_map.cpp      the mapper's map and its nn cloud
+//   icpgpu_outlier.cpp  the statistical and radius outlier filters; a cloud's k-NN grid (build_knn_grid)
+//   icpgpu_search.cpp   the search cloud: k-nearest and radius search, normal estimation, FPFH, euclidean clustering, and the
+//                       steps every stage over that cloud shares (view_of, neighbour_rows, deliver)
+//   icpgpu_boundary.cpp boundary estimation over the search cloud
+//   icpgpu_sac.cpp      plane segmentation (RANSAC) over the search cloud and ExtractIndices over its result
+//   icpgpu_iss.cpp      ISS keypoints over the search cloud, with and without border estimation
 //   icpgpu_feature.cpp  feature-space k-nearest and the sample-consensus alignment over it
 // (until round 4 all of this was one 3 200-line icpgpu_api.cpp).
 #pragma once
@@ -52,6 +60,14 @@ struct DeviceBuf {
   void* ptr = nullptr;
   size_t cap = 0;      // bytes owned (0 when external)
   bool external = false;
+  template <class T>
+  T* as() const { return static_cast<T*>(ptr); }
+};
+
+// An order-preserving compaction's buffers (launch_compact, icp_scan.hip): the 0 / 1 flags, their exclusive scan and its scratch, and
+// the kept indices -- ensure_compaction (below) sizes them for n items.
+struct Compaction {
+  DeviceBuf flags, pos, scan, kept;
 };
 
 struct Cloud {
@@ -401,7 +417,8 @@ struct icpgpu_ctx {
   struct Outlier {
     Cloud cloud;
     GridIndex grid;
-    DeviceBuf measure, flags, pos, scan, kept, far, ints;
+    DeviceBuf measure, far, ints;
+    Compaction comp;  // comp.kept: the kept points' indices
     int kind = 0;  // 0 none (or the last call was refused), 1 SOR, 2 ROR
     size_t n_in = 0, n_kept = 0, n_valid = 0;
     double mean = 0.0, stddev = 0.0, threshold = 0.0;
@@ -437,8 +454,8 @@ struct icpgpu_ctx {
     float coeff[4] = {0.f, 0.f, 0.f, 0.f}, coeff_unrefined[4] = {0.f, 0.f, 0.f, 0.f};
     double moments[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     std::vector<int32_t> counts;  // count[0 .. iterations)
-    DeviceBuf batch, flags, pos, scan, inliers, ints, sums;
-    DeviceBuf xflags, xpos, kept;  // icpgpu_sac_extract's own
+    DeviceBuf batch, ints, sums;
+    Compaction sel, ext;  // sel.kept: the inliers; ext: icpgpu_sac_extract's own (the inlier list outlives an extract)
   } sac;
   // feature-space k-nearest (icpgpu_feature.cpp, icp_feature.hip): the call's descriptors and rows, in buffers no other call reads or
   // writes -- it neither uses nor touches the search cloud, and an unfetched clustering or segmentation result survives it
@@ -460,7 +477,8 @@ struct icpgpu_ctx {
     std::vector<double> sum;
     DeviceBuf source, sfeat, tfeat, finite, rows, rows_d2, found;     // the inputs and the correspondence rows
     DeviceBuf c_status, c_sidx, c_tidx, c_sums, xforms, partials, results;  // a chunk's
-    DeviceBuf flags, pos, scan, inliers, ints, aligned;              // the best hypothesis'
+    Compaction sel;                                                    // the best hypothesis': sel.kept = its inliers
+    DeviceBuf ints, aligned;
   } scp;
   // ISS keypoints (icpgpu_iss.cpp, icp_iss.hip): the last call's result over the search cloud and its scratch, in buffers no other
   // call writes -- an unfetched result outlives later search, normal, FPFH, clustering, segmentation and sample-consensus calls;
@@ -472,7 +490,8 @@ struct icpgpu_ctx {
     bool with_border = false;                     // the last call estimated borders: edge and border hold its flags
     DeviceBuf n_salient, scatter, eig, saliency;  // per point
     DeviceBuf normals, edge, border;              // border estimation's, per point
-    DeviceBuf flags, pos, scan, kept, points, ints;  // the compaction's; kept / points: the keypoints
+    Compaction comp;                              // comp.kept / points: the keypoints
+    DeviceBuf points, ints;
   } iss;
   std::vector<icpgpu_ctx*> workers;  // align_batch: one sub-context (own stream + scratch) per host worker thread
   DeviceBuf batch_table;             // lock-step batch: the BatchPair table of the group this context leads
@@ -606,6 +625,15 @@ int fail(icpgpu_ctx* c, int code, const char* fmt, ...);
 int ensure(icpgpu_ctx* c, DeviceBuf& b, size_t bytes);
 extern std::atomic<unsigned long long> g_alloc_calls, g_alloc_us;  // allocations through ensure() and their host microseconds
 void release(DeviceBuf& b);
+inline void release(Compaction& C) {
+  for (DeviceBuf* b : {&C.flags, &C.pos, &C.scan, &C.kept}) release(*b);
+}
+inline int ensure_compaction(icpgpu_ctx* c, Compaction& C, size_t n) {
+  int rc;
+  for (DeviceBuf* b : {&C.flags, &C.pos, &C.kept})
+    if ((rc = ensure(c, *b, n * sizeof(int)))) return rc;
+  return ensure(c, C.scan, exclusive_scan_scratch_ints((int)n) * sizeof(int));
+}
 Xform to_xform(const Mat4d& T);
 Xform to_xform(const float* T);
 float threshold_from(double r2);
@@ -720,19 +748,46 @@ struct Delivery {
   size_t bytes;
 };
 int deliver(icpgpu_ctx* c, const Delivery* parts, int n_parts);
-// ... what a query call needs of the search cloud
+// ... what a kernel over the search cloud is handed
 struct SearchView {
   const float4* cloud = nullptr;
   int n = 0;
+  int n_eval = 0;                  // n when the cloud has a finite point, else 0: what a kernel that looks for neighbours is given
   const float4* sorted = nullptr;  // null: no grid
   const int* cell_start = nullptr;
   GridDesc g{};
+  // the cube of `shells` cells around a point's cell contains its ball (shells * h * kGridSafety >= radius: the grid search's bound);
+  // a ball of more than kSearchRadiusShells cells, and every ball of a cloud without a grid, is searched by a sweep (-1)
+  int shells(double radius) const {
+    if (!sorted) return -1;
+    const double s = std::ceil(radius / ((double)g.h * (double)kGridSafety));
+    return s <= (double)kSearchRadiusShells ? (int)s : -1;
+  }
 };
 SearchView view_of(const icpgpu_ctx* c);
 // ... the queries of a call in device memory: the caller's (uploaded into the search state's scratch) or the search cloud's own points
 int stage_queries(icpgpu_ctx* c, const char* what, const float* queries_xyzw, size_t n_q, const float4*& d_queries);
-// ... a radius search (max_nn = 0) whose rows stay on the device: search.idx / d2 by search.row_start, lengths in search.counts; ONE wait
+// ... "exactly one of k and radius": a stage's k (min_k .. ICPGPU_SEARCH_MAX_K) or its radius (finite, > 0), the other one zero
+int check_k_or_radius(icpgpu_ctx* c, const char* what, int k, int min_k, double radius);
+// ... neighbour rows that stay on the device, as the *_from_rows launchers take them: dense rows of stride k with n_found (k-nearest)
+// or CSR rows by row_start (radius); counts: the rows' lengths either way (n ints)
+struct NeighbourRows {
+  const int32_t* idx = nullptr;
+  const float* d2 = nullptr;
+  const int32_t* n_found = nullptr;
+  int k = 0;
+  const int* row_start = nullptr;
+  const void* counts = nullptr;
+};
+// a k-nearest search, queued: search.idx / d2 (stride k), search.n_found.  No wait.
+int knn_rows_on_device(icpgpu_ctx* c, const float4* d_points, size_t n_points, int k);
+// a radius search (max_nn = 0): search.idx / d2 by search.row_start, lengths in search.counts.  ONE wait, for the totals.
 int radius_rows_on_device(icpgpu_ctx* c, const char* what, const float4* d_points, size_t n_points, double radius);
+// the one the stage asked for (k != 0: k-nearest, else the radius) -> rows.  reserve_points (> n_points): the buffers are sized for
+// that many rows -- a call that queues two searches names the larger one in the first, since a buffer that grows is freed first and
+// the free waits for the device
+int neighbour_rows(icpgpu_ctx* c, const char* what, const float4* d_points, size_t n_points, int k, double radius, NeighbourRows& rows,
+                   size_t reserve_points = 0);
 // icpgpu_ndt.cpp
 int align_ndt(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitness, icpgpu_result* res);
 

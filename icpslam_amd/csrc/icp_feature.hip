@@ -23,7 +23,7 @@
 //     in double-double (icp_dd.h) in a fixed order: a wave's points ascending, the four waves in order, then
 //   * scp_fold_kernel: a thread per hypothesis folds the workgroups' partials in workgroup order -- the exact sum rounded once
 //     over the range the header states;
-//   * the best hypothesis' inliers: flags by the same test, the exclusive scan of icp_scan.hip and an ordered scatter.
+//   * the best hypothesis' inliers: flags by the same test, the compaction of icp_scan.hip (launch_compact).
 //
 // A feature d2 that overflows is +inf and still a neighbour (its key sorts behind every finite distance and before the empty key); NaN
 // cannot arise from finite rows (the terms are squares, the sum only grows).
@@ -292,16 +292,6 @@ __global__ __launch_bounds__(SCP_BLOCK) void scp_flag_kernel(const float4* __res
   if (lane == 0) flags[i] = in ? 1 : 0;
 }
 
-// the flagged points' indices in ascending order; *n_out behind them
-__global__ __launch_bounds__(SCP_BLOCK) void scp_scatter_kernel(int n, const int* __restrict__ flags, const int* __restrict__ pos, int* __restrict__ out,
-                                                                int* __restrict__ n_out) {
-  const int i = blockIdx.x * SCP_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const int f = flags[i], at = pos[i];
-  if (f) out[at] = i;
-  if (i == n - 1) *n_out = at + f;
-}
-
 }  // namespace
 
 hipError_t launch_feature_knn(const float* target, int n_t, const float* query, int n_q, int k, int* target_finite, int32_t* idx, float* d2,
@@ -344,10 +334,7 @@ hipError_t launch_scp_select(const float4* source, int n_s, const Xform& T, cons
   if (n_s <= 0) return hipSuccess;
   hipLaunchKernelGGL(scp_flag_kernel, dim3((n_s + SCP_WAVES - 1) / SCP_WAVES), dim3(SCP_BLOCK), 0, stream, source, n_s, T, cloud, n, sorted, cell_start, g,
                      shells, box, r2, flags);
-  hipError_t e = launch_exclusive_scan(flags, pos, n_s, scan_scratch, stream);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(scp_scatter_kernel, dim3((n_s + SCP_BLOCK - 1) / SCP_BLOCK), dim3(SCP_BLOCK), 0, stream, n_s, flags, pos, inliers, n_inliers);
-  return hipGetLastError();
+  return launch_compact(flags, n_s, pos, scan_scratch, inliers, n_inliers, nullptr, nullptr, stream);
 }
 
 }  // namespace icpgpu

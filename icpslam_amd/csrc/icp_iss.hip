@@ -10,7 +10,7 @@
 //     the threshold tests.
 //   * iss_suppress_kernel walks the non-max ball, reads saliency[j] through the candidate's index (the key's low word), counts the
 //     ball and leaves -- wave-uniformly -- at the first neighbour with a larger saliency.  It writes a 0 / 1 flag per point.
-//   * the flags are compacted by the exclusive scan of icp_scan.hip and the gather of icp_outlier.hip (launch_outlier_compact).
+//   * the flags are compacted by icp_scan.hip's launch_compact, which gathers the keypoints too.
 #include <hip/hip_runtime.h>
 
 #include "icp_dd.h"
@@ -239,7 +239,7 @@ hipError_t launch_iss_keypoints(const float4* cloud, int n, bool any_finite, con
   hipLaunchKernelGGL(iss_suppress_kernel, grid, block, 0, stream, cloud, n, sorted, cell_start, g, shells_non_max, r2_non_max, min_neighbors, saliency,
                      flags);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  return launch_outlier_compact(cloud, n, flags, pos, scan_scratch, points, kept, n_kept, stream);
+  return launch_compact(flags, n, pos, scan_scratch, kept, n_kept, cloud, points, stream);
 }
 
 }  // namespace icpgpu

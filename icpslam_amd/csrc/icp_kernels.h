@@ -475,6 +475,12 @@ int approx_max_depth();
 // LSD radix sort of (key, value) int32 pairs from the first halves of keys / vals (2 n ints each) into the second halves
 size_t exclusive_scan_scratch_ints(int n);
 hipError_t launch_exclusive_scan(const int* in, int* out, int n, int* scratch, hipStream_t stream);
+// Order-preserving compaction: the indices i with flags[i] != 0 (0 / 1 flags), ascending, into kept and their number into *n_kept;
+// with cloud and points both given, cloud[i] of those into points (device-visible memory) in the same order.  flags, pos, kept
+// (and points): n of room each; scan_scratch: exclusive_scan_scratch_ints(n) ints.  n <= 0 writes nothing.  Every `flags, pos,
+// scan_scratch` below is this launcher's.
+hipError_t launch_compact(const int* flags, int n, int* pos, int* scan_scratch, int* kept, int* n_kept, const float4* cloud, float4* points,
+                          hipStream_t stream);
 size_t radix_sort_scratch_ints(int n);
 hipError_t launch_radix_sort_pairs(int* keys, int* vals, int n, unsigned int end_bit, int* scratch, hipStream_t stream);
 size_t map_scan_temp_bytes(int n);
@@ -535,10 +541,7 @@ hipError_t launch_sor_flags(const float4* cloud, const float* dist, int n, doubl
 // measure[i] = (float)(finite points j with d2(i, j) < r2) and flags[i]; brute: no grid, every point against the whole cloud
 hipError_t launch_ror_counts(const float4* cloud, int n, const float4* sorted, const int* cell_start, const GridDesc& g, int n_binned, float r2,
                              int min_pts, int negative, bool brute, float* measure, int* flags, hipStream_t stream);
-// the flagged points in input order into out (device-visible memory, n points of room), their indices into kept, their number
-// into *n_kept; pos: n ints, scan_scratch: exclusive_scan_scratch_ints(n) ints
-hipError_t launch_outlier_compact(const float4* cloud, int n, const int* flags, int* pos, int* scan_scratch, float4* out, int* kept, int* n_kept,
-                                  hipStream_t stream);
+// (the kept points: launch_compact over flags)
 
 // ---- neighbour search (icp_search.hip): pcl::search::KdTree's nearestKSearch / radiusSearch ------------------------------------
 // (cloud, n: the search cloud; sorted, cell_start, g: its k-NN grid, or sorted == null when it has none -- the caller caps n then)
@@ -577,8 +580,8 @@ hipError_t launch_cluster_extract(const float4* cloud, int n, bool any_finite, c
 // ---- ISS keypoints (icp_iss.hip): pcl::ISSKeypoint3D over the search cloud ------------------------------------------------------------
 // Per point of `cloud` (sorted, cell_start, g, shells_*: as launch_search_radius_count, one `shells` per radius; any_finite: the cloud
 // has a finite point): n_salient (n), scatter6 (n x 6), eig3 (n x 3, descending) and saliency (n) from the salient ball, then the
-// 0 / 1 keypoint flags from the non-max ball, the keypoints' indices ascending into kept, their points into points (n of room each)
-// and their number into *n_kept.  flags, pos: n ints; scan_scratch: exclusive_scan_scratch_ints(n) ints.  n = 0 writes *n_kept alone.
+// 0 / 1 keypoint flags from the non-max ball, the keypoints' indices ascending into kept, their points into points and their number
+// into *n_kept (launch_compact).  n = 0 writes *n_kept alone.
 // border (n ints, or null: no border estimation): a point with border[i] != 0 keeps its n_salient and has zeros otherwise.
 hipError_t launch_iss_keypoints(const float4* cloud, int n, bool any_finite, const float4* sorted, const int* cell_start, const GridDesc& g,
                                 int shells_salient, float r2_salient, int shells_non_max, float r2_non_max, int min_neighbors, double gamma_21,
@@ -603,8 +606,7 @@ hipError_t launch_sac_batch(const float4* cloud, int n, unsigned long long seed,
                             double cos_eps, float thr, SacBatch* batch, hipStream_t stream);
 // flags[i] = 1 where point i is an inlier of `plane` (nowhere when !found), the other way round with `invert`
 hipError_t launch_sac_flags(const float4* cloud, int n, const float plane[4], float thr, bool found, bool invert, int* flags, hipStream_t stream);
-// the inliers of `plane` in ascending order into inliers (n ints), their number into *n_inliers; flags, pos: n ints; scan_scratch:
-// exclusive_scan_scratch_ints(n) ints
+// the inliers of `plane` in ascending order into inliers, their number into *n_inliers (launch_compact)
 hipError_t launch_sac_select(const float4* cloud, int n, const float plane[4], float thr, int* flags, int* pos, int* scan_scratch, int* inliers,
                              int* n_inliers, hipStream_t stream);
 // sums12[0 .. 9): the exact sums, rounded once, of dx dx, dx dy, dx dz, dy dy, dy dz, dz dz, dx, dy, dz over the m > 0 listed points
@@ -675,7 +677,7 @@ int scp_eval_blocks(int n_s);
 hipError_t launch_scp_eval(const float4* source, int n_s, const Xform* xforms, int n_h, const float4* cloud, int n, const float4* sorted,
                            const int* cell_start, const GridDesc& g, int shells, const ScpBox& box, float r2, ScpPartial* partials, ScpResult* results,
                            hipStream_t stream);
-// the inliers of T, ascending, and their number; flags, pos, inliers: n_s ints each; scan_scratch: exclusive_scan_scratch_ints(n_s)
+// the inliers of T, ascending, and their number (launch_compact over n_s flags)
 hipError_t launch_scp_select(const float4* source, int n_s, const Xform& T, const float4* cloud, int n, const float4* sorted, const int* cell_start,
                              const GridDesc& g, int shells, const ScpBox& box, float r2, int* flags, int* pos, int* scan_scratch, int* inliers,
                              int* n_inliers, hipStream_t stream);

@@ -13,8 +13,8 @@
 //     sor_far_kernel -- a workgroup per listed point, the same selection fed from a linear sweep of the whole cloud -- finishes it.
 //     A cloud the grid refuses goes through that kernel point by point (the host caps its size, as for GICP's covariances).
 // ROR counts, per point, the grid neighbours inside the radius: the cells of the cube that contains the ball, one thread per point.
-// The rest is shared: one fixed-order double-double reduction for SOR's sums and its threshold, keep flags, an exclusive prefix sum
-// (icp_scan.hip) and an ordered scatter that writes the kept points where the host will read them.
+// The rest is shared: one fixed-order double-double reduction for SOR's sums and its threshold, keep flags, and the compaction
+// of icp_scan.hip (launch_compact), which writes the kept points where the host will read them.
 #include <hip/hip_runtime.h>
 
 #include "icp_dd.h"
@@ -295,20 +295,6 @@ __global__ __launch_bounds__(OL_BLOCK) void sor_flags_kernel(const float* __rest
   flags[i] = removed ? 0 : 1;
 }
 
-// kept points in input order: out[pos[i]] = cloud[i], kept[pos[i]] = i; *n_kept behind them
-__global__ __launch_bounds__(OL_BLOCK) void outlier_scatter_kernel(const float4* __restrict__ cloud, int n, const int* __restrict__ flags,
-                                                                   const int* __restrict__ pos, float4* __restrict__ out, int* __restrict__ kept,
-                                                                   int* __restrict__ n_kept) {
-  const int i = blockIdx.x * OL_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const int f = flags[i], at = pos[i];
-  if (f) {
-    out[at] = cloud[i];
-    kept[at] = i;
-  }
-  if (i == n - 1) *n_kept = at + f;
-}
-
 }  // namespace
 
 hipError_t launch_sor_distances(const float4* cloud, int n, const float4* sorted, const int* cell_start, const GridDesc& g, int n_binned,
@@ -352,15 +338,6 @@ hipError_t launch_ror_counts(const float4* cloud, int n, const float4* sorted, c
       hipLaunchKernelGGL(ror_count_kernel, dim3((n_binned + OL_BLOCK - 1) / OL_BLOCK), block, 0, stream, sorted, cell_start, g, n_binned, r2, min_pts,
                          negative, measure, flags);
   }
-  return hipGetLastError();
-}
-
-hipError_t launch_outlier_compact(const float4* cloud, int n, const int* flags, int* pos, int* scan_scratch, float4* out, int* kept, int* n_kept,
-                                  hipStream_t stream) {
-  if (n <= 0) return hipSuccess;
-  hipError_t e = launch_exclusive_scan(flags, pos, n, scan_scratch, stream);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(outlier_scatter_kernel, dim3((n + OL_BLOCK - 1) / OL_BLOCK), dim3(OL_BLOCK), 0, stream, cloud, n, flags, pos, out, kept, n_kept);
   return hipGetLastError();
 }
 

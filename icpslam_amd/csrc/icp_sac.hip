@@ -10,7 +10,7 @@
 //     and point register one ballot of the inlier test, and lane h adds the popcount to its own register.  The grid is capped and
 //     every workgroup strides over the cloud.  At the end the four waves of a workgroup add their registers in LDS and 64 lanes do
 //     one integer atomicAdd each into count[h]: integer sums do not depend on their order, so the counts are exact.
-//   * selection: flags by the same test, the exclusive scan of icp_scan.hip and an ordered scatter -- ascending indices.
+//   * selection: flags by the same test, the compaction of icp_scan.hip (launch_compact) -- ascending indices.
 //   * sac_sums_kernel: the refinement's nine sums over the inliers about K = cloud[sample[0]], ONE workgroup in a fixed order, every
 //     term exact in float64 and accumulated in double-double (icp_dd.h): the exact sums rounded once.
 #include <hip/hip_runtime.h>
@@ -128,16 +128,6 @@ __global__ __launch_bounds__(SAC_BLOCK) void sac_flag_kernel(const float4* __res
   flags[i] = (in ? 1 : 0) ^ invert;
 }
 
-// the flagged points' indices in ascending order; *n_out behind them
-__global__ __launch_bounds__(SAC_BLOCK) void sac_scatter_kernel(int n, const int* __restrict__ flags, const int* __restrict__ pos, int* __restrict__ out,
-                                                                int* __restrict__ n_out) {
-  const int i = blockIdx.x * SAC_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const int f = flags[i], at = pos[i];
-  if (f) out[at] = i;
-  if (i == n - 1) *n_out = at + f;
-}
-
 // out[0 .. 9): the sums of dx dx, dx dy, dx dz, dy dy, dy dz, dz dz, dx, dy, dz over the m listed points, d = q - K in float32 with
 // K = cloud[k_index]; out[9 .. 12): K.  Thread t takes entries t, t + 1024, ...; then a binary tree per sum.
 __global__ __launch_bounds__(SAC_REDUCE) void sac_sums_kernel(const float4* __restrict__ cloud, const int* __restrict__ list, int n, int m, int k_index,
@@ -198,9 +188,7 @@ hipError_t launch_sac_select(const float4* cloud, int n, const float plane[4], f
   if (n <= 0) return hipSuccess;
   hipError_t e = launch_sac_flags(cloud, n, plane, thr, true, false, flags, stream);
   if (e != hipSuccess) return e;
-  if ((e = launch_exclusive_scan(flags, pos, n, scan_scratch, stream)) != hipSuccess) return e;
-  hipLaunchKernelGGL(sac_scatter_kernel, dim3((n + SAC_BLOCK - 1) / SAC_BLOCK), dim3(SAC_BLOCK), 0, stream, n, flags, pos, inliers, n_inliers);
-  return hipGetLastError();
+  return launch_compact(flags, n, pos, scan_scratch, inliers, n_inliers, nullptr, nullptr, stream);
 }
 
 hipError_t launch_sac_sums(const float4* cloud, int n, const int* inliers, int m, int k_index, double* sums12, hipStream_t stream) {

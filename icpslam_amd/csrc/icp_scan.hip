@@ -1,6 +1,7 @@
 // icp_scan.hip -- the two generic primitives the widened rows need, hand-written for gfx950 (until round 3 these were
 // rocPRIM calls): an exclusive prefix sum of int32 and a STABLE least-significant-digit radix sort of (int32 key, int32
-// value) pairs.
+// value) pairs; and the order-preserving compaction over the first (launch_compact: the outlier filters, plane segmentation and
+// its extraction, the sample-consensus alignment's inliers, the ISS keypoints).
 //   * exclusive scan: the map's order-preserving compactions (icp_map.hip: winners of an insert, the nn cloud, its distinct
 //     points) and the voxel filter's sort path (icp_voxel.hip) -- three launches: tile sums, one workgroup over the tile
 //     sums, apply.  Same structure as the cell-table scan of icp_grid.hip, for arbitrary in / out arrays.
@@ -99,6 +100,20 @@ __global__ __launch_bounds__(256) void scan_apply_tiles_kernel(const int* __rest
   }
 }
 
+// the flagged items' indices in ascending order: kept[pos[i]] = i, *n_kept behind them; given a cloud and an output array (the null
+// test is uniform over the launch) their points too: points[pos[i]] = cloud[i]
+__global__ __launch_bounds__(256) void compact_scatter_kernel(int n, const int* __restrict__ flags, const int* __restrict__ pos, int* __restrict__ kept,
+                                                              int* __restrict__ n_kept, const float4* __restrict__ cloud, float4* __restrict__ points) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int f = flags[i], at = pos[i];
+  if (f) {
+    kept[at] = i;
+    if (cloud && points) points[at] = cloud[i];
+  }
+  if (i == n - 1) *n_kept = at + f;
+}
+
 // ---- radix sort ---------------------------------------------------------------------------------------------------
 constexpr int RS_ITEMS = 8, RS_TILE = 256 * RS_ITEMS, RS_BITS = 4, RS_DIGITS = 1 << RS_BITS;
 
@@ -185,6 +200,15 @@ hipError_t launch_exclusive_scan(const int* in, int* out, int n, int* scratch, h
   hipLaunchKernelGGL(scan_tile_sums_kernel, dim3(nt), dim3(256), 0, stream, in, n, scratch);
   hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(1024), 0, stream, scratch, nt);
   hipLaunchKernelGGL(scan_apply_tiles_kernel, dim3(nt), dim3(256), 0, stream, in, out, n, scratch);
+  return hipGetLastError();
+}
+
+hipError_t launch_compact(const int* flags, int n, int* pos, int* scan_scratch, int* kept, int* n_kept, const float4* cloud, float4* points,
+                          hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  hipError_t e = launch_exclusive_scan(flags, pos, n, scan_scratch, stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(compact_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, flags, pos, kept, n_kept, cloud, points);
   return hipGetLastError();
 }
 

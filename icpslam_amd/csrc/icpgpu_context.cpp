@@ -667,26 +667,23 @@ int icpgpu_destroy(icpgpu_ctx* c) {
                        &c->map.flags, &c->map.rank, &c->map.temp, &c->map.counter, &c->map.nn_keys, &c->map.first_user,
                        &c->map.uflags, &c->map.urank, &c->map.uniq_index, &c->map.uniq.buf})
     release(*b);
-  for (DeviceBuf* b : {&c->outlier.cloud.buf, &c->outlier.measure, &c->outlier.flags, &c->outlier.pos, &c->outlier.scan, &c->outlier.kept,
-                       &c->outlier.far, &c->outlier.ints})
-    release(*b);
+  for (DeviceBuf* b : {&c->outlier.cloud.buf, &c->outlier.measure, &c->outlier.far, &c->outlier.ints}) release(*b);
+  for (Compaction* C : {&c->outlier.comp, &c->sac.sel, &c->sac.ext, &c->scp.sel, &c->iss.comp}) release(*C);
   for (DeviceBuf* b : {&c->search.cloud.buf, &c->search.queries, &c->search.idx, &c->search.d2, &c->search.n_found, &c->search.far,
                        &c->search.counts, &c->search.longs, &c->search.row_start, &c->search.scratch_start, &c->search.scan,
                        &c->search.scratch, &c->search.totals, &c->search.row_start64, &c->search.normals, &c->search.moments,
-                       &c->search.bnd_normals, &c->search.bnd_flags, &c->search.bnd_dirs, &c->search.bnd_witness})
+                       &c->search.fpfh_normals, &c->search.spfh, &c->search.fpfh, &c->search.bnd_normals, &c->search.bnd_flags, &c->search.bnd_dirs,
+                       &c->search.bnd_witness})
     release(*b);
   for (DeviceBuf* b : {&c->cluster.parent, &c->cluster.sizes, &c->cluster.component, &c->cluster.labels, &c->cluster.rank_of, &c->cluster.csize,
                        &c->cluster.cstart, &c->cluster.cstart64, &c->cluster.keys, &c->cluster.vals, &c->cluster.scratch, &c->cluster.counts})
     release(*b);
-  for (DeviceBuf* b : {&c->sac.batch, &c->sac.flags, &c->sac.pos, &c->sac.scan, &c->sac.inliers, &c->sac.ints, &c->sac.sums, &c->sac.xflags,
-                       &c->sac.xpos, &c->sac.kept})
-    release(*b);
+  for (DeviceBuf* b : {&c->sac.batch, &c->sac.ints, &c->sac.sums}) release(*b);
   for (DeviceBuf* b : {&c->scp.source, &c->scp.sfeat, &c->scp.tfeat, &c->scp.finite, &c->scp.rows, &c->scp.rows_d2, &c->scp.found, &c->scp.c_status,
-                       &c->scp.c_sidx, &c->scp.c_tidx, &c->scp.c_sums, &c->scp.xforms, &c->scp.partials, &c->scp.results, &c->scp.flags, &c->scp.pos,
-                       &c->scp.scan, &c->scp.inliers, &c->scp.ints, &c->scp.aligned})
+                       &c->scp.c_sidx, &c->scp.c_tidx, &c->scp.c_sums, &c->scp.xforms, &c->scp.partials, &c->scp.results, &c->scp.ints, &c->scp.aligned})
     release(*b);
-  for (DeviceBuf* b : {&c->iss.n_salient, &c->iss.scatter, &c->iss.eig, &c->iss.saliency, &c->iss.flags, &c->iss.pos, &c->iss.scan, &c->iss.kept,
-                       &c->iss.points, &c->iss.ints, &c->iss.normals, &c->iss.edge, &c->iss.border})
+  for (DeviceBuf* b : {&c->iss.n_salient, &c->iss.scatter, &c->iss.eig, &c->iss.saliency, &c->iss.points, &c->iss.ints, &c->iss.normals, &c->iss.edge,
+                       &c->iss.border})
     release(*b);
   for (DeviceBuf* b : {&c->feature.target, &c->feature.query, &c->feature.finite, &c->feature.idx, &c->feature.d2, &c->feature.n_found})
     release(*b);

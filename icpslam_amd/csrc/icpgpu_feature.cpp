@@ -40,9 +40,8 @@ int icpgpu_feature_knn(icpgpu_ctx* c, const float* target_feat, size_t n_t, cons
   if ((rc = ensure(c, F.n_found, n_q * sizeof(int32_t)))) return rc;
   if (n_t) HIP_TRY(c, hipMemcpyAsync(F.target.ptr, target_feat, n_t * row, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(F.query.ptr, query_feat, n_q * row, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, launch_feature_knn(static_cast<const float*>(F.target.ptr), (int)n_t, static_cast<const float*>(F.query.ptr), (int)n_q, k,
-                                static_cast<int*>(F.finite.ptr), static_cast<int32_t*>(F.idx.ptr), static_cast<float*>(F.d2.ptr),
-                                static_cast<int32_t*>(F.n_found.ptr), c->stream));
+  HIP_TRY(c, launch_feature_knn(F.target.as<const float>(), (int)n_t, F.query.as<const float>(), (int)n_q, k, F.finite.as<int>(), F.idx.as<int32_t>(),
+                                F.d2.as<float>(), F.n_found.as<int32_t>(), c->stream));
   const Delivery out[3] = {{idx, F.idx.ptr, cells * sizeof(int32_t)}, {d2, F.d2.ptr, cells * sizeof(float)},
                            {n_found, F.n_found.ptr, n_found ? n_q * sizeof(int32_t) : 0}};
   return deliver(c, out, 3);
@@ -93,22 +92,13 @@ int icpgpu_scp_align(icpgpu_ctx* c, const float* source_xyzw, size_t n_s, const 
   K.error.assign((size_t)it, FLT_MAX);
   K.transforms.assign((size_t)it * 16, 0.f);
 
-  // the search cloud as the evaluation sees it (as icpgpu_search_radius: the cube of `shells` cells holds the ball, or the cloud is swept)
-  const float4* d_cloud = S.cloud.data();
-  const int n_eval = S.n_finite > 0 ? (int)n : 0;
-  const float4* d_sorted = nullptr;
-  const int* d_cell_start = nullptr;
-  GridDesc g{};
-  if (n && S.grid.usable) {
-    d_sorted = static_cast<const float4*>(S.grid.sorted.ptr);
-    d_cell_start = static_cast<const int*>(S.grid.cell_start.ptr);
-    g = S.grid.g;
-  }
-  int shells = -1;
+  // the search cloud as the evaluation sees it
+  const SearchView v = view_of(c);
+  const float4* d_cloud = v.cloud;
+  const GridDesc& g = v.g;
+  const int shells = v.shells(max_correspondence_distance);
   ScpBox box{};
-  if (d_sorted) {
-    const double s = std::ceil(max_correspondence_distance / ((double)g.h * (double)kGridSafety));
-    if (s <= (double)kSearchRadiusShells) shells = (int)s;
+  if (v.sorted) {
     // every finite target point lies in the grid's cells; an image farther outside them than the distance (and a margin far above the
     // binning's rounding) has every d2 above r2
     const double grow = max_correspondence_distance * 1.01 + 0.05 * (double)g.h;
@@ -125,7 +115,7 @@ int icpgpu_scp_align(icpgpu_ctx* c, const float* source_xyzw, size_t n_s, const 
   if (n_s > 0) {
     if ((rc = ensure(c, K.source, n_s * sizeof(float4)))) return rc;
     HIP_TRY(c, hipMemcpyAsync(K.source.ptr, source_xyzw, n_s * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    d_source = static_cast<const float4*>(K.source.ptr);
+    d_source = K.source.as<const float4>();
   }
   if (it > 0 && n_s > 0) {
     const size_t row = ICPGPU_FPFH_BINS * sizeof(float);
@@ -146,9 +136,8 @@ int icpgpu_scp_align(icpgpu_ctx* c, const float* source_xyzw, size_t n_s, const 
     HIP_TRY(c, hipMemcpyAsync(K.sfeat.ptr, source_feat, n_s * row, hipMemcpyHostToDevice, c->stream));
     if (n) HIP_TRY(c, hipMemcpyAsync(K.tfeat.ptr, target_feat, n * row, hipMemcpyHostToDevice, c->stream));
     // the correspondence rows of every source point, up front: icpgpu_feature_knn's rows, which stay on the device
-    HIP_TRY(c, launch_feature_knn(static_cast<const float*>(K.tfeat.ptr), (int)n, static_cast<const float*>(K.sfeat.ptr), ns, kc,
-                                  static_cast<int*>(K.finite.ptr), static_cast<int32_t*>(K.rows.ptr), static_cast<float*>(K.rows_d2.ptr),
-                                  static_cast<int32_t*>(K.found.ptr), c->stream));
+    HIP_TRY(c, launch_feature_knn(K.tfeat.as<const float>(), (int)n, K.sfeat.as<const float>(), ns, kc, K.finite.as<int>(), K.rows.as<int32_t>(),
+                                  K.rows_d2.as<float>(), K.found.as<int32_t>(), c->stream));
 
     std::vector<double> sums;
     std::vector<Xform> xforms;
@@ -157,9 +146,8 @@ int icpgpu_scp_align(icpgpu_ctx* c, const float* source_xyzw, size_t n_s, const 
     float best_error = FLT_MAX;
     for (int t0 = 0; t0 < it; t0 += kScpChunk) {
       const int m = std::min(kScpChunk, it - t0);
-      HIP_TRY(c, launch_scp_sample(d_source, ns, d_cloud, (int)n, static_cast<const int32_t*>(K.rows.ptr), static_cast<const int32_t*>(K.found.ptr), kc,
-                                   (unsigned long long)seed, t0, m, nr, sim2, static_cast<int32_t*>(K.c_status.ptr), static_cast<int32_t*>(K.c_sidx.ptr),
-                                   static_cast<int32_t*>(K.c_tidx.ptr), static_cast<double*>(K.c_sums.ptr), c->stream));
+      HIP_TRY(c, launch_scp_sample(d_source, ns, d_cloud, v.n, K.rows.as<const int32_t>(), K.found.as<const int32_t>(), kc, (unsigned long long)seed, t0, m,
+                                   nr, sim2, K.c_status.as<int32_t>(), K.c_sidx.as<int32_t>(), K.c_tidx.as<int32_t>(), K.c_sums.as<double>(), c->stream));
       sums.resize((size_t)m * kReduceTerms);
       HIP_TRY(c, hipMemcpyAsync(K.status.data() + t0, K.c_status.ptr, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(c, hipMemcpyAsync(K.sidx.data() + (size_t)t0 * nr, K.c_sidx.ptr, (size_t)m * nr * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -191,8 +179,8 @@ int icpgpu_scp_align(icpgpu_ctx* c, const float* source_xyzw, size_t n_s, const 
       if (L == 0) continue;
       HIP_TRY(c, hipMemcpyAsync(K.xforms.ptr, xforms.data(), (size_t)L * sizeof(Xform), hipMemcpyHostToDevice, c->stream));
       for (int b = 0; b < L; b += kScpBatch)
-        HIP_TRY(c, launch_scp_eval(d_source, ns, static_cast<const Xform*>(K.xforms.ptr) + b, std::min(kScpBatch, L - b), d_cloud, n_eval, d_sorted, d_cell_start, g,
-                                   shells, box, r2, static_cast<ScpPartial*>(K.partials.ptr), static_cast<ScpResult*>(K.results.ptr) + b, c->stream));
+        HIP_TRY(c, launch_scp_eval(d_source, ns, K.xforms.as<const Xform>() + b, std::min(kScpBatch, L - b), d_cloud, v.n_eval, v.sorted, v.cell_start, g,
+                                   shells, box, r2, K.partials.as<ScpPartial>(), K.results.as<ScpResult>() + b, c->stream));
       results.resize((size_t)L);
       HIP_TRY(c, hipMemcpyAsync(results.data(), K.results.ptr, (size_t)L * sizeof(ScpResult), hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -217,9 +205,7 @@ int icpgpu_scp_align(icpgpu_ctx* c, const float* source_xyzw, size_t n_s, const 
   }
 
   if (n_s > 0) {  // the best hypothesis (or the identity): the inlier list and the aligned cloud
-    for (DeviceBuf* b : {&K.flags, &K.pos, &K.inliers})
-      if ((rc = ensure(c, *b, n_s * sizeof(int)))) return rc;
-    if ((rc = ensure(c, K.scan, exclusive_scan_scratch_ints(ns) * sizeof(int)))) return rc;
+    if ((rc = ensure_compaction(c, K.sel, n_s))) return rc;
     if ((rc = ensure(c, K.ints, 4 * sizeof(int)))) return rc;
     if ((rc = ensure(c, K.aligned, n_s * sizeof(float4)))) return rc;
     Xform Tb = to_xform(static_cast<const float*>(nullptr));
@@ -228,13 +214,12 @@ int icpgpu_scp_align(icpgpu_ctx* c, const float* source_xyzw, size_t n_s, const 
       K.fitness = K.error[(size_t)K.best_t];
       for (int i = 0; i < 16; ++i) K.T[i] = K.transforms[(size_t)K.best_t * 16 + i];
       Tb = to_xform(K.T);
-      HIP_TRY(c, launch_scp_select(d_source, ns, Tb, d_cloud, n_eval, d_sorted, d_cell_start, g, shells, box, r2, static_cast<int*>(K.flags.ptr),
-                                   static_cast<int*>(K.pos.ptr), static_cast<int*>(K.scan.ptr), static_cast<int*>(K.inliers.ptr),
-                                   static_cast<int*>(K.ints.ptr), c->stream));
+      HIP_TRY(c, launch_scp_select(d_source, ns, Tb, d_cloud, v.n_eval, v.sorted, v.cell_start, g, shells, box, r2, K.sel.flags.as<int>(),
+                                   K.sel.pos.as<int>(), K.sel.scan.as<int>(), K.sel.kept.as<int>(), K.ints.as<int>(), c->stream));
     } else {
       HIP_TRY(c, hipMemsetAsync(K.ints.ptr, 0, 4 * sizeof(int), c->stream));
     }
-    HIP_TRY(c, launch_transform(d_source, ns, Tb, static_cast<float4*>(K.aligned.ptr), c->stream));
+    HIP_TRY(c, launch_transform(d_source, ns, Tb, K.aligned.as<float4>(), c->stream));
     int m_in = 0;
     const Delivery out[2] = {{&m_in, K.ints.ptr, sizeof(int)}, {out_xyzw, K.aligned.ptr, out_xyzw ? n_s * sizeof(float4) : 0}};
     if ((rc = deliver(c, out, 2))) return rc;
@@ -262,7 +247,7 @@ int icpgpu_scp_fetch(icpgpu_ctx* c, size_t capacity_hypotheses, size_t capacity_
     return fail(c, ICPGPU_ERR_INVALID_ARG, "scp_fetch: %zu hypotheses and %zu inliers, room for %zu and %zu", it, K.n_inliers, capacity_hypotheses,
                 capacity_inliers);
   if (inliers && K.n_inliers) {
-    const int rc = copy_to_host(c, inliers, K.inliers.ptr, K.n_inliers * sizeof(int32_t));
+    const int rc = copy_to_host(c, inliers, K.sel.kept.ptr, K.n_inliers * sizeof(int32_t));
     if (rc) return rc;
   }
   if (it) {

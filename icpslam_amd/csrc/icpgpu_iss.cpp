@@ -9,16 +9,6 @@
 namespace icpgpu_impl {
 namespace {
 
-// the cube of `shells` cells around a point's cell contains its ball (shells * h * kGridSafety >= radius: the grid search's bound);
-// a ball of more than kSearchRadiusShells cells, and every ball of a cloud without a grid, is searched by a sweep (-1): the rule of
-// icpgpu_search_radius
-int shells_of(const icpgpu_ctx* c, double radius) {
-  const auto& S = c->search;
-  if (!(S.n && S.grid.usable)) return -1;
-  const double s = std::ceil(radius / ((double)S.grid.g.h * (double)kGridSafety));
-  return s <= (double)kSearchRadiusShells ? (int)s : -1;
-}
-
 // both compute calls; border_radius == 0: no border estimation (normals, normal_radius and angle_threshold are not looked at)
 int iss_compute(icpgpu_ctx* c, double salient_radius, double non_max_radius, double gamma_21, double gamma_32, int min_neighbors,
                 double border_radius, double angle_threshold, const float* normals_nxyzc, double normal_radius, size_t* n_keypoints) {
@@ -49,17 +39,11 @@ int iss_compute(icpgpu_ctx* c, double salient_radius, double non_max_radius, dou
   if ((rc = ensure(c, K.scatter, m * 6 * sizeof(double)))) return rc;
   if ((rc = ensure(c, K.eig, m * 3 * sizeof(double)))) return rc;
   if ((rc = ensure(c, K.saliency, m * sizeof(double)))) return rc;
-  for (DeviceBuf* b : {&K.flags, &K.pos, &K.kept})
-    if ((rc = ensure(c, *b, m * sizeof(int)))) return rc;
-  if ((rc = ensure(c, K.scan, exclusive_scan_scratch_ints((int)m) * sizeof(int)))) return rc;
+  if ((rc = ensure_compaction(c, K.comp, m))) return rc;
   if ((rc = ensure(c, K.points, m * sizeof(float4)))) return rc;
   if ((rc = ensure(c, K.ints, 4 * sizeof(int)))) return rc;
-  const bool grid = n && S.grid.usable;
-  const float4* sorted = grid ? static_cast<const float4*>(S.grid.sorted.ptr) : nullptr;
-  const int* cell_start = grid ? static_cast<const int*>(S.grid.cell_start.ptr) : nullptr;
-  const GridDesc g = grid ? S.grid.g : GridDesc{};
+  const SearchView v = view_of(c);
   const float r2_salient = (float)(salient_radius * salient_radius), r2_non_max = (float)(non_max_radius * non_max_radius);
-  int* d_count = static_cast<int*>(K.ints.ptr);
   int waits = 1;
   const int32_t* d_border = nullptr;
   if (with_border) {
@@ -69,34 +53,31 @@ int iss_compute(icpgpu_ctx* c, double salient_radius, double non_max_radius, dou
     HIP_TRY(c, hipMemsetAsync(K.edge.ptr, 0, m * sizeof(int32_t), c->stream));
     HIP_TRY(c, hipMemsetAsync(K.border.ptr, 0, m * sizeof(int32_t), c->stream));
     if (n) {
-      float4* d_normals = static_cast<float4*>(K.normals.ptr);
+      float4* d_normals = K.normals.as<float4>();
       const float origin[3] = {0.f, 0.f, 0.f};
+      NeighbourRows rows;
       if (normals_nxyzc) {
         HIP_TRY(c, hipMemcpyAsync(d_normals, normals_nxyzc, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
       } else {  // icpgpu_normal_estimation(NULL, n, 0, normal_radius, NULL)'s normals, kept on the device
-        if ((rc = radius_rows_on_device(c, "iss_keypoints", S.cloud.data(), n, normal_radius))) return rc;
+        if ((rc = neighbour_rows(c, "iss_keypoints", v.cloud, n, 0, normal_radius, rows))) return rc;
         ++waits;
-        HIP_TRY(c, launch_normals_from_rows(S.cloud.data(), (int)n, S.cloud.data(), (int)n, static_cast<const int32_t*>(S.idx.ptr), nullptr, 0,
-                                            static_cast<const int*>(S.row_start.ptr), origin, d_normals, nullptr, c->stream));
+        HIP_TRY(c, launch_normals_from_rows(v.cloud, v.n, v.cloud, v.n, rows.idx, rows.n_found, rows.k, rows.row_start, origin, d_normals, nullptr, c->stream));
       }
-      if ((rc = radius_rows_on_device(c, "iss_keypoints", S.cloud.data(), n, border_radius))) return rc;
+      if ((rc = neighbour_rows(c, "iss_keypoints", v.cloud, n, 0, border_radius, rows))) return rc;
       ++waits;
-      HIP_TRY(c, launch_boundary_from_rows(S.cloud.data(), (int)n, d_normals, S.cloud.data(), (int)n, static_cast<const int32_t*>(S.idx.ptr), nullptr, 0,
-                                           static_cast<const int*>(S.row_start.ptr), min_neighbors, std::cos(angle_threshold), nullptr,
-                                           static_cast<int32_t*>(K.edge.ptr), nullptr, nullptr, c->stream));
-      HIP_TRY(c, launch_iss_border(S.cloud.data(), (int)n, sorted, cell_start, g, shells_of(c, border_radius), (float)(border_radius * border_radius),
-                                   static_cast<const int32_t*>(K.edge.ptr), static_cast<int32_t*>(K.border.ptr), c->stream));
+      HIP_TRY(c, launch_boundary_from_rows(v.cloud, v.n, d_normals, v.cloud, v.n, rows.idx, rows.n_found, rows.k, rows.row_start, min_neighbors,
+                                           std::cos(angle_threshold), nullptr, K.edge.as<int32_t>(), nullptr, nullptr, c->stream));
+      HIP_TRY(c, launch_iss_border(v.cloud, v.n, v.sorted, v.cell_start, v.g, v.shells(border_radius), (float)(border_radius * border_radius),
+                                   K.edge.as<const int32_t>(), K.border.as<int32_t>(), c->stream));
     }
-    d_border = static_cast<const int32_t*>(K.border.ptr);
+    d_border = K.border.as<const int32_t>();
   }
-  HIP_TRY(c, launch_iss_keypoints(S.cloud.data(), (int)n, S.n_finite > 0, sorted, cell_start, g, shells_of(c, salient_radius), r2_salient,
-                                  shells_of(c, non_max_radius), r2_non_max, min_neighbors, gamma_21, gamma_32, d_border,
-                                  static_cast<int32_t*>(K.n_salient.ptr), static_cast<double*>(K.scatter.ptr), static_cast<double*>(K.eig.ptr),
-                                  static_cast<double*>(K.saliency.ptr), static_cast<int*>(K.flags.ptr), static_cast<int*>(K.pos.ptr),
-                                  static_cast<int*>(K.scan.ptr), static_cast<float4*>(K.points.ptr), static_cast<int*>(K.kept.ptr), d_count,
-                                  c->stream));
+  HIP_TRY(c, launch_iss_keypoints(v.cloud, v.n, v.n_eval > 0, v.sorted, v.cell_start, v.g, v.shells(salient_radius), r2_salient,
+                                  v.shells(non_max_radius), r2_non_max, min_neighbors, gamma_21, gamma_32, d_border, K.n_salient.as<int32_t>(),
+                                  K.scatter.as<double>(), K.eig.as<double>(), K.saliency.as<double>(), K.comp.flags.as<int>(), K.comp.pos.as<int>(),
+                                  K.comp.scan.as<int>(), K.points.as<float4>(), K.comp.kept.as<int>(), K.ints.as<int>(), c->stream));
   int count = 0;
-  if ((rc = fetch_ints(c, d_count, 1, &count))) return rc;
+  if ((rc = fetch_ints(c, K.ints.as<int>(), 1, &count))) return rc;
   K.waits = waits;
   if (count < 0 || (size_t)count > n) return fail(c, ICPGPU_ERR_HIP, "iss_keypoints: %d keypoints of %zu points (internal error)", count, n);
   K.n = n;
@@ -147,7 +128,7 @@ int icpgpu_iss_fetch(icpgpu_ctx* c, size_t capacity_keypoints, int32_t* keypoint
   if (!K.have) return fail(c, ICPGPU_ERR_INVALID_ARG, "iss_fetch: no result (icpgpu_iss_keypoints)");
   if ((keypoint_index || keypoints_xyzw) && K.n_keypoints > capacity_keypoints)
     return fail(c, ICPGPU_ERR_INVALID_ARG, "iss_fetch: %zu keypoints, room for %zu", K.n_keypoints, capacity_keypoints);
-  const Delivery first[3] = {{keypoint_index, K.kept.ptr, keypoint_index ? K.n_keypoints * sizeof(int32_t) : 0},
+  const Delivery first[3] = {{keypoint_index, K.comp.kept.ptr, keypoint_index ? K.n_keypoints * sizeof(int32_t) : 0},
                              {keypoints_xyzw, K.points.ptr, keypoints_xyzw ? K.n_keypoints * sizeof(float4) : 0},
                              {n_salient, K.n_salient.ptr, n_salient ? K.n * sizeof(int32_t) : 0}};
   int rc;

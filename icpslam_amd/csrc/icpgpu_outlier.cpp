@@ -37,7 +37,7 @@ int build_knn_grid(icpgpu_ctx* c, const Cloud& cloud, GridIndex& G) {
   b.post = true;  // (the read-backs go through fetch_ints, as in build_grid)
   int rc = gb_begin(c, b, cloud, 0, /*cut=*/1.0, /*adapt=*/false, G, nullptr, kKnnPopulation, 0.0);
   while (!rc && b.state != GridBuild::Done) {
-    const int* d_ints = static_cast<const int*>(G.ints.ptr);
+    const int* d_ints = G.ints.as<const int>();
     if (b.state == GridBuild::WaitBbox) {
       if ((rc = fetch_ints(c, d_ints, 6, c->h_ints))) break;
       float lo[3], hi[3];
@@ -93,17 +93,14 @@ int outlier_filter(icpgpu_ctx* c, const float* xyzw, size_t n, const OutlierCall
   O.cloud.bbox_version = 0;
   O.cloud.finite_version = 0;
   if ((rc = ensure(c, O.measure, n * sizeof(float)))) return rc;
-  if ((rc = ensure(c, O.flags, n * sizeof(int)))) return rc;
-  if ((rc = ensure(c, O.pos, n * sizeof(int)))) return rc;
-  if ((rc = ensure(c, O.scan, exclusive_scan_scratch_ints(ni) * sizeof(int)))) return rc;
-  if ((rc = ensure(c, O.kept, n * sizeof(int)))) return rc;
+  if ((rc = ensure_compaction(c, O.comp, n))) return rc;
   if ((rc = ensure(c, O.far, (n + 2) * sizeof(int)))) return rc;
   if ((rc = ensure(c, O.ints, kOutlierInts * sizeof(int)))) return rc;
   if ((rc = ensure_stage(c, n * sizeof(float4), /*any_size=*/true))) return rc;  // (a filter's result is never longer than its input)
   const float4* d_cloud = O.cloud.data();
-  float* d_measure = static_cast<float*>(O.measure.ptr);
-  int* d_flags = static_cast<int*>(O.flags.ptr);
-  int* d_ints = static_cast<int*>(O.ints.ptr);
+  float* d_measure = O.measure.as<float>();
+  int* d_flags = O.comp.flags.as<int>();
+  int* d_ints = O.ints.as<int>();
   double* d_stats = reinterpret_cast<double*>(d_ints + 2);
   GridIndex& G = O.grid;
   G.built = G.usable = false;  // (version 0: a build never stands for the next call's cloud)
@@ -114,9 +111,8 @@ int outlier_filter(icpgpu_ctx* c, const float* xyzw, size_t n, const OutlierCall
       return fail(c, ICPGPU_ERR_INVALID_ARG, "statistical outlier removal: %d finite points, mean_k + 1 = %d needed", n_finite, q.mean_k + 1);
     if (!G.usable && n > (size_t)kGicpCovFarMost)
       return fail(c, ICPGPU_ERR_UNSUPPORTED, "statistical outlier removal: cannot index this cloud of %zu points", n);
-    HIP_TRY(c, launch_sor_distances(d_cloud, ni, G.usable ? static_cast<const float4*>(G.sorted.ptr) : nullptr,
-                                    static_cast<const int*>(G.cell_start.ptr), G.g, G.usable ? G.n_binned : 0, q.mean_k, d_measure,
-                                    static_cast<int*>(O.far.ptr), c->stream));
+    HIP_TRY(c, launch_sor_distances(d_cloud, ni, G.usable ? G.sorted.as<const float4>() : nullptr, G.cell_start.as<const int>(), G.g,
+                                    G.usable ? G.n_binned : 0, q.mean_k, d_measure, O.far.as<int>(), c->stream));
     HIP_TRY(c, launch_sor_flags(d_cloud, d_measure, ni, q.stddev_mult, q.negative, d_stats, d_flags, c->stream));
   } else {
     const float r2 = (float)(q.radius * q.radius);
@@ -129,11 +125,11 @@ int outlier_filter(icpgpu_ctx* c, const float* xyzw, size_t n, const OutlierCall
       }
       brute = !grid;
     }
-    HIP_TRY(c, launch_ror_counts(d_cloud, ni, grid ? static_cast<const float4*>(G.sorted.ptr) : nullptr, static_cast<const int*>(G.cell_start.ptr),
-                                 G.g, grid ? G.n_binned : 0, r2, q.min_pts, q.negative, brute, d_measure, d_flags, c->stream));
+    HIP_TRY(c, launch_ror_counts(d_cloud, ni, grid ? G.sorted.as<const float4>() : nullptr, G.cell_start.as<const int>(), G.g,
+                                 grid ? G.n_binned : 0, r2, q.min_pts, q.negative, brute, d_measure, d_flags, c->stream));
   }
-  HIP_TRY(c, launch_outlier_compact(d_cloud, ni, d_flags, static_cast<int*>(O.pos.ptr), static_cast<int*>(O.scan.ptr),
-                                    static_cast<float4*>(c->h_stage_dev), static_cast<int*>(O.kept.ptr), d_ints, c->stream));
+  HIP_TRY(c, launch_compact(d_flags, ni, O.comp.pos.as<int>(), O.comp.scan.as<int>(), O.comp.kept.as<int>(), d_ints, d_cloud,
+                            static_cast<float4*>(c->h_stage_dev), c->stream));
   int hv[10] = {0};
   const int n_ints = q.kind == kOutlierSor ? 10 : 1;
   if ((rc = fetch_ints(c, d_ints, n_ints, hv))) return rc;
@@ -224,7 +220,7 @@ int icpgpu_outlier_fetch(icpgpu_ctx* c, size_t capacity, float* measure, int32_t
   if (!measure && !kept_index) return ICPGPU_OK;  // (the sizes alone: what a caller asks first, to make room)
   if (O.n_in > capacity) return fail(c, ICPGPU_ERR_INVALID_ARG, "outlier_fetch: %zu points, room for %zu", O.n_in, capacity);
   if (measure && O.n_in) HIP_TRY(c, hipMemcpyAsync(measure, O.measure.ptr, O.n_in * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (kept_index && O.n_kept) HIP_TRY(c, hipMemcpyAsync(kept_index, O.kept.ptr, O.n_kept * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (kept_index && O.n_kept) HIP_TRY(c, hipMemcpyAsync(kept_index, O.comp.kept.ptr, O.n_kept * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return ICPGPU_OK;
 }

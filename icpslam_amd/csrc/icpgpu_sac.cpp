@@ -93,7 +93,7 @@ int icpgpu_sac_plane_segmentation(icpgpu_ctx* c, double distance_threshold, int 
   int best_count = 0;
   if (n > 0 && max_iterations > 0) {
     if ((rc = ensure(c, K.batch, sizeof(SacBatch)))) return rc;
-    SacBatch* d_batch = static_cast<SacBatch*>(K.batch.ptr);
+    SacBatch* d_batch = K.batch.as<SacBatch>();
     SacBatch hb;
     double k = INFINITY;
     int t = 0;
@@ -127,30 +127,26 @@ int icpgpu_sac_plane_segmentation(icpgpu_ctx* c, double distance_threshold, int 
 
   if (K.best_t >= 0) {
     if (K.sample[0] < 0 || K.sample[0] >= ni) return fail(c, ICPGPU_ERR_HIP, "sac_plane_segmentation: sample %d of %d points (internal error)", K.sample[0], ni);
-    for (DeviceBuf* b : {&K.flags, &K.pos, &K.inliers})
-      if ((rc = ensure(c, *b, n * sizeof(int)))) return rc;
-    if ((rc = ensure(c, K.scan, exclusive_scan_scratch_ints(ni) * sizeof(int)))) return rc;
+    if ((rc = ensure_compaction(c, K.sel, n))) return rc;
     if ((rc = ensure(c, K.ints, 4 * sizeof(int)))) return rc;
     if ((rc = ensure(c, K.sums, 12 * sizeof(double)))) return rc;
-    int* d_flags = static_cast<int*>(K.flags.ptr);
-    int* d_pos = static_cast<int*>(K.pos.ptr);
-    int* d_scan = static_cast<int*>(K.scan.ptr);
-    int* d_inliers = static_cast<int*>(K.inliers.ptr);
-    int* d_ints = static_cast<int*>(K.ints.ptr);
+    const Compaction& C = K.sel;
     K.found = 1;
     K.n_unrefined = (size_t)best_count;  // (the selection below is the counting kernel's own test: the same number)
     for (int a = 0; a < 4; ++a) K.coeff[a] = K.coeff_unrefined[a];
-    HIP_TRY(c, launch_sac_select(S.cloud.data(), ni, K.coeff_unrefined, thr, d_flags, d_pos, d_scan, d_inliers, d_ints, c->stream));
+    HIP_TRY(c, launch_sac_select(S.cloud.data(), ni, K.coeff_unrefined, thr, C.flags.as<int>(), C.pos.as<int>(), C.scan.as<int>(), C.kept.as<int>(),
+                                 K.ints.as<int>(), c->stream));
     int m = best_count;
     if (optimize_coefficients && best_count >= 3) {
       double sums[12];
-      HIP_TRY(c, launch_sac_sums(S.cloud.data(), ni, d_inliers, best_count, K.sample[0], static_cast<double*>(K.sums.ptr), c->stream));
+      HIP_TRY(c, launch_sac_sums(S.cloud.data(), ni, C.kept.as<int>(), best_count, K.sample[0], K.sums.as<double>(), c->stream));
       if ((rc = copy_to_host(c, sums, K.sums.ptr, sizeof sums))) return rc;
       ++K.waits;
       for (int a = 0; a < 9; ++a) K.moments[a] = sums[a];
       refine_plane(sums, sums + 9, best_count, K.coeff_unrefined, K.coeff);
-      HIP_TRY(c, launch_sac_select(S.cloud.data(), ni, K.coeff, thr, d_flags, d_pos, d_scan, d_inliers, d_ints, c->stream));
-      if ((rc = fetch_ints(c, d_ints, 1, &m))) return rc;
+      HIP_TRY(c, launch_sac_select(S.cloud.data(), ni, K.coeff, thr, C.flags.as<int>(), C.pos.as<int>(), C.scan.as<int>(), C.kept.as<int>(),
+                                   K.ints.as<int>(), c->stream));
+      if ((rc = fetch_ints(c, K.ints.as<int>(), 1, &m))) return rc;
       ++K.waits;
       if (m < 0 || m > ni) return fail(c, ICPGPU_ERR_HIP, "sac_plane_segmentation: %d inliers of %d points (internal error)", m, ni);
     }
@@ -173,7 +169,7 @@ int icpgpu_sac_fetch(icpgpu_ctx* c, size_t capacity_inliers, size_t capacity_cou
     return fail(c, ICPGPU_ERR_INVALID_ARG, "sac_fetch: %zu inliers and %zu counts, room for %zu and %zu", K.n_inliers, K.counts.size(), capacity_inliers,
                 capacity_counts);
   if (inliers && K.n_inliers) {
-    const int rc = copy_to_host(c, inliers, K.inliers.ptr, K.n_inliers * sizeof(int32_t));
+    const int rc = copy_to_host(c, inliers, K.sel.kept.ptr, K.n_inliers * sizeof(int32_t));
     if (rc) return rc;
   }
   if (counts && !K.counts.empty()) std::memcpy(counts, K.counts.data(), K.counts.size() * sizeof(int32_t));
@@ -212,18 +208,16 @@ int sac_extract(icpgpu_ctx* c, int negative, float* out_xyzw, const float** view
   if (want == 0) return ICPGPU_OK;
   const int ni = (int)n;
   int rc;
-  for (DeviceBuf* b : {&K.xflags, &K.xpos, &K.kept})
-    if ((rc = ensure(c, *b, n * sizeof(int)))) return rc;
-  if ((rc = ensure(c, K.scan, exclusive_scan_scratch_ints(ni) * sizeof(int)))) return rc;
+  Compaction& C = K.ext;
+  if ((rc = ensure_compaction(c, C, n))) return rc;
   if ((rc = ensure(c, K.ints, 4 * sizeof(int)))) return rc;
   if ((rc = ensure_stage(c, want * sizeof(float4), /*any_size=*/true))) return rc;
-  int* d_flags = static_cast<int*>(K.xflags.ptr);
-  int* d_ints = static_cast<int*>(K.ints.ptr);
-  HIP_TRY(c, launch_sac_flags(S.cloud.data(), ni, K.coeff, K.thr, K.found != 0, negative != 0, d_flags, c->stream));
-  HIP_TRY(c, launch_outlier_compact(S.cloud.data(), ni, d_flags, static_cast<int*>(K.xpos.ptr), static_cast<int*>(K.scan.ptr),
-                                    static_cast<float4*>(c->h_stage_dev), static_cast<int*>(K.kept.ptr), d_ints + 1, c->stream));
+  int* d_count = K.ints.as<int>() + 1;
+  HIP_TRY(c, launch_sac_flags(S.cloud.data(), ni, K.coeff, K.thr, K.found != 0, negative != 0, C.flags.as<int>(), c->stream));
+  HIP_TRY(c, launch_compact(C.flags.as<int>(), ni, C.pos.as<int>(), C.scan.as<int>(), C.kept.as<int>(), d_count, S.cloud.data(),
+                            static_cast<float4*>(c->h_stage_dev), c->stream));
   int m = 0;
-  if ((rc = fetch_ints(c, d_ints + 1, 1, &m))) return rc;
+  if ((rc = fetch_ints(c, d_count, 1, &m))) return rc;
   if ((size_t)m != want) return fail(c, ICPGPU_ERR_HIP, "sac_extract: %d points extracted, %zu expected (internal error)", m, want);
   if (view) *view_xyzw = static_cast<const float*>(c->h_stage);
   else if (out_xyzw) std::memcpy(out_xyzw, c->h_stage, want * sizeof(float4));

@@ -1,6 +1,9 @@
 // icpgpu_search.cpp -- host side of the neighbour search (pcl::search::KdTree / pcl::KdTreeFLANN: nearestKSearch, radiusSearch;
 // rules: include/icpgpu.h "neighbour search"; kernels: icp_search.hip) and of what runs over the search cloud: normal estimation
-// (icp_normals.hip), fast point feature histograms (icp_fpfh.hip) and euclidean clustering (icp_cluster.hip).
+// (icp_normals.hip), fast point feature histograms (icp_fpfh.hip) and euclidean clustering (icp_cluster.hip).  The steps every stage
+// over the search cloud takes are stated here once and declared in icp_ctx.h: view_of (the cloud as a kernel sees it, with the
+// shells rule; also icpgpu_iss.cpp and icpgpu_feature.cpp's alignment), stage_queries, check_k_or_radius and neighbour_rows (rows left
+// on the device; also icpgpu_boundary.cpp and icpgpu_iss.cpp) and deliver (results to the caller; every unit over the cloud).
 #include "icp_ctx.h"
 
 namespace icpgpu_impl {
@@ -14,18 +17,26 @@ int count_finite(const float* xyzw, size_t n) {
 
 }  // namespace
 
-// (SearchView and the helpers below are shared with icpgpu_boundary.cpp and icpgpu_iss.cpp: icp_ctx.h)
 SearchView view_of(const icpgpu_ctx* c) {
   const auto& S = c->search;
   SearchView v;
   v.cloud = S.cloud.data();
   v.n = (int)S.n;
+  v.n_eval = S.n_finite > 0 ? v.n : 0;
   if (S.n && S.grid.usable) {
-    v.sorted = static_cast<const float4*>(S.grid.sorted.ptr);
-    v.cell_start = static_cast<const int*>(S.grid.cell_start.ptr);
+    v.sorted = S.grid.sorted.as<const float4>();
+    v.cell_start = S.grid.cell_start.as<const int>();
     v.g = S.grid.g;
   }
   return v;
+}
+
+int check_k_or_radius(icpgpu_ctx* c, const char* what, int k, int min_k, double radius) {
+  const bool by_k = k != 0, by_radius = radius != 0.0;
+  if (by_k == by_radius) return fail(c, ICPGPU_ERR_INVALID_ARG, "%s: exactly one of k and radius must be set (k %d, radius %g)", what, k, radius);
+  if (by_k && (k < min_k || k > ICPGPU_SEARCH_MAX_K)) return fail(c, ICPGPU_ERR_INVALID_ARG, "%s: k %d outside %d..%d", what, k, min_k, ICPGPU_SEARCH_MAX_K);
+  if (by_radius && !(std::isfinite(radius) && radius > 0.0)) return fail(c, ICPGPU_ERR_INVALID_ARG, "%s: radius must be finite and > 0", what);
+  return ICPGPU_OK;
 }
 
 // the queries of a call in device memory: the caller's (uploaded into the call's scratch) or the search cloud's own points
@@ -42,7 +53,7 @@ int stage_queries(icpgpu_ctx* c, const char* what, const float* queries_xyzw, si
   int rc;
   if ((rc = ensure(c, S.queries, n_q * sizeof(float4)))) return rc;
   HIP_TRY(c, hipMemcpyAsync(S.queries.ptr, queries_xyzw, n_q * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-  d_queries = static_cast<const float4*>(S.queries.ptr);
+  d_queries = S.queries.as<const float4>();
   return ICPGPU_OK;
 }
 
@@ -69,17 +80,10 @@ int queue_radius_count(icpgpu_ctx* c, const float4* d_queries, size_t n_q, doubl
   if ((rc = reserve_radius_rows(c, n_q + 1))) return rc;
   const SearchView v = view_of(c);
   r2 = (float)(radius * radius);
-  // the cube of `shells` cells around a query's cell contains its ball (shells * h * kGridSafety >= radius: the grid search's bound);
-  // a ball of more than kSearchRadiusShells cells is searched without the grid
-  shells = -1;
-  if (v.sorted) {
-    const double s = std::ceil(radius / ((double)v.g.h * (double)kGridSafety));
-    if (s <= (double)kSearchRadiusShells) shells = (int)s;
-  }
-  HIP_TRY(c, launch_search_radius_count(d_queries, (int)n_q, v.cloud, S.n_finite > 0 ? v.n : 0, v.sorted, v.cell_start, v.g, shells, r2, max_nn,
-                                        static_cast<int*>(S.counts.ptr), static_cast<int*>(S.longs.ptr), static_cast<int*>(S.row_start.ptr),
-                                        static_cast<int*>(S.scratch_start.ptr), static_cast<int*>(S.scan.ptr),
-                                        static_cast<unsigned long long*>(S.totals.ptr), static_cast<long long*>(S.row_start64.ptr), c->stream));
+  shells = v.shells(radius);
+  HIP_TRY(c, launch_search_radius_count(d_queries, (int)n_q, v.cloud, v.n_eval, v.sorted, v.cell_start, v.g, shells, r2, max_nn, S.counts.as<int>(),
+                                        S.longs.as<int>(), S.row_start.as<int>(), S.scratch_start.as<int>(), S.scan.as<int>(),
+                                        S.totals.as<unsigned long long>(), S.row_start64.as<long long>(), c->stream));
   return ICPGPU_OK;
 }
 
@@ -91,9 +95,30 @@ int queue_radius_fill(icpgpu_ctx* c, const float4* d_queries, size_t n_q, int sh
   if ((rc = ensure(c, S.d2, total * sizeof(float)))) return rc;
   if ((rc = ensure(c, S.scratch, std::max<size_t>(scratch_words, 1) * sizeof(unsigned long long)))) return rc;
   const SearchView v = view_of(c);
-  HIP_TRY(c, launch_search_radius_fill(d_queries, (int)n_q, v.cloud, v.n, v.sorted, v.cell_start, v.g, shells, r2, static_cast<int*>(S.row_start.ptr),
-                                       static_cast<int*>(S.scratch_start.ptr), static_cast<unsigned long long*>(S.scratch.ptr),
-                                       static_cast<int32_t*>(S.idx.ptr), static_cast<float*>(S.d2.ptr), c->stream));
+  HIP_TRY(c, launch_search_radius_fill(d_queries, (int)n_q, v.cloud, v.n, v.sorted, v.cell_start, v.g, shells, r2, S.row_start.as<int>(),
+                                       S.scratch_start.as<int>(), S.scratch.as<unsigned long long>(), S.idx.as<int32_t>(), S.d2.as<float>(),
+                                       c->stream));
+  return ICPGPU_OK;
+}
+
+// what launch_search_knn writes for `rows` queries of k neighbours each
+int reserve_knn_rows(icpgpu_ctx* c, size_t rows, int k) {
+  auto& S = c->search;
+  int rc;
+  if ((rc = ensure(c, S.idx, rows * (size_t)k * sizeof(int32_t)))) return rc;
+  if ((rc = ensure(c, S.d2, rows * (size_t)k * sizeof(float)))) return rc;
+  if ((rc = ensure(c, S.n_found, rows * sizeof(int32_t)))) return rc;
+  return ensure(c, S.far, (rows + 2) * sizeof(int));
+}
+
+// One k-nearest search, queued, its rows left on the device: S.idx / S.d2 with stride k, the lengths in S.n_found.  No host wait.
+int knn_rows_on_device(icpgpu_ctx* c, const float4* d_points, size_t n_points, int k) {
+  auto& S = c->search;
+  int rc;
+  if ((rc = reserve_knn_rows(c, n_points, k))) return rc;
+  const SearchView v = view_of(c);
+  HIP_TRY(c, launch_search_knn(d_points, (int)n_points, v.cloud, v.n, v.sorted, v.cell_start, v.g, k, S.idx.as<int32_t>(), S.d2.as<float>(),
+                               S.n_found.as<int32_t>(), S.far.as<int>(), c->stream));
   return ICPGPU_OK;
 }
 
@@ -112,6 +137,22 @@ int radius_rows_on_device(icpgpu_ctx* c, const char* what, const float4* d_point
   if (totals[0]) return queue_radius_fill(c, d_points, n_points, shells, r2, (size_t)totals[0], (size_t)totals[1]);
   if ((rc = ensure(c, S.idx, sizeof(int32_t)))) return rc;  // (every row is empty: nothing is read through the pointers)
   return ensure(c, S.d2, sizeof(float));
+}
+
+int neighbour_rows(icpgpu_ctx* c, const char* what, const float4* d_points, size_t n_points, int k, double radius, NeighbourRows& rows,
+                   size_t reserve_points) {
+  auto& S = c->search;
+  int rc;
+  if (k) {
+    if (reserve_points > n_points && (rc = reserve_knn_rows(c, reserve_points, k))) return rc;
+    if ((rc = knn_rows_on_device(c, d_points, n_points, k))) return rc;
+    rows = {S.idx.as<int32_t>(), S.d2.as<float>(), S.n_found.as<int32_t>(), k, nullptr, S.n_found.ptr};
+  } else {
+    if (reserve_points > n_points && (rc = reserve_radius_rows(c, reserve_points + 1))) return rc;
+    if ((rc = radius_rows_on_device(c, what, d_points, n_points, radius))) return rc;
+    rows = {S.idx.as<int32_t>(), S.d2.as<float>(), nullptr, 0, S.row_start.as<int>(), S.counts.ptr};
+  }
+  return ICPGPU_OK;
 }
 
 // (Delivery: icp_ctx.h)  Results on their way to the caller's (pageable) arrays: up to three device arrays copied into consecutive slices of the pinned
@@ -192,23 +233,17 @@ int icpgpu_search_size(const icpgpu_ctx* c, size_t* n, size_t* n_finite) {
 // One wait per call (deliver): the kernels, the rows into the staging buffer, the stream.
 int icpgpu_search_knn(icpgpu_ctx* c, const float* queries_xyzw, size_t n_q, int k, int32_t* idx, float* d2, int32_t* n_found) {
   ENTER(c);
-  auto& S = c->search;
   const float4* d_queries = nullptr;
   int rc;
   if (k < 1 || k > ICPGPU_SEARCH_MAX_K) return fail(c, ICPGPU_ERR_INVALID_ARG, "search_knn: k %d outside 1..%d", k, ICPGPU_SEARCH_MAX_K);
   if ((rc = stage_queries(c, "search_knn", queries_xyzw, n_q, d_queries))) return rc;
   if (n_q == 0) return ICPGPU_OK;
   if (!idx || !d2) return fail(c, ICPGPU_ERR_INVALID_ARG, "search_knn: null result pointer");
+  NeighbourRows rows;
+  if ((rc = neighbour_rows(c, "search_knn", d_queries, n_q, k, 0.0, rows))) return rc;
   const size_t cells = n_q * (size_t)k;
-  if ((rc = ensure(c, S.idx, cells * sizeof(int32_t)))) return rc;
-  if ((rc = ensure(c, S.d2, cells * sizeof(float)))) return rc;
-  if ((rc = ensure(c, S.n_found, n_q * sizeof(int32_t)))) return rc;
-  if ((rc = ensure(c, S.far, (n_q + 2) * sizeof(int)))) return rc;
-  const SearchView v = view_of(c);
-  HIP_TRY(c, launch_search_knn(d_queries, (int)n_q, v.cloud, v.n, v.sorted, v.cell_start, v.g, k, static_cast<int32_t*>(S.idx.ptr),
-                               static_cast<float*>(S.d2.ptr), static_cast<int32_t*>(S.n_found.ptr), static_cast<int*>(S.far.ptr), c->stream));
-  const Delivery out[3] = {{idx, S.idx.ptr, cells * sizeof(int32_t)}, {d2, S.d2.ptr, cells * sizeof(float)},
-                           {n_found, S.n_found.ptr, n_found ? n_q * sizeof(int32_t) : 0}};
+  const Delivery out[3] = {{idx, rows.idx, cells * sizeof(int32_t)}, {d2, rows.d2, cells * sizeof(float)},
+                           {n_found, rows.n_found, n_found ? n_q * sizeof(int32_t) : 0}};
   return deliver(c, out, 3);
 }
 
@@ -255,10 +290,7 @@ int icpgpu_normal_estimation(icpgpu_ctx* c, const float* queries_xyzw, size_t n_
   auto& S = c->search;
   const float4* d_queries = nullptr;
   int rc;
-  const bool by_k = k != 0, by_radius = radius != 0.0;
-  if (by_k == by_radius) return fail(c, ICPGPU_ERR_INVALID_ARG, "normal_estimation: exactly one of k and radius must be set (k %d, radius %g)", k, radius);
-  if (by_k && (k < 1 || k > ICPGPU_SEARCH_MAX_K)) return fail(c, ICPGPU_ERR_INVALID_ARG, "normal_estimation: k %d outside 1..%d", k, ICPGPU_SEARCH_MAX_K);
-  if (by_radius && !(std::isfinite(radius) && radius > 0.0)) return fail(c, ICPGPU_ERR_INVALID_ARG, "normal_estimation: radius must be finite and > 0");
+  if ((rc = check_k_or_radius(c, "normal_estimation", k, 1, radius))) return rc;
   float vp[3] = {0.f, 0.f, 0.f};
   if (viewpoint3) {
     for (int a = 0; a < 3; ++a) vp[a] = viewpoint3[a];
@@ -269,40 +301,14 @@ int icpgpu_normal_estimation(icpgpu_ctx* c, const float* queries_xyzw, size_t n_
   if (!out_nxyzc) return fail(c, ICPGPU_ERR_INVALID_ARG, "normal_estimation: null result pointer");
   if ((rc = ensure(c, S.normals, n_q * sizeof(float4)))) return rc;
   if (moments9 && (rc = ensure(c, S.moments, n_q * 9 * sizeof(float)))) return rc;
-  float* d_moments = moments9 ? static_cast<float*>(S.moments.ptr) : nullptr;
+  float* d_moments = moments9 ? S.moments.as<float>() : nullptr;
   const SearchView v = view_of(c);
-  const void* d_counts = nullptr;
-  if (by_k) {
-    const size_t cells = n_q * (size_t)k;
-    if ((rc = ensure(c, S.idx, cells * sizeof(int32_t)))) return rc;
-    if ((rc = ensure(c, S.d2, cells * sizeof(float)))) return rc;
-    if ((rc = ensure(c, S.n_found, n_q * sizeof(int32_t)))) return rc;
-    if ((rc = ensure(c, S.far, (n_q + 2) * sizeof(int)))) return rc;
-    HIP_TRY(c, launch_search_knn(d_queries, (int)n_q, v.cloud, v.n, v.sorted, v.cell_start, v.g, k, static_cast<int32_t*>(S.idx.ptr),
-                                 static_cast<float*>(S.d2.ptr), static_cast<int32_t*>(S.n_found.ptr), static_cast<int*>(S.far.ptr), c->stream));
-    HIP_TRY(c, launch_normals_from_rows(d_queries, (int)n_q, v.cloud, v.n, static_cast<const int32_t*>(S.idx.ptr), static_cast<const int32_t*>(S.n_found.ptr),
-                                        k, nullptr, vp, static_cast<float4*>(S.normals.ptr), d_moments, c->stream));
-    d_counts = S.n_found.ptr;
-  } else {
-    int shells;
-    float r2;
-    if ((rc = queue_radius_count(c, d_queries, n_q, radius, 0, shells, r2))) return rc;
-    unsigned long long totals[2] = {0, 0};
-    const Delivery first[1] = {{totals, S.totals.ptr, sizeof totals}};
-    if ((rc = deliver(c, first, 1))) return rc;
-    if (totals[0] > (unsigned long long)INT32_MAX || totals[1] > (unsigned long long)INT32_MAX)
-      return fail(c, ICPGPU_ERR_UNSUPPORTED, "normal_estimation: %llu neighbours in all, more than the int32 scans carry", totals[0]);
-    if (totals[0]) {
-      if ((rc = queue_radius_fill(c, d_queries, n_q, shells, r2, (size_t)totals[0], (size_t)totals[1]))) return rc;
-    } else if ((rc = ensure(c, S.idx, sizeof(int32_t)))) {  // (every row is empty: nothing is read through the pointer)
-      return rc;
-    }
-    HIP_TRY(c, launch_normals_from_rows(d_queries, (int)n_q, v.cloud, v.n, static_cast<const int32_t*>(S.idx.ptr), nullptr, 0,
-                                        static_cast<const int*>(S.row_start.ptr), vp, static_cast<float4*>(S.normals.ptr), d_moments, c->stream));
-    d_counts = S.counts.ptr;
-  }
+  NeighbourRows rows;
+  if ((rc = neighbour_rows(c, "normal_estimation", d_queries, n_q, k, radius, rows))) return rc;
+  HIP_TRY(c, launch_normals_from_rows(d_queries, (int)n_q, v.cloud, v.n, rows.idx, rows.n_found, rows.k, rows.row_start, vp, S.normals.as<float4>(),
+                                      d_moments, c->stream));
   const Delivery out[3] = {{out_nxyzc, S.normals.ptr, n_q * sizeof(float4)},
-                           {n_neighbours, d_counts, n_neighbours ? n_q * sizeof(int32_t) : 0},
+                           {n_neighbours, rows.counts, n_neighbours ? n_q * sizeof(int32_t) : 0},
                            {moments9, d_moments, moments9 ? n_q * 9 * sizeof(float) : 0}};
   return deliver(c, out, 3);
 }
@@ -317,74 +323,31 @@ int icpgpu_fpfh_estimation(icpgpu_ctx* c, const float* normals_nxyzc, const floa
   auto& S = c->search;
   const float4* d_queries = nullptr;
   int rc;
-  const bool by_k = k != 0, by_radius = radius != 0.0;
-  if (by_k == by_radius) return fail(c, ICPGPU_ERR_INVALID_ARG, "fpfh_estimation: exactly one of k and radius must be set (k %d, radius %g)", k, radius);
-  if (by_k && (k < 2 || k > ICPGPU_SEARCH_MAX_K)) return fail(c, ICPGPU_ERR_INVALID_ARG, "fpfh_estimation: k %d outside 2..%d", k, ICPGPU_SEARCH_MAX_K);
-  if (by_radius && !(std::isfinite(radius) && radius > 0.0)) return fail(c, ICPGPU_ERR_INVALID_ARG, "fpfh_estimation: radius must be finite and > 0");
+  if ((rc = check_k_or_radius(c, "fpfh_estimation", k, 2, radius))) return rc;
   if ((rc = stage_queries(c, "fpfh_estimation", queries_xyzw, n_q, d_queries))) return rc;
   const size_t n = S.n;
   if (n && !normals_nxyzc) return fail(c, ICPGPU_ERR_INVALID_ARG, "fpfh_estimation: null normals for a search cloud of %zu points", n);
   if (n_q && !out_fpfh) return fail(c, ICPGPU_ERR_INVALID_ARG, "fpfh_estimation: null result pointer");
   if (n_q == 0) return ICPGPU_OK;
   const bool own = !queries_xyzw;  // the queries' rows are the cloud's own rows
-  const size_t most = std::max(n, n_q);
   if ((rc = ensure(c, S.fpfh_normals, std::max<size_t>(n, 1) * sizeof(float4)))) return rc;
   if ((rc = ensure(c, S.spfh, std::max<size_t>(n, 1) * ICPGPU_FPFH_BINS * sizeof(float)))) return rc;
   if ((rc = ensure(c, S.fpfh, std::max<size_t>(n_q, 1) * ICPGPU_FPFH_BINS * sizeof(float)))) return rc;
   if (n) HIP_TRY(c, hipMemcpyAsync(S.fpfh_normals.ptr, normals_nxyzc, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
   const SearchView v = view_of(c);
-  const float4* d_normals = static_cast<const float4*>(S.fpfh_normals.ptr);
-  float* d_spfh = static_cast<float*>(S.spfh.ptr);
-  float* d_fpfh = static_cast<float*>(S.fpfh.ptr);
-  const void* d_counts = nullptr;
-  if (by_k) {
-    const size_t cells = most * (size_t)k;
-    if ((rc = ensure(c, S.idx, cells * sizeof(int32_t)))) return rc;
-    if ((rc = ensure(c, S.d2, cells * sizeof(float)))) return rc;
-    if ((rc = ensure(c, S.n_found, most * sizeof(int32_t)))) return rc;
-    if ((rc = ensure(c, S.far, (most + 2) * sizeof(int)))) return rc;
-    int32_t* d_idx = static_cast<int32_t*>(S.idx.ptr);
-    float* d_d2 = static_cast<float*>(S.d2.ptr);
-    int32_t* d_found = static_cast<int32_t*>(S.n_found.ptr);
-    if (n) {
-      HIP_TRY(c, launch_search_knn(v.cloud, (int)n, v.cloud, v.n, v.sorted, v.cell_start, v.g, k, d_idx, d_d2, d_found, static_cast<int*>(S.far.ptr), c->stream));
-      HIP_TRY(c, launch_spfh_from_rows(v.cloud, v.n, d_normals, d_idx, d_found, k, nullptr, d_spfh, c->stream));
-    }
-    if (!own)
-      HIP_TRY(c, launch_search_knn(d_queries, (int)n_q, v.cloud, v.n, v.sorted, v.cell_start, v.g, k, d_idx, d_d2, d_found, static_cast<int*>(S.far.ptr), c->stream));
-    HIP_TRY(c, launch_fpfh_from_rows(d_queries, (int)n_q, v.n, d_spfh, d_idx, d_d2, d_found, k, nullptr, d_fpfh, c->stream));
-    d_counts = S.n_found.ptr;
-  } else {
-    if ((rc = reserve_radius_rows(c, most + 1))) return rc;
-    // one search: its rows into S.idx / S.d2 (CSR by S.row_start), after the wait for the totals that size them
-    auto rows_of = [&](const float4* d_points, size_t n_points) -> int {
-      int shells;
-      float r2;
-      int rc2;
-      if ((rc2 = queue_radius_count(c, d_points, n_points, radius, 0, shells, r2))) return rc2;
-      unsigned long long totals[2] = {0, 0};
-      const Delivery first[1] = {{totals, S.totals.ptr, sizeof totals}};
-      if ((rc2 = deliver(c, first, 1))) return rc2;
-      if (totals[0] > (unsigned long long)INT32_MAX || totals[1] > (unsigned long long)INT32_MAX)
-        return fail(c, ICPGPU_ERR_UNSUPPORTED, "fpfh_estimation: %llu neighbours in all, more than the int32 scans carry", totals[0]);
-      if (totals[0]) return queue_radius_fill(c, d_points, n_points, shells, r2, (size_t)totals[0], (size_t)totals[1]);
-      if ((rc2 = ensure(c, S.idx, sizeof(int32_t)))) return rc2;  // (every row is empty: nothing is read through the pointers)
-      return ensure(c, S.d2, sizeof(float));
-    };
-    if (n) {
-      if ((rc = rows_of(v.cloud, n))) return rc;
-      HIP_TRY(c, launch_spfh_from_rows(v.cloud, v.n, d_normals, static_cast<const int32_t*>(S.idx.ptr), nullptr, 0, static_cast<const int*>(S.row_start.ptr),
-                                       d_spfh, c->stream));
-    }
-    if (!own) {
-      if ((rc = rows_of(d_queries, n_q))) return rc;
-    }
-    HIP_TRY(c, launch_fpfh_from_rows(d_queries, (int)n_q, v.n, d_spfh, static_cast<const int32_t*>(S.idx.ptr), static_cast<const float*>(S.d2.ptr), nullptr, 0,
-                                     static_cast<const int*>(S.row_start.ptr), d_fpfh, c->stream));
-    d_counts = S.counts.ptr;
+  float* d_spfh = S.spfh.as<float>();
+  float* d_fpfh = S.fpfh.as<float>();
+  NeighbourRows rows;
+  if (n) {  // (reserved for the longer of the two searches before the first: a buffer that grows is freed first, which waits)
+    if ((rc = neighbour_rows(c, "fpfh_estimation", v.cloud, n, k, radius, rows, n_q))) return rc;
+    HIP_TRY(c, launch_spfh_from_rows(v.cloud, v.n, S.fpfh_normals.as<const float4>(), rows.idx, rows.n_found, rows.k, rows.row_start, d_spfh, c->stream));
   }
+  if (!own) {
+    if ((rc = neighbour_rows(c, "fpfh_estimation", d_queries, n_q, k, radius, rows))) return rc;
+  }
+  HIP_TRY(c, launch_fpfh_from_rows(d_queries, (int)n_q, v.n, d_spfh, rows.idx, rows.d2, rows.n_found, rows.k, rows.row_start, d_fpfh, c->stream));
   const Delivery out[3] = {{out_fpfh, d_fpfh, n_q * ICPGPU_FPFH_BINS * sizeof(float)},
-                           {n_neighbours, d_counts, n_neighbours ? n_q * sizeof(int32_t) : 0},
+                           {n_neighbours, rows.counts, n_neighbours ? n_q * sizeof(int32_t) : 0},
                            {spfh, d_spfh, spfh ? n * ICPGPU_FPFH_BINS * sizeof(float) : 0}};
   return deliver(c, out, 3);
 }
@@ -415,16 +378,10 @@ int icpgpu_euclidean_cluster_extraction(icpgpu_ctx* c, double tolerance, int min
   if ((rc = ensure(c, K.counts, 2 * sizeof(int)))) return rc;
   const SearchView v = view_of(c);
   const float r2 = (float)(tolerance * tolerance);
-  int shells = -1;  // (as queue_radius_count: the cube of `shells` cells contains the ball, or the whole cloud is swept)
-  if (v.sorted) {
-    const double s = std::ceil(tolerance / ((double)v.g.h * (double)kGridSafety));
-    if (s <= (double)kSearchRadiusShells) shells = (int)s;
-  }
-  HIP_TRY(c, launch_cluster_extract(v.cloud, v.n, S.n_finite > 0, v.sorted, v.cell_start, v.g, shells, r2, min_size, max_size,
-                                    static_cast<int*>(K.parent.ptr), static_cast<int*>(K.sizes.ptr), static_cast<int*>(K.component.ptr),
-                                    static_cast<int*>(K.labels.ptr), static_cast<int*>(K.rank_of.ptr), static_cast<int*>(K.csize.ptr),
-                                    static_cast<int*>(K.cstart.ptr), static_cast<long long*>(K.cstart64.ptr), static_cast<int*>(K.keys.ptr),
-                                    static_cast<int*>(K.vals.ptr), static_cast<int*>(K.scratch.ptr), static_cast<int*>(K.counts.ptr), c->stream));
+  HIP_TRY(c, launch_cluster_extract(v.cloud, v.n, v.n_eval > 0, v.sorted, v.cell_start, v.g, v.shells(tolerance), r2, min_size, max_size,
+                                    K.parent.as<int>(), K.sizes.as<int>(), K.component.as<int>(), K.labels.as<int>(), K.rank_of.as<int>(),
+                                    K.csize.as<int>(), K.cstart.as<int>(), K.cstart64.as<long long>(), K.keys.as<int>(), K.vals.as<int>(),
+                                    K.scratch.as<int>(), K.counts.as<int>(), c->stream));
   int counts[2] = {0, 0};
   const Delivery out[1] = {{counts, K.counts.ptr, sizeof counts}};
   if ((rc = deliver(c, out, 1))) return rc;
@@ -447,7 +404,7 @@ int icpgpu_cluster_fetch(icpgpu_ctx* c, size_t capacity_clusters, size_t capacit
     return fail(c, ICPGPU_ERR_INVALID_ARG, "cluster_fetch: %zu clusters of %zu points, room for %zu and %zu", K.n_clusters, K.n_clustered,
                 capacity_clusters, indices ? capacity_indices : (size_t)0);
   const Delivery out[4] = {{cluster_start, K.cstart64.ptr, (K.n_clusters + 1) * sizeof(int64_t)},
-                           {indices, static_cast<const int*>(K.vals.ptr) + K.n, K.n_clustered * sizeof(int32_t)},
+                           {indices, K.vals.as<const int>() + K.n, K.n_clustered * sizeof(int32_t)},
                            {labels, K.labels.ptr, labels ? K.n * sizeof(int32_t) : 0},
                            {component, K.component.ptr, component ? K.n * sizeof(int32_t) : 0}};
   return deliver(c, out, 4);

@@ -198,6 +198,21 @@ def test_ror_sizes(ctx, n):
             check_ror(ctx, cloud, radius, min_pts, negative=(min_pts == 5), ref_k=k)
 
 
+@pytest.mark.parametrize("n", [4095, 4096, 4097])
+def test_ror_sizes_around_the_compactions_tile(ctx, n):
+    """The compaction's scan works in tiles of 4096 flags (icp_scan.hip): a tile less one flag, one tile, a tile and one flag -- the
+    last point is kept by exactly one of the two calls."""
+    cloud = scan(4097)[:n]
+    k = R.ror_counts(cloud, 0.3)
+    kept = 0
+    for negative in (False, True):
+        check_ror(ctx, cloud, 0.3, 5, negative, ref_k=k)
+        got = ctx.outlier_fetch()
+        assert 1000 < got["kept"].size < n - 1000 and got["kept"].size + got["removed"].size == n
+        kept += got["kept"].size
+    assert kept == n
+
+
 def test_ror_lattice_pins_strict_less(ctx):
     """Spacing exactly 0.25, radius 0.25: d2 == r2 is not a neighbour."""
     g = np.arange(8, dtype=np.float32) * np.float32(0.25)

@@ -84,6 +84,25 @@ def test_sizes(ctx, n):
         assert got["found"] == 1
 
 
+@pytest.mark.parametrize("n", [4095, 4096, 4097])
+def test_sizes_around_the_compactions_tile(ctx, n):
+    """The compaction's scan works in tiles of 4096 flags (icp_scan.hip): a tile less one flag, one tile, a tile and one flag, for the
+    inlier list of a refined segmentation and for both extractions -- the last point is kept by exactly one of the two."""
+    cloud = scan(4097)[:n]
+    ctx.search_set_input(cloud)
+    got = check(ctx, cloud, 0.2, 50, 0.99, 0, True)
+    assert got["found"] == 1 and got["n_unrefined"] >= 3 and 1000 < got["inliers"].size < n - 1000
+    mask = np.zeros(n, bool)
+    mask[got["inliers"]] = True
+    for negative in (False, True):
+        want = R.extract(cloud, got["inliers"], negative)
+        assert want.tobytes() == cloud[mask != negative].tobytes()
+        for view in (False, True):
+            assert ctx.sac_extract(negative, view).tobytes() == want.tobytes()
+    rc, f = ctx.sac_fetch_raw(got["inliers"].size, got["iterations"])                # the extracts left the result alone
+    assert rc == 0 and np.array_equal(f["inliers"], got["inliers"])
+
+
 SLAB_SEED = 2
 
 
