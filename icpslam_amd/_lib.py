@@ -112,6 +112,7 @@ EXPORTS = [
     "icpgpu_scp_align", "icpgpu_scp_fetch", "icpgpu_scp_stats",
     "icpgpu_iss_keypoints", "icpgpu_iss_fetch", "icpgpu_iss_stats",
     "icpgpu_boundary_estimation", "icpgpu_iss_keypoints_border", "icpgpu_iss_fetch_border",
+    "icpgpu_moving_least_squares", "icpgpu_mls_fetch", "icpgpu_mls_stats",
     "icpgpu_sac_plane_segmentation", "icpgpu_sac_fetch", "icpgpu_sac_stats", "icpgpu_sac_extract", "icpgpu_sac_extract_view",
     "icpgpu_set_source_normals", "icpgpu_set_p2plane_symmetric", "icpgpu_get_p2plane_symmetric",
     "icpgpu_reduce_symmetric_point_to_plane", "icpgpu_solve_symmetric_point_to_plane",
@@ -235,6 +236,9 @@ def load():
     L.icpgpu_boundary_estimation.argtypes = [vp, fp, fp, C.c_size_t, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_uint8), ip, ip, ip]
     L.icpgpu_iss_keypoints_border.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, fp, C.c_double, szp]
     L.icpgpu_iss_fetch_border.argtypes = [vp, ip, ip]
+    L.icpgpu_moving_least_squares.argtypes = [vp, fp, C.c_size_t, C.c_double, C.c_int, C.c_double, fp, fp, ip, szp]
+    L.icpgpu_mls_fetch.argtypes = [vp, C.c_size_t, ip, ip, dp, dp]
+    L.icpgpu_mls_stats.argtypes = [vp, ip]
     L.icpgpu_sac_extract.argtypes = [vp, C.c_int, fp, szp]
     L.icpgpu_sac_extract_view.argtypes = [vp, C.c_int, C.POINTER(fp), szp]
     L.icpgpu_scp_align.argtypes = [vp, fp, C.c_size_t, fp, fp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64, fp, szp, fp, ip, fp]

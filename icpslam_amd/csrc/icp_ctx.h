@@ -16,6 +16,7 @@
 //   icpgpu_boundary.cpp boundary estimation over the search cloud
 //   icpgpu_sac.cpp      plane segmentation (RANSAC) over the search cloud and ExtractIndices over its result
 //   icpgpu_iss.cpp      ISS keypoints over the search cloud, with and without border estimation
+//   icpgpu_mls.cpp      moving least squares over the search cloud's radius rows
 //   icpgpu_feature.cpp  feature-space k-nearest and the sample-consensus alignment over it
 // (until round 4 all of this was one 3 200-line icpgpu_api.cpp).
 #pragma once
@@ -493,6 +494,20 @@ struct icpgpu_ctx {
     Compaction comp;                              // comp.kept / points: the keypoints
     DeviceBuf points, ints;
   } iss;
+  // moving least squares (icpgpu_mls.cpp, icp_mls.hip): the last call's per-query record and its scratch, in buffers no other call
+  // writes -- an unfetched record outlives later search, normal, FPFH, clustering, segmentation, sample-consensus and ISS calls;
+  // icpgpu_search_set_input drops it.  The rows go through the search calls' scratch, as a normal estimation's do.
+  struct Mls {
+    bool have = false;
+    size_t n_q = 0, n_out = 0;
+    int waits = 0;
+    DeviceBuf n_neighbours, status, plane, coeff;   // per query: what icpgpu_mls_fetch returns
+    DeviceBuf sums, frame, fit, points, normals;    // per query: scratch
+    Compaction comp;                                // comp.kept: the kept queries' indices
+    DeviceBuf out_points, out_normals, ints;
+    std::vector<float> h_points, h_normals;         // the compacted results on the host: n_q slots arrive, n_out reach the caller
+    std::vector<int32_t> h_index;
+  } mls;
   std::vector<icpgpu_ctx*> workers;  // align_batch: one sub-context (own stream + scratch) per host worker thread
   DeviceBuf batch_table;             // lock-step batch: the BatchPair table of the group this context leads
   std::atomic<size_t> batch_table_cells{0};   // align_batch: the largest cell table any worker has needed (icpgpu_index.cpp)

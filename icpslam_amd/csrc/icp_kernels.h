@@ -591,6 +591,18 @@ hipError_t launch_iss_keypoints(const float4* cloud, int n, bool any_finite, con
 hipError_t launch_iss_border(const float4* cloud, int n, const float4* sorted, const int* cell_start, const GridDesc& g, int shells, float r2,
                              const int32_t* edge, int32_t* border, hipStream_t stream);
 
+// ---- moving least squares (icp_mls.hip): pcl::MovingLeastSquares over the search cloud's radius rows ---------------------------------
+// Per query, from its CSR row (idx by row_start, as launch_search_radius_fill leaves it): n_neighbours, status, plane7 (n_q x 7),
+// coeff10 (n_q x 10), the projected point and the normal with the curvature (points / normals, n_q float4 each); the kept queries
+// (status != 0) in query order: their indices into kept, their points and normals into out_points / out_normals, their number into
+// *n_kept (launch_compact).  order: 0 .. 3; s: the weights' squared Gaussian parameter.  sums9 (n_q x 9), frame12 (n_q x 12) and
+// fit (n_q x mls_fit_doubles(order)) are scratch.  n_q = 0 writes *n_kept alone.
+size_t mls_fit_doubles(int order);
+hipError_t launch_mls(const float4* queries, int n_q, const float4* cloud, int n, const int32_t* idx, const int* row_start, int order, double s,
+                      int32_t* n_neighbours, double* sums9, double* frame12, double* fit, int32_t* status, double* plane7, double* coeff10,
+                      float4* points, float4* normals, int* flags, int* pos, int* scan_scratch, int* kept, int* n_kept, float4* out_points,
+                      float4* out_normals, hipStream_t stream);
+
 // ---- plane segmentation (icp_sac.hip): pcl::SACSegmentation's RANSAC over the search cloud ---------------------------------------
 // A batch of kSacBatch hypotheses t0 .. t0 + 63 (hypothesis t0 + h is lane h's): the model kernel fills plane / sample and sets
 // count to 0, or to -1 for an INVALID hypothesis (and for t >= max_iterations), the counting kernel adds the inliers.  thr: the

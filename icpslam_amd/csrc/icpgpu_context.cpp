@@ -668,7 +668,7 @@ int icpgpu_destroy(icpgpu_ctx* c) {
                        &c->map.uflags, &c->map.urank, &c->map.uniq_index, &c->map.uniq.buf})
     release(*b);
   for (DeviceBuf* b : {&c->outlier.cloud.buf, &c->outlier.measure, &c->outlier.far, &c->outlier.ints}) release(*b);
-  for (Compaction* C : {&c->outlier.comp, &c->sac.sel, &c->sac.ext, &c->scp.sel, &c->iss.comp}) release(*C);
+  for (Compaction* C : {&c->outlier.comp, &c->sac.sel, &c->sac.ext, &c->scp.sel, &c->iss.comp, &c->mls.comp}) release(*C);
   for (DeviceBuf* b : {&c->search.cloud.buf, &c->search.queries, &c->search.idx, &c->search.d2, &c->search.n_found, &c->search.far,
                        &c->search.counts, &c->search.longs, &c->search.row_start, &c->search.scratch_start, &c->search.scan,
                        &c->search.scratch, &c->search.totals, &c->search.row_start64, &c->search.normals, &c->search.moments,
@@ -684,6 +684,9 @@ int icpgpu_destroy(icpgpu_ctx* c) {
     release(*b);
   for (DeviceBuf* b : {&c->iss.n_salient, &c->iss.scatter, &c->iss.eig, &c->iss.saliency, &c->iss.points, &c->iss.ints, &c->iss.normals, &c->iss.edge,
                        &c->iss.border})
+    release(*b);
+  for (DeviceBuf* b : {&c->mls.n_neighbours, &c->mls.status, &c->mls.plane, &c->mls.coeff, &c->mls.sums, &c->mls.frame, &c->mls.fit, &c->mls.points,
+                       &c->mls.normals, &c->mls.out_points, &c->mls.out_normals, &c->mls.ints})
     release(*b);
   for (DeviceBuf* b : {&c->feature.target, &c->feature.query, &c->feature.finite, &c->feature.idx, &c->feature.d2, &c->feature.n_found})
     release(*b);

@@ -3,7 +3,7 @@
 // (icp_normals.hip), fast point feature histograms (icp_fpfh.hip) and euclidean clustering (icp_cluster.hip).  The steps every stage
 // over the search cloud takes are stated here once and declared in icp_ctx.h: view_of (the cloud as a kernel sees it, with the
 // shells rule; also icpgpu_iss.cpp and icpgpu_feature.cpp's alignment), stage_queries, check_k_or_radius and neighbour_rows (rows left
-// on the device; also icpgpu_boundary.cpp and icpgpu_iss.cpp) and deliver (results to the caller; every unit over the cloud).
+// on the device; also icpgpu_boundary.cpp, icpgpu_iss.cpp and icpgpu_mls.cpp) and deliver (results to the caller; every unit over the cloud).
 #include "icp_ctx.h"
 
 namespace icpgpu_impl {
@@ -190,7 +190,7 @@ extern "C" {
 
 // Copies the cloud and builds its k-NN grid.  Nothing of the context's source, target, their grids, the covariances, the NDT cells
 // or the filters' results is touched; the previous search cloud, and a clustering,
-// plane segmentation or sample-consensus alignment result over it, is gone whatever this call returns.
+// plane segmentation, sample-consensus alignment, ISS or moving least squares result over it, is gone whatever this call returns.
 int icpgpu_search_set_input(icpgpu_ctx* c, const float* xyzw, size_t n) {
   ENTER(c);
   auto& S = c->search;
@@ -202,6 +202,7 @@ int icpgpu_search_set_input(icpgpu_ctx* c, const float* xyzw, size_t n) {
   c->sac.have = false;                   // (and so is a plane segmentation)
   c->scp.have = false;                   // (and a sample-consensus alignment)
   c->iss.have = false;                   // (and the ISS keypoints)
+  c->mls.have = false;                   // (and the moving least squares record)
   if (n && !xyzw) return fail(c, ICPGPU_ERR_INVALID_ARG, "null cloud pointer with n = %zu", n);
   if (n > (size_t)INT32_MAX - 4096) return fail(c, ICPGPU_ERR_INVALID_ARG, "cloud too large: %zu points", n);
   if (n) {

@@ -833,6 +833,60 @@ class Context:
         out["n_keypoints"] = m
         return out
 
+    # moving least squares (pcl::MovingLeastSquares, UpsamplingMethod NONE; rules: include/icpgpu.h) ---------------------------------
+    def moving_least_squares_raw(self, queries, radius: float, order: int = 2, sqr_gauss_param: float = 0.0, n_q=None,
+                                 want_normals: bool = True) -> tuple:
+        """One icpgpu_moving_least_squares call into arrays of n_q entries pre-filled with -2: (rc, n_out, points (n_q, 4) float32,
+        normals (n_q, 4) float32 or None, index (n_q,) int32); the per-query record stays in the context.  queries None: the search
+        cloud's own points (n_q then defaults to its size)."""
+        q = None if queries is None else _as_cloud(queries)
+        if n_q is None and q is None:
+            n_c = C.c_size_t()
+            self._L.icpgpu_search_size(self._h, C.byref(n_c), None)  # (0 without a search cloud)
+            n_q = n_c.value
+        n_q = q.shape[0] if n_q is None else int(n_q)
+        points = np.full((n_q, 4), -2, np.float32)
+        normals = np.full((n_q, 4), -2, np.float32) if want_normals else None
+        index = np.full(n_q, -2, np.int32)
+        n_out = C.c_size_t()
+        rc = self._L.icpgpu_moving_least_squares(self._h, None if q is None else _fp(q), n_q, float(radius), int(order), float(sqr_gauss_param),
+                                                 _fp(points), None if normals is None else _fp(normals),
+                                                 index.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n_out))
+        return rc, int(n_out.value), points, normals, index
+
+    def mls_fetch_raw(self, capacity: int, want=("status", "n_neighbours", "plane7", "coeff10")) -> tuple:
+        """One icpgpu_mls_fetch call into arrays of `capacity` entries pre-filled with -2: (rc, dict of the outputs named in `want`; the
+        others get NULL)."""
+        cap = int(capacity)
+        shapes = {"status": ((cap,), np.int32), "n_neighbours": ((cap,), np.int32), "plane7": ((cap, 7), np.float64),
+                  "coeff10": ((cap, 10), np.float64)}
+        out = {name: np.full(shape, -2, dtype) for name, (shape, dtype) in shapes.items() if name in want}
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+
+        def ptr(name, kind):
+            return out[name].ctypes.data_as(kind) if name in out else None
+
+        rc = self._L.icpgpu_mls_fetch(self._h, cap, ptr("status", ip), ptr("n_neighbours", ip), ptr("plane7", dp), ptr("coeff10", dp))
+        return rc, out
+
+    def mls_stats(self) -> int:
+        """The host waits of the last moving_least_squares call."""
+        waits = C.c_int32(-1)
+        self._check(self._L.icpgpu_mls_stats(self._h, C.byref(waits)))
+        return int(waits.value)
+
+    def moving_least_squares(self, radius: float, order: int = 2, sqr_gauss_param: float = 0.0, queries=None, want_record: bool = False):
+        """The queries (None: the search cloud's own points) projected onto a polynomial of `order` fitted to their radius neighbourhood
+        in the search cloud: (points (m, 4) float32, normals (m, 4) float32 {nx, ny, nz, curvature}, index (m,) int32 -- the kept
+        queries, in order).  want_record: a fourth item, dict(status, n_neighbours, plane7, coeff10) per query (icpgpu_mls_fetch)."""
+        rc, m, points, normals, index = self.moving_least_squares_raw(queries, radius, order, sqr_gauss_param)
+        self._check(rc)
+        if not want_record:
+            return points[:m].copy(), normals[:m].copy(), index[:m].copy()
+        rc, record = self.mls_fetch_raw(len(index))
+        self._check(rc)
+        return points[:m].copy(), normals[:m].copy(), index[:m].copy(), record
+
     # plane segmentation (pcl::SACSegmentation, pcl::ExtractIndices; rules: include/icpgpu.h) ----------------------------------
     def sac_segment_raw(self, distance_threshold: float, max_iterations: int = 50, probability: float = 0.99, seed: int = 0,
                         optimize_coefficients: bool = True, axis=None, eps_angle: float = 0.0) -> tuple:

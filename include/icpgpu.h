@@ -59,7 +59,7 @@ extern "C" {
  * icpgpu_normal_estimation, and euclidean clustering -- icpgpu_euclidean_cluster_extraction, icpgpu_cluster_fetch, and plane segmentation --
  * icpgpu_sac_plane_segmentation, icpgpu_sac_fetch, icpgpu_sac_stats, icpgpu_sac_extract, icpgpu_sac_extract_view, and ISS keypoints --
  * icpgpu_iss_keypoints, icpgpu_iss_fetch, icpgpu_iss_stats, icpgpu_iss_keypoints_border, icpgpu_iss_fetch_border, and boundary
- * estimation -- icpgpu_boundary_estimation, and fast point feature histograms -- icpgpu_fpfh_estimation, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
+ * estimation -- icpgpu_boundary_estimation, and moving least squares -- icpgpu_moving_least_squares, icpgpu_mls_fetch, icpgpu_mls_stats, and fast point feature histograms -- icpgpu_fpfh_estimation, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
  * icpgpu_set_p2plane_symmetric, icpgpu_get_p2plane_symmetric, icpgpu_reduce_symmetric_point_to_plane,
  * icpgpu_solve_symmetric_point_to_plane, ICPGPU_REJECT_SURFACE_NORMAL (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
@@ -1173,6 +1173,81 @@ int icpgpu_iss_keypoints_border(icpgpu_ctx* ctx, double salient_radius, double n
                                 int min_neighbors, double border_radius, double angle_threshold,
                                 const float* normals_nxyzc /* n float4 or NULL */, double normal_radius, size_t* n_keypoints);
 int icpgpu_iss_fetch_border(icpgpu_ctx* ctx, int32_t* edge /* n, may be NULL */, int32_t* border /* n, may be NULL */);
+
+/* ---- moving least squares (added under 1.2) ------------------------------------------------------------------------- */
+/* replaces pcl::MovingLeastSquares<PointXYZ, PointNormal> (PCL 1.8, surface/impl/mls.hpp) with UpsamplingMethod NONE: setInputCloud,
+ * setSearchRadius, setPolynomialOrder / setPolynomialFit, setSqrGaussParam, setComputeNormals, process, getCorrespondingIndices --
+ * "every point moved onto a weighted polynomial fitted to its radius neighbourhood, the normal taken from the fit", the stage in front
+ * of icpgpu_normal_estimation on a scan with range noise.  The context's SEARCH CLOUD (icpgpu_search_set_input) is the surface.
+ * queries_xyzw == NULL means the search cloud's own points, in their order (n_q must then be 0 or n): PCL's case.  Given queries are
+ * projected onto the cloud's surface; PCL has no spelling for this.  Parity with PCL binaries is unpinned; tests/mls_restated.py is
+ * what the kernels are compared with, bit for bit.  Every operation below is a float64 IEEE operation rounded on its own (no fused
+ * multiply-add), in the order written; float32 inputs are widened first.
+ * ARGUMENTS.  radius is finite and > 0.  order is in 0 .. ICPGPU_MLS_MAX_ORDER; orders 0 and 1 mean the plane projection alone
+ * (setPolynomialFit(false), and later PCL's "order > 1" rule).  sqr_gauss_param -- s below -- is 0 or finite and > 0; 0 means radius *
+ * radius, PCL's default.  out_nxyzc may be NULL (setComputeNormals(false)).  ICPGPU_ERR_INVALID_ARG: anything else; no search cloud;
+ * null queries with n_q neither 0 nor n; with n_q > 0 a null out_xyzw, out_index or n_out.  n_q = 0 is ICPGPU_OK with *n_out = 0.
+ * The rows' entries beyond INT32_MAX in all: ICPGPU_ERR_UNSUPPORTED, as for the other consumers of rows.
+ * ROW.  The row of query i is icpgpu_search_radius(radius, max_nn = 0)'s row, the same set in the same order: the finite cloud points
+ * with d2 < r2, strict, r2 = (float)(radius * radius), ascending by (d2, index).  m is its length, j_0 its first entry.  A non-finite
+ * query has an empty row.
+ * WSUM.  Every sum over a row is taken by one rule.  Entry t, counted from 0 in row order, is added into partial t mod 64; the 64
+ * partials start at +0.0 and each takes its entries in ascending t.  Then, for mask = 32, 16, 8, 4, 2, 1, every partial l becomes
+ * partial[l] + partial[l ^ mask], all 64 at once.  The sum is partial 0 (all 64 hold the same bits: IEEE addition commutes).
+ * PLANE (needs m >= 3).  K = cloud point j_0.  Per entry d = q - K per component, q the entry's cloud point.  Nine WSUMs in the order of
+ * normal estimation's a0 .. a8 -- dx dx, dx dy, dx dz, dy dy, dy dz, dz dz, dx, dy, dz -- each divided by (double)m.  Covariance:
+ * xx = a0 - a6 a6, xy = a1 - a6 a7, xz = a2 - a6 a8, yy = a3 - a7 a7, yz = a4 - a7 a8, zz = a5 - a8 a8.  Centroid c = (a6 + K.x,
+ * a7 + K.y, a8 + K.z).  The cyclic Jacobi of normal estimation (8 sweeps, the same expressions) runs on the covariance; lambda_min is
+ * the smallest diagonal entry, the lowest index among equals, and the plane's normal N that column of the eigenvector matrix, kept in
+ * double.  tr = (xx + yy) + zz; curvature = tr != 0 ? fabsf((float)(lambda_min / tr)) : 0.  With P the query and e = P - c:
+ * dist = (e.x N.x + e.y N.y) + e.z N.z, and Q = P - dist N per component is the query's projection onto the plane.
+ * DEVIATION: PCL takes the moments about the centroid in two passes and decomposes with eigen33.
+ * FRAME (Eigen's unitOrthogonal).  If |N.x| > 1e-12 |N.z| or |N.y| > 1e-12 |N.z|: inv = 1 / sqrt(N.x N.x + N.y N.y), V = (-N.y inv,
+ * N.x inv, 0).  Otherwise inv = 1 / sqrt(N.y N.y + N.z N.z), V = (0, -N.z inv, N.y inv).  U = N x V: (N.y V.z - N.z V.y, N.z V.x -
+ * N.x V.z, N.x V.y - N.y V.x).
+ * FIT (when order >= 2 and m >= nc = (order + 1)(order + 2) / 2).  Per entry: de = q - Q; dd = (de.x de.x + de.y de.y) + de.z de.z;
+ * w = EXP_NEG((-dd) / s); u = de . U, v = de . V, f = de . N, a dot being (x x' + y y') + z z'.  The monomials come in PCL's order --
+ * for ui in 0 .. order: for vi in 0 .. order - ui: P_j = u^ui v^vi -- the powers made by repeated multiplication from 1.0 (u^3 =
+ * ((1 u) u) u) and P_j their product; for order 2 that is 1, v, v^2, u, u v, u^2.  pw_a = P_a w.  A_ab = WSUM(pw_a P_b) for b <= a;
+ * b_a = WSUM(pw_a f).  DEVIATION: PCL rounds dd to float32 first and calls libm's exp.
+ * EXP_NEG(a), a <= 0.  NaN stays NaN; a < -708.0 gives 0.0.  Otherwise k = rint(a * 0x1.71547652b82fep+0); r = (a - k *
+ * 0x1.62e42feep-1) - k * 0x1.a39ef35793c76p-33; p = c_13, then p = p * r + c_n for n = 12 .. 0, c_n the double nearest 1 / n!; the
+ * result is ldexp(p, (int)k).  No libm exp: within 1 ulp of a correctly rounded one on [-708, 0], and EXP_NEG(0) = 1.
+ * SOLVE (A c = b by Cholesky).  For j = 0 .. nc - 1: s = A_jj, then s = s - L_jk L_jk for k < j ascending, L_jj = sqrt(s); for i > j:
+ * s = A_ij, then s = s - L_ik L_jk for k < j ascending, L_ij = s / L_jj.  Forward, for i = 0 .. nc - 1: s = b_i, then s = s - L_ik y_k
+ * for k < i ascending, y_i = s / L_ii.  Backward, for i = nc - 1 .. 0: s = y_i, then s = s - L_ki c_k for k > i ascending, c_i = s /
+ * L_ii.  Nothing is special-cased: a pivot that is not positive yields the NaN or infinity the arithmetic yields (a NaN's sign
+ * and payload are the processor's, not the rule's).
+ * RESULT.  status: 0 dropped (m < 3); 1 plane only (order 0 or 1, or m < nc); 2 polynomial; 3 fit refused.  When the fit ran and c_0
+ * is finite the status is 2, the point is Q + c_0 N and the normal (N - c_(order+1) U) - c_1 V, per component -- NOT normalised or
+ * oriented: PCL 1.8's NONE branch.  Otherwise the fit's status is 3, PCL's pcl_isfinite(c_vec[0]) rule.  With status 1 and 3 the
+ * point is Q and the normal N.
+ * OUTPUT.  The kept queries are those with status != 0, in query order.  out_xyzw: their points rounded to float32, w = 1.
+ * out_nxyzc: {nx, ny, nz, curvature}, the normal rounded to float32.  out_index: the query's index (PCL's
+ * corresponding_input_indices).  *n_out: their number.  The caller's arrays hold n_q entries; nothing is written past n_out.
+ * icpgpu_mls_fetch returns the last call's per-query record, any number of times; each pointer may be NULL: status and n_neighbours
+ * (m), n_q entries each; plane7 = {N.x, N.y, N.z, c.x, c.y, c.z, lambda_min}, NaN at status 0; coeff10 = c_0 .. c_(nc-1), then NaN
+ * up to 10, and all NaN unless the fit ran.  Without a result (none computed, the last call refused, or the search cloud replaced
+ * since) or with capacity < n_q the fetch returns ICPGPU_ERR_INVALID_ARG and writes nothing.  icpgpu_mls_stats reports the host
+ * waits of the last call, and is refused the same way without a result.
+ * HOST WAITS.  Two: the totals that size the rows, then the results; the kept count travels with the results.  (n_q = 0: none.)
+ * LIMITS.  A cloud the grid refuses and a radius of more than 8 grid cells are handled as in icpgpu_search_radius: the same bits.
+ * MEMORY.  O(n_q + the rows' entries); the order-3 fit keeps 65 doubles per query on the device.
+ * Not provided: upsampling methods (SAMPLE_LOCAL_PLANE, RANDOM_UNIFORM_DENSITY, VOXEL_GRID_DILATION, DISTINCT_CLOUD), setDilation*,
+ * setIndices, getMLSResults (icpgpu_mls_fetch returns this library's record instead), and k-nearest neighbourhoods (PCL's MLS has
+ * none either).
+ * ISOLATION.  The answers depend on the search cloud and the arguments alone.  The call leaves the source, the
+ * target, every grid, the covariances, the cached normals, the NDT cells, the filters' results and the search cloud as they were.
+ * Unfetched clustering, segmentation, sample-consensus and ISS results survive it, and its own record survives searches, normal,
+ * FPFH and boundary estimations, clusterings, segmentations, sample-consensus alignments and ISS calls: the rows go through the
+ * search calls' scratch, everything it keeps lives in buffers of its own.  icpgpu_search_set_input drops it, whatever it returns. */
+#define ICPGPU_MLS_MAX_ORDER 3
+int icpgpu_moving_least_squares(icpgpu_ctx* ctx, const float* queries_xyzw /* n_q float4 or NULL */, size_t n_q, double radius, int order,
+                                double sqr_gauss_param, float* out_xyzw /* n_q float4 */, float* out_nxyzc /* n_q float4, may be NULL */,
+                                int32_t* out_index /* n_q */, size_t* n_out);
+int icpgpu_mls_fetch(icpgpu_ctx* ctx, size_t capacity /* >= n_q */, int32_t* status /* n_q */, int32_t* n_neighbours /* n_q */,
+                     double* plane7 /* n_q x 7 */, double* coeff10 /* n_q x 10 */);
+int icpgpu_mls_stats(const icpgpu_ctx* ctx, int32_t* host_waits);
 
 /* ---- the mapper's target: a one-point-per-voxel map and its "nn cloud"  -------- */
 /* replaces OctreeMapper's pcl::octree::OctreePointCloudSearch map

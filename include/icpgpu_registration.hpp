@@ -1142,6 +1142,86 @@ class ISSKeypoint3D {
   PointIndices::Ptr indices_;
 };
 
+// pcl::MovingLeastSquares<PointInT, PointOutT>-shaped front end (rules and deviations: include/icpgpu.h, "moving least squares") -- the
+// smoothing in front of NormalEstimation on a scan with range noise:
+//   pcl::MovingLeastSquares<pcl::PointXYZ, pcl::PointNormal> mls;
+//     ->  icpgpu::MovingLeastSquares<pcl::PointCloud<pcl::PointXYZ>, pcl::PointCloud<pcl::PointNormal>> mls;
+//   mls.setInputCloud(cloud); mls.setSearchRadius(0.45); mls.setPolynomialOrder(2); mls.setComputeNormals(true);
+//   mls.process(smoothed); mls.getCorrespondingIndices();
+// The defaults are PCL's constructor's (radius 0, order 2, the squared Gaussian parameter the radius squared, no normals): process()
+// leaves the output empty until a radius is set, and after any refused call.  The output holds the kept points in the input's
+// order: x, y, z and -- where the output point type has them and setComputeNormals(true) was called -- normal_x, normal_y, normal_z
+// and curvature (not normalised: PCL 1.8).  setPolynomialFit(false) is order 0.  setUpsamplingMethod takes NONE alone; the other
+// methods, setDilation*, setIndices and getMLSResults are not provided.
+template <class CloudInT, class CloudOutT>
+class MovingLeastSquares {
+ public:
+  enum UpsamplingMethod { NONE, DISTINCT_CLOUD, SAMPLE_LOCAL_PLANE, RANDOM_UNIFORM_DENSITY, VOXEL_GRID_DILATION };
+  explicit MovingLeastSquares(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx), indices_(new PointIndices) {}
+  template <class CloudPtr>
+  void setInputCloud(const CloudPtr& cloud) { input_ = &*cloud; }
+  template <class TreePtr>
+  void setSearchMethod(const TreePtr&) {}  // accepted and ignored: the search is the library's own (exact)
+  void setSearchRadius(double radius) { radius_ = radius; }
+  double getSearchRadius() const { return radius_; }
+  void setPolynomialOrder(int order) { order_ = order; }
+  int getPolynomialOrder() const { return order_; }
+  void setPolynomialFit(bool polynomial_fit) { polynomial_fit_ = polynomial_fit; }
+  bool getPolynomialFit() const { return polynomial_fit_; }
+  void setSqrGaussParam(double sqr_gauss_param) { sqr_gauss_param_ = sqr_gauss_param; }
+  double getSqrGaussParam() const { return sqr_gauss_param_ == 0.0 ? radius_ * radius_ : sqr_gauss_param_; }
+  void setComputeNormals(bool compute_normals) { compute_normals_ = compute_normals; }
+  void setUpsamplingMethod(UpsamplingMethod method) {
+    if (method != NONE) throw std::invalid_argument("icpgpu::MovingLeastSquares: upsampling is not provided");
+  }
+  void process(CloudOutT& output) {
+    output.points.resize(0);
+    detail::set_cloud_shape(output, 0, 0);
+    indices_.reset(new PointIndices);
+    if (!input_) return;
+    static_assert(sizeof(input_->points[0]) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+    static_assert(sizeof(int) == sizeof(int32_t), "icpgpu: 32-bit int");
+    const std::size_t n = input_->points.size();
+    if (icpgpu_search_set_input(ctx_, n ? reinterpret_cast<const float*>(&input_->points[0]) : nullptr, n) != ICPGPU_OK) return;
+    std::vector<float> xyzw(4 * n), nxyzc(compute_normals_ ? 4 * n : 0);
+    indices_->indices.resize(n);
+    std::size_t m = 0;
+    if (icpgpu_moving_least_squares(ctx_, nullptr, n, radius_, polynomial_fit_ ? order_ : 0, sqr_gauss_param_, n ? &xyzw[0] : nullptr,
+                                    compute_normals_ && n ? &nxyzc[0] : nullptr, n ? reinterpret_cast<int32_t*>(&indices_->indices[0]) : nullptr,
+                                    &m) != ICPGPU_OK) {
+      indices_->indices.clear();
+      return;
+    }
+    indices_->indices.resize(m);
+    output.points.resize(m);
+    detail::set_cloud_shape(output, m, 0);
+    for (std::size_t i = 0; i < m; ++i) {
+      output.points[i].x = xyzw[4 * i];
+      output.points[i].y = xyzw[4 * i + 1];
+      output.points[i].z = xyzw[4 * i + 2];
+      if (compute_normals_) set_normal(output.points[i], &nxyzc[4 * i], 0);
+    }
+  }
+  // the last process()'s kept points as ascending indices into the input cloud (PCL's corresponding_input_indices)
+  PointIndices::ConstPtr getCorrespondingIndices() const { return indices_; }
+
+ private:
+  template <class P>
+  static auto set_normal(P& p, const float* v, int) -> decltype(p.normal_x = 0.f, p.normal_y = 0.f, p.normal_z = 0.f, p.curvature = 0.f, void()) {
+    p.normal_x = v[0], p.normal_y = v[1], p.normal_z = v[2], p.curvature = v[3];
+  }
+  template <class P>
+  static void set_normal(P&, const float*, long) {}
+
+  detail::ContextPtr ctx_holder_;
+  icpgpu_ctx* ctx_;
+  const CloudInT* input_ = nullptr;
+  double radius_ = 0.0, sqr_gauss_param_ = 0.0;
+  int order_ = 2;
+  bool polynomial_fit_ = true, compute_normals_ = false;
+  PointIndices::Ptr indices_;
+};
+
 // ISSKeypoint3D with PCL's border estimation (include/icpgpu.h, "ISS keypoints", BORDER ESTIMATION): setBorderRadius,
 // setNormalRadius, setNormals and setAngleThreshold work as in pcl::ISSKeypoint3D, and compute() refuses every keypoint within the
 // border radius of a boundary point of the cloud.  Beyond PCL: getEdgePoints() and getBorderPoints().  NormalCloudT: any cloud
