@@ -652,6 +652,7 @@ inline int ensure_compaction(icpgpu_ctx* c, Compaction& C, size_t n) {
 Xform to_xform(const Mat4d& T);
 Xform to_xform(const float* T);
 float threshold_from(double r2);
+float gate_threshold(const icpgpu_ctx* c);  // threshold_from(max_correspondence_distance^2): d2 <= thr is PCL's gate
 // n <= 32 ints from device memory, queued behind everything the stream holds, into host_dst -- returns when they are there
 // (a posted kernel + a polled mailbox instead of hipMemcpyAsync + hipStreamSynchronize: icp_kernels.hip post_ints_kernel)
 int fetch_ints(icpgpu_ctx* c, const int* d_src, int n, int* host_dst);
@@ -700,6 +701,7 @@ int resolve_sweep_timings(icpgpu_ctx* c, bool block = true);
 int resolve_cov_timing(icpgpu_ctx* c);  // icpgpu_gicp.cpp
 double wait_timeout_ms();
 bool flags_ready(const volatile unsigned long long* pairs, int n_pairs, unsigned long long seq);
+void take_pairs(const icpgpu_ctx* c, int n, double* dst);  // the values of the mailbox's first n pairs (their tags have been checked)
 void take_sums(icpgpu_ctx* c);
 int wait_flags(icpgpu_ctx* c, const volatile unsigned long long* flags, int n_flags, unsigned long long seq);
 int wait_sums(icpgpu_ctx* c, unsigned long long seq);
@@ -715,6 +717,22 @@ int write_output_cloud(icpgpu_ctx* c, const Xform& T, float* out_xyzw);
 int output_cloud_issue(icpgpu_ctx* c, const Xform& T, float* out_xyzw, StageTicket& tk);
 int output_cloud_complete(icpgpu_ctx* c, StageTicket& tk, float* out_xyzw);
 void init_result(icpgpu_result* r);
+// ---- an alignment's host steps, each stated once (DESIGN.md section 6a lists who calls which, and what each method does itself) ----
+// the opening: an empty result record, the alignment counted, the last call's kernel timings read if they are in, this call's zeroed
+int call_begin(icpgpu_ctx* c, icpgpu_result* res);
+// nothing carried over from an earlier P2P_SVD / P2PLANE alignment: no search bound, no seed, no stage that "has run"
+void start_cold(icpgpu_ctx* c);
+// the one writer of c->final_T / have_final and of the record's transform, outcome and counts.  T as the method holds it: float64
+// (P2P_SVD, P2PLANE: the record gets it rounded) or float32 (GICP, NDT: the record gets its bits, the context gets it widened).
+void record_result(icpgpu_ctx* c, icpgpu_result* res, const Mat4d& T, bool converged, int iterations, int state, unsigned n_corr, double mse);
+void record_result(icpgpu_ctx* c, icpgpu_result* res, const float T[16], bool converged, int iterations, int state, unsigned n_corr, double mse);
+// getFitnessScore() from a point-to-point sweep's 17 sums: the mean squared distance, DBL_MAX without a pair
+inline double fitness_of(const double* sums) { return sums[0] > 0.0 ? sums[16] / sums[0] : DBL_MAX; }
+// the blocking tail: the aligned cloud, THEN the open-range fitness sweep (want_fitness), the timings, t_total_ms
+int cloud_then_fitness(icpgpu_ctx* c, const Xform& T, float* out_xyzw, bool want_fitness, icpgpu_result* res,
+                       std::chrono::steady_clock::time_point t_start);
+// one of the four methods by c->params.method
+int align_dispatch(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitness, icpgpu_result* res);
 int p2p_finish(icpgpu_ctx* c, P2PRun& r);
 int p2p_prepare(icpgpu_ctx* c, P2PRun& r, const float* guess, float* out_xyzw, int want_fitness, icpgpu_result* res);
 int p2p_begin(icpgpu_ctx* c, P2PRun& r, const float* guess, float* out_xyzw, int want_fitness, icpgpu_result* res);
@@ -745,6 +763,8 @@ int ensure_normals(icpgpu_ctx* c, bool of_target, const float4** out);
 inline bool source_normals_supplied(const icpgpu_ctx* c) { return c->nrm_src_user_version != 0 && c->nrm_src_user_version == c->src_version; }
 // icpgpu_reject.cpp
 int gated_keys(icpgpu_ctx* c, const Xform& T, float thr, unsigned long long* keys);
+// one iteration's keys: the gated search, the reciprocal stage (flag off: nothing), the chain (empty: nothing).  After reject_prepare.
+int correspondence_keys(icpgpu_ctx* c, const Xform& T, float thr, unsigned long long* keys);
 // keys path: the alignment's iterations go search -> reciprocal stage -> chain -> the method's keys reduction
 inline bool keys_stages(const icpgpu_ctx* c) { return c->n_rejectors > 0 || c->reciprocal; }
 int reciprocal_run(icpgpu_ctx* c, const Xform& T, unsigned long long* keys, float thr);

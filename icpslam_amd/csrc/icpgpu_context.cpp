@@ -87,6 +87,7 @@ float threshold_from(double r2) {
   if ((double)f > r2) f = std::nextafterf(f, -INFINITY);
   return f;
 }
+float gate_threshold(const icpgpu_ctx* c) { return threshold_from(c->params.max_correspondence_distance * c->params.max_correspondence_distance); }
 
 unsigned long long sample_fingerprint(const float* xyzw, size_t n) {
   unsigned long long s = 0;

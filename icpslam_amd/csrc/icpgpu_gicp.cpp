@@ -469,6 +469,14 @@ static bool gicp_fits_one_xcd(const icpgpu_ctx* c, int n_s, int nblk) {
 // at its waits (below).  Same kernels, same arguments, same host arithmetic in the same order => the same bits on either path
 // (tests/test_gpu_gicp.py compares); where the two differ on purpose, the call sites say so.
 
+// GICP keeps d2 < r^2 (strict): thr is the largest float below r^2, and d2 < thr_excl  <=>  d2 <= thr
+static void gicp_thresholds(const icpgpu_ctx* c, float* thr, float* thr_excl) {
+  const double r2 = c->params.max_correspondence_distance * c->params.max_correspondence_distance;
+  *thr = threshold_from(r2);
+  if ((double)*thr >= r2) *thr = std::nextafterf(*thr, -INFINITY);
+  *thr_excl = std::nextafterf(*thr, INFINITY);
+}
+
 // every registration starts cold, from the identity, with PCL's strict threshold
 static void gicp_state_begin(icpgpu_ctx* c, GicpState& s, const float* guess_in) {
   c->prev.valid = c->tile_seed.valid = false;
@@ -481,11 +489,7 @@ static void gicp_state_begin(icpgpu_ctx* c, GicpState& s, const float* guess_in)
   s.converged = false;
   s.n_corr = 0;
   s.mse = 0.0;
-  // GICP keeps d2 < r^2 (strict): the largest float below r^2
-  const double r2 = c->params.max_correspondence_distance * c->params.max_correspondence_distance;
-  s.thr = threshold_from(r2);
-  if ((double)s.thr >= r2) s.thr = std::nextafterf(s.thr, -INFINITY);
-  s.thr_excl = std::nextafterf(s.thr, INFINITY);  // d2 < thr_excl  <=>  d2 <= thr
+  gicp_thresholds(c, &s.thr, &s.thr_excl);
 }
 static void gicp_stamp_total(const GicpState& s) {
   s.res->t_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - s.t_start).count();
@@ -497,9 +501,8 @@ static void gicp_stamp_total(const GicpState& s) {
 static bool gicp_too_small(const icpgpu_ctx* c) {
   return c->tgt.n == 0 || cov_cloud_known_too_small(c->src, c->src_version) || cov_cloud_known_too_small(c->tgt, c->tgt_version);
 }
-static void gicp_finish_early(icpgpu_ctx* c) {
-  c->final_T = mat4_identity();
-  c->have_final = true;
+static void gicp_finish_early(icpgpu_ctx* c, const GicpState& s) {  // (s: as gicp_state_begin left it -- nothing has happened)
+  record_result(c, s.res, mat4_identity(), s.converged, s.nr, s.state, s.n_corr, s.mse);
 }
 
 // after the covariances: the search grid (adopts the one the target's covariances were computed over -- no build) and the scratch
@@ -627,14 +630,7 @@ static void gicp_outer_advance(icpgpu_ctx* c, GicpState& s, const Vec6& x) {
 // the registration is over: compose the result (fin) and write the record
 static void gicp_write_result(icpgpu_ctx* c, const GicpState& s, float fin[16]) {
   gicp_compose_final(s.previous, s.guess, fin);
-  std::memcpy(s.res->T, fin, 16 * sizeof(float));
-  for (int i = 0; i < 16; ++i) c->final_T[i] = (double)fin[i];
-  c->have_final = true;
-  s.res->converged = s.converged ? 1 : 0;
-  s.res->iterations = s.nr;
-  s.res->convergence_state = s.state;
-  s.res->n_correspondences = s.n_corr;
-  s.res->mse_last = s.mse;
+  record_result(c, s.res, fin, s.converged, s.nr, s.state, s.n_corr, s.mse);
 }
 
 // ---- align_gicp: the blocking driver ------------------------------------------------------------------------------------------------
@@ -888,7 +884,7 @@ static int gicp_prepare(icpgpu_ctx* c, GicpAlign& a, const float* guess_in, floa
   if (!small && (rc = ensure_covariances(c, c->src, c->src_version, c->cov_grid_src, c->cov_src, c->cov_src_version, /*allow_unchecked=*/true, nullptr, &small)))
     return rc;
   if (small) {
-    gicp_finish_early(c);
+    gicp_finish_early(c, s);
     rc = write_output_cloud(c, to_xform(c->final_T), out_xyzw);
     gicp_stamp_total(s);
     return rc ? rc : 1;
@@ -925,7 +921,7 @@ static int gicp_finish(icpgpu_ctx* c, GicpAlign& a, float* out_xyzw, int want_fi
     if ((rc = sweep_complete(c, tk))) return rc;
     if ((rc = resolve_sweep_timings(c))) return rc;
     a.dev_ms += c->dev_ms_accum;  // 0 when this sweep was not a timed one
-    res->fitness = c->h_sums[0] > 0.0 ? c->h_sums[16] / c->h_sums[0] : DBL_MAX;
+    res->fitness = fitness_of(c->h_sums);
   }
   gicp_mark(c, a, 7);
   if (!out_done && (rc = write_output_cloud(c, Tf, out_xyzw))) return rc;
@@ -948,6 +944,9 @@ int align_gicp(icpgpu_ctx* c, const float* guess_in, float* out_xyzw, int want_f
       if (c->spec_grid.pending) (void)covariance_grid_check(c);
     }
   } spec_guard{c};
+  // Not call_begin: this driver counts the alignment only once its resources are there, and takes its device time from its own
+  // events (a.dev_ms; gicp_finish reads the fitness sweep's through dev_ms_accum, which it zeroes itself) -- it never looks at the
+  // sweeps' timings or counts at its start.
   init_result(res);
   int rc;
   if ((rc = ensure_gicp_resources(c))) return rc;
@@ -1086,7 +1085,7 @@ void gicp_run_solver_launched(icpgpu_ctx*, GicpRun& r, hipStream_t solve_stream)
 
 // a cloud of fewer than k_correspondences_ finite points: the run ends as align_gicp ends (gicp_prepare)
 static void gicp_run_end_too_small(icpgpu_ctx* c, GicpRun& r) {
-  gicp_finish_early(c);
+  gicp_finish_early(c, r);
   gicp_stamp_total(r);
   r.phase = GicpRun::Done;
 }
@@ -1146,19 +1145,13 @@ int gicp_run_begin(icpgpu_ctx* c, GicpRun& r, int want_fitness, icpgpu_result* r
     r.phase = GicpRun::Blocking;
     return ICPGPU_OK;
   }
-  init_result(res);
-  c->prof.aligns += 1;
-  gicp_state_begin(c, r, /*guess_in=*/nullptr);  // (a run never takes a guess)
   {
-    int rc = resolve_sweep_timings(c, /*block=*/false);
+    const int rc = call_begin(c, res);
     if (rc) return rc;
-    c->dev_ms_accum = 0.0;
-    c->call_sweeps = c->call_timed = 0;
   }
+  gicp_state_begin(c, r, /*guess_in=*/nullptr);  // (a run never takes a guess)
   if (gicp_too_small(c)) {
-    gicp_finish_early(c);
-    gicp_stamp_total(r);
-    r.phase = GicpRun::Done;
+    gicp_run_end_too_small(c, r);
     return ICPGPU_OK;
   }
   r.cov_stage = 0;
@@ -1294,7 +1287,7 @@ int gicp_run_step(icpgpu_ctx* c, GicpRun& r) {
         return rc < 0 ? rc : 0;
       }
       if ((rc = sweep_complete(c, r.ticket))) return rc;
-      r.res->fitness = c->h_sums[0] > 0.0 ? c->h_sums[16] / c->h_sums[0] : DBL_MAX;
+      r.res->fitness = fitness_of(c->h_sums);
       if ((rc = resolve_sweep_timings(c, /*block=*/false))) return rc;
       r.res->t_device_ms = 0.0;  // (not sampled on this path)
       gicp_stamp_total(r);
@@ -1339,10 +1332,8 @@ int icpgpu_gicp_quadratic_sums(icpgpu_ctx* c, const float* T, double* sums150) {
   if ((rc = ensure_covariances(c, c->tgt, c->tgt_version, c->cov_grid_tgt, c->cov_tgt, c->cov_tgt_version, false, nullptr, &small))) return rc;
   if (!small && (rc = ensure_covariances(c, c->src, c->src_version, c->cov_grid_src, c->cov_src, c->cov_src_version, false, nullptr, &small))) return rc;
   if (small) return fail(c, ICPGPU_ERR_INVALID_ARG, "GICP needs at least %d finite points per cloud", kGicpK);
-  const double r2 = c->params.max_correspondence_distance * c->params.max_correspondence_distance;
-  float thr = threshold_from(r2);
-  if ((double)thr >= r2) thr = std::nextafterf(thr, -INFINITY);
-  const float thr_excl = std::nextafterf(thr, INFINITY);
+  float thr, thr_excl;
+  gicp_thresholds(c, &thr, &thr_excl);
   if ((rc = ensure_grid(c, thr))) return rc;
   if ((rc = ensure(c, c->keys, (size_t)n_s * sizeof(unsigned long long)))) return rc;
   auto* keys = static_cast<unsigned long long*>(c->keys.ptr);

@@ -379,7 +379,7 @@ int icpgpu_map_nn_target(icpgpu_ctx* c, const float* pose, const float* pose_inv
   // lowest-index tie-break would report on the full cloud.  (A later change of the correspondence gate simply rebuilds
   // the grid from the full cloud.)
   const int mode = c->params.nn_mode;
-  const float thr = threshold_from(c->params.max_correspondence_distance * c->params.max_correspondence_distance);
+  const float thr = gate_threshold(c);
   const double cut = std::sqrt((double)thr) * (1.0 + 1e-6);
   if (m > 0 && (mode == ICPGPU_NN_GRID || (mode == ICPGPU_NN_AUTO && (size_t)m >= kGridMinTarget)) && thr > 0.f && std::isfinite(cut) &&
       cut <= 1e6) {

@@ -549,12 +549,8 @@ static int ndt_step_mt(icpgpu_ctx* c, int iteration, double eps, double p[6], fl
 
 int align_ndt(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitness, icpgpu_result* res) {
   const auto t_start = std::chrono::steady_clock::now();
-  init_result(res);
-  c->prof.aligns += 1;
-  int rc = resolve_sweep_timings(c, /*block=*/false);
+  int rc = call_begin(c, res);
   if (rc) return rc;
-  c->dev_ms_accum = 0.0;
-  c->call_sweeps = c->call_timed = 0;
   c->ndt_probability = NAN;
   c->ndt_trace.clear();
   float Tf[16];
@@ -618,26 +614,11 @@ int align_ndt(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitne
     }
     c->ndt_probability = sums[1] / (double)n_s;
   }
-  Mat4d final_T;
-  for (int i = 0; i < 16; ++i) final_T[i] = (double)Tf[i];
-  c->final_T = final_T;
-  c->have_final = true;
-  std::memcpy(res->T, Tf, sizeof Tf);
-  res->converged = converged ? 1 : 0;
-  res->iterations = nr;
-  res->convergence_state = state;
-  res->n_correspondences = n_corr;
-  res->mse_last = NAN;
-  if ((rc = write_output_cloud(c, to_xform(Tf), out_xyzw))) return rc;
-  if (want_fitness && n_t > 0) {  // getFitnessScore(): the point-to-point sweep with an open range (icpgpu_fitness)
-    const icpgpu_params& P = c->params;
-    if ((rc = ensure_grid(c, threshold_from(P.max_correspondence_distance * P.max_correspondence_distance)))) return rc;
-    if ((rc = nn_and_reduce(c, to_xform(Tf), FLT_MAX, true))) return rc;
-    res->fitness = c->h_sums[0] > 0.0 ? c->h_sums[16] / c->h_sums[0] : DBL_MAX;
-  }
-  if ((rc = resolve_sweep_timings(c, /*block=*/false))) return rc;
-  res->t_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-  return ICPGPU_OK;
+  record_result(c, res, Tf, converged, nr, state, n_corr, /*mse=*/NAN);  // (NDT has no mean squared error to report)
+  const bool fitness = want_fitness && n_t > 0;
+  // the fitness sweep wants the search grid, which nothing of NDT has asked for (built, on a target's first call, ahead of the cloud)
+  if (fitness && (rc = ensure_grid(c, gate_threshold(c)))) return rc;
+  return cloud_then_fitness(c, to_xform(Tf), out_xyzw, fitness, res, t_start);
 }
 
 }  // namespace icpgpu_impl

@@ -127,13 +127,14 @@ bool flags_ready(const volatile unsigned long long* pairs, int n_pairs, unsigned
     if (!mailbox_read(pairs + 2 * k, seq, &bits)) return false;
   return true;
 }
-// ... into c->h_sums, where everybody reads them
-void take_sums(icpgpu_ctx* c) {
-  for (int k = 0; k < kReduceTerms; ++k) {
+void take_pairs(const icpgpu_ctx* c, int n, double* dst) {
+  for (int k = 0; k < n; ++k) {
     const unsigned long long bits = c->h_flags[2 * k];
-    std::memcpy(&c->h_sums[k], &bits, sizeof bits);
+    std::memcpy(&dst[k], &bits, sizeof bits);
   }
 }
+// ... into c->h_sums, where everybody reads them
+void take_sums(icpgpu_ctx* c) { take_pairs(c, kReduceTerms, c->h_sums); }
 
 // Spin on the mailbox flags until every term of sweep `seq` has landed.  The stream is queried now and then so that a
 // faulted kernel turns into an error instead of an endless wait, and the clock so that a hung one does.
@@ -339,6 +340,13 @@ static bool stage_direct() {
   return v;
 }
 
+// one transform kernel over n_s points in the profile: its event time, a read and a write of every point
+static void count_transform(icpgpu_ctx* c, float ms, uint64_t n_s) {
+  c->prof.transform_launches += 1;
+  c->prof.transform_ms += ms;
+  c->prof.transform_bytes += 32ull * n_s;
+}
+
 int output_cloud_issue(icpgpu_ctx* c, const Xform& T, float* out_xyzw, StageTicket& tk) {
   tk.issued = false;
   const int n_s = (int)c->src.n;
@@ -367,9 +375,7 @@ int output_cloud_complete(icpgpu_ctx* c, StageTicket& tk, float* out_xyzw) {
     te = hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
   }
   HIP_TRY(c, te);
-  c->prof.transform_launches += 1;
-  c->prof.transform_ms += ms;
-  c->prof.transform_bytes += 32ull * (uint64_t)n_s;
+  count_transform(c, ms, (uint64_t)n_s);
   return ICPGPU_OK;
 }
 
@@ -392,9 +398,7 @@ int write_output_cloud(icpgpu_ctx* c, const Xform& T, float* out_xyzw) {
   } else if ((rc = copy_to_host(c, out_xyzw, c->out.ptr, (size_t)n_s * sizeof(float4)))) return rc;
   float ms = 0.f;
   HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-  c->prof.transform_launches += 1;
-  c->prof.transform_ms += ms;
-  c->prof.transform_bytes += 32ull * (uint64_t)n_s;
+  count_transform(c, ms, (uint64_t)n_s);
   return ICPGPU_OK;
 }
 
@@ -402,6 +406,54 @@ void init_result(icpgpu_result* r) {
   std::memset(r, 0, sizeof(*r));
   for (int i = 0; i < 16; ++i) r->T[i] = (i % 5 == 0) ? 1.0f : 0.0f;
   r->fitness = NAN;
+}
+
+int call_begin(icpgpu_ctx* c, icpgpu_result* res) {
+  init_result(res);
+  c->prof.aligns += 1;
+  const int rc = resolve_sweep_timings(c, /*block=*/false);
+  if (rc) return rc;
+  c->dev_ms_accum = 0.0;
+  c->call_sweeps = c->call_timed = 0;
+  return ICPGPU_OK;
+}
+
+void start_cold(icpgpu_ctx* c) {
+  c->prev.valid = c->tile_seed.valid = false;
+  c->rej_ran = 0;
+  c->rcp_ran = false;
+}
+
+static void record_outcome(icpgpu_ctx* c, icpgpu_result* res, bool converged, int iterations, int state, unsigned n_corr, double mse) {
+  c->have_final = true;
+  res->converged = converged ? 1 : 0;
+  res->iterations = iterations;
+  res->convergence_state = state;
+  res->n_correspondences = n_corr;
+  res->mse_last = mse;
+}
+void record_result(icpgpu_ctx* c, icpgpu_result* res, const Mat4d& T, bool converged, int iterations, int state, unsigned n_corr, double mse) {
+  c->final_T = T;
+  mat4_to_float(T, res->T);
+  record_outcome(c, res, converged, iterations, state, n_corr, mse);
+}
+void record_result(icpgpu_ctx* c, icpgpu_result* res, const float T[16], bool converged, int iterations, int state, unsigned n_corr, double mse) {
+  for (int i = 0; i < 16; ++i) c->final_T[i] = (double)T[i];
+  std::memcpy(res->T, T, 16 * sizeof(float));
+  record_outcome(c, res, converged, iterations, state, n_corr, mse);
+}
+
+int cloud_then_fitness(icpgpu_ctx* c, const Xform& T, float* out_xyzw, bool want_fitness, icpgpu_result* res,
+                       std::chrono::steady_clock::time_point t_start) {
+  int rc = write_output_cloud(c, T, out_xyzw);
+  if (rc) return rc;
+  if (want_fitness) {  // getFitnessScore(): the point-to-point sweep with an open range (icpgpu_fitness)
+    if ((rc = nn_and_reduce(c, T, FLT_MAX, true))) return rc;
+    res->fitness = fitness_of(c->h_sums);
+  }
+  if ((rc = resolve_sweep_timings(c, /*block=*/false))) return rc;
+  res->t_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+  return ICPGPU_OK;
 }
 
 
@@ -430,17 +482,9 @@ int p2p_prepare(icpgpu_ctx* c, P2PRun& r, const float* guess, float* out_xyzw, i
   r.res = res;
   r.out_xyzw = out_xyzw;
   r.want_fitness = want_fitness;
-  init_result(res);
-  c->prof.aligns += 1;
-  {
-    int rc = resolve_sweep_timings(c, /*block=*/false);
-    if (rc) return rc;
-    c->dev_ms_accum = 0.0;
-    c->call_sweeps = c->call_timed = 0;
-    c->prev.valid = c->tile_seed.valid = false;  // every alignment starts cold
-    c->rej_ran = 0;
-    c->rcp_ran = false;
-  }
+  const int rc = call_begin(c, res);
+  if (rc) return rc;
+  start_cold(c);  // every alignment starts cold
   if (guess)
     for (int i = 0; i < 16; ++i) r.final_T[i] = (double)guess[i];
 
@@ -448,14 +492,13 @@ int p2p_prepare(icpgpu_ctx* c, P2PRun& r, const float* guess, float* out_xyzw, i
   // with converged_ = false and final_transformation_ = identity.
   if (c->tgt.n == 0) {
     r.final_T = mat4_identity();
-    c->final_T = r.final_T;
-    c->have_final = true;
+    record_result(c, res, r.final_T, r.converged, r.nr_iter, r.state, r.n_corr, r.mse);  // (a fresh run's: nothing happened)
     return p2p_finish(c, r);
   }
 
   const icpgpu_params& P = c->params;
   r.crit = ConvergenceCriteria(P.max_iterations, P.transformation_epsilon, P.euclidean_fitness_epsilon, P.force_iterations != 0);
-  r.thr = threshold_from(P.max_correspondence_distance * P.max_correspondence_distance);
+  r.thr = gate_threshold(c);
   return ICPGPU_OK;
 }
 
@@ -478,7 +521,7 @@ int p2p_advance(icpgpu_ctx* c, P2PRun& r, int* deferred) {
   if (rc) return rc;
   const double* sums = c->h_sums;
   if (r.phase == P2PRun::Fitness) {
-    r.res->fitness = sums[0] > 0.0 ? sums[16] / sums[0] : DBL_MAX;
+    r.res->fitness = fitness_of(sums);
     return p2p_finish(c, r);
   }
   const icpgpu_params& P = c->params;
@@ -509,14 +552,7 @@ int p2p_advance(icpgpu_ctx* c, P2PRun& r, int* deferred) {
     return sweep_issue(c, to_xform(r.final_T), r.thr, false, r.ticket);
   }
 
-  c->final_T = r.final_T;
-  c->have_final = true;
-  mat4_to_float(r.final_T, r.res->T);
-  r.res->converged = r.converged ? 1 : 0;
-  r.res->iterations = r.nr_iter;
-  r.res->convergence_state = r.state;
-  r.res->n_correspondences = r.n_corr;
-  r.res->mse_last = r.mse;
+  record_result(c, r.res, r.final_T, r.converged, r.nr_iter, r.state, r.n_corr, r.mse);
   if (r.want_fitness) {
     r.phase = P2PRun::Fitness;
     if (deferred) {
@@ -552,6 +588,28 @@ int align_p2p(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitne
   return rc;
 }
 
+int align_dispatch(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitness, icpgpu_result* res) {
+  return c->params.method == ICPGPU_GICP      ? align_gicp(c, guess, out_xyzw, want_fitness, res)
+         : c->params.method == ICPGPU_P2PLANE ? align_p2plane(c, guess, out_xyzw, want_fitness, res)
+         : c->params.method == ICPGPU_NDT     ? align_ndt(c, guess, out_xyzw, want_fitness, res)
+                                              : align_p2p(c, guess, out_xyzw, want_fitness, res);
+}
+
+// Where an alignment writes its record: the caller's struct when it is this library's, else one of our own, of which the caller
+// gets the leading bytes it knows (include/icpgpu.h, ABI rule) when the entry point is left.
+struct CallerResult {
+  icpgpu_ctx* c;
+  icpgpu_result* user_res;
+  icpgpu_result own;
+  icpgpu_result* res;
+  CallerResult(icpgpu_ctx* ctx, icpgpu_result* user) : c(ctx), user_res(user), res(ctx->abi_result == sizeof(icpgpu_result) ? user : &own) {}
+  ~CallerResult() {
+    if (res == user_res) return;
+    std::memset(user_res, 0, c->abi_result);
+    std::memcpy(user_res, res, std::min(c->abi_result, sizeof(own)));
+  }
+};
+
 }  // namespace icpgpu_impl
 
 extern "C" {
@@ -560,18 +618,8 @@ int icpgpu_align(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fi
   ENTER(c);
   if (!user_res) return fail(c, ICPGPU_ERR_INVALID_ARG, "result is null");
   if (!c->src.set || !c->tgt.set) return fail(c, ICPGPU_ERR_NO_INPUT, "align: source and target must be set first");
-  // a caller whose icpgpu_result is not this library's (include/icpgpu.h, ABI rule) gets the leading bytes it knows
-  icpgpu_result own;
-  icpgpu_result* res = c->abi_result == sizeof(icpgpu_result) ? user_res : &own;
-  const int rc = c->params.method == ICPGPU_GICP      ? align_gicp(c, guess, out_xyzw, want_fitness, res)
-                 : c->params.method == ICPGPU_P2PLANE ? align_p2plane(c, guess, out_xyzw, want_fitness, res)
-                 : c->params.method == ICPGPU_NDT     ? align_ndt(c, guess, out_xyzw, want_fitness, res)
-                                                      : align_p2p(c, guess, out_xyzw, want_fitness, res);
-  if (res != user_res) {
-    std::memset(user_res, 0, c->abi_result);
-    std::memcpy(user_res, res, std::min(c->abi_result, sizeof(own)));
-  }
-  return rc;
+  CallerResult r(c, user_res);
+  return align_dispatch(c, guess, out_xyzw, want_fitness, r.res);
 }
 
 // ICPGPU_GICP_DEVICE=auto: time both inner solvers of GICP on the clouds the context holds (align_gicp alternates and times while
@@ -601,11 +649,11 @@ int icpgpu_fitness(icpgpu_ctx* c, double max_range, double* out) {
   if (!out) return fail(c, ICPGPU_ERR_INVALID_ARG, "out is null");
   if (!c->src.set || !c->tgt.set) return fail(c, ICPGPU_ERR_NO_INPUT, "fitness: source and target must be set first");
   const Mat4d T = c->have_final ? c->final_T : mat4_identity();
-  int rc = ensure_grid(c, threshold_from(c->params.max_correspondence_distance * c->params.max_correspondence_distance));
+  int rc = ensure_grid(c, gate_threshold(c));
   if (rc) return rc;
   rc = nn_and_reduce(c, to_xform(T), threshold_from(max_range), true);
   if (rc) return rc;
-  *out = c->h_sums[0] > 0.0 ? c->h_sums[16] / c->h_sums[0] : DBL_MAX;
+  *out = fitness_of(c->h_sums);
   return ICPGPU_OK;
 }
 
@@ -619,8 +667,7 @@ int icpgpu_nn(icpgpu_ctx* c, const float* T, int32_t* idx, float* d2) {
   if (rc) return rc;
   if ((rc = ensure(c, c->idx, (size_t)n_s * sizeof(int32_t)))) return rc;
   if ((rc = ensure(c, c->d2, (size_t)n_s * sizeof(float)))) return rc;
-  if ((rc = ensure_grid(c, threshold_from(c->params.max_correspondence_distance * c->params.max_correspondence_distance))))
-    return rc;
+  if ((rc = ensure_grid(c, gate_threshold(c)))) return rc;
   auto* keys = static_cast<unsigned long long*>(c->keys.ptr);
   const Xform X = to_xform(T);
   const bool use_grid = grid_ready(c);
@@ -683,21 +730,13 @@ int icpgpu_align_view(icpgpu_ctx* c, const float* guess, int want_fitness, icpgp
   *view_xyzw = nullptr;
   *n_out = 0;
   if (!c->src.set || !c->tgt.set) return fail(c, ICPGPU_ERR_NO_INPUT, "align: source and target must be set first");
-  icpgpu_result own;
-  icpgpu_result* res = c->abi_result == sizeof(icpgpu_result) ? user_res : &own;
+  CallerResult r(c, user_res);
   struct ViewGuard {
     icpgpu_ctx* c;
     ~ViewGuard() { c->want_view = false; }
   } guard{c};
   c->want_view = true;
-  const int rc = c->params.method == ICPGPU_GICP      ? align_gicp(c, guess, nullptr, want_fitness, res)
-                 : c->params.method == ICPGPU_P2PLANE ? align_p2plane(c, guess, nullptr, want_fitness, res)
-                 : c->params.method == ICPGPU_NDT     ? align_ndt(c, guess, nullptr, want_fitness, res)
-                                                      : align_p2p(c, guess, nullptr, want_fitness, res);
-  if (res != user_res) {
-    std::memset(user_res, 0, c->abi_result);
-    std::memcpy(user_res, res, std::min(c->abi_result, sizeof(own)));
-  }
+  const int rc = align_dispatch(c, guess, nullptr, want_fitness, r.res);
   if (rc == ICPGPU_OK && c->src.n) {
     *view_xyzw = static_cast<const float*>(c->h_stage);
     *n_out = c->src.n;

@@ -140,25 +140,15 @@ bool solve_symmetric_point_to_plane(const double sums[kP2planeTerms], Mat4d& Tk)
 // the 29 sums of mailbox sweep `seq` (the pairs at h_flags words 2k, 2k + 1; p2plane_final_kernel)
 static int wait_p2plane_sums(icpgpu_ctx* c, unsigned long long seq, double* sums) {
   const int rc = wait_flags(c, c->h_flags, kP2planeTerms, seq);
-  if (rc) return rc;
-  for (int k = 0; k < kP2planeTerms; ++k) {
-    const unsigned long long bits = c->h_flags[2 * k];
-    std::memcpy(&sums[k], &bits, sizeof bits);
-  }
-  return ICPGPU_OK;
+  if (!rc) take_pairs(c, kP2planeTerms, sums);
+  return rc;
 }
 
 int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_fitness, icpgpu_result* res) {
   const auto t_start = std::chrono::steady_clock::now();
-  init_result(res);
-  c->prof.aligns += 1;
-  int rc = resolve_sweep_timings(c, /*block=*/false);
+  int rc = call_begin(c, res);
   if (rc) return rc;
-  c->dev_ms_accum = 0.0;
-  c->call_sweeps = c->call_timed = 0;
-  c->prev.valid = c->tile_seed.valid = false;  // every alignment starts cold
-  c->rej_ran = 0;
-  c->rcp_ran = false;
+  start_cold(c);  // every alignment starts cold
   Mat4d final_T = mat4_identity();
   if (guess)
     for (int i = 0; i < 16; ++i) final_T[i] = (double)guess[i];
@@ -178,7 +168,7 @@ int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_f
     if ((rc = reject_prepare(c))) return rc;
     const icpgpu_params& P = c->params;
     ConvergenceCriteria crit(P.max_iterations, P.transformation_epsilon, P.euclidean_fitness_epsilon, P.force_iterations != 0);
-    const float thr = threshold_from(P.max_correspondence_distance * P.max_correspondence_distance);
+    const float thr = gate_threshold(c);
     if ((rc = ensure_grid(c, thr))) return rc;
     if ((rc = ensure(c, c->keys, (size_t)(n_s ? n_s : 1) * sizeof(unsigned long long)))) return rc;
     if ((rc = ensure(c, c->p2plane_partials, (size_t)p2plane_blocks(n_s) * kP2planeTerms * sizeof(double)))) return rc;
@@ -186,9 +176,7 @@ int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_f
     double sums[kP2planeTerms];
     for (;;) {
       const Xform T = to_xform(final_T);
-      if ((rc = gated_keys(c, T, thr, keys))) return rc;
-      if ((rc = reciprocal_run(c, T, keys, thr))) return rc;  // (flag off: nothing)
-      if ((rc = reject_run_chain(c, keys, thr, T))) return rc;  // (an empty chain: nothing)
+      if ((rc = correspondence_keys(c, T, thr, keys))) return rc;
       const unsigned long long seq = ++c->sums_seq;
       if (symmetric)
         HIP_TRY(c, launch_p2plane_sym_reduce(c->src.data(), src_normals, n_s, c->tgt.data(), normals, keys, T, thr, c->p2plane_enforce_same_direction,
@@ -223,22 +211,8 @@ int align_p2plane(icpgpu_ctx* c, const float* guess, float* out_xyzw, int want_f
     }
   }
   if ((rc = reject_fetch_stats(c))) return rc;  // the chain's statistics of the last iteration (none, and nothing fetched, without a chain)
-  c->final_T = final_T;
-  c->have_final = true;
-  mat4_to_float(final_T, res->T);
-  res->converged = converged ? 1 : 0;
-  res->iterations = nr;
-  res->convergence_state = state;
-  res->n_correspondences = n_corr;
-  res->mse_last = mse;
-  if ((rc = write_output_cloud(c, to_xform(final_T), out_xyzw))) return rc;
-  if (want_fitness && n_t > 0) {  // getFitnessScore(): the point-to-point sweep with an open range (icpgpu_fitness)
-    if ((rc = nn_and_reduce(c, to_xform(final_T), FLT_MAX, true))) return rc;
-    res->fitness = c->h_sums[0] > 0.0 ? c->h_sums[16] / c->h_sums[0] : DBL_MAX;
-  }
-  if ((rc = resolve_sweep_timings(c, /*block=*/false))) return rc;
-  res->t_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-  return ICPGPU_OK;
+  record_result(c, res, final_T, converged, nr, state, n_corr, mse);
+  return cloud_then_fitness(c, to_xform(final_T), out_xyzw, want_fitness && n_t > 0, res, t_start);
 }
 
 }  // namespace icpgpu_impl

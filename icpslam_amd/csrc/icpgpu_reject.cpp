@@ -108,6 +108,13 @@ int reject_run_chain(icpgpu_ctx* c, unsigned long long* keys, float thr, const X
   return ICPGPU_OK;
 }
 
+int correspondence_keys(icpgpu_ctx* c, const Xform& T, float thr, unsigned long long* keys) {
+  int rc = gated_keys(c, T, thr, keys);
+  if (rc) return rc;
+  if ((rc = reciprocal_run(c, T, keys, thr))) return rc;
+  return reject_run_chain(c, keys, thr, T);
+}
+
 // the statistics of the last run of the chain and of the reciprocal stage -> c->rej_stats, c->rcp_stats (zeroes for whichever has
 // not run since they were last taken); one read-back for both
 int reject_fetch_stats(icpgpu_ctx* c) {
@@ -151,9 +158,7 @@ int sweep_issue_rejected(icpgpu_ctx* c, const Xform& T, float thr, SweepTicket& 
   if (rc) return rc;
   auto* keys = static_cast<unsigned long long*>(c->keys.ptr);
   if ((rc = reject_prepare(c))) return rc;
-  if ((rc = gated_keys(c, T, thr, keys))) return rc;
-  if ((rc = reciprocal_run(c, T, keys, thr))) return rc;
-  if ((rc = reject_run_chain(c, keys, thr, T))) return rc;
+  if ((rc = correspondence_keys(c, T, thr, keys))) return rc;
   if ((rc = ensure(c, c->partials, (size_t)kMaxReduceBlocks * kReduceTerms * sizeof(double)))) return rc;
   const unsigned long long seq = ++c->sums_seq;
   HIP_TRY(c, launch_reduce(c->src.data(), n_s, c->tgt.data(), keys, T, thr, static_cast<double*>(c->partials.ptr), c->h_sums_dev,
@@ -233,20 +238,19 @@ int icpgpu_correspondences(icpgpu_ctx* c, const float* T, int32_t* idx, float* d
   if (rc) return rc;
   if ((rc = ensure(c, c->idx, (size_t)(n_s ? n_s : 1) * sizeof(int32_t)))) return rc;
   if ((rc = ensure(c, c->d2, (size_t)(n_s ? n_s : 1) * sizeof(float)))) return rc;
-  const float thr = threshold_from(c->params.max_correspondence_distance * c->params.max_correspondence_distance);
+  const float thr = gate_threshold(c);
   auto* keys = static_cast<unsigned long long*>(c->keys.ptr);
   c->prev.valid = false;  // (as an alignment's first iteration: nothing carried over)
   c->rcp_ran = false;
   const Xform X = T ? to_xform(T) : to_xform(mat4_identity());
-  if (c->tgt.n == 0) {
+  if (c->tgt.n == 0) {  // no search and no reciprocal stage: every key empty, and the chain over them
     HIP_TRY(c, launch_fill_keys(keys, n_s, c->stream));
+    if ((rc = reject_run_chain(c, keys, thr, X))) return rc;
   } else {
     if ((rc = reject_prepare(c))) return rc;
     if ((rc = ensure_grid(c, thr))) return rc;
-    if ((rc = gated_keys(c, X, thr, keys))) return rc;
-    if ((rc = reciprocal_run(c, X, keys, thr))) return rc;
+    if ((rc = correspondence_keys(c, X, thr, keys))) return rc;
   }
-  if ((rc = reject_run_chain(c, keys, thr, X))) return rc;
   HIP_TRY(c, launch_reject_unpack(keys, n_s, thr, static_cast<int32_t*>(c->idx.ptr), static_cast<float*>(c->d2.ptr), c->stream));
   if (n_s) {
     HIP_TRY(c, hipMemcpyAsync(idx, c->idx.ptr, (size_t)n_s * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));

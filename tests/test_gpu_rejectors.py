@@ -254,6 +254,94 @@ def test_gicp_and_ndt_ignore_the_chain(built):
         assert _align_bits(method, src, tgt, lambda ctx: ctx.set_correspondence_rejectors(CHAINS["one_to_one_trimmed"])) == plain
 
 
+def test_statistics_outlive_gicp_ndt_and_fitness_until_the_next_p2p_alignment(pair3k):
+    """include/icpgpu.h: both statistics are those of "the last P2P_SVD / P2PLANE alignment" -- a GICP or NDT alignment and
+    icpgpu_fitness leave them alone; the next point-to-point alignment, with no chain and the flag off, empties them."""
+    src, tgt = pair3k
+    with Context(0) as ctx:
+        ctx.set_params(max_iterations=3)
+        ctx.set_source(src)
+        ctx.set_target(tgt)
+        ctx.set_correspondence_rejectors(CHAINS["median_one_to_one"])
+        ctx.set_reciprocal_correspondences(True)
+        ctx.align()
+        rej, rcp = ctx.rejector_stats(), ctx.reciprocal_stats()
+        assert len(rej) == 2 and rej[0]["pairs_in"] > 0 and rcp["pairs_in"] > 0
+        for step in (lambda: (ctx.set_params(method=_lib.GICP), ctx.align()), lambda: (ctx.set_params(method=_lib.NDT), ctx.align()),
+                     ctx.fitness):
+            step()
+            assert ctx.rejector_stats() == rej and ctx.reciprocal_stats() == rcp
+        ctx.set_params(method=_lib.P2P_SVD)
+        ctx.set_correspondence_rejectors([])
+        ctx.set_reciprocal_correspondences(False)
+        ctx.align()
+        assert ctx.rejector_stats() == [] and ctx.reciprocal_stats() == dict(pairs_in=0, pairs_out=0)
+
+
+# ---- the ends an alignment reaches without iterating: one record, one count, and the transform icpgpu_fitness goes on with ------
+_EDGE_GUESS = synth.pose_matrix(0.03, -0.02, 0.01, 0.002, -0.001, 0.004).astype(np.float32)
+_DBL_MAX = float(np.finfo(np.float64).max)
+
+
+def _edge_align(method, src, tgt):
+    """A fresh context's alignment from _EDGE_GUESS -> (the record without its two time fields, or the error's code; the
+    alignments counted; icpgpu_fitness afterwards, as bytes)"""
+    with Context(0) as ctx:
+        ctx.set_params(method=method, max_iterations=3)
+        ctx.set_source(src)
+        ctx.set_target(tgt)
+        before = ctx.profile().aligns
+        try:
+            r = ctx.align(guess=_EDGE_GUESS, want_fitness=True)
+            rec = (r["T"].tobytes(), r["converged"], r["iterations"], r["state"], r["n_corr"], np.float64(r["mse"]).tobytes(),
+                   np.float64(r["fitness"]).tobytes(), r["gicp_solver"])
+        except IcpGpuError as e:
+            rec = e.code
+        return rec, ctx.profile().aligns - before, np.float64(ctx.fitness()).tobytes()
+
+
+def _fitness_at(src, tgt, T):
+    """getFitnessScore at T: a point-to-point alignment that may not move (no pair count reaches its minimum) and then sweeps"""
+    if len(tgt) == 0:
+        return _DBL_MAX
+    with Context(0) as ctx:
+        ctx.set_params(min_correspondences=1 << 30)
+        ctx.set_source(src)
+        ctx.set_target(tgt)
+        r = ctx.align(guess=T, want_fitness=True)
+        assert r["iterations"] == 0 and r["T"].tobytes() == np.asarray(T, np.float32).tobytes()
+        return r["fitness"]
+
+
+_EYE = np.eye(4, dtype=np.float32)
+_EDGES = {  # case -> (source points, target points, {method: the transform today's code ends with; None: an error, nothing recorded})
+    "empty_target": (3000, 0, {_lib.P2P_SVD: _EYE, _lib.P2PLANE: _EYE, _lib.NDT: _EYE, _lib.GICP: _EYE}),
+    "empty_source": (0, 3000, {_lib.P2P_SVD: _EDGE_GUESS, _lib.P2PLANE: _EDGE_GUESS, _lib.NDT: _EDGE_GUESS, _lib.GICP: _EYE}),
+    "source_of_19": (19, 3000, {_lib.P2PLANE: "moved", _lib.GICP: _EYE}),      # below kGicpK: GICP refuses (PCL: converged_ = false, T = I);
+    "target_of_19": (3000, 19, {_lib.P2PLANE: None, _lib.GICP: _EYE}),         # P2PLANE estimates the target's normals only: an argument error
+}
+
+
+@pytest.mark.parametrize("case,method", [(k, m) for k, v in _EDGES.items() for m in v[2]])
+def test_edge_alignments_record_once_and_consistently(pair3k, case, method):
+    n_s, n_t, ends = _EDGES[case]
+    src, tgt = pair3k[0][:n_s], pair3k[1][:n_t]
+    rec, counted, fit = _edge_align(method, src, tgt)
+    assert counted == 1
+    assert _edge_align(method, src, tgt) == (rec, counted, fit)
+    want = ends[method]
+    if want is None:
+        assert rec == _lib.ERR_INVALID_ARG
+        T = _EYE                                     # nothing was recorded: a fresh context's icpgpu_fitness uses the identity
+    else:
+        T = np.frombuffer(rec[0], np.float32).reshape(4, 4)
+        if isinstance(want, str):
+            assert rec[2] >= 1 and rec[0] != _EDGE_GUESS.tobytes()
+        else:
+            assert rec[0] == want.tobytes() and rec[2] == 0
+    assert fit == np.float64(_fitness_at(src, tgt, T)).tobytes()
+
+
 def test_batches_refuse_a_chain(built):
     pairs = [synth.make_pair(2000, 2000, seed=s)[:2] for s in (3, 4, 5)]
     srcs, tgts = [p[0] for p in pairs], [p[1] for p in pairs]
