@@ -34,6 +34,8 @@ SCP_MAX_SAMPLES = 8            # ICPGPU_SCP_MAX_SAMPLES
 SCP_INVALID, SCP_PREREJECTED, SCP_NO_TRANSFORM, SCP_EVALUATED = 0, 1, 2, 3   # ICPGPU_SCP_*
 SACMODEL_PLANE, SACMODEL_PERPENDICULAR_PLANE = 0, 15   # pcl::SacModel's values
 SAC_RANSAC = 0                 # pcl's method_types.h
+MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3   # icpgpu_morph_op
+PMF_MAX_PASSES = 32            # ICPGPU_PMF_MAX_PASSES
 STATE_NAMES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE",
                5: "NO_CORRESPONDENCES"}
 
@@ -114,6 +116,8 @@ EXPORTS = [
     "icpgpu_boundary_estimation", "icpgpu_iss_keypoints_border", "icpgpu_iss_fetch_border",
     "icpgpu_moving_least_squares", "icpgpu_mls_fetch", "icpgpu_mls_stats",
     "icpgpu_sac_plane_segmentation", "icpgpu_sac_fetch", "icpgpu_sac_stats", "icpgpu_sac_extract", "icpgpu_sac_extract_view",
+    "icpgpu_morphological_operator", "icpgpu_progressive_morphological_filter", "icpgpu_pmf_fetch", "icpgpu_pmf_stats", "icpgpu_pmf_extract",
+    "icpgpu_pmf_extract_view",
     "icpgpu_set_source_normals", "icpgpu_set_p2plane_symmetric", "icpgpu_get_p2plane_symmetric",
     "icpgpu_reduce_symmetric_point_to_plane", "icpgpu_solve_symmetric_point_to_plane",
 ]
@@ -241,6 +245,12 @@ def load():
     L.icpgpu_mls_stats.argtypes = [vp, ip]
     L.icpgpu_sac_extract.argtypes = [vp, C.c_int, fp, szp]
     L.icpgpu_sac_extract_view.argtypes = [vp, C.c_int, C.POINTER(fp), szp]
+    L.icpgpu_morphological_operator.argtypes = [vp, C.c_double, C.c_int, fp]
+    L.icpgpu_progressive_morphological_filter.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, szp, ip]
+    L.icpgpu_pmf_fetch.argtypes = [vp, C.c_size_t, C.c_size_t, ip, fp, fp, ip, ip]
+    L.icpgpu_pmf_stats.argtypes = [vp, ip, C.POINTER(C.c_uint64)]
+    L.icpgpu_pmf_extract.argtypes = [vp, C.c_int, fp, szp]
+    L.icpgpu_pmf_extract_view.argtypes = [vp, C.c_int, C.POINTER(fp), szp]
     L.icpgpu_scp_align.argtypes = [vp, fp, C.c_size_t, fp, fp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64, fp, szp, fp, ip, fp]
     L.icpgpu_scp_fetch.argtypes = [vp, C.c_size_t, C.c_size_t, ip, ip, ip, fp, ip, dp, fp, ip, ip]
     L.icpgpu_scp_stats.argtypes = [vp, ip, ip, dp]

@@ -15,6 +15,7 @@
 //                       steps every stage over that cloud shares (view_of, neighbour_rows, deliver)
 //   icpgpu_boundary.cpp boundary estimation over the search cloud
 //   icpgpu_sac.cpp      plane segmentation (RANSAC) over the search cloud and ExtractIndices over its result
+//   icpgpu_pmf.cpp      the ground filter: morphological operators and the progressive morphological filter over the search cloud
 //   icpgpu_iss.cpp      ISS keypoints over the search cloud, with and without border estimation
 //   icpgpu_mls.cpp      moving least squares over the search cloud's radius rows
 //   icpgpu_feature.cpp  feature-space k-nearest and the sample-consensus alignment over it
@@ -458,6 +459,21 @@ struct icpgpu_ctx {
     DeviceBuf batch, ints, sums;
     Compaction sel, ext;  // sel.kept: the inliers; ext: icpgpu_sac_extract's own (the inlier list outlives an extract)
   } sac;
+  // ground filter (icpgpu_pmf.cpp, icp_morph.hip): the last filter call's result over the search cloud and the scratch of a filter or
+  // an operator call, in buffers no other call writes -- an unfetched result outlives every other call over the search cloud (an
+  // operator call included: it compacts into `op`); icpgpu_search_set_input drops it
+  struct Pmf {
+    bool have = false;    // a filter result is in place
+    bool ran = false;     // a filter or an operator call has completed since the search cloud was set: `waits` is its
+    size_t n = 0, n_ground = 0;
+    int waits = 0;
+    unsigned long long tests_total = 0;      // exact point tests of the last filter call's rim scans
+    std::vector<float> windows, thresholds;  // the schedule
+    std::vector<int32_t> ground_after;       // the ground set's size after each pass
+    DeviceBuf removed_at, after, ints, tests;  // per point; per pass; [0..4) the xy box, [4] a live count, [5] extract's count; rim tests
+    DeviceBuf grid, table, cell_start, scan, cellid, sxy, sval, va, vb, sidx, scell, out_z;  // a binning and its sorted arrays
+    Compaction sel, op, ext;  // sel.kept: the ground; op: an operator call's active set; ext: icpgpu_pmf_extract's own
+  } pmf;
   // feature-space k-nearest (icpgpu_feature.cpp, icp_feature.hip): the call's descriptors and rows, in buffers no other call reads or
   // writes -- it neither uses nor touches the search cloud, and an unfetched clustering or segmentation result survives it
   struct Feature {

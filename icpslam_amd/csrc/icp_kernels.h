@@ -694,4 +694,45 @@ hipError_t launch_scp_select(const float4* source, int n_s, const Xform& T, cons
                              const GridDesc& g, int shells, const ScpBox& box, float r2, int* flags, int* pos, int* scan_scratch, int* inliers,
                              int* n_inliers, hipStream_t stream);
 
+// ---- ground filter (icp_morph.hip): pcl::applyMorphologicalOperator / pcl::ProgressiveMorphologicalFilter over the search cloud ----
+// "The extremum of a value array over every active point's xy box" (rule: include/icpgpu.h "ground filter"), over a 2-D cell table
+// of the active points whose cell side the DEVICE derives from the cloud's finite xy box and the window: window / kMorphCellsPerWindow,
+// coarsened until no axis has more than kMorphAxisCells cells.  Every count below is read from device memory (*d_count): launches
+// are sized by n and no step needs the host.
+static constexpr int kMorphCellsPerWindow = 8;
+static constexpr int kMorphAxisCells = 512;
+static constexpr int kMorphMaxCells = kMorphAxisCells * kMorphAxisCells;
+// ints of the cell tables (counts: kMorphMaxCells + 1; fill, the two extremum tables: kMorphMaxCells each), zeroed before every binning
+static constexpr size_t kMorphTableInts = 4 * (size_t)kMorphMaxCells + 1;
+struct MorphGrid {  // cell(x) = clamp((int)((x - ox) * inv), 0, nx - 1), likewise y: the ONE cell function of binning and of box bounds
+  float ox, oy, inv;
+  int nx, ny;
+};
+// flags[i] = 1 for a finite point (x, y, z), else 0; removed_at[i] = -1 / -2 and out_z[i] = the point's own z where given; bbox4 (zeroed
+// by the launcher) receives the finite points' xy box as ordered keys
+hipError_t launch_morph_init(const float4* cloud, int n, int* flags, int32_t* removed_at, float* out_z, unsigned int* bbox4, hipStream_t stream);
+// One binning of the active points act[0 .. *d_count) for `window`: the grid from bbox4, the counting sort into cell-row-major order
+// (sxy, sval = z, sidx = cloud index, scell = cell; n of room each; cellid: n ints of scratch) with cell_start (kMorphMaxCells + 1
+// ints) and, in the first extremum table of `table` (kMorphTableInts ints), every cell's extremum of z (is_max: max, else min).
+hipError_t launch_morph_bin(const float4* cloud, int n, const int* act, const int* d_count, const unsigned int* bbox4, float window, MorphGrid* grid,
+                            int* table, int* cell_start, int* scan_scratch, int* cellid, float2* sxy, float* sval, int* sidx, int* scell, bool is_max,
+                            hipStream_t stream);
+// out_val[p] = the extremum (is_max) of in_val over the box of sorted point p, a wave per point: the cells strictly inside the box's cell
+// range through extremum table `phase` (0 / 1) of `table`, the rim's cells point by point with the rule's four comparisons.  With
+// feed_next the OPPOSITE extremum of out_val per cell goes into table 1 - phase (what the second half of OPEN / CLOSE reads).
+// tests (optional, kMorphTestSlots * kMorphTestStride counters, one per cache line in use): the number of exact point tests is added;
+// launch_morph_tests_total sums the counters into *total.
+static constexpr int kMorphTestSlots = 64, kMorphTestStride = 16;
+hipError_t launch_morph_tests_total(const unsigned long long* tests, unsigned long long* total, hipStream_t stream);
+hipError_t launch_morph_box(int n, const int* d_count, const MorphGrid* grid, float window, const float2* sxy, const int* cell_start, const int* scell,
+                            const float* in_val, int* table, int phase, bool is_max, bool feed_next, float* out_val, unsigned long long* tests,
+                            hipStream_t stream);
+// the filter's verdict: sorted point p stays iff sval[p] - opened[p] < thr; flags[sidx[p]] = that, removed_at[sidx[p]] = pass where not
+hipError_t launch_morph_judge(int n, const int* d_count, const float* sval, const float* opened, const int* sidx, float thr, int pass, int* flags,
+                              int32_t* removed_at, hipStream_t stream);
+// out_z[sidx[p]] = val[p]
+hipError_t launch_morph_unsort(int n, const int* d_count, const float* val, const int* sidx, float* out_z, hipStream_t stream);
+// flags[i] = 1 where removed_at[i] == -1 (ground), the other way round with `invert`
+hipError_t launch_pmf_flags(const int32_t* removed_at, int n, bool invert, int* flags, hipStream_t stream);
+
 }  // namespace icpgpu

@@ -669,7 +669,7 @@ int icpgpu_destroy(icpgpu_ctx* c) {
                        &c->map.uflags, &c->map.urank, &c->map.uniq_index, &c->map.uniq.buf})
     release(*b);
   for (DeviceBuf* b : {&c->outlier.cloud.buf, &c->outlier.measure, &c->outlier.far, &c->outlier.ints}) release(*b);
-  for (Compaction* C : {&c->outlier.comp, &c->sac.sel, &c->sac.ext, &c->scp.sel, &c->iss.comp, &c->mls.comp}) release(*C);
+  for (Compaction* C : {&c->outlier.comp, &c->sac.sel, &c->sac.ext, &c->pmf.sel, &c->pmf.op, &c->pmf.ext, &c->scp.sel, &c->iss.comp, &c->mls.comp}) release(*C);
   for (DeviceBuf* b : {&c->search.cloud.buf, &c->search.queries, &c->search.idx, &c->search.d2, &c->search.n_found, &c->search.far,
                        &c->search.counts, &c->search.longs, &c->search.row_start, &c->search.scratch_start, &c->search.scan,
                        &c->search.scratch, &c->search.totals, &c->search.row_start64, &c->search.normals, &c->search.moments,
@@ -680,6 +680,9 @@ int icpgpu_destroy(icpgpu_ctx* c) {
                        &c->cluster.cstart, &c->cluster.cstart64, &c->cluster.keys, &c->cluster.vals, &c->cluster.scratch, &c->cluster.counts})
     release(*b);
   for (DeviceBuf* b : {&c->sac.batch, &c->sac.ints, &c->sac.sums}) release(*b);
+  for (DeviceBuf* b : {&c->pmf.removed_at, &c->pmf.after, &c->pmf.ints, &c->pmf.tests, &c->pmf.grid, &c->pmf.table, &c->pmf.cell_start, &c->pmf.scan,
+                       &c->pmf.cellid, &c->pmf.sxy, &c->pmf.sval, &c->pmf.va, &c->pmf.vb, &c->pmf.sidx, &c->pmf.scell, &c->pmf.out_z})
+    release(*b);
   for (DeviceBuf* b : {&c->scp.source, &c->scp.sfeat, &c->scp.tfeat, &c->scp.finite, &c->scp.rows, &c->scp.rows_d2, &c->scp.found, &c->scp.c_status,
                        &c->scp.c_sidx, &c->scp.c_tidx, &c->scp.c_sums, &c->scp.xforms, &c->scp.partials, &c->scp.results, &c->scp.ints, &c->scp.aligned})
     release(*b);

@@ -190,7 +190,7 @@ extern "C" {
 
 // Copies the cloud and builds its k-NN grid.  Nothing of the context's source, target, their grids, the covariances, the NDT cells
 // or the filters' results is touched; the previous search cloud, and a clustering,
-// plane segmentation, sample-consensus alignment, ISS or moving least squares result over it, is gone whatever this call returns.
+// plane segmentation, ground filter, sample-consensus alignment, ISS or moving least squares result over it, is gone whatever this call returns.
 int icpgpu_search_set_input(icpgpu_ctx* c, const float* xyzw, size_t n) {
   ENTER(c);
   auto& S = c->search;
@@ -200,6 +200,7 @@ int icpgpu_search_set_input(icpgpu_ctx* c, const float* xyzw, size_t n) {
   S.grid.built = S.grid.usable = false;  // (version 0: a build never stands for the next cloud)
   c->cluster.have = false;               // (a clustering result is a result over the cloud that goes)
   c->sac.have = false;                   // (and so is a plane segmentation)
+  c->pmf.have = c->pmf.ran = false;      // (and a ground filter's)
   c->scp.have = false;                   // (and a sample-consensus alignment)
   c->iss.have = false;                   // (and the ISS keypoints)
   c->mls.have = false;                   // (and the moving least squares record)

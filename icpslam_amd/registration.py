@@ -953,6 +953,75 @@ class Context:
         self._check(self._L.icpgpu_sac_stats(self._h, C.byref(w)))
         return int(w.value)
 
+    # ground filter (pcl::applyMorphologicalOperator, pcl::ProgressiveMorphologicalFilter; rules: include/icpgpu.h) --------------
+    def morphological_operator_raw(self, resolution: float, op: int) -> tuple:
+        """One icpgpu_morphological_operator call: (rc, z (n,) float32, pre-filled with -2)."""
+        n_c = C.c_size_t()
+        self._L.icpgpu_search_size(self._h, C.byref(n_c), None)  # (0 without a search cloud)
+        out = np.full(int(n_c.value), -2, np.float32)
+        rc = self._L.icpgpu_morphological_operator(self._h, float(resolution), int(op), _fp(out))
+        return rc, out
+
+    def morphological_operator(self, resolution: float, op: int) -> np.ndarray:
+        """z (n,) float32 of the search cloud after MORPH_ERODE / DILATE / OPEN / CLOSE over xy boxes of side `resolution`; non-finite
+        rows keep their own z."""
+        rc, out = self.morphological_operator_raw(resolution, op)
+        self._check(rc)
+        return out
+
+    def pmf_filter_raw(self, max_window_size: int = 33, slope: float = 0.7, initial_distance: float = 0.15, max_distance: float = 10.0,
+                       cell_size: float = 1.0, base: float = 2.0, exponential: bool = True) -> tuple:
+        """One icpgpu_progressive_morphological_filter call: (rc, n_ground, n_passes); the result stays in the context."""
+        n_ground, n_passes = C.c_size_t(), C.c_int32()
+        rc = self._L.icpgpu_progressive_morphological_filter(self._h, int(max_window_size), float(slope), float(initial_distance), float(max_distance),
+                                                             float(cell_size), float(base), int(bool(exponential)), C.byref(n_ground),
+                                                             C.byref(n_passes))
+        self._pmf_last = (int(n_ground.value), int(n_passes.value))
+        return rc, int(n_ground.value), int(n_passes.value)
+
+    def pmf_fetch_raw(self, capacity_ground: int, capacity_passes: int, want=("ground", "windows", "thresholds", "ground_after", "removed_at")) -> tuple:
+        """One icpgpu_pmf_fetch call into arrays pre-filled with -2 (those not in `want` are handed over as NULL): (rc, dict)."""
+        ip = C.POINTER(C.c_int32)
+        n_c = C.c_size_t()
+        self._L.icpgpu_search_size(self._h, C.byref(n_c), None)  # (0 without a search cloud)
+        out = {"ground": np.full(capacity_ground, -2, np.int32), "windows": np.full(capacity_passes, -2, np.float32),
+               "thresholds": np.full(capacity_passes, -2, np.float32), "ground_after": np.full(capacity_passes, -2, np.int32),
+               "removed_at": np.full(int(n_c.value), -2, np.int32)}
+        ptr = {k: (None if k not in want else _fp(v) if v.dtype == np.float32 else v.ctypes.data_as(ip)) for k, v in out.items()}
+        rc = self._L.icpgpu_pmf_fetch(self._h, int(capacity_ground), int(capacity_passes), ptr["ground"], ptr["windows"], ptr["thresholds"],
+                                      ptr["ground_after"], ptr["removed_at"])
+        return rc, out
+
+    def pmf_stats(self) -> tuple:
+        """(host waits of the last filter or operator call, exact point tests of the last filter call's rim scans): icpgpu_pmf_stats."""
+        w, t = C.c_int32(), C.c_uint64()
+        self._check(self._L.icpgpu_pmf_stats(self._h, C.byref(w), C.byref(t)))
+        return int(w.value), int(t.value)
+
+    def progressive_morphological_filter(self, max_window_size: int = 33, slope: float = 0.7, initial_distance: float = 0.15,
+                                         max_distance: float = 10.0, cell_size: float = 1.0, base: float = 2.0, exponential: bool = True) -> dict:
+        """The ground of the search cloud: ground (int32 ascending), windows and thresholds (the schedule), ground_after (per pass),
+        removed_at (per point: the pass that removed it, -1 ground, -2 non-finite) and host_waits."""
+        rc, n_ground, n_passes = self.pmf_filter_raw(max_window_size, slope, initial_distance, max_distance, cell_size, base, exponential)
+        self._check(rc)
+        rc, out = self.pmf_fetch_raw(n_ground, n_passes)
+        self._check(rc)
+        out["host_waits"] = self.pmf_stats()[0]
+        return out
+
+    def pmf_extract(self, negative: bool = False, view: bool = False) -> np.ndarray:
+        """pcl::ExtractIndices over the last ground filter: the search cloud's points in (negative: not in) the ground, in order."""
+        n_out = C.c_size_t()
+        if view:
+            ptr = C.POINTER(C.c_float)()
+            self._check(self._L.icpgpu_pmf_extract_view(self._h, int(bool(negative)), C.byref(ptr), C.byref(n_out)))
+            if n_out.value == 0:
+                return np.empty((0, 4), np.float32)
+            return np.ctypeslib.as_array(ptr, shape=(n_out.value, 4)).copy()
+        out = np.empty((self.search_size()[0], 4), np.float32)
+        self._check(self._L.icpgpu_pmf_extract(self._h, int(bool(negative)), _fp(out), C.byref(n_out)))
+        return out[: n_out.value].copy()
+
     # measurement -----------------------------------------------------------------------------------------------
     def calibrate(self) -> int:
         """icpgpu_calibrate: time GICP's two inner solvers on the clouds this context holds and keep the faster (GICP_SOLVER_*)."""
@@ -1791,6 +1860,85 @@ class SACSegmentation:
         if not found:
             return np.empty(0, np.int32), np.empty(0, np.float32)
         return inliers, coeff
+
+
+class ProgressiveMorphologicalFilter:
+    """pcl::ProgressiveMorphologicalFilter<PointXYZ>-shaped front end (include/icpgpu.h, "ground filter"): setInputCloud,
+    setMaxWindowSize, setSlope, setMaxDistance, setInitialDistance, setCellSize, setBase, setExponential and
+    extract() -> the ground's indices (int32, ascending).  The defaults are PCL's (33, 0.7, 10.0, 0.15, 1.0, 2.0, true).  After an
+    extract, `last` holds everything Context.progressive_morphological_filter returned and extractCloud(negative) is
+    pcl::ExtractIndices over it.  setIndices is not provided."""
+
+    def __init__(self, device_id: int = 0):
+        self._ctx = Context(device_id)
+        self._input = None
+        self._max_window_size = 33
+        self._slope = 0.7
+        self._max_distance = 10.0
+        self._initial_distance = 0.15
+        self._cell_size = 1.0
+        self._base = 2.0
+        self._exponential = True
+        self.last = None
+
+    def setInputCloud(self, cloud):
+        self._input = _as_cloud(cloud).copy()
+
+    def setMaxWindowSize(self, max_window_size: int):
+        self._max_window_size = int(max_window_size)
+
+    def getMaxWindowSize(self) -> int:
+        return self._max_window_size
+
+    def setSlope(self, slope: float):
+        self._slope = float(slope)
+
+    def getSlope(self) -> float:
+        return self._slope
+
+    def setMaxDistance(self, max_distance: float):
+        self._max_distance = float(max_distance)
+
+    def getMaxDistance(self) -> float:
+        return self._max_distance
+
+    def setInitialDistance(self, initial_distance: float):
+        self._initial_distance = float(initial_distance)
+
+    def getInitialDistance(self) -> float:
+        return self._initial_distance
+
+    def setCellSize(self, cell_size: float):
+        self._cell_size = float(cell_size)
+
+    def getCellSize(self) -> float:
+        return self._cell_size
+
+    def setBase(self, base: float):
+        self._base = float(base)
+
+    def getBase(self) -> float:
+        return self._base
+
+    def setExponential(self, exponential: bool):
+        self._exponential = bool(exponential)
+
+    def getExponential(self) -> bool:
+        return self._exponential
+
+    def extract(self) -> np.ndarray:
+        if self._input is None:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "extract: setInputCloud first")
+        self._ctx.search_set_input(self._input)
+        self.last = self._ctx.progressive_morphological_filter(self._max_window_size, self._slope, self._initial_distance, self._max_distance,
+                                                               self._cell_size, self._base, self._exponential)
+        return self.last["ground"]
+
+    def extractCloud(self, negative: bool = False) -> np.ndarray:
+        """NOT a PCL method: the input's ground points (negative: the others) of the last extract(), in cloud order."""
+        if self.last is None:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "extractCloud: extract first")
+        return self._ctx.pmf_extract(negative)
 
 
 class ExtractIndices:

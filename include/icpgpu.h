@@ -57,7 +57,8 @@ extern "C" {
  * icpgpu_radius_outlier_removal, their _view forms, icpgpu_outlier_stats, icpgpu_outlier_fetch, and the neighbour search --
  * icpgpu_search_set_input, icpgpu_search_size, icpgpu_search_knn, icpgpu_search_radius, and normal estimation --
  * icpgpu_normal_estimation, and euclidean clustering -- icpgpu_euclidean_cluster_extraction, icpgpu_cluster_fetch, and plane segmentation --
- * icpgpu_sac_plane_segmentation, icpgpu_sac_fetch, icpgpu_sac_stats, icpgpu_sac_extract, icpgpu_sac_extract_view, and ISS keypoints --
+ * icpgpu_sac_plane_segmentation, icpgpu_sac_fetch, icpgpu_sac_stats, icpgpu_sac_extract, icpgpu_sac_extract_view, and the ground filter -- icpgpu_morphological_operator,
+ * icpgpu_progressive_morphological_filter, icpgpu_pmf_fetch, icpgpu_pmf_stats, icpgpu_pmf_extract, icpgpu_pmf_extract_view, and ISS keypoints --
  * icpgpu_iss_keypoints, icpgpu_iss_fetch, icpgpu_iss_stats, icpgpu_iss_keypoints_border, icpgpu_iss_fetch_border, and boundary
  * estimation -- icpgpu_boundary_estimation, and moving least squares -- icpgpu_moving_least_squares, icpgpu_mls_fetch, icpgpu_mls_stats, and fast point feature histograms -- icpgpu_fpfh_estimation, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
  * icpgpu_set_p2plane_symmetric, icpgpu_get_p2plane_symmetric, icpgpu_reduce_symmetric_point_to_plane,
@@ -1011,6 +1012,76 @@ int icpgpu_sac_fetch(icpgpu_ctx* ctx, size_t capacity_inliers, size_t capacity_c
 int icpgpu_sac_stats(const icpgpu_ctx* ctx, int32_t* host_waits);
 int icpgpu_sac_extract(icpgpu_ctx* ctx, int negative, float* out_xyzw, size_t* n_out);
 int icpgpu_sac_extract_view(icpgpu_ctx* ctx, int negative, const float** view_xyzw, size_t* n_out);
+
+/* ---- ground filter (added under 1.2) -------------------------------------------------------------------------------- */
+/* replaces pcl::applyMorphologicalOperator<PointXYZ> and pcl::ProgressiveMorphologicalFilter<PointXYZ> -- setInputCloud,
+ * setMaxWindowSize, setSlope, setMaxDistance, setInitialDistance, setCellSize, setBase, setExponential, extract -- and
+ * pcl::ExtractIndices<PointXYZ> over its result: "which points are ground" where the ground slopes, crowns or ripples and is no
+ * plane.  Both calls work on the context's SEARCH CLOUD (icpgpu_search_set_input), as clustering and plane segmentation do.  Parity
+ * with PCL binaries is unpinned; tests/pmf_restated.py is what the kernels are compared with, bit for bit.  Everything is float32,
+ * every operation rounded on its own, unless said otherwise.
+ * BOX.  For a centre p and a window w (float32): h = w / 2.0f, lo = p - h and hi = p + h per axis x and y, each rounded once.  A
+ * finite point q is in p's box iff lo.x <= q.x and q.x <= hi.x and lo.y <= q.y and q.y <= hi.y: inclusive bounds, as in PCL's
+ * boxSearch; z does not take part.  A point with a non-finite x, y or z is in no box and has no box.  A finite point is always in its
+ * own box.  After rounding the relation need NOT be symmetric: q in p's box does not imply p in q's (p - h and q + h round apart).
+ * EXTREMUM.  min and max over a box's members are taken in the total order of finite floats in which -0.0f is below +0.0f: the
+ * order of the integer keys bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000).  The result's bits are therefore defined.
+ * OPERATOR (icpgpu_morphological_operator; the window is (float)resolution), over an active set A of finite points.  ERODE:
+ * out[i] = min z[j] over the j in A inside i's box.  DILATE: the same with max.  OPEN: e = ERODE(z), then out[i] = max e[j] over
+ * the same boxes.  CLOSE: d = DILATE(z), then out[i] = min d[j].  Boxes always come from the input x, y.  Points outside A keep
+ * their own z (its bits) on output.  For the entry point A is every finite point; inside the filter it is the current ground.
+ * SCHEDULE (extract's loop).  The parameters arrive as doubles and each is rounded to float32 once (PCL's setters take floats);
+ * max_window_size is converted to float32.  it = 0, window = 0; while window < max_window_size:
+ *     exponential: window = (float)((double)cell * (2.0 * B + 1.0)), B = base^it by `it` successive double multiplications of 1.0 with
+ *                  (double)base.  DEVIATION: PCL calls std::pow on floats; the two are equal for base 2.
+ *     linear:      window = cell * (2.0f * (float)(it + 1) * base + 1.0f), float32, left to right.
+ *     threshold:   thr = initial_distance when it == 0, else slope * (window - previous window) * cell + initial_distance, float32,
+ *                  left to right; then if (thr > max_distance) thr = max_distance.
+ *     append (window, thr); ++it.
+ * PASSES.  The ground starts as every finite point.  For every schedule entry, in order: o = OPEN(z) over the current ground with
+ * that window; point i stays iff z[i] - o[i] < thr (one float32 subtraction, a strict comparison; a NaN difference removes the
+ * point).  With initial_distance = 0 the first pass's threshold is 0 and a point stays only where o[i] > z[i]; wherever the box
+ * relation is symmetric around i (i is in the box of every member of its own box) e[j] <= z[i] for all of them, so o[i] <= z[i] and
+ * the point is removed: on such clouds the first pass removes every point.
+ * removed_at[i] is the pass that removed i, -1 for a ground point, -2 for a non-finite point (DEVIATION: PCL keeps non-finite
+ * points' indices in the ground).  The ground indices are ascending.
+ * OUTPUT.  icpgpu_progressive_morphological_filter computes and KEEPS the result in the context and returns the number of ground
+ * points and of passes; icpgpu_pmf_fetch copies the rest out, any number of times: the ground indices, the schedule's windows and
+ * thresholds, the ground's size after each pass and removed_at (n entries).  Any output of the fetch may be NULL; with
+ * capacity_ground < n_ground or capacity_passes < n_passes nothing is written.  icpgpu_pmf_stats reports the host waits of the last
+ * filter or operator call on this search cloud, whichever was later: exactly one, whatever the number of passes (the schedule is
+ * known before anything is launched and the ground's size stays on the device between passes), and none for an empty cloud or a
+ * schedule without a pass.  ARGUMENT ADDED to the proposed icpgpu_pmf_stats(ctx, host_waits): point_tests (may be NULL), the exact
+ * point tests the last filter call's rim scans made (0 after an operator call) -- the figure that says what the cell table saves
+ * over testing every pair, which no other entry point could report.
+ * EXTRACT.  icpgpu_pmf_extract copies out the search cloud's points that are (negative = 0) or are not (negative = 1) in the ground,
+ * in cloud order: pcl::ExtractIndices with setNegative.  With negative = 1 non-finite rows are kept: they are "not ground".
+ * out_xyzw may be NULL (the count alone).  The _view form hands out a view of the pinned staging buffer under the outlier filters'
+ * view rule: valid until the next call on the context; NULL for an empty result.
+ * ICPGPU_ERR_INVALID_ARG (nothing is kept and a previous filter result is dropped): no search cloud; a parameter that is not finite
+ * after rounding; cell_size <= 0; a negative slope, initial_distance or max_distance; exponential with base <= 1 or linear with
+ * base <= 0 (PCL would loop for ever); a schedule of more than ICPGPU_PMF_MAX_PASSES passes; a window that is not finite; a null
+ * n_ground or n_passes; for the operator a resolution that is not finite or is <= 0 as a float, an op outside 0 .. 3, a null out_z;
+ * a fetch or an extract without a result (none computed, the last filter call refused, or the search cloud replaced since); a null
+ * n_out or view pointer.  max_window_size <= 0 is ICPGPU_OK with zero passes and every finite point ground; an empty cloud and a
+ * cloud without a finite point are ICPGPU_OK with zero ground points.
+ * Not provided: setIndices, pcl::ApproximateProgressiveMorphologicalFilter, batch entry points.
+ * ISOLATION.  The result depends on the search cloud and the arguments alone; the calls need no grid and work
+ * on a cloud the grid refuses.  They leave the source, the target, every grid, the covariances, the cached normals, the NDT cells,
+ * the filters' results, the search cloud and a clustering, plane segmentation, sample-consensus, ISS or moving least squares result as
+ * they were; an unfetched result of any of those survives a ground filter call, an unfetched ground filter result survives those
+ * calls and icpgpu_morphological_operator.  icpgpu_search_set_input drops it, whatever it returns. */
+#define ICPGPU_PMF_MAX_PASSES 32
+typedef enum { ICPGPU_MORPH_ERODE = 0, ICPGPU_MORPH_DILATE = 1, ICPGPU_MORPH_OPEN = 2, ICPGPU_MORPH_CLOSE = 3 } icpgpu_morph_op;
+int icpgpu_morphological_operator(icpgpu_ctx* ctx, double resolution, int op, float* out_z /* n */);
+int icpgpu_progressive_morphological_filter(icpgpu_ctx* ctx, int max_window_size, double slope, double initial_distance, double max_distance,
+                                            double cell_size, double base, int exponential, size_t* n_ground, int32_t* n_passes);
+int icpgpu_pmf_fetch(icpgpu_ctx* ctx, size_t capacity_ground, size_t capacity_passes, int32_t* ground /* n_ground */,
+                     float* window_sizes /* n_passes */, float* height_thresholds /* n_passes */, int32_t* ground_after /* n_passes */,
+                     int32_t* removed_at /* n */);
+int icpgpu_pmf_stats(const icpgpu_ctx* ctx, int32_t* host_waits, uint64_t* point_tests);
+int icpgpu_pmf_extract(icpgpu_ctx* ctx, int negative, float* out_xyzw, size_t* n_out);
+int icpgpu_pmf_extract_view(icpgpu_ctx* ctx, int negative, const float** view_xyzw, size_t* n_out);
 
 /* ---- sample-consensus alignment with pre-rejection (added under 1.2) ------------------------------------------------ */
 /* replaces pcl::SampleConsensusPrerejective<PointXYZ, PointXYZ, FPFHSignature33>: setInputSource, setSourceFeatures, setInputTarget,

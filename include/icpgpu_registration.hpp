@@ -1403,6 +1403,89 @@ class ExtractIndices {
   bool negative_ = false;
 };
 
+// pcl::ProgressiveMorphologicalFilter<PointXYZ> and pcl::applyMorphologicalOperator-shaped front ends (rules and deviations:
+// include/icpgpu.h, "ground filter") -- the ground of a scan whose ground is no plane:
+//   pcl::ProgressiveMorphologicalFilter<pcl::PointXYZ> pmf;  ->  icpgpu::ProgressiveMorphologicalFilter<pcl::PointCloud<pcl::PointXYZ>> pmf;
+//   pmf.setInputCloud(cloud); pmf.setMaxWindowSize(33); pmf.setSlope(0.7f); pmf.setInitialDistance(0.15f); pmf.setMaxDistance(10.0f);
+//   pmf.setCellSize(1.0f); pmf.setBase(2.0f); pmf.setExponential(true); pmf.extract(ground->indices);
+//   pcl::applyMorphologicalOperator<pcl::PointXYZ>(cloud, resolution, pcl::MORPH_OPEN, out)  ->  icpgpu::applyMorphologicalOperator(...)
+// The defaults are PCL's.  A refused call leaves the ground empty (and the output cloud of the operator empty).  Non-finite points are
+// never ground (PCL keeps their indices).  setIndices is not provided.
+enum MorphologicalOperators { MORPH_OPEN, MORPH_CLOSE, MORPH_DILATE, MORPH_ERODE };  // (pcl's order, not icpgpu_morph_op's)
+
+template <class CloudT>
+class ProgressiveMorphologicalFilter {
+ public:
+  explicit ProgressiveMorphologicalFilter(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {}
+  template <class CloudPtr>
+  void setInputCloud(const CloudPtr& cloud) { input_ = &*cloud; }
+  void setMaxWindowSize(int max_window_size) { max_window_size_ = max_window_size; }
+  int getMaxWindowSize() const { return max_window_size_; }
+  void setSlope(float slope) { slope_ = slope; }
+  float getSlope() const { return slope_; }
+  void setMaxDistance(float max_distance) { max_distance_ = max_distance; }
+  float getMaxDistance() const { return max_distance_; }
+  void setInitialDistance(float initial_distance) { initial_distance_ = initial_distance; }
+  float getInitialDistance() const { return initial_distance_; }
+  void setCellSize(float cell_size) { cell_size_ = cell_size; }
+  float getCellSize() const { return cell_size_; }
+  void setBase(float base) { base_ = base; }
+  float getBase() const { return base_; }
+  void setExponential(bool exponential) { exponential_ = exponential; }
+  bool getExponential() const { return exponential_; }
+  int getPasses() const { return passes_; }  // NOT a PCL method: the schedule's length at the last extract()
+  void extract(std::vector<int>& ground) {
+    ground.clear();
+    passes_ = 0;
+    if (!input_) return;
+    static_assert(sizeof(input_->points[0]) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+    static_assert(sizeof(int) == sizeof(int32_t), "icpgpu: 32-bit int");
+    const std::size_t n = input_->points.size();
+    if (icpgpu_search_set_input(ctx_, n ? reinterpret_cast<const float*>(&input_->points[0]) : nullptr, n) != ICPGPU_OK) return;
+    std::size_t n_ground = 0;
+    int32_t n_passes = 0;
+    if (icpgpu_progressive_morphological_filter(ctx_, max_window_size_, slope_, initial_distance_, max_distance_, cell_size_, base_,
+                                                exponential_ ? 1 : 0, &n_ground, &n_passes) != ICPGPU_OK)
+      return;
+    std::vector<int> indices(n_ground);
+    if (icpgpu_pmf_fetch(ctx_, n_ground, (std::size_t)n_passes, n_ground ? reinterpret_cast<int32_t*>(&indices[0]) : nullptr, nullptr, nullptr,
+                         nullptr, nullptr) != ICPGPU_OK)
+      return;
+    passes_ = n_passes;
+    ground.swap(indices);
+  }
+
+ private:
+  detail::ContextPtr ctx_holder_;
+  icpgpu_ctx* ctx_;
+  const CloudT* input_ = nullptr;
+  int max_window_size_ = 33, passes_ = 0;
+  float slope_ = 0.7f, max_distance_ = 10.0f, initial_distance_ = 0.15f, cell_size_ = 1.0f, base_ = 2.0f;
+  bool exponential_ = true;
+};
+
+// cloud_out = cloud_in with every finite point's z replaced by the operator's (non-finite points keep theirs)
+template <class CloudPtr, class CloudT>
+void applyMorphologicalOperator(const CloudPtr& cloud_in, float resolution, int morphological_operator, CloudT& cloud_out, int device = 0) {
+  cloud_out.points.resize(0);
+  const int op = morphological_operator == MORPH_OPEN    ? ICPGPU_MORPH_OPEN
+                 : morphological_operator == MORPH_CLOSE  ? ICPGPU_MORPH_CLOSE
+                 : morphological_operator == MORPH_DILATE ? ICPGPU_MORPH_DILATE
+                 : morphological_operator == MORPH_ERODE  ? ICPGPU_MORPH_ERODE
+                                                          : -1;
+  const std::size_t n = cloud_in->points.size();
+  static_assert(sizeof(cloud_in->points[0]) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+  detail::ContextPtr holder = detail::acquire_context(device);
+  std::vector<float> z(n);
+  float none = 0.f;  // (an empty cloud still hands over a valid pointer)
+  if (icpgpu_search_set_input(holder->ctx, n ? reinterpret_cast<const float*>(&cloud_in->points[0]) : nullptr, n) == ICPGPU_OK &&
+      icpgpu_morphological_operator(holder->ctx, resolution, op, n ? &z[0] : &none) == ICPGPU_OK) {
+    cloud_out.points = cloud_in->points;
+    for (std::size_t i = 0; i < n; ++i) cloud_out.points[i].z = z[i];
+  }
+  detail::set_cloud_shape(cloud_out, cloud_out.points.size(), 0);
+}
+
 // pcl::KdTreeFLANN<pcl::FPFHSignature33> and pcl::SampleConsensusPrerejective<PointSource, PointTarget, FeatureT>-shaped front ends
 // (rules and deviations: include/icpgpu.h, "feature-space k-nearest" and "sample-consensus alignment") -- the pose of a cloud in
 // another WITHOUT a guess, the end of the chain VoxelGrid -> NormalEstimation -> FPFHEstimation and the start ICP needs:
