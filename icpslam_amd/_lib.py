@@ -88,7 +88,7 @@ EXPORTS = [
     "icpgpu_calibrate", "icpgpu_set_params", "icpgpu_get_params", "icpgpu_set_source", "icpgpu_set_target",
     "icpgpu_set_source_device", "icpgpu_set_target_device", "icpgpu_promote_source_to_target", "icpgpu_align", "icpgpu_align_view",
     "icpgpu_fingerprint", "icpgpu_cloud_sizes", "icpgpu_align_batch_multi_sz", "icpgpu_multi_last_error",
-    "icpgpu_fitness", "icpgpu_align_batch", "icpgpu_nn", "icpgpu_reduce", "icpgpu_solve", "icpgpu_transform",
+    "icpgpu_fitness", "icpgpu_align_batch", "icpgpu_nn", "icpgpu_reduce", "icpgpu_sweep_sums", "icpgpu_solve", "icpgpu_transform",
     "icpgpu_profile_reset", "icpgpu_profile_get", "icpgpu_profile_set_sampling", "icpgpu_get_stream", "icpgpu_synchronize",
     "icpgpu_voxel_grid", "icpgpu_voxel_plan", "icpgpu_voxel_grid_fetch", "icpgpu_voxel_grid_view", "icpgpu_set_source_voxel_filtered", "icpgpu_gicp_covariances",
     "icpgpu_gicp_quadratic_eval", "icpgpu_gicp_quadratic_sums",
@@ -178,6 +178,7 @@ def load():
     L.icpgpu_multi_last_error.restype = C.c_char_p
     L.icpgpu_nn.argtypes = [vp, fp, ip, fp]
     L.icpgpu_reduce.argtypes = [vp, fp, C.c_double, dp]
+    L.icpgpu_sweep_sums.argtypes = [vp, fp, C.c_double, dp]
     L.icpgpu_solve.argtypes = [dp, dp]
     L.icpgpu_transform.argtypes = [vp, fp, fp]
     L.icpgpu_gicp_covariances.argtypes = [vp, C.c_int, dp]

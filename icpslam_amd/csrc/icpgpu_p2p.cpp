@@ -716,6 +716,25 @@ int icpgpu_reduce(icpgpu_ctx* c, const float* T, double max_dist, double sums[17
   return ICPGPU_OK;
 }
 
+// One sweep of a point-to-point alignment, alone: p2p_begin's opening for the context's gate (no start_cold: what bounds the
+// search is valid by the clouds' versions, so a repeated call is an alignment's later iteration), then nn_and_reduce.
+int icpgpu_sweep_sums(icpgpu_ctx* c, const float* T, double max_dist, double sums[17]) {
+  ENTER(c);
+  if (!sums) return fail(c, ICPGPU_ERR_INVALID_ARG, "sums is null");
+  if (!c->src.set || !c->tgt.set) return fail(c, ICPGPU_ERR_NO_INPUT, "sweep_sums: source and target must be set first");
+  if (!std::isfinite(max_dist)) return fail(c, ICPGPU_ERR_INVALID_ARG, "sweep_sums: max_dist is not finite");
+  if (c->params.method != ICPGPU_P2P_SVD) return fail(c, ICPGPU_ERR_INVALID_ARG, "sweep_sums: the context's method is not P2P_SVD");
+  for (int k = 0; k < kReduceTerms; ++k) sums[k] = 0.0;
+  if (c->tgt.n == 0) return ICPGPU_OK;  // (an alignment over an empty target runs no sweep)
+  const float gate = gate_threshold(c);
+  int rc = ensure_grid(c, gate);
+  if (rc) return rc;
+  if ((rc = ensure_source_order(c, gate))) return rc;
+  if ((rc = nn_and_reduce(c, to_xform(T), threshold_from(max_dist * max_dist), false))) return rc;
+  std::memcpy(sums, c->h_sums, kReduceTerms * sizeof(double));
+  return resolve_sweep_timings(c, /*block=*/false);
+}
+
 int icpgpu_solve(const double sums[17], double Tk[16]) {
   if (!sums || !Tk) return ICPGPU_ERR_INVALID_ARG;
   Mat4d M;

@@ -279,6 +279,15 @@ class Context:
         self._check(self._L.icpgpu_reduce(self._h, _fp(Tb), float(max_dist), sums.ctypes.data_as(C.POINTER(C.c_double))))
         return sums
 
+    def sweep_sums(self, T=None, max_dist: float = 1.0) -> np.ndarray:
+        """icpgpu_sweep_sums: the (17,) sums of one P2P_SVD sweep at T by the alignment's own path -- its opening, then what an
+        iteration launches (the fused grid sweep where the grid serves max_dist); reduce()'s layout.  For tests."""
+        sums = np.zeros(17, np.float64)
+        Tb = None if T is None else _colmajor16(T)
+        self._check(self._L.icpgpu_sweep_sums(self._h, None if Tb is None else _fp(Tb), float(max_dist),
+                                              sums.ctypes.data_as(C.POINTER(C.c_double))))
+        return sums
+
     def solve(self, sums) -> np.ndarray:
         sums = np.ascontiguousarray(sums, np.float64)
         Tk = np.zeros(16, np.float64)

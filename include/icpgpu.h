@@ -62,7 +62,7 @@ extern "C" {
  * icpgpu_iss_keypoints, icpgpu_iss_fetch, icpgpu_iss_stats, icpgpu_iss_keypoints_border, icpgpu_iss_fetch_border, and boundary
  * estimation -- icpgpu_boundary_estimation, and moving least squares -- icpgpu_moving_least_squares, icpgpu_mls_fetch, icpgpu_mls_stats, and fast point feature histograms -- icpgpu_fpfh_estimation, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
  * icpgpu_set_p2plane_symmetric, icpgpu_get_p2plane_symmetric, icpgpu_reduce_symmetric_point_to_plane,
- * icpgpu_solve_symmetric_point_to_plane, ICPGPU_REJECT_SURFACE_NORMAL (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
+ * icpgpu_solve_symmetric_point_to_plane, ICPGPU_REJECT_SURFACE_NORMAL, and the diagnostic icpgpu_sweep_sums (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
  * icpgpu_profile.gicp_quadratic_solves; 0.3 icpgpu_profile (sources_adopted, gicp_host_solves, gicp_solver_choice). */
 
@@ -361,6 +361,15 @@ int icpgpu_nn(icpgpu_ctx* ctx, const float* T, int32_t* idx, float* d2);
 /* a3+a4: over pairs of the last icpgpu_nn/align NN sweep with (double)d2 <= max_dist^2:
  * sums = {n, sum p(3), sum q(3), sum q p^T (9, row = q), sum d2}, p = T*source[i], q = target[idx[i]]. */
 int icpgpu_reduce(icpgpu_ctx* ctx, const float* T, double max_dist, double sums[17]);
+/* One sweep of a P2P_SVD alignment at T, by the alignment's own path: the alignment's opening (the target's grid for the context's
+ * max_correspondence_distance where nn_mode asks for one, the cell-ordered source from 100000 points on), then exactly what iteration
+ * k of icpgpu_align launches for the gate (double)d2 <= max_dist^2 -- the grid search with the fused reduction, or the keys and
+ * their reduction where no grid serves max_dist (brute force, a gate above the grid's), or the rejectors' keys step -- and the 17
+ * sums it receives, in icpgpu_reduce's layout.  Calls on unchanged clouds are bounded by the previous sweep's neighbours as an
+ * alignment's later iterations are; the sums never depend on it.  T NULL = identity.  An empty target: 17 zeros, no sweep.
+ * ICPGPU_ERR_INVALID_ARG: sums NULL, max_dist not finite, another method.  icpgpu_profile shows which path ran (grid_launches,
+ * nn_launches, grid_bounded).  Diagnostic entry (tests); it leaves the last alignment's transform and record alone.  Added under 1.2 */
+int icpgpu_sweep_sums(icpgpu_ctx* ctx, const float* T, double max_dist, double sums[17]);
 /* a5 (host): Umeyama without scaling from the 17 sums -> double[16] column-major. */
 int icpgpu_solve(const double sums[17], double Tk[16]);
 /* a6: out = T * source (w = 1), pcl::transformPointCloud (icp_odometer.cpp:205). */

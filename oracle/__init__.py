@@ -20,6 +20,7 @@ PREC_F64, PREC_PCL_F32 = 0, 1
 ARITH_FMA, ARITH_FLANN = 0, 1
 GICP_SUMS_EXACT, GICP_SUMS_SEQUENTIAL, GICP_SUMS_SEQUENTIAL_REVERSED, GICP_SUMS_SMOOTH = 0, 1, 2, 3
 P2PLANE_SUMS_EXACT, P2PLANE_SUMS_SEQUENTIAL, P2PLANE_SUMS_ABS = 0, 1, 2
+REDUCE_EXACT, REDUCE_SEQUENTIAL, REDUCE_ABS = 0, 1, 2
 STATE_NAMES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE",
                5: "NO_CORRESPONDENCES"}
 
@@ -28,7 +29,7 @@ class Params(C.Structure):
     _fields_ = [("method", C.c_int), ("max_iterations", C.c_int), ("transformation_epsilon", C.c_double),
                 ("max_correspondence_distance", C.c_double), ("euclidean_fitness_epsilon", C.c_double),
                 ("min_correspondences", C.c_int), ("force_iterations", C.c_int), ("nn_mode", C.c_int),
-                ("precision", C.c_int), ("arith", C.c_int), ("gicp_sums", C.c_int)]
+                ("precision", C.c_int), ("arith", C.c_int), ("gicp_sums", C.c_int), ("p2p_sums", C.c_int)]
 
 
 class Result(C.Structure):
@@ -66,7 +67,7 @@ NDT_SEARCH_BRUTE, NDT_SEARCH_HASH = 0, 1
 def build(force: bool = False) -> str:
     """Compile oracle/liboracle.so with the committed Makefile (gcc only)."""
     srcs = [os.path.join(_HERE, f) for f in ("icp_oracle.c", "gicp_oracle.c", "map_oracle.c", "p2plane_oracle.c", "ndt_oracle.c",
-                                            "icp_oracle.h", "Makefile")]
+                                            "icp_oracle.h", "oracle_internal.h", "Makefile")]
     stale = (not os.path.exists(_LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(_LIB_PATH) for s in srcs)
     if force or stale:
@@ -87,6 +88,7 @@ def lib():
         L.orc_default_params.argtypes = [C.POINTER(Params)]
         L.orc_nn.argtypes = [fp, C.c_size_t, fp, C.c_size_t, fp, C.c_int, C.c_int, ip, fp]
         L.orc_reduce.argtypes = [fp, C.c_size_t, fp, fp, ip, fp, C.c_double, dp]
+        L.orc_reduce_ex.argtypes = [fp, C.c_size_t, fp, fp, ip, fp, C.c_double, C.c_int, dp]
         L.orc_umeyama.argtypes = [dp, dp]
         L.orc_transform_cloud.argtypes = [fp, C.c_size_t, fp, fp]
         L.orc_transform_cloud.restype = None
@@ -185,16 +187,20 @@ def nn(src, tgt, T=np.eye(4), nn_mode=NN_KDTREE, arith=ARITH_FMA):
     return idx, d2
 
 
-def reduce(src, tgt, T, idx, d2, max_corr_dist):
+def reduce(src, tgt, T, idx, d2, max_corr_dist, mode=REDUCE_SEQUENTIAL):
+    """(17,) float64: n, sum p, sum q, sum q p^T (row = q), sum d2 over the pairs (idx >= 0, (double)d2 <= max_corr_dist^2) of
+    p = T * src and q = tgt[idx].  mode SEQUENTIAL (default): one float64 accumulator per sum in source order; EXACT: each sum
+    rounded once from the exact sum of its terms; ABS: the exact sums of |term|."""
     src, ps = _f32(src)
     tgt, pt = _f32(tgt)
     Tc, pT = _f32(_colmajor(T))
     idx = np.ascontiguousarray(idx, np.int32)
     d2 = np.ascontiguousarray(d2, np.float32)
     sums = np.zeros(17, np.float64)
-    lib().orc_reduce(ps, src.shape[0], pt, pT, idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                     d2.ctypes.data_as(C.POINTER(C.c_float)), float(max_corr_dist),
-                     sums.ctypes.data_as(C.POINTER(C.c_double)))
+    if lib().orc_reduce_ex(ps, src.shape[0], pt, pT, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                           d2.ctypes.data_as(C.POINTER(C.c_float)), float(max_corr_dist), int(mode),
+                           sums.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+        raise ValueError(f"orc_reduce_ex: mode {mode}")
     return sums
 
 

@@ -6,6 +6,7 @@
  *   src/icpslam/octree_mapper.cpp:104-117, include/icpslam/octree_mapper.h:53-56.
  */
 #include "icp_oracle.h"
+#include "oracle_internal.h"
 
 #include <float.h>
 #include <math.h>
@@ -556,6 +557,39 @@ int orc_reduce(const float* src, size_t n_s, const float* tgt, const float T[16]
   return 0;
 }
 
+/* The 17 terms of one accepted pair in accumulate_pair's order: 1, p, q, q p^T row by row, d2.  A float
+ * widened and a product of two widened floats are exact in float64. */
+static void pair_terms17(const float* p, const float* q, float d2, double t[ORC_REDUCE_TERMS]) {
+  t[0] = 1.0;
+  for (int a = 0; a < 3; ++a) {
+    t[1 + a] = (double)p[a];
+    t[4 + a] = (double)q[a];
+    for (int b = 0; b < 3; ++b) t[7 + 3 * a + b] = (double)q[a] * (double)p[b];
+  }
+  t[16] = (double)d2;
+}
+
+int orc_reduce_ex(const float* src, size_t n_s, const float* tgt, const float T[16], const int32_t* idx, const float* d2,
+                  double max_corr_dist, int mode, double sums[ORC_REDUCE_TERMS]) {
+  if (mode == ORC_REDUCE_SEQUENTIAL) return orc_reduce(src, n_s, tgt, T, idx, d2, max_corr_dist, sums);
+  if (mode != ORC_REDUCE_EXACT && mode != ORC_REDUCE_ABS) return -1;
+  const double r2 = max_corr_dist * max_corr_dist;
+  xsum* acc = (xsum*)malloc(ORC_REDUCE_TERMS * sizeof(xsum));
+  if (!acc) return -1;
+  for (int k = 0; k < ORC_REDUCE_TERMS; ++k) xsum_init(&acc[k]);
+  for (size_t i = 0; i < n_s; ++i) {
+    if (idx[i] < 0 || !((double)d2[i] <= r2)) continue; /* accept: (double)d2 <= r * r */
+    float p[4];
+    orc_transform_cloud(src + 4 * i, 1, T, p);
+    double t[ORC_REDUCE_TERMS];
+    pair_terms17(p, tgt + 4 * (size_t)idx[i], d2[i], t);
+    for (int k = 0; k < ORC_REDUCE_TERMS; ++k) xsum_add(&acc[k], mode == ORC_REDUCE_ABS ? fabs(t[k]) : t[k]);
+  }
+  for (int k = 0; k < ORC_REDUCE_TERMS; ++k) sums[k] = xsum_value(&acc[k]);
+  free(acc);
+  return 0;
+}
+
 /* ------------------------------------------------------------------------------------------ */
 /* a5: Umeyama without scaling (Eigen::umeyama(src, dst, false))                               */
 /* ------------------------------------------------------------------------------------------ */
@@ -681,6 +715,7 @@ void orc_default_params(orc_params* p) {
   p->precision = ORC_PREC_F64;
   p->arith = ORC_ARITH_FMA;
   p->gicp_sums = ORC_GICP_SUMS_EXACT;
+  p->p2p_sums = ORC_REDUCE_SEQUENTIAL;
 }
 
 int orc_gicp_align(const float* src, size_t n_s, const float* tgt, size_t n_t, const orc_params* P,
@@ -735,6 +770,16 @@ int orc_icp_align(const float* src, size_t n_s, const float* tgt, size_t n_t, co
     nn_all(X, n_s, tgt, n_t, tree, P->arith, idx, d2);
     double sums[17];
     reduce_X(X, n_s, tgt, idx, d2, P->max_correspondence_distance, sums);
+    /* the order-free sums (X = finalf * src here): where the cloud lies kilometres from the origin the sequential sums' rounding
+     * alone moves the float transform, and with it every later iteration (tests/test_gpu_point_to_point_oracle.py) */
+    if (P->p2p_sums == ORC_REDUCE_EXACT && P->precision == ORC_PREC_F64 &&
+        orc_reduce_ex(src, n_s, tgt, finalf, idx, d2, P->max_correspondence_distance, ORC_REDUCE_EXACT, sums) != 0) {
+      kd_free(tree);
+      free(X);
+      free(idx);
+      free(d2);
+      return -1;
+    }
     n_corr = (unsigned)sums[0];
     if ((int)n_corr < P->min_correspondences) {
       state = ORC_NO_CORRESPONDENCES;

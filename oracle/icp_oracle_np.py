@@ -91,6 +91,53 @@ def icp_align(src, tgt, max_iterations=10, transformation_epsilon=1e-6, max_corr
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the 17 point-to-point sums, the second restatement of oracle/icp_oracle.c's orc_reduce_ex: the fma chain of p = T s rounded
+# once per step (no double rounding), the terms widened, math.fsum for the exact sums
+# ---------------------------------------------------------------------------------------------------------------------
+def fma_f32(a, b, c):
+    """fmaf(a, b, c) for float32 arrays of finite values, correctly rounded: a b is exact in float64, TwoSum gives a b + c as a
+    rounded float64 s and its exact error e, and where s is the midpoint of two neighbouring floats e decides the side."""
+    f = np.float32
+    ab = a.astype(np.float64) * b.astype(np.float64)
+    c = c.astype(np.float64)
+    s = ab + c
+    bb = s - ab
+    e = (ab - (s - bb)) + (c - bb)
+    r = s.astype(f)
+    d = r.astype(np.float64)
+    other = np.where(s > d, np.nextafter(r, f(np.inf)), np.nextafter(r, f(-np.inf))).astype(f)
+    tie = (d != s) & ((other.astype(np.float64) + d) * 0.5 == s) & (e != 0.0)
+    return np.where(tie, np.where(e > 0.0, np.maximum(r, other), np.minimum(r, other)), r).astype(f)
+
+
+def transform_cloud_fma(T32, xyz):
+    """p.x = fma(m02, s.z, fma(m01, s.y, fma(m00, s.x, m03))) ... in float32, rows of finite points"""
+    T = np.asarray(T32, np.float32)
+    xyz = np.asarray(xyz, np.float32)
+    out = np.empty((xyz.shape[0], 3), np.float32)
+    for r in range(3):
+        acc = np.full(xyz.shape[0], T[r, 3], np.float32)
+        for k in range(3):
+            acc = fma_f32(np.full(xyz.shape[0], T[r, k], np.float32), xyz[:, k], acc)
+        out[:, r] = acc
+    return out
+
+
+def reduce_sums(src, tgt, T32, idx, d2, max_dist, absolute=False):
+    """(17,) float64: the exact sums (of the magnitudes with absolute) of 1, p, q, q p^T row by row and d2 over the pairs with
+    idx >= 0 and (double)d2 <= max_dist^2, each rounded once (math.fsum)."""
+    import math
+    idx = np.asarray(idx)
+    d2 = np.asarray(d2, np.float32)
+    keep = (idx >= 0) & (d2.astype(np.float64) <= max_dist * max_dist)
+    p = transform_cloud_fma(T32, np.asarray(src, np.float32)[keep, :3]).astype(np.float64)
+    q = np.asarray(tgt, np.float32)[idx[keep], :3].astype(np.float64)
+    cols = [np.ones(p.shape[0])] + [p[:, a] for a in range(3)] + [q[:, a] for a in range(3)]
+    cols += [q[:, a] * p[:, b] for a in range(3) for b in range(3)] + [d2[keep].astype(np.float64)]
+    return np.array([math.fsum(np.abs(c) if absolute else c) for c in cols])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # point-to-plane (pcl::IterativeClosestPointWithNormals + TransformationEstimationPointToPlaneLLS), the second restatement
 # of oracle/p2plane_oracle.c: float32 terms from NumPy casts, math.fsum for the exact sums, the LU in plain Python floats,
 # sin / cos from mpmath at 120 bits rounded once.  Correspondences from the library kd-tree, re-ranked by the float32 key.

@@ -109,6 +109,10 @@ def test_reduce_matches_oracle(ctx, n, seed, r):
     ref = oracle.reduce(src, tgt, T, idx, d2, r)
     assert sums[0] == ref[0]                        # accepted-pair count: exact
     np.testing.assert_allclose(sums, ref, rtol=1e-12, atol=1e-9)
+    # ... and against the order-free value, by the yardstick of DESIGN.md section 3: within 1e-12 sum |terms| of the EXACT sums
+    exact = oracle.reduce(src, tgt, T, idx, d2, r, mode=oracle.REDUCE_EXACT)
+    mag = oracle.reduce(src, tgt, T, idx, d2, r, mode=oracle.REDUCE_ABS)
+    assert sums[0] == exact[0] and np.all(np.abs(sums - exact) <= 1e-12 * mag)
     Tk = ctx.solve(sums)
     np.testing.assert_allclose(Tk, oracle.umeyama(ref), rtol=0, atol=1e-10)
 

@@ -407,6 +407,98 @@ def test_gicp_normals_two_restatements_agree():
     assert np.isfinite(oracle.gicp_normals(few)[~np.isnan(few[:, 0]), :3]).all()
 
 
+# ---- the 17 point-to-point sums: orc_reduce_ex against oracle/icp_oracle_np.py (reduce_sums: math.fsum) ----------------------
+def _reduce_case(kind):
+    src, tgt, _ = synth.make_pair(4000, 5000, seed=31)
+    T = synth.pose_matrix(0.12, -0.07, 0.03, 0.01, -0.02, 0.03).astype(np.float32)
+    if kind == "non_finite":
+        src[::97, 1] = np.nan
+        src[5::101, 0] = np.inf
+        tgt[::89, 2] = np.nan
+        tgt[7::103, 1] = -np.inf
+    elif kind == "3km":                                        # sum q p^T is ~1e7 n while the covariance it feeds is ~1e2 n
+        off = np.array([3000.0, -1200.0, 40.0, 0.0], np.float32)
+        src, tgt = src + off, tgt + off
+        A = np.eye(4)
+        A[:3, 3] = off[:3]
+        T = (A @ T.astype(np.float64) @ np.linalg.inv(A)).astype(np.float32)     # the same small motion, about the clouds
+    elif kind == "centred":                                    # +-pairs about the origin: sum p and sum q cancel to rounding
+        src = np.concatenate([src[:2000], -src[:2000]]).astype(np.float32)
+        tgt = np.concatenate([tgt[:2500], -tgt[:2500]]).astype(np.float32)
+        src[:, 3] = tgt[:, 3] = 1.0
+        T = np.eye(4, dtype=np.float32)
+    return src, tgt, T
+
+
+@pytest.mark.parametrize("kind", ["plain", "non_finite", "3km", "centred"])
+def test_reduce_exact_and_abs_equal_the_fsum_restatement(kind):
+    """orc_reduce_ex's EXACT and ABS sums equal math.fsum over the restated terms bit for bit; SEQUENTIAL is orc_reduce itself and
+    within its n roundings of EXACT; EXACT does not depend on the order of the pairs."""
+    src, tgt, T = _reduce_case(kind)
+    idx, d2 = oracle.nn(src, tgt, T)
+    assert np.array_equal(oracle.transform_cloud(src[idx >= 0], T)[:, :3].view(np.uint32),
+                          onp.transform_cloud_fma(T, src[idx >= 0, :3]).view(np.uint32))
+    for r in (1.0, 0.3):
+        ex = oracle.reduce(src, tgt, T, idx, d2, r, mode=oracle.REDUCE_EXACT)
+        mag = oracle.reduce(src, tgt, T, idx, d2, r, mode=oracle.REDUCE_ABS)
+        assert np.array_equal(ex.view(np.uint64), onp.reduce_sums(src, tgt, T, idx, d2, r).view(np.uint64))
+        assert np.array_equal(mag.view(np.uint64), onp.reduce_sums(src, tgt, T, idx, d2, r, absolute=True).view(np.uint64))
+        seq = oracle.reduce(src, tgt, T, idx, d2, r)
+        assert np.array_equal(seq.view(np.uint64), oracle.reduce(src, tgt, T, idx, d2, r, mode=oracle.REDUCE_SEQUENTIAL).view(np.uint64))
+        n = int(ex[0])
+        assert ex[0] == seq[0] == mag[0] == ((idx >= 0) & (d2.astype(np.float64) <= r * r)).sum() and 100 < n < src.shape[0]
+        assert np.all(np.abs(seq - ex) <= n * 2.0 ** -53 * mag) and np.all(np.abs(ex) <= mag)
+        perm = np.random.default_rng(0).permutation(src.shape[0])
+        assert np.array_equal(ex.view(np.uint64), oracle.reduce(src[perm], tgt, T, idx[perm], d2[perm], r, mode=oracle.REDUCE_EXACT).view(np.uint64))
+    if kind == "non_finite":
+        assert (idx < 0).sum() >= 80
+    if kind in ("3km", "centred"):                             # the case is what it says: a sum far below its terms' magnitudes
+        S = ex[7:16].reshape(3, 3) / n - np.outer(ex[4:7], ex[1:4]) / n ** 2
+        assert np.abs(S).max() < 1e-4 * mag[7:16].max() / n if kind == "3km" else np.abs(ex[1:7]).max() < 1e-3 * mag[1:7].max()
+    with pytest.raises(ValueError):
+        oracle.reduce(src, tgt, T, idx, d2, 1.0, mode=7)
+
+
+def test_alignment_on_exact_sums_is_order_free():
+    """p2p_sums = REDUCE_EXACT: orc_icp_align's loop with each iteration's 17 sums rounded once from the exact sums -- the loop
+    restated here from oracle.nn, oracle.reduce(EXACT) and oracle.umeyama gives the same bits, a permuted source gives the same
+    bits, and about the sensor it is the default's result; 3 km out the default's sequential sums move its own result with the
+    order of the source by more than the parity bound, the exact ones by nothing."""
+    src, tgt, _ = synth.make_pair(6000, 6000, seed=79)
+    exact = oracle.default_params(p2p_sums=oracle.REDUCE_EXACT)
+    assert oracle.default_params().p2p_sums == oracle.REDUCE_SEQUENTIAL
+    perm = np.random.default_rng(0).permutation(src.shape[0])
+    for off in (np.zeros(4, np.float32), np.array([3000.0, -1200.0, 40.0, 0.0], np.float32)):
+        s, t = src + off, tgt + off
+        a = oracle.icp_align(s, t, exact, want_fitness=True, want_trace=True)
+        final = np.eye(4)
+        for k in range(a["iterations"]):
+            Tf = final.astype(np.float32)
+            idx, d2 = oracle.nn(s, t, Tf)
+            sums = oracle.reduce(s, t, Tf, idx, d2, 1.0, mode=oracle.REDUCE_EXACT)
+            assert np.array_equal(sums.view(np.uint64), a["trace"][k]["sums"].view(np.uint64))
+            final = oracle.umeyama(sums) @ final
+        assert np.array_equal(final.astype(np.float32).view(np.uint32), a["T"].view(np.uint32))
+        b = oracle.icp_align(s[perm], t, exact, want_fitness=True)
+        assert np.array_equal(a["T"].view(np.uint32), b["T"].view(np.uint32))
+        assert (a["iterations"], a["state"], a["n_corr"], a["mse"], a["fitness"]) == (b["iterations"], b["state"], b["n_corr"], b["mse"], b["fitness"])
+        seq, seq_again = oracle.icp_align(s, t), oracle.icp_align(s[perm], t)
+        if off[0] == 0:
+            assert np.array_equal(seq["T"].view(np.uint32), a["T"].view(np.uint32)) and np.array_equal(seq["T"], seq_again["T"])
+        else:
+            assert np.linalg.norm(seq["T"][:3, 3].astype(np.float64) - seq_again["T"][:3, 3]) > 1e-3
+
+
+def test_reduce_exact_without_a_pair_is_plus_zero():
+    src, tgt, T = _reduce_case("plain")
+    idx, d2 = oracle.nn(src, tgt, T)
+    for mode in (oracle.REDUCE_EXACT, oracle.REDUCE_ABS, oracle.REDUCE_SEQUENTIAL):
+        z = oracle.reduce(src, tgt, T, idx, d2, 0.0, mode=mode)
+        assert np.array_equal(z.view(np.uint64), np.zeros(17, np.uint64))
+        z = oracle.reduce(src[:0], tgt, T, idx[:0], d2[:0], 1.0, mode=mode)
+        assert np.array_equal(z.view(np.uint64), np.zeros(17, np.uint64))
+
+
 # ---- point-to-plane: oracle/p2plane_oracle.c against oracle/icp_oracle_np.py (p2plane_align) --------------------------------
 P2_CASES = [(s, n) for s, n in zip(range(12), (300, 1000, 3000, 8000) * 3)]
 
