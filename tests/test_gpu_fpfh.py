@@ -274,6 +274,7 @@ def test_cloud_the_grid_refuses(ctx, monkeypatch, capfd):
     monkeypatch.delenv("ICPGPU_DEBUG")
     assert found and int(found[-1]) > 4096
     queries = np.concatenate([cloud[:100], clustered(28, 2)])
+    monkeypatch.setattr(R.S, "TREE_ABOVE", float("inf"))  # 22 000 x 22 000 rows for the SPFH: this test's reference stays the brute form
     for mode in (dict(k=20), dict(radius=0.1)):
         check(ctx, "refused", cloud, normals, queries, **mode)
 

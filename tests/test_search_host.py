@@ -1,5 +1,5 @@
 """The neighbour search's rules (include/icpgpu.h, "neighbour search") without a device: the NumPy restatement against a literal
-per-pair loop, answers known by hand, and the C-ABI's new symbols."""
+per-pair loop, answers known by hand, the tree-narrowed forms against the brute forms, and the C-ABI's new symbols."""
 import math
 import os
 import subprocess
@@ -9,8 +9,10 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+import oracle
 import search_restated as R
 from icpslam_amd import _lib, synth
+from test_gpu_search import KS, SIZES, clustered, lattice, scan, size_of  # (the clouds the device tests use)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 F32 = np.float32
@@ -171,3 +173,170 @@ def test_entry_points_refuse_a_null_context(built):
     assert L.icpgpu_search_size(None, None, None) == _lib.ERR_INVALID_ARG
     assert L.icpgpu_search_knn(None, None, 0, 1, None, None, None) == _lib.ERR_INVALID_ARG
     assert L.icpgpu_search_radius(None, None, 0, 1.0, 0, 0, None, None, None, None) == _lib.ERR_INVALID_ARG
+
+
+# ---- the tree-narrowed forms (knn_tree / radius_tree) are the brute forms, byte for byte --------------------------------------------
+def forms_agree(cloud, queries, ks=(), radii=()):
+    for k in ks:
+        a, b = R.knn(cloud, queries, k, form="tree"), R.knn(cloud, queries, k, form="brute")
+        assert [v.dtype for v in a] == [np.int32, np.float32, np.int32] and same(a, b), ("knn", k)
+    for radius, max_nn in radii:
+        a, b = R.radius(cloud, queries, radius, max_nn, form="tree"), R.radius(cloud, queries, radius, max_nn, form="brute")
+        assert [v.dtype for v in a] == [np.int64, np.int32, np.float32] and same(a, b), ("radius", radius, max_nn)
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_tree_form_scan_sizes(n):
+    """Sizes 1 to 3 000 (k - 1, k, k + 1 among them: k above the finite count, and k + 8 proposals reaching the whole cloud) with two
+    NaN rows where the cloud has them."""
+    for k in KS:
+        cloud = scan(3000)[:size_of(n, k)].copy()
+        cloud[[i for i in (7, 700) if i < len(cloud)], 1] = np.nan
+        forms_agree(cloud, None, ks=(k,), radii=((0.0, 0), (0.3, 0), (0.5, 0)) if k == 20 else ())
+
+
+def test_tree_form_ties_fall_back_to_the_sweep():
+    """The shuffled 9 x 9 x 9 lattice at its points and at cell centres, every point 2 and 70 times, one point 70 times: rows whose
+    decision lies inside a group of equals are answered by the whole-cloud sweep (counted), never by the tree's order."""
+    cloud = lattice(9)
+    cloud = cloud[np.random.default_rng(3).permutation(len(cloud))]
+    centres = cloud[:200].copy()
+    centres[:, :3] += F32(0.5)
+    radii = ((1.0, 0), (math.sqrt(2.0), 0), (1.5, 0), (1.5, 4), (3.0, 0), (3.0, 65))
+    R.tree_stats.update(rows=0, swept=0)
+    forms_agree(cloud, None, ks=KS, radii=radii)
+    assert R.tree_stats["swept"] > 0
+    forms_agree(cloud, centres, ks=KS, radii=radii)
+    for copies in (2, 70):
+        base = scan(400 if copies == 2 else 40)
+        for c in (np.repeat(base, copies, axis=0), np.tile(base, (copies, 1))):
+            forms_agree(c, None, ks=(1, 8, 63, 64), radii=((0.3, 0), (0.3, 64), (2.0, 65)))
+    one = np.tile(F32([4.0, 5.0, -6.0, 1.0]), (70, 1))
+    forms_agree(one, None, ks=(1, 64), radii=((0.1, 0), (0.0, 0)))
+    forms_agree(np.tile(one, (3, 1)), one[:5], ks=(1, 64), radii=((0.1, 0), (0.1, 65)))
+
+
+def test_tree_form_queries_and_points_in_odd_places():
+    """Queries outside the box out to 1e6, isolated returns at 300 to 1 000 m, NaN and inf rows in the cloud and among the queries,
+    the clustered cloud the grid refuses, an empty cloud, no queries, radius 0, and coordinates of 1e19, whose d2 is +inf."""
+    cloud = scan(1025)
+    lo, hi = cloud[:, :3].min(axis=0), cloud[:, :3].max(axis=0)
+    mid = (lo + hi) / 2
+    q = [lo - 0.01, hi + 0.01, lo - 1.5, hi + 1.5, hi + 30.0, mid + np.array([1000.0, 0, 0]), mid - np.array([0, 700.0, 700.0]),
+         np.array([1e6, -1e6, 1e6])]
+    queries = np.ones((len(q), 4), F32)
+    queries[:, :3] = np.array(q, F32)
+    forms_agree(cloud, queries, ks=(1, 20, 64), radii=((0.5, 0), (2.0, 0), (40.0, 0), (1100.0, 0), (1100.0, 100)))
+
+    far = np.ones((5, 4), F32)
+    far[:, :3] = F32([[300, 0, 0], [-450, 200, 5], [0, 700, -3], [600, -600, 40], [1000, 10, 0]])
+    base = scan(2000)
+    isolated = np.concatenate([base[:1000], far[:2], base[1000:], far[2:]])
+    forms_agree(isolated, None, ks=(20,), radii=((0.5, 0),))
+    forms_agree(isolated, isolated[[1000, 2004, 5]], ks=(1, 64), radii=((500.0, 0),))
+
+    holes = scan(1025).copy()
+    rows = [0, 63, 64, 65, 255, 256, 1024]
+    for j, i in enumerate(rows):
+        holes[i, j % 3] = [np.nan, np.inf, -np.inf][j % 3]
+    queries = scan(300, 9).copy()
+    queries[[0, 3, 4, 63, 64, 299], 2] = [np.nan, np.inf, -np.inf, np.nan, np.inf, np.nan]
+    for qq in (None, queries):
+        forms_agree(holes, qq, ks=(8, 64), radii=((0.5, 0), (1e4, 0), (1e4, 1000)))
+        idx = R.knn(holes, qq, 64, form="tree")[0]
+        assert not np.isin(idx, rows).any()
+
+    refused = clustered(22000, 1)
+    refused[7, 1] = np.nan
+    forms_agree(refused, np.concatenate([refused[:100], clustered(28, 2)]), ks=(1, 20, 64), radii=((0.3, 0), (0.3, 8), (1.0, 100)))
+
+    empty = np.empty((0, 4), F32)
+    forms_agree(empty, scan(64), ks=(5,), radii=((10.0, 0),))
+    forms_agree(empty, None, ks=(5,), radii=((10.0, 0),))
+    forms_agree(scan(64), empty, ks=(5,), radii=((1.0, 0),))
+    forms_agree(scan(3000), None, radii=((0.0, 0),))
+    assert R.radius(scan(3000), None, 0.0, form="tree")[0].tolist() == [0] * 3001
+
+    huge = scan(300).copy()
+    huge[::3, :3] *= F32(1e19)  # d2 between a huge point and any other: +inf; among the others: finite
+    huge[1::3, 0] += F32(1e19)
+    with np.errstate(over="ignore", invalid="ignore"):  # (the brute forms' float32 products overflow aloud)
+        forms_agree(huge, None, ks=(1, 8, 64), radii=((0.5, 0), (1e4, 0), (1e18, 0), (1e19, 70)))
+        forms_agree(huge, scan(40, 9), ks=(8, 64), radii=((1e4, 0),))
+        assert np.isinf(R.knn(huge, None, 64, form="tree")[1]).any()
+
+
+@pytest.mark.parametrize("max_nn", [1, 8, 64, 65, 1000])
+def test_tree_form_max_nn(max_nn):
+    cloud = scan(1025).copy()
+    cloud[[5, 900], 0] = np.nan
+    forms_agree(cloud, None, radii=((1e4, max_nn), (0.5, max_nn), (2.0, max_nn)))
+
+
+def test_forms_are_picked_by_size_and_can_be_forced(monkeypatch):
+    """Every caller from before the tree forms keeps the brute form: 3 000 and 6 000 points asked for themselves
+    (test_gpu_search.py, test_cluster_host.py), cluster_restated's windows of 1 024 queries over 22 000 points."""
+    calls = []
+    for name in ("knn_brute", "knn_tree", "radius_brute", "radius_tree"):
+        monkeypatch.setattr(R, name, lambda *a, _n=name: calls.append(_n))
+    small, six, big = scan(3000), np.ones((6000, 4), F32), np.ones((8193, 4), F32)
+    assert max(6000 * 6000, 1024 * 22000) < 8192 * 8192 == R.TREE_ABOVE < 8193 * 8193
+    R.knn(small, None, 8), R.radius(small, None, 0.5), R.knn(six, None, 8), R.radius(six, None, 1.5)
+    R.radius(np.ones((22000, 4), F32), six[:1024], 0.5), R.knn(big[:8192], None, 8)
+    assert calls == ["knn_brute", "radius_brute", "knn_brute", "radius_brute", "radius_brute", "knn_brute"]
+    del calls[:]
+    R.knn(big, None, 8), R.radius(big, None, 0.5, 3), R.knn(small, None, 8, form="tree"), R.radius(big, None, 0.5, form="brute")
+    assert calls == ["knn_tree", "radius_tree", "knn_tree", "radius_brute"]
+    with pytest.raises(ValueError):
+        R.knn(small, None, 8, form="kd")
+
+
+def test_tree_form_refusals():
+    for k in (0, 65):
+        with pytest.raises(R.Refused):
+            R.knn_tree(lattice3(), None, k)
+    for radius, max_nn in ((-1.0, 0), (float("nan"), 0), (float("inf"), 0), (0.3, -1)):
+        with pytest.raises(R.Refused):
+            R.radius_tree(lattice3(), None, radius, max_nn)
+
+
+def test_scan_size_rows_are_decided_without_the_sweep():
+    """A CONDITION of the scan-size device tests (test_gpu_search_scale.py, test_gpu_search_consumers_scale.py), not a measurement:
+    on their inputs -- the bench scan voxel-filtered at 0.2 m, here from the oracle's filter; self-queries, scan queries, the
+    clustered cloud -- fewer than 1 % of the rows fall back to the whole-cloud sweep.  Otherwise the fast reference is the slow one
+    in disguise.  (It is 0 on every one of these.)  One sampled comparison with the brute form at that size closes the loop."""
+    F = oracle.voxel_grid(scan(200000, 6), 0.2)
+    assert len(F) > 16384
+    R.tree_stats.update(rows=0, swept=0)
+
+    def share(what):
+        rows, swept = R.tree_stats["rows"], R.tree_stats["swept"]
+        R.tree_stats.update(rows=0, swept=0)
+        print(f"{what}: {swept} of {rows} rows swept")
+        assert rows > 0 and swept < 0.01 * rows, (what, swept, rows)
+
+    for k in (1, 10, 20, 64):
+        R.knn(F, None, k)
+        share(f"F self k={k}")
+    for radius, max_nn in ((0.3, 0), (0.5, 0), (0.8, 0), (1.0, 0), (1.0, 8), (1.0, 65), (1.2, 0)):
+        R.radius(F, None, radius, max_nn)
+        share(f"F self radius {radius} max_nn={max_nn}")
+    q = scan(8193, 9)
+    for radius in (0.5, 1.0):
+        R.radius(F, q, radius)
+        share(f"F, 8193 scan queries, radius {radius}")
+    q = scan(131073, 9)
+    R.knn(F, q, 8)
+    share("F, 131073 scan queries, k=8")
+    R.radius(F, q, 0.3)
+    share("F, 131073 scan queries, radius 0.3")
+    moved = q.copy()
+    moved[:-40, 2] += F32(1000.0)
+    R.radius(F, moved, 0.3)
+    share("F, 131073 queries of which 131033 are 1 000 m up, radius 0.3")
+    c = clustered(22000, 1)
+    R.knn(c, None, 20)
+    share("clustered 22 000 self k=20")
+    sample = F[::37]
+    assert same(R.knn(F, sample, 64, form="tree"), R.knn(F, sample, 64, form="brute"))
+    assert same(R.radius(F, sample, 1.0, 65, form="tree"), R.radius(F, sample, 1.0, 65, form="brute"))
