@@ -18,6 +18,7 @@
 
 #include "../../include/icpgpu.h"
 #include "icp_kernels.h"
+#include "icp_wave.h"
 
 namespace icpgpu {
 namespace {
@@ -65,7 +66,6 @@ __device__ __forceinline__ int bin_of_angle(float y, float x) {
   return passed;
 }
 
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
 // the three bins of the pair (p, j); false: the pair is skipped
 __device__ __forceinline__ bool pair_bins(const float4 Pp, const float4 Np, const float4 Pj, const float4 Nj, int& b1, int& b2, int& b3) {

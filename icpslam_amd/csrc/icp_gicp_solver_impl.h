@@ -7,7 +7,7 @@
 // published algorithm (PCL is not in /root/reference).  The test oracle holds an independent restatement in plain C.
 //
 // Since round 4 the solver runs in two places: on the host (icp_gicp_solver.cpp: the fallback path, one device evaluation per
-// call) and INSIDE the resident kernel gicp_solve_kernel (icp_gicp.hip: the whole BFGS run of an outer iteration without a
+// call) and INSIDE the resident kernel gicp_solve_kernel (icp_gicp_solve_device.h: the whole BFGS run of an outer iteration without a
 // host round trip).  Both instantiate the templates below -- same operations in the same order, IEEE float64 (and float32 in
 // apply_state), no contraction (-ffp-contract=off), sines and cosines from icp_trig.h -- so both produce the same bits.
 // The evaluator is a template parameter: bool eval(const V6& x, Eval& out) fills value and gradient (one device reduction
@@ -42,7 +42,7 @@ ICPGPU_HDI inline double dmax(double a, double b) { return a < b ? b : a; }
 
 // The six sine / cosine pairs of a state: of the float half angles (applyState's quaternions) and of the double angles
 // (computeRDerivative).  They depend on x only, so an evaluation computes them once -- the device six lanes at a time
-// (icp_gicp.hip), the host one after the other; the same correctly rounded values either way (icp_trig.h).
+// (icp_gicp_solve_device.h), the host one after the other; the same correctly rounded values either way (icp_trig.h).
 struct Trig6 {
   float shr, chr, shp, chp, shy, chy;  // sin / cos of 0.5f * (float) roll, pitch, yaw
   double sr, cr, sp, cp, sy, cy;       // sin / cos of roll, pitch, yaw

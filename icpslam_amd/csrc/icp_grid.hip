@@ -112,34 +112,12 @@ __global__ __launch_bounds__(256) void grid_count_kernel(const float4* __restric
   rank[i] = c >= 0 ? atomicAdd(&counts[c], 1) : 0;
 }
 
-// ---- exclusive scan of the per-cell counts (three small kernels) ---------------------------------------------
-__device__ __forceinline__ int block_exclusive_scan_256(int v, int* total) {
-  // 256 threads; returns the exclusive prefix of v, *total = block sum (valid in all threads)
-  __shared__ int wsum[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += t;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    if (w < wave) base += wsum[w];
-    tot += wsum[w];
-  }
-  __syncthreads();
-  *total = tot;
-  return base + incl - v;
-}
-
+// ---- exclusive scan of the per-cell counts (three small kernels; the scans themselves: icp_wave.h) -----------
 constexpr int SCAN_PER_THREAD = kScanItems / 256;  // 16
 
 __global__ __launch_bounds__(256) void scan_sums_kernel(const int* __restrict__ counts, int n, int* __restrict__ block_sums,
                                                         int* __restrict__ stats) {
+  __shared__ int wsum[4];
   const int base = blockIdx.x * kScanItems + threadIdx.x * SCAN_PER_THREAD;
   int s = 0, m = 0;
   unsigned long long sq = 0;  // sum of squared populations: sq / sum = the population a random POINT sees in its cell
@@ -151,7 +129,7 @@ __global__ __launch_bounds__(256) void scan_sums_kernel(const int* __restrict__ 
     sq += (unsigned long long)v * (unsigned long long)v;
   }
   int tot;
-  (void)block_exclusive_scan_256(s, &tot);
+  (void)wg_exclusive_scan<4>(s, wsum, &tot);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     m = max(m, __shfl_down(m, off, 64));
@@ -185,11 +163,7 @@ __global__ __launch_bounds__(1024) void scan_top_kernel(int* __restrict__ block_
   // exclusive scan of the 1024 slice sums: 64-lane shuffle scans + one scan of the 16 wave totals
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int incl = s;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += t;
-  }
+  ICPGPU_WAVE_INCLUSIVE_SCAN(incl, lane);
   __shared__ int wtot[16];
   if (lane == 63) wtot[wave] = incl;
   __syncthreads();
@@ -210,6 +184,7 @@ __global__ __launch_bounds__(1024) void scan_top_kernel(int* __restrict__ block_
 
 __global__ __launch_bounds__(256) void scan_apply_kernel(int* __restrict__ counts, int n, const int* __restrict__ block_sums,
                                                          const int* __restrict__ stats) {
+  __shared__ int wsum[4];
   const int base = blockIdx.x * kScanItems + threadIdx.x * SCAN_PER_THREAD;
   int v[SCAN_PER_THREAD], s = 0;
 #pragma unroll
@@ -218,7 +193,7 @@ __global__ __launch_bounds__(256) void scan_apply_kernel(int* __restrict__ count
     s += v[k];
   }
   int tot;
-  int run = block_exclusive_scan_256(s, &tot) + block_sums[blockIdx.x];
+  int run = wg_exclusive_scan<4>(s, wsum, &tot) + block_sums[blockIdx.x];
 #pragma unroll
   for (int k = 0; k < SCAN_PER_THREAD; ++k) {
     if (base + k < n) counts[base + k] = run;

@@ -6,16 +6,13 @@
 
 #include "icp_device.h"
 #include "icp_kernels.h"
+#include "icp_wave.h"
 
 #ifndef ICPGPU_BALL_PRUNING
 #define ICPGPU_BALL_PRUNING 1  // 0: walk whole cubes (the first version; for A/B measurements)
 #endif
 
 namespace icpgpu {
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-  return isfinite(x) && isfinite(y) && isfinite(z);
-}
 
 // Cell coordinates: the SAME float expression bins targets and queries, and floor((x - o) * inv_h) is monotone in x,
 // which is what the early-exit proof needs.

@@ -25,11 +25,6 @@ namespace {
 
 constexpr int ISS_BLOCK = 256, ISS_WAVES = ISS_BLOCK / 64;
 
-__device__ __forceinline__ double shfl_xor_double(double v, int j) {  // a double moves in two halves
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return __longlong_as_double((long long)shfl_xor_key(b, j));
-}
-
 // n_salient and scatter6 are zero before: what a non-finite point and a point with too few neighbours keep (n_salient of the latter
 // is written).
 __global__ __launch_bounds__(ISS_BLOCK) void iss_scatter_kernel(const float4* __restrict__ cloud, int n, const float4* __restrict__ sorted,
@@ -69,8 +64,8 @@ __global__ __launch_bounds__(ISS_BLOCK) void iss_scatter_kernel(const float4* __
 #pragma unroll
     for (int j = 32; j > 0; j >>= 1) {  // (TwoSum is exact in either order: every lane holds the same pair after each step)
       DD o;
-      o.hi = shfl_xor_double(a.hi, j);
-      o.lo = shfl_xor_double(a.lo, j);
+      o.hi = shfl_xor_f64(a.hi, j);
+      o.lo = shfl_xor_f64(a.lo, j);
       a = dd_add(a, o);
     }
     s[e] = a.hi + a.lo;

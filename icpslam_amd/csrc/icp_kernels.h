@@ -231,7 +231,7 @@ hipError_t launch_nn_brute_few(const float4* src, const int* list, const int* co
 hipError_t launch_nn_brute_list(const float4* src, const int* list, int n_list, const float4* tgt, int n_t,
                                 const Xform& T, int num_cus, unsigned long long* keys, hipStream_t stream);
 
-// ---- GICP mode (icp_gicp.hip), SURVEY.md 8(f1) ----------------------------------------------------------------
+// ---- GICP mode (icp_gicp_cov.hip, icp_gicp.hip, icp_gicp_solve*.hip), SURVEY.md 8(f1) ----------------------------------------------------------------
 static constexpr int kGicpK = 20;              // PCL k_correspondences_
 static constexpr double kGicpEpsilon = 1e-3;   // PCL gicp_epsilon_
 struct Rot3d {
@@ -247,14 +247,14 @@ hipError_t launch_gicp_covariances_brute(const float4* cloud, int n, double* cov
 hipError_t launch_gicp_covariances(const float4* cloud, int n, const float4* sorted, const int* cell_start,
                                    const GridDesc& g, double* cov6, hipStream_t stream, int* list = nullptr, bool list_counters_zero = false,
                                    float4* normals = nullptr);
-// (list: 2 n + 2 ints of scratch -- the points the selecting kernel hands to the far-field and the streaming kernel; icp_gicp.hip.
+// (list: 2 n + 2 ints of scratch -- the points the selecting kernel hands to the far-field and the streaming kernel; icp_gicp_cov.hip.
 //  list_counters_zero: list[0] and list[1] are zero -- true from the second cloud on the same buffer: the last kernel leaves them so)
 // maha6[i] = upper triangle of (C_t[j] + R C_s[i] R^T)^-1 for every source point whose key passes d2 < thr
 hipError_t launch_gicp_mahalanobis(int n_s, const unsigned long long* keys, float thr, const Rot3d& R, const double* cov_s,
                                    const double* cov_t, double* maha6, hipStream_t stream);
 // One BFGS function/gradient evaluation: at most kGicpDirectBlocks workgroups, each stores its partial sums straight into
 // host-mapped memory (host_partials[block * kGicpPartialStride + ...]: [0] = m, [1..13] = high parts of sum r^T M r, sum M r
-// (3), sum (base p)(M r)^T (9), [14] = sum d2, [16..28] = the 13 low parts -- the sums are double-double, see icp_gicp.hip)
+// (3), sum (base p)(M r)^T (9), [14] = sum d2, [16..28] = the 13 low parts -- the sums are double-double, see icp_gicp_device.h)
 // followed by host_flags[block] = seq; the host adds the partials in block order.  blocks = gicp_direct_blocks(n_s, share).
 // Since round 2 every value travels WITH its sequence number: entry e of a block is the 16-byte pair {value, tag} at doubles
 // [2e, 2e + 1], written by ONE 16-byte store -- a pair is never seen half-written, so no flag and no system-scope release
@@ -280,7 +280,7 @@ hipError_t launch_gicp_cost_direct(int blocks, const float4* src, int n_s, const
 // memory the host writes through the BAR (cmd: 12 floats of T, then the sequence number), evaluates, answers through
 // host_partials / host_flags like the direct kernel (flag = seq_hi << 32 | sequence number) and leaves on sequence number
 // kGicpServerExit (acknowledged by host_flags[0] = ~0) or after 50 ms without a command.
-// The device solver (icp_gicp.hip: gicp_solve_kernel): the whole BFGS run of an outer iteration inside one resident kernel.
+// The device solver (icp_gicp_solve_device.h: gicp_solve_kernel): the whole BFGS run of an outer iteration inside one resident kernel.
 // slots: gicp_solve_slot_bytes(blocks) of FINE-GRAINED device memory; host_out: gicp_solve_out_granules() granules (16 B each) of
 // the host mailbox -- granule 0 the status (gicp::Status), 1..6 the state, 7 m, 8 sum d2, 9 f at the start, 10 evaluations --
 // each carrying number seq0 and a checksum (gicp_granule_read).  Evaluation e of the run uses number seq0 + e.

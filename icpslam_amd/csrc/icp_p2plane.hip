@@ -4,7 +4,7 @@
 //
 //   p2plane_reduce_kernel  over the keys of a correspondence sweep (icp_grid.hip's key-writing search or the brute-force keys):
 //                          pairs with d2 <= thr (the point-to-point accept rule); per pair s = T * source
-//                          (float32, xform_point), d = target, n = target normal (float4, icp_gicp.hip: gicp_normal_finish_kernel
+//                          (float32, xform_point), d = target, n = target normal (float4, icp_gicp_cov.hip: gicp_normal_finish_kernel
 //                          or the caller's) and the terms of estimateRigidTransformation in float, widened to double:
 //                            a = nz sy - ny sz,  b = nx sz - nz sx,  c = ny sx - nx sy
 //                            r = ((((nx dx + ny dy) + nz dz) - nx sx) - ny sy) - nz sz
@@ -25,6 +25,7 @@
 
 #include "icp_device.h"
 #include "icp_kernels.h"
+#include "icp_wave.h"
 
 namespace icpgpu {
 namespace {
@@ -32,8 +33,6 @@ namespace {
 constexpr int PP_BLOCK = 256;
 constexpr int PP_FINAL_BLOCK = 1024;
 constexpr int kP2planeMaxBlocks = 1024;
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
 // one row (v, r) of the linear system into the 27 sums behind count and sum d2: the upper triangle of v v^T row by row, then v r
 __device__ __forceinline__ void accumulate_row(double (&acc)[kP2planeTerms], const double (&v)[6], double r) {

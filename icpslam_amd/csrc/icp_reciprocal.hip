@@ -42,19 +42,6 @@ __device__ __forceinline__ bool key_alive(unsigned long long key, float thr) {
   return (unsigned int)key != 0xFFFFFFFFu && __uint_as_float((unsigned int)(key >> 32)) <= thr;
 }
 
-// the sum of the workgroup's lane counts into *counter (one device atomic per workgroup); every thread of the workgroup calls it
-__device__ __forceinline__ void block_count_add(unsigned int lane_count, unsigned int* counter) {
-  __shared__ unsigned int total;
-  if (threadIdx.x == 0) total = 0u;
-  __syncthreads();
-  unsigned int v = lane_count;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  if ((threadIdx.x & 63) == 0 && v) atomicAdd(&total, v);
-  __syncthreads();
-  if (threadIdx.x == 0 && total) atomicAdd(counter, total);
-}
-
 // the cell a transformed source point is binned into: -1 = dropped (not finite, or more than `reach` cells outside the box)
 __device__ __forceinline__ int bin_of(const GridDesc& g, int reach, float x, float y, float z) {
   if (!finite3(x, y, z)) return -1;

@@ -25,6 +25,7 @@
 // in, pairs out, the cut's bits) stay in device memory behind its histograms (RejectState) until the host asks for them.
 #include "icp_device.h"
 #include "icp_kernels.h"
+#include "icp_wave.h"
 
 namespace icpgpu {
 namespace {
@@ -151,19 +152,6 @@ __global__ __launch_bounds__(RJ_BLOCK) void reject_hist_kernel(const unsigned lo
   unsigned int* hist = state + (P == 0 ? kRejectHist0 : P == 1 ? kRejectHist1 : kRejectHist2);
   for (int b = threadIdx.x; b < kBins; b += RJ_BLOCK)
     if (bins[b]) atomicAdd(&hist[b], bins[b]);
-}
-
-// the sum of the workgroup's lane counts into *counter (one device atomic per workgroup)
-__device__ __forceinline__ void block_count_add(unsigned int lane_count, unsigned int* counter) {
-  __shared__ unsigned int total;
-  if (threadIdx.x == 0) total = 0u;
-  __syncthreads();
-  unsigned int v = lane_count;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  if ((threadIdx.x & 63) == 0 && v) atomicAdd(&total, v);
-  __syncthreads();
-  if (threadIdx.x == 0 && total) atomicAdd(counter, total);
 }
 
 __global__ __launch_bounds__(RJ_BLOCK) void reject_cut_apply_kernel(unsigned long long* __restrict__ keys, int n, float thr, RejectStage S,

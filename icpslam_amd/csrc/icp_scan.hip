@@ -4,7 +4,8 @@
 // its extraction, the sample-consensus alignment's inliers, the ISS keypoints).
 //   * exclusive scan: the map's order-preserving compactions (icp_map.hip: winners of an insert, the nn cloud, its distinct
 //     points) and the voxel filter's sort path (icp_voxel.hip) -- three launches: tile sums, one workgroup over the tile
-//     sums, apply.  Same structure as the cell-table scan of icp_grid.hip, for arbitrary in / out arrays.
+//     sums, apply.  The workgroup scans are icp_wave.h's, the ones the cell-table scan of icp_grid.hip uses (that one fuses
+//     the occupancy statistics); these take arbitrary in / out arrays.
 //   * radix sort: the voxel filter's FALLBACK path only (clouds over 2 M points, a voxel bucket that exceeds the group
 //     kernel's LDS capacity, int32 index wrap-around): PCL's VoxelGrid sorts (cell index, point index) pairs and adds the
 //     members of a cell in input order, so the sort must be stable.  4 bits per pass: tile histogram (digit-major) -> scan
@@ -12,42 +13,21 @@
 #include <hip/hip_runtime.h>
 
 #include "icp_kernels.h"
+#include "icp_wave.h"
 
 namespace icpgpu {
 namespace {
 
 constexpr int SC_TILE = 4096, SC_PER = SC_TILE / 256;
 
-// exclusive prefix of v over the 256 threads of the workgroup; *total = the workgroup's sum
-__device__ __forceinline__ int wg_exclusive_scan_256(int v, int* total) {
-  __shared__ int wsum[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += t;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    if (w < wave) base += wsum[w];
-    tot += wsum[w];
-  }
-  __syncthreads();
-  *total = tot;
-  return base + incl - v;
-}
-
 __global__ __launch_bounds__(256) void scan_tile_sums_kernel(const int* __restrict__ in, int n, int* __restrict__ tile_sums) {
+  __shared__ int wsum[4];
   const long long base = (long long)blockIdx.x * SC_TILE + threadIdx.x * SC_PER;
   int s = 0;
 #pragma unroll
   for (int k = 0; k < SC_PER; ++k) s += (base + k < n) ? in[base + k] : 0;
   int tot;
-  (void)wg_exclusive_scan_256(s, &tot);
+  (void)wg_exclusive_scan<4>(s, wsum, &tot);
   if (threadIdx.x == 0) tile_sums[blockIdx.x] = tot;
 }
 
@@ -59,11 +39,7 @@ __global__ __launch_bounds__(1024) void scan_tiles_kernel(int* __restrict__ tile
   for (int k = lo; k < hi; ++k) s += tile_sums[k];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int incl = s;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += t;
-  }
+  ICPGPU_WAVE_INCLUSIVE_SCAN(incl, lane);
   __shared__ int wtot[16];
   if (lane == 63) wtot[wave] = incl;
   __syncthreads();
@@ -84,6 +60,7 @@ __global__ __launch_bounds__(1024) void scan_tiles_kernel(int* __restrict__ tile
 
 __global__ __launch_bounds__(256) void scan_apply_tiles_kernel(const int* __restrict__ in, int* __restrict__ out, int n,
                                                                const int* __restrict__ tile_sums) {
+  __shared__ int wsum[4];
   const long long base = (long long)blockIdx.x * SC_TILE + threadIdx.x * SC_PER;
   int v[SC_PER], s = 0;
 #pragma unroll
@@ -92,7 +69,7 @@ __global__ __launch_bounds__(256) void scan_apply_tiles_kernel(const int* __rest
     s += v[k];
   }
   int tot;
-  int run = wg_exclusive_scan_256(s, &tot) + tile_sums[blockIdx.x];
+  int run = wg_exclusive_scan<4>(s, wsum, &tot) + tile_sums[blockIdx.x];
 #pragma unroll
   for (int k = 0; k < SC_PER; ++k) {
     if (base + k < n) out[base + k] = run;
@@ -168,11 +145,7 @@ __global__ __launch_bounds__(256) void radix_scatter_kernel(const int* __restric
       for (int c = 0; c < 4; ++c) {
         const int x = cnt[q][c * 64 + lane];
         int incl = x;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          const int y = __shfl_up(incl, off, 64);
-          if (lane >= off) incl += y;
-        }
+        ICPGPU_WAVE_INCLUSIVE_SCAN(incl, lane);
         cnt[q][c * 64 + lane] = carry + incl - x;
         carry += __shfl(incl, 63, 64);
       }

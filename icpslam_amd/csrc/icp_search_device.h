@@ -1,6 +1,6 @@
 // icp_search_device.h -- device helpers of the neighbour search that more than one unit walks a ball with (internal): the keys and
 // the walk of icp_search.hip's radius search, shared with icp_cluster.hip and icp_iss.hip, and the keyed selection of its k-nearest search, shared
-// with icp_feature.hip.  Moved here unchanged from icp_search.hip.
+// with icp_feature.hip.  (The lane moves and finite3 underneath: icp_wave.h; cell_of: icp_grid_device.h.)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -18,15 +18,9 @@ constexpr int kSearchOutside = 64;  // cells a query may lie outside the grid an
 
 __device__ __forceinline__ u64 make_key(float d, unsigned int index) { return ((u64)__float_as_uint(d) << 32) | index; }
 
-__device__ __forceinline__ u64 shfl_xor_key(u64 v, int j) {  // a key moves in two halves
-  const unsigned int lo = (unsigned int)__shfl_xor((int)(unsigned int)v, j, 64), hi = (unsigned int)__shfl_xor((int)(unsigned int)(v >> 32), j, 64);
-  return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 readlane_key(u64 v, int lane) {  // lane must be wave-uniform
-  const unsigned int lo = (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)v, lane),
-                     hi = (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)(v >> 32), lane);
-  return ((u64)hi << 32) | lo;
-}
+// a key moves between lanes in two halves (icp_wave.h)
+__device__ __forceinline__ u64 shfl_xor_key(u64 v, int j) { return shfl_xor_u64(v, j); }
+__device__ __forceinline__ u64 readlane_key(u64 v, int lane) { return readlane_u64(v, lane); }  // lane must be wave-uniform
 __device__ __forceinline__ u64 key_min(u64 a, u64 b) { return a < b ? a : b; }
 __device__ __forceinline__ u64 key_max(u64 a, u64 b) { return a < b ? b : a; }
 

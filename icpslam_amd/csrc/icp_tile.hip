@@ -62,15 +62,6 @@ __device__ __forceinline__ float bf16_hi(unsigned int p) { return __uint_as_floa
 __device__ __forceinline__ unsigned int dup_lo(unsigned int p) { return __builtin_amdgcn_perm(p, p, 0x01000100u); }
 __device__ __forceinline__ unsigned int dup_hi(unsigned int p) { return __builtin_amdgcn_perm(p, p, 0x03020302u); }
 
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(v, off, 64);
-    if (lane >= off) v += o;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(TS_BLOCK) void nn_tile_kernel(const float4* __restrict__ src_morton, int n_q, Xform T,
                                                            const float4* __restrict__ sorted,
                                                            const int* __restrict__ cell_start, GridDesc g,
@@ -231,7 +222,7 @@ __global__ __launch_bounds__(TS_BLOCK) void nn_tile_kernel(const float4* __restr
       mine[u] = local;
       local += len;
     }
-    const int incl = wave_incl_scan(local, lane);
+    const int incl = wave_inclusive_scan(local, lane);
     if (lane == 63) s_wsum[wave] = incl;
     __syncthreads();
     int before = incl - local, total = 0;

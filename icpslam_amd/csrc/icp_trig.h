@@ -2,7 +2,7 @@
 //
 // Why: GICP's inner BFGS (pcl::GeneralizedIterativeClosestPoint::estimateRigidTransformationBFGS, reached from
 // /root/reference/src/icpslam/icp_odometer.cpp:198) is a chaotic consumer of its inputs -- an ulp flips a line-search decision
-// -- and since round 4 it runs INSIDE a kernel (icp_gicp.hip: gicp_solve_kernel) as well as on the host (the fallback path).
+// -- and since round 4 it runs INSIDE a kernel (icp_gicp_solve_device.h: gicp_solve_kernel) as well as on the host (the fallback path).
 // PCL takes its sines and cosines from the platform's libm (Eigen::AngleAxisf: std::cos/std::sin(float); computeRDerivative:
 // std::cos/std::sin(double)); libm results are not portable: glibc 2.35's sin / cos / sinf / cosf differ from the correctly
 // rounded value on 0.2 % / 0.1 % / 1.8 % / 0.7 % of random arguments (measured, EXPERIMENTS.md section 9-f1), and the device's

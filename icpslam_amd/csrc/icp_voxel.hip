@@ -24,6 +24,7 @@
 
 #include "icp_kernels.h"
 #include "icp_voxel_plan.h"
+#include "icp_wave.h"
 
 namespace icpgpu {
 namespace {
@@ -237,29 +238,6 @@ __global__ __launch_bounds__(VX_BLOCK) void voxel_hist_kernel(const float4* __re
   }
 }
 
-// exclusive scan over the workgroup's 1024 threads (one value each); *total = the sum
-__device__ __forceinline__ int block_exclusive_scan_1024(int v, int* wsum /* 16 ints of LDS */, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int base = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < VX_BLOCK / 64; ++w) {
-    const int s = wsum[w];
-    base += w < wave ? s : 0;
-    all += s;
-  }
-  __syncthreads();  // wsum may be reused
-  if (total) *total = all;
-  return base + inc - v;
-}
-
 __global__ __launch_bounds__(VX_BLOCK) void voxel_scatter_kernel(const int* __restrict__ keys, const int* __restrict__ relpos,
                                                                  int n, unsigned int cpb, int nbins, const int* __restrict__ hist,
                                                                  int n_groups, int4* __restrict__ group_range,
@@ -292,7 +270,7 @@ __global__ __launch_bounds__(VX_BLOCK) void voxel_scatter_kernel(const int* __re
 #pragma unroll
   for (int k = 0; k < VX_PER; ++k) s += v[k];
   int total = 0;
-  int off = block_exclusive_scan_1024(s, wsum, &total);
+  int off = wg_exclusive_scan<VX_BLOCK / 64>(s, wsum, &total);
 #pragma unroll
   for (int k = 0; k < VX_PER; ++k) {
     st[threadIdx.x * VX_PER + k] = off;   // (buckets beyond nbins: = total)
@@ -550,7 +528,7 @@ __global__ __launch_bounds__(VX_BLOCK) void voxel_group_kernel(const float4* __r
     }
     if (!ok) *status = 2;
     int total = 0;
-    (void)block_exclusive_scan_1024(part, wsum, &total);
+    (void)wg_exclusive_scan<VX_BLOCK / 64>(part, wsum, &total);
     return __syncthreads_or(ok ? 0 : 1) ? -1 : total;  // -1: no offset (whatever the stale words held must not place a write)
   };
   if (m <= 0 || m > VX_CAP) {
@@ -629,7 +607,7 @@ __global__ __launch_bounds__(VX_BLOCK) void voxel_group_kernel(const float4* __r
     n_heads += head[k] ? 1 : 0;
   }
   int heads = 0;
-  int rank = block_exclusive_scan_1024(n_heads, wsum, &heads);  // (its barriers: the composites are dead from here on)
+  int rank = wg_exclusive_scan<VX_BLOCK / 64>(n_heads, wsum, &heads);  // (its barriers: the composites are dead from here on)
   publish(heads);
 #pragma unroll
   for (int k = 0; k < OWN; ++k) {
