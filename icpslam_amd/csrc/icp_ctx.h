@@ -5,7 +5,9 @@
 //   icpgpu_p2p.cpp      point-to-point ICP: sweeps (search + fused reduction), the mailbox, the resumable run, align / fitness
 //   icpgpu_reject.cpp   the correspondence rejectors: the chain, its sweep, icpgpu_correspondences
 //   icpgpu_gicp.cpp     GICP: covariances, the evaluation server, the BFGS outer loop
-//   icpgpu_batch.cpp    icpgpu_align_batch: lock-step groups and the round-robin scheduler
+//   icpgpu_batch.cpp    icpgpu_align_batch: provisioning, the host threads, GICP's runs and the round-robin scheduler
+//   icpgpu_batch_lockstep.cpp  ... its point-to-point lock-step groups (icp_batch.h: what the two share; icp_batch_plan.h: a
+//                       call's threads, depth and groups)
 //   icpgpu_p2plane.cpp  point-to-plane ICP (plain and symmetric): the clouds' normals, the 29-sum reduction, the solve
 //   icpgpu_ndt.cpp      NDT: the target's cells, the derivative passes, Newton with either step rule
 //   icpgpu_voxel.cpp    the voxel-grid filter's host side
@@ -192,7 +194,7 @@ using namespace icpgpu_impl;
 constexpr size_t kMaxServerWorkers = 8;
 
 // ICPGPU_GICP_DEVICE: where GICP's inner BFGS runs -- 0: on the host over the evaluation server; 1: inside a resident kernel
-// (icp_gicp.hip: gicp_solve_kernel); unset or "auto": MEASURED per context.  Same bits either way (tests/test_gpu_gicp.py,
+// (icp_gicp_solve_device.h: gicp_solve_kernel, instantiated by the icp_gicp_solve*.hip units); unset or "auto": MEASURED per context.  Same bits either way (tests/test_gpu_gicp.py,
 // 1 200 campaign registrations through both).  Which one is faster depends on the box: the host loop's evaluation is 6.8-8.3 us
 // with the box's PCIe and CPU, the kernel's 7.2-7.7 us wherever it runs (EXPERIMENTS.md section 9-f1) -- so a context times a few
 // outer iterations each way (align_gicp) and keeps the faster; runs the one-XCD variant cannot take stay on the host.
@@ -327,7 +329,7 @@ struct icpgpu_ctx {
   unsigned long long* h_gicp_flags_dev = nullptr;
   // resident evaluation server (icp_gicp.hip): its command line, fine-grained device memory the host writes through the BAR
   unsigned int* gicp_cmd = nullptr;
-  // the device solver (icp_gicp.hip: gicp_solve_kernel): the workgroups' partial-sum slots (fine-grained device memory), the
+  // the device solver (icp_gicp_solve_device.h: gicp_solve_kernel): the workgroups' partial-sum slots (fine-grained device memory), the
   // result granules (host, mapped), the number the next run's granules carry, and whether the path is (still) in use
   unsigned long long* gicp_slots = nullptr;
   volatile unsigned long long* h_solve = nullptr;

@@ -1,5 +1,5 @@
 // icpgpu_gicp.cpp -- GICP mode behind icpgpu_align (pcl::GeneralizedIterativeClosestPoint, what the reference instantiates at
-// icp_odometer.cpp:188 and octree_mapper.cpp:104; kernels: icp_gicp.hip, solver: icp_gicp_solver.cpp).
+// icp_odometer.cpp:188 and octree_mapper.cpp:104; kernels: icp_gicp_cov.hip, icp_gicp.hip, icp_gicp_solve*.hip, solver: icp_gicp_solver.cpp).
 #include "icp_ctx.h"
 
 
@@ -227,7 +227,7 @@ int resolve_cov_timing(icpgpu_ctx* c) {
 
 // The host's merge of an evaluation's answers (validated lines of nblk workgroups, icp_kernels.h: gicp_line_value -- value s of a
 // block sits at word 8 (s / 7) + s % 7: [0] m, [1..13] the high parts, [14] sum d2, [15..27] the low parts): workgroup by workgroup,
-// in double-double like the kernel (icp_gicp.hip) -- (hi, lo) += (bh, bl) is a TwoSum on the high parts, the small parts in plain
+// in double-double like the kernels (icp_gicp_device.h) -- (hi, lo) += (bh, bl) is a TwoSum on the high parts, the small parts in plain
 // float64 -- the 13 sums rounded once at the end.  sums15: [0] m, [1..13], [14] sum d2.
 // Round 6: the thirteen accumulators take the same steps on different numbers, so they advance together as four vectors of four
 // doubles (three lanes idle): element-wise IEEE operations without contraction = the bits of the scalar loop (20 000 random merges

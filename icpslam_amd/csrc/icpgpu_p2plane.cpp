@@ -4,7 +4,7 @@
 // search GICP uses, or the brute-force keys) -> p2plane_reduce_kernel + p2plane_final_kernel (icp_p2plane.hip) store the 29 sums as
 // result pairs into the pinned host mailbox -> the host polls them, solves the 6 x 6 system (partial-pivot LU, float64), builds
 // the incremental transform and runs the point-to-point loop's convergence test (icp_solver.cpp) -> next search.  The target's
-// normals are the caller's or GICP's plane, estimated once per target cloud by the covariance kernels (icp_gicp.hip).
+// normals are the caller's or GICP's plane, estimated once per target cloud by the covariance kernels (icp_gicp_cov.hip).
 #include "icp_ctx.h"
 #include "icp_trig.h"
 

@@ -506,6 +506,86 @@ def test_batch_of_different_sizes_equals_single_alignments(depth, monkeypatch):
     whole(got[0], ref, fitness=False)
 
 
+# ---- the batch's schedulers: every pair, whichever thread, group, slot or scheduler takes it, is the single alignment ---------------------
+@functools.lru_cache(maxsize=None)
+def scheduler_case(lockstep):
+    """seven pairs of about 6000 x 7000 points, an empty source and an empty target, and what a single alignment (with its fitness)
+    makes of each.  One of the seven has a target one point short of kGridMinTarget: AUTO gives it no grid.
+    lockstep: the twelve pairs of the several-groups test, in the order in which one thread's groups take them.  A source below
+    32768 points (use_quad, icp_grid.hip) never enters a lock-step launch, so three pairs of batch_case's sizes are added; and one
+    of the seven gets a source of kOrderSourceMin points (the cell-ordered source is past the lock-step path)."""
+    src, tgt, _ = synth.make_pair(6300, 7300, seed=502)
+    srcs = [src[40 * k: 40 * k + 6000 + 7 * k].copy() for k in range(7)]
+    tgts = [tgt[30 * k: 30 * k + 7000 + 11 * k].copy() for k in range(7)]
+    tgts[2] = tgts[2][:GRID_MIN_TARGET - 1].copy()
+    empty = np.zeros((0, 4), F)
+    if not lockstep:
+        srcs[3:3], tgts[3:3] = [empty], [tgts[0].copy()]               # an empty source in the middle, an empty target at the end
+        srcs, tgts = srcs + [srcs[0].copy()], tgts + [empty]
+        assert len(srcs) == 9
+    else:
+        big_s, big_t = big_pair()
+        srcs[4], tgts[4] = big_s[:ORDER_MIN].copy(), big_t[:7000].copy()
+        lock_s = [big_s[:33000].copy(), big_s[20000:60001].copy(), big_s[60000:125536].copy()]
+        lock_t = [big_t.copy(), big_t[:12000].copy(), big_t[3000:20001].copy()]
+        assert all(QUAD_MIN <= s.shape[0] < ORDER_MIN and t.shape[0] >= GRID_MIN_TARGET for s, t in zip(lock_s, lock_t))
+        # taken in this order, two pairs to a group from the eighth on: (lock, lock), (lock, no grid), (empty target)
+        srcs = [srcs[0], srcs[1], srcs[3], empty, srcs[4], srcs[5], srcs[6], lock_s[0], lock_s[1], lock_s[2], srcs[2], srcs[0].copy()]
+        tgts = [tgts[0], tgts[1], tgts[3], tgts[0].copy(), tgts[4], tgts[5], tgts[6], lock_t[0], lock_t[1], lock_t[2], tgts[2], empty]
+        assert len(srcs) == 12 and srcs[4].shape[0] >= ORDER_MIN and tgts[10].shape[0] < GRID_MIN_TARGET
+    single = []
+    with _ctx(max_iterations=3) as ctx:
+        for s, t in zip(srcs, tgts):
+            ctx.set_target(t)
+            ctx.set_source(s)
+            single.append(ctx.align(want_fitness=True))
+    return srcs, tgts, single
+
+
+def same_as_single(got, single, tag):
+    assert len(got) == len(single)
+    for k, (g, s) in enumerate(zip(got, single)):
+        assert (g["converged"], g["iterations"], g["state"], g["n_corr"]) == (s["converged"], s["iterations"], s["state"], s["n_corr"]), (tag, k)
+        assert np.array_equal(g["T"].view(np.uint32), s["T"].view(np.uint32)), (tag, k)
+        assert np.float64(g["mse"]).view(np.uint64) == np.float64(s["mse"]).view(np.uint64), (tag, k)
+        assert g["fitness"] == s["fitness"] or (np.isnan(g["fitness"]) and np.isnan(s["fitness"])), (tag, k, g["fitness"], s["fitness"])
+
+
+def test_round_robin_scheduler_equals_single_alignments(built, dev_flavour, monkeypatch):
+    """ICPGPU_BATCH_LOCKSTEP=0 (development flavour): a host thread drives `depth` workers round-robin, each pair a single-pair
+    state machine on its worker's own stream.  One thread x three workers, then two x two, over the same nine pairs."""
+    if dev_flavour.delegated:
+        return
+    monkeypatch.setenv("ICPGPU_BATCH_LOCKSTEP", "0")     # (read once, at the process's first batch: the delegated run is this test alone)
+    srcs, tgts, single = scheduler_case(False)
+    for threads, depth in ((1, 3), (2, 2)):
+        monkeypatch.setenv("ICPGPU_BATCH_THREADS", str(threads))
+        monkeypatch.setenv("ICPGPU_BATCH_DEPTH", str(depth))
+        with _ctx(max_iterations=3) as ctx:
+            got = ctx.align_batch(srcs, tgts, want_fitness=True)
+        same_as_single(got, single, (threads, depth))
+
+
+def test_several_lockstep_groups_on_one_thread(built, monkeypatch):
+    """One host thread leading several lock-step groups -- the shape of a 64-pair call, which no other small test reaches (they all
+    collapse to one group per thread).  Twelve pairs at a depth of 2: ICPGPU_BATCH_GROUPS unset gives min(8, ceil(12 / 2)) = 6
+    groups on the one thread, their first fills capped at 1, 1, 1, 2, 2, 2 pairs; ICPGPU_BATCH_GROUPS=3 gives three, first fills
+    1, 2, 2.  The groups take turns filling, so that both ways pairs 7 and 8 share a group and iterate in ONE lock-step launch,
+    pair 9 iterates in lock-step beside pair 10 (no grid: the keys path), and the pairs below 32768 source points, the
+    cell-ordered source and the empty clouds run as single-pair state machines on their groups' streams."""
+    srcs, tgts, single = scheduler_case(True)
+    monkeypatch.setenv("ICPGPU_BATCH_THREADS", "1")
+    monkeypatch.setenv("ICPGPU_BATCH_DEPTH", "2")
+    for groups in (None, 3):
+        if groups is None:
+            monkeypatch.delenv("ICPGPU_BATCH_GROUPS", raising=False)
+        else:
+            monkeypatch.setenv("ICPGPU_BATCH_GROUPS", str(groups))
+        with _ctx(max_iterations=3) as ctx:
+            got = ctx.align_batch(srcs, tgts, want_fitness=True)
+        same_as_single(got, single, groups)
+
+
 def test_zz_report_worst_differences():
     """(the largest differences against the oracle seen by this module; printed with -s)"""
     print(f"\nP2P_SVD vs oracle: worst |dR| {WORST['dR']:.3g}, |dt| {WORST['dt']:.3g} m; worst sum error in units of sum|terms| 2^-53: "
