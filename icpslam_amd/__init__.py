@@ -6,6 +6,7 @@ the PCL-Registration-shaped host mirror and the synthetic scan generator.  No CP
 from ._lib import GICP, GICP_INNER_EXACT, NDT, NDT_LINE_SEARCH_MORE_THUENTE, NDT_LINE_SEARCH_PCL18, P2PLANE, GICP_INNER_QUADRATIC, NN_AUTO, NN_BRUTE, NN_GRID, P2P_SVD, STATE_NAMES, IcpGpuError, Params, Profile, Result  # noqa: F401
 from .registration import CorrespondenceRejectorMedianDistance, CorrespondenceRejectorOneToOne, CorrespondenceRejectorTrimmed  # noqa: F401
 from .registration import CorrespondenceRejectorSurfaceNormal, solve_symmetric_point_to_plane  # noqa: F401
+from .registration import CorrespondenceRejectorSampleConsensus  # noqa: F401
 from ._lib import REJECT_MEDIAN_DISTANCE, REJECT_ONE_TO_ONE, REJECT_SURFACE_NORMAL, REJECT_TRIMMED, Rejector  # noqa: F401
 from .registration import RadiusOutlierRemoval, StatisticalOutlierRemoval  # noqa: F401
 from .registration import KdTree, KdTreeFLANN  # noqa: F401

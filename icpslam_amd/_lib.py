@@ -24,6 +24,9 @@ GICP_SOLVER_NONE, GICP_SOLVER_HOST, GICP_SOLVER_DEVICE, GICP_SOLVER_QUADRATIC = 
 HEADER_VERSION = 1002          # the icpgpu.h these mirrors were written against (ICPGPU_HEADER_VERSION)
 NN_AUTO, NN_BRUTE, NN_GRID = 0, 1, 2
 REJECT_MEDIAN_DISTANCE, REJECT_TRIMMED, REJECT_ONE_TO_ONE, REJECT_SURFACE_NORMAL = 1, 2, 3, 4   # icpgpu_rejector_kind
+REJECT_SAMPLE_CONSENSUS = 5    # ... a stage that waits on the host (include/icpgpu.h "sample-consensus rejector")
+RSAC_DRAWS = 16                # ICPGPU_RSAC_DRAWS
+RSAC_MAX_ITERATIONS = 65536    # ICPGPU_RSAC_MAX_ITERATIONS
 MAX_REJECTORS = 4
 SOR_MAX_K = 63                 # ICPGPU_SOR_MAX_K
 SEARCH_MAX_K = 64              # ICPGPU_SEARCH_MAX_K
@@ -104,6 +107,8 @@ EXPORTS = [
     "icpgpu_ndt_line_search_replay", "icpgpu_ndt_line_search_trace",
     "icpgpu_set_correspondence_rejectors", "icpgpu_get_correspondence_rejectors", "icpgpu_correspondences", "icpgpu_rejector_stats",
     "icpgpu_set_reciprocal_correspondences", "icpgpu_get_reciprocal_correspondences", "icpgpu_reciprocal_stats",
+    "icpgpu_set_rejector_sac_seed", "icpgpu_get_rejector_sac_seed", "icpgpu_correspondence_rejector_sample_consensus",
+    "icpgpu_rejector_sac_fetch",
     "icpgpu_statistical_outlier_removal", "icpgpu_statistical_outlier_removal_view", "icpgpu_radius_outlier_removal",
     "icpgpu_radius_outlier_removal_view", "icpgpu_outlier_stats", "icpgpu_outlier_fetch",
     "icpgpu_search_set_input", "icpgpu_search_size", "icpgpu_search_knn", "icpgpu_search_radius",
@@ -212,6 +217,11 @@ def load():
     L.icpgpu_set_reciprocal_correspondences.argtypes = [vp, C.c_int]
     L.icpgpu_get_reciprocal_correspondences.argtypes = [vp, C.POINTER(C.c_int)]
     L.icpgpu_reciprocal_stats.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.icpgpu_set_rejector_sac_seed.argtypes = [vp, C.c_uint64]
+    L.icpgpu_get_rejector_sac_seed.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.icpgpu_correspondence_rejector_sample_consensus.argtypes = [vp, fp, C.c_size_t, fp, C.c_size_t, ip, ip, C.c_size_t, C.c_double, C.c_int,
+                                                                  C.c_uint64, ip, C.POINTER(C.c_size_t), fp]
+    L.icpgpu_rejector_sac_fetch.argtypes = [vp, C.c_size_t, ip, dp, dp, ip, ip, ip, ip, fp, ip, fp, C.POINTER(C.c_size_t), ip]
     L.icpgpu_voxel_grid.argtypes = [vp, fp, C.c_size_t, C.c_float, fp, C.POINTER(C.c_size_t)]
     L.icpgpu_voxel_grid_fetch.argtypes = [vp, fp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.icpgpu_voxel_grid_view.argtypes = [vp, fp, C.c_size_t, C.c_float, C.POINTER(fp), C.POINTER(C.c_size_t)]

@@ -461,6 +461,22 @@ struct icpgpu_ctx {
     DeviceBuf batch, ints, sums;
     Compaction sel, ext;  // sel.kept: the inliers; ext: icpgpu_sac_extract's own (the inlier list outlives an extract)
   } sac;
+  // the sample-consensus rejector (icpgpu_reject_sac.cpp, icp_reject_sac.hip): the last run of its core -- a stage of the chain or
+  // icpgpu_correspondence_rejector_sample_consensus -- and its scratch, in buffers no other call reads or writes.  It depends on no
+  // search cloud, so icpgpu_search_set_input leaves it.  rsac_seed: the chain stage's seed (icpgpu_set_rejector_sac_seed).
+  struct Rsac {
+    bool have = false;
+    int m = 0, iterations = 0, status = 0, best_t = -1, waits = 0;
+    size_t n_kept = 0;
+    double sample_d2 = 0.0;
+    double moments[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    float best_T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    std::vector<int32_t> counts, ranks;  // count[0 .. iterations); three ranks per evaluated hypothesis
+    std::vector<float> transforms;       // 16 per evaluated hypothesis, column-major; zeros for an INVALID one
+    DeviceBuf P, Q, rank, source, target, iq, im, models, batch, sums, ints;
+    Compaction sel;  // the gather's scratch; sel.flags: the kept flags of the call of its own
+  } rsac;
+  uint64_t rsac_seed = 12345;
   // ground filter (icpgpu_pmf.cpp, icp_morph.hip): the last filter call's result over the search cloud and the scratch of a filter or
   // an operator call, in buffers no other call writes -- an unfetched result outlives every other call over the search cloud (an
   // operator call included: it compacts into `op`); icpgpu_search_set_input drops it
@@ -792,6 +808,10 @@ int reject_run_chain(icpgpu_ctx* c, unsigned long long* keys, float thr, const X
 int reject_prepare(icpgpu_ctx* c);
 int reject_fetch_stats(icpgpu_ctx* c);
 int sweep_issue_rejected(icpgpu_ctx* c, const Xform& T, float thr, SweepTicket& tk);
+// icpgpu_reject_sac.cpp: the sample-consensus stage of the chain over the keys the stages before it left -- it WAITS on the host
+// (1 + 2 per batch of 64 hypotheses entered; max_iterations >= 1: the setter refuses a stage of none), empties the keys of the pairs it rejects and leaves {pairs in, pairs out, 0} in
+// stats (the stage's kRejectStats words, device memory)
+int reject_sac_stage(icpgpu_ctx* c, unsigned long long* keys, float thr, const Xform& T, const icpgpu_rejector& r, unsigned int* stats);
 // icpgpu_outlier.cpp: a cloud's k-NN grid, its first cell size taken from the cloud's own box (the filters and the neighbour search)
 int build_knn_grid(icpgpu_ctx* c, const Cloud& cloud, GridIndex& G);
 // icpgpu_search.cpp: up to a few device arrays into the caller's (pageable) arrays through the pinned staging buffer, ONE wait

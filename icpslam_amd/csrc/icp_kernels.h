@@ -354,6 +354,7 @@ hipError_t launch_terms29_final(const double* partials, int n_blocks, double* su
 // ---- correspondence rejectors (icp_reject.hip): stages between a key-writing search and a keys reduction ---------------------
 // A stage rewrites the keys of the pairs it rejects to kEmptyKey; a pair is alive when its key names a target and its d2 <= thr.
 static constexpr int kRejectMedian = 1, kRejectTrimmed = 2, kRejectOneToOne = 3, kRejectSurfaceNormal = 4;  // = icpgpu_rejector_kind
+static constexpr int kRejectSampleConsensus = 5;  // (a stage of the HOST's: icpgpu_reject_sac.cpp; launch_reject_chain refuses it)
 static constexpr int kRejectMaxStages = 4;
 struct RejectStage {
   int kind;
@@ -624,6 +625,41 @@ hipError_t launch_sac_select(const float4* cloud, int n, const float plane[4], f
 // sums12[0 .. 9): the exact sums, rounded once, of dx dx, dx dy, dx dz, dy dy, dy dz, dz dz, dx, dy, dz over the m > 0 listed points
 // about K = cloud[k_index] (d = q - K in float32); sums12[9 .. 12): K.  One workgroup, a fixed order.
 hipError_t launch_sac_sums(const float4* cloud, int n, const int* inliers, int m, int k_index, double* sums12, hipStream_t stream);
+
+// ---- sample-consensus rejector (icp_reject_sac.hip): pcl::registration::CorrespondenceRejectorSampleConsensus over m pairs --------
+// The pairs live in arrays of the stage's own: P, Q (m float4 each) and rank (m ints: the source index of pair r in the chain, r in
+// the call of its own).  A batch is kSacBatch hypotheses t0 .. t0 + 63 (hypothesis t0 + h is lane h's); the counting grid is capped
+// as the plane segmentation's (kSacGridCap workgroups of kSacBlockPoints pairs a step).
+static constexpr int kRsacDraws = 16;  // = ICPGPU_RSAC_DRAWS
+struct RsacModels {  // what the model kernel hands the host: the 17 sums of a good draw's three pairs, its ranks (-1: no good draw)
+  double sums[kSacBatch][kReduceTerms];
+  int ranks[kSacBatch][3];
+  int good[kSacBatch];
+};
+struct RsacBatch {  // what the host hands the counting kernel: count = 0 and the float transform, or -1 and NaN for an INVALID one
+  int count[kSacBatch];
+  Xform T[kSacBatch];
+};
+// the chain's gather: flags of the alive pairs (d2 <= thr, a target index below n_t), their ascending source ranks and number
+// (launch_compact: flags, pos, scan_scratch are its scratch over n_s entries), then P_r = T * src[rank[r]], Q_r = tgt[index].  n_s, n_t > 0.
+hipError_t launch_rsac_gather_keys(const float4* src, int n_s, const float4* tgt, int n_t, const unsigned long long* keys, float thr, const Xform& T,
+                                   int* flags, int* pos, int* scan_scratch, int* rank, int* m_dev, float4* P, float4* Q, hipStream_t stream);
+// the call's gather: P_r = source[iq[r]], Q_r = target[im[r]], rank[r] = r (every index inside its cloud; m, n_s, n_t > 0)
+hipError_t launch_rsac_gather_index(const float4* source, int n_s, const float4* target, int n_t, const int32_t* iq, const int32_t* im, int m,
+                                    float4* P, float4* Q, int* rank, hipStream_t stream);
+// out14[0 .. 9): the exact sums, rounded once, of dx dx, dx dy, dx dz, dy dy, dy dz, dz dz, dx, dy, dz over the finite P_r about
+// K = the first finite P (d = P_r - K in float32); out14[9 .. 12): K; out14[12]: the finite P_r; out14[13]: m = *m_dev, or m_host
+// with m_dev == null, capped at m_cap.  One workgroup, a fixed order.
+hipError_t launch_rsac_moments(const float4* P, int m_host, const int* m_dev, int m_cap, double* out14, hipStream_t stream);
+hipError_t launch_rsac_models(const float4* P, const float4* Q, int m, unsigned long long seed, int t0, int max_iterations, double sample_d2,
+                              RsacModels* models, hipStream_t stream);
+// batch->count[h] += the pairs with d2(T_h P_r, Q_r) < thr (thr: the smallest float32 not below the double threshold squared)
+hipError_t launch_rsac_count(const float4* P, const float4* Q, int m, float thr, RsacBatch* batch, hipStream_t stream);
+// flags[r] (or null) = pair r stays: an inlier of T, or every pair with keep_all; keys (or null): kEmptyKey into keys[rank[r]] of a
+// pair that does not.  The pairs that stay are ADDED to *n_kept, or with stats (a chain stage's kRejectStats words, zeroed) to
+// stats[1], and stats[0] = m.
+hipError_t launch_rsac_flags(const float4* P, const float4* Q, const int* rank, int m, const Xform& T, float thr, bool keep_all, int* flags,
+                             unsigned long long* keys, int n_s, unsigned int* n_kept, unsigned int* stats, hipStream_t stream);
 
 // ---- normal estimation (icp_normals.hip): pcl::NormalEstimation over neighbour rows still in device memory --------------------
 // out[i] = {nx, ny, nz, curvature} of query i from its row of cloud indices (ascending by key, as the launchers above leave them):

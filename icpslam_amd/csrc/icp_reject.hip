@@ -250,6 +250,8 @@ hipError_t launch_reject_chain(unsigned long long* keys, int n_s, int n_t, float
                                const float4* tgt_normals, const Xform* T) {
   if (n_stages <= 0) return hipSuccess;
   if (n_stages > kRejectMaxStages) return hipErrorInvalidValue;
+  for (int s = 0; s < n_stages; ++s)
+    if (stages[s].kind == kRejectSampleConsensus) return hipErrorInvalidValue;  // (the host's stage: the caller splits the chain around it)
   hipError_t e = hipMemsetAsync(state, 0, (size_t)n_stages * kRejectStateInts * sizeof(unsigned int), stream);
   if (e != hipSuccess) return e;
   const dim3 grid(reject_blocks(n_s)), block(RJ_BLOCK);

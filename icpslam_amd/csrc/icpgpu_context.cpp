@@ -680,6 +680,10 @@ int icpgpu_destroy(icpgpu_ctx* c) {
                        &c->cluster.cstart, &c->cluster.cstart64, &c->cluster.keys, &c->cluster.vals, &c->cluster.scratch, &c->cluster.counts})
     release(*b);
   for (DeviceBuf* b : {&c->sac.batch, &c->sac.ints, &c->sac.sums}) release(*b);
+  for (DeviceBuf* b : {&c->rsac.P, &c->rsac.Q, &c->rsac.rank, &c->rsac.source, &c->rsac.target, &c->rsac.iq, &c->rsac.im, &c->rsac.models,
+                       &c->rsac.batch, &c->rsac.sums, &c->rsac.ints})
+    release(*b);
+  release(c->rsac.sel);
   for (DeviceBuf* b : {&c->pmf.removed_at, &c->pmf.after, &c->pmf.ints, &c->pmf.tests, &c->pmf.grid, &c->pmf.table, &c->pmf.cell_start, &c->pmf.scan,
                        &c->pmf.cellid, &c->pmf.sxy, &c->pmf.sval, &c->pmf.va, &c->pmf.vb, &c->pmf.sidx, &c->pmf.scell, &c->pmf.out_z})
     release(*b);

@@ -4,7 +4,9 @@
 // chain's (icp_reject.hip), the point-to-point sweep with either, and the entry points that show what they keep
 // (icpgpu_correspondences, icpgpu_rejector_stats, icpgpu_reciprocal_stats).  An iteration on the keys path is search -> reciprocal
 // stage -> chain stages -> the method's keys reduction, queued back to back: nothing of the stages is read by the host until the
-// alignment ends (reject_fetch_stats: one posted read-back of the last iteration's statistics through the result mailbox).
+// alignment ends (reject_fetch_stats: one posted read-back of the last iteration's statistics through the result mailbox).  The one
+// exception is a sample-consensus stage (kind 5; icpgpu_reject_sac.cpp), whose loop runs on the host and waits inside the iteration:
+// reject_run_chain queues the device's stages run by run around it.
 #include "icp_ctx.h"
 
 namespace icpgpu_impl {
@@ -102,8 +104,18 @@ int reject_run_chain(icpgpu_ctx* c, unsigned long long* keys, float thr, const X
   }
   if ((rc = ensure(c, c->rej_state, (size_t)kRejectMaxStages * kRejectStateInts * sizeof(unsigned int)))) return rc;
   if (winners && (rc = ensure(c, c->rej_winners, (size_t)(n_t ? n_t : 1) * sizeof(unsigned long long)))) return rc;
-  HIP_TRY(c, launch_reject_chain(keys, n_s, n_t, thr, stages, n, static_cast<unsigned int*>(c->rej_state.ptr),
-                                 static_cast<unsigned long long*>(c->rej_winners.ptr), c->stream, src_normals, tgt_normals, &T));
+  // The device's stages are queued run by run around the sample-consensus stages, which are the host's (icpgpu_reject_sac.cpp: they
+  // wait); `state` is offset per stage.  Without such a stage this is one call over the whole chain, as before the stage existed.
+  auto* state = static_cast<unsigned int*>(c->rej_state.ptr);
+  int first = 0;
+  for (int s = 0; s <= n; ++s) {
+    if (s < n && stages[s].kind != kRejectSampleConsensus) continue;
+    if (s > first)
+      HIP_TRY(c, launch_reject_chain(keys, n_s, n_t, thr, stages + first, s - first, state + (size_t)first * kRejectStateInts,
+                                     static_cast<unsigned long long*>(c->rej_winners.ptr), c->stream, src_normals, tgt_normals, &T));
+    if (s < n && (rc = reject_sac_stage(c, keys, thr, T, c->rejectors[s], state + (size_t)s * kRejectStateInts + kRejectStats))) return rc;
+    first = s + 1;
+  }
   c->rej_ran = n;
   return ICPGPU_OK;
 }
@@ -181,6 +193,8 @@ static bool rejector_valid(const icpgpu_rejector& r) {
     case ICPGPU_REJECT_TRIMMED: return r.value >= 0.0 && r.value <= 1.0 && r.min_correspondences >= 0;
     case ICPGPU_REJECT_ONE_TO_ONE: return true;
     case ICPGPU_REJECT_SURFACE_NORMAL: return std::isfinite(r.value);
+    case ICPGPU_REJECT_SAMPLE_CONSENSUS:
+      return std::isfinite(r.value) && r.value >= 0.0 && r.min_correspondences >= 1 && r.min_correspondences <= ICPGPU_RSAC_MAX_ITERATIONS;
     default: return false;
   }
 }

@@ -248,6 +248,59 @@ class Context:
         self._check(self._L.icpgpu_rejector_stats(self._h, cap, a.ctypes.data_as(u32), b.ctypes.data_as(u32), _fp(cut), C.byref(n)))
         return [dict(pairs_in=int(a[s]), pairs_out=int(b[s]), cut=np.float32(cut[s])) for s in range(n.value)]
 
+    # the sample-consensus rejector (pcl::registration::CorrespondenceRejectorSampleConsensus) --------------------------
+    def set_rejector_sac_seed(self, seed: int):
+        """The seed of the chain's sample-consensus stages (default 12345), used afresh in every iteration."""
+        self._check(self._L.icpgpu_set_rejector_sac_seed(self._h, C.c_uint64(int(seed) & (2 ** 64 - 1))))
+
+    def get_rejector_sac_seed(self) -> int:
+        v = C.c_uint64(0)
+        self._check(self._L.icpgpu_get_rejector_sac_seed(self._h, C.byref(v)))
+        return int(v.value)
+
+    def reject_sample_consensus(self, source, target, index_query, index_match, inlier_threshold: float = 0.05, max_iterations: int = 1000,
+                                seed: int = 12345, want_flags: bool = True) -> dict:
+        """RANSAC over the pairs (source[index_query[r]], target[index_match[r]]): dict(kept (bool per pair, or None), n_kept,
+        best_T (4x4, getBestTransformation())).  Everything else of the run: rejector_sac_fetch()."""
+        src, tgt = _as_cloud(source), _as_cloud(target)
+        iq = np.ascontiguousarray(index_query, dtype=np.int32).reshape(-1)
+        im = np.ascontiguousarray(index_match, dtype=np.int32).reshape(-1)
+        if iq.size != im.size:
+            raise ValueError("index_query and index_match must have the same length")
+        ip = C.POINTER(C.c_int32)
+        kept = np.zeros(max(1, iq.size), np.int32) if want_flags else None
+        n_kept = C.c_size_t(0)
+        T = np.zeros(16, np.float32)
+        self._check(self._L.icpgpu_correspondence_rejector_sample_consensus(
+            self._h, _fp(src), len(src), _fp(tgt), len(tgt), iq.ctypes.data_as(ip), im.ctypes.data_as(ip), iq.size, float(inlier_threshold),
+            int(max_iterations), C.c_uint64(int(seed) & (2 ** 64 - 1)), kept.ctypes.data_as(ip) if want_flags else None, C.byref(n_kept), _fp(T)))
+        return dict(kept=kept[:iq.size].astype(bool) if want_flags else None, n_kept=int(n_kept.value), best_T=T.reshape(4, 4).T.copy())
+
+    def rejector_sac_fetch(self, per_hypothesis: bool = True) -> dict:
+        """The last run of the sample-consensus core on this context (the call, correspondences(), or the last iteration of the last
+        alignment with such a stage): m, sample_d2, moments9, iterations, status, counts, ranks (iterations x 3), transforms
+        (iterations x 4 x 4), best_t, best_T, n_kept, host_waits."""
+        ip = C.POINTER(C.c_int32)
+        m, it, status, best_t, waits = (C.c_int32(0) for _ in range(5))
+        d2 = C.c_double(0.0)
+        mom = np.zeros(9, np.float64)
+        T = np.zeros(16, np.float32)
+        n_kept = C.c_size_t(0)
+        dp = C.POINTER(C.c_double)
+        self._check(self._L.icpgpu_rejector_sac_fetch(self._h, 0, C.byref(m), C.byref(d2), mom.ctypes.data_as(dp), C.byref(it), C.byref(status), None,
+                                                      None, None, C.byref(best_t), _fp(T), C.byref(n_kept), C.byref(waits)))
+        out = dict(m=int(m.value), sample_d2=float(d2.value), moments9=mom, iterations=int(it.value), status=int(status.value),
+                   best_t=int(best_t.value), best_T=T.reshape(4, 4).T.copy(), n_kept=int(n_kept.value), host_waits=int(waits.value))
+        if per_hypothesis:
+            n = out["iterations"]
+            counts = np.zeros(max(1, n), np.int32)
+            ranks = np.zeros((max(1, n), 3), np.int32)
+            tr = np.zeros((max(1, n), 16), np.float32)
+            self._check(self._L.icpgpu_rejector_sac_fetch(self._h, n, None, None, None, None, None, counts.ctypes.data_as(ip), ranks.ctypes.data_as(ip),
+                                                          _fp(tr), None, None, None, None))
+            out.update(counts=counts[:n], ranks=ranks[:n], transforms=tr[:n].reshape(n, 4, 4).transpose(0, 2, 1).copy())
+        return out
+
     # reciprocal correspondences (pcl::Registration::setUseReciprocalCorrespondences) -----------------------------------
     def set_reciprocal_correspondences(self, on: bool):
         """P2P_SVD / P2PLANE: keep a pair only if the target point's nearest transformed source point is the pair's own (the
@@ -1129,7 +1182,7 @@ def result_dict(res: Result, cloud):
 
 
 class CorrespondenceRejector:
-    """pcl::registration::CorrespondenceRejector-shaped base of the four rejectors a registration object's chain may hold
+    """pcl::registration::CorrespondenceRejector-shaped base of the five rejectors a registration object's chain may hold
     (addCorrespondenceRejector).  The objects carry parameters only: the stages run on the device inside align()."""
 
     KIND = 0
@@ -1207,6 +1260,73 @@ class CorrespondenceRejectorSurfaceNormal(CorrespondenceRejector):
 
     def _entry(self) -> Rejector:
         return Rejector(self.KIND, 0, self._threshold)
+
+
+class CorrespondenceRejectorSampleConsensus(CorrespondenceRejector):
+    """RANSAC over the pairs with a rigid transform as the model: a pair stays iff it is an inlier of the best hypothesis.  In a
+    registration object's chain it runs inside align() (and waits on the host there); alone -- setInputSource, setInputTarget,
+    setInputCorrespondences, getRemainingCorrespondences -- it filters a pair list, e.g. descriptor matches, on a context of its
+    own.  setRefineModel(True) is not provided."""
+
+    KIND = _lib.REJECT_SAMPLE_CONSENSUS
+
+    def __init__(self, ctx: "Context | None" = None):
+        self._threshold = 0.05
+        self._max_iterations = 1000
+        self._best_T = np.eye(4, dtype=np.float32)
+        self._ctx = ctx
+        self._source = self._target = None
+        self._pairs = (np.zeros(0, np.int32), np.zeros(0, np.int32))
+        self._seed = 12345
+
+    def setInlierThreshold(self, threshold):
+        self._threshold = float(threshold)
+
+    def getInlierThreshold(self) -> float:
+        return self._threshold
+
+    def setMaximumIterations(self, n):
+        self._max_iterations = int(n)
+
+    def getMaximumIterations(self) -> int:
+        return self._max_iterations
+
+    def setRefineModel(self, on: bool):
+        if on:
+            raise NotImplementedError("CorrespondenceRejectorSampleConsensus.setRefineModel(True) is not provided")
+
+    def getRefineModel(self) -> bool:
+        return False
+
+    def setInputSource(self, cloud):
+        self._source = _as_cloud(cloud)
+
+    def setInputTarget(self, cloud):
+        self._target = _as_cloud(cloud)
+
+    def setInputCorrespondences(self, index_query, index_match):
+        self._pairs = (np.ascontiguousarray(index_query, np.int32).reshape(-1), np.ascontiguousarray(index_match, np.int32).reshape(-1))
+
+    def getRemainingCorrespondences(self):
+        """(index_query, index_match) of the pairs that stay, in their order."""
+        if self._source is None or self._target is None:
+            raise RuntimeError("CorrespondenceRejectorSampleConsensus: setInputSource and setInputTarget first")
+        if self._ctx is None:
+            self._ctx = Context()
+        r = self._ctx.reject_sample_consensus(self._source, self._target, self._pairs[0], self._pairs[1], self._threshold, self._max_iterations,
+                                              self._seed)
+        self._best_T = r["best_T"]
+        return self._pairs[0][r["kept"]], self._pairs[1][r["kept"]]
+
+    getCorrespondences = getRemainingCorrespondences
+
+    def getBestTransformation(self) -> np.ndarray:
+        """The best hypothesis' transform: of the last getRemainingCorrespondences(), or of the last iteration of the last
+        align() this rejector took part in."""
+        return self._best_T
+
+    def _entry(self) -> Rejector:
+        return Rejector(self.KIND, self._max_iterations, self._threshold)
 
 
 class _OutlierFilter:
@@ -2061,6 +2181,12 @@ class IterativeClosestPoint:
         for r, s in zip(self._rejectors, self._ctx.rejector_stats()):
             if isinstance(r, CorrespondenceRejectorMedianDistance):
                 r._median = float(s["cut"])
+        sac = [r for r in self._rejectors if isinstance(r, CorrespondenceRejectorSampleConsensus)]
+        if sac:  # (the fetch is of the LAST such stage's last run)
+            try:
+                sac[-1]._best_T = self._ctx.rejector_sac_fetch(per_hypothesis=False)["best_T"]
+            except IcpGpuError:  # (GICP and NDT ignore the chain: no run)
+                pass
 
     def setInputSource(self, cloud):             # icp_odometer.cpp:193
         self._source = _as_cloud(cloud)

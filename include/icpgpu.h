@@ -62,7 +62,9 @@ extern "C" {
  * icpgpu_iss_keypoints, icpgpu_iss_fetch, icpgpu_iss_stats, icpgpu_iss_keypoints_border, icpgpu_iss_fetch_border, and boundary
  * estimation -- icpgpu_boundary_estimation, and moving least squares -- icpgpu_moving_least_squares, icpgpu_mls_fetch, icpgpu_mls_stats, and fast point feature histograms -- icpgpu_fpfh_estimation, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
  * icpgpu_set_p2plane_symmetric, icpgpu_get_p2plane_symmetric, icpgpu_reduce_symmetric_point_to_plane,
- * icpgpu_solve_symmetric_point_to_plane, ICPGPU_REJECT_SURFACE_NORMAL, and the diagnostic icpgpu_sweep_sums (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
+ * icpgpu_solve_symmetric_point_to_plane, ICPGPU_REJECT_SURFACE_NORMAL, and the sample-consensus rejector -- ICPGPU_REJECT_SAMPLE_CONSENSUS,
+ * icpgpu_set_rejector_sac_seed, icpgpu_get_rejector_sac_seed, icpgpu_correspondence_rejector_sample_consensus, icpgpu_rejector_sac_fetch,
+ * and the diagnostic icpgpu_sweep_sums (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
  * icpgpu_profile.gicp_quadratic_solves; 0.3 icpgpu_profile (sources_adopted, gicp_host_solves, gicp_solver_choice). */
 
@@ -472,19 +474,21 @@ int icpgpu_solve_symmetric_point_to_plane(const double sums[29], double Tk[16]);
  * GeneralizedIterativeClosestPoint::computeTransformation and NormalDistributionsTransform never read correspondence_rejectors_.
  * icpgpu_align_batch with a non-empty chain returns ICPGPU_ERR_UNSUPPORTED for every method (the lock-step kernels fuse the
  * reduction); icpgpu_align_batch_multi runs on contexts of the library's own, which never carry a chain.  With an empty chain an
- * alignment launches exactly the kernels it launched before rejectors existed.  Not provided: the var-trimmed,
- * sample-consensus and feature rejectors. */
+ * alignment launches exactly the kernels it launched before rejectors existed.  SAMPLE_CONSENSUS is a stage of another kind -- it
+ * waits on the host -- and has a section of its own below.  Not provided: the var-trimmed and feature rejectors. */
 typedef enum {
   ICPGPU_REJECT_MEDIAN_DISTANCE = 1,
   ICPGPU_REJECT_TRIMMED = 2,
   ICPGPU_REJECT_ONE_TO_ONE = 3,
-  ICPGPU_REJECT_SURFACE_NORMAL = 4
+  ICPGPU_REJECT_SURFACE_NORMAL = 4,
+  ICPGPU_REJECT_SAMPLE_CONSENSUS = 5 /* "sample-consensus rejector" below */
 } icpgpu_rejector_kind;
 #define ICPGPU_MAX_REJECTORS 4
 typedef struct {
   int32_t kind;                /* icpgpu_rejector_kind */
-  int32_t min_correspondences; /* TRIMMED only */
-  double value;                /* MEDIAN_DISTANCE: factor; TRIMMED: overlap ratio; ONE_TO_ONE: unused; SURFACE_NORMAL: threshold */
+  int32_t min_correspondences; /* TRIMMED: min_correspondences; SAMPLE_CONSENSUS: carries max_iterations (1 .. ICPGPU_RSAC_MAX_ITERATIONS) */
+  double value;                /* MEDIAN_DISTANCE: factor; TRIMMED: overlap ratio; ONE_TO_ONE: unused; SURFACE_NORMAL: threshold;
+                                  SAMPLE_CONSENSUS: the inlier threshold (finite, >= 0) */
 } icpgpu_rejector;
 /* the whole chain at once; n = 0 clears it.  A bad kind or value, n > ICPGPU_MAX_REJECTORS or a null context:
  * ICPGPU_ERR_INVALID_ARG, and the chain in force stays. */
@@ -524,6 +528,90 @@ int icpgpu_get_reciprocal_correspondences(const icpgpu_ctx* ctx, int* on);
  * alignment or its last icpgpu_correspondences call, whichever came later (the lifetime of icpgpu_rejector_stats); zeroes when that
  * run had the flag off.  Either output may be NULL. */
 int icpgpu_reciprocal_stats(const icpgpu_ctx* ctx, uint32_t* pairs_in, uint32_t* pairs_out);
+
+/* ---- sample-consensus rejector (added under 1.2) ------------------------------------------------------------------ */
+/* replaces pcl::registration::CorrespondenceRejectorSampleConsensus<PointXYZ> (PCL 1.8): setInlierThreshold, setMaximumIterations,
+ * setInputSource, setInputTarget, getRemainingCorrespondences, getBestTransformation -- RANSAC over a list of pairs with a rigid
+ * transform as the model.  It removes STRUCTURED outliers (a parked car that moved, a repeated facade): pairs that are close and
+ * merely inconsistent with one rigid motion, which the distance-based rejectors cannot see.  It is a stage of the chain
+ * (ICPGPU_REJECT_SAMPLE_CONSENSUS) and a call of its own (icpgpu_correspondence_rejector_sample_consensus), the latter behind
+ * descriptor matching: icpgpu_feature_knn(k = 1) -> this call -> best_T16.  The rule restates getRemainingCorrespondences,
+ * SampleConsensusModelRegistration and RandomSampleConsensus::computeModel; each departure is a DEVIATION.  Parity with PCL binaries
+ * is unpinned; tests/rsac_restated.py is what the kernels are compared with, bit for bit.
+ * CORE.  It works on m pairs (P_r, Q_r) of float4 points, r = 0 .. m - 1.
+ * HYPOTHESIS t = 0 .. max_iterations - 1.  Draws use the splitmix generator of the plane-segmentation section.  A hypothesis gets up
+ * to ICPGPU_RSAC_DRAWS = 16 redraws d = 0 .. 15 of three ranks: with the counter (48 t + 3 d + c + 1) in place of that section's
+ * (3 t + c + 1), rank_c = ((z >> 32) * m) >> 32 for c = 0, 1, 2.  A draw is GOOD iff the three ranks differ, all six points are
+ * finite, the three pairwise squared distances among the sampled P points each satisfy (double)d2 > sample_d2, strictly, with d2 the
+ * search section's float32 expression fma(dz, dz, fma(dy, dy, dx * dx)) (PCL's isSampleGood), and m >= 3.  The first good draw is the
+ * sample; with none the hypothesis is INVALID (count = -1, ranks -1), and it counts as an iteration.  DEVIATION: PCL redraws up to
+ * 1000 times from rand() and skips failed models; here a hypothesis is a pure function of (seed, t, the pairs).
+ * SAMPLE DISTANCE (PCL's computeSampleDistanceThreshold).  The nine sums of the plane refinement's rule over the FINITE P_r, about
+ * K = the first finite P: differences in float32, terms exact in double, each sum the exact sum rounded once (moments9).  With n the
+ * number of finite P_r, means and covariances in double by that section's formulas, then the cyclic Jacobi (8 sweeps).  Eigenvalues
+ * below 0 count as 0 (DEVIATION: PCL takes sqrt of whatever eigen33 returns).  s = ((sqrt(e0) + sqrt(e1)) + sqrt(e2)) / 3.0 with the
+ * eigenvalues ascending, in double, sqrt correctly rounded; sample_d2 = s * s.  Without a finite P: moments9 and sample_d2 are 0.
+ * TRANSFORM.  As the SCP section's: the 17 sums {3, sum p, sum q, sum q p^T, 0} of the sample's three pairs, taken in sample order
+ * in double, go through the host's Umeyama solve (icpgpu_solve's arithmetic); the result is rounded to float32, column-major.  A
+ * solve that fails or a result that is not finite makes the hypothesis INVALID (it keeps its ranks; its transform reads as zeros).
+ * INLIER.  p' = H p by the fma chain of DESIGN.md section 3, d2 = the search's float32 expression over (p', q).  A pair is an inlier
+ * iff (double)d2 < inlier_threshold * inlier_threshold (the product in double), strictly; a pair with a non-finite point never is.
+ * count[t] is an exact integer.
+ * LOOP.  The plane section's loop word for word, with n = m in w = count / (double)m and probability fixed at 0.99 (PCL's rejector
+ * has no setter for it).  `iterations` is the t at which it stops.
+ * RESULT.  status 0: m = 0, nothing is kept.  status 1: no t has count > 0 -- this covers m < 3, max_iterations = 0 and a threshold
+ * of 0 -- EVERY pair stays and best_T is the identity (PCL's remaining = original).  status 2: the best count is below 3; again
+ * every pair stays and best_T is the identity.  status 3: a pair stays iff it is an inlier of the best hypothesis' transform, which is
+ * best_T (getBestTransformation()).
+ * AS A STAGE.  kind = ICPGPU_REJECT_SAMPLE_CONSENSUS, value = the inlier threshold (finite, >= 0; PCL's default 0.05),
+ * min_correspondences = max_iterations (1 .. ICPGPU_RSAC_MAX_ITERATIONS; PCL's default 1000).  DEVIATION: a STAGE with max_iterations = 0
+ * is ICPGPU_ERR_INVALID_ARG of icpgpu_set_correspondence_rejectors -- it would keep every pair and pay a wait for it, and an entry
+ * {5, 0, value} is what a caller that never filled in min_correspondences sends (a chain written before this kind existed was
+ * refused with it); the call of its own accepts max_iterations = 0 (status 1).  ICPGPU_RSAC_MAX_ITERATIONS = 65536: the
+ * per-hypothesis record a run keeps on the host (76 bytes each) stays under 5 MB, and the device holds one batch of 64 at a time.
+ * The seed is the context's (icpgpu_set_rejector_sac_seed; default 12345, the fixed seed of PCL's non-random RandomSampleConsensus)
+ * and is used afresh in every iteration, as PCL constructs a fresh model per call.  The stage runs wherever the chain runs --
+ * ICPGPU_P2P_SVD, ICPGPU_P2PLANE, the symmetric objective, icpgpu_correspondences, after the reciprocal stage -- on the pairs the
+ * stages before it left, in ascending source index: P_r = x_i = T * source[i], rounded as the search rounds it, Q_r = target[j].  It
+ * then empties the keys of the pairs it rejects, as the surface-normal stage does; icpgpu_rejector_stats reports pairs_in = m and
+ * pairs_out for it, cut = 0.  ICPGPU_GICP and ICPGPU_NDT go on ignoring the chain and icpgpu_align_batch goes on refusing one.
+ * HOST WAITS.  This stage, unlike the others, WAITS ON THE HOST INSIDE AN ITERATION: the sequential loop runs on the host over
+ * counts the device takes 64 hypotheses at a time, and the host solves each batch's transforms.  A run of the core waits
+ *     1 + 2 B
+ * times, B = the batches of 64 hypotheses the loop enters (it enters batch b iff it has not stopped before t = 64 b): one wait for m
+ * and moments9, then per batch one for the 17-sum records and one for the counts.  With m < 3 no draw can be good: every hypothesis
+ * is INVALID by rule, `iterations` = max_iterations and B = 0.  A stage over an empty source or target, and a call with n_pairs = 0,
+ * launch nothing and wait 0 times.  The call of its own waits once more when `kept` is not NULL (the flags' way back).  A chain
+ * WITHOUT a stage of this kind queues exactly the launches it queued before the stage existed.
+ * THE CALL.  icpgpu_correspondence_rejector_sample_consensus takes two host clouds and a pair list; the same core with
+ * P_r = source[index_query[r]], Q_r = target[index_match[r]].  kept[r] (n_pairs int32 flags; may be NULL) = 1 iff pair r stays,
+ * *n_kept their number, best_T16 the transform (column-major).  It is defined pair by pair, so duplicated pairs and repeated query
+ * indices are ordinary input.  DEVIATION: PCL maps inliers back through the source index, which is undefined for a repeated query
+ * index.  ICPGPU_ERR_INVALID_ARG (and a previous result is dropped): an index outside its cloud, a null array against a non-zero
+ * size, a threshold that is not finite or is negative, max_iterations outside 0 .. ICPGPU_RSAC_MAX_ITERATIONS, a null n_kept or
+ * best_T16.
+ * FETCH.  icpgpu_rejector_sac_fetch hands out, for the LAST RUN OF THE CORE on the context -- the call, icpgpu_correspondences, or the
+ * last iteration of the last P2P_SVD / P2PLANE alignment with such a stage (the LAST such stage of a chain that has several) -- m,
+ * sample_d2, moments9, iterations, status, count[0 .. iterations), per evaluated hypothesis its three ranks (iterations x 3) and its
+ * float transform (iterations x 16, column-major), best_t (-1 without one), best_T16, the number kept and the host waits.  Any output
+ * may be NULL; with counts, ranks or transforms and capacity_iterations < iterations nothing is written and the call is
+ * ICPGPU_ERR_INVALID_ARG, as without a result.
+ * ISOLATION.  As the plane section's paragraph: the result lives in buffers of its own and depends on the pairs and the arguments
+ * alone.  It reads no search cloud (icpgpu_search_set_input leaves it) and disturbs nothing else of the
+ * context; unfetched clustering, segmentation, ISS and ground-filter results survive it and it survives them.
+ * Not provided: setRefineModel(true), setSaveInliers / getInliersIndices. */
+#define ICPGPU_RSAC_DRAWS 16
+#define ICPGPU_RSAC_MAX_ITERATIONS 65536
+int icpgpu_set_rejector_sac_seed(icpgpu_ctx* ctx, uint64_t seed);
+int icpgpu_get_rejector_sac_seed(const icpgpu_ctx* ctx, uint64_t* seed);
+int icpgpu_correspondence_rejector_sample_consensus(icpgpu_ctx* ctx, const float* source_xyzw, size_t n_s, const float* target_xyzw, size_t n_t,
+                                                    const int32_t* index_query, const int32_t* index_match, size_t n_pairs,
+                                                    double inlier_threshold, int max_iterations, uint64_t seed,
+                                                    int32_t* kept /* n_pairs int32 flags, may be NULL */, size_t* n_kept, float best_T16[16]);
+int icpgpu_rejector_sac_fetch(icpgpu_ctx* ctx, size_t capacity_iterations, int32_t* m, double* sample_d2, double moments9[9],
+                              int32_t* iterations, int32_t* status, int32_t* counts /* iterations */, int32_t* ranks /* iterations x 3 */,
+                              float* transforms /* iterations x 16 */, int32_t* best_t, float best_T16[16], size_t* n_kept,
+                              int32_t* host_waits);
 
 /* ---- NDT mode (ICPGPU_NDT, added under 1.2) --------------------------------------------------------------------- */
 /* setResolution / setStepSize / setOulierRatio.  resolution > 0, step_size > 0, 0 < outlier_ratio < 1, else ICPGPU_ERR_INVALID_ARG.

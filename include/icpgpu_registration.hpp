@@ -195,7 +195,14 @@ inline void release_cached_contexts() {
   }
 }
 
-// --- pcl::registration::CorrespondenceRejector and the four rejectors a registration object's chain may hold (PCL 1.8's names;
+// pcl::Correspondence, as far as the sample-consensus rejector reads and writes it
+struct Correspondence {
+  int index_query, index_match;
+  float distance;
+};
+typedef std::vector<Correspondence> Correspondences;
+
+// --- pcl::registration::CorrespondenceRejector and the five rejectors a registration object's chain may hold (PCL 1.8's names;
 // include/icpgpu.h, "correspondence rejectors", states the rules and the two deviations).  The objects carry parameters: the
 // stages run on the device inside align(), which also leaves the last iteration's median in the median rejector.
 namespace registration {
@@ -207,6 +214,7 @@ class CorrespondenceRejector {
   const std::string& getClassName() const { return rejection_name_; }
   virtual icpgpu_rejector entry() const = 0;            // (no PCL counterpart: what the C-ABI takes)
   virtual void takeCut(float /*d2*/) {}
+  virtual void takeBestTransformation(const float* /*colmajor16*/) {}  // (the sample-consensus rejector's: as takeCut hands over the median)
 
  protected:
   std::string rejection_name_;
@@ -257,6 +265,77 @@ class CorrespondenceRejectorSurfaceNormal : public CorrespondenceRejector {
 
  private:
   double threshold_;
+};
+// RANSAC over the pairs with a rigid transform as the model (include/icpgpu.h, "sample-consensus rejector").  In a registration
+// object's chain it carries its two parameters, the stage runs inside align() -- and WAITS ON THE HOST there -- and align() leaves
+// the last iteration's best transform here.  Alone (setInputSource, setInputTarget, setInputCorrespondences,
+// getRemainingCorrespondences / getCorrespondences) it filters a pair list on a context of its own, taken at the first such call.
+class CorrespondenceRejectorSampleConsensus : public CorrespondenceRejector {
+ public:
+  typedef std::shared_ptr<CorrespondenceRejectorSampleConsensus> Ptr;
+  explicit CorrespondenceRejectorSampleConsensus(int device = 0) : device_(device) {
+    rejection_name_ = "CorrespondenceRejectorSampleConsensus";
+    for (int i = 0; i < 16; ++i) best_T_[i] = (i % 5 == 0) ? 1.f : 0.f;
+  }
+  void setInlierThreshold(double threshold) { inlier_threshold_ = threshold; }
+  double getInlierThreshold() const { return inlier_threshold_; }
+  void setMaximumIterations(int max_iterations) { max_iterations_ = std::max(max_iterations, 0); }  // (0: the call alone; a chain refuses it)
+  int getMaximumIterations() const { return max_iterations_; }
+  void setRefineModel(bool refine) {
+    if (refine) throw std::invalid_argument("CorrespondenceRejectorSampleConsensus: setRefineModel(true) is not provided");
+  }
+  bool getRefineModel() const { return false; }
+  void setSeed(uint64_t seed) { seed_ = seed; }  // no PCL counterpart: the call's seed (PCL's non-random RandomSampleConsensus: 12345)
+  icpgpu_rejector entry() const override { return icpgpu_rejector{ICPGPU_REJECT_SAMPLE_CONSENSUS, (int32_t)max_iterations_, inlier_threshold_}; }
+  void takeBestTransformation(const float* colmajor16) override { std::memcpy(best_T_, colmajor16, sizeof best_T_); }
+  Matrix4 getBestTransformation() const { return make_matrix4(best_T_); }
+
+  // --- the rejector alone: clouds of 16-byte points, valid until getRemainingCorrespondences() returns
+  template <class CloudPtr>
+  void setInputSource(const CloudPtr& cloud) {
+    static_assert(sizeof(cloud->points[0]) == 16, "point type must be the 16-byte pcl::PointXYZ layout");
+    source_ = cloud->points.empty() ? nullptr : reinterpret_cast<const float*>(&cloud->points[0]);
+    n_source_ = cloud->points.size();
+  }
+  template <class CloudPtr>
+  void setInputTarget(const CloudPtr& cloud) {
+    static_assert(sizeof(cloud->points[0]) == 16, "point type must be the 16-byte pcl::PointXYZ layout");
+    target_ = cloud->points.empty() ? nullptr : reinterpret_cast<const float*>(&cloud->points[0]);
+    n_target_ = cloud->points.size();
+  }
+  void setInputCorrespondences(const std::shared_ptr<const Correspondences>& correspondences) { input_ = correspondences; }
+  void setInputCorrespondences(const std::shared_ptr<Correspondences>& correspondences) { input_ = correspondences; }
+  // the pairs of `original` that stay, in their order; false (and `remaining` empty) when the library refuses the call
+  bool getRemainingCorrespondences(const Correspondences& original, Correspondences& remaining) {
+    remaining.clear();
+    if (!ctx_holder_) ctx_holder_ = detail::acquire_context(device_);
+    std::vector<int32_t> iq(original.size()), im(original.size()), kept(original.size());
+    for (std::size_t r = 0; r < original.size(); ++r) iq[r] = original[r].index_query, im[r] = original[r].index_match;
+    std::size_t n_kept = 0;
+    if (icpgpu_correspondence_rejector_sample_consensus(ctx_holder_->ctx, source_, n_source_, target_, n_target_, iq.data(), im.data(), original.size(),
+                                                        inlier_threshold_, max_iterations_, seed_, kept.data(), &n_kept, best_T_) != ICPGPU_OK)
+      return false;
+    remaining.reserve(n_kept);
+    for (std::size_t r = 0; r < original.size(); ++r)
+      if (kept[r]) remaining.push_back(original[r]);
+    return true;
+  }
+  void getCorrespondences(Correspondences& correspondences) {
+    if (input_) getRemainingCorrespondences(*input_, correspondences);
+    else correspondences.clear();
+  }
+  const char* lastError() const { return ctx_holder_ ? icpgpu_last_error(ctx_holder_->ctx) : ""; }
+
+ private:
+  int device_;
+  double inlier_threshold_ = 0.05;
+  int max_iterations_ = 1000;
+  uint64_t seed_ = 12345;
+  float best_T_[16];
+  const float *source_ = nullptr, *target_ = nullptr;
+  std::size_t n_source_ = 0, n_target_ = 0;
+  std::shared_ptr<const Correspondences> input_;
+  detail::ContextPtr ctx_holder_;
 };
 }  // namespace registration
 
@@ -375,6 +454,14 @@ class IterativeClosestPoint {
     std::size_t n = 0;
     if (correspondence_rejectors_.empty() || icpgpu_rejector_stats(ctx_, ICPGPU_MAX_REJECTORS, nullptr, nullptr, cut, &n) != ICPGPU_OK) return;
     for (std::size_t s = 0; s < n && s < correspondence_rejectors_.size(); ++s) correspondence_rejectors_[s]->takeCut(cut[s]);
+    // the last iteration's best transform goes to the sample-consensus rejector (the last one, when the chain holds several)
+    for (std::size_t s = correspondence_rejectors_.size(); s-- > 0;) {
+      if (correspondence_rejectors_[s]->entry().kind != ICPGPU_REJECT_SAMPLE_CONSENSUS) continue;
+      float T[16];
+      if (icpgpu_rejector_sac_fetch(ctx_, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, T, nullptr, nullptr) == ICPGPU_OK)
+        correspondence_rejectors_[s]->takeBestTransformation(T);
+      break;
+    }
   }
 
   bool apply_ndt() {
