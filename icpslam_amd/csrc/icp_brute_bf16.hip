@@ -402,6 +402,31 @@ hipError_t launch_morton_order(const float4* sorted, int n, const GridDesc& g, i
   return hipGetLastError();
 }
 
+// The launch shape.  check: the test mode (ICPGPU_MFMA_CHECK_BOUND) has its own instantiation, one shape.  Experiments, read
+// once per process: ICPGPU_BF16_G (sources per wave / 32: 2 or 4), ICPGPU_BF16_TILE (512 / 1024), ICPGPU_BF16_BLOCK (256 / 512),
+// ICPGPU_MFMA_WAVES (target waves per SIMD the splits aim at).
+MatrixNnPlan plan_nn_brute_bf16(int n_q, int n_t, int num_cus, bool check) {
+  static const int g_env = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_BF16_G"); return e ? atoi(e) : 2; }();
+  static const int tile_env = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_BF16_TILE"); return e ? atoi(e) : 1024; }();
+  static const int block_env = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_BF16_BLOCK"); return e ? atoi(e) : 512; }();
+  static const int waves_env = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_MFMA_WAVES"); return e ? atoi(e) : 32; }();
+  MatrixNnPlan p;
+  p.g = check ? 2 : g_env == 4 ? 4 : 2;
+  p.tile = check ? 512 : tile_env == 1024 ? 1024 : 512;
+  p.block = check ? 256 : block_env == 512 ? 512 : 256;
+  const int per_block = (p.block / 64) * 32 * p.g;
+  p.grid_x = (n_q + per_block - 1) / per_block;
+  int splits = (num_cus * waves_env * 4 / (p.block / 64) + p.grid_x - 1) / p.grid_x;
+  const int max_splits = (n_t + p.tile - 1) / p.tile;
+  if (splits > max_splits) splits = max_splits;
+  if (splits < 1) splits = 1;
+  int per = (n_t + splits - 1) / splits;
+  per = ((per + p.tile - 1) / p.tile) * p.tile;
+  p.tgt_per_split = per;
+  p.splits = (n_t + per - 1) / per;
+  return p;
+}
+
 // src_sorted: the source in MORTON order with the ORIGINAL index in .w (launch_morton_order); keys are written at the original
 // indices and must be pre-filled with kEmptyKey (points missing from src_sorted -- the non-finite ones -- stay unmatched, and
 // target splits merge by atomic min).  seed (optional, n_s keys indexed like `keys`): every source's neighbour from an earlier
@@ -410,12 +435,7 @@ hipError_t launch_nn_brute_bf16(const float4* src_sorted, int n_q, const float4*
                                 unsigned long long* keys, const unsigned long long* seed, unsigned long long* check,
                                 hipStream_t stream) {
   if (n_q <= 0 || n_t <= 0) return hipSuccess;
-  // experiments: ICPGPU_BF16_G (sources per wave / 32: 2 or 4), ICPGPU_BF16_TILE (512 / 1024), ICPGPU_BF16_BLOCK (256 / 512),
-  // ICPGPU_MFMA_WAVES (target waves per SIMD the splits aim at), ICPGPU_MFMA_NO_EXACT (timing only: results are wrong)
-  static const int g_env = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_BF16_G"); return e ? atoi(e) : 2; }();
-  static const int tile_env = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_BF16_TILE"); return e ? atoi(e) : 1024; }();
-  static const int block_env = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_BF16_BLOCK"); return e ? atoi(e) : 512; }();
-  static const int waves_env = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_MFMA_WAVES"); return e ? atoi(e) : 32; }();
+  // experiment: ICPGPU_MFMA_NO_EXACT (timing only: results are wrong)
   static const int no_exact = [] {
     if (!ICPGPU_DEV_ENV("ICPGPU_MFMA_NO_EXACT")) return 0;
     fprintf(stderr, "[icpgpu] WARNING: ICPGPU_MFMA_NO_EXACT is set -- the matrix-core search skips its exact path, every brute-force result "
@@ -423,18 +443,9 @@ hipError_t launch_nn_brute_bf16(const float4* src_sorted, int n_q, const float4*
     return 1;
   }();
   const int flags = no_exact;
-  const int G = check ? 2 : g_env == 4 ? 4 : 2;  // (the test mode: its own instantiation, one shape)
-  const int TILE = check ? 512 : tile_env == 1024 ? 1024 : 512;
-  const int BLOCK = check ? 256 : block_env == 512 ? 512 : 256;
-  const int per_block = (BLOCK / 64) * 32 * G;
-  const int grid_x = (n_q + per_block - 1) / per_block;
-  int splits = (num_cus * waves_env * 4 / (BLOCK / 64) + grid_x - 1) / grid_x;
-  const int max_splits = (n_t + TILE - 1) / TILE;
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  int per = (n_t + splits - 1) / splits;
-  per = ((per + TILE - 1) / TILE) * TILE;
-  splits = (n_t + per - 1) / per;
+  const MatrixNnPlan plan = plan_nn_brute_bf16(n_q, n_t, num_cus, check != nullptr);
+  const int G = plan.g, TILE = plan.tile, BLOCK = plan.block;
+  const int grid_x = plan.grid_x, splits = plan.splits, per = plan.tgt_per_split;
 #define ICPGPU_BF16_LAUNCH(BLK, ...)                                                                                       \
   hipLaunchKernelGGL((__VA_ARGS__), dim3(grid_x, splits), dim3(BLK), 0, stream, src_sorted, n_q, tgt, n_t, T, per, splits, \
                      keys, seed, flags, check)

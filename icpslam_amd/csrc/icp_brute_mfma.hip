@@ -27,8 +27,13 @@
 //   p' and q' are rounded differences (1 each, of |p'|, |q'|): moves |q' - p'|^2 by <= 2 |q-p| (|p'| + |q'|) 2^-24 sqrt(3)
 //   |q'|^2 by three roundings (3 of |q'|^2); the four fused steps of the chain (4 of 2|p'||q'| + |q'|^2)
 //   sum <= 2^-24 * 16 (P + |q'|)^2 <= 2^-24 * 32 (P^2 + |q'|^2) = 2^-19 (P^2 + |q'|^2); tau carries a further factor 2.
-// tests/test_gpu_parity.py / test_gpu_grid.py / test_gpu_fullsize.py compare this kernel's keys with the VALU kernel and the
-// oracle bit for bit (ties, duplicates, NaN / inf points, far outliers, 200k x 200k and 200k x 1M).
+// This kernel runs only where brute_variant = 2 asks for it (the default from 8192 x 8192 points on is icp_brute_bf16.hip):
+// tests/test_gpu_brute_edges.py holds its keys to the oracle's bit for bit at every boundary of its launch arithmetic (sources
+// 1 .. 8193, targets around every step and tile, several tiles per split, a non-finite target in every row of a step, ties
+// across every seam, degenerate centres, seeded sweeps) and reads from the ICPGPU_DEBUG line that it is this kernel that ran;
+// tests/test_gpu_brute_bf16.py compares it with the bf16 and the VALU kernel on seven clouds of 9 000 - 90 000 points, and
+// tests/history_model.py runs it among a context's histories.  (test_gpu_parity.py, test_gpu_grid.py and test_gpu_fullsize.py
+// run the default variant: since the default changed they exercise the bf16 kernel or the VALU kernel, not this one.)
 #include <hip/hip_runtime.h>
 
 #include "icp_env.h"
@@ -271,6 +276,30 @@ __global__ __launch_bounds__(MF_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))
 
 }  // namespace
 
+// The launch shape: ICPGPU_MFMA_G (sources per wave / 32: 2 or 4) and ICPGPU_MFMA_WAVES (target waves per SIMD the splits aim
+// at) are experiments, read once per process.
+MatrixNnPlan plan_nn_brute_mfma(int n_q, int n_t, int num_cus) {
+  static const int g_env = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_MFMA_G"); return e ? atoi(e) : 2; }();
+  static const int waves_env = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_MFMA_WAVES"); return e ? atoi(e) : 32; }();
+  MatrixNnPlan p;
+  p.g = g_env == 4 ? 4 : 2;
+  p.tile = MF_TILE;
+  p.block = MF_BLOCK;
+  const int per_block = (MF_BLOCK / 64) * 32 * p.g;
+  p.grid_x = (n_q + per_block - 1) / per_block;
+  // target splits for ~32 waves' worth of workgroups per SIMD (measured at 200k x 200k: 2 -> 4.8 ms, 8 -> 3.45, 16 -> 3.23,
+  // 32 -> 3.14: the tail of the last round of workgroups), never less than one tile per split
+  int splits = (num_cus * waves_env + p.grid_x - 1) / p.grid_x;
+  const int max_splits = (n_t + MF_TILE - 1) / MF_TILE;
+  if (splits > max_splits) splits = max_splits;
+  if (splits < 1) splits = 1;
+  int per = (n_t + splits - 1) / splits;
+  per = ((per + MF_TILE - 1) / MF_TILE) * MF_TILE;
+  p.tgt_per_split = per;
+  p.splits = (n_t + per - 1) / per;
+  return p;
+}
+
 // src_sorted: the source in cell order with the ORIGINAL index in .w (what the grid machinery's sorted copy holds); keys are
 // written at the original indices and must be pre-filled with kEmptyKey (points missing from src_sorted -- the non-finite ones
 // -- stay unmatched, and target splits merge by atomic min).
@@ -278,28 +307,15 @@ __global__ __launch_bounds__(MF_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))
 hipError_t launch_nn_brute_mfma(const float4* src_sorted, int n_q, const float4* tgt, int n_t, const Xform& T, int num_cus,
                                 unsigned long long* keys, const unsigned long long* seed, hipStream_t stream) {
   if (n_q <= 0 || n_t <= 0) return hipSuccess;
-  // experiments: ICPGPU_MFMA_G (sources per wave / 32: 2 or 4), ICPGPU_MFMA_WAVES (target waves per SIMD the splits aim at),
-  // ICPGPU_MFMA_NO_EXACT (timing only: the exact path is skipped, results are wrong)
-  static const int g_env = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_MFMA_G"); return e ? atoi(e) : 2; }();
-  static const int waves_env = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_MFMA_WAVES"); return e ? atoi(e) : 32; }();
+  // experiment: ICPGPU_MFMA_NO_EXACT (timing only: the exact path is skipped, results are wrong)
   static const int no_exact = [] {
     if (!ICPGPU_DEV_ENV("ICPGPU_MFMA_NO_EXACT")) return 0;
     fprintf(stderr, "[icpgpu] WARNING: ICPGPU_MFMA_NO_EXACT is set -- the matrix-core search skips its exact path, every brute-force result "
                     "of this process is WRONG (a timing experiment's switch, never a production setting)\n");
     return 1;
   }();
-  const int G = g_env == 4 ? 4 : 2;
-  const int per_block = (MF_BLOCK / 64) * 32 * G;
-  const int grid_x = (n_q + per_block - 1) / per_block;
-  // target splits for ~32 waves' worth of workgroups per SIMD (measured at 200k x 200k: 2 -> 4.8 ms, 8 -> 3.45, 16 -> 3.23,
-  // 32 -> 3.14: the tail of the last round of workgroups), never less than one tile per split
-  int splits = (num_cus * waves_env + grid_x - 1) / grid_x;
-  const int max_splits = (n_t + MF_TILE - 1) / MF_TILE;
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  int per = (n_t + splits - 1) / splits;
-  per = ((per + MF_TILE - 1) / MF_TILE) * MF_TILE;
-  splits = (n_t + per - 1) / per;
+  const MatrixNnPlan plan = plan_nn_brute_mfma(n_q, n_t, num_cus);
+  const int G = plan.g, grid_x = plan.grid_x, splits = plan.splits, per = plan.tgt_per_split;
   static const int pipe_env = [] { const char* e = ICPGPU_DEV_ENV("ICPGPU_MFMA_PIPE"); return e ? atoi(e) : 0; }();
 #define ICPGPU_MFMA_LAUNCH(...)                                                                                         \
   hipLaunchKernelGGL((__VA_ARGS__), dim3(grid_x, splits), dim3(MF_BLOCK), 0, stream, src_sorted, n_q, tgt, n_t, T, per, splits, \

@@ -65,6 +65,18 @@ struct NnPlan {
 
 NnPlan plan_nn_brute(int n_s, int n_t, int variant, int num_cus);
 
+// The launch shape of a matrix-core brute-force sweep (icp_brute_mfma.hip, icp_brute_bf16.hip): g groups of 32 sources per wave,
+// block threads per workgroup (block / 64 * 32 g sources), tile targets per LDS tile; grid (grid_x, splits), every split
+// tgt_per_split targets (whole tiles).  The launchers launch what these say; nn_keys_brute prints it under ICPGPU_DEBUG.
+struct MatrixNnPlan {
+  int g, tile, block;
+  int grid_x, splits, tgt_per_split;
+};
+MatrixNnPlan plan_nn_brute_mfma(int n_q, int n_t, int num_cus);
+MatrixNnPlan plan_nn_brute_bf16(int n_q, int n_t, int num_cus, bool check);
+// (the plain kernel's shape for the same line: NN_TILE, NN_BLOCK, source points per lane)
+void nn_brute_shape(const NnPlan& plan, int* tile, int* block, int* per_lane);
+
 // keys[i] = min over target of (d2, j) for p = T*src[i]. When plan.splits > 1 keys must be pre-filled with kEmptyKey.
 hipError_t launch_nn_brute(const float4* src, int n_s, const float4* tgt, int n_t, const Xform& T, const NnPlan& plan,
                            unsigned long long* keys, hipStream_t stream);

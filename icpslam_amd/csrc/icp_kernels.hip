@@ -409,6 +409,12 @@ NnPlan plan_nn_brute(int n_s, int n_t, int variant, int num_cus) {
   return p;
 }
 
+void nn_brute_shape(const NnPlan& plan, int* tile, int* block, int* per_lane) {
+  *tile = NN_TILE;
+  *block = NN_BLOCK;
+  *per_lane = points_per_lane(plan.variant);
+}
+
 hipError_t launch_nn_brute(const float4* src, int n_s, const float4* tgt, int n_t, const Xform& T, const NnPlan& plan,
                            unsigned long long* keys, hipStream_t stream) {
   if (n_s <= 0) return hipSuccess;

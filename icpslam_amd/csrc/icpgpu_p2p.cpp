@@ -7,6 +7,16 @@
 
 namespace icpgpu_impl {
 
+// ICPGPU_DEBUG (read per call): which brute-force kernel a sweep ran and in what shape -- the one place a test can see that the
+// matrix-core kernels ran at all (a source grid that refuses its cloud falls back to the plain kernel without a word otherwise).
+// g: groups of 32 sources per wave (matrix kernels) or source points per lane (valu).
+static void say_brute_sweep(const icpgpu_ctx* c, const char* kernel, int n_q, int n_s, int n_t, int g, int tile, int block, int grid_x,
+                            int splits, int per, bool seeded) {
+  if (!std::getenv("ICPGPU_DEBUG")) return;
+  fprintf(stderr, "[icpgpu] brute kernel=%s n_q=%d n_s=%d n_t=%d num_cus=%d G=%d TILE=%d BLOCK=%d grid_x=%d splits=%d per=%d seeded=%d\n", kernel,
+          n_q, n_s, n_t, c->num_cus, g, tile, block, grid_x, splits, per, seeded ? 1 : 0);
+}
+
 int nn_keys_brute(icpgpu_ctx* c, const float4* tgt_pts, int n_t, const Xform& T, unsigned long long* keys, bool* used_mfma) {
   const int n_s = (int)c->src.n;
   if (used_mfma) *used_mfma = false;
@@ -27,6 +37,8 @@ int nn_keys_brute(icpgpu_ctx* c, const float4* tgt_pts, int n_t, const Xform& T,
       HIP_TRY(c, launch_fill_keys(keys, n_s, c->stream));
       const unsigned long long* seed_keys = seeded ? static_cast<const unsigned long long*>(S.keys.ptr) : nullptr;
       if (c->params.brute_variant == 2) {
+        const MatrixNnPlan mp = plan_nn_brute_mfma(c->src_grid.n_binned, n_t, c->num_cus);
+        say_brute_sweep(c, "mfma", c->src_grid.n_binned, n_s, n_t, mp.g, mp.tile, mp.block, mp.grid_x, mp.splits, mp.tgt_per_split, seeded);
         HIP_TRY(c, launch_nn_brute_mfma(static_cast<const float4*>(c->src_grid.sorted.ptr), c->src_grid.n_binned, tgt_pts, n_t, T,
                                         c->num_cus, keys, seed_keys, c->stream));
       } else {
@@ -42,6 +54,8 @@ int nn_keys_brute(icpgpu_ctx* c, const float4* tgt_pts, int n_t, const Xform& T,
           d_check = static_cast<unsigned long long*>(O.check.ptr);
           HIP_TRY(c, hipMemsetAsync(d_check, 0, 2 * sizeof(unsigned long long), c->stream));
         }
+        const MatrixNnPlan mp = plan_nn_brute_bf16(n_b, n_t, c->num_cus, d_check != nullptr);
+        say_brute_sweep(c, d_check ? "bf16-check" : "bf16", n_b, n_s, n_t, mp.g, mp.tile, mp.block, mp.grid_x, mp.splits, mp.tgt_per_split, seeded);
         HIP_TRY(c, launch_nn_brute_bf16(static_cast<const float4*>(O.pts.ptr), n_b, tgt_pts, n_t, T, c->num_cus, keys, seed_keys,
                                         d_check, c->stream));
         if (d_check) {
@@ -67,6 +81,11 @@ int nn_keys_brute(icpgpu_ctx* c, const float4* tgt_pts, int n_t, const Xform& T,
     }
   }
   const NnPlan plan = plan_nn_brute(n_s, n_t, c->nn_variant < 0 ? 0 : c->nn_variant, c->num_cus);
+  {
+    int tile, block, per_lane;
+    nn_brute_shape(plan, &tile, &block, &per_lane);
+    say_brute_sweep(c, "valu", n_s, n_s, n_t, per_lane, tile, block, plan.grid_x, plan.splits, plan.tgt_per_split, false);
+  }
   if (plan.splits > 1 && n_t > 0) HIP_TRY(c, launch_fill_keys(keys, n_s, c->stream));
   HIP_TRY(c, launch_nn_brute(c->src.data(), n_s, tgt_pts, n_t, T, plan, keys, c->stream));
   return ICPGPU_OK;
