@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "icp_brute_plan.h"
+
 namespace icpgpu {
 
 // Rigid transform as 12 floats (row-major 3x4) so that it travels in SGPRs as a kernel argument.
@@ -65,15 +67,19 @@ struct NnPlan {
 
 NnPlan plan_nn_brute(int n_s, int n_t, int variant, int num_cus);
 
-// The launch shape of a matrix-core brute-force sweep (icp_brute_mfma.hip, icp_brute_bf16.hip): g groups of 32 sources per wave,
-// block threads per workgroup (block / 64 * 32 g sources), tile targets per LDS tile; grid (grid_x, splits), every split
-// tgt_per_split targets (whole tiles).  The launchers launch what these say; nn_keys_brute prints it under ICPGPU_DEBUG.
-struct MatrixNnPlan {
-  int g, tile, block;
-  int grid_x, splits, tgt_per_split;
-};
+// The launch shape of a matrix-core brute-force sweep (MatrixNnPlan and its arithmetic: icp_brute_plan.h), with each unit's
+// development switches applied.  The launchers launch what these say; nn_keys_brute prints it under ICPGPU_DEBUG.
 MatrixNnPlan plan_nn_brute_mfma(int n_q, int n_t, int num_cus);
 MatrixNnPlan plan_nn_brute_bf16(int n_q, int n_t, int num_cus, bool check);
+// ICPGPU_MFMA_NO_EXACT (a timing experiment: the exact path is skipped, results are WRONG), read and warned about once per process
+int matrix_nn_no_exact();
+// the launch line of both launchers: `kernel` over the plan's grid with the arguments the two kernels share, then `extra`
+template <typename Kernel, typename... Extra>
+void launch_matrix_nn(Kernel kernel, const MatrixNnPlan& plan, hipStream_t stream, const float4* src_sorted, int n_q, const float4* tgt,
+                      int n_t, const Xform& T, unsigned long long* keys, const unsigned long long* seed, Extra... extra) {
+  hipLaunchKernelGGL(kernel, dim3(plan.grid_x, plan.splits), dim3(plan.block), 0, stream, src_sorted, n_q, tgt, n_t, T,
+                     plan.tgt_per_split, plan.splits, keys, seed, matrix_nn_no_exact(), extra...);
+}
 // (the plain kernel's shape for the same line: NN_TILE, NN_BLOCK, source points per lane)
 void nn_brute_shape(const NnPlan& plan, int* tile, int* block, int* per_lane);
 

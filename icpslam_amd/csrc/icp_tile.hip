@@ -18,49 +18,25 @@
 // A converged sweep at 200k x 200k offers ~2 000 candidates to each source instead of 200 000 (or the octant's ~150 at 70 times
 // the price per pair).  Exactness: the box holds every cell that holds a point within a source's radius (the binning
 // expression is monotone and the box is the float-rounded ball, inflated); inside the box the search is the brute-force
-// kernel's, whose bound is certified (header of icp_brute_bf16.hip; tau is small here: all candidates are within metres of the
+// kernel's, whose bound is certified (icp_bound_device.h: the error budget; tau is small here: all candidates are within metres of the
 // centre).  The key a source ends with is its exact nearest neighbour if that neighbour lies within the threshold, in contract
 // arithmetic with the lowest original index among ties -- what nn_quad_kernel returns -- and empty otherwise.
 #include <hip/hip_runtime.h>
 
-#include "icp_env.h"
-
 #include <cstdio>
 #include <cstdlib>
-#include <math.h>
 
-#include "icp_device.h"
+#include "icp_bound_device.h"
+#include "icp_env.h"
 #include "icp_grid_device.h"
-#include "icp_kernels.h"
 
 namespace icpgpu {
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr float kTauBf16 = 1.220703125e-04f;  // 2^-13 (icp_brute_bf16.hip's error budget)
-constexpr float kTinyScale = 1e-18f;
 constexpr int TS_BLOCK = 256;   // 4 waves x 64 sources
 constexpr int TS_G = 2;         // groups of 32 sources per wave
 constexpr int TS_TILE = 512;    // candidates per LDS tile
 constexpr int TS_ROWS = 1024;   // segments (cell rows) listed at a time
-
-__device__ __forceinline__ float min3f(float a, float b, float c) {
-  float r;
-  asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-__device__ __forceinline__ unsigned int pack_bf16(float lo, float hi) {
-  const floatx2 f = {lo, hi};
-  return __builtin_bit_cast(unsigned int, __builtin_convertvector(f, bf16x2));
-}
-__device__ __forceinline__ float bf16_lo(unsigned int p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned int p) { return __uint_as_float(p & 0xffff0000u); }
-__device__ __forceinline__ unsigned int dup_lo(unsigned int p) { return __builtin_amdgcn_perm(p, p, 0x01000100u); }
-__device__ __forceinline__ unsigned int dup_hi(unsigned int p) { return __builtin_amdgcn_perm(p, p, 0x03020302u); }
 
 __global__ __launch_bounds__(TS_BLOCK) void nn_tile_kernel(const float4* __restrict__ src_morton, int n_q, Xform T,
                                                            const float4* __restrict__ sorted,
@@ -106,7 +82,7 @@ __global__ __launch_bounds__(TS_BLOCK) void nn_tile_kernel(const float4* __restr
       const float4 t = prev[min(k, n_q - 1)];
       const float e = dist2(t.x, t.y, t.z, px[gi], py[gi], pz[gi]);
       if (e <= thr) {
-        best[gi] = ((unsigned long long)__float_as_uint(e) << 32) | __float_as_uint(t.w);
+        best[gi] = key_of(e, __float_as_uint(t.w));
         r2[gi] = e;
         bqx[gi] = t.x; bqy[gi] = t.y; bqz[gi] = t.z;
       }
@@ -116,7 +92,7 @@ __global__ __launch_bounds__(TS_BLOCK) void nn_tile_kernel(const float4* __restr
         const float4 t = tgt[j];
         const float e = dist2(t.x, t.y, t.z, px[gi], py[gi], pz[gi]);
         if (e <= thr) {  // the old neighbour is a target point: a candidate, and a ball the new neighbour lies in
-          best[gi] = ((unsigned long long)__float_as_uint(e) << 32) | j;
+          best[gi] = key_of(e, j);
           r2[gi] = e;
           bqx[gi] = t.x; bqy[gi] = t.y; bqz[gi] = t.z;
         }
@@ -133,32 +109,7 @@ __global__ __launch_bounds__(TS_BLOCK) void nn_tile_kernel(const float4* __restr
       valid[gi] = false;  // (a negative threshold accepts nothing)
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = fminf(lo[a], __shfl_xor(lo[a], off, 64));
-      hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off, 64));
-    }
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      s_box[wave][a] = lo[a];
-      s_box[wave][3 + a] = hi[a];
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    lo[a] = s_box[0][a];
-    hi[a] = s_box[0][3 + a];
-#pragma unroll
-    for (int w = 1; w < BLOCK / 64; ++w) {
-      lo[a] = fminf(lo[a], s_box[w][a]);
-      hi[a] = fmaxf(hi[a], s_box[w][3 + a]);
-    }
-  }
+  workgroup_box<BLOCK>(lo, hi, s_box, lane, wave);
   // cells of the box (cell_of is the binning's own expression, monotone per axis: every point between lo and hi lands between
   // their cells); clamped to the grid; an empty intersection leaves the seeds as they are
   int c0x, c0y, c0z, c1x, c1y, c1z;
@@ -170,25 +121,21 @@ __global__ __launch_bounds__(TS_BLOCK) void nn_tile_kernel(const float4* __restr
   const int rows_y = any ? c1y - c0y + 1 : 0, rows_z = any ? c1z - c0z + 1 : 0;
   const int n_rows = rows_y * rows_z;
 
-  // ---- the filter's source side (icp_brute_bf16.hip): centre, P, the B operands ------------------------------------------------
+  // ---- the filter's source side (icp_bound_device.h): centre, P, the B operands ------------------------------------------------
   const float cx = 0.5f * lo[0] + 0.5f * hi[0], cy = 0.5f * lo[1] + 0.5f * hi[1], cz = 0.5f * lo[2] + 0.5f * hi[2];
   uint4 bop[G];
   float p2[G], bound[G], pmax2 = 0.f;
 #pragma unroll
   for (int gi = 0; gi < G; ++gi) {
     const float ux = px[gi] - cx, uy = py[gi] - cy, uz = pz[gi] - cz;
-    p2[gi] = __builtin_fmaf(uz, uz, __builtin_fmaf(uy, uy, ux * ux));
+    p2[gi] = len2(ux, uy, uz);
     if (valid[gi]) pmax2 = fmaxf(pmax2, p2[gi]);
-    const float Ux = -2.0f * ux, Uy = -2.0f * uy, Uz = -2.0f * uz;
-    const unsigned int hxy = pack_bf16(Ux, Uy), lxy = pack_bf16(Ux - bf16_lo(hxy), Uy - bf16_hi(hxy));
-    const unsigned int hz = pack_bf16(Uz, 1.0f), lz = pack_bf16(Uz - bf16_lo(hz), 0.0f);
-    const unsigned int dx = (hxy & 0xffffu) | (lxy << 16), dy = (hxy >> 16) | (lxy & 0xffff0000u);
-    const unsigned int dz = (hz & 0xffffu) | (lz << 16);
-    bop[gi] = half ? make_uint4(dz, dz, 0x3F803F80u, 0u) : make_uint4(dx, dx, dy, dy);
-    // everything that can beat or tie what is known (or be accepted at all) has |q - p|^2 - |u|^2 <= r2 - |u|^2, widened for
-    // the rounding of p2 and of this subtraction; a source that takes no part never asks for an exact evaluation
-    bound[gi] = valid[gi] ? __builtin_fmaf(r2[gi] + p2[gi], 9.5367431640625e-07f, r2[gi] - p2[gi]) : -INFINITY;
+    bop[gi] = bf16_source_operand(ux, uy, uz, half);
+    // everything that can beat or tie what is known (or be accepted at all) lies within r2: the bound of that distance; a source
+    // that takes no part never asks for an exact evaluation
+    bound[gi] = valid[gi] ? bound_of(r2[gi], p2[gi]) : -INFINITY;
   }
+  // (workgroup_max of icp_bound_device.h, written out: called as the function, this kernel comes out one VGPR wider)
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) pmax2 = fmaxf(pmax2, __shfl_xor(pmax2, off, 64));
   if (lane == 0) s_pmax[wave] = pmax2;
@@ -198,8 +145,7 @@ __global__ __launch_bounds__(TS_BLOCK) void nn_tile_kernel(const float4* __restr
   for (int w = 1; w < BLOCK / 64; ++w) pmax2 = fmaxf(pmax2, s_pmax[w]);
 
   if (stats) { const unsigned long long t = __builtin_amdgcn_s_memtime(); t_pre = t - tk0; tk0 = t; }
-  float minus_inf;  // (opaque to the compiler: see icp_brute_bf16.hip)
-  asm volatile("v_mov_b32 %0, 0xff800000" : "=v"(minus_inf));
+  const float minus_inf = opaque_minus_inf();
   unsigned long long n_cand = 0;
 
   // ---- the box's rows, TS_ROWS at a time: segments of the sorted copy, their running total, this workgroup's share ---------------
@@ -270,18 +216,10 @@ __global__ __launch_bounds__(TS_BLOCK) void nn_tile_kernel(const float4* __restr
 #pragma unroll
       for (int u = 0; u < TILE / BLOCK; ++u) {
         const int kk = u * BLOCK + threadIdx.x;
-        uint4 r0 = make_uint4(0u, 0u, 0u, 0u), r1 = make_uint4(0u, 0u, 0x00007F80u, 0u);  // a row past the end: S = +inf
+        uint4 r0, r1;
+        bf16_padding_records(r0, r1);
         const float4 q = qn[u];
-        if (kk < lim) {
-          const float vx = q.x - cx, vy = q.y - cy, vz = q.z - cz;
-          const float q2 = __builtin_fmaf(vz, vz, __builtin_fmaf(vy, vy, vx * vx));
-          const float scale = pmax2 + q2;
-          const float S = scale < kTinyScale ? -INFINITY : q2 - scale * kTauBf16;
-          const unsigned int hxy = pack_bf16(vx, vy), lxy = pack_bf16(vx - bf16_lo(hxy), vy - bf16_hi(hxy));
-          const unsigned int hzs = pack_bf16(vz, S), lzs = pack_bf16(vz - bf16_lo(hzs), isinf(S) ? 0.0f : S - bf16_hi(hzs));
-          r0 = make_uint4(dup_lo(hxy), dup_lo(lxy), dup_hi(hxy), dup_hi(lxy));
-          r1 = make_uint4(dup_lo(hzs), dup_lo(lzs), (hzs >> 16) | (lzs & 0xffff0000u), 0u);
-        }
+        if (kk < lim) bf16_target_records(q.x - cx, q.y - cy, q.z - cz, pmax2, r0, r1);
         tile[kk] = q;
         aop[kk] = r0;
         aop[TILE + kk] = r1;
@@ -300,23 +238,14 @@ __global__ __launch_bounds__(TS_BLOCK) void nn_tile_kernel(const float4* __restr
           const floatx16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
           acc[gi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bop[gi]), zero, 0, 0, 0);
         }
-        __builtin_amdgcn_sched_barrier(0);
-        float tail[G];
-#pragma unroll
-        for (int gi = 0; gi < G; ++gi) tail[gi] = __builtin_amdgcn_fmed3f(acc[gi][14], acc[gi][15], minus_inf);
-        __builtin_amdgcn_sched_barrier(0);
         // the fold keeps its five partial minima: they say which values to look at when the bound is undercut
-        float part[G][5], mn[G];
+        float tail[G], part[G][5], mn[G];
+        first_read_tails<G>(acc, minus_inf, tail);
         bool hit = false;
 #pragma unroll
         for (int gi = 0; gi < G; ++gi) {
-          const floatx16 d = acc[gi];
-          part[gi][0] = min3f(d[0], d[1], d[2]);
-          part[gi][1] = min3f(d[3], d[4], d[5]);
-          part[gi][2] = min3f(d[6], d[7], d[8]);
-          part[gi][3] = min3f(d[9], d[10], d[11]);
-          part[gi][4] = min3f(d[12], d[13], tail[gi]);
-          mn[gi] = min3f(min3f(part[gi][0], part[gi][1], part[gi][2]), part[gi][3], part[gi][4]);
+          fold_parts(acc[gi], tail[gi], part[gi]);
+          mn[gi] = fold_min(part[gi]);
           hit |= mn[gi] <= bound[gi];
         }
         if (!(use_prev & 2) && __ballot(hit)) {  // (bit 1: timing experiments only -- no exact path, wrong results)
@@ -330,15 +259,15 @@ __global__ __launch_bounds__(TS_BLOCK) void nn_tile_kernel(const float4* __restr
 #pragma unroll
               for (int v = 3 * pt; v < (pt == 4 ? 16 : 3 * pt + 3); ++v) {
                 if (d[v] <= bound[gi]) {
-                  const int row = 8 * (v >> 2) + 4 * half + (v & 3);
+                  const int row = row_of(v, half);
                   if (st + row < lim) {
                     const float4 t = tile[st + row];
                     const float e = dist2(t.x, t.y, t.z, px[gi], py[gi], pz[gi]);
-                    const unsigned long long key = ((unsigned long long)__float_as_uint(e) << 32) | __float_as_uint(t.w);
+                    const unsigned long long key = key_of(e, __float_as_uint(t.w));
                     if (e <= thr && key < best[gi]) {  // (NaN and inf distances fail the first test)
                       best[gi] = key;
                       bqx[gi] = t.x; bqy[gi] = t.y; bqz[gi] = t.z;
-                      bound[gi] = __builtin_fmaf(e + p2[gi], 9.5367431640625e-07f, e - p2[gi]);
+                      bound[gi] = bound_of(e, p2[gi]);
                     }
                   }
                 }
@@ -361,26 +290,19 @@ __global__ __launch_bounds__(TS_BLOCK) void nn_tile_kernel(const float4* __restr
     atomicAdd(&stats[6], n_cand);
     atomicMax(&stats[7], t_pre + t_rows + t_fill + t_steps);
   }
-  // the two half-waves hold the same sources: merge, write under the source's original index
 #pragma unroll
   for (int gi = 0; gi < G; ++gi) {
-    const unsigned int ohi = (unsigned int)__shfl_xor((int)(best[gi] >> 32), 32, 64);
-    const unsigned int olo = (unsigned int)__shfl_xor((int)(unsigned int)best[gi], 32, 64);
-    const unsigned long long other = ((unsigned long long)ohi << 32) | olo;
-    const unsigned long long k = other < best[gi] ? other : best[gi];
-    if (prev && splits == 1) {  // the winner as a point, for the next sweep (the half that holds it writes)
+    const unsigned long long k = merge_halves(best[gi]);
+    const bool mine = k == best[gi], write = half == 0 && q0 + gi * 32 + col < n_q;
+    if (prev && splits == 1) {  // the winner as a point, for the next sweep (the half that holds it hands it over)
       const float ox = __shfl_xor(bqx[gi], 32, 64), oy = __shfl_xor(bqy[gi], 32, 64), oz = __shfl_xor(bqz[gi], 32, 64);
-      const bool mine = best[gi] <= other;
-      if (half == 0 && q0 + gi * 32 + col < n_q) {
+      if (write) {
         const float none = __builtin_nanf("");
         prev[q0 + gi * 32 + col] = k == kEmptyKey ? make_float4(none, none, none, 0.f)
                                                    : make_float4(mine ? bqx[gi] : ox, mine ? bqy[gi] : oy, mine ? bqz[gi] : oz, __uint_as_float((unsigned int)k));
       }
     }
-    if (half == 0 && q0 + gi * 32 + col < n_q && k != kEmptyKey) {
-      if (splits > 1) atomicMin(&keys[orig[gi]], k);
-      else keys[orig[gi]] = k;
-    }
+    if (write && k != kEmptyKey) write_key(keys, orig[gi], k, splits);
   }
 }
 
