@@ -116,6 +116,7 @@ EXPORTS = [
     "icpgpu_fpfh_estimation",
     "icpgpu_feature_knn",
     "icpgpu_euclidean_cluster_extraction", "icpgpu_cluster_fetch",
+    "icpgpu_region_growing", "icpgpu_region_fetch",
     "icpgpu_scp_align", "icpgpu_scp_fetch", "icpgpu_scp_stats",
     "icpgpu_iss_keypoints", "icpgpu_iss_fetch", "icpgpu_iss_stats",
     "icpgpu_boundary_estimation", "icpgpu_iss_keypoints_border", "icpgpu_iss_fetch_border",
@@ -241,6 +242,8 @@ def load():
     L.icpgpu_feature_knn.argtypes = [vp, fp, C.c_size_t, fp, C.c_size_t, C.c_int, ip, fp, ip]
     L.icpgpu_euclidean_cluster_extraction.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.icpgpu_cluster_fetch.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_int64), ip, ip, ip]
+    L.icpgpu_region_growing.argtypes = [vp, fp, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.icpgpu_region_fetch.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_int64), ip, ip, ip, ip, ip]
     szp = C.POINTER(C.c_size_t)
     L.icpgpu_sac_plane_segmentation.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_uint64, C.c_int, dp, C.c_double, fp, szp, ip, ip]
     L.icpgpu_sac_fetch.argtypes = [vp, C.c_size_t, C.c_size_t, ip, ip, ip, ip, fp, dp, szp]

@@ -8,6 +8,7 @@
 //     and takes the pairs (i, j) with j < i, so that every edge is handled once.  Per batch of 64 candidates every lane finds the
 //     root of its own j, the wave takes the minimum m of those roots and of the smallest root it knows for i, and every lane whose
 //     root is not m hooks it under m: in a dense cloud most candidates already share a root and the batch costs finds only;
+//   (the find / hook / path-halving functions themselves: icp_unionfind_device.h, shared with icp_region.hip)
 //   * a hook puts the LARGER root under the SMALLER with one atomicCAS(parent[larger], larger, smaller).  parent[x] <= x always, and
 //     a value only ever decreases, so a find walks a strictly decreasing chain, and when everything is hooked the root of a
 //     component is its lowest index whatever order the hooks arrived in: the answer is the same from run to run;
@@ -28,42 +29,12 @@
 #include "icp_grid_device.h"
 #include "icp_kernels.h"
 #include "icp_search_device.h"
+#include "icp_unionfind_device.h"
 
 namespace icpgpu {
 namespace {
 
 constexpr int CL_BLOCK = 256, CL_WAVES = CL_BLOCK / 64;
-constexpr int kNoRoot = 0x7FFFFFFF;
-
-__device__ __forceinline__ int parent_load(const int* parent, int x) {
-  return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the root of x (x is a finite point's index).  Ends: every step moves to a strictly smaller index.
-__device__ __forceinline__ int cluster_find(int* parent, int x) {
-  int p = parent_load(parent, x);
-  while (p != x) {
-    const int gp = parent_load(parent, p);
-    if (gp != p) __hip_atomic_fetch_min(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // path halving
-    x = p;
-    p = gp;
-  }
-  return x;
-}
-
-// joins the sets of a and b.  Ends: a failed CAS hands back a smaller parent of `hi`, and the pair of roots only ever decreases.
-__device__ __forceinline__ void cluster_unite(int* parent, int a, int b) {
-  for (;;) {
-    a = cluster_find(parent, a);
-    b = cluster_find(parent, b);
-    if (a == b) return;
-    const int hi = max(a, b), lo = min(a, b);
-    const int old = atomicCAS(parent + hi, hi, lo);
-    if (old == hi) return;
-    a = old;  // hi is no root any more: go on from what it was hooked under
-    b = lo;
-  }
-}
 
 __global__ __launch_bounds__(CL_BLOCK) void cluster_init_kernel(const float4* __restrict__ cloud, int n, int* __restrict__ parent,
                                                                 int* __restrict__ sizes) {
@@ -99,14 +70,7 @@ __global__ __launch_bounds__(CL_BLOCK) void cluster_flatten_kernel(int* parent, 
   int root = -1;
   if (i < n && parent_load(parent, i) >= 0) root = cluster_find(parent, i);
   if (i < n) component[i] = root;
-  // one atomic for the lanes that share the first lane's root (neighbouring indices mostly do), one each for the others
-  const int first = __builtin_amdgcn_readfirstlane(root);
-  const unsigned long long same = __ballot(root == first);
-  if (root == first) {
-    if (first >= 0 && (threadIdx.x & 63u) == (unsigned int)(__ffsll((long long)same) - 1)) atomicAdd(sizes + first, __popcll(same));
-  } else if (root >= 0) {
-    atomicAdd(sizes + root, 1);
-  }
+  cluster_count_root(sizes, root);
 }
 
 // per point: the first sort's pair.  An emitted root carries n - size (0 .. n - 1), every other point n.
@@ -168,19 +132,14 @@ unsigned int bit_length(int n) {
 
 size_t cluster_scratch_ints(int n) { return std::max(radix_sort_scratch_ints(n), exclusive_scan_scratch_ints(n + 1)); }
 
-hipError_t launch_cluster_extract(const float4* cloud, int n, bool any_finite, const float4* sorted, const int* cell_start, const GridDesc& g,
-                                  int shells, float r2, int min_size, int max_size, int* parent, int* sizes, int* component, int* labels,
-                                  int* rank_of, int* csize, int* cstart, long long* cstart64, int* keys, int* vals, int* scratch, int* counts,
-                                  hipStream_t stream) {
+// the tail after the components are named and counted: the emitted roots' ranks, every point's label, the two stable sorts
+hipError_t launch_cluster_tail(const int* component, const int* sizes, int n, int min_size, int max_size, int* labels, int* rank_of, int* csize,
+                               int* cstart, long long* cstart64, int* keys, int* vals, int* scratch, int* counts, hipStream_t stream) {
   hipError_t e;
   if ((e = hipMemsetAsync(counts, 0, 2 * sizeof(int), stream)) != hipSuccess) return e;
   if (n <= 0) return hipMemsetAsync(cstart64, 0, sizeof(long long), stream);
   const dim3 per_point((n + CL_BLOCK - 1) / CL_BLOCK), per_slot((n + 1 + CL_BLOCK - 1) / CL_BLOCK), block(CL_BLOCK);
   const unsigned int end_bit = bit_length(n);  // the keys of both sorts are 0 .. n
-  hipLaunchKernelGGL(cluster_init_kernel, per_point, block, 0, stream, cloud, n, parent, sizes);
-  if (any_finite && r2 > 0.f)  // (r2 == 0: no d2 is below it)
-    hipLaunchKernelGGL(cluster_hook_kernel, dim3((n + CL_WAVES - 1) / CL_WAVES), block, 0, stream, cloud, n, sorted, cell_start, g, shells, r2, parent);
-  hipLaunchKernelGGL(cluster_flatten_kernel, per_point, block, 0, stream, parent, n, component, sizes);
   hipLaunchKernelGGL(cluster_root_keys_kernel, per_point, block, 0, stream, component, sizes, n, min_size, max_size, keys, vals, rank_of);
   if ((e = launch_radix_sort_pairs(keys, vals, n, end_bit, scratch, stream)) != hipSuccess) return e;
   hipLaunchKernelGGL(cluster_rank_kernel, per_slot, block, 0, stream, keys + n, vals + n, n, rank_of, csize);
@@ -188,6 +147,20 @@ hipError_t launch_cluster_extract(const float4* cloud, int n, bool any_finite, c
   hipLaunchKernelGGL(cluster_label_kernel, per_slot, block, 0, stream, component, rank_of, keys + n, cstart, n, labels, keys, vals, cstart64, counts);
   if ((e = launch_radix_sort_pairs(keys, vals, n, end_bit, scratch, stream)) != hipSuccess) return e;
   return hipGetLastError();
+}
+
+hipError_t launch_cluster_extract(const float4* cloud, int n, bool any_finite, const float4* sorted, const int* cell_start, const GridDesc& g,
+                                  int shells, float r2, int min_size, int max_size, int* parent, int* sizes, int* component, int* labels,
+                                  int* rank_of, int* csize, int* cstart, long long* cstart64, int* keys, int* vals, int* scratch, int* counts,
+                                  hipStream_t stream) {
+  if (n > 0) {
+    const dim3 per_point((n + CL_BLOCK - 1) / CL_BLOCK), block(CL_BLOCK);
+    hipLaunchKernelGGL(cluster_init_kernel, per_point, block, 0, stream, cloud, n, parent, sizes);
+    if (any_finite && r2 > 0.f)  // (r2 == 0: no d2 is below it)
+      hipLaunchKernelGGL(cluster_hook_kernel, dim3((n + CL_WAVES - 1) / CL_WAVES), block, 0, stream, cloud, n, sorted, cell_start, g, shells, r2, parent);
+    hipLaunchKernelGGL(cluster_flatten_kernel, per_point, block, 0, stream, parent, n, component, sizes);
+  }
+  return launch_cluster_tail(component, sizes, n, min_size, max_size, labels, rank_of, csize, cstart, cstart64, keys, vals, scratch, counts, stream);
 }
 
 }  // namespace icpgpu

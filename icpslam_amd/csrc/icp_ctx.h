@@ -15,6 +15,7 @@
 //   icpgpu_outlier.cpp  the statistical and radius outlier filters; a cloud's k-NN grid (build_knn_grid)
 //   icpgpu_search.cpp   the search cloud: k-nearest and radius search, normal estimation, FPFH, euclidean clustering, and the
 //                       steps every stage over that cloud shares (view_of, neighbour_rows, deliver)
+//   icpgpu_region.cpp   region growing over the search cloud
 //   icpgpu_boundary.cpp boundary estimation over the search cloud
 //   icpgpu_sac.cpp      plane segmentation (RANSAC) over the search cloud and ExtractIndices over its result
 //   icpgpu_pmf.cpp      the ground filter: morphological operators and the progressive morphological filter over the search cloud
@@ -447,6 +448,16 @@ struct icpgpu_ctx {
     size_t n = 0, n_clusters = 0, n_clustered = 0;
     DeviceBuf parent, sizes, component, labels, rank_of, csize, cstart, cstart64, keys, vals, scratch, counts;
   } cluster;
+  // region growing (icpgpu_region.cpp, icp_region.hip): the last call's result over the search cloud, the caller's normals and the
+  // scratch, in buffers no other call writes -- an unfetched result outlives later search, normal, clustering, segmentation, ground
+  // filter, sample-consensus, ISS and moving least squares calls; icpgpu_search_set_input drops it.  The k-nearest rows go through
+  // the search calls' scratch, as a normal estimation's do.
+  struct Region {
+    bool have = false;
+    size_t n = 0, n_regions = 0, n_in_regions = 0;
+    int waits = 0;
+    DeviceBuf normals, kind, border_key, anchor, parent, sizes, region, labels, rank_of, csize, cstart, cstart64, keys, vals, scratch, counts;
+  } region;
   // plane segmentation (icpgpu_sac.cpp, icp_sac.hip): the last call's result over the search cloud and its scratch, in buffers no other
   // call writes -- an unfetched result outlives later search, normal and clustering calls; icpgpu_search_set_input drops it
   struct Sac {

@@ -595,6 +595,22 @@ hipError_t launch_cluster_extract(const float4* cloud, int n, bool any_finite, c
                                   int shells, float r2, int min_size, int max_size, int* parent, int* sizes, int* component, int* labels,
                                   int* rank_of, int* csize, int* cstart, long long* cstart64, int* keys, int* vals, int* scratch, int* counts,
                                   hipStream_t stream);
+// ... its tail alone, for any partition stated the same way (region growing's): component[i] = the name of i's set (the set's lowest
+// member that names itself: component[name] == name) or -1, sizes[name] = the set's size.  Writes everything above but parent,
+// sizes and component.
+hipError_t launch_cluster_tail(const int* component, const int* sizes, int n, int min_size, int max_size, int* labels, int* rank_of, int* csize,
+                               int* cstart, long long* cstart64, int* keys, int* vals, int* scratch, int* counts, hipStream_t stream);
+
+// ---- region growing (icp_region.hip): pcl::RegionGrowing over the search cloud, the order-free rule of include/icpgpu.h ---------
+// normals: n float4 {nx, ny, nz, curvature}; rows_idx / rows_d2 / rows_found: the cloud's own k-nearest rows (launch_search_knn with
+// the cloud as queries, stride k), not read when any_finite is false.  kind (2 core, 1 border, 0 single, -1 none), anchor, region
+// (the region's name, -1: none): n ints; border_key: n 64-bit words; the rest as launch_cluster_extract's, whose tail orders the
+// regions.  The number of launches depends on n's bit length only.
+hipError_t launch_region_growing(const float4* cloud, const float4* normals, int n, bool any_finite, const int32_t* rows_idx, const float* rows_d2,
+                                 const int32_t* rows_found, int k, float smoothness_cos, float curvature_threshold, int min_size, int max_size,
+                                 int* kind, unsigned long long* border_key, int* anchor, int* parent, int* sizes, int* region, int* labels,
+                                 int* rank_of, int* csize, int* cstart, long long* cstart64, int* keys, int* vals, int* scratch, int* counts,
+                                 hipStream_t stream);
 
 // ---- ISS keypoints (icp_iss.hip): pcl::ISSKeypoint3D over the search cloud ------------------------------------------------------------
 // Per point of `cloud` (sorted, cell_start, g, shells_*: as launch_search_radius_count, one `shells` per radius; any_finite: the cloud

@@ -679,6 +679,10 @@ int icpgpu_destroy(icpgpu_ctx* c) {
   for (DeviceBuf* b : {&c->cluster.parent, &c->cluster.sizes, &c->cluster.component, &c->cluster.labels, &c->cluster.rank_of, &c->cluster.csize,
                        &c->cluster.cstart, &c->cluster.cstart64, &c->cluster.keys, &c->cluster.vals, &c->cluster.scratch, &c->cluster.counts})
     release(*b);
+  for (DeviceBuf* b : {&c->region.normals, &c->region.kind, &c->region.border_key, &c->region.anchor, &c->region.parent, &c->region.sizes,
+                       &c->region.region, &c->region.labels, &c->region.rank_of, &c->region.csize, &c->region.cstart, &c->region.cstart64,
+                       &c->region.keys, &c->region.vals, &c->region.scratch, &c->region.counts})
+    release(*b);
   for (DeviceBuf* b : {&c->sac.batch, &c->sac.ints, &c->sac.sums}) release(*b);
   for (DeviceBuf* b : {&c->rsac.P, &c->rsac.Q, &c->rsac.rank, &c->rsac.source, &c->rsac.target, &c->rsac.iq, &c->rsac.im, &c->rsac.models,
                        &c->rsac.batch, &c->rsac.sums, &c->rsac.ints})

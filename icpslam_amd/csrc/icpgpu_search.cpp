@@ -189,7 +189,7 @@ int deliver(icpgpu_ctx* c, const Delivery* parts, int n_parts) {
 extern "C" {
 
 // Copies the cloud and builds its k-NN grid.  Nothing of the context's source, target, their grids, the covariances, the NDT cells
-// or the filters' results is touched; the previous search cloud, and a clustering,
+// or the filters' results is touched; the previous search cloud, and a clustering, region growing,
 // plane segmentation, ground filter, sample-consensus alignment, ISS or moving least squares result over it, is gone whatever this call returns.
 int icpgpu_search_set_input(icpgpu_ctx* c, const float* xyzw, size_t n) {
   ENTER(c);
@@ -199,6 +199,7 @@ int icpgpu_search_set_input(icpgpu_ctx* c, const float* xyzw, size_t n) {
   S.n_finite = 0;
   S.grid.built = S.grid.usable = false;  // (version 0: a build never stands for the next cloud)
   c->cluster.have = false;               // (a clustering result is a result over the cloud that goes)
+  c->region.have = false;                // (and so is a region growing result)
   c->sac.have = false;                   // (and so is a plane segmentation)
   c->pmf.have = c->pmf.ran = false;      // (and a ground filter's)
   c->scp.have = false;                   // (and a sample-consensus alignment)

@@ -813,6 +813,42 @@ class Context:
         self._check(rc)
         return start, indices, labels, component
 
+    # region growing (pcl::RegionGrowing by the order-free rule of include/icpgpu.h, "region growing") ----------------------------
+    def region_growing_raw(self, normals, k: int, smoothness_cos: float, curvature_threshold: float, min_size: int, max_size: int) -> tuple:
+        """One icpgpu_region_growing call: (rc, n_regions, n_in_regions); the result stays in the context.  normals: (n, 4) float32
+        {nx, ny, nz, curvature} or None (a null pointer)."""
+        nr, ni = C.c_size_t(), C.c_size_t()
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 4)
+        rc = self._L.icpgpu_region_growing(self._h, None if nrm is None else _fp(nrm), int(k), float(smoothness_cos), float(curvature_threshold),
+                                           int(min_size), int(max_size), C.byref(nr), C.byref(ni))
+        return rc, int(nr.value), int(ni.value)
+
+    def region_fetch_raw(self, capacity_regions: int, capacity_indices: int, want=("labels", "region", "kind", "anchor")) -> tuple:
+        """One icpgpu_region_fetch call into arrays pre-filled with -2: (rc, region_start, indices, labels, region, kind, anchor); the
+        per-point arrays not named in `want` are passed as NULL and come back as None."""
+        n_c = C.c_size_t()
+        self._L.icpgpu_search_size(self._h, C.byref(n_c), None)  # (0 without a search cloud)
+        n = int(n_c.value)
+        start = np.full(capacity_regions + 1, -2, np.int64)
+        indices = np.full(capacity_indices, -2, np.int32)
+        per_point = [np.full(n, -2, np.int32) if name in want else None for name in ("labels", "region", "kind", "anchor")]
+        ip = C.POINTER(C.c_int32)
+        rc = self._L.icpgpu_region_fetch(self._h, int(capacity_regions), int(capacity_indices), start.ctypes.data_as(C.POINTER(C.c_int64)),
+                                         indices.ctypes.data_as(ip), *[None if a is None else a.ctypes.data_as(ip) for a in per_point])
+        return (rc, start, indices, *per_point)
+
+    def region_growing(self, normals, k: int = 30, smoothness: float = math.radians(30.0), curvature_threshold: float = 0.05,
+                       min_size: int = 1, max_size: int = 2**31 - 1, smoothness_cos=None) -> tuple:
+        """(region_start (n_regions + 1,) int64, indices (n_in_regions,) int32, labels, region, kind, anchor (n,) int32 each): the
+        search cloud's smooth regions of min_size .. max_size points by size descending (the lowest name first among equal sizes),
+        indices ascending inside a region.  smoothness: PCL's theta in radians; smoothness_cos, when given, is used as it is."""
+        cos = np.float32(math.cos(float(smoothness))) if smoothness_cos is None else smoothness_cos
+        rc, n_regions, n_in = self.region_growing_raw(normals, k, cos, curvature_threshold, min_size, max_size)
+        self._check(rc)
+        rc, *arrays = self.region_fetch_raw(n_regions, n_in)
+        self._check(rc)
+        return tuple(arrays)
+
     # ISS keypoints (pcl::ISSKeypoint3D; the _border calls with border estimation; rules: include/icpgpu.h) -------------------------
     def iss_keypoints_raw(self, salient_radius: float, non_max_radius: float, gamma_21: float = 0.975, gamma_32: float = 0.975,
                           min_neighbors: int = 5) -> tuple:
@@ -1786,6 +1822,109 @@ class EuclideanClusterExtraction:
         self._ctx.search_set_input(self._input)
         start, indices, self._labels, _ = self._ctx.euclidean_cluster_extraction(self._tolerance, self._min, self._max)
         return [indices[start[r]:start[r + 1]].copy() for r in range(start.size - 1)]
+
+
+class RegionGrowing:
+    """pcl::RegionGrowing<PointXYZ, Normal>-shaped front end (include/icpgpu.h, "region growing": an order-free rule, not PCL's seed
+    queue): setInputCloud, setInputNormals (as NormalEstimation.compute() returns them), setNumberOfNeighbours, setSmoothnessThreshold
+    (radians), setCurvatureThreshold, setCurvatureTestFlag, setMinClusterSize, setMaxClusterSize, extract() -> a list of int32 index
+    arrays, the largest region first, ascending inside a region; getSegmentFromPoint(index).  The defaults are PCL's constructor's
+    (30 neighbours, 30 degrees, 0.05, sizes 1 .. INT_MAX).  setIndices, setSmoothModeFlag(False) and setResidualTestFlag(True) raise."""
+
+    def __init__(self, device_id: int = 0):
+        self._ctx = Context(device_id)
+        self._input = None
+        self._normals = None
+        self._k = 30
+        self._theta = 30.0 / 180.0 * math.pi
+        self._curvature = 0.05
+        self._curvature_test = True
+        self._min = 1
+        self._max = 2**31 - 1
+        self._result = None
+
+    def setInputCloud(self, cloud):
+        self._input = _as_cloud(cloud).copy()
+        self._result = None
+
+    def setInputNormals(self, normals):
+        self._normals = _as_cloud(normals).copy()
+        self._result = None
+
+    def setSearchMethod(self, tree=None):
+        """Accepted and ignored: the search is the library's own (exact, ascending by (d2, index))."""
+
+    def setIndices(self, indices):
+        raise IcpGpuError(_lib.ERR_UNSUPPORTED, "RegionGrowing.setIndices is not provided")
+
+    def setSmoothModeFlag(self, value: bool):
+        if not value:
+            raise IcpGpuError(_lib.ERR_UNSUPPORTED, "RegionGrowing.setSmoothModeFlag(False) is not provided")
+
+    def setResidualTestFlag(self, value: bool):
+        if value:
+            raise IcpGpuError(_lib.ERR_UNSUPPORTED, "RegionGrowing.setResidualTestFlag(True) is not provided")
+
+    def setNumberOfNeighbours(self, k: int):
+        self._k = int(k)
+
+    def getNumberOfNeighbours(self) -> int:
+        return self._k
+
+    def setSmoothnessThreshold(self, theta: float):
+        self._theta = float(theta)
+
+    def getSmoothnessThreshold(self) -> float:
+        return self._theta
+
+    def setCurvatureThreshold(self, curvature: float):
+        self._curvature = float(curvature)
+
+    def getCurvatureThreshold(self) -> float:
+        return self._curvature
+
+    def setCurvatureTestFlag(self, value: bool):
+        self._curvature_test = bool(value)
+
+    def getCurvatureTestFlag(self) -> bool:
+        return self._curvature_test
+
+    def setMinClusterSize(self, min_cluster_size: int):
+        self._min = int(min_cluster_size)
+
+    def getMinClusterSize(self) -> int:
+        return self._min
+
+    def setMaxClusterSize(self, max_cluster_size: int):
+        self._max = int(max_cluster_size)
+
+    def getMaxClusterSize(self) -> int:
+        return self._max
+
+    def getLabels(self) -> np.ndarray:
+        """The last extract()'s region rank of every input point, -1 where it is in none (not PCL's)."""
+        return np.empty(0, np.int32) if self._result is None else self._result[2]
+
+    def extract(self) -> list:
+        if self._input is None or self._normals is None:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "extract: setInputCloud and setInputNormals first")
+        if len(self._normals) != len(self._input):
+            raise IcpGpuError(_lib.ERR_INVALID_ARG, f"extract: {len(self._normals)} normals for {len(self._input)} points")
+        self._ctx.search_set_input(self._input)
+        threshold = self._curvature if self._curvature_test else math.inf
+        self._result = self._ctx.region_growing(self._normals, self._k, self._theta, threshold, self._min, self._max)
+        start, indices = self._result[:2]
+        return [indices[start[r]:start[r + 1]].copy() for r in range(start.size - 1)]
+
+    def getSegmentFromPoint(self, index: int) -> np.ndarray:
+        """The emitted region the point lies in (extract() runs first if it has not), empty when it is in none."""
+        if self._result is None:
+            self.extract()
+        start, indices, labels = self._result[:3]
+        if not 0 <= int(index) < labels.size:
+            raise IcpGpuError(_lib.ERR_INVALID_ARG, f"getSegmentFromPoint: index {index} outside the cloud")
+        r = int(labels[int(index)])
+        return np.empty(0, np.int32) if r < 0 else indices[start[r]:start[r + 1]].copy()
 
 
 class ISSKeypoint3D:

@@ -56,7 +56,7 @@ extern "C" {
  * icpgpu_get_reciprocal_correspondences, icpgpu_reciprocal_stats, and the outlier filters -- icpgpu_statistical_outlier_removal,
  * icpgpu_radius_outlier_removal, their _view forms, icpgpu_outlier_stats, icpgpu_outlier_fetch, and the neighbour search --
  * icpgpu_search_set_input, icpgpu_search_size, icpgpu_search_knn, icpgpu_search_radius, and normal estimation --
- * icpgpu_normal_estimation, and euclidean clustering -- icpgpu_euclidean_cluster_extraction, icpgpu_cluster_fetch, and plane segmentation --
+ * icpgpu_normal_estimation, and euclidean clustering -- icpgpu_euclidean_cluster_extraction, icpgpu_cluster_fetch, and region growing -- icpgpu_region_growing, icpgpu_region_fetch, and plane segmentation --
  * icpgpu_sac_plane_segmentation, icpgpu_sac_fetch, icpgpu_sac_stats, icpgpu_sac_extract, icpgpu_sac_extract_view, and the ground filter -- icpgpu_morphological_operator,
  * icpgpu_progressive_morphological_filter, icpgpu_pmf_fetch, icpgpu_pmf_stats, icpgpu_pmf_extract, icpgpu_pmf_extract_view, and ISS keypoints --
  * icpgpu_iss_keypoints, icpgpu_iss_fetch, icpgpu_iss_stats, icpgpu_iss_keypoints_border, icpgpu_iss_fetch_border, and boundary
@@ -1037,6 +1037,64 @@ int icpgpu_euclidean_cluster_extraction(icpgpu_ctx* ctx, double tolerance, int m
                                         size_t* n_clustered);
 int icpgpu_cluster_fetch(icpgpu_ctx* ctx, size_t capacity_clusters, size_t capacity_indices, int64_t* cluster_start /* n_clusters + 1 */,
                          int32_t* indices /* n_clustered */, int32_t* labels /* n, may be NULL */, int32_t* component /* n, may be NULL */);
+
+/* ---- region growing (added under 1.2) ------------------------------------------------------------------------------- */
+/* replaces pcl::RegionGrowing<PointXYZ, Normal>: setInputCloud, setInputNormals, setNumberOfNeighbours, setSmoothnessThreshold,
+ * setCurvatureThreshold, setCurvatureTestFlag, setMinClusterSize, setMaxClusterSize, extract -- "which points of this cloud lie on one
+ * smooth surface".  The call works on the context's SEARCH CLOUD (icpgpu_search_set_input), as clustering does.  PCL's algorithm is a
+ * sequential seed queue whose regions depend on the order the points are visited in; this section defines an ORDER-FREE RULE instead,
+ * stated as a deviation as the cluster order rules are.  tests/region_restated.py is what the kernels are compared with, bit for bit
+ * -- the answer is a partition of integers and there is no tolerance anywhere; its pcl_literal transcribes PCL 1.8's loop, and
+ * DESIGN.md section 3 has how far the two are apart on scans.
+ * INPUTS.  normals_nxyzc: n float4 {nx, ny, nz, curvature}, one per search-cloud point, required -- what icpgpu_normal_estimation
+ * writes.  k in 1 .. ICPGPU_SEARCH_MAX_K: PCL's setNumberOfNeighbours (default 30).  smoothness_cos: the COSINE of PCL's theta; the
+ * call takes the cosine itself so that no kernel calls a libm cosine -- the shims compute (float)cos((double)theta).
+ * curvature_threshold, min_size, max_size: PCL's.
+ * PARTICIPANT.  A finite point whose four normal floats are finite.  Every other point is in no region: kind = -1, region = -1,
+ * label = -1, and it cannot bridge two regions.
+ * ROW.  row(i) is exactly the row icpgpu_search_knn(k) returns for point i as a query: i itself (or a lower-indexed duplicate of it)
+ * first, equal distances in index order.
+ * SMOOTH.  smooth(i, j): dot = (nx_i * nx_j + ny_i * ny_j) + nz_i * nz_j in float32, every product and sum rounded on its own -- exactly
+ * symmetric in i and j; smooth = fabsf(dot) >= smoothness_cos.  (PCL rejects dot < threshold.)  Antiparallel normals join, as in PCL.
+ * CORE.  A participant with !(curvature > curvature_threshold): PCL's test for "may continue as a seed".  A threshold of +inf makes
+ * every participant core, which is setCurvatureTestFlag(false).
+ * CORE GRAPH.  Cores i != j are joined iff smooth(i, j) and (j is in row(i) or i is in row(j)).  A region's cores are a connected
+ * component of this graph, and the region's name is its lowest core index.
+ * BORDER.  A participant j that is not core attaches through a core i only when j is in row(i) and smooth(i, j) holds.  Among those
+ * cores it takes the one with the smallest key ((uint64)bits(d2) << 32) | i, where d2 is row(i)'s own d2 for j, and joins that core's
+ * region: kind = 1, anchor[j] = i.
+ * SINGLE.  A non-core participant that no core claims is a region of its own, named by its own index: kind = 0.
+ * EMISSION AND ORDER.  Exactly the clustering section's rules: a region is emitted iff min_size <= size <= max_size; size descending,
+ * the lowest name first among equals, ascending indices inside a region; labels[i] = the rank of i's region or -1.  Any ints are
+ * accepted; max_size < min_size emits nothing.
+ * DEVIATIONS from PCL 1.8.  (1) The neighbour relation is symmetrised for cores; PCL follows row(i) only, from whichever seed it
+ * visits first.  (2) A border point goes to its nearest listing core, not to the first region that reaches it.  (3) Unclaimed
+ * non-core points stay single; in PCL such a point seeds a region and collects its unlabelled smooth neighbours once.  (4) Regions
+ * come out in size order; PCL uses seed order.  (5) Non-finite points and normals are defined, not asserted.
+ * A RELATION THAT HOLDS EXACTLY.  PCL's propagation edges between cores are a subset of the core graph's edges, so all core points of
+ * any region PCL's literal loop grows from a core initial seed lie in ONE region of this rule (tests/test_region_host.py).
+ * CALLS.  icpgpu_region_growing computes and KEEPS the result in buffers of its own in the context, and returns the number of regions
+ * and of points in them after ONE host wait (the k-nearest rows are queued without one); icpgpu_region_fetch copies it out, any
+ * number of times.  region_start / indices are CSR as icpgpu_cluster_fetch's; labels, region (the name of the point's region, emitted
+ * or not, -1: none), kind (2 core, 1 border, 0 single, -1 none) and anchor (the claiming core of a border point, else -1) hold n
+ * entries each and may be NULL.
+ * ICPGPU_ERR_INVALID_ARG: no search cloud; null normals with n > 0; k outside its range; a NaN smoothness_cos or curvature_threshold;
+ * a null count pointer; a fetch without a result (none computed, the last call refused, or the search cloud replaced since); a fetch
+ * with capacity_regions < n_regions or capacity_indices < n_in_regions, or null region_start, or null indices with n_in_regions > 0
+ * -- nothing is written then.  An empty cloud, or a cloud with no participant, is ICPGPU_OK with zero regions.
+ * LIMITS.  A cloud the grid refuses is handled as in clustering: its rows come from the search's whole-cloud kernel.
+ * Not provided: setIndices, setSmoothModeFlag(false), setResidualTestFlag(true) -- the shims throw or raise on these.
+ * ISOLATION.  The result depends on the search cloud and the arguments alone.  The call leaves the source, the
+ * target, every grid, the covariances, the cached normals, the NDT cells, the filters' results and the search cloud itself as they
+ * were.  Later icpgpu_search_*, normal estimation, clustering, plane segmentation, ground filter, ISS and moving least squares calls
+ * do not disturb a result that has not been fetched yet, nor it theirs: the rows go through the search calls' scratch, everything
+ * it keeps -- its copy of the normals included -- lives in buffers of its own.  icpgpu_search_set_input drops it, whatever it
+ * returns. */
+int icpgpu_region_growing(icpgpu_ctx* ctx, const float* normals_nxyzc /* n float4 */, int k, float smoothness_cos, float curvature_threshold,
+                          int min_size, int max_size, size_t* n_regions, size_t* n_in_regions);
+int icpgpu_region_fetch(icpgpu_ctx* ctx, size_t capacity_regions, size_t capacity_indices, int64_t* region_start /* n_regions + 1 */,
+                        int32_t* indices /* n_in_regions */, int32_t* labels /* n, may be NULL */, int32_t* region /* n, may be NULL */,
+                        int32_t* kind /* n, may be NULL: 2 core, 1 border, 0 single, -1 none */, int32_t* anchor /* n, may be NULL */);
 
 /* ---- plane segmentation (added under 1.2) --------------------------------------------------------------------------- */
 /* replaces pcl::SACSegmentation<PointXYZ> with SACMODEL_PLANE or SACMODEL_PERPENDICULAR_PLANE and SAC_RANSAC -- setInputCloud,

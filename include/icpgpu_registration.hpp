@@ -25,6 +25,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -1164,6 +1165,110 @@ class EuclideanClusterExtraction {
   double tolerance_ = 0.0;
   int min_ = 1, max_ = 0x7FFFFFFF;
   std::vector<int> labels_;
+};
+
+// pcl::RegionGrowing<PointT, NormalT>-shaped front end (rules and deviations: include/icpgpu.h, "region growing" -- an ORDER-FREE
+// rule, not PCL's seed queue: regions agree with PCL's on smooth surfaces and differ where PCL's depend on its visiting order):
+//   pcl::RegionGrowing<pcl::PointXYZ, pcl::Normal> reg;
+//     ->  icpgpu::RegionGrowing<pcl::PointCloud<pcl::PointXYZ>, pcl::PointCloud<pcl::Normal>> reg;
+//   reg.setMinClusterSize(50); reg.setMaxClusterSize(1000000); reg.setSearchMethod(tree); reg.setNumberOfNeighbours(30);
+//   reg.setInputCloud(cloud); reg.setInputNormals(normals); reg.setSmoothnessThreshold(3.0 / 180.0 * M_PI);
+//   reg.setCurvatureThreshold(1.0); std::vector<icpgpu::PointIndices> clusters; reg.extract(clusters);
+// The normals are one per input point (any point type with normal_x, normal_y, normal_z and curvature: icpgpu::NormalEstimation's
+// output cloud as it is).  The regions come out by size descending (the lowest name first among equal sizes), the indices ascending
+// inside each; the defaults are PCL's constructor's (30 neighbours, 30 degrees, curvature 0.05, sizes 1 .. INT_MAX, smooth mode and
+// the curvature test on, the residual test off).  A refused call (no normals, normals that do not match the cloud, ...) leaves
+// `clusters` empty.  setIndices is not provided; setSmoothModeFlag(false) and setResidualTestFlag(true) throw.
+template <class CloudT, class NormalCloudT>
+class RegionGrowing {
+ public:
+  explicit RegionGrowing(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {}
+  template <class CloudPtr>
+  void setInputCloud(const CloudPtr& cloud) { input_ = &*cloud, have_ = false; }
+  template <class NormalsPtr>
+  void setInputNormals(const NormalsPtr& normals) { normals_ = &*normals, have_ = false; }
+  template <class TreePtr>
+  void setSearchMethod(const TreePtr&) {}  // accepted and ignored: the search is the library's own (exact)
+  void setNumberOfNeighbours(unsigned int neighbour_number) { k_ = (int)neighbour_number; }
+  unsigned int getNumberOfNeighbours() const { return (unsigned int)k_; }
+  void setSmoothnessThreshold(float theta) { theta_ = theta; }  // radians
+  float getSmoothnessThreshold() const { return theta_; }
+  void setCurvatureThreshold(float curvature) { curvature_ = curvature; }
+  float getCurvatureThreshold() const { return curvature_; }
+  void setCurvatureTestFlag(bool value) { curvature_test_ = value; }
+  bool getCurvatureTestFlag() const { return curvature_test_; }
+  void setSmoothModeFlag(bool value) {
+    if (!value) throw std::invalid_argument("icpgpu::RegionGrowing: setSmoothModeFlag(false) is not provided");
+  }
+  bool getSmoothModeFlag() const { return true; }
+  void setResidualTestFlag(bool value) {
+    if (value) throw std::invalid_argument("icpgpu::RegionGrowing: setResidualTestFlag(true) is not provided");
+  }
+  bool getResidualTestFlag() const { return false; }
+  void setMinClusterSize(int min_cluster_size) { min_ = min_cluster_size; }
+  int getMinClusterSize() const { return min_; }
+  void setMaxClusterSize(int max_cluster_size) { max_ = max_cluster_size; }
+  int getMaxClusterSize() const { return max_; }
+  void extract(std::vector<PointIndices>& clusters) {
+    clusters.clear();
+    clusters_.clear();
+    labels_.clear();
+    have_ = false;
+    if (!input_ || !normals_) return;
+    static_assert(sizeof(input_->points[0]) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+    static_assert(sizeof(int) == sizeof(int32_t) && sizeof(long long) == sizeof(int64_t), "icpgpu: 32-bit int, 64-bit long long");
+    const std::size_t n = input_->points.size();
+    if (normals_->points.size() != n) return;
+    std::vector<float> nxyzc(4 * n);
+    for (std::size_t i = 0; i < n; ++i) {
+      nxyzc[4 * i] = normals_->points[i].normal_x;
+      nxyzc[4 * i + 1] = normals_->points[i].normal_y;
+      nxyzc[4 * i + 2] = normals_->points[i].normal_z;
+      nxyzc[4 * i + 3] = normals_->points[i].curvature;
+    }
+    if (icpgpu_search_set_input(ctx_, n ? reinterpret_cast<const float*>(&input_->points[0]) : nullptr, n) != ICPGPU_OK) return;
+    const float smoothness_cos = (float)std::cos((double)theta_);
+    const float threshold = curvature_test_ ? curvature_ : std::numeric_limits<float>::infinity();
+    std::size_t n_regions = 0, n_in = 0;
+    if (icpgpu_region_growing(ctx_, n ? &nxyzc[0] : nullptr, k_, smoothness_cos, threshold, min_, max_, &n_regions, &n_in) != ICPGPU_OK) return;
+    std::vector<long long> start(n_regions + 1, 0);
+    std::vector<int> indices(n_in);
+    labels_.assign(n, -1);
+    if (icpgpu_region_fetch(ctx_, n_regions, n_in, reinterpret_cast<int64_t*>(&start[0]), n_in ? reinterpret_cast<int32_t*>(&indices[0]) : nullptr,
+                            n ? reinterpret_cast<int32_t*>(&labels_[0]) : nullptr, nullptr, nullptr, nullptr) != ICPGPU_OK) {
+      labels_.clear();
+      return;
+    }
+    clusters_.resize(n_regions);
+    for (std::size_t r = 0; r < n_regions; ++r) clusters_[r].indices.assign(indices.begin() + start[r], indices.begin() + start[r + 1]);
+    clusters = clusters_;
+    have_ = true;
+  }
+  // the emitted region the point lies in (extract() runs first if it has not), empty when it lies in none or the index is outside
+  void getSegmentFromPoint(int index, PointIndices& cluster) {
+    cluster.indices.clear();
+    if (!have_) {
+      std::vector<PointIndices> clusters;
+      extract(clusters);
+    }
+    if (!have_ || index < 0 || (std::size_t)index >= labels_.size() || labels_[index] < 0) return;
+    cluster = clusters_[labels_[index]];
+  }
+  // NOT a PCL method: the last extract()'s region rank of every input point, -1 where it is in none (empty after a refused call)
+  const std::vector<int>& getLabels() const { return labels_; }
+
+ private:
+  detail::ContextPtr ctx_holder_;
+  icpgpu_ctx* ctx_;
+  const CloudT* input_ = nullptr;
+  const NormalCloudT* normals_ = nullptr;
+  int k_ = 30;
+  float theta_ = 30.0f / 180.0f * 3.14159265358979323846f;  // PCL's default
+  float curvature_ = 0.05f;
+  bool curvature_test_ = true, have_ = false;
+  int min_ = 1, max_ = 0x7FFFFFFF;
+  std::vector<int> labels_;
+  std::vector<PointIndices> clusters_;
 };
 
 // pcl::ISSKeypoint3D<PointT, PointT>-shaped front end (rules and deviations: include/icpgpu.h, "ISS keypoints") -- the keypoints at
