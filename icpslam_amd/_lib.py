@@ -39,6 +39,9 @@ SACMODEL_PLANE, SACMODEL_PERPENDICULAR_PLANE = 0, 15   # pcl::SacModel's values
 SAC_RANSAC = 0                 # pcl's method_types.h
 MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3   # icpgpu_morph_op
 PMF_MAX_PASSES = 32            # ICPGPU_PMF_MAX_PASSES
+SEGMENTS_HOST, SEGMENTS_CLUSTERS, SEGMENTS_REGIONS = 0, 1, 2   # ICPGPU_SEGMENTS_*
+SEGMENT_OK, SEGMENT_EMPTY = 0, 1                               # ICPGPU_SEGMENT_*
+SEGMENT_CHUNK = 64             # ICPGPU_SEGMENT_CHUNK
 STATE_NAMES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE",
                5: "NO_CORRESPONDENCES"}
 
@@ -81,6 +84,13 @@ class Rejector(C.Structure):
     _fields_ = [("kind", C.c_int32), ("min_correspondences", C.c_int32), ("value", C.c_double)]
 
 
+class SegmentRecord(C.Structure):
+    _fields_ = [("count", C.c_int64), ("status", C.c_int32), ("first", C.c_int32), ("K", C.c_double * 3), ("moments", C.c_double * 9),
+                ("centroid", C.c_double * 3), ("cov", C.c_double * 6), ("eigenvalues", C.c_double * 3), ("axes", C.c_double * 9),
+                ("aabb_min", C.c_float * 3), ("aabb_max", C.c_float * 3), ("obb_lo", C.c_double * 3), ("obb_hi", C.c_double * 3),
+                ("obb_position", C.c_double * 3), ("obb_dims", C.c_double * 3)]
+
+
 class Pose(C.Structure):
     _fields_ = [("pos", C.c_double * 3), ("quat", C.c_double * 4)]
 
@@ -117,6 +127,7 @@ EXPORTS = [
     "icpgpu_feature_knn",
     "icpgpu_euclidean_cluster_extraction", "icpgpu_cluster_fetch",
     "icpgpu_region_growing", "icpgpu_region_fetch",
+    "icpgpu_segment_moments", "icpgpu_segment_stats",
     "icpgpu_scp_align", "icpgpu_scp_fetch", "icpgpu_scp_stats",
     "icpgpu_iss_keypoints", "icpgpu_iss_fetch", "icpgpu_iss_stats",
     "icpgpu_boundary_estimation", "icpgpu_iss_keypoints_border", "icpgpu_iss_fetch_border",
@@ -248,6 +259,8 @@ def load():
     L.icpgpu_sac_plane_segmentation.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_uint64, C.c_int, dp, C.c_double, fp, szp, ip, ip]
     L.icpgpu_sac_fetch.argtypes = [vp, C.c_size_t, C.c_size_t, ip, ip, ip, ip, fp, dp, szp]
     L.icpgpu_sac_stats.argtypes = [vp, ip]
+    L.icpgpu_segment_moments.argtypes = [vp, C.c_int, C.c_size_t, C.POINTER(C.c_int64), ip, C.c_size_t, C.c_void_p]
+    L.icpgpu_segment_stats.argtypes = [vp, ip]
     L.icpgpu_iss_keypoints.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, szp]
     L.icpgpu_iss_fetch.argtypes = [vp, C.c_size_t, ip, fp, ip, dp, dp, dp]
     L.icpgpu_iss_stats.argtypes = [vp, ip]

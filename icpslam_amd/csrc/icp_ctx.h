@@ -458,6 +458,12 @@ struct icpgpu_ctx {
     int waits = 0;
     DeviceBuf normals, kind, border_key, anchor, parent, sizes, region, labels, rank_of, csize, cstart, cstart64, keys, vals, scratch, counts;
   } region;
+  // segment moments (icpgpu_segment.cpp, icp_segment.hip): the scratch of a call -- a HOST source's CSR, the entries' segments, the pieces' partials, the
+  // records on their way out.  The call keeps nothing; no other call reads or writes these buffers.
+  struct Segment {
+    int waits = 0;
+    DeviceBuf start, list, seg_of, first, partials, box_partials, records;
+  } segment;
   // plane segmentation (icpgpu_sac.cpp, icp_sac.hip): the last call's result over the search cloud and its scratch, in buffers no other
   // call writes -- an unfetched result outlives later search, normal and clustering calls; icpgpu_search_set_input drops it
   struct Sac {

@@ -612,6 +612,30 @@ hipError_t launch_region_growing(const float4* cloud, const float4* normals, int
                                  int* rank_of, int* csize, int* cstart, long long* cstart64, int* keys, int* vals, int* scratch, int* counts,
                                  hipStream_t stream);
 
+// ---- segment moments (icp_segment.hip): per-segment sums, boxes and axes over CSR segments of the search cloud -----------------
+// The list -- all segments' entries, one after the other, `total` of them -- is cut into chunks of kSegmentChunk entries; a wave
+// takes a chunk, a lane an entry, and every segment that has entries in the chunk has one PIECE there.  Piece (segment s, chunk g) owns slot g + s of the two
+// partial arrays (segment_partials(n_segments, total) of each): no two pieces share a slot, since a later segment lies in a later or
+// the same chunk.  start: n_segments + 1 ints, non-decreasing from 0 to total; list: total cloud indices (clamped to the cloud).
+static constexpr int kSegmentChunk = 64;  // = ICPGPU_SEGMENT_CHUNK: a wave
+struct SegmentPartial {  // a piece's nine double-double sums about K, its finite entries and their float32 box as ordered keys
+  double hi[9], lo[9];
+  unsigned int box_min[3], box_max[3];
+  int count, pad;
+};
+struct SegmentBoxPartial {  // a piece's extents along the segment's axes as ordered 64-bit keys
+  unsigned long long lo[3], hi[3];
+};
+inline size_t segment_chunks(size_t total) { return (total + kSegmentChunk - 1) / kSegmentChunk; }
+inline size_t segment_slots(size_t n_segments, size_t total) { return segment_chunks(total) + n_segments; }
+// ... and behind the slots one folded partial per segment: what the two partial arrays hold
+inline size_t segment_partials(size_t n_segments, size_t total) { return segment_slots(n_segments, total) + n_segments; }
+// seg_of (total ints): every entry's segment.  first (n_segments words): the list position of each segment's first finite entry, all
+// ones where it has none.  records: n_segments icpgpu_segment_record (void*: this header does not know the public one).  Seven
+// launches and a memset, whatever the rows' lengths.
+hipError_t launch_segment_moments(const float4* cloud, int n, const int* start, const int* list, int n_segments, int total, int* seg_of,
+                                  unsigned int* first, SegmentPartial* partials, SegmentBoxPartial* box_partials, void* records, hipStream_t stream);
+
 // ---- ISS keypoints (icp_iss.hip): pcl::ISSKeypoint3D over the search cloud ------------------------------------------------------------
 // Per point of `cloud` (sorted, cell_start, g, shells_*: as launch_search_radius_count, one `shells` per radius; any_finite: the cloud
 // has a finite point): n_salient (n), scatter6 (n x 6), eig3 (n x 3, descending) and saliency (n) from the salient ball, then the

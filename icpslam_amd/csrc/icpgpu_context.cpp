@@ -683,6 +683,8 @@ int icpgpu_destroy(icpgpu_ctx* c) {
                        &c->region.region, &c->region.labels, &c->region.rank_of, &c->region.csize, &c->region.cstart, &c->region.cstart64,
                        &c->region.keys, &c->region.vals, &c->region.scratch, &c->region.counts})
     release(*b);
+  for (DeviceBuf* b : {&c->segment.start, &c->segment.list, &c->segment.seg_of, &c->segment.first, &c->segment.partials, &c->segment.box_partials, &c->segment.records})
+    release(*b);
   for (DeviceBuf* b : {&c->sac.batch, &c->sac.ints, &c->sac.sums}) release(*b);
   for (DeviceBuf* b : {&c->rsac.P, &c->rsac.Q, &c->rsac.rank, &c->rsac.source, &c->rsac.target, &c->rsac.iq, &c->rsac.im, &c->rsac.models,
                        &c->rsac.batch, &c->rsac.sums, &c->rsac.ints})

@@ -25,6 +25,7 @@ from ._lib import IcpGpuError, Params, Profile, Rejector, Result
 
 
 FPFH_BINS = 33  # ICPGPU_FPFH_BINS: pcl::FPFHSignature33
+SEGMENT_RECORD = np.dtype(_lib.SegmentRecord)  # icpgpu_segment_record as a NumPy structured dtype
 
 
 def _as_cloud(a) -> np.ndarray:
@@ -848,6 +849,49 @@ class Context:
         rc, *arrays = self.region_fetch_raw(n_regions, n_in)
         self._check(rc)
         return tuple(arrays)
+
+    # segment moments (pcl::MomentOfInertiaEstimation for every segment at once; rules: include/icpgpu.h, "segment moments") --------
+    def segment_moments_raw(self, source: int, n_segments: int, segment_start=None, indices=None, sizeof_record=None, null_out: bool = False) -> tuple:
+        """One icpgpu_segment_moments call into n_segments records pre-filled with the byte 0xAB: (rc, records).  segment_start /
+        indices: int64 / int32 arrays or None (null pointers); sizeof_record: the record's size unless given; null_out: out = NULL."""
+        records = np.frombuffer(bytearray(b"\xab" * (int(n_segments) * SEGMENT_RECORD.itemsize)), SEGMENT_RECORD)
+        start = None if segment_start is None else np.ascontiguousarray(segment_start, np.int64)
+        idx = None if indices is None else np.ascontiguousarray(indices, np.int32)
+        rc = self._L.icpgpu_segment_moments(self._h, int(source), int(n_segments),
+                                            None if start is None else start.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            SEGMENT_RECORD.itemsize if sizeof_record is None else int(sizeof_record),
+                                            None if null_out or records.size == 0 else records.ctypes.data)
+        return rc, records
+
+    def segment_moments(self, segment_start=None, indices=None, source: str = "host", n_segments=None) -> np.ndarray:
+        """One record per segment of the search cloud (a NumPy structured array of SEGMENT_RECORD: count, status, first, K, moments,
+        centroid, cov, eigenvalues, axes, aabb_min, aabb_max, obb_lo, obb_hi, obb_position, obb_dims).  source "host": the CSR
+        segment_start (n_segments + 1) / indices; "clusters" / "regions": the last euclidean_cluster_extraction / region_growing
+        result over this search cloud, read where it lies on the device (n_segments: its count, checked by the library)."""
+        if source == "host":
+            if segment_start is None:
+                raise IcpGpuError(_lib.ERR_INVALID_ARG, "segment_moments: a host source needs segment_start")
+            n_seg = len(segment_start) - 1
+            code = _lib.SEGMENTS_HOST
+        elif source in ("clusters", "regions"):
+            if segment_start is not None or indices is not None:
+                raise IcpGpuError(_lib.ERR_INVALID_ARG, f"segment_moments: source {source!r} takes no segment_start or indices")
+            if n_segments is None:
+                raise IcpGpuError(_lib.ERR_INVALID_ARG, f"segment_moments: source {source!r} needs n_segments, the result's count")
+            n_seg = int(n_segments)
+            code = _lib.SEGMENTS_CLUSTERS if source == "clusters" else _lib.SEGMENTS_REGIONS
+        else:
+            raise IcpGpuError(_lib.ERR_INVALID_ARG, f"segment_moments: unknown source {source!r}")
+        rc, records = self.segment_moments_raw(code, n_seg, segment_start, indices)
+        self._check(rc)
+        return records
+
+    def segment_stats(self) -> dict:
+        """host_waits of the last segment_moments call (icpgpu_segment_stats)."""
+        w = C.c_int32()
+        self._check(self._L.icpgpu_segment_stats(self._h, C.byref(w)))
+        return {"host_waits": int(w.value)}
 
     # ISS keypoints (pcl::ISSKeypoint3D; the _border calls with border estimation; rules: include/icpgpu.h) -------------------------
     def iss_keypoints_raw(self, salient_radius: float, non_max_radius: float, gamma_21: float = 0.975, gamma_32: float = 0.975,
@@ -1925,6 +1969,97 @@ class RegionGrowing:
             raise IcpGpuError(_lib.ERR_INVALID_ARG, f"getSegmentFromPoint: index {index} outside the cloud")
         r = int(labels[int(index)])
         return np.empty(0, np.int32) if r < 0 else indices[start[r]:start[r + 1]].copy()
+
+
+class MomentOfInertiaEstimation:
+    """pcl::MomentOfInertiaEstimation<PointXYZ>-shaped front end (include/icpgpu.h, "segment moments"): setInputCloud, setIndices (ONE
+    segment; the whole cloud without), compute(), getAABB() -> (min, max), getOBB() -> (min, max, position, rotation) as PCL hands them
+    out (min / max relative to the box's centre, the rotation's COLUMNS the major, middle and minor axis), getEigenValues() -> (major,
+    middle, minor), getEigenVectors() -> three vectors, getMassCenter().  Beyond PCL, every segment of a segmentation in one call:
+    compute_segments(list of index arrays), compute_clusters(EuclideanClusterExtraction) and compute_regions(RegionGrowing) -- the
+    last two read the extractor's unfetched result on the device -- each returning the records (Context.segment_moments).
+    getMomentOfInertia, getEccentricity, setAngleStep and setIndices on top of a segment list raise."""
+
+    def __init__(self, device_id: int = 0):
+        self._ctx = Context(device_id)
+        self._input = None
+        self._indices = None
+        self._records = None
+
+    def setInputCloud(self, cloud):
+        self._input = _as_cloud(cloud).copy()
+        self._records = None
+
+    def setIndices(self, indices):
+        self._indices = np.ascontiguousarray(indices, np.int32).copy()
+        self._records = None
+
+    def setAngleStep(self, step: float):
+        raise IcpGpuError(_lib.ERR_UNSUPPORTED, "MomentOfInertiaEstimation.setAngleStep: the moment-of-inertia sweep is not provided")
+
+    def getMomentOfInertia(self):
+        raise IcpGpuError(_lib.ERR_UNSUPPORTED, "MomentOfInertiaEstimation.getMomentOfInertia is not provided")
+
+    def getEccentricity(self):
+        raise IcpGpuError(_lib.ERR_UNSUPPORTED, "MomentOfInertiaEstimation.getEccentricity is not provided")
+
+    def compute(self):
+        if self._input is None:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "compute: setInputCloud first")
+        indices = np.arange(len(self._input), dtype=np.int32) if self._indices is None else self._indices
+        self.compute_segments([indices])
+
+    def compute_segments(self, segments) -> np.ndarray:
+        """One record per index array of `segments` over the input cloud; the getters then describe the first."""
+        if self._input is None:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "compute_segments: setInputCloud first")
+        if self._indices is not None and not (len(segments) == 1 and segments[0] is self._indices):
+            raise IcpGpuError(_lib.ERR_UNSUPPORTED, "MomentOfInertiaEstimation: setIndices on top of a segment list is not provided")
+        lists = [np.ascontiguousarray(s, np.int32).reshape(-1) for s in segments]
+        start = np.zeros(len(lists) + 1, np.int64)
+        np.cumsum([len(s) for s in lists], out=start[1:])
+        self._ctx.search_set_input(self._input)
+        self._records = self._ctx.segment_moments(start, np.concatenate(lists) if lists else np.empty(0, np.int32))
+        return self._records
+
+    def _compute_extractor(self, extractor, source: str) -> np.ndarray:
+        if self._indices is not None:
+            raise IcpGpuError(_lib.ERR_UNSUPPORTED, "MomentOfInertiaEstimation: setIndices on top of a segment list is not provided")
+        segments = extractor.extract()  # (its context holds the search cloud and the result this call reads on the device)
+        self._records = extractor._ctx.segment_moments(source=source, n_segments=len(segments))
+        return self._records
+
+    def compute_clusters(self, extractor: "EuclideanClusterExtraction") -> np.ndarray:
+        """extractor.extract(), then one record per cluster in emitted order, read from the device-resident result."""
+        return self._compute_extractor(extractor, "clusters")
+
+    def compute_regions(self, extractor: "RegionGrowing") -> np.ndarray:
+        """extractor.extract(), then one record per region in emitted order, read from the device-resident result."""
+        return self._compute_extractor(extractor, "regions")
+
+    def _first(self):
+        if self._records is None or self._records.size == 0:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "MomentOfInertiaEstimation: compute first")
+        return self._records[0]
+
+    def getAABB(self) -> tuple:
+        r = self._first()
+        return r["aabb_min"].copy(), r["aabb_max"].copy()
+
+    def getOBB(self) -> tuple:
+        r = self._first()
+        half = r["obb_dims"] / 2.0
+        return -half, half, r["obb_position"].copy(), r["axes"].reshape(3, 3).T.copy()
+
+    def getEigenValues(self) -> tuple:
+        return tuple(float(v) for v in self._first()["eigenvalues"])
+
+    def getEigenVectors(self) -> tuple:
+        axes = self._first()["axes"].reshape(3, 3)
+        return axes[0].copy(), axes[1].copy(), axes[2].copy()
+
+    def getMassCenter(self) -> np.ndarray:
+        return self._first()["centroid"].copy()
 
 
 class ISSKeypoint3D:

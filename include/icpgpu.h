@@ -56,7 +56,7 @@ extern "C" {
  * icpgpu_get_reciprocal_correspondences, icpgpu_reciprocal_stats, and the outlier filters -- icpgpu_statistical_outlier_removal,
  * icpgpu_radius_outlier_removal, their _view forms, icpgpu_outlier_stats, icpgpu_outlier_fetch, and the neighbour search --
  * icpgpu_search_set_input, icpgpu_search_size, icpgpu_search_knn, icpgpu_search_radius, and normal estimation --
- * icpgpu_normal_estimation, and euclidean clustering -- icpgpu_euclidean_cluster_extraction, icpgpu_cluster_fetch, and region growing -- icpgpu_region_growing, icpgpu_region_fetch, and plane segmentation --
+ * icpgpu_normal_estimation, and euclidean clustering -- icpgpu_euclidean_cluster_extraction, icpgpu_cluster_fetch, and region growing -- icpgpu_region_growing, icpgpu_region_fetch, and segment moments -- icpgpu_segment_moments, icpgpu_segment_stats, and plane segmentation --
  * icpgpu_sac_plane_segmentation, icpgpu_sac_fetch, icpgpu_sac_stats, icpgpu_sac_extract, icpgpu_sac_extract_view, and the ground filter -- icpgpu_morphological_operator,
  * icpgpu_progressive_morphological_filter, icpgpu_pmf_fetch, icpgpu_pmf_stats, icpgpu_pmf_extract, icpgpu_pmf_extract_view, and ISS keypoints --
  * icpgpu_iss_keypoints, icpgpu_iss_fetch, icpgpu_iss_stats, icpgpu_iss_keypoints_border, icpgpu_iss_fetch_border, and boundary
@@ -1095,6 +1095,90 @@ int icpgpu_region_growing(icpgpu_ctx* ctx, const float* normals_nxyzc /* n float
 int icpgpu_region_fetch(icpgpu_ctx* ctx, size_t capacity_regions, size_t capacity_indices, int64_t* region_start /* n_regions + 1 */,
                         int32_t* indices /* n_in_regions */, int32_t* labels /* n, may be NULL */, int32_t* region /* n, may be NULL */,
                         int32_t* kind /* n, may be NULL: 2 core, 1 border, 0 single, -1 none */, int32_t* anchor /* n, may be NULL */);
+
+/* ---- segment moments (added under 1.2) ------------------------------------------------------------------------------ */
+/* replaces, for EVERY segment of a segmentation in one call, pcl::MomentOfInertiaEstimation<PointXYZ> -- setInputCloud, setIndices,
+ * compute, getAABB, getOBB, getEigenValues, getEigenVectors, getMassCenter -- and the per-cluster calls that follow a clustering in
+ * PCL pipelines: compute3DCentroid, getMinMax3D, computeMeanAndCovarianceMatrix, pcl::PCA.  The call works on the context's SEARCH
+ * CLOUD (icpgpu_search_set_input), n points.  Parity with PCL binaries is unpinned; tests/segment_restated.py is what the kernels are
+ * compared with, bit for bit.
+ * SOURCE.  ICPGPU_SEGMENTS_HOST: the caller's CSR -- segment r lists indices[segment_start[r] .. segment_start[r + 1]), with
+ * segment_start[0] = 0, the offsets non-decreasing and every index in [0, n).  Segments may overlap, repeat an index (it counts as often
+ * as it is listed), be unsorted or be empty.  ICPGPU_SEGMENTS_CLUSTERS / ICPGPU_SEGMENTS_REGIONS: the result of the last
+ * icpgpu_euclidean_cluster_extraction / icpgpu_region_growing over this search cloud, fetched or not, read WHERE IT LIES on the
+ * device: nothing is copied to the host or back.  segment_start and indices must then be NULL and n_segments must equal the result's
+ * count (a check); record r describes cluster / region r in emitted order.
+ * POINTS.  A listed point whose x, y or z is not finite is skipped.  count = the number of finite listed entries.  K = the first finite
+ * listed entry of the segment in list order, first = its cloud index.  A segment without one has status = ICPGPU_SEGMENT_EMPTY,
+ * count = 0 and every other field zero (first included); every other segment has status = ICPGPU_SEGMENT_OK.
+ * SUMS (the plane refinement's rule, restated for a segment).  For every finite listed entry q, (dx, dy, dz) = q - K in float32; the
+ * nine sums of dx dx, dx dy, dx dz, dy dy, dy dz, dz dz, dx, dy, dz take their terms in double, where each term is exact, and each sum
+ * is the EXACT sum rounded once: moments9.  They are accumulated in double-double in a FIXED order: the segment's entries are cut at
+ * the multiples of ICPGPU_SEGMENT_CHUNK = 64 of their position in the whole list (all segments' entries, one after the other) into
+ * pieces; a piece starts with one value per entry, the term or zero for a skipped entry, and is folded in six rounds d = 1, 2, 4, 8,
+ * 16, 32: in a round every position p of the piece with p + d inside the piece becomes x[p] + x[p + d], all positions at once; the
+ * piece's sum is its first position's.  A segment's pieces are then folded: lane l of 64 adds the pieces l, l + 64, ... in ascending
+ * order, starting from zero, and in six rounds d = 32, 16, 8, 4, 2, 1 every lane l < d becomes x[l] + x[l + d]; lane 0 holds the
+ * sum.  Two runs give the same bits.  RANGE: with dmax the largest
+ * and dmin the smallest non-zero |dx|, |dy| or |dz| of the segment, every sum is the exact one whenever
+ * count * (dmax / dmin) < 2^28 (sufficient, not necessary: every difference is a multiple of 2^-24 dmin, every term of 2^-48 dmin^2,
+ * and the low parts, at most count^2 dmax^2 2^-53, must stay below 2^53 such units; a factor 4 is kept back) -- 25 entries between
+ * 1e-5 and 100 m, or 8000 between 1 mm and 30 m, are inside it; beyond it a sum is that fixed order's double-double result, within
+ * an ulp of the exact sum.
+ * FINISH.  In double, every operation rounded, with m = count: the means m_a = S_a / m; cov_ab = S_ab / m - m_a m_b, the NORMALISED
+ * covariance (divided by m, not by m - 1), cov6 = xx, xy, xz, yy, yz, zz; centroid = K + mean.  The cyclic Jacobi of normal
+ * estimation (8 sweeps) gives three eigenvalues with their columns.  ORDER: major >= middle >= minor by eigenvalue, the lower column
+ * index first among equals (columns 0 and 1, then 1 and 2, then 0 and 1 change places iff the later one's eigenvalue is strictly
+ * larger).  SIGNS: the major and the middle axis are each negated when their component of largest magnitude, the lowest index among
+ * equal magnitudes, is negative; minor = major x middle, (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x), every product and
+ * difference rounded.  eigenvalues3 = major, middle, minor; axes9 = the three axes as rows.  DEVIATION: PCL leaves the order among
+ * ties and the signs to Eigen, and scales nothing differently.  Coincident points give a zero matrix and the identity.
+ * AXIS-ALIGNED BOX.  aabb_min / aabb_max: the minimum and maximum of the finite listed float32 coordinates themselves, -0 ordered
+ * below +0 (the ground filter's sign-flipped integer keys).  Exact and order-free.
+ * ORIENTED BOX.  For every finite listed entry and each axis a (major, middle, minor): u_a = (dx e_ax + dy e_ay) + dz e_az in double,
+ * d the same float32 difference from K widened, every product and sum rounded on its own.  obb_lo / obb_hi: the minimum and maximum
+ * of u_a, -0 below +0, order-free; obb_dims = hi - lo; with c_a = (hi_a + lo_a) / 2,
+ * obb_position = K + ((c_0 e_0 + c_1 e_1) + c_2 e_2) per component, in double.  The box's rotation is axes9 (rows).
+ * RECORD.  icpgpu_segment_record below; sizeof_record travels with the call (the ABI rule of this header): a size no 1.x header had
+ * is refused.
+ * ICPGPU_ERR_INVALID_ARG: no search cloud; an unknown source; HOST with a null segment_start, a segment_start that is not a
+ * non-decreasing sequence from 0, null indices with a non-zero total, or an index outside [0, n); CLUSTERS / REGIONS with no result
+ * (none computed, the last call refused, or the search cloud replaced since), another count, or non-NULL arrays; a null out with
+ * n_segments > 0; a wrong sizeof_record.  Nothing is written then.  n_segments = 0 is ICPGPU_OK.  ICPGPU_ERR_UNSUPPORTED: more than
+ * 2^31 - 1 listed entries or segments.
+ * CALLS.  One host wait per call, the delivery of the records; icpgpu_segment_stats reports the host waits of the last call.
+ * Not provided: getMomentOfInertia / getEccentricity (the angle-step sweep of axes), setIndices on top of a segment list -- the
+ * shims throw or raise on these.
+ * ISOLATION.  The result depends on the search cloud and the arguments alone.  The call keeps nothing; its
+ * scratch is its own.  It leaves the source, the target, every grid, the covariances, the cached normals, the NDT cells, the filters'
+ * results and the search cloud as they were, and with them unfetched clustering, region growing, plane segmentation, ground filter,
+ * ISS and moving least squares results -- the very cluster or region result it reads included. */
+#define ICPGPU_SEGMENTS_HOST 0
+#define ICPGPU_SEGMENTS_CLUSTERS 1
+#define ICPGPU_SEGMENTS_REGIONS 2
+#define ICPGPU_SEGMENT_OK 0
+#define ICPGPU_SEGMENT_EMPTY 1
+#define ICPGPU_SEGMENT_CHUNK 64
+typedef struct icpgpu_segment_record {
+  int64_t count;          /* finite listed entries */
+  int32_t status;         /* ICPGPU_SEGMENT_OK / ICPGPU_SEGMENT_EMPTY */
+  int32_t first;          /* K's cloud index */
+  double K[3];
+  double moments[9];      /* the sums of dx dx, dx dy, dx dz, dy dy, dy dz, dz dz, dx, dy, dz about K */
+  double centroid[3];
+  double cov[6];          /* xx, xy, xz, yy, yz, zz */
+  double eigenvalues[3];  /* major, middle, minor */
+  double axes[9];         /* rows: major, middle, minor */
+  float aabb_min[3];
+  float aabb_max[3];
+  double obb_lo[3];       /* along the axes, about K */
+  double obb_hi[3];
+  double obb_position[3]; /* the oriented box's centre */
+  double obb_dims[3];     /* its extents along major, middle, minor */
+} icpgpu_segment_record;
+int icpgpu_segment_moments(icpgpu_ctx* ctx, int source, size_t n_segments, const int64_t* segment_start /* n_segments + 1 */,
+                           const int32_t* indices, size_t sizeof_record, icpgpu_segment_record* out /* n_segments */);
+int icpgpu_segment_stats(const icpgpu_ctx* ctx, int32_t* host_waits);
 
 /* ---- plane segmentation (added under 1.2) --------------------------------------------------------------------------- */
 /* replaces pcl::SACSegmentation<PointXYZ> with SACMODEL_PLANE or SACMODEL_PERPENDICULAR_PLANE and SAC_RANSAC -- setInputCloud,

@@ -1136,6 +1136,7 @@ class EuclideanClusterExtraction {
   void extract(std::vector<PointIndices>& clusters) {
     clusters.clear();
     labels_.clear();
+    have_ = false;
     if (!input_) return;
     static_assert(sizeof(input_->points[0]) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
     static_assert(sizeof(int) == sizeof(int32_t) && sizeof(long long) == sizeof(int64_t), "icpgpu: 32-bit int, 64-bit long long");
@@ -1143,6 +1144,7 @@ class EuclideanClusterExtraction {
     if (icpgpu_search_set_input(ctx_, n ? reinterpret_cast<const float*>(&input_->points[0]) : nullptr, n) != ICPGPU_OK) return;
     std::size_t n_clusters = 0, n_clustered = 0;
     if (icpgpu_euclidean_cluster_extraction(ctx_, tolerance_, min_, max_, &n_clusters, &n_clustered) != ICPGPU_OK) return;
+    have_ = true, n_emitted_ = n_clusters;
     std::vector<long long> start(n_clusters + 1, 0);
     std::vector<int> indices(n_clustered);
     labels_.assign(n, -1);
@@ -1157,6 +1159,11 @@ class EuclideanClusterExtraction {
   }
   // NOT a PCL method: the last extract()'s cluster rank of every input point, -1 where it is in none (empty after a refused call)
   const std::vector<int>& getLabels() const { return labels_; }
+  // NOT PCL methods: the context that holds the last extract()'s result on the device, and whether and how many clusters it holds
+  // (what MomentOfInertiaEstimation::computeClusters reads)
+  icpgpu_ctx* context() const { return ctx_; }
+  bool hasResult() const { return have_; }
+  std::size_t getNumberOfSegments() const { return n_emitted_; }
 
  private:
   detail::ContextPtr ctx_holder_;
@@ -1164,6 +1171,8 @@ class EuclideanClusterExtraction {
   const CloudT* input_ = nullptr;
   double tolerance_ = 0.0;
   int min_ = 1, max_ = 0x7FFFFFFF;
+  bool have_ = false;
+  std::size_t n_emitted_ = 0;
   std::vector<int> labels_;
 };
 
@@ -1256,6 +1265,11 @@ class RegionGrowing {
   }
   // NOT a PCL method: the last extract()'s region rank of every input point, -1 where it is in none (empty after a refused call)
   const std::vector<int>& getLabels() const { return labels_; }
+  // NOT PCL methods: the context that holds the last extract()'s result on the device, and whether and how many regions it holds
+  // (what MomentOfInertiaEstimation::computeRegions reads)
+  icpgpu_ctx* context() const { return ctx_; }
+  bool hasResult() const { return have_; }
+  std::size_t getNumberOfSegments() const { return clusters_.size(); }
 
  private:
   detail::ContextPtr ctx_holder_;
@@ -1270,6 +1284,172 @@ class RegionGrowing {
   std::vector<int> labels_;
   std::vector<PointIndices> clusters_;
 };
+
+// pcl::MomentOfInertiaEstimation<PointT>-shaped front end (rules and deviations: include/icpgpu.h, "segment moments"):
+//   pcl::MomentOfInertiaEstimation<pcl::PointXYZ> fe;  ->  icpgpu::MomentOfInertiaEstimation<pcl::PointCloud<pcl::PointXYZ>> fe;
+//   fe.setInputCloud(cloud); fe.setIndices(indices); fe.compute();
+//   fe.getAABB(min, max); fe.getOBB(min, max, position, rotation); fe.getEigenValues(major, middle, minor);
+//   fe.getEigenVectors(major, middle, minor); fe.getMassCenter(centre);
+// The points are anything with x, y, z; the vectors anything with operator[]; the rotation anything with operator()(row, column)
+// (Eigen's or this header's).  As in PCL the oriented box's min and max are relative to its centre `position` and the rotation's
+// COLUMNS are the major, middle and minor axis.  The getters return false before a successful compute and for an EMPTY segment.
+// Beyond PCL, every segment of a segmentation in ONE call: compute(segments) over a vector of PointIndices, computeClusters(ec) and
+// computeRegions(reg) over the result the extractor's last extract() left ON THE DEVICE (no indices travel); getRecords() then
+// holds one icpgpu_segment_record per segment and the getters describe the first.  getMomentOfInertia, getEccentricity,
+// setAngleStep and setIndices on top of a segment list throw.
+template <class CloudT>
+class MomentOfInertiaEstimation {
+ public:
+  explicit MomentOfInertiaEstimation(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {}
+  template <class CloudPtr>
+  void setInputCloud(const CloudPtr& cloud) { input_ = &*cloud, records_.clear(); }
+  template <class IndicesPtr>
+  void setIndices(const IndicesPtr& indices) { indices_ = indices->indices, have_indices_ = true, records_.clear(); }
+  void setAngleStep(float) { throw std::invalid_argument("icpgpu::MomentOfInertiaEstimation: the moment-of-inertia sweep is not provided"); }
+  bool getMomentOfInertia(std::vector<float>&) const { throw std::invalid_argument("icpgpu::MomentOfInertiaEstimation: getMomentOfInertia is not provided"); }
+  bool getEccentricity(std::vector<float>&) const { throw std::invalid_argument("icpgpu::MomentOfInertiaEstimation: getEccentricity is not provided"); }
+  // one segment: the indices, or the whole cloud
+  void compute() {
+    records_.clear();
+    if (!input_) return;
+    std::vector<PointIndices> one(1);
+    if (have_indices_) {
+      one[0].indices = indices_;
+    } else {
+      one[0].indices.resize(input_->points.size());
+      for (std::size_t i = 0; i < one[0].indices.size(); ++i) one[0].indices[i] = (int)i;
+    }
+    run_host(one);
+  }
+  // NOT PCL methods: every segment in one call
+  void compute(const std::vector<PointIndices>& segments) {
+    if (have_indices_) throw std::invalid_argument("icpgpu::MomentOfInertiaEstimation: setIndices on top of a segment list is not provided");
+    records_.clear();
+    if (input_) run_host(segments);
+  }
+  template <class ExtractorT>
+  void computeClusters(const ExtractorT& ec) { run_device(ec, ICPGPU_SEGMENTS_CLUSTERS); }
+  template <class ExtractorT>
+  void computeRegions(const ExtractorT& reg) { run_device(reg, ICPGPU_SEGMENTS_REGIONS); }
+  const std::vector<icpgpu_segment_record>& getRecords() const { return records_; }
+
+  template <class PointT>
+  bool getAABB(PointT& min_point, PointT& max_point) const {
+    if (!usable()) return false;
+    const icpgpu_segment_record& r = records_[0];
+    min_point.x = r.aabb_min[0], min_point.y = r.aabb_min[1], min_point.z = r.aabb_min[2];
+    max_point.x = r.aabb_max[0], max_point.y = r.aabb_max[1], max_point.z = r.aabb_max[2];
+    return true;
+  }
+  template <class PointT, class Matrix3T>
+  bool getOBB(PointT& min_point, PointT& max_point, PointT& position, Matrix3T& rotational_matrix) const {
+    if (!usable()) return false;
+    const icpgpu_segment_record& r = records_[0];
+    max_point.x = (float)(r.obb_dims[0] / 2.0), max_point.y = (float)(r.obb_dims[1] / 2.0), max_point.z = (float)(r.obb_dims[2] / 2.0);
+    min_point.x = -max_point.x, min_point.y = -max_point.y, min_point.z = -max_point.z;
+    position.x = (float)r.obb_position[0], position.y = (float)r.obb_position[1], position.z = (float)r.obb_position[2];
+    for (int a = 0; a < 3; ++a)
+      for (int k = 0; k < 3; ++k) rotational_matrix(k, a) = (float)r.axes[3 * a + k];
+    return true;
+  }
+  bool getEigenValues(float& major, float& middle, float& minor) const {
+    if (!usable()) return false;
+    major = (float)records_[0].eigenvalues[0], middle = (float)records_[0].eigenvalues[1], minor = (float)records_[0].eigenvalues[2];
+    return true;
+  }
+  template <class Vector3T>
+  bool getEigenVectors(Vector3T& major, Vector3T& middle, Vector3T& minor) const {
+    if (!usable()) return false;
+    for (int k = 0; k < 3; ++k) major[k] = (float)records_[0].axes[k], middle[k] = (float)records_[0].axes[3 + k], minor[k] = (float)records_[0].axes[6 + k];
+    return true;
+  }
+  template <class Vector3T>
+  bool getMassCenter(Vector3T& mass_center) const {
+    if (!usable()) return false;
+    for (int k = 0; k < 3; ++k) mass_center[k] = (float)records_[0].centroid[k];
+    return true;
+  }
+
+ private:
+  bool usable() const { return !records_.empty() && records_[0].status == ICPGPU_SEGMENT_OK; }
+  void run_host(const std::vector<PointIndices>& segments) {
+    static_assert(sizeof(input_->points[0]) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+    static_assert(sizeof(int) == sizeof(int32_t), "icpgpu: 32-bit int");
+    const std::size_t n = input_->points.size();
+    std::vector<int64_t> start(segments.size() + 1, 0);
+    for (std::size_t r = 0; r < segments.size(); ++r) start[r + 1] = start[r] + (int64_t)segments[r].indices.size();
+    std::vector<int32_t> flat;
+    flat.reserve((std::size_t)start.back());
+    for (const PointIndices& s : segments) flat.insert(flat.end(), s.indices.begin(), s.indices.end());
+    if (icpgpu_search_set_input(ctx_, n ? reinterpret_cast<const float*>(&input_->points[0]) : nullptr, n) != ICPGPU_OK) return;
+    records_.resize(segments.size());
+    if (icpgpu_segment_moments(ctx_, ICPGPU_SEGMENTS_HOST, segments.size(), &start[0], flat.empty() ? nullptr : &flat[0], sizeof(icpgpu_segment_record),
+                               records_.empty() ? nullptr : &records_[0]) != ICPGPU_OK)
+      records_.clear();
+  }
+  template <class ExtractorT>
+  void run_device(const ExtractorT& extractor, int source) {
+    if (have_indices_) throw std::invalid_argument("icpgpu::MomentOfInertiaEstimation: setIndices on top of a segment list is not provided");
+    records_.clear();
+    if (!extractor.hasResult()) return;
+    records_.resize(extractor.getNumberOfSegments());
+    if (icpgpu_segment_moments(extractor.context(), source, records_.size(), nullptr, nullptr, sizeof(icpgpu_segment_record),
+                               records_.empty() ? nullptr : &records_[0]) != ICPGPU_OK)
+      records_.clear();
+  }
+
+  detail::ContextPtr ctx_holder_;
+  icpgpu_ctx* ctx_;
+  const CloudT* input_ = nullptr;
+  std::vector<int> indices_;
+  bool have_indices_ = false;
+  std::vector<icpgpu_segment_record> records_;
+};
+
+// pcl::getMinMax3D, pcl::compute3DCentroid and pcl::computeMeanAndCovarianceMatrix over a cloud and an index list, as one-segment
+// calls of the same rule ("segment moments": the NORMALISED covariance, as PCL's).  min_pt / max_pt / centroid: anything with
+// operator[] and four entries (the fourth is set to 0 for the extremes and to 1 for the centroid, as PCL does); covariance_matrix:
+// anything with operator()(row, column).  The two counting functions return the number of finite listed points, 0 on a refusal.
+namespace detail {
+template <class CloudT>
+inline bool one_segment(const CloudT& cloud, const std::vector<int>& indices, icpgpu_segment_record& r) {
+  static_assert(sizeof(cloud.points[0]) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+  ContextPtr holder = acquire_context(0);
+  const std::size_t n = cloud.points.size();
+  const int64_t start[2] = {0, (int64_t)indices.size()};
+  if (icpgpu_search_set_input(holder->ctx, n ? reinterpret_cast<const float*>(&cloud.points[0]) : nullptr, n) != ICPGPU_OK) return false;
+  return icpgpu_segment_moments(holder->ctx, ICPGPU_SEGMENTS_HOST, 1, start, indices.empty() ? nullptr : reinterpret_cast<const int32_t*>(&indices[0]),
+                                sizeof r, &r) == ICPGPU_OK && r.status == ICPGPU_SEGMENT_OK;
+}
+}  // namespace detail
+
+template <class CloudT, class Vector4T>
+inline void getMinMax3D(const CloudT& cloud, const std::vector<int>& indices, Vector4T& min_pt, Vector4T& max_pt) {
+  icpgpu_segment_record r;
+  if (!detail::one_segment(cloud, indices, r)) return;
+  for (int k = 0; k < 3; ++k) min_pt[k] = r.aabb_min[k], max_pt[k] = r.aabb_max[k];
+  min_pt[3] = 0, max_pt[3] = 0;
+}
+template <class CloudT, class Vector4T>
+inline unsigned int compute3DCentroid(const CloudT& cloud, const std::vector<int>& indices, Vector4T& centroid) {
+  icpgpu_segment_record r;
+  if (!detail::one_segment(cloud, indices, r)) return 0;
+  for (int k = 0; k < 3; ++k) centroid[k] = (typename std::decay<decltype(centroid[0])>::type)r.centroid[k];
+  centroid[3] = 1;
+  return (unsigned int)r.count;
+}
+template <class CloudT, class Matrix3T, class Vector4T>
+inline unsigned int computeMeanAndCovarianceMatrix(const CloudT& cloud, const std::vector<int>& indices, Matrix3T& covariance_matrix, Vector4T& centroid) {
+  icpgpu_segment_record r;
+  if (!detail::one_segment(cloud, indices, r)) return 0;
+  const int at[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
+  for (int a = 0; a < 3; ++a) {
+    centroid[a] = (typename std::decay<decltype(centroid[0])>::type)r.centroid[a];
+    for (int b = 0; b < 3; ++b) covariance_matrix(a, b) = (typename std::decay<decltype(covariance_matrix(0, 0))>::type)r.cov[at[a][b]];
+  }
+  centroid[3] = 1;
+  return (unsigned int)r.count;
+}
 
 // pcl::ISSKeypoint3D<PointT, PointT>-shaped front end (rules and deviations: include/icpgpu.h, "ISS keypoints") -- the keypoints at
 // which FPFHEstimation computes its descriptors (fpfh.setInputCloud(keypoints); fpfh.setSearchSurface(cloud)):
