@@ -55,10 +55,16 @@ double det_cols(const Col3 c[3]) { return c[0].dot(cross(c[1], c[2])); }
 
 // Hestenes one-sided Jacobi: orthogonalise the columns of W = A V by plane rotations accumulated in V.
 void svd3x3(const double A[9], double U[9], double s[3], double V[9]) {
+  // The sweeps square the entries (aa * bb overflows from 1e77 on, underflows below 1e-160), so they run on A / 2^scale with the largest
+  // entry in [0.5, 1).  A power of two is exact: every ratio the sweeps and the rank cut look at is unchanged, bit for bit.
+  double amax = 0.0;
+  for (int i = 0; i < 9; ++i) amax = std::fmax(amax, std::fabs(A[i]));
+  int scale = 0;
+  if (amax > 0.0 && std::isfinite(amax)) std::frexp(amax, &scale);
   Col3 w[3], v[3];
   for (int j = 0; j < 3; ++j) {
     for (int r = 0; r < 3; ++r) {
-      w[j].v[r] = A[r * 3 + j];
+      w[j].v[r] = std::ldexp(A[r * 3 + j], -scale);
       v[j].v[r] = (r == j) ? 1.0 : 0.0;
     }
   }
@@ -106,13 +112,20 @@ void svd3x3(const double A[9], double U[9], double s[3], double V[9]) {
       const double n = e.norm();
       for (int r = 0; r < 3; ++r) u[1].v[r] = e.v[r] / n;
     }
-    if (s[2] <= tiny) u[2] = cross(u[0], u[1]);
+    if (s[2] <= tiny) {
+      // on the side the sweeps found, so that U diag(s) V^T stays A to rounding for 0 < s2 <= tiny.  The solve's R does not depend on
+      // the side: it takes sign(det U det V) u2 v2^T, and negating u2 negates det U exactly.
+      const Col3 n = cross(u[0], u[1]);
+      const double side = n.dot(u[2]) < 0.0 ? -1.0 : 1.0;
+      for (int r = 0; r < 3; ++r) u[2].v[r] = side * n.v[r];
+    }
   }
   for (int j = 0; j < 3; ++j)
     for (int r = 0; r < 3; ++r) {
       U[r * 3 + j] = u[j].v[r];
       V[r * 3 + j] = vs[j].v[r];
     }
+  for (int j = 0; j < 3; ++j) s[j] = std::ldexp(s[j], scale);
 }
 
 bool solve_umeyama(const double sums[17], Mat4d& Tk) {
@@ -127,6 +140,9 @@ bool solve_umeyama(const double sums[17], Mat4d& Tk) {
   // Sigma = E[(q - mu_q)(p - mu_p)^T] from the raw second moment (double: 80 m ranges leave > 9 digits of headroom)
   for (int a = 0; a < 3; ++a)
     for (int b = 0; b < 3; ++b) sigma[3 * a + b] = sums[7 + 3 * a + b] / n - mu_q[a] * mu_p[b];
+  // an infinite entry would pass the sweeps (inf <= inf skips every rotation) and come out of the completion as a finite matrix
+  for (double x : sigma)
+    if (!std::isfinite(x)) return false;
 
   double U[9], s[3], V[9];
   svd3x3(sigma, U, s, V);

@@ -19,10 +19,12 @@ Mat4d mat4_mul(const Mat4d& a, const Mat4d& b);
 void mat4_to_float(const Mat4d& a, float out[16]);
 
 // sums = {n, sum p(3), sum q(3), sum q p^T (9, row-major, row = q), sum d2}. Returns false when n < 1 or the
-// result is not finite (Tk is then identity).
+// covariance or the result is not finite (Tk is then identity).  Otherwise Tk's rotation maximises tr(R^T Sigma) over
+// SO(3) (Umeyama's reflection rule), also where Sigma is rank deficient and any maximiser will do.
 bool solve_umeyama(const double sums[17], Mat4d& Tk);
 
-// A = U diag(s) V^T for a row-major 3x3, singular values descending, U and V orthonormal.
+// A = U diag(s) V^T for a row-major 3x3, singular values descending, U and V orthonormal, at any scale of A (the sweeps
+// run on A / 2^e).  Columns of U whose singular value is at most 1e-13 s0 are completed to an orthonormal basis.
 void svd3x3(const double A[9], double U[9], double s[3], double V[9]);
 
 // pcl::registration::DefaultConvergenceCriteria with the settings IterativeClosestPoint applies:

@@ -60,8 +60,13 @@ static double det3(const double A[9]) {
 
 /* One-sided (Hestenes) Jacobi SVD of a 3x3 row-major matrix: A = U diag(s) V^T. */
 void orc_svd3(const double A[9], double U[9], double s[3], double V[9]) {
+  /* The sweeps square the entries: run them on A / 2^e, largest entry in [0.5, 1) (exact; no ratio below changes by a bit). */
+  double amax = 0.0;
+  for (int i = 0; i < 9; ++i) amax = fmax(amax, fabs(A[i]));
+  int e = 0;
+  if (amax > 0.0 && isfinite(amax)) frexp(amax, &e);
   double W[9]; /* working copy, columns get orthogonalised: W = A*V */
-  memcpy(W, A, sizeof(W));
+  for (int i = 0; i < 9; ++i) W[i] = ldexp(A[i], -e);
   for (int i = 0; i < 9; ++i) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
 
   for (int sweep = 0; sweep < 60; ++sweep) {
@@ -132,14 +137,18 @@ void orc_svd3(const double A[9], double U[9], double s[3], double V[9]) {
       Us[7] = v[2] / n;
     }
     if (s[2] <= tiny) {
+      /* on the side the sweeps found (U diag(s) V^T stays A for 0 < s2 <= tiny); umeyama's R is the same on either side */
       double a[3] = {Us[0], Us[3], Us[6]}, b[3] = {Us[1], Us[4], Us[7]};
-      Us[2] = a[1] * b[2] - a[2] * b[1];
-      Us[5] = a[2] * b[0] - a[0] * b[2];
-      Us[8] = a[0] * b[1] - a[1] * b[0];
+      double c[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+      double side = (c[0] * Us[2] + c[1] * Us[5] + c[2] * Us[8] < 0.0) ? -1.0 : 1.0;
+      Us[2] = side * c[0];
+      Us[5] = side * c[1];
+      Us[8] = side * c[2];
     }
   }
   memcpy(U, Us, sizeof(Us));
   memcpy(V, Vs, sizeof(Vs));
+  for (int j = 0; j < 3; ++j) s[j] = ldexp(s[j], e);
 }
 
 /* ------------------------------------------------------------------------------------------ */
@@ -618,7 +627,7 @@ static int umeyama_from_cov(const double mu_p[3], const double mu_q[3], const do
 
 int orc_umeyama(const double sums[17], double Tk[16]) {
   double n = sums[0];
-  if (n < 1.0) {
+  if (!(n >= 1.0)) {
     mat4_identity(Tk);
     return -1;
   }
@@ -629,7 +638,13 @@ int orc_umeyama(const double sums[17], double Tk[16]) {
   }
   for (int a = 0; a < 3; ++a)
     for (int b = 0; b < 3; ++b) Sigma[3 * a + b] = sums[7 + 3 * a + b] / n - mu_q[a] * mu_p[b];
-  return umeyama_from_cov(mu_p, mu_q, Sigma, Tk);
+  int finite = 1;
+  for (int i = 0; i < 9; ++i) finite &= isfinite(Sigma[i]) != 0;
+  if (!finite || umeyama_from_cov(mu_p, mu_q, Sigma, Tk) != 0) { /* not finite: refused with the identity, like n < 1 */
+    mat4_identity(Tk);
+    return -1;
+  }
+  return 0;
 }
 
 /* PCL-float flavour: two-pass (means, then demeaned covariance), float accumulators. */

@@ -1,7 +1,8 @@
 """The sample-consensus rejector on the device (icp_reject_sac.hip, icpgpu_reject_sac.cpp) against tests/rsac_restated.py.  m,
 sample_d2, moments9, the ranks, status, iterations, best_t, the counts, the kept set and best_T are compared bit for bit with the
 restatement FED THE DEVICE'S OWN TRANSFORMS; the transforms themselves with float32(oracle.umeyama(sums)) to one ulp plus 1e-10 on
-well-spread samples (scp_scenes.well_spread; at most 10 % of the evaluated hypotheses may be left out of that comparison)."""
+well-spread samples (scp_scenes.well_spread; at most 10 % of the evaluated hypotheses may be left out of that comparison), and EVERY evaluated hypothesis' transform with tests/solve_reference.py's float32 check on its own
+sums."""
 import ctypes as C
 import functools
 
@@ -13,6 +14,7 @@ import rejectors_restated as RR
 import rsac_restated as R
 import rsac_scenes as S
 import scp_scenes as SC
+import solve_reference as SR
 from icpslam_amd import Context, CorrespondenceRejectorSampleConsensus, IcpGpuError, IterativeClosestPoint, _lib
 
 pytestmark = pytest.mark.gpu
@@ -58,6 +60,8 @@ def compare_core(f, want, what=""):
         ref = want["solved"][t]
         tol = np.spacing(np.abs(ref)).astype(np.float64) + 1e-10
         assert (np.abs(f["transforms"][t].astype(np.float64) - ref.astype(np.float64)) <= tol).all(), (what, t, f["transforms"][t], ref)
+    for t in ev:                                                # EVERY hypothesis, skinny samples included: a proper rotation that maximises the trace
+        SR.check32(want["sums17"][t], f["transforms"][t])
 
 
 def check_call(ctx, P, Q, thr, it, seed, what=""):

@@ -1,6 +1,6 @@
 """icpgpu_scp_align / _fetch / _stats on the GPU against tests/scp_restated.py.  Per hypothesis, status and indices are compared bit for
 bit; the transforms against float32(oracle.umeyama(sums)) within one float32 ulp per entry plus 1e-10 (on samples that are not nearly
-collinear); count, S, error, best_t, the inliers, fitness and the aligned cloud bit for bit against the restatement FED THE DEVICE'S OWN
+collinear), and EVERY evaluated hypothesis' transform against tests/solve_reference.py's float32 check on its own sums; count, S, error, best_t, the inliers, fitness and the aligned cloud bit for bit against the restatement FED THE DEVICE'S OWN
 TRANSFORMS.  Then the end-to-end chain on the device: normals, FPFH, alignment, ICP."""
 import ctypes as C
 import functools
@@ -12,6 +12,7 @@ import pytest
 import oracle
 import scp_restated as R
 import scp_scenes as S
+import solve_reference as SR
 from icpslam_amd import Context, IterativeClosestPoint, _lib
 
 pytestmark = pytest.mark.gpu
@@ -50,6 +51,8 @@ def compare(dev, source, sf, target, tf, nr, kc, similarity, distance, fraction,
             assert (np.abs(dev["transforms"][e].astype(np.float64) - ref32.astype(np.float64)) <= tol).all(), (e, dev["transforms"][e], ref)
             checked += 1
     assert checked >= 0.90 * evaluated.size, (checked, evaluated.size)         # (tests/test_scp_host.py checks the scenes on the CPU)
+    for e in evaluated:                                         # EVERY hypothesis, skinny samples included: a proper rotation that maximises the trace
+        SR.check32(want["sums17"][e], dev["transforms"][e].reshape(4, 4).T)
     assert not dev["transforms"][want["status"] != R.EVALUATED].any()
     for name in ("count", "sum", "error"):                      # the scoring, bit for bit
         assert dev[name].dtype == want[name].dtype and dev[name].tobytes() == want[name].tobytes(), name
