@@ -235,7 +235,11 @@ int gb_on_count(icpgpu_ctx* c, GridBuild& b) {
   }
   G.max_pop = c->h_ints[7];
   G.point_population = pop;
-  if (std::getenv("ICPGPU_DEBUG")) fprintf(stderr, "[icpgpu] grid n=%d binned=%d h=%.4f dims=%dx%dx%d pop=%.1f max=%d attempt=%d\n", n_t, binned, h, b.g.nx, b.g.ny, b.g.nz, pop, G.max_pop, attempt);
+  // (the tail is the exact descriptor the kernels get, as hex floats: tests/grid_adversary.py builds its clouds on it)
+  if (std::getenv("ICPGPU_DEBUG"))
+    fprintf(stderr, "[icpgpu] grid n=%d binned=%d h=%.4f dims=%dx%dx%d pop=%.1f max=%d attempt=%d desc=%a,%a,%a,%a,%a sy=%d sz=%d r_max=%d\n",
+            n_t, binned, h, b.g.nx, b.g.ny, b.g.nz, pop, G.max_pop, attempt, (double)b.g.h, (double)b.g.inv_h, (double)b.g.ox,
+            (double)b.g.oy, (double)b.g.oz, b.g.sy, b.g.sz, b.g.r_max);
   int rc;
   if ((rc = ensure(c, G.sorted, (size_t)n_t * sizeof(float4)))) return rc;
   HIP_TRY(c, launch_grid_finish(b.cloud->data(), n_t, b.g, static_cast<const int*>(G.cell_of_point.ptr),

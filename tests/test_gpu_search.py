@@ -113,8 +113,10 @@ def test_lattice_ties(ctx):
     """9 x 9 x 9 integer lattice: queried at its points, whole shells of candidates share one d2 (6 at 1, 12 at 2, 8 at 3, ...);
     queried at cell centres the 8 corners tie at 0.75.  The order inside every group of equals is the index order, and a list cut
     inside a group keeps its lowest indices.  The whole-key batch skip test meets exact ties with the kept worst here.  The strict
-    form of the shell certificate (kept worst d2 < bound, not <=) is NOT pinned by this or any other test: it matters only when the
-    kept worst equals (rho h 63/64)^2 exactly, and h comes from the cloud's density."""
+    form of the shell certificate (kept worst d2 < bound, not <=) needs no pin: an unseen point lies more than rho cells from the
+    query's cell on some axis, and the float binning is exact to about 2^-9 of a cell, so it is farther than (rho - 2^-8) h -- a
+    kept worst equal to (rho h 63/64)^2 cannot tie with it, and `<=` would certify the same answers.  (The certificate's two sides
+    are pinned on clouds built on the grid itself: tests/test_gpu_grid_adversary.py.)"""
     cloud = lattice(9)
     rng = np.random.default_rng(3)
     cloud = cloud[rng.permutation(len(cloud))]  # (index order is not spatial order)
