@@ -15,14 +15,15 @@ from .registration import FPFH_BINS, FPFHEstimation  # noqa: F401
 from .registration import FeatureKdTree, SampleConsensusPrerejective  # noqa: F401
 from .registration import EuclideanClusterExtraction, RegionGrowing  # noqa: F401
 from .registration import SEGMENT_RECORD, MomentOfInertiaEstimation  # noqa: F401
-from .registration import ExtractIndices, SACSegmentation  # noqa: F401
+from .registration import ExtractIndices, SACSegmentation, SACSegmentationFromNormals  # noqa: F401
 from .registration import ISSKeypoint3D  # noqa: F401
 from .registration import BoundaryEstimation, ISSKeypoint3DBorder  # noqa: F401
 from ._lib import SAC_RANSAC, SACMODEL_PERPENDICULAR_PLANE, SACMODEL_PLANE  # noqa: F401
+from ._lib import SACMODEL_CYLINDER, SACMODEL_NORMAL_PLANE  # noqa: F401
 from .registration import ProgressiveMorphologicalFilter  # noqa: F401
 from ._lib import MORPH_CLOSE, MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, PMF_MAX_PASSES  # noqa: F401
 from .registration import Context, GeneralizedIterativeClosestPoint, IterativeClosestPoint, IterativeClosestPointWithNormals, NormalDistributionsTransform  # noqa: F401
 
-__all__ = ["Context", "IterativeClosestPoint", "GeneralizedIterativeClosestPoint", "IterativeClosestPointWithNormals", "NormalDistributionsTransform", "StatisticalOutlierRemoval", "RadiusOutlierRemoval", "KdTree", "KdTreeFLANN", "NormalEstimation", "FPFHEstimation", "FPFH_BINS", "FeatureKdTree", "SampleConsensusPrerejective", "EuclideanClusterExtraction", "RegionGrowing", "MomentOfInertiaEstimation", "SEGMENT_RECORD", "ISSKeypoint3D", "ISSKeypoint3DBorder", "BoundaryEstimation", "SACSegmentation", "ExtractIndices", "SACMODEL_PLANE", "SACMODEL_PERPENDICULAR_PLANE", "SAC_RANSAC", "ProgressiveMorphologicalFilter", "MORPH_ERODE", "MORPH_DILATE", "MORPH_OPEN", "MORPH_CLOSE", "PMF_MAX_PASSES", "IcpGpuError", "Params", "Result",
+__all__ = ["Context", "IterativeClosestPoint", "GeneralizedIterativeClosestPoint", "IterativeClosestPointWithNormals", "NormalDistributionsTransform", "StatisticalOutlierRemoval", "RadiusOutlierRemoval", "KdTree", "KdTreeFLANN", "NormalEstimation", "FPFHEstimation", "FPFH_BINS", "FeatureKdTree", "SampleConsensusPrerejective", "EuclideanClusterExtraction", "RegionGrowing", "MomentOfInertiaEstimation", "SEGMENT_RECORD", "ISSKeypoint3D", "ISSKeypoint3DBorder", "BoundaryEstimation", "SACSegmentation", "SACSegmentationFromNormals", "ExtractIndices", "SACMODEL_CYLINDER", "SACMODEL_NORMAL_PLANE", "SACMODEL_PLANE", "SACMODEL_PERPENDICULAR_PLANE", "SAC_RANSAC", "ProgressiveMorphologicalFilter", "MORPH_ERODE", "MORPH_DILATE", "MORPH_OPEN", "MORPH_CLOSE", "PMF_MAX_PASSES", "IcpGpuError", "Params", "Result",
            "Profile", "P2P_SVD", "GICP", "P2PLANE", "NDT", "NDT_LINE_SEARCH_PCL18", "NDT_LINE_SEARCH_MORE_THUENTE", "GICP_INNER_EXACT", "GICP_INNER_QUADRATIC",
            "NN_AUTO", "NN_BRUTE", "NN_GRID", "STATE_NAMES"]

@@ -37,6 +37,11 @@ SCP_MAX_SAMPLES = 8            # ICPGPU_SCP_MAX_SAMPLES
 SCP_INVALID, SCP_PREREJECTED, SCP_NO_TRANSFORM, SCP_EVALUATED = 0, 1, 2, 3   # ICPGPU_SCP_*
 SACMODEL_PLANE, SACMODEL_PERPENDICULAR_PLANE = 0, 15   # pcl::SacModel's values
 SAC_RANSAC = 0                 # pcl's method_types.h
+# ICPGPU_SACMODEL_CYLINDER / _NORMAL_PLANE: pcl::SacModel's values by the order of PCL 1.8's model_types.h (PCL itself is not
+# installed where this was written, so no PCL build has confirmed them)
+SACMODEL_CYLINDER, SACMODEL_NORMAL_PLANE = 5, 11
+SAC_CYLINDER_ITERATIONS = 10   # ICPGPU_SAC_CYLINDER_ITERATIONS
+SAC_STOP_PASSES, SAC_STOP_CHOLESKY, SAC_STOP_NOT_FINITE, SAC_STOP_SMALL_STEP, SAC_STOP_NO_DECREASE = 1, 2, 3, 4, 5   # ICPGPU_SAC_STOP_*
 MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3   # icpgpu_morph_op
 PMF_MAX_PASSES = 32            # ICPGPU_PMF_MAX_PASSES
 SEGMENTS_HOST, SEGMENTS_CLUSTERS, SEGMENTS_REGIONS = 0, 1, 2   # ICPGPU_SEGMENTS_*
@@ -133,6 +138,7 @@ EXPORTS = [
     "icpgpu_boundary_estimation", "icpgpu_iss_keypoints_border", "icpgpu_iss_fetch_border",
     "icpgpu_moving_least_squares", "icpgpu_mls_fetch", "icpgpu_mls_stats",
     "icpgpu_sac_plane_segmentation", "icpgpu_sac_fetch", "icpgpu_sac_stats", "icpgpu_sac_extract", "icpgpu_sac_extract_view",
+    "icpgpu_sac_segmentation_from_normals", "icpgpu_sac_normals_fetch", "icpgpu_sac_normals_stats",
     "icpgpu_morphological_operator", "icpgpu_progressive_morphological_filter", "icpgpu_pmf_fetch", "icpgpu_pmf_stats", "icpgpu_pmf_extract",
     "icpgpu_pmf_extract_view",
     "icpgpu_set_source_normals", "icpgpu_set_p2plane_symmetric", "icpgpu_get_p2plane_symmetric",
@@ -259,6 +265,10 @@ def load():
     L.icpgpu_sac_plane_segmentation.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_uint64, C.c_int, dp, C.c_double, fp, szp, ip, ip]
     L.icpgpu_sac_fetch.argtypes = [vp, C.c_size_t, C.c_size_t, ip, ip, ip, ip, fp, dp, szp]
     L.icpgpu_sac_stats.argtypes = [vp, ip]
+    L.icpgpu_sac_segmentation_from_normals.argtypes = [vp, C.c_int, fp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double,
+                                                       C.c_uint64, C.c_int, dp, C.c_double, fp, ip, szp, ip, ip]
+    L.icpgpu_sac_normals_fetch.argtypes = [vp, C.c_size_t, C.c_size_t, ip, ip, ip, ip, fp, szp, dp, dp, ip, ip]
+    L.icpgpu_sac_normals_stats.argtypes = [vp, ip]
     L.icpgpu_segment_moments.argtypes = [vp, C.c_int, C.c_size_t, C.POINTER(C.c_int64), ip, C.c_size_t, C.c_void_p]
     L.icpgpu_segment_stats.argtypes = [vp, ip]
     L.icpgpu_iss_keypoints.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, szp]

@@ -477,6 +477,13 @@ struct icpgpu_ctx {
     std::vector<int32_t> counts;  // count[0 .. iterations)
     DeviceBuf batch, ints, sums;
     Compaction sel, ext;  // sel.kept: the inliers; ext: icpgpu_sac_extract's own (the inlier list outlives an extract)
+    // a result of the segmentation from normals (icpgpu_sac_normals.cpp, icp_sac_normals.hip) is "the last segmentation" too:
+    // model != 0 names it (ICPGPU_SACMODEL_NORMAL_PLANE / _CYLINDER), and then coeff7 / coeff7_unrefined hold the n_coeff
+    // coefficients, cyl_sums the 21 sums of each of the cyl_passes refinement passes; the caller's normals stay in `normals`
+    int model = 0, n_coeff = 0, cyl_passes = 0, cyl_stop = 0;
+    float coeff7[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, coeff7_unrefined[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    std::vector<double> cyl_sums;
+    DeviceBuf normals, nbatch;
   } sac;
   // the sample-consensus rejector (icpgpu_reject_sac.cpp, icp_reject_sac.hip): the last run of its core -- a stage of the chain or
   // icpgpu_correspondence_rejector_sample_consensus -- and its scratch, in buffers no other call reads or writes.  It depends on no
@@ -829,6 +836,10 @@ int sweep_issue_rejected(icpgpu_ctx* c, const Xform& T, float thr, SweepTicket& 
 // (1 + 2 per batch of 64 hypotheses entered; max_iterations >= 1: the setter refuses a stage of none), empties the keys of the pairs it rejects and leaves {pairs in, pairs out, 0} in
 // stats (the stage's kRejectStats words, device memory)
 int reject_sac_stage(icpgpu_ctx* c, unsigned long long* keys, float thr, const Xform& T, const icpgpu_rejector& r, unsigned int* stats);
+// icpgpu_sac.cpp: the threshold's float32 image (the smallest float32 not below t >= 0) and the plane refinement's host half, shared
+// with the segmentation from normals
+float sac_threshold_image(double t);
+void sac_refine_plane(const double S[9], const double K[3], int m, const float unrefined[4], float out[4]);
 // icpgpu_outlier.cpp: a cloud's k-NN grid, its first cell size taken from the cloud's own box (the filters and the neighbour search)
 int build_knn_grid(icpgpu_ctx* c, const Cloud& cloud, GridIndex& G);
 // icpgpu_search.cpp: up to a few device arrays into the caller's (pageable) arrays through the pinned staging buffer, ONE wait

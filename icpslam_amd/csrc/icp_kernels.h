@@ -684,6 +684,30 @@ hipError_t launch_sac_select(const float4* cloud, int n, const float plane[4], f
 // about K = cloud[k_index] (d = q - K in float32); sums12[9 .. 12): K.  One workgroup, a fixed order.
 hipError_t launch_sac_sums(const float4* cloud, int n, const int* inliers, int m, int k_index, double* sums12, hipStream_t stream);
 
+// ---- segmentation from normals (icp_sac_normals.hip): pcl::SACSegmentationFromNormals' RANSAC over the search cloud ---------------
+// The plane segmentation's scheme with the cloud's normals (n float4: nx, ny, nz, curvature) beside it.  model: kSacnPlane or
+// kSacnCylinder (icp_sac_normals.h).  A record holds the coefficients in rec[0 .. 7) (4 for a plane) and, for a cylinder, the band
+// of squared axis distances that can hold inliers in rec[8], rec[9] and its first sample point in rec[12 .. 15); NaN for an INVALID hypothesis.  weight: the float32 image of
+// normal_distance_weight.  The counting grid is capped at kSacnGridCap workgroups of kSacnBlockPoints points a step.  n > 0.
+static constexpr int kSacnRecord = 16, kSacnBlockPoints = 512, kSacnGridCap = 1024;
+struct SacnBatch {
+  int count[kSacBatch];
+  float rec[kSacBatch][kSacnRecord];
+  int sample[kSacBatch][3];
+};
+hipError_t launch_sacn_batch(const float4* cloud, const float4* normals, int n, int model, unsigned long long seed, int t0, int max_iterations,
+                             bool use_axis, const double axis[3], double cos_eps, double radius_min, double radius_max, float thr, float weight,
+                             SacnBatch* batch, hipStream_t stream);
+// the inliers of the model in ascending order into inliers, their number into *n_inliers (launch_compact)
+hipError_t launch_sacn_select(const float4* cloud, const float4* normals, int n, int model, const float coeff7[7], float thr, float weight, int* flags,
+                              int* pos, int* scan_scratch, int* inliers, int* n_inliers, hipStream_t stream);
+// sums21: the sums of sacn_cyl_terms (icp_sac_normals.h) over the m > 0 listed points for the axis P + s D, the chart coordinates
+// ia < ib and the radius r, each the double-double sum of its terms rounded once.  One workgroup, a fixed order.
+hipError_t launch_sacn_cyl_sums(const float4* cloud, int n, const int* inliers, int m, const double P[3], const double D[3], int ia, int ib, double r,
+                                double* sums21, hipStream_t stream);
+// flags[i] = 1 where i is among the m listed indices, the other way round with `invert`
+hipError_t launch_sacn_list_flags(const int* list, int m, int n, bool invert, int* flags, hipStream_t stream);
+
 // ---- sample-consensus rejector (icp_reject_sac.hip): pcl::registration::CorrespondenceRejectorSampleConsensus over m pairs --------
 // The pairs live in arrays of the stage's own: P, Q (m float4 each) and rank (m ints: the source index of pair r in the chain, r in
 // the call of its own).  A batch is kSacBatch hypotheses t0 .. t0 + 63 (hypothesis t0 + h is lane h's); the counting grid is capped

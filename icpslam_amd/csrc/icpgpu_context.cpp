@@ -685,7 +685,7 @@ int icpgpu_destroy(icpgpu_ctx* c) {
     release(*b);
   for (DeviceBuf* b : {&c->segment.start, &c->segment.list, &c->segment.seg_of, &c->segment.first, &c->segment.partials, &c->segment.box_partials, &c->segment.records})
     release(*b);
-  for (DeviceBuf* b : {&c->sac.batch, &c->sac.ints, &c->sac.sums}) release(*b);
+  for (DeviceBuf* b : {&c->sac.batch, &c->sac.ints, &c->sac.sums, &c->sac.normals, &c->sac.nbatch}) release(*b);
   for (DeviceBuf* b : {&c->rsac.P, &c->rsac.Q, &c->rsac.rank, &c->rsac.source, &c->rsac.target, &c->rsac.iq, &c->rsac.im, &c->rsac.models,
                        &c->rsac.batch, &c->rsac.sums, &c->rsac.ints})
     release(*b);

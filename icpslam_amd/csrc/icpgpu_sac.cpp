@@ -8,17 +8,17 @@
 #include "icp_jacobi3.h"
 
 namespace icpgpu_impl {
-namespace {
 
+// (both shared with the segmentation from normals, icpgpu_sac_normals.cpp: declared in icp_ctx.h)
 // the smallest float32 that is not below t (t >= 0, finite): for every float32 f, f < it <=> (double)f < t
-float threshold_image(double t) {
+float sac_threshold_image(double t) {
   float f = (float)t;
   if ((double)f < t) f = std::nextafterf(f, INFINITY);
   return f;
 }
 
 // the refinement's host half: the nine sums about K over m inliers -> the refined coefficients (rule: include/icpgpu.h)
-void refine_plane(const double S[9], const double K[3], int m, const float unrefined[4], float out[4]) {
+void sac_refine_plane(const double S[9], const double K[3], int m, const float unrefined[4], float out[4]) {
   const double dm = (double)m;
   const double mx = S[6] / dm, my = S[7] / dm, mz = S[8] / dm;
   double a[3][3], V[3][3];
@@ -40,7 +40,6 @@ void refine_plane(const double S[9], const double K[3], int m, const float unref
   out[3] = (float)-(((double)nx * cx + (double)ny * cy) + (double)nz * cz);
 }
 
-}  // namespace
 }  // namespace icpgpu_impl
 
 extern "C" {
@@ -52,6 +51,7 @@ int icpgpu_sac_plane_segmentation(icpgpu_ctx* c, double distance_threshold, int 
   auto& S = c->search;
   auto& K = c->sac;
   K.have = false;
+  K.model = 0;  // (a plane result: icpgpu_sac_normals.cpp sets its own)
   if (coeff4) coeff4[0] = coeff4[1] = coeff4[2] = coeff4[3] = 0.f;
   if (n_inliers) *n_inliers = 0;
   if (iterations) *iterations = 0;
@@ -76,7 +76,7 @@ int icpgpu_sac_plane_segmentation(icpgpu_ctx* c, double distance_threshold, int 
 
   const size_t n = S.n;
   const int ni = (int)n;
-  const float thr = threshold_image(distance_threshold);
+  const float thr = sac_threshold_image(distance_threshold);
   K.n = n;
   K.thr = thr;
   K.found = 0;
@@ -143,7 +143,7 @@ int icpgpu_sac_plane_segmentation(icpgpu_ctx* c, double distance_threshold, int 
       if ((rc = copy_to_host(c, sums, K.sums.ptr, sizeof sums))) return rc;
       ++K.waits;
       for (int a = 0; a < 9; ++a) K.moments[a] = sums[a];
-      refine_plane(sums, sums + 9, best_count, K.coeff_unrefined, K.coeff);
+      sac_refine_plane(sums, sums + 9, best_count, K.coeff_unrefined, K.coeff);
       HIP_TRY(c, launch_sac_select(S.cloud.data(), ni, K.coeff, thr, C.flags.as<int>(), C.pos.as<int>(), C.scan.as<int>(), C.kept.as<int>(),
                                    K.ints.as<int>(), c->stream));
       if ((rc = fetch_ints(c, K.ints.as<int>(), 1, &m))) return rc;
@@ -165,6 +165,7 @@ int icpgpu_sac_fetch(icpgpu_ctx* c, size_t capacity_inliers, size_t capacity_cou
   ENTER(c);
   const auto& K = c->sac;
   if (!K.have) return fail(c, ICPGPU_ERR_INVALID_ARG, "sac_fetch: no result (icpgpu_sac_plane_segmentation)");
+  if (K.model != 0) return fail(c, ICPGPU_ERR_INVALID_ARG, "sac_fetch: the last segmentation is from normals (icpgpu_sac_normals_fetch)");
   if ((inliers && K.n_inliers > capacity_inliers) || (counts && K.counts.size() > capacity_counts))
     return fail(c, ICPGPU_ERR_INVALID_ARG, "sac_fetch: %zu inliers and %zu counts, room for %zu and %zu", K.n_inliers, K.counts.size(), capacity_inliers,
                 capacity_counts);
@@ -213,7 +214,10 @@ int sac_extract(icpgpu_ctx* c, int negative, float* out_xyzw, const float** view
   if ((rc = ensure(c, K.ints, 4 * sizeof(int)))) return rc;
   if ((rc = ensure_stage(c, want * sizeof(float4), /*any_size=*/true))) return rc;
   int* d_count = K.ints.as<int>() + 1;
-  HIP_TRY(c, launch_sac_flags(S.cloud.data(), ni, K.coeff, K.thr, K.found != 0, negative != 0, C.flags.as<int>(), c->stream));
+  if (K.model != 0)  // (a result from normals: its kept inlier list says which points)
+    HIP_TRY(c, launch_sacn_list_flags(K.sel.kept.as<int>(), (int)K.n_inliers, ni, negative != 0, C.flags.as<int>(), c->stream));
+  else
+    HIP_TRY(c, launch_sac_flags(S.cloud.data(), ni, K.coeff, K.thr, K.found != 0, negative != 0, C.flags.as<int>(), c->stream));
   HIP_TRY(c, launch_compact(C.flags.as<int>(), ni, C.pos.as<int>(), C.scan.as<int>(), C.kept.as<int>(), d_count, S.cloud.data(),
                             static_cast<float4*>(c->h_stage_dev), c->stream));
   int m = 0;

@@ -1095,6 +1095,66 @@ class Context:
         self._check(self._L.icpgpu_sac_stats(self._h, C.byref(w)))
         return int(w.value)
 
+    # segmentation from normals (pcl::SACSegmentationFromNormals; rules: include/icpgpu.h) --------------------------------------
+    def sac_segmentation_from_normals_raw(self, model: int, normals, distance_threshold: float, normal_distance_weight: float = 0.1,
+                                          radius_min: float = 0.0, radius_max: float = 0.0, max_iterations: int = 50, probability: float = 0.99,
+                                          seed: int = 0, optimize_coefficients: bool = True, axis=None, eps_angle: float = 0.0) -> tuple:
+        """One icpgpu_sac_segmentation_from_normals call: (rc, coefficients (7,) float32, n_coeff, n_inliers, iterations, found); the
+        result stays in the context.  normals: (n, 4) float32 rows (nx, ny, nz, curvature) of the search cloud, or None (NULL)."""
+        coeff = np.full(7, -2, np.float32)
+        n_in, it, found, n_coeff = C.c_size_t(), C.c_int32(), C.c_int32(), C.c_int32()
+        ax = None if axis is None else (C.c_double * 3)(*[float(v) for v in axis])
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float32)
+        rc = self._L.icpgpu_sac_segmentation_from_normals(self._h, int(model), None if nrm is None else _fp(nrm), float(distance_threshold),
+                                                          float(normal_distance_weight), float(radius_min), float(radius_max), int(max_iterations),
+                                                          float(probability), int(seed) & (2**64 - 1), int(bool(optimize_coefficients)), ax,
+                                                          float(eps_angle), _fp(coeff), C.byref(n_coeff), C.byref(n_in), C.byref(it), C.byref(found))
+        self._sac_last = (int(n_in.value), int(it.value))
+        return rc, coeff, int(n_coeff.value), int(n_in.value), int(it.value), int(found.value)
+
+    def sac_normals_fetch_raw(self, capacity_inliers: int, capacity_counts: int) -> tuple:
+        """One icpgpu_sac_normals_fetch call into arrays pre-filled with -2: (rc, dict of everything the fetch hands out)."""
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        inliers = np.full(capacity_inliers, -2, np.int32)
+        counts = np.full(capacity_counts, -2, np.int32)
+        sample = np.full(3, -2, np.int32)
+        best_t, n_unref, passes, stop = C.c_int32(-2), C.c_size_t(0), C.c_int32(-2), C.c_int32(-2)
+        coeff = np.full(7, -2, np.float32)
+        moments = np.full(9, -2, np.float64)
+        sums = np.full((_lib.SAC_CYLINDER_ITERATIONS, 21), -2, np.float64)
+        rc = self._L.icpgpu_sac_normals_fetch(self._h, int(capacity_inliers), int(capacity_counts), inliers.ctypes.data_as(ip),
+                                              counts.ctypes.data_as(ip), sample.ctypes.data_as(ip), C.byref(best_t), _fp(coeff), C.byref(n_unref),
+                                              moments.ctypes.data_as(dp), sums.ctypes.data_as(dp), C.byref(passes), C.byref(stop))
+        return rc, {"inliers": inliers, "counts": counts, "sample": sample, "best_t": int(best_t.value), "coeff_unrefined": coeff,
+                    "n_unrefined": int(n_unref.value), "moments": moments, "cylinder_sums": sums, "cylinder_passes": int(passes.value),
+                    "cylinder_stop": int(stop.value)}
+
+    def sac_segmentation_from_normals(self, model: int, normals, distance_threshold: float, normal_distance_weight: float = 0.1,
+                                      radius_min: float = 0.0, radius_max: float = 0.0, max_iterations: int = 50, probability: float = 0.99,
+                                      seed: int = 0, optimize_coefficients: bool = True, axis=None, eps_angle: float = 0.0) -> tuple:
+        """(inliers (m,) int32 ascending, coefficients (4,) or (7,) float32, iterations, found) of the search cloud's dominant
+        normal-aware plane (SACMODEL_NORMAL_PLANE) or cylinder (SACMODEL_CYLINDER: point on the axis, direction, radius)."""
+        rc, coeff, n_coeff, n_in, it, found = self.sac_segmentation_from_normals_raw(model, normals, distance_threshold, normal_distance_weight,
+                                                                                     radius_min, radius_max, max_iterations, probability, seed,
+                                                                                     optimize_coefficients, axis, eps_angle)
+        self._check(rc)
+        return self.sac_normals_fetch(n_in, it)["inliers"], coeff[:n_coeff].copy(), it, found
+
+    def sac_normals_fetch(self, n_inliers: int | None = None, n_counts: int | None = None) -> dict:
+        """Everything icpgpu_sac_normals_fetch hands out of the last segmentation from normals.  Sizes that are not given are the
+        last call's."""
+        n_inliers = self._sac_last[0] if n_inliers is None else n_inliers
+        n_counts = self._sac_last[1] if n_counts is None else n_counts
+        rc, out = self.sac_normals_fetch_raw(n_inliers, n_counts)
+        self._check(rc)
+        return out
+
+    def sac_normals_host_waits(self) -> int:
+        """The host waits of the last segmentation from normals (icpgpu_sac_normals_stats)."""
+        w = C.c_int32()
+        self._check(self._L.icpgpu_sac_normals_stats(self._h, C.byref(w)))
+        return int(w.value)
+
     # ground filter (pcl::applyMorphologicalOperator, pcl::ProgressiveMorphologicalFilter; rules: include/icpgpu.h) --------------
     def morphological_operator_raw(self, resolution: float, op: int) -> tuple:
         """One icpgpu_morphological_operator call: (rc, z (n,) float32, pre-filled with -2)."""
@@ -2263,6 +2323,123 @@ class SACSegmentation:
         if not found:
             return np.empty(0, np.int32), np.empty(0, np.float32)
         return inliers, coeff
+
+
+class SACSegmentationFromNormals:
+    """pcl::SACSegmentationFromNormals<PointXYZ, Normal>-shaped front end (include/icpgpu.h, "segmentation from normals"):
+    setInputCloud, setInputNormals ((n, 4) rows nx, ny, nz, curvature: NormalEstimation's output), setModelType
+    (SACMODEL_NORMAL_PLANE, SACMODEL_CYLINDER), setMethodType (SAC_RANSAC: anything else raises), setDistanceThreshold,
+    setNormalDistanceWeight, setRadiusLimits, setMaxIterations, setProbability, setOptimizeCoefficients, setAxis, setEpsAngle, our
+    own setSeed, and segment() -> (inliers int32 ascending, coefficients (4,) or (7,) float32; both empty when no model was found).
+    The defaults are PCL's (threshold 0, weight 0.1, limits 0 / 0, 50 iterations, probability 0.99, optimize true).  An axis of zero
+    length (the default) means none, as in PCL.  After a segment, extractCloud(negative) is pcl::ExtractIndices over it."""
+
+    def __init__(self, device_id: int = 0):
+        self._ctx = Context(device_id)
+        self._input = None
+        self._normals = None
+        self._model = _lib.SACMODEL_NORMAL_PLANE
+        self._threshold = 0.0
+        self._weight = 0.1
+        self._radius = (0.0, 0.0)
+        self._max_iterations = 50
+        self._probability = 0.99
+        self._optimize = True
+        self._axis = (0.0, 0.0, 0.0)
+        self._eps_angle = 0.0
+        self._seed = 0
+        self.iterations = 0
+
+    def setInputCloud(self, cloud):
+        self._input = _as_cloud(cloud).copy()
+
+    def setInputNormals(self, normals):
+        self._normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 4).copy()
+
+    def setModelType(self, model: int):
+        if model not in (_lib.SACMODEL_NORMAL_PLANE, _lib.SACMODEL_CYLINDER):
+            raise IcpGpuError(_lib.ERR_UNSUPPORTED, "setModelType: SACMODEL_NORMAL_PLANE or SACMODEL_CYLINDER")
+        self._model = int(model)
+
+    def getModelType(self) -> int:
+        return self._model
+
+    def setMethodType(self, method: int):
+        if method != _lib.SAC_RANSAC:
+            raise IcpGpuError(_lib.ERR_UNSUPPORTED, "setMethodType: SAC_RANSAC is the only method")
+
+    def getMethodType(self) -> int:
+        return _lib.SAC_RANSAC
+
+    def setDistanceThreshold(self, threshold: float):
+        self._threshold = float(threshold)
+
+    def getDistanceThreshold(self) -> float:
+        return self._threshold
+
+    def setNormalDistanceWeight(self, weight: float):
+        self._weight = float(weight)
+
+    def getNormalDistanceWeight(self) -> float:
+        return self._weight
+
+    def setRadiusLimits(self, radius_min: float, radius_max: float):
+        self._radius = (float(radius_min), float(radius_max))
+
+    def getRadiusLimits(self) -> tuple:
+        return self._radius
+
+    def setMaxIterations(self, max_iterations: int):
+        self._max_iterations = int(max_iterations)
+
+    def getMaxIterations(self) -> int:
+        return self._max_iterations
+
+    def setProbability(self, probability: float):
+        self._probability = float(probability)
+
+    def getProbability(self) -> float:
+        return self._probability
+
+    def setOptimizeCoefficients(self, optimize: bool):
+        self._optimize = bool(optimize)
+
+    def getOptimizeCoefficients(self) -> bool:
+        return self._optimize
+
+    def setAxis(self, axis):
+        self._axis = tuple(float(v) for v in np.asarray(axis, np.float64).reshape(3))
+
+    def getAxis(self) -> tuple:
+        return self._axis
+
+    def setEpsAngle(self, eps_angle: float):
+        self._eps_angle = float(eps_angle)
+
+    def getEpsAngle(self) -> float:
+        return self._eps_angle
+
+    def setSeed(self, seed: int):
+        """NOT a PCL method: the counter-based generator's seed (PCL seeds rand() with a constant)."""
+        self._seed = int(seed)
+
+    def segment(self) -> tuple:
+        if self._input is None or self._normals is None:
+            raise IcpGpuError(_lib.ERR_NO_INPUT, "segment: setInputCloud and setInputNormals first")
+        if self._normals.shape[0] != self._input.shape[0]:
+            raise IcpGpuError(_lib.ERR_INVALID_ARG, "segment: %d normals for %d points" % (self._normals.shape[0], self._input.shape[0]))
+        self._ctx.search_set_input(self._input)
+        axis = self._axis if self._model == _lib.SACMODEL_CYLINDER and any(v != 0.0 for v in self._axis) else None
+        inliers, coeff, self.iterations, found = self._ctx.sac_segmentation_from_normals(
+            self._model, self._normals, self._threshold, self._weight, self._radius[0], self._radius[1], self._max_iterations, self._probability,
+            self._seed, self._optimize, axis, self._eps_angle)
+        if not found:
+            return np.empty(0, np.int32), np.empty(0, np.float32)
+        return inliers, coeff
+
+    def extractCloud(self, negative: bool = False) -> np.ndarray:
+        """NOT a PCL method: the input's inliers (negative: the others) of the last segment(), in cloud order."""
+        return self._ctx.sac_extract(negative)
 
 
 class ProgressiveMorphologicalFilter:

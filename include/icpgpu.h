@@ -57,7 +57,8 @@ extern "C" {
  * icpgpu_radius_outlier_removal, their _view forms, icpgpu_outlier_stats, icpgpu_outlier_fetch, and the neighbour search --
  * icpgpu_search_set_input, icpgpu_search_size, icpgpu_search_knn, icpgpu_search_radius, and normal estimation --
  * icpgpu_normal_estimation, and euclidean clustering -- icpgpu_euclidean_cluster_extraction, icpgpu_cluster_fetch, and region growing -- icpgpu_region_growing, icpgpu_region_fetch, and segment moments -- icpgpu_segment_moments, icpgpu_segment_stats, and plane segmentation --
- * icpgpu_sac_plane_segmentation, icpgpu_sac_fetch, icpgpu_sac_stats, icpgpu_sac_extract, icpgpu_sac_extract_view, and the ground filter -- icpgpu_morphological_operator,
+ * icpgpu_sac_plane_segmentation, icpgpu_sac_fetch, icpgpu_sac_stats, icpgpu_sac_extract, icpgpu_sac_extract_view, and segmentation from normals --
+ * icpgpu_sac_segmentation_from_normals, icpgpu_sac_normals_fetch, icpgpu_sac_normals_stats, and the ground filter -- icpgpu_morphological_operator,
  * icpgpu_progressive_morphological_filter, icpgpu_pmf_fetch, icpgpu_pmf_stats, icpgpu_pmf_extract, icpgpu_pmf_extract_view, and ISS keypoints --
  * icpgpu_iss_keypoints, icpgpu_iss_fetch, icpgpu_iss_stats, icpgpu_iss_keypoints_border, icpgpu_iss_fetch_border, and boundary
  * estimation -- icpgpu_boundary_estimation, and moving least squares -- icpgpu_moving_least_squares, icpgpu_mls_fetch, icpgpu_mls_stats, and fast point feature histograms -- icpgpu_fpfh_estimation, and the symmetric point-to-plane objective with the surface-normal rejector -- icpgpu_set_source_normals,
@@ -1235,7 +1236,7 @@ int icpgpu_segment_stats(const icpgpu_ctx* ctx, int32_t* host_waits);
  * eps_angle that is not finite or is negative; a null coeff4, n_inliers, iterations or found; a fetch or an extract without a result
  * (none computed, the last call refused, or the search cloud replaced since); a null n_out or view pointer.  max_iterations = 0,
  * fewer than three finite points, a threshold of 0 and an empty cloud are all ICPGPU_OK with no model.
- * Not provided: models other than planes, SAC_LMEDS / MSAC, setIndices, normals-based plane models.
+ * Not provided: SAC_LMEDS / MSAC, setIndices; the normal-aware plane and the cylinder are the next section's.
  * ISOLATION.  The result depends on the search cloud and the arguments alone; the call needs no grid and works
  * on a cloud the grid refuses.  It leaves the source, the target, every grid, the covariances, the cached normals, the NDT cells, the
  * filters' results, the search cloud and a clustering result as they were; an unfetched clustering result survives a segmentation and
@@ -1251,6 +1252,103 @@ int icpgpu_sac_fetch(icpgpu_ctx* ctx, size_t capacity_inliers, size_t capacity_c
 int icpgpu_sac_stats(const icpgpu_ctx* ctx, int32_t* host_waits);
 int icpgpu_sac_extract(icpgpu_ctx* ctx, int negative, float* out_xyzw, size_t* n_out);
 int icpgpu_sac_extract_view(icpgpu_ctx* ctx, int negative, const float** view_xyzw, size_t* n_out);
+
+/* ---- segmentation from normals (added under 1.2) -------------------------------------------------------------------- */
+/* replaces pcl::SACSegmentationFromNormals<PointXYZ, Normal> with SACMODEL_NORMAL_PLANE or SACMODEL_CYLINDER and SAC_RANSAC --
+ * setInputCloud, setInputNormals, setDistanceThreshold, setNormalDistanceWeight, setRadiusLimits, setMaxIterations, setProbability,
+ * setOptimizeCoefficients, setAxis, setEpsAngle, segment: a plane that does not take in the foot of a wall, and then the poles,
+ * trunks and pipes of what remains.  The call works on the context's SEARCH CLOUD and on normals_nxyzc, n rows (nx, ny, nz,
+ * curvature) for its n points -- icpgpu_normal_estimation's output as it is.  Parity with PCL binaries is unpinned;
+ * tests/sac_normals_restated.py is what the kernels are compared with, bit for bit.  Everything the plane section states holds
+ * here unless this section says otherwise; every float32 and float64 operation below is rounded on its own, and fmaf is the only
+ * fused one.
+ * SAMPLES.  The plane section's generator.  NORMAL_PLANE draws three indices with the plane's counter 3 t + c + 1: with the same
+ * seed it proposes the triples of icpgpu_sac_plane_segmentation.  CYLINDER draws two with the counter 2 t + c + 1, c = 0, 1.  A
+ * hypothesis is INVALID when two indices are equal, a sampled point is not finite, for the cylinder a sampled normal's x, y or z is
+ * not finite, or the model below is degenerate.  INVALID counts as an iteration (count = -1).
+ * NORMAL_PLANE MODEL.  The plane section's MODEL, operation for operation; four coefficients.  No axis: axis3 != NULL is refused.
+ * CYLINDER MODEL.  Seven coefficients (A, dir, r): a point on the axis, the unit direction, the radius.  With (p1, n1), (p2, n2) the
+ * two samples and their normals, in float32: w = p1 - p2; a = (n1.x n1.x + n1.y n1.y) + n1.z n1.z, and in the same order b = n1 . n2,
+ * c = n2 . n2, d = n1 . w, e = n2 . w; den = a c - b b; sc = (b e - c d) / den, tc = (a e - b d) / den; A = p1 + sc n1, B = p2 + tc n2
+ * (a product and a sum per component): the points of closest approach of the two normal lines, PCL's construction (DEVIATION: PCL
+ * offsets the first line's origin by n1, which moves A along its line and nothing else).  u = B - A, l2 = (u.x u.x + u.y u.y) +
+ * u.z u.z, l = sqrtf(l2), dir = u / l (a division per component); v = p1 - A, x = v x dir (components a b - c d),
+ * r = sqrtf((x.x x.x + x.y x.y) + x.z x.z).  INVALID when den <= 0 or den is not finite (parallel lines); when l2 == 0 or l2 is not
+ * finite (the closest points coincide: samples on one cross-section); when a component of A or r is not finite; unless radius_min =
+ * radius_max = 0, when (double)r < radius_min or (double)r > radius_max; with axis3 != NULL, the axis normalised as the plane
+ * section's, when |(a.x dir.x + a.y dir.y) + a.z dir.z| < cos(eps_angle) in double.  DEVIATION: each of these is an exact comparison
+ * and not one of PCL's tolerances.
+ * THE ANGLE (icpslam_amd/csrc/icp_angle.h).  DEVIATION: PCL takes acos of a normalised dot product, which is portable neither across
+ * C libraries nor onto the device.  For a normal m and a direction g, in float32: x = m x g, y = sqrtf((x.x x.x + x.y x.y) + x.z x.z),
+ * X = fabsf((m.x g.x + m.y g.y) + m.z g.z), theta = A(y, X), the angle between the two lines folded into [0, pi/2]:
+ *     A(y, X) = 0 when y == 0;  P(y / X) when y <= X;  H - P(X / y) when y > X, H = 0x1.921fb6p+0f, the float32 image of pi / 2
+ *     P(t) = fmaf(t s, R, t), s = t t, R = C8, then R = fmaf(R, s, Ck) for k = 7 .. 0, with
+ *     C0 .. C8 = -0x1.55551ep-2f, 0x1.998bbcp-3f, -0x1.23e71cp-3f, 0x1.be6df6p-4f, -0x1.525702p-4f, 0x1.c7f87cp-5f, -0x1.db5118p-6f,
+ *                0x1.414704p-7f, -0x1.97ba58p-10f
+ * so theta is exactly 0 for parallel and exactly H for perpendicular directions.  |A(y, X) - atan2(y, X)| <= 2^-22 for finite
+ * arguments that are not both 0 (2 ulp of pi / 2 asserted, 1.31 measured: tests/test_sac_normals_host.py).  Neither m nor g is
+ * normalised: the angle does not depend on their lengths.  A NaN that an overflow makes here fails the inlier test.
+ * DISTANCE.  W = (float)normal_distance_weight.  For a point q with normal row (m, c): NORMAL_PLANE: d_e = fabsf(s) with the plane
+ * section's s, g = the plane's normal, w = W (1 - c) (PCL's curvature weighting).  CYLINDER: v = q - A, x = v x dir, dist =
+ * sqrtf((x.x x.x + x.y x.y) + x.z x.z), d_e = fabsf(dist - r); t = (v.x dir.x + v.y dir.y) + v.z dir.z, g = v - t dir (a product and
+ * a difference per component), w = W.  val = w theta + (1 - w) d_e, evaluated as (w * theta) + ((1 - w) * d_e); q is an inlier iff
+ * (double)val < distance_threshold, strict.  A point that is not finite, a normal row with a non-finite x, y, z or curvature, and
+ * for the cylinder a g that is (0, 0, 0) (a point on the axis) are never inliers.  With W = 0 and finite normal rows whose
+ * products do not overflow, NORMAL_PLANE is icpgpu_sac_plane_segmentation byte for byte.
+ * LOOP.  The plane section's LOOP; for the cylinder p = 1 - w w, the sample size being 2.
+ * REFINEMENT (optimize_coefficients != 0).  NORMAL_PLANE, with at least 3 inliers: the plane section's REFINEMENT (moments9, the
+ * Jacobi, the sign rule), then the inliers are selected again under this section's DISTANCE.  CYLINDER, with at least 5 inliers --
+ * DEVIATION: PCL runs Eigen's Levenberg-Marquardt; this is a Gauss-Newton on rho_q = dist(q, axis) - r over the unrefined inliers
+ * in a five-parameter chart.  e = the coordinate with the largest |dir_e| of the unrefined model, the lowest index among equals;
+ * ia < ib the other two; K = the best sample's first point.  The axis is P + s D with P_e = K_e, D_e = 1 and the parameters p =
+ * (P_ia, P_ib, D_ia, D_ib, r), started in double from the unrefined coefficients: D_i = dir_i / dir_e, P_i = A_i + ((K_e - A_e) /
+ * dir_e) dir_i, r.  A PASS at p is one device pass over the inliers giving 21 sums: per inlier, in float64, v = (double)q - P,
+ * c = v x D, cn = sqrt((c.x c.x + c.y c.y) + c.z c.z), L2 = (D.x D.x + D.y D.y) + D.z D.z, L = sqrt(L2); with cn == 0: rho = -r,
+ * J = (0, 0, 0, 0, -1); else dist = cn / L, rho = dist - r, den = cn L, u = D x c, w = c x v, JP_j = -u_j / den, JD_j = w_j / den -
+ * (dist D_j) / L2, J = (JP_ia, JP_ib, JD_ia, JD_ib, -1); the terms are J_i J_j for i <= j row by row (15), J_i rho (5), rho rho.
+ * Each sum is accumulated in double-double in a fixed order and rounded once: within 1e-12 of the sum of its terms' magnitudes
+ * from the exact sum.  Pass 0 is taken at the start.  Then, while fewer than ICPGPU_SAC_CYLINDER_ITERATIONS passes were taken: the
+ * host solves (J^T J) delta = -J^T rho by Cholesky (L L^T, column by column, each inner sum subtracted term by term in index
+ * order; forward then backward substitution) -- a pivot that is not > 0 stops (STOP_CHOLESKY); a non-finite p + delta stops
+ * (STOP_NOT_FINITE); max |delta_i| <= 1e-12 (1 + max |p_i|) stops (STOP_SMALL_STEP); otherwise a pass is taken at p + delta, and the
+ * step is kept only if that pass's sum of rho rho is strictly smaller -- if not, p stays and the loop stops (STOP_NO_DECREASE).
+ * Reaching the pass limit is STOP_PASSES.  So the final sum of squares is never above the unrefined one.  The refined
+ * coefficients: A = (float)P, dir = (float)(sgn D / sqrt((D.x D.x + D.y D.y) + D.z D.z)) with sgn = -1 when the unrefined dir_e < 0,
+ * r = (float)fabs(r).  Neither the radius limits nor the axis are validated again.  Then the inliers are selected again.
+ * OUTPUT.  As the plane section's.  n_coeff is 4 or 7 (0 without a model), the unused entries of coeff7 are 0.
+ * icpgpu_sac_normals_fetch copies out the inliers, count[0 .. iterations), the best sample (the third entry -1 for a cylinder) and
+ * t, the unrefined coefficients and inlier count, moments9 (NORMAL_PLANE's refinement, else zeros), cylinder_sums (21 per pass,
+ * room for 21 * ICPGPU_SAC_CYLINDER_ITERATIONS doubles, zeros beyond the passes taken), the number of passes and the stop reason (0:
+ * no cylinder refinement ran).  Any output may be NULL; capacities as icpgpu_sac_fetch.  The result is "the last segmentation":
+ * icpgpu_sac_extract and icpgpu_sac_extract_view work on it, icpgpu_sac_fetch refuses it, and icpgpu_sac_normals_fetch refuses a
+ * plane segmentation's result (ICPGPU_ERR_INVALID_ARG, nothing written).  icpgpu_sac_normals_stats: the host waits of the last call
+ * -- one per batch of 64 hypotheses entered; NORMAL_PLANE's refinement two more; the cylinder's one per pass and one more.
+ * ICPGPU_ERR_INVALID_ARG (nothing written, a previous segmentation result gone): every refusal of the plane call; a model that is
+ * neither of the two; null normals; a normal_distance_weight outside [0, 1] or not finite; radius limits that are negative, not
+ * finite, or radius_max < radius_min unless both are 0; an axis with NORMAL_PLANE; with CYLINDER the plane call's axis refusals.
+ * An empty cloud, max_iterations = 0, a threshold of 0 and fewer finite points than the sample size are ICPGPU_OK with no model.
+ * Not provided: the other models, SAC_LMEDS / MSAC, setIndices.
+ * ISOLATION.  As the plane section's: the result depends on the search cloud, the normals and the arguments alone, lives in the
+ * segmentation's own buffers (the caller's normals are copied there), needs no grid, and leaves everything else in the context as
+ * it was.  It replaces a plane segmentation's result and is replaced by one; icpgpu_search_set_input drops it. */
+#define ICPGPU_SACMODEL_CYLINDER 5       /* pcl::SacModel's values (PCL 1.8 model_types.h) */
+#define ICPGPU_SACMODEL_NORMAL_PLANE 11
+#define ICPGPU_SAC_CYLINDER_ITERATIONS 10
+#define ICPGPU_SAC_STOP_PASSES 1
+#define ICPGPU_SAC_STOP_CHOLESKY 2
+#define ICPGPU_SAC_STOP_NOT_FINITE 3
+#define ICPGPU_SAC_STOP_SMALL_STEP 4
+#define ICPGPU_SAC_STOP_NO_DECREASE 5
+int icpgpu_sac_segmentation_from_normals(icpgpu_ctx* ctx, int model, const float* normals_nxyzc /* n float4, the search cloud's */,
+                                         double distance_threshold, double normal_distance_weight, double radius_min, double radius_max,
+                                         int max_iterations, double probability, uint64_t seed, int optimize_coefficients,
+                                         const double* axis3 /* may be NULL */, double eps_angle, float coeff7[7], int32_t* n_coeff,
+                                         size_t* n_inliers, int32_t* iterations, int32_t* found);
+int icpgpu_sac_normals_fetch(icpgpu_ctx* ctx, size_t capacity_inliers, size_t capacity_counts, int32_t* inliers /* n_inliers */,
+                             int32_t* counts /* iterations */, int32_t best_sample3[3], int32_t* best_t, float coeff_unrefined7[7],
+                             size_t* n_unrefined_inliers, double moments9[9], double* cylinder_sums /* 21 * ICPGPU_SAC_CYLINDER_ITERATIONS */,
+                             int32_t* cylinder_passes, int32_t* cylinder_stop);
+int icpgpu_sac_normals_stats(const icpgpu_ctx* ctx, int32_t* host_waits);
 
 /* ---- ground filter (added under 1.2) -------------------------------------------------------------------------------- */
 /* replaces pcl::applyMorphologicalOperator<PointXYZ> and pcl::ProgressiveMorphologicalFilter<PointXYZ> -- setInputCloud,

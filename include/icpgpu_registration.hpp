@@ -1745,6 +1745,101 @@ class SACSegmentation {
   uint64_t seed_ = 0;
 };
 
+// pcl::SACSegmentationFromNormals<PointT, PointNT>-shaped front end (rules and deviations: include/icpgpu.h, "segmentation from
+// normals") -- the normal-aware ground plane, then the poles and pipes of what remains:
+//   pcl::SACSegmentationFromNormals<pcl::PointXYZ, pcl::Normal> seg;
+//     ->  icpgpu::SACSegmentationFromNormals<pcl::PointCloud<pcl::PointXYZ>, pcl::PointCloud<pcl::Normal>> seg;
+//   seg.setModelType(icpgpu::SACMODEL_CYLINDER); seg.setMethodType(icpgpu::SAC_RANSAC); seg.setNormalDistanceWeight(0.1);
+//   seg.setMaxIterations(10000); seg.setDistanceThreshold(0.05); seg.setRadiusLimits(0, 0.1); seg.setInputCloud(cloud);
+//   seg.setInputNormals(normals); seg.segment(*inliers, *coefficients);
+// The normals are the input cloud's, one per point (any point type with normal_x, normal_y, normal_z, curvature: NormalEstimation's
+// output).  The defaults are PCL's (weight 0.1, limits 0 / 0); an axis of zero length, the default, means none.  The coefficients
+// hold 4 (NORMAL_PLANE) or 7 (CYLINDER: point on the axis, direction, radius) values.
+enum SacModelFromNormals { SACMODEL_CYLINDER = ICPGPU_SACMODEL_CYLINDER, SACMODEL_NORMAL_PLANE = ICPGPU_SACMODEL_NORMAL_PLANE };
+
+template <class CloudT, class NormalCloudT>
+class SACSegmentationFromNormals {
+ public:
+  explicit SACSegmentationFromNormals(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {}
+  template <class CloudPtr>
+  void setInputCloud(const CloudPtr& cloud) { input_ = &*cloud; }
+  template <class NormalsPtr>
+  void setInputNormals(const NormalsPtr& normals) { normals_ = &*normals; }
+  void setModelType(int model) {
+    if (model != SACMODEL_NORMAL_PLANE && model != SACMODEL_CYLINDER)
+      throw std::invalid_argument("icpgpu::SACSegmentationFromNormals: SACMODEL_NORMAL_PLANE or SACMODEL_CYLINDER");
+    model_ = model;
+  }
+  int getModelType() const { return model_; }
+  void setMethodType(int method) {
+    if (method != SAC_RANSAC) throw std::invalid_argument("icpgpu::SACSegmentationFromNormals: SAC_RANSAC is the only method");
+  }
+  int getMethodType() const { return SAC_RANSAC; }
+  void setDistanceThreshold(double threshold) { threshold_ = threshold; }
+  double getDistanceThreshold() const { return threshold_; }
+  void setNormalDistanceWeight(double weight) { weight_ = weight; }
+  double getNormalDistanceWeight() const { return weight_; }
+  void setRadiusLimits(double radius_min, double radius_max) { radius_min_ = radius_min, radius_max_ = radius_max; }
+  void getRadiusLimits(double& radius_min, double& radius_max) const { radius_min = radius_min_, radius_max = radius_max_; }
+  void setMaxIterations(int max_iterations) { max_iterations_ = max_iterations; }
+  int getMaxIterations() const { return max_iterations_; }
+  void setProbability(double probability) { probability_ = probability; }
+  double getProbability() const { return probability_; }
+  void setOptimizeCoefficients(bool optimize) { optimize_ = optimize; }
+  bool getOptimizeCoefficients() const { return optimize_; }
+  template <class Vec3>
+  void setAxis(const Vec3& axis) { axis_[0] = axis[0], axis_[1] = axis[1], axis_[2] = axis[2]; }  // (Eigen::Vector3f, or any [] of three)
+  void setEpsAngle(double eps_angle) { eps_angle_ = eps_angle; }
+  double getEpsAngle() const { return eps_angle_; }
+  void setSeed(uint64_t seed) { seed_ = seed; }  // NOT a PCL method
+  int getIterations() const { return iterations_; }   // NOT a PCL method: the iterations of the last segment()
+  void segment(PointIndices& inliers, ModelCoefficients& coefficients) {
+    inliers.indices.clear();
+    coefficients.values.clear();
+    iterations_ = 0;
+    if (!input_ || !normals_) return;
+    static_assert(sizeof(input_->points[0]) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+    static_assert(sizeof(int) == sizeof(int32_t), "icpgpu: 32-bit int");
+    const std::size_t n = input_->points.size();
+    if (normals_->points.size() != n) return;
+    if (icpgpu_search_set_input(ctx_, n ? reinterpret_cast<const float*>(&input_->points[0]) : nullptr, n) != ICPGPU_OK) return;
+    std::vector<float> nxyzc(4 * n + 4);
+    for (std::size_t i = 0; i < n; ++i) {
+      nxyzc[4 * i] = normals_->points[i].normal_x;
+      nxyzc[4 * i + 1] = normals_->points[i].normal_y;
+      nxyzc[4 * i + 2] = normals_->points[i].normal_z;
+      nxyzc[4 * i + 3] = normals_->points[i].curvature;
+    }
+    const bool axis = model_ == SACMODEL_CYLINDER && (axis_[0] != 0.0 || axis_[1] != 0.0 || axis_[2] != 0.0);
+    float coeff[7];
+    std::size_t n_inliers = 0;
+    int32_t n_coeff = 0, iterations = 0, found = 0;
+    if (icpgpu_sac_segmentation_from_normals(ctx_, model_, &nxyzc[0], threshold_, weight_, radius_min_, radius_max_, max_iterations_, probability_, seed_,
+                                             optimize_ ? 1 : 0, axis ? axis_ : nullptr, eps_angle_, coeff, &n_coeff, &n_inliers, &iterations,
+                                             &found) != ICPGPU_OK)
+      return;
+    iterations_ = iterations;
+    if (!found) return;
+    std::vector<int> indices(n_inliers);
+    if (icpgpu_sac_normals_fetch(ctx_, n_inliers, 0, n_inliers ? reinterpret_cast<int32_t*>(&indices[0]) : nullptr, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr, nullptr) != ICPGPU_OK)
+      return;
+    inliers.indices.swap(indices);
+    coefficients.values.assign(coeff, coeff + n_coeff);
+  }
+
+ private:
+  detail::ContextPtr ctx_holder_;
+  icpgpu_ctx* ctx_;
+  const CloudT* input_ = nullptr;
+  const NormalCloudT* normals_ = nullptr;
+  int model_ = SACMODEL_NORMAL_PLANE, max_iterations_ = 50, iterations_ = 0;
+  double threshold_ = 0.0, weight_ = 0.1, radius_min_ = 0.0, radius_max_ = 0.0, probability_ = 0.99, eps_angle_ = 0.0;
+  double axis_[3] = {0.0, 0.0, 0.0};
+  bool optimize_ = true;
+  uint64_t seed_ = 0;
+};
+
 // (a plain host loop over the caller's indices: nothing here needs the device)
 template <class CloudT>
 class ExtractIndices {
