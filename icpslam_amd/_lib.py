@@ -47,6 +47,9 @@ PMF_MAX_PASSES = 32            # ICPGPU_PMF_MAX_PASSES
 SEGMENTS_HOST, SEGMENTS_CLUSTERS, SEGMENTS_REGIONS = 0, 1, 2   # ICPGPU_SEGMENTS_*
 SEGMENT_OK, SEGMENT_EMPTY = 0, 1                               # ICPGPU_SEGMENT_*
 SEGMENT_CHUNK = 64             # ICPGPU_SEGMENT_CHUNK
+FPS_ONE_WORKGROUP_MAX = 16384  # ICPGPU_FPS_ONE_WORKGROUP_MAX
+SUBSET_PASS_THROUGH, SUBSET_CROP_BOX, SUBSET_UNIFORM_SAMPLING, SUBSET_FARTHEST_POINT_SAMPLING = 1, 2, 3, 4   # ICPGPU_SUBSET_*
+FPS_PATH_ONE, FPS_PATH_MANY = 1, 2                             # ICPGPU_FPS_PATH_*
 STATE_NAMES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE",
                5: "NO_CORRESPONDENCES"}
 
@@ -137,6 +140,9 @@ EXPORTS = [
     "icpgpu_iss_keypoints", "icpgpu_iss_fetch", "icpgpu_iss_stats",
     "icpgpu_boundary_estimation", "icpgpu_iss_keypoints_border", "icpgpu_iss_fetch_border",
     "icpgpu_moving_least_squares", "icpgpu_mls_fetch", "icpgpu_mls_stats",
+    "icpgpu_pass_through", "icpgpu_pass_through_view", "icpgpu_crop_box", "icpgpu_crop_box_view", "icpgpu_crop_box_matrix",
+    "icpgpu_uniform_sampling", "icpgpu_uniform_sampling_view", "icpgpu_farthest_point_sampling", "icpgpu_farthest_point_sampling_view",
+    "icpgpu_subset_fetch", "icpgpu_subset_removed", "icpgpu_subset_stats",
     "icpgpu_sac_plane_segmentation", "icpgpu_sac_fetch", "icpgpu_sac_stats", "icpgpu_sac_extract", "icpgpu_sac_extract_view",
     "icpgpu_sac_segmentation_from_normals", "icpgpu_sac_normals_fetch", "icpgpu_sac_normals_stats",
     "icpgpu_morphological_operator", "icpgpu_progressive_morphological_filter", "icpgpu_pmf_fetch", "icpgpu_pmf_stats", "icpgpu_pmf_extract",
@@ -291,6 +297,18 @@ def load():
     L.icpgpu_scp_align.argtypes = [vp, fp, C.c_size_t, fp, fp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64, fp, szp, fp, ip, fp]
     L.icpgpu_scp_fetch.argtypes = [vp, C.c_size_t, C.c_size_t, ip, ip, ip, fp, ip, dp, fp, ip, ip]
     L.icpgpu_scp_stats.argtypes = [vp, ip, ip, dp]
+    L.icpgpu_pass_through.argtypes = [vp, fp, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_int, fp, szp]
+    L.icpgpu_pass_through_view.argtypes = [vp, fp, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(fp), szp]
+    L.icpgpu_crop_box.argtypes = [vp, fp, C.c_size_t, fp, fp, fp, C.c_int, fp, szp]
+    L.icpgpu_crop_box_view.argtypes = [vp, fp, C.c_size_t, fp, fp, fp, C.c_int, C.POINTER(fp), szp]
+    L.icpgpu_crop_box_matrix.argtypes = [fp, fp, fp, fp]
+    L.icpgpu_uniform_sampling.argtypes = [vp, fp, C.c_size_t, C.c_float, fp, szp]
+    L.icpgpu_uniform_sampling_view.argtypes = [vp, fp, C.c_size_t, C.c_float, C.POINTER(fp), szp]
+    L.icpgpu_farthest_point_sampling.argtypes = [vp, fp, C.c_size_t, C.c_size_t, C.c_int64, fp, szp]
+    L.icpgpu_farthest_point_sampling_view.argtypes = [vp, fp, C.c_size_t, C.c_size_t, C.c_int64, C.POINTER(fp), szp]
+    L.icpgpu_subset_fetch.argtypes = [vp, C.c_size_t, ip, fp, szp, szp]
+    L.icpgpu_subset_removed.argtypes = [vp, C.c_size_t, ip, szp]
+    L.icpgpu_subset_stats.argtypes = [vp, ip, ip, ip, ip]
     pp, lp = C.POINTER(Pose), C.POINTER(C.c_long)
     L.icpgpu_pose_from_matrix.argtypes = [fp, pp]
     L.icpgpu_pose_to_matrix.argtypes = [pp, fp]

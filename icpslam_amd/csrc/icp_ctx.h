@@ -566,6 +566,18 @@ struct icpgpu_ctx {
     std::vector<float> h_points, h_normals;         // the compacted results on the host: n_q slots arrive, n_out reach the caller
     std::vector<int32_t> h_index;
   } mls;
+  // the cropping and sampling filters (icpgpu_sampling.cpp, icp_sampling.hip): the filtered cloud is neither the source, the target, the
+  // outlier filters' nor the search cloud -- its own buffer and scratch, which no other call reads or writes -- and what the observers
+  // (icpgpu_subset_fetch / _removed / _stats) report of the last call; replaced only by the next call of that section
+  struct Subset {
+    Cloud cloud;
+    int kind = 0;  // 0 none (or the last call was refused), else kSubset* (icp_sampling.h)
+    size_t n_in = 0, n_kept = 0;
+    int waits = 0, launches = 0, path = 0;
+    Compaction comp;            // comp.kept: the kept rows (ascending, or in selection order)
+    Compaction rem;             // icpgpu_subset_removed's own
+    DeviceBuf measure, d2_of, cells, best, slot_of, m, slots, ints;
+  } subset;
   std::vector<icpgpu_ctx*> workers;  // align_batch: one sub-context (own stream + scratch) per host worker thread
   DeviceBuf batch_table;             // lock-step batch: the BatchPair table of the group this context leads
   std::atomic<size_t> batch_table_cells{0};   // align_batch: the largest cell table any worker has needed (icpgpu_index.cpp)

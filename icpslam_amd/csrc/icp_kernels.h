@@ -853,4 +853,40 @@ hipError_t launch_morph_unsort(int n, const int* d_count, const float* val, cons
 // flags[i] = 1 where removed_at[i] == -1 (ground), the other way round with `invert`
 hipError_t launch_pmf_flags(const int32_t* removed_at, int n, bool invert, int* flags, hipStream_t stream);
 
+// ---- cropping and sampling filters (icp_sampling.hip): pcl::PassThrough, CropBox, UniformSampling, FarthestPointSampling -------------
+// (arithmetic: icp_sampling.h; every filter ends in flags for launch_compact or in a list of kept rows for launch_subset_gather)
+struct CropRule {  // box = 0: PassThrough over `field` (-1: none) with lo[0] .. hi[0]; box = 1: CropBox over T * p (has_T) or p
+  int box, field, negative, has_T;
+  float lo[3], hi[3];
+  Xform T;
+};
+hipError_t launch_crop_flags(const float4* cloud, int n, const CropRule& rule, int* flags, hipStream_t stream);
+// UniformSampling over the plan's lattice (icp_voxel_plan.h: kVoxelPlanDirect): flags[i] = 1 for the row with the smallest (d2 bits,
+// index) key of its cell, d2_of[i] = the row's d2 to its cell's centre (0 for a non-finite row).  cells (ints), best (64-bit words):
+// uniform_table_slots(n) each; slot_of, d2_of: n.  Three launches whatever the cloud.  n <= kUniformMaxRows.
+struct UniformLattice {
+  float inv, leaf;
+  int minb[3], divb[3];
+};
+static constexpr int kUniformMaxRows = 1 << 30;
+unsigned int uniform_table_slots(int n);
+hipError_t launch_uniform_flags(const float4* cloud, int n, const UniformLattice& L, int* cells, unsigned long long* best, unsigned int* slot_of,
+                                float* d2_of, int* flags, hipStream_t stream);
+// for j < count (*d_count when given, else count_most; the launch is sized by count_most): points[j] = cloud[kept[j]] and
+// measure_out[j] = measure_in[kept[j]], each where given; *n_out = count where given
+hipError_t launch_subset_gather(const int* kept, const int* d_count, int count_most, const float4* cloud, float4* points, const float* measure_in,
+                                float* measure_out, int* n_out, hipStream_t stream);
+// flags[i] = 1 for the n rows except kept[0 .. n_kept): what launch_compact turns into the removed indices
+hipError_t launch_subset_removed_flags(const int* kept, int n_kept, int n, int* flags, hipStream_t stream);
+// FarthestPointSampling from row `first` (finite, inside the cloud; n_samples <= the finite rows: the caller checks both): the
+// selected rows in selection order into kept, each one's d2 to the set selected before it into measure (+inf for the first).
+// launch_fps_one: n <= kFpsOneMax, ONE workgroup and one launch.  launch_fps_many: any n; m (n floats) and slots (2 x
+// kFpsManyBlocksMax 64-bit words) are scratch; 1 + n_samples launches (*launches) over fps_many_blocks(n) workgroups.
+static constexpr int kFpsOneMax = 16384;       // ICPGPU_FPS_ONE_WORKGROUP_MAX: 1024 lanes x 16 rows in registers
+static constexpr int kFpsManyBlocksMax = 1024;  // the many-workgroup shape's grid cap: beyond 2^20 rows a workgroup makes several trips
+int fps_many_blocks(int n);
+hipError_t launch_fps_one(const float4* cloud, int n, int n_samples, int first, int* kept, float* measure, hipStream_t stream);
+hipError_t launch_fps_many(const float4* cloud, int n, int n_samples, int first, float* m, unsigned long long* slots, int* kept, float* measure,
+                           int* launches, hipStream_t stream);
+
 }  // namespace icpgpu

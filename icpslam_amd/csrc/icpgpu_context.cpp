@@ -669,6 +669,10 @@ int icpgpu_destroy(icpgpu_ctx* c) {
                        &c->map.uflags, &c->map.urank, &c->map.uniq_index, &c->map.uniq.buf})
     release(*b);
   for (DeviceBuf* b : {&c->outlier.cloud.buf, &c->outlier.measure, &c->outlier.far, &c->outlier.ints}) release(*b);
+  for (DeviceBuf* b : {&c->subset.cloud.buf, &c->subset.measure, &c->subset.d2_of, &c->subset.cells, &c->subset.best, &c->subset.slot_of, &c->subset.m,
+                       &c->subset.slots, &c->subset.ints})
+    release(*b);
+  for (Compaction* C : {&c->subset.comp, &c->subset.rem}) release(*C);
   for (Compaction* C : {&c->outlier.comp, &c->sac.sel, &c->sac.ext, &c->pmf.sel, &c->pmf.op, &c->pmf.ext, &c->scp.sel, &c->iss.comp, &c->mls.comp}) release(*C);
   for (DeviceBuf* b : {&c->search.cloud.buf, &c->search.queries, &c->search.idx, &c->search.d2, &c->search.n_found, &c->search.far,
                        &c->search.counts, &c->search.longs, &c->search.row_start, &c->search.scratch_start, &c->search.scan,

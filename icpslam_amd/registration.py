@@ -43,6 +43,42 @@ def _colmajor16(T) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(T, dtype=np.float32).reshape(4, 4).T).reshape(16)
 
 
+FLT_MIN, FLT_MAX = float(np.finfo(np.float32).tiny), float(np.finfo(np.float32).max)  # pcl::PassThrough's default limits
+
+
+def crop_box_matrix(transform=None, translation=(0.0, 0.0, 0.0), rotation=(0.0, 0.0, 0.0)) -> np.ndarray:
+    """icpgpu_crop_box_matrix: pcl::CropBox's transform, translation and rotation (rx, ry, rz) as the ONE 4 x 4 float32 matrix
+    Context.crop_box applies to a row before the box test."""
+    L = _lib.load()
+    out = np.zeros(16, np.float32)
+    Tb = None if transform is None else _colmajor16(transform)
+    tr, ro = (np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (translation, rotation))
+    rc = L.icpgpu_crop_box_matrix(None if Tb is None else _fp(Tb), _fp(tr), _fp(ro), _fp(out))
+    if rc != 0:
+        raise IcpGpuError(rc, "icpgpu_crop_box_matrix")
+    return out.reshape(4, 4).T.copy()
+
+
+def seeded_first_row(cloud, seed: int) -> int:
+    """FarthestPointSampling.setSeed's first row: the plane segmentation's generator (splitmix64 of the rule's counter, t = 0, c = 0) over
+    the cloud's n rows, advanced cyclically to the next finite row; -1 when no row is finite."""
+    cloud = _as_cloud(cloud)
+    n = cloud.shape[0]
+    if n == 0:
+        return -1
+    M = (1 << 64) - 1
+    z = (int(seed) + 0x9E3779B97F4A7C15) & M
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M
+    z ^= z >> 31
+    start = ((z >> 32) * n) >> 32
+    finite = np.flatnonzero(np.isfinite(cloud[:, :3]).all(axis=1))
+    if finite.size == 0:
+        return -1
+    at = np.searchsorted(finite, start)
+    return int(finite[at] if at < finite.size else finite[0])
+
+
 class Context:
     """One icpgpu_ctx: one device, one HIP stream, reusable scratch."""
 
@@ -572,6 +608,62 @@ class Context:
         mask = np.ones(n_in.value, bool)
         mask[kept] = False
         return {"measure": measure, "kept": kept, "removed": np.flatnonzero(mask).astype(np.int32)}
+
+    # cropping and sampling filters (pcl::PassThrough / CropBox / UniformSampling / FarthestPointSampling; rules: include/icpgpu.h) ----
+    def pass_through(self, cloud, field: int = -1, lo: float = FLT_MIN, hi: float = FLT_MAX, negative: bool = False, view: bool = False) -> np.ndarray:
+        """The kept rows in input order.  field: 0, 1, 2 = x, y, z; -1 = none (only the non-finite rows go)."""
+        fn = self._L.icpgpu_pass_through_view if view else self._L.icpgpu_pass_through
+        return self._outlier(view, fn, cloud, int(field), float(lo), float(hi), int(bool(negative)))
+
+    def crop_box(self, cloud, min3, max3, T=None, negative: bool = False, view: bool = False) -> np.ndarray:
+        """The kept rows in input order.  T: a 4 x 4 matrix applied to every row before the box test (crop_box_matrix makes PCL's), or None."""
+        fn = self._L.icpgpu_crop_box_view if view else self._L.icpgpu_crop_box
+        mn, mx = (np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (min3, max3))
+        Tb = None if T is None else _colmajor16(T)
+        return self._outlier(view, fn, cloud, _fp(mn), _fp(mx), None if Tb is None else _fp(Tb), int(bool(negative)))
+
+    def uniform_sampling(self, cloud, leaf: float, view: bool = False) -> np.ndarray:
+        """One input row per occupied cell of side `leaf`, the one closest to the cell's centre, in input order."""
+        fn = self._L.icpgpu_uniform_sampling_view if view else self._L.icpgpu_uniform_sampling
+        return self._outlier(view, fn, cloud, float(leaf))
+
+    def farthest_point_sampling(self, cloud, n_samples: int, first_index: int = -1, view: bool = False) -> np.ndarray:
+        """n_samples input rows in selection order, from row first_index (-1: the lowest finite row)."""
+        fn = self._L.icpgpu_farthest_point_sampling_view if view else self._L.icpgpu_farthest_point_sampling
+        return self._outlier(view, fn, cloud, int(n_samples), int(first_index))
+
+    def subset_fetch_raw(self, capacity: int, want=("kept", "measure")) -> tuple:
+        """icpgpu_subset_fetch as it is: (rc, kept, measure, n_in, n_kept) with arrays of `capacity` entries (None where not wanted)."""
+        kept = np.full(capacity, -1, np.int32) if "kept" in want else None
+        measure = np.full(capacity, -1.0, np.float32) if "measure" in want else None
+        n_in, n_kept = C.c_size_t(), C.c_size_t()
+        rc = self._L.icpgpu_subset_fetch(self._h, int(capacity), None if kept is None else kept.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         None if measure is None else _fp(measure), C.byref(n_in), C.byref(n_kept))
+        return rc, kept, measure, int(n_in.value), int(n_kept.value)
+
+    def subset_removed_raw(self, capacity: int, want: bool = True) -> tuple:
+        """icpgpu_subset_removed as it is: (rc, removed, n_removed)."""
+        removed = np.full(capacity, -1, np.int32) if want else None
+        n_removed = C.c_size_t()
+        rc = self._L.icpgpu_subset_removed(self._h, int(capacity), None if removed is None else removed.ctypes.data_as(C.POINTER(C.c_int32)),
+                                           C.byref(n_removed))
+        return rc, removed, int(n_removed.value)
+
+    def subset_fetch(self) -> dict:
+        """The last cropping or sampling call's kept indices (ascending; farthest point sampling: selection order), the removed ones
+        (ascending), one measure per kept row and the input's size."""
+        rc, _, _, n_in, n_kept = self.subset_fetch_raw(0, want=())
+        self._check(rc)
+        rc, kept, measure, _, _ = self.subset_fetch_raw(n_kept)
+        self._check(rc)
+        rc, removed, _ = self.subset_removed_raw(n_in - n_kept)
+        self._check(rc)
+        return {"kept": kept, "removed": removed, "measure": measure, "n_in": n_in}
+
+    def subset_stats(self) -> dict:
+        v = [C.c_int32() for _ in range(4)]
+        self._check(self._L.icpgpu_subset_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("kind", "host_waits", "launches", "path"), (int(x.value) for x in v)))
 
     # neighbour search (pcl::search::KdTree / pcl::KdTreeFLANN; rules: include/icpgpu.h) --------------------------------
     def search_set_input(self, cloud) -> None:
@@ -1550,6 +1642,145 @@ class RadiusOutlierRemoval(_OutlierFilter):
 
     def _run(self, cloud) -> np.ndarray:
         return self._ctx.radius_outlier_removal(cloud, self._radius, self._min_pts, self._negative, view=True)
+
+
+class _SubsetFilter:
+    """What pcl::PassThrough, CropBox, UniformSampling and FarthestPointSampling share here: the input cloud, filter() as the kept
+    rows or (indices=True: PCL's filter(indices)) their indices, and the removed indices."""
+
+    def __init__(self, device_id: int = 0):
+        self._ctx = Context(device_id)
+        self._cloud = np.empty((0, 4), np.float32)
+        self._removed = np.empty(0, np.int32)
+
+    def setInputCloud(self, cloud):
+        self._cloud = _as_cloud(cloud)
+
+    def getRemovedIndices(self) -> np.ndarray:
+        return self._removed
+
+    def _run(self, cloud) -> np.ndarray:
+        raise NotImplementedError
+
+    def filter(self, indices: bool = False) -> np.ndarray:
+        """The filtered cloud (indices: the kept rows' indices); a refused call returns an empty one, as PCL's error path does."""
+        self._removed = np.empty(0, np.int32)
+        try:
+            out = self._run(self._cloud)
+        except IcpGpuError:
+            return np.empty(0, np.int32) if indices else np.empty((0, 4), np.float32)
+        res = self._ctx.subset_fetch()
+        self._removed = res["removed"]
+        return res["kept"] if indices else out
+
+
+class PassThrough(_SubsetFilter):
+    """pcl::PassThrough<PointXYZ> (PCL's defaults: no field, FLT_MIN .. FLT_MAX, not negative)."""
+
+    def __init__(self, device_id: int = 0):
+        super().__init__(device_id)
+        self._field, self._lo, self._hi, self._negative = -1, FLT_MIN, FLT_MAX, False
+
+    def setFilterFieldName(self, name: str):
+        if name not in ("x", "y", "z"):
+            raise ValueError(f"PassThrough: field {name!r} is not one of x, y, z")
+        self._field = "xyz".index(name)
+
+    def getFilterFieldName(self) -> str:
+        return "" if self._field < 0 else "xyz"[self._field]
+
+    def setFilterLimits(self, lo: float, hi: float):
+        self._lo, self._hi = float(lo), float(hi)
+
+    def getFilterLimits(self) -> tuple:
+        return self._lo, self._hi
+
+    def setNegative(self, negative: bool):
+        self._negative = bool(negative)
+
+    def getNegative(self) -> bool:
+        return self._negative
+
+    def _run(self, cloud) -> np.ndarray:
+        return self._ctx.pass_through(cloud, self._field, self._lo, self._hi, self._negative, view=True)
+
+
+class CropBox(_SubsetFilter):
+    """pcl::CropBox<PointXYZ> (PCL's defaults: the box -1 .. 1, no translation, rotation or transform, not negative)."""
+
+    def __init__(self, device_id: int = 0):
+        super().__init__(device_id)
+        self._min, self._max = np.full(3, -1.0, np.float32), np.full(3, 1.0, np.float32)
+        self._translation, self._rotation = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        self._transform = None
+        self._negative = False
+
+    def setMin(self, min_pt):
+        self._min = np.asarray(min_pt, np.float32).reshape(-1)[:3].copy()
+
+    def setMax(self, max_pt):
+        self._max = np.asarray(max_pt, np.float32).reshape(-1)[:3].copy()
+
+    def setTranslation(self, translation):
+        self._translation = np.asarray(translation, np.float32).reshape(3).copy()
+
+    def setRotation(self, rotation):
+        self._rotation = np.asarray(rotation, np.float32).reshape(3).copy()
+
+    def setTransform(self, transform):
+        self._transform = None if transform is None else np.asarray(transform, np.float32).reshape(4, 4).copy()
+
+    def setNegative(self, negative: bool):
+        self._negative = bool(negative)
+
+    def getNegative(self) -> bool:
+        return self._negative
+
+    def _run(self, cloud) -> np.ndarray:
+        plain = self._transform is None and not self._translation.any() and not self._rotation.any()
+        T = None if plain else crop_box_matrix(self._transform, self._translation, self._rotation)
+        return self._ctx.crop_box(cloud, self._min, self._max, T, self._negative, view=True)
+
+
+class UniformSampling(_SubsetFilter):
+    """pcl::UniformSampling<PointXYZ>: setRadiusSearch is the leaf size."""
+
+    def __init__(self, device_id: int = 0):
+        super().__init__(device_id)
+        self._leaf = 0.0
+
+    def setRadiusSearch(self, radius: float):
+        self._leaf = float(radius)
+
+    def getRadiusSearch(self) -> float:
+        return self._leaf
+
+    def _run(self, cloud) -> np.ndarray:
+        return self._ctx.uniform_sampling(cloud, self._leaf, view=True)
+
+
+class FarthestPointSampling(_SubsetFilter):
+    """pcl::FarthestPointSampling<PointXYZ> (PCL 1.12): setSample rows in selection order; setSeed picks the first row
+    (seeded_first_row), not mt19937's."""
+
+    def __init__(self, device_id: int = 0):
+        super().__init__(device_id)
+        self._sample, self._seed = 0, 0
+
+    def setSample(self, sample: int):
+        self._sample = int(sample)
+
+    def getSample(self) -> int:
+        return self._sample
+
+    def setSeed(self, seed: int):
+        self._seed = int(seed)
+
+    def getSeed(self) -> int:
+        return self._seed
+
+    def _run(self, cloud) -> np.ndarray:
+        return self._ctx.farthest_point_sampling(cloud, self._sample, seeded_first_row(cloud, self._seed), view=True)
 
 
 class KdTree:

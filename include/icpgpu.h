@@ -65,6 +65,8 @@ extern "C" {
  * icpgpu_set_p2plane_symmetric, icpgpu_get_p2plane_symmetric, icpgpu_reduce_symmetric_point_to_plane,
  * icpgpu_solve_symmetric_point_to_plane, ICPGPU_REJECT_SURFACE_NORMAL, and the sample-consensus rejector -- ICPGPU_REJECT_SAMPLE_CONSENSUS,
  * icpgpu_set_rejector_sac_seed, icpgpu_get_rejector_sac_seed, icpgpu_correspondence_rejector_sample_consensus, icpgpu_rejector_sac_fetch,
+ * and the cropping and sampling filters -- icpgpu_pass_through, icpgpu_crop_box, icpgpu_crop_box_matrix, icpgpu_uniform_sampling,
+ * icpgpu_farthest_point_sampling, their _view forms, icpgpu_subset_fetch, icpgpu_subset_removed, icpgpu_subset_stats,
  * and the diagnostic icpgpu_sweep_sums (no struct changed); 1.1 icpgpu_align_view, icpgpu_voxel_grid_view (result clouds as views of the pinned staging
  * buffer), icpgpu_profile.voxel_views_direct; 1.0 icpgpu_result.gicp_solver, icpgpu_calibrate, sized entry points; 0.4 icpgpu_params.gicp_inner,
  * icpgpu_profile.gicp_quadratic_solves; 0.3 icpgpu_profile (sources_adopted, gicp_host_solves, gicp_solver_choice). */
@@ -1656,6 +1658,92 @@ int icpgpu_moving_least_squares(icpgpu_ctx* ctx, const float* queries_xyzw /* n_
 int icpgpu_mls_fetch(icpgpu_ctx* ctx, size_t capacity /* >= n_q */, int32_t* status /* n_q */, int32_t* n_neighbours /* n_q */,
                      double* plane7 /* n_q x 7 */, double* coeff10 /* n_q x 10 */);
 int icpgpu_mls_stats(const icpgpu_ctx* ctx, int32_t* host_waits);
+
+/* ---- cropping and sampling filters (added under 1.2) ---------------------------------------------------------------- */
+/* replaces pcl::PassThrough<PointXYZ>, pcl::CropBox<PointXYZ>, pcl::UniformSampling<PointXYZ> (PCL 1.8) and
+ * pcl::FarthestPointSampling<PointXYZ> (PCL 1.12): the filters that keep a SUBSET OF THE INPUT ROWS -- what a LIDAR front end runs
+ * before the voxel filter (range, height, the vehicle's own body) and what picks the points descriptors are computed at.  The rules
+ * below restate PCL; parity with PCL binaries is unpinned (tests/sampling_restated.py is what the kernels are compared with, bit for
+ * bit).
+ * COMMON.  Every call takes a host cloud (n float4), uploads it into a buffer of this section's own and writes the kept rows, w
+ * carried through, into the pinned staging buffer.  out_xyzw must hold n rows (n_samples for the farthest point sampling) or be
+ * NULL (the count alone); a _view form hands out a view of the staging buffer under the outlier filters' view rule: valid until the
+ * context's next call, NULL for an empty result.  n = 0 is ICPGPU_OK with an empty result; n > INT32_MAX - 4096 is
+ * ICPGPU_ERR_INVALID_ARG.  A row is finite when x, y and z are.  A NON-FINITE ROW IS NEVER KEPT by any of the four, in either mode:
+ * PCL's behaviour for PassThrough and CropBox -- and NOT icpgpu_sac_extract's, whose negative mode returns every row outside the
+ * inliers, non-finite ones included.  One host wait per call (none for an empty result).
+ * PASS THROUGH (field, lo, hi, negative; PCL's defaults: no field, FLT_MIN, FLT_MAX, false).  field 0, 1, 2 = x, y, z; field -1 is
+ * PCL's empty field name: only the non-finite rows are removed and `negative` is ignored.  With v the field's float, a finite row
+ * is removed when (!negative && (v < lo || v > hi)) || (negative && v >= lo && v <= hi): float32 comparisons, both ends inclusive,
+ * as in PCL 1.8's applyFilterIndices.  lo > hi is legal and keeps nothing in positive mode.  A NaN limit or another field is
+ * ICPGPU_ERR_INVALID_ARG; infinite limits are legal.
+ * CROP BOX (min3, max3, T, negative).  q = p without T; with T (16 floats, column-major, as everywhere in this header) q is
+ * xform_point's three fma chains, the arithmetic of icpgpu_transform.  A finite row is outside iff q.a < min.a or q.a > max.a on an
+ * axis -- a NaN q (an infinite entry of T) is therefore INSIDE, as PCL's comparisons make it.  Positive mode keeps the inside rows,
+ * negative mode the outside ones.  A NaN corner is ICPGPU_ERR_INVALID_ARG.  icpgpu_crop_box_matrix (host only) composes what PCL's
+ * CropBox applies in three float steps -- the user transform, the translation, the inverse of the rotation -- into that one matrix:
+ * M = R^-1 * Tr(-translation) * transform with R = Rz(rotation.z) * Ry(rotation.y) * Rx(rotation.x), pcl::getTransformation's order,
+ * R^-1 = R's transpose; (Rz Ry) Rx, Tr * transform and R^-1 * (Tr * transform) are 4 x 4 products in double, each entry added from
+ * the left, and the result is rounded to float32 ONCE.  DEVIATION: PCL rounds after each of its three steps.
+ * UNIFORM SAMPLING (leaf > 0, finite; else ICPGPU_ERR_INVALID_ARG).  inv = 1 / leaf in float32.  The lattice is the voxel filter's
+ * plan (icpgpu_voxel_plan) over the finite rows' box: its min_b and div_b.  The plan's verdict without a finite point gives an empty
+ * result; PCL's "leaf size is too small" verdict and the wrapped cell index are ICPGPU_ERR_UNSUPPORTED -- a stated DEVIATION: PCL's
+ * UniformSampling has no such test and lets the index wrap.  The cell of a finite row is i_a = (int)floorf(p.a * inv), the cell's
+ * centre c_a = ((float)i_a + 0.5f) * leaf, each operation rounded; d = p - c in float32 and d2 = fma(dz, dz, fma(dy, dy, dx * dx)).
+ * Each occupied cell keeps the row with the smallest (d2 bits, index) key -- the search's 64-bit key: ties go to the lowest index.
+ * The output is in ascending index order.  DEVIATIONS: PCL emits in unordered_map order; PCL 1.8's expression, as far as it could be
+ * recalled without its source at hand, subtracts the cell's integer coordinates instead of its centre -- the rule here is the one
+ * PCL's own comment names, "closer to the leaf center".  More than 2^30 rows: ICPGPU_ERR_UNSUPPORTED (the cell table's index).
+ * FARTHEST POINT SAMPLING (n_samples, first_index: setSample and the first point).  m[i] = +inf for every finite row; non-finite
+ * rows take no part.  s_0 = first_index, or the lowest finite row with first_index = -1.  For j = 1 .. n_samples - 1: every
+ * unselected finite i takes m[i] = min(m[i], d2(i, s_(j-1))) with the outlier filters' d2, and s_j is the unselected finite row
+ * with the largest m, ties to the lowest index -- so duplicates of selected points come last, lowest index first.  The output and
+ * the kept indices are in SELECTION order.  n_samples = 0 is ICPGPU_OK and empty; n_samples above the number of finite rows (PCL
+ * throws there), a first_index outside the cloud or one that names a non-finite row is ICPGPU_ERR_INVALID_ARG.  DEVIATIONS: squared
+ * distances instead of distances (the square root can merge two distinct d2 into a tie); the first point is an argument, not
+ * mt19937's draw; n_samples == n is still returned in selection order.  Two kernel shapes compute the same bits: one workgroup that
+ * runs all samples in one launch for n <= ICPGPU_FPS_ONE_WORKGROUP_MAX, one launch per sample over many workgroups above it;
+ * icpgpu_subset_stats says which ran.
+ * OBSERVERS of the LAST call of this section on the context; a refused call leaves nothing to observe (ICPGPU_ERR_INVALID_ARG).
+ * icpgpu_subset_fetch: the kept rows' indices -- ascending for the crops and the uniform sampling, in selection order for the
+ * farthest point sampling -- and one float per kept row: uniform sampling, the row's d2 to its cell's centre; farthest point
+ * sampling, the row's d2 to the already selected set when it was chosen, +inf for the first; the crops, 0.  *n_in and *n_kept are
+ * always set; either output may be NULL, with both NULL the call only reports the sizes; nothing is written when n_kept exceeds
+ * capacity (ICPGPU_ERR_INVALID_ARG).  icpgpu_subset_removed: the complement, ascending (getRemovedIndices), under the same
+ * capacity rule.  icpgpu_subset_stats: kind (ICPGPU_SUBSET_*), the call's host waits and kernel launches, and path
+ * (ICPGPU_FPS_PATH_*; 0 for the other filters) -- a silent fall-back cannot pass as agreement.
+ * ISOLATION.  The calls read nothing but their arguments.  They leave the source, the target, every grid, the
+ * covariances, the normals, the NDT cells, the voxel and outlier filters' results, the search cloud and every unfetched clustering,
+ * segmentation, ground filter, ISS and MLS result as they were; their own result survives all of those calls and is replaced only
+ * by the next call of this section.
+ * Not provided: setKeepOrganized / setUserFilterValue, setIndices, RandomSample, NormalSpaceSampling, CovarianceSampling, and a
+ * crop fused into icpgpu_set_source_voxel_filtered. */
+#define ICPGPU_FPS_ONE_WORKGROUP_MAX 16384
+#define ICPGPU_SUBSET_PASS_THROUGH 1
+#define ICPGPU_SUBSET_CROP_BOX 2
+#define ICPGPU_SUBSET_UNIFORM_SAMPLING 3
+#define ICPGPU_SUBSET_FARTHEST_POINT_SAMPLING 4
+#define ICPGPU_FPS_PATH_ONE 1
+#define ICPGPU_FPS_PATH_MANY 2
+int icpgpu_pass_through(icpgpu_ctx* ctx, const float* xyzw, size_t n, int field, float lo, float hi, int negative, float* out_xyzw,
+                        size_t* n_out);
+int icpgpu_pass_through_view(icpgpu_ctx* ctx, const float* xyzw, size_t n, int field, float lo, float hi, int negative,
+                             const float** view_xyzw, size_t* n_out);
+int icpgpu_crop_box(icpgpu_ctx* ctx, const float* xyzw, size_t n, const float* min3, const float* max3,
+                    const float* T /* 16 floats or NULL */, int negative, float* out_xyzw, size_t* n_out);
+int icpgpu_crop_box_view(icpgpu_ctx* ctx, const float* xyzw, size_t n, const float* min3, const float* max3,
+                         const float* T /* 16 floats or NULL */, int negative, const float** view_xyzw, size_t* n_out);
+int icpgpu_crop_box_matrix(const float* transform16 /* NULL = identity */, const float* translation3, const float* rotation3,
+                           float* out16);
+int icpgpu_uniform_sampling(icpgpu_ctx* ctx, const float* xyzw, size_t n, float leaf, float* out_xyzw, size_t* n_out);
+int icpgpu_uniform_sampling_view(icpgpu_ctx* ctx, const float* xyzw, size_t n, float leaf, const float** view_xyzw, size_t* n_out);
+int icpgpu_farthest_point_sampling(icpgpu_ctx* ctx, const float* xyzw, size_t n, size_t n_samples, int64_t first_index,
+                                   float* out_xyzw, size_t* n_out);
+int icpgpu_farthest_point_sampling_view(icpgpu_ctx* ctx, const float* xyzw, size_t n, size_t n_samples, int64_t first_index,
+                                        const float** view_xyzw, size_t* n_out);
+int icpgpu_subset_fetch(icpgpu_ctx* ctx, size_t capacity, int32_t* kept_index, float* measure, size_t* n_in, size_t* n_kept);
+int icpgpu_subset_removed(icpgpu_ctx* ctx, size_t capacity, int32_t* removed_index, size_t* n_removed);
+int icpgpu_subset_stats(const icpgpu_ctx* ctx, int32_t* kind, int32_t* host_waits, int32_t* launches, int32_t* path);
 
 /* ---- the mapper's target: a one-point-per-voxel map and its "nn cloud"  -------- */
 /* replaces OctreeMapper's pcl::octree::OctreePointCloudSearch map

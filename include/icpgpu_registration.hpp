@@ -768,6 +768,181 @@ class RadiusOutlierRemoval : public OutlierFilterBase<CloudT, RadiusOutlierRemov
   int min_pts_ = 1;
 };
 
+// What pcl::PassThrough, pcl::CropBox, pcl::UniformSampling and pcl::FarthestPointSampling share (the filters that keep a subset of
+// the input rows): the input cloud, filter(output) from the view, filter(indices) -- the kept rows' indices -- and
+// getRemovedIndices().  Rules and deviations: include/icpgpu.h, "cropping and sampling filters".  A refused call leaves the output
+// empty, as PCL's error path does.  Not provided: setKeepOrganized / setUserFilterValue, setIndices.
+template <class CloudT, class Derived>
+class SubsetFilterBase {
+ public:
+  explicit SubsetFilterBase(int device = 0) : ctx_holder_(detail::acquire_context(device)), ctx_(ctx_holder_->ctx) {}
+  template <class CloudPtr>
+  void setInputCloud(const CloudPtr& cloud) { input_ = &*cloud; }
+  // the indices of the rows the last filter() removed, ascending
+  const std::vector<int>& getRemovedIndices() const { return removed_; }
+  void filter(CloudT& output) {
+    typedef typename std::remove_reference<decltype(output.points[0])>::type PointT;
+    static_assert(sizeof(PointT) == 16, "icpgpu: 16-byte points (pcl::PointXYZ)");
+    const float* view = nullptr;
+    const std::size_t m = call(&view);
+    if (m) {
+      const PointT* first = reinterpret_cast<const PointT*>(view);
+      output.points.assign(first, first + m);
+    } else {
+      output.points.resize(0);
+    }
+    detail::set_cloud_shape(output, output.points.size(), 0);
+    observe(nullptr);
+  }
+  // the kept rows' indices: ascending, or in selection order for FarthestPointSampling
+  void filter(std::vector<int>& indices) {
+    const float* view = nullptr;
+    call(&view);
+    observe(&indices);
+  }
+
+ protected:
+  std::size_t call(const float** view) {
+    removed_.clear();
+    ok_ = false;
+    if (!input_) return 0;
+    const std::size_t n = input_->points.size();
+    std::size_t m = 0;
+    ok_ = static_cast<Derived*>(this)->run(ctx_, n ? reinterpret_cast<const float*>(&input_->points[0]) : nullptr, n, view, &m) == ICPGPU_OK;
+    return ok_ ? m : 0;
+  }
+  void observe(std::vector<int>* indices) {
+    if (indices) indices->clear();
+    if (!ok_) return;
+    std::size_t n_in = 0, n_kept = 0, n_removed = 0;
+    if (icpgpu_subset_fetch(ctx_, 0, nullptr, nullptr, &n_in, &n_kept) != ICPGPU_OK) return;
+    static_assert(sizeof(int) == sizeof(int32_t), "icpgpu: 32-bit int");
+    if (indices && n_kept) {
+      indices->resize(n_kept);
+      if (icpgpu_subset_fetch(ctx_, n_kept, reinterpret_cast<int32_t*>(&(*indices)[0]), nullptr, &n_in, &n_kept) != ICPGPU_OK) indices->clear();
+    }
+    removed_.resize(n_in - n_kept);
+    if (!removed_.empty() && icpgpu_subset_removed(ctx_, removed_.size(), reinterpret_cast<int32_t*>(&removed_[0]), &n_removed) != ICPGPU_OK)
+      removed_.clear();
+  }
+  detail::ContextPtr ctx_holder_;
+  icpgpu_ctx* ctx_;
+  const CloudT* input_ = nullptr;
+  bool ok_ = false;
+  std::vector<int> removed_;
+};
+
+//   pcl::PassThrough<pcl::PointXYZ> pass;  ->  icpgpu::PassThrough<pcl::PointCloud<pcl::PointXYZ>> pass;
+//   pass.setInputCloud(in); pass.setFilterFieldName("z"); pass.setFilterLimits(-1.5, 3.0); pass.filter(out);
+template <class CloudT>
+class PassThrough : public SubsetFilterBase<CloudT, PassThrough<CloudT>> {
+ public:
+  explicit PassThrough(int device = 0) : SubsetFilterBase<CloudT, PassThrough<CloudT>>(device) {}
+  void setFilterFieldName(const std::string& name) {
+    if (name != "x" && name != "y" && name != "z") throw std::invalid_argument("icpgpu::PassThrough: the field is one of x, y, z");
+    field_ = name[0] - 'x';
+  }
+  std::string getFilterFieldName() const { return field_ < 0 ? std::string() : std::string(1, (char)('x' + field_)); }
+  void setFilterLimits(float lo, float hi) { lo_ = lo, hi_ = hi; }
+  void getFilterLimits(float& lo, float& hi) const { lo = lo_, hi = hi_; }
+  void setNegative(bool negative) { negative_ = negative; }
+  bool getNegative() const { return negative_; }
+  int run(icpgpu_ctx* ctx, const float* xyzw, std::size_t n, const float** view, std::size_t* m) {
+    return icpgpu_pass_through_view(ctx, xyzw, n, field_, lo_, hi_, negative_ ? 1 : 0, view, m);
+  }
+
+ private:
+  int field_ = -1;  // (PCL's constructor defaults: no field, FLT_MIN .. FLT_MAX)
+  float lo_ = std::numeric_limits<float>::min(), hi_ = std::numeric_limits<float>::max();
+  bool negative_ = false;
+};
+
+//   pcl::CropBox<pcl::PointXYZ> crop;  ->  icpgpu::CropBox<pcl::PointCloud<pcl::PointXYZ>> crop;
+//   crop.setInputCloud(in); crop.setMin(Eigen::Vector4f(...)); crop.setMax(...); crop.setNegative(true); crop.filter(out);
+// setMin / setMax / setTranslation / setRotation read v[0], v[1], v[2]; setTransform reads t(r, c) for r, c < 4 (Eigen::Affine3f,
+// Eigen::Matrix4f).  The three poses are composed into one matrix by icpgpu_crop_box_matrix.
+template <class CloudT>
+class CropBox : public SubsetFilterBase<CloudT, CropBox<CloudT>> {
+ public:
+  explicit CropBox(int device = 0) : SubsetFilterBase<CloudT, CropBox<CloudT>>(device) {}
+  template <class Vec>
+  void setMin(const Vec& v) { for (int a = 0; a < 3; ++a) min_[a] = (float)v[a]; }
+  template <class Vec>
+  void setMax(const Vec& v) { for (int a = 0; a < 3; ++a) max_[a] = (float)v[a]; }
+  template <class Vec>
+  void setTranslation(const Vec& v) { for (int a = 0; a < 3; ++a) translation_[a] = (float)v[a]; posed_ = true; }
+  template <class Vec>
+  void setRotation(const Vec& v) { for (int a = 0; a < 3; ++a) rotation_[a] = (float)v[a]; posed_ = true; }
+  template <class TransformT>
+  void setTransform(const TransformT& t) {
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) transform_[4 * c + r] = (float)t(r, c);
+    posed_ = true;
+  }
+  void setNegative(bool negative) { negative_ = negative; }
+  bool getNegative() const { return negative_; }
+  int run(icpgpu_ctx* ctx, const float* xyzw, std::size_t n, const float** view, std::size_t* m) {
+    float T[16];
+    if (posed_ && icpgpu_crop_box_matrix(transform_, translation_, rotation_, T) != ICPGPU_OK) return ICPGPU_ERR_INVALID_ARG;
+    return icpgpu_crop_box_view(ctx, xyzw, n, min_, max_, posed_ ? T : nullptr, negative_ ? 1 : 0, view, m);
+  }
+
+ private:
+  float min_[3] = {-1.f, -1.f, -1.f}, max_[3] = {1.f, 1.f, 1.f};  // (PCL's constructor defaults)
+  float translation_[3] = {0.f, 0.f, 0.f}, rotation_[3] = {0.f, 0.f, 0.f};
+  float transform_[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  bool posed_ = false, negative_ = false;
+};
+
+//   pcl::UniformSampling<pcl::PointXYZ> us;  ->  icpgpu::UniformSampling<pcl::PointCloud<pcl::PointXYZ>> us;
+//   us.setInputCloud(in); us.setRadiusSearch(0.5); us.filter(keypoints);      (filter(indices): the rows to compute descriptors at)
+template <class CloudT>
+class UniformSampling : public SubsetFilterBase<CloudT, UniformSampling<CloudT>> {
+ public:
+  explicit UniformSampling(int device = 0) : SubsetFilterBase<CloudT, UniformSampling<CloudT>>(device) {}
+  void setRadiusSearch(double radius) { leaf_ = (float)radius; }
+  double getRadiusSearch() const { return leaf_; }
+  int run(icpgpu_ctx* ctx, const float* xyzw, std::size_t n, const float** view, std::size_t* m) {
+    return icpgpu_uniform_sampling_view(ctx, xyzw, n, leaf_, view, m);
+  }
+
+ private:
+  float leaf_ = 0.f;
+};
+
+//   pcl::FarthestPointSampling<pcl::PointXYZ> fps;  ->  icpgpu::FarthestPointSampling<pcl::PointCloud<pcl::PointXYZ>> fps;
+//   fps.setInputCloud(in); fps.setSample(1024); fps.setSeed(7); fps.filter(out);
+// The first row is the plane segmentation's generator (hypothesis 0, sample 0) over the cloud's rows, advanced cyclically to the
+// next finite row -- not mt19937's draw; the rows come in selection order.
+template <class CloudT>
+class FarthestPointSampling : public SubsetFilterBase<CloudT, FarthestPointSampling<CloudT>> {
+ public:
+  explicit FarthestPointSampling(int device = 0) : SubsetFilterBase<CloudT, FarthestPointSampling<CloudT>>(device) {}
+  void setSample(std::size_t sample) { sample_ = sample; }
+  std::size_t getSample() const { return sample_; }
+  void setSeed(unsigned int seed) { seed_ = seed; }
+  unsigned int getSeed() const { return seed_; }
+  int run(icpgpu_ctx* ctx, const float* xyzw, std::size_t n, const float** view, std::size_t* m) {
+    int64_t first = -1;
+    if (n) {
+      unsigned long long z = (unsigned long long)seed_ + 0x9E3779B97F4A7C15ull;  // splitmix64 of the rule's counter 3 t + c + 1 = 1
+      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+      z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+      z ^= z >> 31;
+      const std::size_t start = (std::size_t)(((z >> 32) * (unsigned long long)n) >> 32);
+      for (std::size_t step = 0; step < n && first < 0; ++step) {
+        const float* p = xyzw + 4 * ((start + step) % n);
+        if (std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2])) first = (int64_t)((start + step) % n);
+      }
+    }
+    return icpgpu_farthest_point_sampling_view(ctx, xyzw, n, sample_, first, view, m);
+  }
+
+ private:
+  std::size_t sample_ = 0;
+  unsigned int seed_ = 0;
+};
+
 // pcl::search::KdTree<PointT> / pcl::KdTreeFLANN<PointT>-shaped front end of the neighbour search (rules and deviations:
 // include/icpgpu.h, "neighbour search": exact, results ascending by (squared distance, index)):
 //   pcl::search::KdTree<pcl::PointXYZ> tree;  ->  icpgpu::search::KdTree<pcl::PointCloud<pcl::PointXYZ>> tree;
